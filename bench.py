@@ -17,20 +17,33 @@ MASTER_*).  A plain `python bench.py --gpus N` with N > 1 starts the N ranks its
 GPUs and talk over gloo instead of RCCL; the line then says "oversubscribed": true and is a functional
 check of the N > 1 path, not a scaling number.
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both
-sides and reduced with max over ranks; blocks are repeated until at least --min-time seconds have been
-timed (a 20-step block of the headline workload is 7 ms) and the MEDIAN block is reported (`ms_per_step`, `value`;
-round 2 reported the fastest block, which is still listed as `fastest_block_ms_per_step`); every block is under
-`blocks_ms_per_step`.
+Timing: warm-up (W steps, then steps for at least --warmup-time seconds), then ONE block of exactly K timed steps,
+bracketed by barrier + synchronize on both sides and reduced with max over ranks: `ms_per_step` = that block / K,
+`value` = voxels of all ranks / ms_per_step.  (MinkUNet: the training state after the first step is restored after
+the warm-up, so that the timed steps compute the same thing whatever the warm-up's length.)
+
+A plain run does only that: set-up (scene, layer, first forward + backward), warm-up, the K timed steps, the
+outputs (--dump-outputs DIR) and the JSON line (`roofline`, `cpu_baseline` null).  --full adds, after the
+timed steps, everything else the benchmark measures:
+  * repeated K-step blocks until --min-time seconds, the per-launch HIP events of the hot kernels recorded in
+    every --timer-blocks-th block: `timing.blocks_ms_per_step` (median / fastest block), `kernels`, `roofline`
+    (dominant kernel, HIP-event timed on the launch stream);
+  * the warm coordinate-insert / kernel-map / plan build (`cold`), the exchange priced at N > 1 (`multi_gpu`),
+    the hipGraph replay and rocm-smi sample of the MinkUNet step;
+  * `cpu_baseline`: the reference's own CPU operators (oracle/_ref) on the host cores at N = 1, bounded sample;
+  * `workloads`: the other BASELINE configurations, compact (default headline only, --extra-workloads);
+  * in-run rocprofv3 --pmc passes over child processes (`roofline.traffic`, `mfma_busy_frac`; --pmc).
+
+--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy (float32; coordinates float64), rows in
+coordinate order, 64 MB at most (a fixed, seeded sample of rows when the outputs are larger).  The inputs are
+seeded: the same arguments give the same inputs on every run.
 
 Other workloads (never the default; parity-test configurations timed for DESIGN.md):
     --workload conv4d     BASELINE configs[4]: 4-D k = 3 (K = 81), 400k voxels in 100^3 x 8 frames, 32 -> 64
     --workload minkunet   BASELINE configs[2]/[3]: MinkUNet34C forward + loss + backward + SGD step on the
                           200k-voxel plane-union scene of SURVEY 8(d); one scene per rank, DDP
 
-Rank 0 prints ONE JSON line carrying `roofline` (dominant kernel, HIP-event timed inside the timed region
-on the launch stream) and `cpu_baseline` (the reference's own CPU operators, oracle/_ref, timed on this
-box's host cores at N = 1 on a bounded sample).
+Rank 0 prints ONE JSON line, the last line of stdout.
 """
 import argparse
 import json
@@ -702,6 +715,98 @@ def run_timed(step, args, dist_utils, MEB, dev, timers_in_blocks=True):
     return median, blocks, timer, args.steps * (n_timed_blocks if timers_in_blocks else 1)
 
 
+def run_steps(step, args, dist_utils, dev, reset=None):
+    """The headline measurement: warm-up (W steps, then more steps for at least --warmup-time seconds: the W steps may be
+    spent on one-time costs — lazy code-object loads, first allocations — and the timed block needs a device that has
+    been running steps), then ONE block of exactly K steps — barrier + synchronize | K steps |
+    synchronize + barrier — with no per-launch events in it -> seconds of the K steps (max over ranks).
+    reset(): called after the warm-up, so that the timed steps start from the same state whatever the warm-up's length."""
+    n_warm = 0
+    for _ in range(args.warmup):
+        step()
+        n_warm += 1
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    n_timed_warm = 0
+    while True:
+        # every rank takes the same decision (a step may hold a collective): time left and chunk are maxima over ranks
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        left = dist_utils.max_over_ranks(args.warmup_time - el, dev)
+        if left <= 0:
+            break
+        chunk = max(1, min(10000, int(left / (el / n_timed_warm)) if n_timed_warm and el > 0 else 1))
+        for _ in range(int(dist_utils.max_over_ranks(float(chunk), dev))):
+            step()
+            n_warm += 1
+            n_timed_warm += 1
+    n_warm = int(dist_utils.max_over_ranks(float(n_warm), dev))
+    LAST_RUN["warmup_steps"] = n_warm
+    if reset is not None:
+        reset()
+    dist_utils.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    torch.cuda.synchronize()
+    own = time.perf_counter() - t0
+    dist_utils.barrier()
+    elapsed = dist_utils.max_over_ranks(time.perf_counter() - t0, dev)
+    LAST_RUN["per_rank_ms_per_step"] = [round(v / args.steps * 1e3, 4) for v in dist_utils.gather_over_ranks(own, dev)]
+    return elapsed
+
+
+def headline_timing(args, best, blocks=None, event_blocks=None):
+    """`timing` of the line: the K timed steps, and under --full the repeated blocks measured after them"""
+    t = {"timed_steps": args.steps, "timed_region_s": round(best, 6), "warmup_steps": LAST_RUN.get("warmup_steps"),
+         "reported": "ms_per_step = one block of exactly --steps steps after the warm-up (max over ranks), no per-launch "
+                     "events in it"}
+    if blocks:
+        t.update({"blocks": len(blocks), "steps_per_block": args.steps,
+                  "blocks_ms_per_step": [round(b / args.steps * 1e3, 4) for b in blocks],
+                  "median_block_ms_per_step": round(sorted(blocks)[(len(blocks) - 1) // 2] / args.steps * 1e3, 4),
+                  "fastest_block_ms_per_step": round(min(blocks) / args.steps * 1e3, 4),
+                  "kernel_events": event_blocks,
+                  "blocks_reported": "--full: K-step blocks repeated after the timed steps until --min-time (max over "
+                                     "ranks inside each block); the per-launch HIP events behind `roofline` / `kernels`"})
+    return t
+
+
+DUMP_BYTES = 60 * 1000 * 1000      # --dump-outputs: array bytes written, at most (64 MB with margin)
+
+
+def dump_outputs(out_dir, per_row, whole):
+    """--dump-outputs: write the arrays a caller of the timed path received in its last step as out_dir/<name>.npy.
+    per_row: {name: (rows, coordinates of the rows)} of ONE coordinate set (each in its own row order); whole: {name:
+    array}.  Rows are put in coordinate order (the row order of a coordinate map is the library's own business) and
+    written with `coords`; when the whole would pass DUMP_BYTES, the same fixed, seeded sample of rows is kept for every
+    per-row array.  float32 (coordinates float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    whole = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float32)) for k, v in whole.items()}
+    per_row = {k: (np.asarray(v, dtype=np.float32), np.asarray(c)) for k, (v, c) in per_row.items()}
+    out = dict(whole)
+    if per_row:
+        n = {v.shape[0] for v, _ in per_row.values()} | {c.shape[0] for _, c in per_row.values()}
+        assert len(n) == 1, f"per-row outputs of different lengths: {n}"
+        n = n.pop()
+        c0 = next(iter(per_row.values()))[1]
+        row_bytes = 8 * c0.shape[1] + sum(v[0].nbytes for v, _ in per_row.values())
+        m = min(n, max(1, (DUMP_BYTES - sum(v.nbytes for v in whole.values())) // row_bytes))
+        keep = np.arange(n) if m == n else np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+        for k, (v, c) in per_row.items():
+            order = np.lexsort(c.T[::-1])[keep]        # coordinate order (batch index first), then the sample
+            if "coords" not in out:
+                out["coords"] = c[order].astype(np.float64)
+            else:
+                assert np.array_equal(out["coords"], c[order]), f"{k}: another coordinate set than the other outputs"
+            out[k] = np.ascontiguousarray(v[order])
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in out.items()}
+
+
 def roofline_entry(kernel, flops, compulsory_bytes, avg_ms, bf16, traffic, traffic_src, split=False):
     """the roof is chosen by the launch's arithmetic intensity on its COMPULSORY bytes.
     split: an fp32 workload computed by k_conv_tile_f32x3 — `peak` / `frac` are those of the pipe the kernel issues to
@@ -784,6 +889,7 @@ def bench_conv(args, ME, MEB, dist_utils, rank, world, dev, startup):
         n_pairs = mgr_._kernel_map(x.coordinate_map_key, y.coordinate_map_key, [3] * D, [1] * D, [1] * D,
                                    ME.RegionType.HYPER_CUBE, None, False, False).n_pairs
     grad_seed = torch.ones_like(y.F)
+    last = {}
 
     def step(zero=True, sync=True):
         if zero:
@@ -791,18 +897,31 @@ def bench_conv(args, ME, MEB, dist_utils, rank, world, dev, startup):
         x.F.grad = None
         out = net(x)
         ex.backward(lambda: out.F.backward(grad_seed), sync)
+        # (detached: holding the step's autograd graph would keep its AccumulateGrad nodes alive into the next step)
+        last["F"], last["at"] = out.F.detach(), (out.coordinate_manager, out.coordinate_map_key)
 
     if getattr(args, "pmc_child_mode", False):     # profiled child (measure_traffic): the steps and nothing else
         for _ in range(args.steps):
             step()
         torch.cuda.synchronize()
         return None
-    best, blocks, timer, timed_steps = run_timed(step, args, dist_utils, MEB, dev)
+    best = run_steps(step, args, dist_utils, dev)
     per_rank = LAST_RUN.get("per_rank_ms_per_step")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the caller of the layer holds after the last timed step: output features, input and weight gradients
+        mgr, key = last["at"]
+        dumped = dump_outputs(args.dump_outputs,
+                              {"out_features": (last["F"].float().cpu().numpy(), mgr.get_coordinates(key).cpu().numpy()),
+                               "grad_in_features": (x.F.grad.float().cpu().numpy(), x.C.cpu().numpy())},
+                              {"grad_kernel": conv.kernel.grad.float().cpu().numpy()})
     total_points = dist_utils.sum_over_ranks(n, dev)
     pairs_all = dist_utils.sum_over_ranks(n_pairs, dev)
+    blocks = None
+    if args.full:
+        _, blocks, timer, timed_steps = run_timed(step, args, dist_utils, MEB, dev)
     multi = None
-    if dist_utils.exchange_active():
+    if args.full and dist_utils.exchange_active():
         # What the one-layer headline hides nothing behind: its 0.88 MB all-reduce starts when the ONLY layer's backward
         # is done.  Beside the synchronous step: the same step without the exchange (DDP.no_sync), the exchange on its
         # own, and a gradient-accumulation window (A - 1 micro-steps under no_sync, the A-th reduces) — the loop a
@@ -840,31 +959,11 @@ def bench_conv(args, ME, MEB, dist_utils, rank, world, dev, startup):
                      note="parallel_efficiency = step time without the gradient exchange (DDP.no_sync, max over ranks) / "
                           "step time with it, on THIS world size — the share of the step that is not exposed exchange; "
                           "the 1 -> N scaling efficiency is the driver's to compute from the per-N values")
-    cold = cold_path(ME, MEB, feats, coords.to(dev), dev, n, D, K, cin, cout, args.dtype == "bf16") if rank == 0 else None
+    cold = cold_path(ME, MEB, feats, coords.to(dev), dev, n, D, K, cin, cout, args.dtype == "bf16") \
+        if (rank == 0 and args.full) else None
     if rank != 0:
         return None
-    kernels = kernel_table(timer, timed_steps)
-    flops_per_launch = 2.0 * n_pairs * cin * cout     # each of forward / dgrad / wgrad
-    nc = 32 if 0 < cout % 64 <= 32 else 64                     # conv_variant() of csrc/conv.hip
-    kc = 64 if cin % 64 == 0 else 32 if cin % 32 == 0 else 16
     bf16 = args.dtype == "bf16"
-    if bf16:
-        # conv_variant_bf16() of csrc/conv_bf16.hip
-        kc = 128 if cin % 128 == 0 else 96 if cin % 96 == 0 else 32 if cin <= 32 else 64 if cin <= 64 else 128
-    from minkowskiengine_amd import _lib
-    split = (not bf16) and MEB._use_split(_lib.load(), cin, cout)   # (same policy in csrc_host/manager.cpp use_split)
-    if split:
-        # conv_variant_f32x3() of csrc/conv_f32x3.hip: fp32 operands split exactly into three bf16 terms, six bf16 MFMAs
-        nc = 128 if cout % 128 == 0 else 96 if cout % 96 == 0 else 32 if cout <= 32 else 64
-        kc = 128 if cin % 128 == 0 and nc <= 64 else 64 if cin % 64 == 0 else 96 if cin % 96 == 0 else \
-            32 if cin <= 32 else 64
-    # (64- and 128-column slabs of the split kernel run its wave-specialised instantiation)
-    kname = "k_conv_tile_bf16" if bf16 else ("k_conv_tile_f32x3_ws" if nc in (64, 128) else "k_conv_tile_f32x3") \
-        if split else "k_conv_tile_f32"
-    esz = 2 if bf16 else 4
-    compulsory = esz * (n * cin + n * cout + K * cin * cout) + 8 * n_pairs   # SURVEY 8d, forward
-    traffic, traffic_src = pmc_traffic("k_conv_tile_bf16_forward" if bf16 else kname, n, extent, cin,
-                                       cout) if D == 3 else (None, None)
     ms_step = best / args.steps * 1e3
     line = {
         "metric": f"MinkowskiConvolution fwd+bwd Mpoints/sec ({n // 1000}k-pt {D}D, k=3)",
@@ -883,16 +982,9 @@ def bench_conv(args, ME, MEB, dist_utils, rank, world, dev, startup):
                    "imbalance": bool(args.imbalance and world > 1),
                    "oversubscribed": world > max(1, dist_utils.visible_gpus())},
         "multi_gpu": multi,
-        "timing": {"blocks": len(blocks), "steps_per_block": args.steps,
-                   "blocks_ms_per_step": [round(b / args.steps * 1e3, 4) for b in blocks],
-                   "timed_region_s": round(sum(blocks), 4),
-                   "fastest_block_ms_per_step": round(min(blocks) / args.steps * 1e3, 4),
-                   "kernel_events": LAST_RUN.get("event_blocks"),
-                   "reported": "median block (max over ranks inside each block); the per-launch HIP events behind "
-                               "`roofline` / `kernels` are recorded in every --timer-blocks-th block of the timed region"},
-        "roofline": roofline_entry(f"{kname}<{nc},{kc}> (forward)", flops_per_launch,
-                                   compulsory, kernels["conv_forward"]["avg_ms"], bf16, traffic, traffic_src, split),
-        "kernels": kernels,
+        "timing": headline_timing(args, best, blocks, LAST_RUN.get("event_blocks") if blocks else None),
+        "roofline": None,
+        "cpu_baseline": None,
         "cold_ms": round(cold_ms, 2),
         "cold_breakdown_ms": {"process_startup_to_first_launch": startup,
                               "sparse_tensor_insert": round((t1 - t0) * 1e3, 2),
@@ -902,9 +994,36 @@ def bench_conv(args, ME, MEB, dist_utils, rank, world, dev, startup):
                                       "use of the library; it contains the one-time load of the code object's kernels "
                                       "(hipModule lazy loading, reported under process_startup_to_first_launch."
                                       "first_kernel_ms for one trivial kernel), the allocator's first hipMallocs and the "
-                                      "host synchronisations of the build; the warm build is under `cold`"},
-        "cold": cold,
+                                      "host synchronisations of the build; the warm build is under `cold` (--full)"},
+        "dumped_outputs": dumped,
     }
+    if not args.full:
+        return line
+    kernels = kernel_table(timer, timed_steps)
+    flops_per_launch = 2.0 * n_pairs * cin * cout     # each of forward / dgrad / wgrad
+    nc = 32 if 0 < cout % 64 <= 32 else 64                     # conv_variant() of csrc/conv.hip
+    kc = 64 if cin % 64 == 0 else 32 if cin % 32 == 0 else 16
+    if bf16:
+        # conv_variant_bf16() of csrc/conv_bf16.hip
+        kc = 128 if cin % 128 == 0 else 96 if cin % 96 == 0 else 32 if cin <= 32 else 64 if cin <= 64 else 128
+    from minkowskiengine_amd import _lib
+    split = (not bf16) and MEB._use_split(_lib.load(), cin, cout)   # (same policy in csrc_host/manager.cpp use_split)
+    if split:
+        # conv_variant_f32x3() of csrc/conv_f32x3.hip: fp32 operands split exactly into three bf16 terms, six bf16 MFMAs
+        nc = 128 if cout % 128 == 0 else 96 if cout % 96 == 0 else 32 if cout <= 32 else 64
+        kc = 128 if cin % 128 == 0 and nc <= 64 else 64 if cin % 64 == 0 else 96 if cin % 96 == 0 else \
+            32 if cin <= 32 else 64
+    # (64- and 128-column slabs of the split kernel run its wave-specialised instantiation)
+    kname = "k_conv_tile_bf16" if bf16 else ("k_conv_tile_f32x3_ws" if nc in (64, 128) else "k_conv_tile_f32x3") \
+        if split else "k_conv_tile_f32"
+    esz = 2 if bf16 else 4
+    compulsory = esz * (n * cin + n * cout + K * cin * cout) + 8 * n_pairs   # SURVEY 8d, forward
+    traffic, traffic_src = pmc_traffic("k_conv_tile_bf16_forward" if bf16 else kname, n, extent, cin,
+                                       cout) if D == 3 else (None, None)
+    line["roofline"] = roofline_entry(f"{kname}<{nc},{kc}> (forward)", flops_per_launch,
+                                      compulsory, kernels["conv_forward"]["avg_ms"], bf16, traffic, traffic_src, split)
+    line["kernels"] = kernels
+    line["cold"] = cold
     # compulsory HBM bytes of each pass (every tensor touched once, the pair lists read once): forward = X + Y +
     # W + 8P; input gradient = dY + dX + W + 8P; weight gradient = X + dY + dW + 8P (its reduce: the partial images are
     # not compulsory — dW once)
@@ -917,8 +1036,6 @@ def bench_conv(args, ME, MEB, dist_utils, rank, world, dev, startup):
         w_cpu = conv.kernel.detach().float().cpu()
         line["cpu_baseline"] = cpu_baseline_both(lambda b: cpu_baseline(coords, feats, w_cpu, b), args.cpu_budget)
         line["speedup_vs_cpu_baseline"] = round(line["value"] / line["cpu_baseline"]["value"], 1)
-    else:
-        line["cpu_baseline"] = None
     return line
 
 
@@ -949,7 +1066,7 @@ def bench_minkunet(args, ME, MEB, dist_utils, rank, world, dev, startup):
 
     # layer census for the CPU baseline, recorded by forward hooks during the first step
     specs, hooks = [], []
-    if rank == 0 and world == 1 and args.cpu_budget > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_budget > 0:
         def record(mod, inp, out):
             kg = mod.kernel_generator
             specs.append((bool(mod.is_transpose), list(kg.kernel_size), list(kg.kernel_stride), mod.in_channels,
@@ -974,6 +1091,8 @@ def bench_minkunet(args, ME, MEB, dist_utils, rank, world, dev, startup):
         loader = ME.utils.ScenePrefetcher(scenes_forever(), depth=args.loader_depth)
         pending[0] = iter(loader)
 
+    last = {}
+
     def step(sync=True):
         ex.zero_grad()
         if args.scenes == "cached":
@@ -984,9 +1103,13 @@ def bench_minkunet(args, ME, MEB, dist_utils, rank, world, dev, startup):
             xin = next(pending[0])
             if os.environ.get("ME_BENCH_DISCARD_LOADED") == "1":   # (interference experiment: the loader runs, the step
                 xin = x                                            # trains on the cached scene)
-        loss = crit(net(xin).F.float(), labels)   # mean cross-entropy over the voxels
+        out = net(xin)
+        loss = crit(out.F.float(), labels)   # mean cross-entropy over the voxels
         ex.backward(loss.backward, sync)
         opt.step()
+        # (detached: holding the step's autograd graph would keep its AccumulateGrad nodes alive into the next step — and
+        # into a hipGraph capture on a side stream)
+        last["F"], last["loss"], last["at"] = out.F.detach(), loss.detach(), (out.coordinate_manager, out.coordinate_map_key)
 
     if getattr(args, "pmc_child_mode", False):     # profiled child (measure_traffic): exactly `steps` steps
         for _ in range(args.steps):
@@ -1005,13 +1128,45 @@ def bench_minkunet(args, ME, MEB, dist_utils, rank, world, dev, startup):
         raise SystemExit("--graph needs --scenes cached (a captured step replays fixed shapes and addresses)")
     if args.graph:
         step, graphed = capture_step(step), True
-    # (per-launch HIP events — ~130 event pairs per step — stay out of the timed blocks: the kernel table comes from ONE
-    # extra, untimed block, so that `ms_per_step` is the step a training loop would see)
-    best, blocks, timer, timed_steps = run_timed(step, args, dist_utils, MEB, dev, timers_in_blocks=False)
+    # the training state after the first step (parameters, momentum, batch-norm statistics), put back in place after the
+    # warm-up: the timed steps start from it however many warm-up steps ran (a captured graph keeps its addresses)
+    state = [t for t in model.state_dict().values() if torch.is_tensor(t)] + \
+        [t for s in opt.state.values() for t in s.values() if torch.is_tensor(t)]
+    saved = [t.detach().clone() for t in state]
+
+    def reset():
+        with torch.no_grad():
+            for t, s in zip(state, saved):
+                t.copy_(s)
+
+    best = run_steps(step, args, dist_utils, dev, reset)
+    del saved
     per_rank = LAST_RUN.get("per_rank_ms_per_step")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a training loop holds after the last timed step: the logits and the loss of that step, and (a fixed,
+        # seeded sample of) the parameters the step's SGD update left and the gradients it applied
+        import numpy as np
+        params = [p for p in model.parameters()]
+        flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+        pick = torch.from_numpy(np.sort(np.random.default_rng(0).choice(flat.numel(), min(flat.numel(), 1 << 20),
+                                                                         replace=False))).to(dev)
+        grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                           for p in params])
+        mgr, key = last["at"]
+        dumped = dump_outputs(args.dump_outputs,
+                              {"logits": (last["F"].float().cpu().numpy(), mgr.get_coordinates(key).cpu().numpy())},
+                              {"loss": last["loss"].float().reshape(1).cpu().numpy(),
+                               "params_sample": flat[pick].cpu().numpy(), "grads_sample": grads[pick].cpu().numpy()})
+        del flat, grads
     total_points = dist_utils.sum_over_ranks(n, dev)
+    blocks = None
+    if args.full:
+        # (per-launch HIP events — ~130 event pairs per step — stay out of the timed blocks: the kernel table comes from
+        # ONE extra, untimed block, so that the block times are the step a training loop would see)
+        _, blocks, timer, timed_steps = run_timed(step, args, dist_utils, MEB, dev, timers_in_blocks=False)
     multi = None
-    if dist_utils.exchange_active():
+    if args.full and dist_utils.exchange_active():
         # BASELINE configs[3]: what the exchange costs THIS step — the step without it (DDP.no_sync: same kernels, no
         # collectives), the 151 MB of gradients all-reduced on their own, and the difference the bucketed overlap leaves
         def step_nosync():
@@ -1037,7 +1192,8 @@ def bench_minkunet(args, ME, MEB, dist_utils, rank, world, dev, startup):
     # the same step replayed from a hipGraph (maps cached: fixed shapes and addresses) — the GPU time of the step with
     # the host out of the way; reported beside the eager figure, never instead of it
     graph_ms, graph_blocks = None, []
-    if args.scenes == "cached" and not graphed and world == 1 and not args.no_graph_probe and not dist_utils.exchange_active():
+    if args.full and args.scenes == "cached" and not graphed and world == 1 and not args.no_graph_probe and \
+            not dist_utils.exchange_active():
         try:
             replay = capture_step(step)
             for _ in range(2):
@@ -1055,13 +1211,7 @@ def bench_minkunet(args, ME, MEB, dist_utils, rank, world, dev, startup):
             graph_ms = f"capture failed: {type(e).__name__}: {e}"
     if rank != 0:
         return None
-    kernels = kernel_table(timer, timed_steps)
-    tot_ms = sum(k["ms_per_step"] for k in kernels.values())
-    tot_flops = sum(f for _, _, f in timer.totals().values()) / max(timed_steps, 1)
-    peak = PEAK_BF16_MATRIX_TFLOPS if bf16 else PEAK_F32_MATRIX_TFLOPS
     ms_step = best / args.steps * 1e3
-    achieved = round(tot_flops / (tot_ms * 1e-3) / 1e12, 2) if tot_ms > 0 else None
-    whole = round(1567e9 / (ms_step * 1e-3) / 1e12, 2)
     line = {
         "metric": "MinkUNet34C fwd+bwd+SGD Mpoints/sec (200k-pt synthetic scene)",
         "value": round(total_points / (best / args.steps) / 1e6, 3),
@@ -1093,12 +1243,22 @@ def bench_minkunet(args, ME, MEB, dist_utils, rank, world, dev, startup):
                    "imbalance": bool(args.imbalance and world > 1),
                    "oversubscribed": world > max(1, dist_utils.visible_gpus())},
         "multi_gpu": multi,
-        "timing": {"blocks": len(blocks), "steps_per_block": args.steps,
-                   "blocks_ms_per_step": [round(b / args.steps * 1e3, 3) for b in blocks],
-                   "timed_region_s": round(sum(blocks), 4),
-                   "fastest_block_ms_per_step": round(min(blocks) / args.steps * 1e3, 3),
-                   "reported": "median block (max over ranks inside each block); per-kernel HIP events recorded in one "
-                               "extra block outside the timed region"},
+        "timing": headline_timing(args, best, blocks),
+        "roofline": None,
+        "cpu_baseline": None,
+        "cold_ms": round(cold_ms, 2),
+        "dumped_outputs": dumped,
+    }
+    if not args.full:
+        return line
+    kernels = kernel_table(timer, timed_steps)
+    tot_ms = sum(k["ms_per_step"] for k in kernels.values())
+    tot_flops = sum(f for _, _, f in timer.totals().values()) / max(timed_steps, 1)
+    peak = PEAK_BF16_MATRIX_TFLOPS if bf16 else PEAK_F32_MATRIX_TFLOPS
+    achieved = round(tot_flops / (tot_ms * 1e-3) / 1e12, 2) if tot_ms > 0 else None
+    whole = round(1567e9 / (ms_step * 1e-3) / 1e12, 2)
+    line["timing"]["kernel_events"] = "per-kernel HIP events recorded in one extra block outside the timed blocks"
+    line.update({
         "roofline": {"bound": "mfma", "kernel": "all convolution launches of a step (k_conv_tile_* / k_conv_halo / k_conv_stem forward + dgrad, "
                                                 "k_wgrad_*); HIP-event timed" + (" in a separate eager pass: the timed "
                                                 "region replays a hipGraph" if graphed else ""),
@@ -1111,12 +1271,8 @@ def bench_minkunet(args, ME, MEB, dist_utils, rank, world, dev, startup):
                                      "budget allows (--pmc)",
                      "flops_per_step": tot_flops, "conv_kernel_ms_per_step": round(tot_ms, 3)},
         "kernels": kernels,
-        "cold_ms": round(cold_ms, 2),
-        # every timed block (eager): the spread says how much a fresh lease's clock ramp moves the number
-        "timing": {"blocks_ms_per_step": [round(b / args.steps * 1e3, 3) for b in blocks],
-                   "median_ms_per_step": round(ms_step, 3), "min_ms_per_step": round(min(blocks) / args.steps * 1e3, 3)},
         "gpu_state": gpu_state_under_load(step) if (world == 1 and not args.no_gpu_state) else None,
-    }
+    })
     if graph_ms is not None:
         line["hip_graph"] = ({"ms_per_step": round(graph_ms, 3), "value": round(n / (graph_ms * 1e-3) / 1e6, 3),
                               "blocks_ms_per_step": [round(b, 3) for b in graph_blocks],
@@ -1128,8 +1284,6 @@ def bench_minkunet(args, ME, MEB, dist_utils, rank, world, dev, startup):
             if args.cpu_capped else cpu_baseline_minkunet(coords, specs, args.cpu_budget)
         if line["cpu_baseline"]:
             line["speedup_vs_cpu_baseline"] = round(line["value"] / line["cpu_baseline"]["value"], 1)
-    else:
-        line["cpu_baseline"] = None
     return line
 
 
@@ -1159,6 +1313,7 @@ def extra_workloads(args, ME, MEB, dist_utils, rank, world, dev, startup):
         a = argparse.Namespace(**vars(args))
         a.points = a.cin = a.cout = 0
         a.scenes, a.graph, a.sync_bn, a.imbalance = "cached", False, False, False
+        a.full, a.dump_outputs = True, ""
         for k, v in over.items():
             setattr(a, k, v)
         t0 = time.perf_counter()
@@ -1208,6 +1363,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--warmup-time", type=float, default=0.5,
+                    help="after the --warmup steps, keep warming up with steps for at least this many seconds")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure everything else: repeated K-step blocks with per-kernel HIP events "
+                         "(kernels, roofline), the warm map build, the exchange at N > 1, the hipGraph / rocm-smi probes of "
+                         "the MinkUNet step, the reference CPU baseline, the other workloads and the in-run PMC passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, rows in coordinate order, "
+                         "64 MB at most: a fixed, seeded sample of rows beyond that)")
     ap.add_argument("--workload", choices=("conv3d", "conv4d", "minkunet"), default="conv3d")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
                     help="feature dtype (bf16: fp32 master weights, bf16 features, fp32 accumulation)")
@@ -1215,8 +1379,9 @@ def main():
     ap.add_argument("--extent", type=int, default=70, help="conv3d: 70 = dense headline (P ~ 8.4 N); 215 = sparse")
     ap.add_argument("--cin", type=int, default=0)
     ap.add_argument("--cout", type=int, default=0)
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU baseline timing (0 = skip)")
-    ap.add_argument("--min-time", type=float, default=0.2, help="keep timing K-step blocks until this many seconds")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="--full: seconds of CPU baseline timing (0 = skip)")
+    ap.add_argument("--min-time", type=float, default=0.2,
+                    help="--full: keep timing K-step blocks until this many seconds")
     ap.add_argument("--min-blocks", type=int, default=3)
     ap.add_argument("--no-gpu-state", action="store_true", help="skip the rocm-smi sample under load (MinkUNet lines)")
     ap.add_argument("--timer-blocks", type=int, default=4,
@@ -1246,12 +1411,12 @@ def main():
                     help="minkunet: skip the extra hipGraph replay measurement reported beside the eager step")
     ap.add_argument("--extra-workloads", choices=("auto", "on", "off"), default="auto",
                     help="append compact entries for BASELINE configs[2] (MinkUNet34C bf16 @200k) and configs[4] (4-D "
-                         "conv) under `workloads` (auto: with the default single-GPU headline run only)")
+                         "conv) under `workloads` (auto: --full with the default headline; on: implies --full)")
     ap.add_argument("--cpu-capped", action="store_true",
                     help="minkunet: also time the reference CPU layers under its own 16-thread cap (doubles the CPU time)")
     ap.add_argument("--pmc", choices=("auto", "on", "off"), default="auto",
                     help="measure roofline.traffic in this run with rocprofv3 --pmc passes over child processes (auto: "
-                         "single-GPU runs when rocprofv3 is installed; bounded by --pmc-budget)")
+                         "single-GPU --full runs when rocprofv3 is installed; on: implies --full; bounded by --pmc-budget)")
     ap.add_argument("--pmc-budget", type=float, default=140.0, help="seconds the in-run PMC passes may take in total")
     ap.add_argument("--pmc-child", type=int, default=0, help=argparse.SUPPRESS)   # internal: run N untimed steps and exit
     ap.add_argument("--accum", type=int, default=4,
@@ -1265,6 +1430,8 @@ def main():
     ap.add_argument("--debug-conv-variant", type=int, default=0,
                     help="kernel-selection switch of csrc/me_amd_debug.h (tuning scripts; 0 = shipped kernels)")
     args = ap.parse_args()
+    if args.extra_workloads == "on" or args.pmc == "on":
+        args.full = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -1318,7 +1485,7 @@ def main():
         # profiled child of measure_traffic(): the same workload objects, `pmc_child` untimed steps, no JSON line
         args.steps, args.warmup, args.cpu_budget = args.pmc_child, 0, 0.0
         args.min_time, args.min_blocks, args.max_blocks, args.no_graph_probe = 0.0, 1, 1, True
-        args.extra_workloads, args.pmc = "off", "off"
+        args.extra_workloads, args.pmc, args.full, args.dump_outputs = "off", "off", False, ""
         args.pmc_child_mode = True
         fn(args, ME, MEB, dist_utils, rank, world, dev, startup)
         print(f"PMC_CHILD_STEPS={args.steps}", flush=True)
@@ -1326,12 +1493,12 @@ def main():
     line = fn(args, ME, MEB, dist_utils, rank, world, dev, startup)
     default_headline = (args.workload == "conv3d" and args.dtype == "f32" and not args.points and
                         not args.cin and not args.cout and args.extent == 70)
-    if args.extra_workloads == "on" or (args.extra_workloads == "auto" and default_headline):
+    if args.full and args.extra_workloads != "off" and (args.extra_workloads == "on" or default_headline):
         # (every rank takes part: the N > 1 entry is a collective workload; only rank 0 holds a line to attach it to)
         extra = extra_workloads(args, ME, MEB, dist_utils, rank, world, dev, startup)
         if line is not None:
             line["workloads"] = extra
-    if rank == 0 and world == 1 and args.pmc != "off":
+    if args.full and rank == 0 and world == 1 and args.pmc != "off":
         t_pmc = time.perf_counter()
         attach_sq(line, args, t_pmc + 0.45 * args.pmc_budget)      # MFMA utilisation first (two passes at most)
         attach_traffic(line, args, t_pmc + args.pmc_budget)

@@ -12,17 +12,17 @@ echo "pytest rc=$?" | tee -a $OUT/pytest_new.log
 grep -E "^(FAILED|ERROR)|passed|failed|Error|error" $OUT/pytest_new.log | head -40
 echo "== bench conv3d f32 / bf16"
 for dt in f32 bf16; do
-  timeout 300 python bench.py --steps 50 --warmup 10 --dtype $dt --cpu-budget 3 > $OUT/bench_conv3d_$dt.json 2> $OUT/bench_conv3d_$dt.err; echo "rc=$?"
+  timeout 300 python bench.py --full --steps 50 --warmup 10 --dtype $dt --cpu-budget 3 > $OUT/bench_conv3d_$dt.json 2> $OUT/bench_conv3d_$dt.err; echo "rc=$?"
   cut -c1-1500 $OUT/bench_conv3d_$dt.json; tail -3 $OUT/bench_conv3d_$dt.err
 done
 echo "== bench conv4d"
 for dt in f32 bf16; do
-  timeout 400 python bench.py --workload conv4d --steps 30 --warmup 5 --dtype $dt --cpu-budget 5 > $OUT/bench_conv4d_$dt.json 2> $OUT/bench_conv4d_$dt.err; echo "rc=$?"
+  timeout 400 python bench.py --full --workload conv4d --steps 30 --warmup 5 --dtype $dt --cpu-budget 5 > $OUT/bench_conv4d_$dt.json 2> $OUT/bench_conv4d_$dt.err; echo "rc=$?"
   cut -c1-1500 $OUT/bench_conv4d_$dt.json; tail -3 $OUT/bench_conv4d_$dt.err
 done
 echo "== bench minkunet"
 for dt in f32 bf16; do
-  timeout 400 python bench.py --workload minkunet --steps 10 --warmup 3 --dtype $dt > $OUT/bench_minkunet_$dt.json 2> $OUT/bench_minkunet_$dt.err; echo "rc=$?"
+  timeout 400 python bench.py --full --workload minkunet --steps 10 --warmup 3 --dtype $dt > $OUT/bench_minkunet_$dt.json 2> $OUT/bench_minkunet_$dt.err; echo "rc=$?"
   cut -c1-2500 $OUT/bench_minkunet_$dt.json; tail -3 $OUT/bench_minkunet_$dt.err
 done
 echo "== rocprofv3 minkunet bf16"

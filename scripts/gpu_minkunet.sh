@@ -6,9 +6,9 @@ OUT=$PWD/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 for dt in f32 bf16; do
-  timeout 400 python bench.py --workload minkunet --steps 10 --warmup 3 --dtype $dt > $OUT/bench_minkunet_$dt.json 2> $OUT/bench_minkunet_$dt.err
+  timeout 400 python bench.py --full --workload minkunet --steps 10 --warmup 3 --dtype $dt > $OUT/bench_minkunet_$dt.json 2> $OUT/bench_minkunet_$dt.err
   python -c "import json;d=json.load(open('$OUT/bench_minkunet_$dt.json'));print('$dt', d['ms_per_step'],'ms', d['value'],'Mpts/s', {k:(v['ms_per_step'],v['tflops']) for k,v in d['kernels'].items()})"
-  ME_AMD_TORCH_BN=1 timeout 400 python bench.py --workload minkunet --steps 10 --warmup 3 --dtype $dt > $OUT/bench_minkunet_${dt}_torchbn.json 2>/dev/null
+  ME_AMD_TORCH_BN=1 timeout 400 python bench.py --full --workload minkunet --steps 10 --warmup 3 --dtype $dt > $OUT/bench_minkunet_${dt}_torchbn.json 2>/dev/null
   python -c "import json;d=json.load(open('$OUT/bench_minkunet_${dt}_torchbn.json'));print('$dt torch BN', d['ms_per_step'],'ms')"
 done
 cd /tmp

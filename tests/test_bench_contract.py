@@ -3,6 +3,11 @@ every line carries the driver's keys plus `roofline` and `cpu_baseline`, and the
 import glob
 import json
 import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -93,3 +98,58 @@ def test_multi_gpu_line_carries_the_exchange_and_the_ddp_workload():
     assert w["multi_gpu"]["per_rank_points"] == [200000, 200000]
     pts = 2 * 200000
     assert abs(w["value"] - pts / (w["ms_per_step"] * 1e-3) / 1e6) < 0.01 * w["value"]
+
+
+def test_dump_outputs_rows_in_coordinate_order_within_the_byte_cap(tmp_path):
+    """--dump-outputs: per-row outputs of one coordinate set, each in its own row order, come out in coordinate order
+    with their coordinates; past the cap the same seeded sample of rows is kept for every array."""
+    import bench
+    rng = np.random.default_rng(1)
+    n = 100000
+    ids = rng.permutation(n).astype(np.int32)
+    coords = np.stack([np.zeros(n, np.int32), ids // 1000, ids % 1000, ids % 7], 1)
+    y = rng.standard_normal((n, 128)).astype(np.float32)
+    g = rng.standard_normal((n, 64)).astype(np.float32)
+    perm = rng.permutation(n)
+    shapes = bench.dump_outputs(str(tmp_path), {"y": (y, coords), "g": (g[perm], coords[perm])},
+                                {"w": np.ones((27, 64, 128))})
+    total = sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path))
+    assert total <= 64e6 and shapes["w"] == [27, 64, 128]
+    c = np.load(tmp_path / "coords.npy")
+    assert c.dtype == np.float64 and 0 < c.shape[0] < n
+    assert np.all(np.diff(c[:, 1] * 1000 + c[:, 2]) > 0)                 # coordinate order
+    row = {int(v): i for i, v in enumerate(ids)}
+    rows = np.array([row[int(a * 1000 + b)] for a, b in c[:, 1:3]])
+    assert np.array_equal(np.load(tmp_path / "y.npy"), y[rows]) and np.array_equal(np.load(tmp_path / "g.npy"), g[rows])
+    assert np.load(tmp_path / "y.npy").dtype == np.float32
+    again = tmp_path / "again"                                          # the sample is fixed: same call, same files
+    bench.dump_outputs(str(again), {"y": (y, coords), "g": (g[perm], coords[perm])}, {"w": np.ones((27, 64, 128))})
+    for f in ("coords", "y", "g"):
+        assert np.array_equal(np.load(again / f"{f}.npy"), np.load(tmp_path / f"{f}.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_the_steps_and_dumps_the_last_one(device, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps (ms_per_step = that region / K), carries the
+    headline keys and nothing of --full, and --dump-outputs writes the layer's outputs and gradients of the last step."""
+    out = tmp_path / "out"
+    env = {k: v for k, v in os.environ.items() if k != "ME_AMD_HOST"}     # the product's default host layer
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["timing"]["timed_steps"] == 7 and d["dtype"] == "f32" and d["unit"] == "Mpoints/s"
+    assert abs(d["ms_per_step"] - d["timing"]["timed_region_s"] * 1e3 / 7) < 1e-3
+    assert abs(d["value"] - d["config"]["points_per_gpu"] / (d["ms_per_step"] * 1e-3) / 1e6) < 0.01 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "workloads" not in d and "kernels" not in d
+    names = set(os.listdir(out))
+    assert names == {"out_features.npy", "grad_in_features.npy", "grad_kernel.npy", "coords.npy"}, names
+    assert sum(os.path.getsize(out / f) for f in names) <= 64e6
+    arrays = {f[:-4]: np.load(out / f) for f in names}
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), k
+    m = arrays["coords"].shape[0]
+    assert arrays["out_features"].shape == (m, 128) and arrays["grad_in_features"].shape == (m, 64)
+    assert arrays["grad_kernel"].shape == (27, 64, 128) and np.abs(arrays["grad_kernel"]).max() > 0

@@ -65,7 +65,9 @@ typedef struct me_region {
  *   1.6 (160)  round 6: row-wise launches for kernel-map sides with exactly one pair per target row — K = 1 layers
  *              (the reference's `input.F.mm(kernel)`) and the fine side of kernel_size == stride maps
  *              (me_conv_rowwise_supported_bf16, me_conv_rowwise_bf16); Z-order of a map by the library's own radix sort
- *              (me_coords_zorder) */
+ *              (me_coords_zorder)
+ *   1.7 (170)  round 7: channelwise (depthwise) convolution, forward and backward (me_cwconv_forward_*,
+ *              me_cwconv_backward_workspace_bytes, me_cwconv_backward_*) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -660,6 +662,45 @@ int me_global_pool_bf16(const uint16_t *src_dev, const uint16_t *src2_dev, int32
                         float *dst_count_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 int me_broadcast_bf16(const uint16_t *in_dev, const uint16_t *glob_dev, const int32_t *batch_row_dev, int64_t n,
                       int32_t c, int32_t multiply, uint16_t *out_dev, void *stream);
+
+/* ---- channelwise (depthwise) convolution (MinkowskiChannelwiseConvolution, the reference's
+ *      MinkowskiEngine/MinkowskiChannelwiseConvolution.py:184-189: plain Python, one gather / multiply / index_put
+ *      per kernel offset, no native operator) ---------------------------------------------------------------------
+ * Every channel has its own kernel: weight [volume, c] row-major, bias [c] (may be NULL); n_src / n_tgt: rows of the
+ * source / target feature matrices.
+ *   forward:  dst[t, ch] = bias[ch] + sum_k weight[k, ch] * src[tbl[k, t], ch]      tbl = nbr [volume, n_tgt]
+ *   backward: dx[i, ch]  = sum_k weight[k, ch] * dy[tbl_t[k, i], ch]                 tbl_t = nbrT [volume, n_src]
+ *             dweight[k, ch] = sum_i x[i, ch] * dy[tbl_t[k, i], ch],   dbias[ch] = sum_t dy[t, ch]
+ * Target-stationary on the tables like pooling: every output row is written once (rows without neighbours get the bias
+ * or 0), the sums over k run in ascending order, and the weight / bias gradients are a two-level reduction (per chunk
+ * of source rows, then the chunks) in a fixed order, without atomics: every result is bitwise reproducible.
+ * bf16 rows (uint16_t = raw bfloat16 bits) take fp32 weight and bias, accumulate in fp32 and round once at the store;
+ * dweight / dbias are fp32 (double for the _f64 variants: plain double fma in the same order, no workspace needed).
+ * need_dx = 0 skips dx (dx may then be NULL).  dbias NULL skips the bias gradient.  The volume may be 1 .. 65535
+ * (larger: error); n_tgt = 0 launches nothing; n_src = n_tgt = 0 in the backward only zero-fills dweight / dbias.
+ * Workspace of the fp32 / bf16 backward: me_cwconv_backward_workspace_bytes(n_src, volume, c) bytes. */
+int me_cwconv_forward_f32(const float *src_dev, int32_t c, const float *weight_dev, const float *bias_dev,
+                          const int32_t *tbl_dev, int64_t n_src, int64_t n_tgt, int64_t volume, float *dst_dev,
+                          void *stream);
+int me_cwconv_forward_bf16(const uint16_t *src_dev, int32_t c, const float *weight_dev, const float *bias_dev,
+                           const int32_t *tbl_dev, int64_t n_src, int64_t n_tgt, int64_t volume, uint16_t *dst_dev,
+                           void *stream);
+int me_cwconv_forward_f64(const double *src_dev, int32_t c, const double *weight_dev, const double *bias_dev,
+                          const int32_t *tbl_dev, int64_t n_src, int64_t n_tgt, int64_t volume, double *dst_dev,
+                          void *stream);
+int64_t me_cwconv_backward_workspace_bytes(int64_t n_src, int64_t volume, int32_t c);
+int me_cwconv_backward_f32(const float *x_dev, const float *dy_dev, int32_t c, const float *weight_dev,
+                           const int32_t *tbl_t_dev, int64_t n_src, int64_t n_tgt, int64_t volume, int32_t need_dx,
+                           float *dx_dev, float *dweight_dev, float *dbias_dev, void *workspace_dev,
+                           int64_t workspace_bytes, void *stream);
+int me_cwconv_backward_bf16(const uint16_t *x_dev, const uint16_t *dy_dev, int32_t c, const float *weight_dev,
+                            const int32_t *tbl_t_dev, int64_t n_src, int64_t n_tgt, int64_t volume, int32_t need_dx,
+                            uint16_t *dx_dev, float *dweight_dev, float *dbias_dev, void *workspace_dev,
+                            int64_t workspace_bytes, void *stream);
+int me_cwconv_backward_f64(const double *x_dev, const double *dy_dev, int32_t c, const double *weight_dev,
+                           const int32_t *tbl_t_dev, int64_t n_src, int64_t n_tgt, int64_t volume, int32_t need_dx,
+                           double *dx_dev, double *dweight_dev, double *dbias_dev, void *workspace_dev,
+                           int64_t workspace_bytes, void *stream);
 
 /* Generative / expanding convolutions (CoordinateMapCPU::stride_region, src/coordinate_map_cpu.hpp:446-487;
  * manager: src/coordinate_map_manager.cpp:436-466): candidate output coordinates = every kernel offset of the

@@ -19,6 +19,7 @@ from .common import convert_to_int_list, get_minkowski_function  # noqa: F401
 from .convolution import (  # noqa: F401
     MinkowskiConvolution, MinkowskiConvolutionFunction, MinkowskiConvolutionTranspose,
     MinkowskiConvolutionTransposeFunction, MinkowskiGenerativeConvolutionTranspose)
+from .channelwise import MinkowskiChannelwiseConvolution, MinkowskiChannelwiseConvolutionFunction  # noqa: F401
 from .pruning import MinkowskiPruning, MinkowskiPruningFunction  # noqa: F401
 from .union import MinkowskiUnion, MinkowskiUnionFunction  # noqa: F401
 from .coordinate_manager import (  # noqa: F401

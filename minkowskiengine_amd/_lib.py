@@ -198,6 +198,16 @@ SIGNATURES = {
     "me_global_pool_bf16": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                            c_i64, c_vp]),
     "me_broadcast_bf16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "me_cwconv_forward_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "me_cwconv_forward_bf16": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "me_cwconv_forward_f64": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "me_cwconv_backward_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "me_cwconv_backward_f32": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp,
+                                              c_vp, c_vp, c_i64, c_vp]),
+    "me_cwconv_backward_bf16": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp,
+                                               c_vp, c_vp, c_i64, c_vp]),
+    "me_cwconv_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp,
+                                              c_vp, c_vp, c_i64, c_vp]),
     "me_conv_forward_naive_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64,
                                                  c_vp, c_vp]),
     "me_conv_backward_naive_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,

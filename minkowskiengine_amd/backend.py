@@ -2107,6 +2107,90 @@ def LocalPoolingTransposeBackwardGPU(in_feat, grad_out_feat, num_nonzero, kernel
     return grad_in
 
 
+# ------------------------------------------------------------------------------------------------
+# channelwise (depthwise) convolution (MinkowskiChannelwiseConvolution.py:184-189; the reference has no native
+# operator: its module gathers, multiplies and index_puts once per offset in Python).  csrc/conv_channelwise.hip
+# ------------------------------------------------------------------------------------------------
+def _cw_kernel_dtype(feat):
+    """bf16 features take fp32 weights (the fp32 master weights of the modules); fp32 / f64 take their own dtype"""
+    return torch.float64 if feat.dtype == torch.float64 else torch.float32
+
+
+def _check_cw(in_feat, kernel, bias, volume):
+    _check_feat("in_feat", in_feat)
+    _check(in_feat.dim() == 2, "in_feat.dim():", in_feat.dim())
+    _check(kernel.is_cuda and kernel.is_contiguous(), "kernel must be a contiguous CUDA (ROCm) tensor")
+    c = int(in_feat.shape[1])
+    _check(tuple(kernel.shape) == (volume, c), "kernel shape", tuple(kernel.shape), "!= (kernel volume, channels)",
+           (volume, c))
+    _check(kernel.dtype == _cw_kernel_dtype(in_feat), "kernel must be", _cw_kernel_dtype(in_feat), "for",
+           in_feat.dtype, "features, got", kernel.dtype)
+    _check(kernel.device == in_feat.device, "kernel and features must be on one device")
+    if bias is not None:
+        _check(bias.is_cuda and bias.is_contiguous() and bias.numel() == c, "bias must be a contiguous CUDA tensor of",
+               c, "values")
+        _check(bias.dtype == kernel.dtype, "bias must have the kernel's dtype", kernel.dtype, "got", bias.dtype)
+        _check(bias.device == in_feat.device, "bias and features must be on one device")
+
+
+def ChannelwiseConvolutionForwardGPU(in_feat, kernel, bias, kernel_size, kernel_stride, kernel_dilation, region_type,
+                                     offset, in_key, out_key, manager):
+    """out[t] = bias + sum_k kernel[k] * in_feat[nbr[k][t]] (elementwise over the channels) -> out_feat.
+    The reference has no native operator of this name (MinkowskiChannelwiseConvolution.py:184-189 runs it in Python);
+    the name follows the package's `<Op>{Forward,Backward}GPU` convention.  An unset out_key becomes
+    stride(in_key, kernel_stride), as in the reference (:170)."""
+    _prepare_pool(in_feat, kernel_stride, in_key, out_key, manager, False)
+    km = manager._kernel_map(in_key, out_key, kernel_size, kernel_stride, kernel_dilation, region_type, offset,
+                             False, False)
+    _check_cw(in_feat, kernel, bias, km.volume)
+    lib = _lib.load()
+    dev = in_feat.device
+    c = int(in_feat.shape[1])
+    out = torch.empty((km.n_out, c), dtype=in_feat.dtype, device=dev)
+    fn = _by_dtype(lib, "cwconv_forward", in_feat)
+    with _on(dev):
+        _timed("cwconv_forward", dev, lambda: _lib.check(fn(
+            _ptr(in_feat), c, _ptr(kernel), _ptr(bias), _ptr(km.table("out")), km.n_in, km.n_out, km.volume, _ptr(out),
+            _stream(dev))))
+    return out
+
+
+def ChannelwiseConvolutionBackwardGPU(in_feat, grad_out_feat, kernel, kernel_size, kernel_stride, kernel_dilation,
+                                      region_type, offset, in_key, out_key, manager, need_grad_in=True,
+                                      need_grad_bias=True):
+    """-> (grad_in | None, grad_kernel [volume, C], grad_bias [C] | None): one pass over the transposed table (dx and
+    the weight-gradient partials), then the fixed-order reduction of the partials.  The weight and bias gradients have
+    the kernel's dtype (fp32 for bf16 features).  No reference native operator exists (see the forward)."""
+    _check_feat("in_feat", in_feat)
+    if not grad_out_feat.is_contiguous():
+        grad_out_feat = grad_out_feat.contiguous()
+    _check_feat("grad_out_feat", grad_out_feat)
+    if grad_out_feat.dtype != in_feat.dtype:
+        grad_out_feat = grad_out_feat.to(in_feat.dtype)
+    _check(grad_out_feat.dim() == 2 and grad_out_feat.shape[1] == in_feat.shape[1],
+           "Output feature size and kernel size mismatch")
+    km = manager._kernel_map(in_key, out_key, kernel_size, kernel_stride, kernel_dilation, region_type, offset,
+                             False, False)
+    _check_cw(in_feat, kernel, None, km.volume)
+    _check(in_feat.shape[0] == km.n_in, "Invalid in_feat size", in_feat.shape[0], "!=", km.n_in)
+    _check(grad_out_feat.shape[0] == km.n_out, "Invalid grad_out size")
+    lib = _lib.load()
+    dev = in_feat.device
+    c = int(in_feat.shape[1])
+    grad_in = torch.empty((km.n_in, c), dtype=in_feat.dtype, device=dev) if need_grad_in else None
+    grad_kernel = torch.empty((km.volume, c), dtype=kernel.dtype, device=dev)
+    grad_bias = torch.empty((c,), dtype=kernel.dtype, device=dev) if need_grad_bias else None
+    ws_bytes = 0 if in_feat.dtype == torch.float64 else int(lib.me_cwconv_backward_workspace_bytes(km.n_in, km.volume, c))
+    ws = _workspace(ws_bytes, dev)
+    fn = _by_dtype(lib, "cwconv_backward", in_feat)
+    with _on(dev):
+        _timed("cwconv_backward", dev, lambda: _lib.check(fn(
+            _ptr(in_feat), _ptr(grad_out_feat), c, _ptr(kernel), _ptr(km.table("in")), km.n_in, km.n_out, km.volume,
+            1 if need_grad_in else 0, _ptr(grad_in), _ptr(grad_kernel), _ptr(grad_bias), _ptr(ws), ws.numel(),
+            _stream(dev))))
+    return grad_in, grad_kernel, grad_bias
+
+
 _GLOBAL_SUM = (PoolingMode.GLOBAL_SUM_POOLING_DEFAULT, PoolingMode.GLOBAL_SUM_POOLING_KERNEL,
                PoolingMode.GLOBAL_SUM_POOLING_PYTORCH_INDEX)
 _GLOBAL_AVG = (PoolingMode.GLOBAL_AVG_POOLING_DEFAULT, PoolingMode.GLOBAL_AVG_POOLING_KERNEL,

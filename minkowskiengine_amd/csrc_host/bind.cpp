@@ -375,6 +375,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return local_pooling_transpose_backward(in_feat, grad_out, num_nonzero, ks, st, dl, to_int(region_type),
                                                   to_int(pooling_mode), in_key, out_key, mgr);
         });
+  // channelwise convolution: no reference native operator (MinkowskiChannelwiseConvolution.py runs in Python); the
+  // names follow the package's <Op>{Forward,Backward}GPU convention.  The GIL is released around the map and launches.
+  m.def("ChannelwiseConvolutionForwardGPU",
+        [](const Tensor &in_feat, const Tensor &kernel, const py::object &bias, const ivec &ks, const ivec &st,
+           const ivec &dl, const py::object &region_type, const py::object & /*offset*/, CoordinateMapKey *in_key,
+           CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
+          const Tensor b = opt_tensor(bias);
+          const int rt = to_int(region_type);
+          py::gil_scoped_release nogil;
+          return channelwise_forward(in_feat, kernel, b, ks, st, dl, rt, in_key, out_key, mgr);
+        },
+        py::arg("in_feat"), py::arg("kernel"), py::arg("bias"), py::arg("kernel_size"), py::arg("kernel_stride"),
+        py::arg("kernel_dilation"), py::arg("region_type"), py::arg("offset"), py::arg("in_key"), py::arg("out_key"),
+        py::arg("manager"));
+  m.def("ChannelwiseConvolutionBackwardGPU",
+        [](const Tensor &in_feat, const Tensor &grad_out, const Tensor &kernel, const ivec &ks, const ivec &st,
+           const ivec &dl, const py::object &region_type, const py::object & /*offset*/, CoordinateMapKey *in_key,
+           CoordinateMapKey *out_key, CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_bias) {
+          const int rt = to_int(region_type);
+          std::tuple<Tensor, Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = channelwise_backward(in_feat, grad_out, kernel, ks, st, dl, rt, in_key, out_key, mgr, need_grad_in,
+                                     need_grad_bias);
+          }
+          return py::make_tuple(opt_out(std::get<0>(r)), std::get<1>(r), opt_out(std::get<2>(r)));
+        },
+        py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("kernel"), py::arg("kernel_size"), py::arg("kernel_stride"),
+        py::arg("kernel_dilation"), py::arg("region_type"), py::arg("offset"), py::arg("in_key"), py::arg("out_key"),
+        py::arg("manager"), py::arg("need_grad_in") = true, py::arg("need_grad_bias") = true);
   m.def("GlobalPoolingForwardGPU",
         [](const Tensor &in_feat, const py::object &pooling_mode, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
            CoordinateMapManager *mgr) {

@@ -295,6 +295,14 @@ std::pair<Tensor, Tensor> local_pooling_transpose_forward(const Tensor &in_feat,
 Tensor local_pooling_transpose_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &num_nonzero, const ivec &ks,
                                         const ivec &st, const ivec &dl, int region_type, int pooling_mode,
                                         CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr);
+Tensor channelwise_forward(const Tensor &in_feat, const Tensor &kernel, const Tensor &bias, const ivec &ks,
+                           const ivec &st, const ivec &dl, int region_type, CoordinateMapKey *in_key,
+                           CoordinateMapKey *out_key, CoordinateMapManager *mgr);
+std::tuple<Tensor, Tensor, Tensor> channelwise_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &kernel,
+                                                        const ivec &ks, const ivec &st, const ivec &dl, int region_type,
+                                                        CoordinateMapKey *in_key, CoordinateMapKey *out_key,
+                                                        CoordinateMapManager *mgr, bool need_grad_in,
+                                                        bool need_grad_bias);
 std::pair<Tensor, Tensor> global_pooling_forward(const Tensor &in_feat, int pooling_mode, CoordinateMapKey *in_key,
                                                  CoordinateMapKey *out_key, CoordinateMapManager *mgr);
 Tensor global_pooling_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &num_nonzero, int pooling_mode,

@@ -766,6 +766,88 @@ Tensor local_pooling_transpose_backward(const Tensor &in_feat, Tensor grad_out, 
   return pool_sum(grad_out, km->table("in"), km->n_in, km->volume, Tensor(), false, false).first;
 }
 
+// ---- channelwise (depthwise) convolution (csrc/conv_channelwise.hip; twin of backend.ChannelwiseConvolution*GPU) --------
+static void check_cw(const Tensor &in_feat, const Tensor &kernel, const Tensor &bias, int64_t volume) {
+  check_feat("in_feat", in_feat);
+  check(in_feat.dim() == 2, "in_feat.dim() must be 2");
+  check(kernel.is_cuda() && kernel.is_contiguous(), "kernel must be a contiguous CUDA (ROCm) tensor");
+  const int64_t c = in_feat.size(1);
+  check(kernel.dim() == 2 && kernel.size(0) == volume && kernel.size(1) == c,
+        "kernel shape != (kernel volume, channels)");
+  const at::ScalarType kt = in_feat.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
+  check(kernel.scalar_type() == kt, "kernel must be float64 for float64 features and float32 otherwise");
+  check(kernel.device() == in_feat.device(), "kernel and features must be on one device");
+  if (bias.defined()) {
+    check(bias.is_cuda() && bias.is_contiguous() && bias.numel() == c, "bias must be a contiguous CUDA tensor of C values");
+    check(bias.scalar_type() == kernel.scalar_type(), "bias must have the kernel's dtype");
+    check(bias.device() == in_feat.device(), "bias and features must be on one device");
+  }
+}
+
+Tensor channelwise_forward(const Tensor &in_feat, const Tensor &kernel, const Tensor &bias, const ivec &ks,
+                           const ivec &st, const ivec &dl, int region_type, CoordinateMapKey *in_key,
+                           CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
+  prepare_pool(in_feat, st, in_key, out_key, mgr, false);
+  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, false, false);
+  check_cw(in_feat, kernel, bias, km->volume);
+  const c10::Device dev = in_feat.device();
+  const int c = (int)in_feat.size(1);
+  Tensor out = at::empty({km->n_out, c}, in_feat.options());
+  Tensor tbl = km->table("out");
+  c10::DeviceGuard guard(dev);
+  if (in_feat.scalar_type() == at::kDouble)
+    me_ok(me_cwconv_forward_f64(ptr<double>(in_feat), c, ptr<double>(kernel), ptr<double>(bias), ptr<int32_t>(tbl),
+                                km->n_in, km->n_out, km->volume, ptr<double>(out), stream_of(dev)));
+  else if (in_feat.scalar_type() == at::kBFloat16)
+    me_ok(me_cwconv_forward_bf16(ptr<uint16_t>(in_feat), c, ptr<float>(kernel), ptr<float>(bias), ptr<int32_t>(tbl),
+                                 km->n_in, km->n_out, km->volume, ptr<uint16_t>(out), stream_of(dev)));
+  else
+    me_ok(me_cwconv_forward_f32(ptr<float>(in_feat), c, ptr<float>(kernel), ptr<float>(bias), ptr<int32_t>(tbl),
+                                km->n_in, km->n_out, km->volume, ptr<float>(out), stream_of(dev)));
+  return out;
+}
+
+std::tuple<Tensor, Tensor, Tensor> channelwise_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &kernel,
+                                                        const ivec &ks, const ivec &st, const ivec &dl, int region_type,
+                                                        CoordinateMapKey *in_key, CoordinateMapKey *out_key,
+                                                        CoordinateMapManager *mgr, bool need_grad_in,
+                                                        bool need_grad_bias) {
+  check_feat("in_feat", in_feat);
+  grad_out = grad_out.contiguous();
+  check_feat("grad_out_feat", grad_out);
+  if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
+  check(grad_out.dim() == 2 && grad_out.size(1) == in_feat.size(1), "Output feature size and kernel size mismatch");
+  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, false, false);
+  check_cw(in_feat, kernel, Tensor(), km->volume);
+  check(in_feat.size(0) == km->n_in, "Invalid in_feat size");
+  check(grad_out.size(0) == km->n_out, "Invalid grad_out size");
+  const c10::Device dev = in_feat.device();
+  const int c = (int)in_feat.size(1);
+  Tensor grad_in = need_grad_in ? at::empty({km->n_in, c}, in_feat.options()) : Tensor();
+  Tensor grad_kernel = at::empty({km->volume, c}, kernel.options());
+  Tensor grad_bias = need_grad_bias ? at::empty({c}, kernel.options()) : Tensor();
+  Tensor tbl = km->table("in");
+  c10::DeviceGuard guard(dev);
+  if (in_feat.scalar_type() == at::kDouble) {
+    me_ok(me_cwconv_backward_f64(ptr<double>(in_feat), ptr<double>(grad_out), c, ptr<double>(kernel), ptr<int32_t>(tbl),
+                                 km->n_in, km->n_out, km->volume, need_grad_in ? 1 : 0, ptr<double>(grad_in),
+                                 ptr<double>(grad_kernel), ptr<double>(grad_bias), nullptr, 0, stream_of(dev)));
+    return {grad_in, grad_kernel, grad_bias};
+  }
+  const int64_t ws_bytes = me_cwconv_backward_workspace_bytes(km->n_in, km->volume, c);
+  Tensor ws = workspace(ws_bytes, dev);
+  if (in_feat.scalar_type() == at::kBFloat16)
+    me_ok(me_cwconv_backward_bf16(ptr<uint16_t>(in_feat), ptr<uint16_t>(grad_out), c, ptr<float>(kernel),
+                                  ptr<int32_t>(tbl), km->n_in, km->n_out, km->volume, need_grad_in ? 1 : 0,
+                                  ptr<uint16_t>(grad_in), ptr<float>(grad_kernel), ptr<float>(grad_bias), vptr(ws),
+                                  ws.numel(), stream_of(dev)));
+  else
+    me_ok(me_cwconv_backward_f32(ptr<float>(in_feat), ptr<float>(grad_out), c, ptr<float>(kernel), ptr<int32_t>(tbl),
+                                 km->n_in, km->n_out, km->volume, need_grad_in ? 1 : 0, ptr<float>(grad_in),
+                                 ptr<float>(grad_kernel), ptr<float>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
+  return {grad_in, grad_kernel, grad_bias};
+}
+
 // mode 0 sum / 1 avg / 2 max over the rows of each origin row -> (out, argmax | undefined, count | undefined)
 static std::tuple<Tensor, Tensor, Tensor> global_pool(const Tensor &src, const Tensor &src2, const Tensor &rows,
                                                       int64_t n_batch, int mode) {

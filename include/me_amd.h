@@ -67,7 +67,9 @@ typedef struct me_region {
  *              (me_conv_rowwise_supported_bf16, me_conv_rowwise_bf16); Z-order of a map by the library's own radix sort
  *              (me_coords_zorder)
  *   1.7 (170)  round 7: channelwise (depthwise) convolution, forward and backward (me_cwconv_forward_*,
- *              me_cwconv_backward_workspace_bytes, me_cwconv_backward_*) */
+ *              me_cwconv_backward_workspace_bytes, me_cwconv_backward_*)
+ *   1.8 (180)  round 8: tensor fields: quantisation, field -> sparse lookup and trilinear interpolation maps (me_field_*), stable
+ *              CSR from COO and the weighted CSR gather-sum (me_csr_*) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -701,6 +703,67 @@ int me_cwconv_backward_f64(const double *x_dev, const double *dy_dev, int32_t c,
                            const int32_t *tbl_t_dev, int64_t n_src, int64_t n_tgt, int64_t volume, int32_t need_dx,
                            double *dx_dev, double *dweight_dev, double *dbias_dev, void *workspace_dev,
                            int64_t workspace_bytes, void *stream);
+
+/* ---- tensor fields (TensorField, SparseTensor.slice / interpolate, MinkowskiInterpolation, spmm; the reference's
+ *      quantize_coordinates_kernel, field_map_kernel and interpolation_kernel, src/coordinate_map_gpu.cu:107-145,
+ *      1977-2112, and its cuSPARSE coo_spmm, src/spmm.cu) ------------------------------------------------------------
+ * Field coordinates x: [n, ncol] contiguous, float32 (_f32) or float64 (_f64), column 0 the batch index.
+ * tensor_stride: host int32 [ncol - 1], every entry > 0 (NULL: all 1).  ncol in [2, 8].
+ * Quantisation of point i: (lrint(x[i, 0]), floor(x[i, j] / s_j) * s_j) — a division, as the reference's kernel.
+ *
+ * me_field_quantize_*: out int32 [n, ncol] (feed it to me_coords_insert_and_map).  No sync.
+ * me_field_lookup_*: quantise and probe a map (table / capacity / map_coords as me_coords_find; 16-byte aligned for
+ *   ncol 4): (sparse_rows[k], field_rows[k]) for the points whose voxel is present, in ascending field row order;
+ *   sparse_rows / field_rows int32 [n] (first *n_hit valid).  SYNC (one 4-byte copy for *n_hit).
+ *   Workspace: me_field_lookup_workspace_bytes(n).
+ * me_field_interp_map_*: trilinear interpolation map of the points on a map of tensor stride s.  Corner v of point p
+ *   (v in [0, 2^D)): bit (D - j) of v selects floor(x_j / s_j) * s_j + s_j in column j, else floor(x_j / s_j) * s_j;
+ *   batch lrint(x_0).  Every present corner gives an entry (in_rows = map row, out_rows = p,
+ *   weights = prod_{j=1..D} (1 - |x_j - c_j| / s_j), in the coordinate type, j ascending); entries ordered by (p, v)
+ *   ascending (the reference's order after its stable remove_if).  in_rows / out_rows int32 and weights [n * 2^D]
+ *   (first *nnz valid); rowptr int32 [n + 1]: entries of point p at [rowptr[p], rowptr[p + 1]).  n * 2^D < 2^31.
+ *   SYNC (one 4-byte copy for *nnz).  Workspace: me_field_interp_workspace_bytes(n, ncol).
+ * me_csr_from_coo: rows of a COO matrix by keys[e] in [0, n_rows), stable in entry order (the library's radix sort):
+ *   rowptr int32 [n_rows + 1], cols_out[i] = cols[e_i] (cols NULL: e_i itself), vals_out[i] = vals[e_i] (val_bytes 4
+ *   or 8; vals NULL: none) for the entries e_0 < e_1 < ... of each row in turn.  nnz, n_rows < 2^31.  No sync.
+ *   Workspace: me_csr_from_coo_workspace_bytes(nnz).
+ * me_csr_gather_*: y[r] = scale[r] * sum_{e in [rowptr[r], rowptr[r + 1])} w[e] * x[col[e]] for r < n_rows; x and y
+ *   [*, c] contiguous, every col[e] a row of x.  w NULL: unweighted; scale NULL: 1.  The sum runs in entry order in fp32
+ *   (fma with weights) for fp32 and bf16 features (bf16 rounds once at the store; w and scale fp32) and in double for
+ *   float64 (w and scale double); rows without entries are written as zeros; no atomics, bitwise reproducible.
+ *   No sync, no workspace. */
+int me_field_quantize_f32(const float *x_dev, int64_t n, int32_t ncol, const int32_t *tensor_stride, int32_t *out_dev,
+                          void *stream);
+int me_field_quantize_f64(const double *x_dev, int64_t n, int32_t ncol, const int32_t *tensor_stride, int32_t *out_dev,
+                          void *stream);
+int64_t me_field_lookup_workspace_bytes(int64_t n);
+int me_field_lookup_f32(const float *x_dev, int64_t n, int32_t ncol, const int32_t *tensor_stride,
+                        const uint64_t *table_dev, int64_t capacity, const int32_t *map_coords_dev,
+                        int32_t *sparse_rows_dev, int32_t *field_rows_dev, int64_t *n_hit, void *workspace_dev,
+                        int64_t workspace_bytes, void *stream);
+int me_field_lookup_f64(const double *x_dev, int64_t n, int32_t ncol, const int32_t *tensor_stride,
+                        const uint64_t *table_dev, int64_t capacity, const int32_t *map_coords_dev,
+                        int32_t *sparse_rows_dev, int32_t *field_rows_dev, int64_t *n_hit, void *workspace_dev,
+                        int64_t workspace_bytes, void *stream);
+int64_t me_field_interp_workspace_bytes(int64_t n, int32_t ncol);
+int me_field_interp_map_f32(const float *x_dev, int64_t n, int32_t ncol, const int32_t *tensor_stride,
+                            const uint64_t *table_dev, int64_t capacity, const int32_t *map_coords_dev,
+                            int32_t *in_rows_dev, int32_t *out_rows_dev, float *weights_dev, int32_t *rowptr_dev,
+                            int64_t *nnz, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_field_interp_map_f64(const double *x_dev, int64_t n, int32_t ncol, const int32_t *tensor_stride,
+                            const uint64_t *table_dev, int64_t capacity, const int32_t *map_coords_dev,
+                            int32_t *in_rows_dev, int32_t *out_rows_dev, double *weights_dev, int32_t *rowptr_dev,
+                            int64_t *nnz, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int64_t me_csr_from_coo_workspace_bytes(int64_t nnz);
+int me_csr_from_coo(const int32_t *keys_dev, const int32_t *cols_dev, const void *vals_dev, int32_t val_bytes,
+                    int64_t nnz, int64_t n_rows, int32_t *rowptr_dev, int32_t *cols_out_dev, void *vals_out_dev,
+                    void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_csr_gather_f32(const float *x_dev, int32_t c, const int32_t *rowptr_dev, const int32_t *col_dev,
+                      const float *w_dev, const float *scale_dev, int64_t n_rows, float *y_dev, void *stream);
+int me_csr_gather_bf16(const uint16_t *x_dev, int32_t c, const int32_t *rowptr_dev, const int32_t *col_dev,
+                       const float *w_dev, const float *scale_dev, int64_t n_rows, uint16_t *y_dev, void *stream);
+int me_csr_gather_f64(const double *x_dev, int32_t c, const int32_t *rowptr_dev, const int32_t *col_dev,
+                      const double *w_dev, const double *scale_dev, int64_t n_rows, double *y_dev, void *stream);
 
 /* Generative / expanding convolutions (CoordinateMapCPU::stride_region, src/coordinate_map_cpu.hpp:446-487;
  * manager: src/coordinate_map_manager.cpp:436-466): candidate output coordinates = every kernel offset of the

@@ -21,6 +21,10 @@ from .convolution import (  # noqa: F401
     MinkowskiConvolutionTransposeFunction, MinkowskiGenerativeConvolutionTranspose)
 from .channelwise import MinkowskiChannelwiseConvolution, MinkowskiChannelwiseConvolutionFunction  # noqa: F401
 from .pruning import MinkowskiPruning, MinkowskiPruningFunction  # noqa: F401
+from .tensor_field import TensorField, create_splat_coordinates  # noqa: F401
+from .interpolation import MinkowskiInterpolation, MinkowskiInterpolationFunction  # noqa: F401
+from .sparse_matrix_functions import (  # noqa: F401
+    MinkowskiSPMMAverageFunction, MinkowskiSPMMFunction, spmm, spmm_average)
 from .union import MinkowskiUnion, MinkowskiUnionFunction  # noqa: F401
 from .coordinate_manager import (  # noqa: F401
     CoordinateManager, set_gpu_allocator, set_memory_manager_backend, set_map_prefetch, map_prefetch_enabled, map_prefetch_tag)

@@ -208,6 +208,23 @@ SIGNATURES = {
                                                c_vp, c_vp, c_i64, c_vp]),
     "me_cwconv_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp,
                                               c_vp, c_vp, c_i64, c_vp]),
+    "me_field_quantize_f32": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "me_field_quantize_f64": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "me_field_lookup_workspace_bytes": (c_i64, [c_i64]),
+    "me_field_lookup_f32": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                           c_vp]),
+    "me_field_lookup_f64": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                           c_vp]),
+    "me_field_interp_workspace_bytes": (c_i64, [c_i64, c_i32]),
+    "me_field_interp_map_f32": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                               c_vp, c_vp, c_i64, c_vp]),
+    "me_field_interp_map_f64": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                               c_vp, c_vp, c_i64, c_vp]),
+    "me_csr_from_coo_workspace_bytes": (c_i64, [c_i64]),
+    "me_csr_from_coo": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_csr_gather_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "me_csr_gather_bf16": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "me_csr_gather_f64": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "me_conv_forward_naive_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64,
                                                  c_vp, c_vp]),
     "me_conv_backward_naive_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,

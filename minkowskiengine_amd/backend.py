@@ -704,6 +704,9 @@ class CoordinateMapManagerGPU_c10:
         self._origin_maps = {}
         self._prune_rows = {}
         self._stride_maps = {}
+        self._fields = {}        # field key tuple -> fp32 coordinates [N, D+1]
+        self._field_maps = {}    # (field key, sparse key) -> (unique_index, inverse_mapping): field_to_sparse_insert_and_map
+        self._field_lookups = {}  # (field key, sparse key) -> (sparse rows, field rows): field_to_sparse_map
         # Not in the reference: the map-building requests this manager served on a cache miss, in order — strided
         # maps, kernel maps, tile-plan / weight-gradient configurations.  `prefetch(recipe)` replays such a list on a
         # NEW scene right after its coordinates are inserted, so that every host read-back of the build (output sizes,
@@ -926,6 +929,134 @@ class CoordinateMapManagerGPU_c10:
 
     def get_coordinates(self, key):
         return self._get(key).coords
+
+    # ---- tensor fields (src/coordinate_map_manager.cpp:200-350; pybind/extern.hpp:780-805) ---------------------------
+    # Field keys live in a namespace of their own (self._fields), as in the reference; the manager keeps the fp32
+    # coordinates of each field (the reference stores `coordinates.float()`) and caches the field -> sparse maps per
+    # (field key, sparse key).
+    def insert_field(self, coordinates, tensor_stride, string_id=""):
+        """-> CoordinateMapKey of the field (continuous coordinates [N, D+1], the batch index in column 0)."""
+        _check(isinstance(coordinates, torch.Tensor) and coordinates.dim() == 2, "coordinates must be 2-D")
+        _check(coordinates.is_cuda, "coordinates must be on the GPU (the MI355X path has no CPU map)")
+        _check(coordinates.is_floating_point(), "field coordinates must be floating point")
+        ts = tuple(int(s) for s in tensor_stride)
+        _check(coordinates.shape[1] - 1 == len(ts), "The coordinate dimension (coordinate_size - 1):",
+               coordinates.shape[1] - 1, " must match the size of tensor stride:", list(ts))
+        _lib.preload_device(coordinates.device.index)
+        key = (ts, str(string_id))
+        while key in self._fields:
+            key = (ts, (str(string_id) + "-" if string_id else "") + "".join(random.choice(_CHARSET) for _ in range(5)))
+        self._fields[key] = coordinates.detach().float().contiguous()
+        return CoordinateMapKey(list(key[0]), key[1])
+
+    def _field(self, key):
+        k = self._k(key)
+        _check(k in self._fields, "coordinate field not found", k)
+        return self._fields[k]
+
+    def get_coordinate_field(self, key):
+        return self._field(key)
+
+    def field_to_sparse_insert_and_map(self, field_key, sparse_tensor_stride, string_id=""):
+        """Quantise the field at `sparse_tensor_stride` (me_field_quantize) and insert the voxels ->
+        (sparse key, (unique_index, inverse_mapping)), both int64, as insert_and_map."""
+        x = self._field(field_key)
+        ts = tuple(int(s) for s in sparse_tensor_stride)
+        _check(x.shape[1] - 1 == len(ts), "The coordinate dimension (coordinate_size - 1):", x.shape[1] - 1,
+               " must match the size of tensor stride:", list(ts))
+        lib = _lib.load()
+        dev = x.device
+        n, ncol = int(x.shape[0]), int(x.shape[1])
+        q = torch.empty((max(n, 1), ncol), dtype=torch.int32, device=dev)
+        with _on(dev):
+            _lib.check(lib.me_field_quantize_f32(_ptr(x), n, ncol, (ctypes.c_int32 * len(ts))(*ts), _ptr(q),
+                                                 _stream(dev)))
+        cmap, unique_map, inverse_map = _insert(q[:n], ts)
+        key = self._register(ts, cmap, string_id)
+        self._field_maps[(self._k(field_key), key)] = (unique_map, inverse_map)
+        return CoordinateMapKey(list(key[0]), key[1]), (unique_map, inverse_map)
+
+    def field_to_sparse_map(self, field_key, sparse_key):
+        """(sparse rows, field rows), int64, of the field points whose voxel is in `sparse_key`, in field row order
+        (me_field_lookup).  Cached; get_field_to_sparse_map returns (field rows, sparse rows) for such a pair, so that
+        its second tensor is the sparse row of each point when every point hits."""
+        fk, sk = self._k(field_key), self._k(sparse_key)
+        x = self._field(field_key)
+        smap = self._get(sparse_key)
+        _check(x.shape[1] == len(sk[0]) + 1, "The coordinate dimension mismatch.")
+        cached = self._field_lookups.get((fk, sk))
+        if cached is not None:
+            return cached
+        lib = _lib.load()
+        dev = x.device
+        n, ncol = int(x.shape[0]), int(x.shape[1])
+        srow = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        frow = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        ws = _workspace(lib.me_field_lookup_workspace_bytes(n), dev)
+        n_hit = ctypes.c_int64(0)
+        with _on(dev):
+            _lib.check(lib.me_field_lookup_f32(_ptr(x), n, ncol, (ctypes.c_int32 * len(sk[0]))(*sk[0]), _ptr(smap.table),
+                                               smap.capacity, _ptr(smap.coords), _ptr(srow), _ptr(frow),
+                                               ctypes.byref(n_hit), _ptr(ws), ws.numel(), _stream(dev)))
+        h = int(n_hit.value)
+        srow, frow = srow[:h].long(), frow[:h].long()
+        self._field_lookups[(fk, sk)] = (srow, frow)
+        return srow, frow
+
+    def exists_field_to_sparse(self, field_key, sparse_key):
+        k = (self._k(field_key), self._k(sparse_key))
+        return k in self._field_maps or k in self._field_lookups
+
+    def get_field_to_sparse_map(self, field_key, sparse_key):
+        """(unique_index, inverse_mapping) of a pair made by field_to_sparse_insert_and_map; for a pair made only by
+        field_to_sparse_map, (field rows, sparse rows) — the second is the sparse row of each point when every point
+        hits.  The maps of the two calls are kept apart: neither overwrites the other."""
+        k = (self._k(field_key), self._k(sparse_key))
+        if k in self._field_maps:
+            return self._field_maps[k]
+        _check(k in self._field_lookups, "Field To Sparse Map doesn't exist")
+        srow, frow = self._field_lookups[k]
+        return frow, srow
+
+    def field_to_sparse_keys(self, field_key):
+        """sparse keys with a map from this field, in key order (the native host's std::map order)"""
+        fk = self._k(field_key)
+        keys = sorted({sk for (f, sk) in list(self._field_maps) + list(self._field_lookups) if f == fk})
+        return [CoordinateMapKey(list(sk[0]), sk[1]) for sk in keys]
+
+    def _interpolation_map(self, in_key, samples):
+        """-> (in_map int32, out_map int32, weights (samples' dtype), rowptr int32 [N + 1]: the entries of sample p)"""
+        smap = self._get(in_key)
+        ts = self._k(in_key)[0]
+        _check(isinstance(samples, torch.Tensor) and samples.dim() == 2 and samples.shape[1] == len(ts) + 1,
+               "samples must be [N, D+1]")
+        _check(samples.is_cuda, "samples must be on the GPU (the MI355X path has no CPU map)")
+        _check(samples.dtype in (torch.float32, torch.float64), "samples must be float32 or float64, got",
+               samples.dtype)
+        x = samples.detach().contiguous()
+        lib = _lib.load()
+        dev = x.device
+        n, ncol = int(x.shape[0]), int(x.shape[1])
+        cap = max(n << (ncol - 1), 1)
+        in_map = torch.empty(cap, dtype=torch.int32, device=dev)
+        out_map = torch.empty(cap, dtype=torch.int32, device=dev)
+        w = torch.empty(cap, dtype=x.dtype, device=dev)
+        rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        ws = _workspace(lib.me_field_interp_workspace_bytes(n, ncol), dev)
+        nnz = ctypes.c_int64(0)
+        fn = lib.me_field_interp_map_f64 if x.dtype == torch.float64 else lib.me_field_interp_map_f32
+        with _on(dev):
+            _lib.check(fn(_ptr(x), n, ncol, (ctypes.c_int32 * len(ts))(*ts), _ptr(smap.table), smap.capacity,
+                          _ptr(smap.coords), _ptr(in_map), _ptr(out_map), _ptr(w), _ptr(rowptr), ctypes.byref(nnz),
+                          _ptr(ws), ws.numel(), _stream(dev)))
+        e = int(nnz.value)
+        return in_map[:e], out_map[:e], w[:e], rowptr
+
+    def interpolation_map_weight(self, samples, in_key):
+        """src/coordinate_map_gpu.cu:1977-2065 -> [in_map, out_map, weights]: trilinear corners of every sample present
+        in `in_key`, ordered by (sample, corner); int32 maps, weights in the samples' dtype."""
+        in_map, out_map, w, _ = self._interpolation_map(in_key, samples)
+        return [in_map, out_map, w]
 
     # ---- origin map (one row per batch index) --------------------------------------------------
     def origin(self):
@@ -2189,6 +2320,116 @@ def ChannelwiseConvolutionBackwardGPU(in_feat, grad_out_feat, kernel, kernel_siz
             1 if need_grad_in else 0, _ptr(grad_in), _ptr(grad_kernel), _ptr(grad_bias), _ptr(ws), ws.numel(),
             _stream(dev))))
     return grad_in, grad_kernel, grad_bias
+
+
+# ------------------------------------------------------------------------------------------------
+# tensor fields: one weighted CSR gather-sum carries every feature movement (csrc/field.hip); the reference's
+# InterpolationForwardGPU / InterpolationBackwardGPU (src/interpolation_gpu.cu) and coo_spmm / coo_spmm_average
+# (src/spmm.cu, pybind/extern.hpp:497-506) on cuSPARSE
+# ------------------------------------------------------------------------------------------------
+def _acc_dtype(feat):
+    """weights and scales of the gather: double for float64 features, fp32 for fp32 and bf16"""
+    return torch.float64 if feat.dtype == torch.float64 else torch.float32
+
+
+def CsrFromCooGPU(keys, n_rows, cols=None, vals=None):
+    """Rows of a COO matrix by `keys` (int32 in [0, n_rows)), stable in entry order -> (rowptr int32 [n_rows + 1],
+    cols int32 [nnz] (the entry indices when cols is None), vals [nnz] | None).  No reference counterpart (cuSPARSE
+    sorts inside coo_spmm)."""
+    _check(keys.is_cuda and keys.dim() == 1, "keys must be a 1-D CUDA tensor")
+    keys = keys.to(torch.int32).contiguous()
+    dev = keys.device
+    nnz, n_rows = int(keys.numel()), int(n_rows)
+    if cols is not None:
+        cols = cols.to(device=dev, dtype=torch.int32).contiguous()
+        _check(cols.numel() == nnz, "cols and keys must have one entry each")
+    if vals is not None:
+        vals = vals.contiguous()
+        _check(vals.is_cuda and vals.numel() == nnz and vals.element_size() in (4, 8), "vals: 4- or 8-byte values")
+    lib = _lib.load()
+    rowptr = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
+    cols_out = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+    vals_out = None if vals is None else torch.empty(max(nnz, 1), dtype=vals.dtype, device=dev)
+    ws = _workspace(lib.me_csr_from_coo_workspace_bytes(nnz), dev)
+    with _on(dev):
+        _lib.check(lib.me_csr_from_coo(_ptr(keys), _ptr(cols), _ptr(vals), 0 if vals is None else vals.element_size(),
+                                       nnz, n_rows, _ptr(rowptr), _ptr(cols_out), _ptr(vals_out), _ptr(ws), ws.numel(),
+                                       _stream(dev)))
+    return rowptr, cols_out[:nnz], (None if vals_out is None else vals_out[:nnz])
+
+
+def CsrGatherGPU(x, rowptr, col, w=None, scale=None):
+    """y[r] = scale[r] * sum_{e in row r} w[e] * x[col[e]] (me_csr_gather): rows = rowptr.numel() - 1; w and scale
+    (optional) in the accumulation dtype (double for float64 features, else fp32)."""
+    if not x.is_contiguous():
+        x = x.contiguous()
+    _check_feat("x", x)
+    _check(x.dim() == 2, "x must be 2-D")
+    a = _acc_dtype(x)
+    n_rows = int(rowptr.numel()) - 1
+    for name, t in (("w", w), ("scale", scale)):
+        _check(t is None or (t.is_cuda and t.dtype == a and t.is_contiguous()), name, "must be a contiguous", a,
+               "CUDA tensor")
+    c = int(x.shape[1])
+    y = torch.empty((n_rows, c), dtype=x.dtype, device=x.device)
+    if n_rows == 0 or c == 0:
+        return y.zero_()
+    lib = _lib.load()
+    fn = _by_dtype(lib, "csr_gather", x)
+    dev = x.device
+    with _on(dev):
+        _timed("csr_gather", dev, lambda: _lib.check(fn(_ptr(x), c, _ptr(rowptr), _ptr(col), _ptr(w), _ptr(scale),
+                                                         n_rows, _ptr(y), _stream(dev))))
+    return y
+
+
+def _check_index_range(name, t, n):
+    if t.numel():
+        lo, hi = int(t.min()), int(t.max())
+        _check(lo >= 0 and hi < n, name, "out of range [0,", n, "):", lo, hi)
+
+
+def InterpolationForwardGPU(in_feat, tfield, in_key, manager):
+    """src/interpolation_gpu.cu -> [out_feat, in_map, out_map, weights]: out[p] = sum over the present corners of
+    sample p of w * in_feat[corner row]; samples without a present corner give zero rows."""
+    in_map, out_map, w, rowptr = manager._interpolation_map(in_key, tfield)
+    _check(in_feat.shape[0] == manager.size(in_key), "Invalid in_feat size", in_feat.shape[0])
+    out = CsrGatherGPU(in_feat, rowptr, in_map, w.to(_acc_dtype(in_feat)))
+    return [out, in_map, out_map, w]
+
+
+def InterpolationBackwardGPU(grad_out_feat, in_map, out_map, weights, in_key, manager):
+    """grad_in[r] = sum over the entries with in_map == r, in entry order, of w * grad_out[out_map] (CSR by in_map)."""
+    n_in = manager.size(in_key)
+    rowptr, cols, w = CsrFromCooGPU(in_map, n_in, out_map, weights.to(_acc_dtype(grad_out_feat)))
+    return CsrGatherGPU(grad_out_feat, rowptr, cols, w)
+
+
+def coo_spmm_int32(rows, cols, vals, dim_i, dim_j, mat2, spmm_algorithm_id=1, is_sorted=False):
+    """out [dim_i, C] = A @ mat2 for A = COO(rows, cols, vals) of shape [dim_i, dim_j] (src/spmm.cu); sums in entry
+    order per row, no atomics."""
+    _check(mat2.dim() == 2 and mat2.shape[0] == dim_j, "mat2 must be [dim_j, C]")
+    _check(rows.numel() == cols.numel() == vals.numel(), "rows, cols and vals must have one entry each")
+    _check_index_range("rows", rows, int(dim_i))
+    _check_index_range("cols", cols, int(dim_j))
+    rowptr, c, v = CsrFromCooGPU(rows, dim_i, cols, vals.to(_acc_dtype(mat2)))
+    return CsrGatherGPU(mat2, rowptr, c, v)
+
+
+def coo_spmm_average_int32(rows, cols, dim_i, dim_j, mat2, spmm_algorithm_id=1):
+    """A @ mat2 with A[i, j] = 1 / (entries of row i) (src/spmm.cu coo_spmm_average) -> [out, rows, cols, vals] in row
+    order (the CSR the product ran on; vals = 1 / count per entry)."""
+    _check(mat2.dim() == 2 and mat2.shape[0] == dim_j, "mat2 must be [dim_j, C]")
+    _check(rows.numel() == cols.numel(), "rows and cols must have one entry each")
+    _check_index_range("rows", rows, int(dim_i))
+    _check_index_range("cols", cols, int(dim_j))
+    rowptr, c, _ = CsrFromCooGPU(rows, dim_i, cols)
+    count = (rowptr[1:] - rowptr[:-1]).to(_acc_dtype(mat2))
+    scale = torch.where(count > 0, 1.0 / count.clamp_min(1), torch.zeros_like(count))
+    out = CsrGatherGPU(mat2, rowptr, c, None, scale)
+    row_of = torch.repeat_interleave(torch.arange(int(dim_i), dtype=torch.int32, device=rowptr.device),
+                                     (rowptr[1:] - rowptr[:-1]).long())
+    return [out, row_of, c, scale[row_of.long()]]
 
 
 _GLOBAL_SUM = (PoolingMode.GLOBAL_SUM_POOLING_DEFAULT, PoolingMode.GLOBAL_SUM_POOLING_KERNEL,

@@ -192,6 +192,36 @@ class CoordinateManager:
         """one int64 [2, n_i] tensor per input key: (its rows, rows of the union map created under out_key)"""
         return self._manager.union_map(in_keys, out_key)
 
+    # ---- tensor fields (MinkowskiCoordinateManager.py:181-215, pybind/extern.hpp:780-805) -------------------------------
+    def insert_field(self, coordinates, tensor_stride=1, string_id=""):
+        """-> CoordinateMapKey of a field of continuous coordinates (kept as fp32, as in the reference)"""
+        return self._manager.insert_field(coordinates, convert_to_int_list(tensor_stride, self.D), string_id)
+
+    def field_to_sparse_insert_and_map(self, field_map_key, sparse_tensor_stride, sparse_tensor_string_id=""):
+        """-> (sparse key, (unique_index, inverse_mapping)): the field quantised at the stride and inserted"""
+        return self._manager.field_to_sparse_insert_and_map(
+            field_map_key, convert_to_int_list(sparse_tensor_stride, self.D), sparse_tensor_string_id)
+
+    def field_to_sparse_map(self, field_map_key, sparse_map_key):
+        """-> (sparse rows, field rows), int64, of the points whose voxel is in the sparse map, in field order"""
+        return self._manager.field_to_sparse_map(field_map_key, sparse_map_key)
+
+    def exists_field_to_sparse(self, field_map_key, sparse_map_key):
+        return self._manager.exists_field_to_sparse(field_map_key, sparse_map_key)
+
+    def get_field_to_sparse_map(self, field_map_key, sparse_map_key):
+        return self._manager.get_field_to_sparse_map(field_map_key, sparse_map_key)
+
+    def field_to_sparse_keys(self, field_map_key):
+        return self._manager.field_to_sparse_keys(field_map_key)
+
+    def get_coordinate_field(self, field_map_key):
+        return self._manager.get_coordinate_field(field_map_key)
+
+    def interpolation_map_weight(self, key, samples):
+        """-> [in_map, out_map, weights]: trilinear corners of the samples present in `key`, by (sample, corner)"""
+        return self._manager.interpolation_map_weight(samples, key)
+
     def get_unique_coordinate_map_key(self, tensor_stride):
         ts = convert_to_int_list(tensor_stride, self.D)
         sid = self._manager.get_random_string_id(ts, "")

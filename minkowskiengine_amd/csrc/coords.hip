@@ -1328,6 +1328,56 @@ __global__ __launch_bounds__(256) void k_bbox(const int32_t *__restrict__ coords
   }
 }
 
+__global__ __launch_bounds__(256) void k_iota_copy(const uint32_t *__restrict__ keys, int64_t n,
+                                                  uint32_t *__restrict__ sorted, uint32_t *__restrict__ order) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  sorted[i] = keys[i];
+  order[i] = (uint32_t)i;
+}
+
+// Stable argsort of uint32 keys by their low `bits` bits with the radix passes above (csr_from_coo of field.hip):
+// sorted_keys[i] = keys[order[i]].  Workspace: radix_argsort_workspace_bytes(n).
+int64_t radix_argsort_workspace_bytes(int64_t n) {
+  const int64_t m = n < 1 ? 1 : n, nb = ceil_div(m, kRsTile);
+  return 2 * align_up(m * 4, 256) + align_up(256 * nb * 4, 256) + 256 + scan_workspace_bytes(256 * nb);
+}
+int radix_argsort_u32(const uint32_t *keys, int64_t n, int bits, uint32_t *sorted_keys, uint32_t *order, void *ws,
+                      int64_t ws_bytes, hipStream_t stream) {
+  ME_CHECK(ws_bytes >= radix_argsort_workspace_bytes(n), "workspace too small");
+  if (n <= 0) return 0;
+  const int64_t nb = ceil_div(n, kRsTile), asz = align_up(n * 4, 256);
+  char *p = reinterpret_cast<char *>(ws);
+  uint32_t *tk = reinterpret_cast<uint32_t *>(p), *tv = reinterpret_cast<uint32_t *>(p + asz);
+  uint32_t *hist = reinterpret_cast<uint32_t *>(p + 2 * asz);
+  uint32_t *hist_total = reinterpret_cast<uint32_t *>(p + 2 * asz + align_up(256 * nb * 4, 256));
+  void *scan_ws = p + 2 * asz + align_up(256 * nb * 4, 256) + 256;
+  const int passes = (bits + 7) / 8;
+  if (passes == 0) {
+    hipLaunchKernelGGL(k_iota_copy, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream, keys, n, sorted_keys, order);
+    ME_LAUNCH_CHECK();
+    return 0;
+  }
+  // ping-pong so that the last pass lands in (sorted_keys, order): pass p writes the outputs when passes - 1 - p is
+  // even, the temporaries otherwise (the first pass reads the caller's keys and takes the positions as values)
+  uint32_t *bk[2] = {sorted_keys, tk}, *bv[2] = {order, tv};
+  const uint32_t *kin = keys;
+  const uint32_t *vin = nullptr;
+  for (int pass = 0; pass < passes; ++pass) {
+    const int dst = ((passes - 1 - pass) % 2 == 0) ? 0 : 1;
+    hipLaunchKernelGGL(k_rs_hist<uint32_t>, dim3((unsigned)nb), dim3(256), 0, stream, kin, n, 8 * pass, nb, hist);
+    ME_LAUNCH_CHECK();
+    if (int rc = exclusive_scan_u32(hist, hist, 256 * nb, hist_total, scan_ws, scan_workspace_bytes(256 * nb), stream))
+      return rc;
+    hipLaunchKernelGGL(k_rs_scatter<uint32_t>, dim3((unsigned)nb), dim3(64), 0, stream, kin, vin, n, 8 * pass, nb, hist,
+                       bk[dst], bv[dst]);
+    ME_LAUNCH_CHECK();
+    kin = bk[dst];
+    vin = bv[dst];
+  }
+  return 0;
+}
+
 }  // namespace me
 
 // =================================================================================================
@@ -1337,7 +1387,7 @@ using namespace me;
 
 extern "C" {
 
-int me_version(void) { return 170; }   // 100 * major + 10 * minor: see the changelog in include/me_amd.h
+int me_version(void) { return 180; }   // 100 * major + 10 * minor: see the changelog in include/me_amd.h
 const char *me_last_error(void) { return g_last_error; }
 
 int64_t me_region_volume(const me_region *rg) {
@@ -2159,11 +2209,11 @@ extern "C" {
 void me_preload_conv(void); void me_preload_conv_bf16(void); void me_preload_conv_bf16_ws(void); void me_preload_conv_f32x3(void);
 void me_preload_conv_halo(void); void me_preload_coords(void); void me_preload_norm(void); void me_preload_pack(void);
 void me_preload_f64(void); void me_preload_pool(void); void me_preload_conv_stem(void); void me_preload_conv_rowwise(void);
-void me_preload_conv_channelwise(void);
+void me_preload_conv_channelwise(void); void me_preload_field(void);
 int me_preload(void) {
   me_preload_coords(); me_preload_conv(); me_preload_conv_bf16(); me_preload_conv_bf16_ws(); me_preload_conv_f32x3();
   me_preload_conv_halo(); me_preload_conv_stem(); me_preload_conv_rowwise(); me_preload_norm(); me_preload_pack(); me_preload_pool(); me_preload_f64();
-  me_preload_conv_channelwise();
+  me_preload_conv_channelwise(); me_preload_field();
   ME_HIP(hipGetLastError());
   return 0;
 }

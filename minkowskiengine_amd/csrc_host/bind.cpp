@@ -4,6 +4,7 @@
 // MinkowskiConvolution.py:42-121; this is where its per-layer host time goes).
 #include <torch/csrc/autograd/custom_function.h>
 
+#include <set>
 #include <sstream>
 
 #include "host.hpp"
@@ -235,6 +236,62 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            })
       .def("_origin_rows", [](CoordinateMapManager &s, const CoordinateMapKey *k) { return s.origin_rows(keyt(k)); })
       .def("get_coordinates", [](CoordinateMapManager &s, const CoordinateMapKey *k) { return s.get(keyt(k))->coords; })
+      // tensor fields (pybind/extern.hpp:780-805; field.cpp)
+      .def("insert_field",
+           [](CoordinateMapManager &s, const Tensor &coords, const ivec &ts, const std::string &sid) {
+             return new_key(s.insert_field(coords, ts, sid));
+           },
+           py::arg("coordinates"), py::arg("tensor_stride"), py::arg("string_id") = "",
+           py::return_value_policy::take_ownership)
+      .def("get_coordinate_field", [](CoordinateMapManager &s, const CoordinateMapKey *k) { return s.field(keyt(k)); })
+      .def("field_to_sparse_insert_and_map",
+           [](CoordinateMapManager &s, const CoordinateMapKey *fk, const ivec &ts, const std::string &sid) {
+             auto r = s.field_to_sparse_insert_and_map(keyt(fk), ts, sid);
+             return py::make_tuple(py::cast(new_key(std::get<0>(r)), py::return_value_policy::take_ownership),
+                                   py::make_tuple(std::get<1>(r), std::get<2>(r)));
+           },
+           py::arg("field_key"), py::arg("sparse_tensor_stride"), py::arg("string_id") = "")
+      .def("field_to_sparse_map",
+           [](CoordinateMapManager &s, const CoordinateMapKey *fk, const CoordinateMapKey *sk) {
+             auto r = s.field_to_sparse_map(keyt(fk), keyt(sk));
+             return py::make_tuple(r.first, r.second);
+           })
+      .def("exists_field_to_sparse",
+           [](CoordinateMapManager &s, const CoordinateMapKey *fk, const CoordinateMapKey *sk) {
+             const std::pair<KeyT, KeyT> k{keyt(fk), keyt(sk)};
+             return s.field_maps.count(k) != 0 || s.field_lookups.count(k) != 0;
+           })
+      .def("get_field_to_sparse_map",   // see backend.CoordinateMapManagerGPU_c10.get_field_to_sparse_map
+           [](CoordinateMapManager &s, const CoordinateMapKey *fk, const CoordinateMapKey *sk) {
+             const std::pair<KeyT, KeyT> k{keyt(fk), keyt(sk)};
+             auto it = s.field_maps.find(k);
+             if (it != s.field_maps.end()) return py::make_tuple(it->second.first, it->second.second);
+             auto jt = s.field_lookups.find(k);
+             check(jt != s.field_lookups.end(), "Field To Sparse Map doesn't exist");
+             return py::make_tuple(jt->second.second, jt->second.first);
+           })
+      .def("field_to_sparse_keys",   // in key order
+           [](CoordinateMapManager &s, const CoordinateMapKey *fk) {
+             const KeyT f = keyt(fk);
+             std::set<KeyT> keys;
+             for (const auto &kv : s.field_maps)
+               if (kv.first.first == f) keys.insert(kv.first.second);
+             for (const auto &kv : s.field_lookups)
+               if (kv.first.first == f) keys.insert(kv.first.second);
+             py::list out;
+             for (const KeyT &k : keys) out.append(py::cast(new_key(k), py::return_value_policy::take_ownership));
+             return out;
+           })
+      .def("_interpolation_map",
+           [](CoordinateMapManager &s, const CoordinateMapKey *k, const Tensor &samples) {
+             auto r = s.interpolation_map(keyt(k), samples);
+             return py::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r));
+           })
+      .def("interpolation_map_weight",   // (samples, key): the reference's argument order
+           [](CoordinateMapManager &s, const Tensor &samples, const CoordinateMapKey *k) {
+             auto r = s.interpolation_map(keyt(k), samples);
+             return std::vector<Tensor>{std::get<0>(r), std::get<1>(r), std::get<2>(r)};
+           })
       .def("size", [](CoordinateMapManager &s, const CoordinateMapKey *k) { return s.get(keyt(k))->n; })
       .def("get_random_string_id",
            [](CoordinateMapManager &s, const ivec &ts, const std::string &sid) {
@@ -405,6 +462,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("kernel"), py::arg("kernel_size"), py::arg("kernel_stride"),
         py::arg("kernel_dilation"), py::arg("region_type"), py::arg("offset"), py::arg("in_key"), py::arg("out_key"),
         py::arg("manager"), py::arg("need_grad_in") = true, py::arg("need_grad_bias") = true);
+  // tensor fields (field.cpp): the reference's InterpolationForwardGPU / InterpolationBackwardGPU and coo_spmm_int32 /
+  // coo_spmm_average_int32 (pybind/extern.hpp:497-506), plus the CSR building blocks the autograd functions cache
+  m.def("CsrFromCooGPU",
+        [](const Tensor &keys, int64_t n_rows, const py::object &cols, const py::object &vals) {
+          auto r = csr_from_coo(keys, n_rows, opt_tensor(cols), opt_tensor(vals));
+          return py::make_tuple(std::get<0>(r), std::get<1>(r), opt_out(std::get<2>(r)));
+        },
+        py::arg("keys"), py::arg("n_rows"), py::arg("cols") = py::none(), py::arg("vals") = py::none());
+  m.def("CsrGatherGPU",
+        [](const Tensor &x, const Tensor &rowptr, const Tensor &col, const py::object &w, const py::object &scale) {
+          return csr_gather(x, rowptr, col, opt_tensor(w), opt_tensor(scale));
+        },
+        py::arg("x"), py::arg("rowptr"), py::arg("col"), py::arg("w") = py::none(), py::arg("scale") = py::none());
+  m.def("InterpolationForwardGPU",
+        [](const Tensor &in_feat, const Tensor &tfield, const CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+          return interpolation_forward(in_feat, tfield, keyt(in_key), mgr);
+        });
+  m.def("InterpolationBackwardGPU",
+        [](const Tensor &grad_out, const Tensor &in_map, const Tensor &out_map, const Tensor &weights,
+           const CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+          return interpolation_backward(grad_out, in_map, out_map, weights, keyt(in_key), mgr);
+        });
+  m.def("coo_spmm_int32",
+        [](const Tensor &rows, const Tensor &cols, const Tensor &vals, int64_t dim_i, int64_t dim_j, const Tensor &mat2,
+           int64_t /*spmm_algorithm_id*/, bool /*is_sorted*/) { return coo_spmm(rows, cols, vals, dim_i, dim_j, mat2); },
+        py::arg("rows"), py::arg("cols"), py::arg("vals"), py::arg("dim_i"), py::arg("dim_j"), py::arg("mat2"),
+        py::arg("spmm_algorithm_id") = 1, py::arg("is_sorted") = false);
+  m.def("coo_spmm_average_int32",
+        [](const Tensor &rows, const Tensor &cols, int64_t dim_i, int64_t dim_j, const Tensor &mat2,
+           int64_t /*spmm_algorithm_id*/) { return coo_spmm_average(rows, cols, dim_i, dim_j, mat2); },
+        py::arg("rows"), py::arg("cols"), py::arg("dim_i"), py::arg("dim_j"), py::arg("mat2"),
+        py::arg("spmm_algorithm_id") = 1);
   m.def("GlobalPoolingForwardGPU",
         [](const Tensor &in_feat, const py::object &pooling_mode, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
            CoordinateMapManager *mgr) {

@@ -1,0 +1,219 @@
+// Tensor fields in the native host layer: the manager's field methods (src/coordinate_map_manager.cpp:200-350) and the
+// field operators over csrc/field.hip.  C++ twin of the tensor-field parts of backend.py: same C-ABI calls in the same
+// order, so both hosts give the same bits.
+#include "host.hpp"
+
+namespace meh {
+
+void preload_device(const c10::Device &dev);
+
+namespace {
+void check_feat_f(const char *name, const Tensor &t) {
+  check(t.is_contiguous(), std::string(name) + " must be contiguous");
+  check(t.is_cuda(), std::string(name) + " must be CUDA (ROCm) — the MI355X path has no CPU implementation");
+  check(t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kDouble,
+        std::string(name) + " must be float32, bfloat16 or float64");
+}
+at::ScalarType acc_type(const Tensor &feat) { return feat.scalar_type() == at::kDouble ? at::kDouble : at::kFloat; }
+at::TensorOptions i32(const c10::Device &dev) { return at::TensorOptions().dtype(at::kInt).device(dev); }
+void check_range(const char *name, const Tensor &t, int64_t n) {
+  if (t.numel() == 0) return;
+  const int64_t lo = t.min().item<int64_t>(), hi = t.max().item<int64_t>();
+  check(lo >= 0 && hi < n, std::string(name) + " out of range [0, " + std::to_string(n) + ")");
+}
+}  // namespace
+
+KeyT CoordinateMapManager::insert_field(const Tensor &coordinates, const ivec &tensor_stride,
+                                        const std::string &string_id) {
+  check(coordinates.dim() == 2, "coordinates must be 2-D");
+  check(coordinates.is_cuda(), "coordinates must be on the GPU (the MI355X path has no CPU map)");
+  check(coordinates.is_floating_point(), "field coordinates must be floating point");
+  check(coordinates.size(1) - 1 == (int64_t)tensor_stride.size(),
+        "The coordinate dimension (coordinate_size - 1) must match the size of tensor stride");
+  preload_device(coordinates.device());
+  KeyT key(tensor_stride, string_id);
+  for (int i = 0; fields.count(key); ++i) key = KeyT(tensor_stride, (string_id.empty() ? "" : string_id + "-") + "f" + std::to_string(i));
+  fields[key] = coordinates.detach().to(at::kFloat).contiguous();
+  return key;
+}
+
+const Tensor &CoordinateMapManager::field(const KeyT &k) const {
+  auto it = fields.find(k);
+  check(it != fields.end(), "coordinate field not found");
+  return it->second;
+}
+
+std::tuple<KeyT, Tensor, Tensor> CoordinateMapManager::field_to_sparse_insert_and_map(const KeyT &field_key,
+                                                                                     const ivec &ts,
+                                                                                     const std::string &string_id) {
+  const Tensor x = field(field_key);
+  check(x.size(1) - 1 == (int64_t)ts.size(),
+        "The coordinate dimension (coordinate_size - 1) must match the size of tensor stride");
+  const c10::Device dev = x.device();
+  const int64_t n = x.size(0);
+  const int ncol = (int)x.size(1);
+  Tensor q = at::empty({n > 0 ? n : 1, ncol}, i32(dev));
+  {
+    c10::DeviceGuard guard(dev);
+    me_ok(me_field_quantize_f32(ptr<float>(x), n, ncol, ts.data(), ptr<int32_t>(q), stream_of(dev)));
+  }
+  InsertResult r = insert_coords(q.narrow(0, 0, n), ts);
+  const KeyT key = register_map(ts, r.map, string_id);
+  field_maps[{field_key, key}] = {r.unique_map, r.inverse_map};
+  return {key, r.unique_map, r.inverse_map};
+}
+
+std::pair<Tensor, Tensor> CoordinateMapManager::field_to_sparse_map(const KeyT &field_key, const KeyT &sparse_key) {
+  const Tensor x = field(field_key);
+  auto smap = get(sparse_key);
+  check(x.size(1) == (int64_t)sparse_key.first.size() + 1, "The coordinate dimension mismatch.");
+  auto it = field_lookups.find({field_key, sparse_key});
+  if (it != field_lookups.end()) return it->second;
+  const c10::Device dev = x.device();
+  const int64_t n = x.size(0);
+  const int ncol = (int)x.size(1);
+  Tensor srow = at::empty({n > 0 ? n : 1}, i32(dev)), frow = at::empty({n > 0 ? n : 1}, i32(dev));
+  Tensor ws = workspace(me_field_lookup_workspace_bytes(n), dev);
+  int64_t n_hit = 0;
+  {
+    c10::DeviceGuard guard(dev);
+    me_ok(me_field_lookup_f32(ptr<float>(x), n, ncol, sparse_key.first.data(), ptr<uint64_t>(smap->table),
+                              smap->capacity, ptr<int32_t>(smap->coords), ptr<int32_t>(srow), ptr<int32_t>(frow), &n_hit,
+                              vptr(ws), ws.numel(), stream_of(dev)));
+  }
+  Tensor s64 = srow.narrow(0, 0, n_hit).to(at::kLong), f64 = frow.narrow(0, 0, n_hit).to(at::kLong);
+  field_lookups[{field_key, sparse_key}] = {s64, f64};
+  return {s64, f64};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> CoordinateMapManager::interpolation_map(const KeyT &in_key,
+                                                                                   const Tensor &samples) {
+  auto smap = get(in_key);
+  const ivec &ts = in_key.first;
+  check(samples.dim() == 2 && samples.size(1) == (int64_t)ts.size() + 1, "samples must be [N, D+1]");
+  check(samples.is_cuda(), "samples must be on the GPU (the MI355X path has no CPU map)");
+  check(samples.scalar_type() == at::kFloat || samples.scalar_type() == at::kDouble,
+        "samples must be float32 or float64");
+  const Tensor x = samples.detach().contiguous();
+  const c10::Device dev = x.device();
+  const int64_t n = x.size(0);
+  const int ncol = (int)x.size(1);
+  int64_t cap = n << (ncol - 1);
+  if (cap < 1) cap = 1;
+  Tensor in_map = at::empty({cap}, i32(dev)), out_map = at::empty({cap}, i32(dev));
+  Tensor w = at::empty({cap}, x.options());
+  Tensor rowptr = at::empty({n + 1}, i32(dev));
+  Tensor ws = workspace(me_field_interp_workspace_bytes(n, ncol), dev);
+  int64_t nnz = 0;
+  {
+    c10::DeviceGuard guard(dev);
+    if (x.scalar_type() == at::kDouble)
+      me_ok(me_field_interp_map_f64(ptr<double>(x), n, ncol, ts.data(), ptr<uint64_t>(smap->table), smap->capacity,
+                                    ptr<int32_t>(smap->coords), ptr<int32_t>(in_map), ptr<int32_t>(out_map),
+                                    ptr<double>(w), ptr<int32_t>(rowptr), &nnz, vptr(ws), ws.numel(), stream_of(dev)));
+    else
+      me_ok(me_field_interp_map_f32(ptr<float>(x), n, ncol, ts.data(), ptr<uint64_t>(smap->table), smap->capacity,
+                                    ptr<int32_t>(smap->coords), ptr<int32_t>(in_map), ptr<int32_t>(out_map),
+                                    ptr<float>(w), ptr<int32_t>(rowptr), &nnz, vptr(ws), ws.numel(), stream_of(dev)));
+  }
+  return {in_map.narrow(0, 0, nnz), out_map.narrow(0, 0, nnz), w.narrow(0, 0, nnz), rowptr};
+}
+
+// ---- operators ------------------------------------------------------------------------------------------------------
+std::tuple<Tensor, Tensor, Tensor> csr_from_coo(const Tensor &keys_, int64_t n_rows, const Tensor &cols_,
+                                                const Tensor &vals_) {
+  check(keys_.is_cuda() && keys_.dim() == 1, "keys must be a 1-D CUDA tensor");
+  const Tensor keys = keys_.to(at::kInt).contiguous();
+  const c10::Device dev = keys.device();
+  const int64_t nnz = keys.numel();
+  Tensor cols, vals;
+  if (cols_.defined()) {
+    cols = cols_.to(dev, at::kInt).contiguous();
+    check(cols.numel() == nnz, "cols and keys must have one entry each");
+  }
+  if (vals_.defined()) {
+    vals = vals_.contiguous();
+    check(vals.is_cuda() && vals.numel() == nnz && (vals.element_size() == 4 || vals.element_size() == 8),
+          "vals: 4- or 8-byte values");
+  }
+  Tensor rowptr = at::empty({n_rows + 1}, i32(dev));
+  Tensor cols_out = at::empty({nnz > 0 ? nnz : 1}, i32(dev));
+  Tensor vals_out = vals.defined() ? at::empty({nnz > 0 ? nnz : 1}, vals.options()) : Tensor();
+  Tensor ws = workspace(me_csr_from_coo_workspace_bytes(nnz), dev);
+  {
+    c10::DeviceGuard guard(dev);
+    me_ok(me_csr_from_coo(ptr<int32_t>(keys), ptr<int32_t>(cols), vptr(vals),
+                          vals.defined() ? (int32_t)vals.element_size() : 0, nnz, n_rows, ptr<int32_t>(rowptr),
+                          ptr<int32_t>(cols_out), vptr(vals_out), vptr(ws), ws.numel(), stream_of(dev)));
+  }
+  return {rowptr, cols_out.narrow(0, 0, nnz), vals_out.defined() ? vals_out.narrow(0, 0, nnz) : Tensor()};
+}
+
+Tensor csr_gather(Tensor x, const Tensor &rowptr, const Tensor &col, const Tensor &w, const Tensor &scale) {
+  x = x.contiguous();
+  check_feat_f("x", x);
+  check(x.dim() == 2, "x must be 2-D");
+  const at::ScalarType a = acc_type(x);
+  for (const Tensor *t : {&w, &scale})
+    check(!t->defined() || (t->is_cuda() && t->scalar_type() == a && t->is_contiguous()),
+          "weights and scales must be contiguous CUDA tensors of the accumulation dtype");
+  const int64_t n_rows = rowptr.numel() - 1;
+  const int c = (int)x.size(1);
+  Tensor y = at::empty({n_rows, (int64_t)c}, x.options());
+  if (n_rows == 0 || c == 0) return y.zero_();
+  const c10::Device dev = x.device();
+  c10::DeviceGuard guard(dev);
+  if (x.scalar_type() == at::kDouble)
+    me_ok(me_csr_gather_f64(ptr<double>(x), c, ptr<int32_t>(rowptr), ptr<int32_t>(col), ptr<double>(w),
+                            ptr<double>(scale), n_rows, ptr<double>(y), stream_of(dev)));
+  else if (x.scalar_type() == at::kBFloat16)
+    me_ok(me_csr_gather_bf16(ptr<uint16_t>(x), c, ptr<int32_t>(rowptr), ptr<int32_t>(col), ptr<float>(w),
+                             ptr<float>(scale), n_rows, ptr<uint16_t>(y), stream_of(dev)));
+  else
+    me_ok(me_csr_gather_f32(ptr<float>(x), c, ptr<int32_t>(rowptr), ptr<int32_t>(col), ptr<float>(w),
+                            ptr<float>(scale), n_rows, ptr<float>(y), stream_of(dev)));
+  return y;
+}
+
+std::vector<Tensor> interpolation_forward(const Tensor &in_feat, const Tensor &tfield, const KeyT &in_key,
+                                          CoordinateMapManager *mgr) {
+  auto r = mgr->interpolation_map(in_key, tfield);
+  check(in_feat.size(0) == mgr->get(in_key)->n, "Invalid in_feat size");
+  Tensor out = csr_gather(in_feat, std::get<3>(r), std::get<0>(r), std::get<2>(r).to(acc_type(in_feat)), Tensor());
+  return {out, std::get<0>(r), std::get<1>(r), std::get<2>(r)};
+}
+
+Tensor interpolation_backward(const Tensor &grad_out, const Tensor &in_map, const Tensor &out_map, const Tensor &weights,
+                              const KeyT &in_key, CoordinateMapManager *mgr) {
+  const int64_t n_in = mgr->get(in_key)->n;
+  auto t = csr_from_coo(in_map, n_in, out_map, weights.to(acc_type(grad_out)));
+  return csr_gather(grad_out, std::get<0>(t), std::get<1>(t), std::get<2>(t), Tensor());
+}
+
+Tensor coo_spmm(const Tensor &rows, const Tensor &cols, const Tensor &vals, int64_t dim_i, int64_t dim_j,
+                const Tensor &mat2) {
+  check(mat2.dim() == 2 && mat2.size(0) == dim_j, "mat2 must be [dim_j, C]");
+  check(rows.numel() == cols.numel() && rows.numel() == vals.numel(), "rows, cols and vals must have one entry each");
+  check_range("rows", rows, dim_i);
+  check_range("cols", cols, dim_j);
+  auto t = csr_from_coo(rows, dim_i, cols, vals.to(acc_type(mat2)));
+  return csr_gather(mat2, std::get<0>(t), std::get<1>(t), std::get<2>(t), Tensor());
+}
+
+std::vector<Tensor> coo_spmm_average(const Tensor &rows, const Tensor &cols, int64_t dim_i, int64_t dim_j,
+                                     const Tensor &mat2) {
+  check(mat2.dim() == 2 && mat2.size(0) == dim_j, "mat2 must be [dim_j, C]");
+  check(rows.numel() == cols.numel(), "rows and cols must have one entry each");
+  check_range("rows", rows, dim_i);
+  check_range("cols", cols, dim_j);
+  auto t = csr_from_coo(rows, dim_i, cols, Tensor());
+  const Tensor &rowptr = std::get<0>(t);
+  const Tensor cnt = rowptr.narrow(0, 1, dim_i) - rowptr.narrow(0, 0, dim_i);
+  const Tensor count = cnt.to(acc_type(mat2));
+  const Tensor scale = at::where(count.gt(0), 1.0 / count.clamp_min(1), at::zeros_like(count));
+  Tensor out = csr_gather(mat2, rowptr, std::get<1>(t), Tensor(), scale);
+  Tensor row_of = at::repeat_interleave(at::arange(dim_i, i32(rowptr.device())), cnt.to(at::kLong));
+  return {out, row_of, std::get<1>(t), scale.index({row_of.to(at::kLong)})};
+}
+
+}  // namespace meh

@@ -241,6 +241,12 @@ struct CoordinateMapManager {
   std::map<KeyT, Tensor> origin_rows_cache;
   std::map<std::pair<KeyT, KeyT>, Tensor> prune_rows;
   std::map<std::pair<KeyT, KeyT>, std::pair<Tensor, Tensor>> stride_maps;
+  // tensor fields (field.cpp): fp32 coordinates per field key (a namespace of its own, as in the reference) and the
+  // field -> sparse maps per (field key, sparse key): field_maps (unique_index, inverse_mapping) of
+  // field_to_sparse_insert_and_map, field_lookups (sparse rows, field rows) of field_to_sparse_map, kept apart
+  std::map<KeyT, Tensor> fields;
+  std::map<std::pair<KeyT, KeyT>, std::pair<Tensor, Tensor>> field_maps;
+  std::map<std::pair<KeyT, KeyT>, std::pair<Tensor, Tensor>> field_lookups;
 
   CoordinateMapManager(int algorithm_ = 0, int num_threads_ = 0) : algorithm(algorithm_), num_threads(num_threads_) {}
 
@@ -271,6 +277,14 @@ struct CoordinateMapManager {
   void log_request(const std::string &r) { recipe_log->push_back(r); }
   std::vector<Tensor> device_tensors();
   std::string repr() const;
+
+  KeyT insert_field(const Tensor &coordinates, const ivec &tensor_stride, const std::string &string_id);
+  const Tensor &field(const KeyT &k) const;
+  std::tuple<KeyT, Tensor, Tensor> field_to_sparse_insert_and_map(const KeyT &field_key, const ivec &tensor_stride,
+                                                                  const std::string &string_id);
+  std::pair<Tensor, Tensor> field_to_sparse_map(const KeyT &field_key, const KeyT &sparse_key);
+  // (in_map, out_map, weights, rowptr [N + 1] by sample)
+  std::tuple<Tensor, Tensor, Tensor, Tensor> interpolation_map(const KeyT &in_key, const Tensor &samples);
 };
 
 // ---- operators (ops.cpp) ----------------------------------------------------------------------------------------------
@@ -303,6 +317,17 @@ std::tuple<Tensor, Tensor, Tensor> channelwise_backward(const Tensor &in_feat, T
                                                         CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                                                         CoordinateMapManager *mgr, bool need_grad_in,
                                                         bool need_grad_bias);
+// tensor fields (field.cpp; twin of backend.CsrFromCooGPU / CsrGatherGPU / Interpolation*GPU / coo_spmm*)
+std::tuple<Tensor, Tensor, Tensor> csr_from_coo(const Tensor &keys, int64_t n_rows, const Tensor &cols, const Tensor &vals);
+Tensor csr_gather(Tensor x, const Tensor &rowptr, const Tensor &col, const Tensor &w, const Tensor &scale);
+std::vector<Tensor> interpolation_forward(const Tensor &in_feat, const Tensor &tfield, const KeyT &in_key,
+                                          CoordinateMapManager *mgr);
+Tensor interpolation_backward(const Tensor &grad_out, const Tensor &in_map, const Tensor &out_map, const Tensor &weights,
+                              const KeyT &in_key, CoordinateMapManager *mgr);
+Tensor coo_spmm(const Tensor &rows, const Tensor &cols, const Tensor &vals, int64_t dim_i, int64_t dim_j,
+                const Tensor &mat2);
+std::vector<Tensor> coo_spmm_average(const Tensor &rows, const Tensor &cols, int64_t dim_i, int64_t dim_j,
+                                     const Tensor &mat2);
 std::pair<Tensor, Tensor> global_pooling_forward(const Tensor &in_feat, int pooling_mode, CoordinateMapKey *in_key,
                                                  CoordinateMapKey *out_key, CoordinateMapManager *mgr);
 Tensor global_pooling_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &num_nonzero, int pooling_mode,

@@ -16,6 +16,10 @@ _FUSE_RESIDUAL = os.environ.get("ME_AMD_FUSE_RESIDUAL", "1") != "0"   # bn + res
 
 
 def _rewrap(x, feats):
+    """the same kind of tensor on the same coordinates: a TensorField input gives a TensorField on its field key (the
+    reference's MinkowskiNonlinearity.py does this), a SparseTensor a SparseTensor"""
+    if not isinstance(x, SparseTensor) and hasattr(x, "coordinate_field_map_key"):
+        return x._like(feats)
     return SparseTensor(feats, coordinate_map_key=x.coordinate_map_key, coordinate_manager=x._manager)
 
 
@@ -250,10 +254,17 @@ class MinkowskiLinear(nn.Module):
 
 
 def cat(*sparse_tensors):
-    """Concatenate the features of tensors that share one coordinate map (MinkowskiOps.py:141-158)."""
+    """Concatenate the features of tensors that share one coordinate map (MinkowskiOps.py:141-158): sparse tensors,
+    or tensor fields on one field key."""
     if len(sparse_tensors) == 1 and isinstance(sparse_tensors[0], (list, tuple)):
         sparse_tensors = tuple(sparse_tensors[0])
     first = sparse_tensors[0]
+    if not isinstance(first, SparseTensor) and hasattr(first, "coordinate_field_map_key"):
+        for s in sparse_tensors:
+            assert hasattr(s, "coordinate_field_map_key"), "Inputs must all be tensor fields."
+            assert s._manager is first._manager, "coordinate managers must match"
+            assert s.coordinate_field_map_key == first.coordinate_field_map_key, "cat needs a shared field key"
+        return _rewrap(first, torch.cat([s.F for s in sparse_tensors], dim=1))
     for s in sparse_tensors:
         assert isinstance(s, SparseTensor), "Inputs must be sparse tensors."
         assert s._manager is first._manager, "coordinate managers must match"

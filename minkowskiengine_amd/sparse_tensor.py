@@ -246,6 +246,52 @@ class SparseTensor:
     def __neg__(self):
         return SparseTensor(-self._F, coordinate_map_key=self.coordinate_map_key, coordinate_manager=self._manager)
 
+    # ---- back to the points (MinkowskiSparseTensor.py:541-720) ----------------------------------------------------------
+    def interpolate(self, X):
+        """Features at the points of the TensorField X: through the splat weights when this tensor is X.splat(),
+        trilinear interpolation otherwise."""
+        from .tensor_field import TensorField
+        from .sparse_matrix_functions import MinkowskiSPMMFunction
+        assert isinstance(X, TensorField)
+        if self.coordinate_map_key in X._splat:
+            tensor_map, field_map, weights, size = X._splat[self.coordinate_map_key]
+            size = torch.Size([size[1], size[0]])
+            features = MinkowskiSPMMFunction.apply(field_map, tensor_map, weights, size, self._F)
+        else:
+            features = self.features_at_coordinates(X.C)
+        return X._like(features)
+
+    def slice(self, X):
+        """One row per ORIGINAL point of X (a TensorField, or the SparseTensor whose coordinates were quantised), in
+        the original order: the features of the voxel each point fell in."""
+        from .tensor_field import TensorField, _gather_rows
+        if isinstance(X, TensorField):
+            key = self.coordinate_map_key
+            return X._like(_gather_rows(self._F, X.inverse_mapping(key), self._manager, lambda: X.voxel_csr(key)))
+        if isinstance(X, SparseTensor):
+            assert X.coordinate_map_key == self.coordinate_map_key, \
+                "Slice can only be applied on the same coordinates (coordinate_map_key)"
+            inv_map = X.inverse_mapping
+            return TensorField(_gather_rows(self._F, inv_map, self._manager), coordinates=self.C[inv_map].float(),
+                               coordinate_manager=self.coordinate_manager, quantization_mode=self.quantization_mode)
+        raise ValueError("Invalid input. The input must be an instance of TensorField or SparseTensor.")
+
+    def cat_slice(self, X):
+        """slice(X) with X's own features concatenated after the sliced ones"""
+        out = self.slice(X)
+        xf = X.F if not isinstance(X, SparseTensor) else X.F[X.inverse_mapping]   # one row per point
+        return out._like(torch.cat((out.F, xf), dim=1))
+
+    def features_at_coordinates(self, query_coordinates):
+        """Trilinear interpolation at continuous coordinates [N, D+1]; rows of queries without a present corner are
+        zeros."""
+        from .interpolation import MinkowskiInterpolationFunction
+        assert query_coordinates.is_floating_point(), "query coordinates must be float32 or float64"
+        assert query_coordinates.device == self.device, \
+            f"query coordinates device ({query_coordinates.device}) does not match the sparse tensor device ({self.device})."
+        return MinkowskiInterpolationFunction.apply(self._F, query_coordinates, self.coordinate_map_key,
+                                                    self.coordinate_manager)[0]
+
     @property
     def _batchwise_row_indices(self):
         batch = self.C[:, 0]

@@ -69,7 +69,9 @@ typedef struct me_region {
  *   1.7 (170)  round 7: channelwise (depthwise) convolution, forward and backward (me_cwconv_forward_*,
  *              me_cwconv_backward_workspace_bytes, me_cwconv_backward_*)
  *   1.8 (180)  round 8: tensor fields: quantisation, field -> sparse lookup and trilinear interpolation maps (me_field_*), stable
- *              CSR from COO and the weighted CSR gather-sum (me_csr_*) */
+ *              CSR from COO and the weighted CSR gather-sum (me_csr_*)
+ *   1.9 (190)  round 9: instance normalisation: per-instance statistics, apply and backward (me_inorm_workspace_bytes,
+ *              me_inorm_stats, me_inorm_apply, me_inorm_backward and their _f64 twins) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -833,6 +835,45 @@ int me_bn_backward_residual(const void *x_dev, const void *dy_dev, const void *y
                             int32_t c, const float *mean_dev, const float *rstd_dev, const float *gamma_dev,
                             const float *beta_dev, int32_t relu, void *dx_dev, void *dskip_dev, float *grad_gamma_dev,
                             float *grad_beta_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
+/* ---- instance normalisation over feature rows (MinkowskiInstanceNorm / MinkowskiStableInstanceNorm,
+ *      MinkowskiEngine/MinkowskiNormalization.py:194-399: there a chain of global poolings and broadcasts; here batch
+ *      norm's pipeline with the statistics segmented by the batch index of each row; csrc/instance_norm.hip, ABI 1.9) ----
+ * x / y / dy / dx: [n, c] row-major, fp32 (is_bf16 = 0) or bf16 (is_bf16 = 1: rows widened to fp32, one rounding at the
+ * store); batch_row: int32 [n], the instance (origin-map row) of every row, values in [0, n_batch), rows of an instance
+ * in ANY order; mean / rstd: fp32 [n_batch, c]; gamma / beta / grad_gamma / grad_beta: fp32 [c].
+ *   me_inorm_stats:    mean[b] and rstd[b] = 1 / sqrt(biased variance of instance b + eps) per channel.  Two-level
+ *                      reduction in a fixed order: per (chunk of rows, instance) count / mean / M2 from shifted sums,
+ *                      merged with Chan's formula; bitwise reproducible.  An instance without rows: mean = 0,
+ *                      rstd = 1 / sqrt(eps).
+ *   me_inorm_apply:    y[i] = (x[i] - mean[b_i]) * rstd[b_i] * gamma + beta          (gamma / beta may be NULL: 1 / 0)
+ *   me_inorm_backward: with xhat = (x - mean[b]) * rstd[b]: t1[b] = sum_{i in b} dy, t2[b] = sum_{i in b} dy * xhat,
+ *                      dx[i] = gamma * rstd[b_i] * (dy[i] - t1[b_i] / n_b - xhat[i] * t2[b_i] / n_b),
+ *                      grad_beta = sum_b t1[b], grad_gamma = sum_b t2[b] (ascending b).  gamma may be NULL (1); dx,
+ *                      grad_gamma and grad_beta may each be NULL (skipped).  No atomics on values: reproducible.
+ * workspace bytes for stats and backward (either precision): me_inorm_workspace_bytes(n, n_batch, c); about
+ * 8 * min(512, n / 4) * n_batch * c bytes of per-chunk partials.  The _f64 entry points are the same formulae in plain double (parameters and statistics
+ * double as well): the yardstick of gradcheck, not a hot path. */
+int64_t me_inorm_workspace_bytes(int64_t n, int32_t n_batch, int32_t c);
+int me_inorm_stats(const void *x_dev, int32_t is_bf16, const int32_t *batch_row_dev, int64_t n, int32_t n_batch,
+                   int32_t c, float eps, float *mean_dev, float *rstd_dev, void *workspace_dev,
+                   int64_t workspace_bytes, void *stream);
+int me_inorm_apply(const void *x_dev, int32_t is_bf16, const int32_t *batch_row_dev, int64_t n, int32_t n_batch,
+                   int32_t c, const float *mean_dev, const float *rstd_dev, const float *gamma_dev,
+                   const float *beta_dev, void *y_dev, void *stream);
+int me_inorm_backward(const void *x_dev, const void *dy_dev, int32_t is_bf16, const int32_t *batch_row_dev, int64_t n,
+                      int32_t n_batch, int32_t c, const float *mean_dev, const float *rstd_dev, const float *gamma_dev,
+                      void *dx_dev, float *grad_gamma_dev, float *grad_beta_dev, void *workspace_dev,
+                      int64_t workspace_bytes, void *stream);
+int me_inorm_stats_f64(const double *x_dev, const int32_t *batch_row_dev, int64_t n, int32_t n_batch, int32_t c,
+                       double eps, double *mean_dev, double *rstd_dev, void *stream);
+int me_inorm_apply_f64(const double *x_dev, const int32_t *batch_row_dev, int64_t n, int32_t n_batch, int32_t c,
+                       const double *mean_dev, const double *rstd_dev, const double *gamma_dev, const double *beta_dev,
+                       double *y_dev, void *stream);
+int me_inorm_backward_f64(const double *x_dev, const double *dy_dev, const int32_t *batch_row_dev, int64_t n,
+                          int32_t n_batch, int32_t c, const double *mean_dev, const double *rstd_dev,
+                          const double *gamma_dev, double *dx_dev, double *grad_gamma_dev, double *grad_beta_dev,
+                          void *workspace_dev, int64_t workspace_bytes, void *stream);
 
 /* Plain VALU + atomics versions on the pair lists (debug cross-check only; never the default).
  * out / grad_in / grad_w must be zero-filled by the caller. */

@@ -130,6 +130,15 @@ SIGNATURES = {
     "me_bn_apply_residual": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "me_bn_backward_residual": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp,
                                                c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_inorm_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "me_inorm_stats": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_inorm_apply": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "me_inorm_backward": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                         c_vp, c_i64, c_vp]),
+    "me_inorm_stats_f64": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.c_double, c_vp, c_vp, c_vp]),
+    "me_inorm_apply_f64": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "me_inorm_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                             c_vp, c_i64, c_vp]),
     "me_coords_expand_region": (ctypes.c_int, [c_vp, c_i64, c_i32, _P_REGION, _P_I32, c_vp, c_vp, c_vp]),
     "me_coords_quantize_labels": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "me_segment_sum_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),

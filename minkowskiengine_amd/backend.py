@@ -2749,6 +2749,106 @@ def bn_backward(x, dy, mean, rstd, gamma, beta=None, relu=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# instance normalisation (csrc/instance_norm.hip; the reference's MinkowskiInstanceNorm is a chain of its global
+# pooling and broadcast operators, MinkowskiNormalization.py:194-399, and has no native operator of its own)
+# ------------------------------------------------------------------------------------------------
+def _inorm_param_dtype(feat):
+    """bf16 features take the fp32 parameters and statistics; fp32 / f64 take their own dtype"""
+    return torch.float64 if feat.dtype == torch.float64 else torch.float32
+
+
+def _inorm_check_vec(name, t, in_feat, numel):
+    want = _inorm_param_dtype(in_feat)
+    _check(t is None or (t.is_cuda and t.is_contiguous() and t.dtype == want and t.numel() == numel and
+                         t.device == in_feat.device),
+           name, "must be a contiguous", want, "GPU tensor of", numel, "values on the device of the features")
+
+
+def _inorm_prepare(in_feat, in_key, glob_key, manager):
+    """-> (batch_row int32 [n], n_batch); an unset glob_key becomes the origin map, as GlobalPoolingForwardGPU does"""
+    _check_feat("in_feat", in_feat)
+    _check(in_feat.dim() == 2 and in_feat.shape[1] > 0, "Invalid in_feat shape:", tuple(in_feat.shape))
+    _check(manager.exists(in_key), "coordinate map not found")
+    _check(in_feat.shape[0] == manager.size(in_key), "Invalid in_feat size", in_feat.shape[0], "!=",
+           manager.size(in_key))
+    if not glob_key.is_key_set():
+        glob_key.set_key(manager.origin().get_key())
+    rows = manager._origin_rows(in_key)
+    return rows, manager.size(glob_key)
+
+
+def InstanceNormForwardGPU(in_feat, weight, bias, eps, in_key, glob_key, manager):
+    """-> (out_feat, mean, rstd): out[i] = (x[i] - mean[b_i]) * rstd[b_i] * weight + bias with the mean and the biased
+    variance of every instance (batch index) per channel, rstd = 1 / sqrt(var + eps); mean / rstd: [batch, C] in the
+    parameter dtype (fp32 for fp32 and bf16 features, float64 for float64).  weight / bias: C values or None.  The
+    reference has no native operator of this name; it follows the package's `<Op>{Forward,Backward}GPU` convention."""
+    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
+    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
+    _inorm_check_vec("weight", weight, in_feat, c)
+    _inorm_check_vec("bias", bias, in_feat, c)
+    lib = _lib.load()
+    dev = in_feat.device
+    pd = _inorm_param_dtype(in_feat)
+    mean = torch.empty((n_batch, c), dtype=pd, device=dev)
+    rstd = torch.empty((n_batch, c), dtype=pd, device=dev)
+    out = torch.empty_like(in_feat)
+    with _on(dev):
+        if in_feat.dtype == torch.float64:
+            _lib.check(lib.me_inorm_stats_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, float(eps), _ptr(mean),
+                                              _ptr(rstd), _stream(dev)))
+            _lib.check(lib.me_inorm_apply_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, _ptr(mean), _ptr(rstd),
+                                              _ptr(weight), _ptr(bias), _ptr(out), _stream(dev)))
+        else:
+            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
+            ws = _workspace(int(lib.me_inorm_workspace_bytes(n, n_batch, c)), dev)
+            _timed("inorm_forward", dev, lambda: (
+                _lib.check(lib.me_inorm_stats(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, float(eps), _ptr(mean),
+                                              _ptr(rstd), _ptr(ws), ws.numel(), _stream(dev))),
+                _lib.check(lib.me_inorm_apply(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, _ptr(mean), _ptr(rstd),
+                                              _ptr(weight), _ptr(bias), _ptr(out), _stream(dev)))))
+    return out, mean, rstd
+
+
+def InstanceNormBackwardGPU(in_feat, grad_out_feat, weight, mean, rstd, in_key, glob_key, manager, need_grad_in=True,
+                            need_grad_weight=True, need_grad_bias=True):
+    """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None) from the statistics of the forward pass; the
+    parameter gradients have the parameter dtype (fp32 for bf16 features)."""
+    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
+    if not grad_out_feat.is_contiguous():
+        grad_out_feat = grad_out_feat.contiguous()
+    _check_feat("grad_out_feat", grad_out_feat)
+    if grad_out_feat.dtype != in_feat.dtype:
+        grad_out_feat = grad_out_feat.to(in_feat.dtype)
+    _check(tuple(grad_out_feat.shape) == tuple(in_feat.shape), "grad_out_feat must have the shape of in_feat")
+    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
+    _inorm_check_vec("weight", weight, in_feat, c)
+    _check(mean is not None and rstd is not None, "instance norm backward needs mean and rstd")
+    _inorm_check_vec("mean", mean, in_feat, n_batch * c)
+    _inorm_check_vec("rstd", rstd, in_feat, n_batch * c)
+    lib = _lib.load()
+    dev = in_feat.device
+    pd = _inorm_param_dtype(in_feat)
+    grad_in = torch.empty_like(in_feat) if need_grad_in else None
+    grad_weight = torch.empty(c, dtype=pd, device=dev) if need_grad_weight else None
+    grad_bias = torch.empty(c, dtype=pd, device=dev) if need_grad_bias else None
+    if n == 0:
+        return grad_in, (None if grad_weight is None else grad_weight.zero_()), \
+            (None if grad_bias is None else grad_bias.zero_())
+    ws = _workspace(int(lib.me_inorm_workspace_bytes(n, n_batch, c)), dev)
+    with _on(dev):
+        if in_feat.dtype == torch.float64:
+            _lib.check(lib.me_inorm_backward_f64(_ptr(in_feat), _ptr(grad_out_feat), _ptr(rows), n, n_batch, c, _ptr(mean),
+                                                 _ptr(rstd), _ptr(weight), _ptr(grad_in), _ptr(grad_weight),
+                                                 _ptr(grad_bias), _ptr(ws), ws.numel(), _stream(dev)))
+        else:
+            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
+            _timed("inorm_backward", dev, lambda: _lib.check(lib.me_inorm_backward(
+                _ptr(in_feat), _ptr(grad_out_feat), bf, _ptr(rows), n, n_batch, c, _ptr(mean), _ptr(rstd), _ptr(weight),
+                _ptr(grad_in), _ptr(grad_weight), _ptr(grad_bias), _ptr(ws), ws.numel(), _stream(dev))))
+    return grad_in, grad_weight, grad_bias
+
+
+# ------------------------------------------------------------------------------------------------
 # pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu)
 # ------------------------------------------------------------------------------------------------
 def PruningForwardGPU(in_feat, keep, in_key, out_key, manager):

@@ -1,0 +1,113 @@
+// Shared by the normalisation translation units (norm.hip: batch norm over all rows, instance_norm.hip: the same
+// arithmetic segmented by the batch index of each row): row pieces widened to fp32, the chunking of the two-level
+// reductions and the fixed-order LDS combine of the row lanes.
+#pragma once
+#include "conv_common.hpp"
+
+namespace me {
+
+constexpr int kBnMaxChunks = 512;
+constexpr int kBnRowsPerThread = 8;   // fully unrolled: 8 rows in flight per thread (2 or 4 with more workgroups
+                                      // measured 2x slower: the loads in flight per thread matter, not the grid size)
+
+template <typename T, int V>
+struct Row {
+  float v[V];
+};
+template <typename T, int V>
+__device__ __forceinline__ Row<T, V> load_row(const T *p) {
+  Row<T, V> r;
+  if constexpr (V == 1) {
+    r.v[0] = (float)p[0];
+  } else {
+    typedef T tvec __attribute__((ext_vector_type(V)));
+    const tvec t = *reinterpret_cast<const tvec *>(p);
+#pragma unroll
+    for (int j = 0; j < V; ++j) r.v[j] = (float)t[j];
+  }
+  return r;
+}
+template <typename T, int V>
+__device__ __forceinline__ void store_row(T *p, const Row<T, V> &r) {
+  if constexpr (V == 1) {
+    p[0] = (T)r.v[0];
+  } else {
+    typedef T tvec __attribute__((ext_vector_type(V)));
+    tvec t;
+#pragma unroll
+    for (int j = 0; j < V; ++j) t[j] = (T)r.v[j];
+    *reinterpret_cast<tvec *>(p) = t;
+  }
+}
+
+// rows of chunk g: [g * n / G, (g + 1) * n / G)
+__device__ __forceinline__ int64_t chunk_begin(int64_t g, int64_t n, int64_t G) { return g * n / G; }
+
+// LDS of the partial kernels: s_red[R][2c] (one row of 2c sums per row lane) | s_out[2c] | s_tmp[256] | s_shift[c]
+__host__ __device__ constexpr size_t bn_partial_lds_bytes(int c, int row_lanes) {
+  return ((size_t)row_lanes * 2 * c + 2 * c + 256 + c) * sizeof(float);
+}
+
+// s_out[q] = sum over the row lanes l (ascending) of s_red[l * 2c + q], by the whole workgroup: with fewer than 256
+// values (c < 128) G = 256 / 2c threads share a value — contiguous lane ranges, their G partial sums added in range
+// order — instead of c / V threads walking all R lanes (R = 32 - 64 on the narrow layers: 500 - 1000 serial LDS reads
+// on a handful of threads were 5 - 10 us of every partial kernel).  A fixed order: bitwise reproducible.
+__device__ __forceinline__ void bn_reduce_lanes(const float *__restrict__ s_red, float *__restrict__ s_out,
+                                                float *__restrict__ s_tmp, int c, int R) {
+  const int NV = 2 * c, tid = (int)threadIdx.x, NT = (int)blockDim.x;
+  __syncthreads();
+  if (NV * 2 > NT) {
+    for (int q = tid; q < NV; q += NT) {
+      float a = 0.f;
+      for (int l = 0; l < R; ++l) a += s_red[l * NV + q];
+      s_out[q] = a;
+    }
+  } else {
+    const int G = NT / NV, g = tid / NV, q = tid % NV;
+    if (g < G) {
+      float a = 0.f;
+      for (int l = g * R / G; l < (g + 1) * R / G; ++l) a += s_red[l * NV + q];
+      s_tmp[g * NV + q] = a;
+    }
+    __syncthreads();
+    if (tid < NV) {
+      float a = 0.f;
+      for (int gg = 0; gg < G; ++gg) a += s_tmp[gg * NV + tid];
+      s_out[tid] = a;
+    }
+  }
+  __syncthreads();
+}
+
+// per-channel parameters of V consecutive channels (gamma / beta may be NULL: 1 / 0 — one uniform branch, not one
+// per element)
+template <int V>
+__device__ __forceinline__ void load_affine(const float *__restrict__ gamma, const float *__restrict__ beta, int ch0,
+                                            float (&ga)[V], float (&be)[V]) {
+  if (gamma != nullptr) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) ga[j] = gamma[ch0 + j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j) ga[j] = 1.f;
+  }
+  if (beta != nullptr) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) be[j] = beta[ch0 + j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j) be[j] = 0.f;
+  }
+}
+
+// chunks of a reduction over n rows by workgroups of `row_lanes` row lanes: one batch of rows in flight per thread
+// where that fills the chip (rows_per_thread * row_lanes rows per chunk), more per thread beyond kBnMaxChunks chunks
+static int bn_chunks(int64_t n, int row_lanes, int rows_per_thread) {
+  int64_t g = ceil_div(n, (int64_t)row_lanes * rows_per_thread);
+  if (g > kBnMaxChunks) g = kBnMaxChunks;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+static int bn_chunks_max(int64_t n) { return bn_chunks(n, 1, kBnRowsPerThread / 2); }   // workspace bound
+
+}  // namespace me

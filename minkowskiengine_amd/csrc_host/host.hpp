@@ -317,6 +317,14 @@ std::tuple<Tensor, Tensor, Tensor> channelwise_backward(const Tensor &in_feat, T
                                                         CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                                                         CoordinateMapManager *mgr, bool need_grad_in,
                                                         bool need_grad_bias);
+// instance normalisation (csrc/instance_norm.hip; twin of backend.InstanceNorm{Forward,Backward}GPU)
+std::tuple<Tensor, Tensor, Tensor> instance_norm_forward(const Tensor &in_feat, const Tensor &weight, const Tensor &bias,
+                                                         double eps, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
+                                                         CoordinateMapManager *mgr);
+std::tuple<Tensor, Tensor, Tensor> instance_norm_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &weight,
+                                                          const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key,
+                                                          CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
+                                                          bool need_grad_in, bool need_grad_weight, bool need_grad_bias);
 // tensor fields (field.cpp; twin of backend.CsrFromCooGPU / CsrGatherGPU / Interpolation*GPU / coo_spmm*)
 std::tuple<Tensor, Tensor, Tensor> csr_from_coo(const Tensor &keys, int64_t n_rows, const Tensor &cols, const Tensor &vals);
 Tensor csr_gather(Tensor x, const Tensor &rowptr, const Tensor &col, const Tensor &w, const Tensor &scale);

@@ -972,6 +972,106 @@ std::pair<Tensor, Tensor> broadcast_backward(const Tensor &in_feat, const Tensor
   return {grad_in, grad_glob};
 }
 
+// ---- instance normalisation (csrc/instance_norm.hip; twin of backend.InstanceNorm{Forward,Backward}GPU) ------------------------
+static void inorm_check_vec(const char *name, const Tensor &t, const Tensor &in_feat, int64_t numel) {
+  const at::ScalarType want = in_feat.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
+  check(!t.defined() || (t.is_cuda() && t.is_contiguous() && t.scalar_type() == want && t.numel() == numel &&
+                         t.device() == in_feat.device()),
+        std::string(name) + " must be a contiguous GPU tensor of the parameter dtype (float64 for float64 features, float32 "
+                            "otherwise) with one value per (instance and) channel, on the device of the features");
+}
+
+// -> (batch_row, n_batch); an unset glob_key becomes the origin map, as global_pooling_forward does
+static std::pair<Tensor, int64_t> inorm_prepare(const Tensor &in_feat, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
+                                                CoordinateMapManager *mgr) {
+  check_feat("in_feat", in_feat);
+  check(in_feat.dim() == 2 && in_feat.size(1) > 0, "Invalid in_feat shape");
+  const KeyT &ik = in_key->get();
+  check(mgr->exists(ik), "coordinate map not found");
+  check(in_feat.size(0) == mgr->get(ik)->n, "Invalid in_feat size");
+  if (!glob_key->key_set) {
+    KeyT ok = mgr->origin();
+    glob_key->set_key(ok.first, ok.second);
+  }
+  Tensor rows = mgr->origin_rows(ik);
+  return {rows, mgr->get(glob_key->get())->n};
+}
+
+std::tuple<Tensor, Tensor, Tensor> instance_norm_forward(const Tensor &in_feat, const Tensor &weight, const Tensor &bias,
+                                                         double eps, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
+                                                         CoordinateMapManager *mgr) {
+  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
+  const Tensor &rows = pr.first;
+  const int n_batch = (int)pr.second;
+  const int64_t n = in_feat.size(0);
+  const int c = (int)in_feat.size(1);
+  inorm_check_vec("weight", weight, in_feat, c);
+  inorm_check_vec("bias", bias, in_feat, c);
+  const c10::Device dev = in_feat.device();
+  const bool f64 = in_feat.scalar_type() == at::kDouble;
+  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  Tensor mean = at::empty({n_batch, c}, popt), rstd = at::empty({n_batch, c}, popt);
+  Tensor out = at::empty_like(in_feat);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_inorm_stats_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, eps, ptr<double>(mean),
+                             ptr<double>(rstd), stream_of(dev)));
+    me_ok(me_inorm_apply_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, ptr<double>(mean), ptr<double>(rstd),
+                             ptr<double>(weight), ptr<double>(bias), ptr<double>(out), stream_of(dev)));
+    return {out, mean, rstd};
+  }
+  const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
+  Tensor ws = workspace(me_inorm_workspace_bytes(n, n_batch, c), dev);
+  me_ok(me_inorm_stats(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, (float)eps, ptr<float>(mean),
+                       ptr<float>(rstd), vptr(ws), ws.numel(), stream_of(dev)));
+  me_ok(me_inorm_apply(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, ptr<float>(mean), ptr<float>(rstd),
+                       ptr<float>(weight), ptr<float>(bias), out.data_ptr(), stream_of(dev)));
+  return {out, mean, rstd};
+}
+
+std::tuple<Tensor, Tensor, Tensor> instance_norm_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &weight,
+                                                          const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key,
+                                                          CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
+                                                          bool need_grad_in, bool need_grad_weight, bool need_grad_bias) {
+  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
+  const Tensor &rows = pr.first;
+  const int n_batch = (int)pr.second;
+  grad_out = grad_out.contiguous();
+  check_feat("grad_out_feat", grad_out);
+  if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
+  check(grad_out.sizes() == in_feat.sizes(), "grad_out_feat must have the shape of in_feat");
+  const int64_t n = in_feat.size(0);
+  const int c = (int)in_feat.size(1);
+  inorm_check_vec("weight", weight, in_feat, c);
+  check(mean.defined() && rstd.defined(), "instance norm backward needs mean and rstd");
+  inorm_check_vec("mean", mean, in_feat, (int64_t)n_batch * c);
+  inorm_check_vec("rstd", rstd, in_feat, (int64_t)n_batch * c);
+  const c10::Device dev = in_feat.device();
+  const bool f64 = in_feat.scalar_type() == at::kDouble;
+  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  Tensor grad_in = need_grad_in ? at::empty_like(in_feat) : Tensor();
+  Tensor grad_weight = need_grad_weight ? at::empty({c}, popt) : Tensor();
+  Tensor grad_bias = need_grad_bias ? at::empty({c}, popt) : Tensor();
+  if (n == 0) {
+    if (grad_weight.defined()) grad_weight.zero_();
+    if (grad_bias.defined()) grad_bias.zero_();
+    return {grad_in, grad_weight, grad_bias};
+  }
+  Tensor ws = workspace(me_inorm_workspace_bytes(n, n_batch, c), dev);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_inorm_backward_f64(ptr<double>(in_feat), ptr<double>(grad_out), ptr<int32_t>(rows), n, n_batch, c,
+                                ptr<double>(mean), ptr<double>(rstd), ptr<double>(weight), ptr<double>(grad_in),
+                                ptr<double>(grad_weight), ptr<double>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
+  } else {
+    const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
+    me_ok(me_inorm_backward(in_feat.data_ptr(), grad_out.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c,
+                            ptr<float>(mean), ptr<float>(rstd), ptr<float>(weight), vptr(grad_in), ptr<float>(grad_weight),
+                            ptr<float>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
+  }
+  return {grad_in, grad_weight, grad_bias};
+}
+
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------
 Tensor pruning_forward(const Tensor &in_feat, const Tensor &keep, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr) {

@@ -1,0 +1,125 @@
+"""MinkowskiInstanceNorm, MinkowskiStableInstanceNorm and MinkowskiInstanceNormFunction (reference:
+MinkowskiEngine/MinkowskiNormalization.py:194-399).  The reference normalises every instance (batch index) with a chain
+of its global average pooling and broadcast operators plus torch element-wise ops; here one operator pair,
+`InstanceNorm{Forward,Backward}GPU`, resolved in the backend by name as the other operators are, runs the kernels of
+csrc/instance_norm.hip: per instance b and channel
+
+    out[i] = (x[i] - mean[b_i]) / sqrt(var[b_i] + eps) * weight + bias        (var: biased)
+
+in three passes over the feature matrix forward and five backward."""
+import torch
+from torch.autograd import Function
+from torch.nn import Parameter
+
+from . import host as _host
+from .backend import PoolingMode
+from .common import get_minkowski_function
+from .convolution import MinkowskiModuleBase
+from .sparse_tensor import SparseTensor
+
+
+class _InstanceNormAffineFunction(Function):
+    """The fused form the modules use: normalisation and affine map in one operator.  weight / bias: (1, C) or (C,)
+    tensors of the parameter dtype (fp32 for fp32 and bf16 features, float64 for float64) or None."""
+
+    @staticmethod
+    def forward(ctx, in_feat, weight, bias, eps, in_coords_key, glob_coords_key, coords_manager):
+        if glob_coords_key is None:
+            glob_coords_key = _host.key_like(in_coords_key)
+        in_feat = in_feat.contiguous()
+        w = None if weight is None else weight.detach().reshape(-1).contiguous()
+        b = None if bias is None else bias.detach().reshape(-1).contiguous()
+        fw_fn = get_minkowski_function("InstanceNormForward", in_feat, in_coords_key)
+        out, mean, rstd = fw_fn(in_feat, w, b, float(eps), in_coords_key, glob_coords_key, coords_manager._manager)
+        ctx.save_for_backward(in_feat, w, mean, rstd)
+        ctx.misc = (in_coords_key, glob_coords_key, coords_manager,
+                    None if weight is None else weight.shape, None if bias is None else bias.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        in_feat, w, mean, rstd = ctx.saved_tensors
+        in_key, glob_key, coords_manager, w_shape, b_shape = ctx.misc
+        need_w = w_shape is not None and ctx.needs_input_grad[1]
+        need_b = b_shape is not None and ctx.needs_input_grad[2]
+        bw_fn = get_minkowski_function("InstanceNormBackward", grad_out, in_key)
+        grad_in, grad_w, grad_b = bw_fn(in_feat, grad_out.contiguous(), w, mean, rstd, in_key, glob_key,
+                                        coords_manager._manager, need_grad_in=ctx.needs_input_grad[0],
+                                        need_grad_weight=need_w, need_grad_bias=need_b)
+        return (grad_in, grad_w.view(w_shape) if need_w else None, grad_b.view(b_shape) if need_b else None,
+                None, None, None, None)
+
+
+class MinkowskiInstanceNormFunction(Function):
+    """The reference's Function (MinkowskiNormalization.py:194-310): the normalised features WITHOUT an affine map,
+    eps = 1e-8.  `gpooling_mode` is accepted for compatibility; every global average mode computes the same mean."""
+
+    @staticmethod
+    def forward(ctx, in_feat, in_coords_key, glob_coords_key=None, coords_manager=None,
+                gpooling_mode=PoolingMode.GLOBAL_AVG_POOLING_KERNEL):
+        if glob_coords_key is None:
+            glob_coords_key = _host.key_like(in_coords_key)
+        in_feat = in_feat.contiguous()
+        fw_fn = get_minkowski_function("InstanceNormForward", in_feat, in_coords_key)
+        out, mean, rstd = fw_fn(in_feat, None, None, 1e-8, in_coords_key, glob_coords_key, coords_manager._manager)
+        ctx.save_for_backward(in_feat, mean, rstd)
+        ctx.saved_vars = (in_coords_key, glob_coords_key, coords_manager, gpooling_mode)
+        return out
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        in_feat, mean, rstd = ctx.saved_tensors
+        in_key, glob_key, coords_manager, _ = ctx.saved_vars
+        bw_fn = get_minkowski_function("InstanceNormBackward", out_grad, in_key)
+        grad_in, _, _ = bw_fn(in_feat, out_grad.contiguous(), None, mean, rstd, in_key, glob_key,
+                              coords_manager._manager, need_grad_in=True, need_grad_weight=False, need_grad_bias=False)
+        return grad_in, None, None, None, None
+
+
+class _InstanceNormBase(MinkowskiModuleBase):
+    eps = 1e-8
+
+    def __init__(self, num_features):
+        super().__init__()
+        self.num_features = num_features
+        self.weight = Parameter(torch.ones(1, num_features, dtype=torch.float32))
+        self.bias = Parameter(torch.zeros(1, num_features, dtype=torch.float32))
+        self.reset_parameters()
+
+    def __repr__(self):
+        return self.__class__.__name__ + f"(nchannels={self.num_features})"
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            self.weight.fill_(1)
+            self.bias.zero_()
+
+    def forward(self, input):
+        assert isinstance(input, SparseTensor)
+        assert input.shape[1] == self.num_features, f"Channel size mismatch {self.num_features} != {input.shape[1]}"
+        output = _InstanceNormAffineFunction.apply(input.F, self.weight, self.bias, self.eps, input.coordinate_map_key,
+                                                   None, input._manager)
+        return SparseTensor(output, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
+
+
+class MinkowskiInstanceNorm(_InstanceNormBase):
+    r"""Instance normalisation of a sparse tensor: every batch index is normalised per channel with its own mean and
+    biased variance (eps = 1e-8 inside the square root), then `* weight + bias` (MinkowskiNormalization.py:361-399).
+    Parameters `weight`, `bias` of shape (1, num_features), fp32, as in the reference, so its state dicts load strictly.
+    bf16 features run with the fp32 parameters and give bf16 outputs; float64 features need a `.double()` module."""
+
+    def __init__(self, num_features):
+        super().__init__(num_features)
+        self.inst_norm = MinkowskiInstanceNormFunction       # (the reference keeps the Function as an attribute)
+
+
+class MinkowskiStableInstanceNorm(_InstanceNormBase):
+    r"""The formula MinkowskiNormalization.py:313-358 spells out — centre, biased variance, `1 / sqrt(var + 1e-6)`,
+    affine — on the same kernels as MinkowskiInstanceNorm.  (The reference's forward reads `x.coords_key` /
+    `x.coords_man`, attributes its 0.5.4 tensors no longer have; its five pooling / broadcast sub-modules have no
+    parameters or buffers, so a reference state dict loads strictly without them.)"""
+    eps = 1e-6
+
+    def __init__(self, num_features):
+        super().__init__(num_features)
+        self.eps = 1e-6

@@ -71,7 +71,9 @@ typedef struct me_region {
  *   1.8 (180)  round 8: tensor fields: quantisation, field -> sparse lookup and trilinear interpolation maps (me_field_*), stable
  *              CSR from COO and the weighted CSR gather-sum (me_csr_*)
  *   1.9 (190)  round 9: instance normalisation: per-instance statistics, apply and backward (me_inorm_workspace_bytes,
- *              me_inorm_stats, me_inorm_apply, me_inorm_backward and their _f64 twins) */
+ *              me_inorm_stats, me_inorm_apply, me_inorm_backward and their _f64 twins)
+ *   1.10 (200) round 10: dense <-> sparse conversion: cell indices, the row grid, the two movers, occupied cells and all
+ *              cells of a box (me_dense_*) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -874,6 +876,51 @@ int me_inorm_backward_f64(const double *x_dev, const double *dy_dev, const int32
                           int32_t n_batch, int32_t c, const double *mean_dev, const double *rstd_dev,
                           const double *gamma_dev, double *dx_dev, double *grad_gamma_dev, double *grad_beta_dev,
                           void *workspace_dev, int64_t workspace_bytes, void *stream);
+
+/* ---- dense <-> sparse conversion (SparseTensor.dense, ME.to_sparse, ME.to_sparse_all, ME.dense_coordinates:
+ *      MinkowskiEngine/MinkowskiSparseTensor.py:460-557 and MinkowskiOps.py:246-348, torch indexing there;
+ *      csrc/dense.hip, ABI 1.10) ----
+ * Feature rows [n, c] row-major <-> a strided box [outer, c, inner].  A cell is (o, i), its linear index o * inner + i =
+ * its linear index over shape = (B, X1, .., XD), wherever the channel axis sits in the layout (outer = B, inner = X1*..*XD
+ * for BCX..X; outer = B*X1*..*XD, inner = 1 for channels-last).  Values move as raw words of elem_bytes = 2 (bf16), 4
+ * (fp32) or 8 (float64): copies, no arithmetic, no atomics, bitwise reproducible.  min_coord / divisor / shape are HOST
+ * arrays of D / D / D+1 values.
+ *   me_dense_cell_index:  cell[r] = linear index of (b, floor((x_k - min_coord_k) / divisor_k)) in `shape`, or -1 — and
+ *                         *flag_dev = 1 (0 otherwise) — when row r lies outside the box on EITHER side.  No movers ever
+ *                         write such a row.  min_coord / divisor NULL: 0 / 1.
+ *   me_dense_grid:        grid[cell] = row of the cell, -1 = empty (int32 [n_cells]); unique coordinates: race-free.
+ *   me_dense_rows_to_box: EVERY element of the box is written exactly once, zeros included.  ME_DENSE_CELL_STATIONARY:
+ *                         tiles of 64 consecutive cells gather their rows (contiguous c-vectors) through the grid,
+ *                         transpose through LDS and store coalesced along `inner` (128-bit stores when inner % 4 == 0 and
+ *                         the box is 16-byte aligned); needs grid_dev.  ME_DENSE_ROW_STATIONARY: zero fill, then one wave per
+ *                         row scatters its elements `inner` apart; needs cell_dev.  policy 0: cell-stationary when the grid
+ *                         is given.  cell_dev == grid_dev == NULL: identity (row r is cell r, n == outer * inner).
+ *   me_dense_box_to_rows: rows[r] = the c elements of cell[r]; the same two shapes backwards (cell-stationary reads the box
+ *                         coalesced and pays for empty cells; it writes only rows the grid names; row-stationary writes
+ *                         zeros into a row whose cell is -1).
+ *   me_dense_policy:      host only; the cheaper shape for n rows in n_cells cells (to_box: 1 rows -> box, 0 box -> rows):
+ *                         bytes moved, weighted by the measured rates of the two shapes (csrc/dense.hip).
+ *   me_dense_occupied_count (SYNC) / me_dense_occupied_fill: cells with a channel that is not +-0 (= `abs(x).sum(ch) != 0`,
+ *                         a NaN keeps its cell), in ASCENDING cell order (torch.where's order): count first, then, into
+ *                         buffers of that many rows, coords [n, D+1] (batch first) and cell [n].  The workspace carries the
+ *                         wave masks from count to fill.  Fewer than 2^31 cells.
+ *   me_dense_all_coords:  coords [n_cells, D+1] of every cell in cell order (ME.dense_coordinates on the device). */
+#define ME_DENSE_ROW_STATIONARY 1
+#define ME_DENSE_CELL_STATIONARY 2
+int me_dense_policy(int64_t n, int64_t n_cells, int32_t c, int32_t elem_bytes, int32_t to_box);
+int me_dense_cell_index(const int32_t *coords_dev, int64_t n, int32_t ncol, const int32_t *min_coord,
+                        const int32_t *divisor, const int64_t *shape, int64_t *cell_dev, int32_t *flag_dev, void *stream);
+int me_dense_grid(const int64_t *cell_dev, int64_t n, int64_t n_cells, int32_t *grid_dev, void *stream);
+int me_dense_rows_to_box(const void *rows_dev, int32_t elem_bytes, const int64_t *cell_dev, const int32_t *grid_dev,
+                         int64_t n, int64_t outer, int32_t c, int64_t inner, void *box_dev, int32_t policy, void *stream);
+int me_dense_box_to_rows(const void *box_dev, int32_t elem_bytes, const int64_t *cell_dev, const int32_t *grid_dev,
+                         int64_t n, int64_t outer, int32_t c, int64_t inner, void *rows_dev, int32_t policy, void *stream);
+int64_t me_dense_occupied_workspace_bytes(int64_t n_cells);
+int me_dense_occupied_count(const void *box_dev, int32_t elem_bytes, int64_t outer, int32_t c, int64_t inner,
+                            void *workspace_dev, int64_t workspace_bytes, int64_t *n_occupied, void *stream);
+int me_dense_occupied_fill(const void *workspace_dev, int64_t workspace_bytes, int32_t ncol, const int64_t *shape,
+                           int32_t *coords_dev, int64_t *cell_dev, void *stream);
+int me_dense_all_coords(int32_t ncol, const int64_t *shape, int32_t *coords_dev, void *stream);
 
 /* Plain VALU + atomics versions on the pair lists (debug cross-check only; never the default).
  * out / grad_in / grad_w must be zero-filled by the caller. */

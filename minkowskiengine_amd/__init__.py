@@ -45,6 +45,11 @@ from .sparse_tensor import (  # noqa: F401
     SparseTensor, SparseTensorOperationMode, SparseTensorQuantizationMode, clear_global_coordinate_manager,
     global_coordinate_manager, set_global_coordinate_manager, set_sparse_tensor_operation_mode,
     sparse_tensor_operation_mode)
+from .ops import (  # noqa: F401
+    MinkowskiStackCat, MinkowskiStackMean, MinkowskiStackSum, MinkowskiStackVar, MinkowskiToDenseFunction,
+    MinkowskiToDenseTensor, MinkowskiToFeature, MinkowskiToSparseFunction, MinkowskiToSparseTensor, dense_coordinates,
+    mean, to_sparse, to_sparse_all, var)
+from .ops import _sum as sum  # noqa: F401,A001  (ME.sum, as the reference exports it)
 from . import utils  # noqa: F401
 
 

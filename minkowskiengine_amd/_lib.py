@@ -139,6 +139,15 @@ SIGNATURES = {
     "me_inorm_apply_f64": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "me_inorm_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                              c_vp, c_i64, c_vp]),
+    "me_dense_policy": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, c_i32]),
+    "me_dense_cell_index": (ctypes.c_int, [c_vp, c_i64, c_i32, _P_I32, _P_I32, _P_I64, c_vp, c_vp, c_vp]),
+    "me_dense_grid": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "me_dense_rows_to_box": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp]),
+    "me_dense_box_to_rows": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp]),
+    "me_dense_occupied_workspace_bytes": (c_i64, [c_i64]),
+    "me_dense_occupied_count": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_i64, _P_I64, c_vp]),
+    "me_dense_occupied_fill": (ctypes.c_int, [c_vp, c_i64, c_i32, _P_I64, c_vp, c_vp, c_vp]),
+    "me_dense_all_coords": (ctypes.c_int, [c_i32, _P_I64, c_vp, c_vp]),
     "me_coords_expand_region": (ctypes.c_int, [c_vp, c_i64, c_i32, _P_REGION, _P_I32, c_vp, c_vp, c_vp]),
     "me_coords_quantize_labels": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "me_segment_sum_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),

@@ -2873,3 +2873,149 @@ def PruningBackwardGPU(grad_out_feat, in_key, out_key, manager):
                           device=grad_out_feat.device)
     grad_in.index_copy_(0, rows.long(), grad_out_feat)
     return grad_in
+
+
+# ------------------------------------------------------------------------------------------------
+# dense <-> sparse conversion (csrc/dense.hip; the reference does these with torch indexing in Python:
+# MinkowskiSparseTensor.py:460-557, MinkowskiOps.py:246-348, so the operator names below are this package's own)
+# ------------------------------------------------------------------------------------------------
+DENSE_AUTO, DENSE_ROW_STATIONARY, DENSE_CELL_STATIONARY = 0, 1, 2
+
+
+def _i32s(values):
+    return (ctypes.c_int32 * max(len(values), 1))(*[int(v) for v in values])
+
+
+def _i64s(values):
+    return (ctypes.c_int64 * max(len(values), 1))(*[int(v) for v in values])
+
+
+def _cells_of(shape):
+    n = 1
+    for s in shape:
+        n *= int(s)
+    return n
+
+
+def _check_index(name, t, dtype, dev, numel=None):
+    _check(t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.device == dev and
+                         (numel is None or t.numel() == numel)),
+           name, "must be a contiguous", dtype, "GPU tensor on the device of the features" +
+           ("" if numel is None else f" with {numel} values"))
+
+
+def DensePolicy(n, n_cells, c, elem_bytes, to_box):
+    """DENSE_ROW_STATIONARY | DENSE_CELL_STATIONARY: the cheaper mover by bytes moved (me_dense_policy; host only)"""
+    return int(_lib.load().me_dense_policy(int(n), int(n_cells), int(c), int(elem_bytes), 1 if to_box else 0))
+
+
+def DenseCellIndexGPU(coordinates, min_coordinate, divisor, shape, want_grid=True):
+    """-> (cell int64 [N], grid int32 [cells] | None, flag int32 [1]) of int32 coordinates [N, D+1] in the box
+    `shape` = (B, X1, .., XD) whose origin is `min_coordinate`, coordinates floor-divided by `divisor` (D host ints
+    each).  A row outside the box, on either side, has cell -1 and raises the flag; nothing here synchronises."""
+    _check(isinstance(coordinates, torch.Tensor) and coordinates.dim() == 2 and coordinates.is_cuda and
+           coordinates.dtype == torch.int32 and coordinates.is_contiguous(),
+           "coordinates must be a contiguous int32 [N, D+1] GPU tensor")
+    n, ncol = int(coordinates.shape[0]), int(coordinates.shape[1])
+    _check(len(min_coordinate) == ncol - 1 and len(divisor) == ncol - 1 and len(shape) == ncol,
+           "min_coordinate / divisor / shape must have D / D / D+1 values")
+    lib = _lib.load()
+    dev = coordinates.device
+    n_cells = _cells_of(shape)
+    cell = torch.empty(n, dtype=torch.int64, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    grid = torch.empty(n_cells, dtype=torch.int32, device=dev) if want_grid else None
+    with _on(dev):
+        _lib.check(lib.me_dense_cell_index(_ptr(coordinates), n, ncol, _i32s(min_coordinate), _i32s(divisor),
+                                           _i64s(shape), _ptr(cell), _ptr(flag), _stream(dev)))
+        if want_grid:
+            _lib.check(lib.me_dense_grid(_ptr(cell), n, n_cells, _ptr(grid), _stream(dev)))
+    return cell, grid, flag
+
+
+def DenseGridGPU(cell, n_cells):
+    """-> grid int32 [n_cells]: the row of every cell, -1 = empty"""
+    _check(cell.is_cuda and cell.dtype == torch.int64 and cell.is_contiguous() and cell.dim() == 1,
+           "cell must be a contiguous int64 GPU vector")
+    dev = cell.device
+    grid = torch.empty(int(n_cells), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().me_dense_grid(_ptr(cell), cell.numel(), int(n_cells), _ptr(grid), _stream(dev)))
+    return grid
+
+
+def DenseRowsToBoxGPU(rows, cell, grid, outer, inner, policy=DENSE_AUTO):
+    """-> box [outer, C, inner] with box[o, :, i] = rows[r] for cell[r] = o * inner + i and zeros elsewhere; every element
+    written once.  cell = grid = None: row r is cell r."""
+    _check_feat("rows", rows)
+    _check(rows.dim() == 2 and rows.shape[1] > 0, "Invalid rows shape:", tuple(rows.shape))
+    dev = rows.device
+    n, c = int(rows.shape[0]), int(rows.shape[1])
+    outer, inner = int(outer), int(inner)
+    _check_index("cell", cell, torch.int64, dev, n)
+    _check_index("grid", grid, torch.int32, dev, outer * inner)
+    box = torch.empty((outer, c, inner), dtype=rows.dtype, device=dev)
+    with _on(dev):
+        _timed("dense_rows_to_box", dev, lambda: _lib.check(_lib.load().me_dense_rows_to_box(
+            _ptr(rows), rows.element_size(), _ptr(cell), _ptr(grid), n, outer, c, inner, _ptr(box), int(policy),
+            _stream(dev))))
+    return box
+
+
+def DenseBoxToRowsGPU(box, cell, grid, n, outer, inner, policy=DENSE_AUTO):
+    """-> rows [n, C] with rows[r] = box[o, :, i] of cell[r] = o * inner + i; `box`: contiguous, outer * C * inner
+    elements.  cell = grid = None: row r is cell r (n = outer * inner)."""
+    _check_feat("box", box)
+    dev = box.device
+    n, outer, inner = int(n), int(outer), int(inner)
+    _check(outer * inner > 0 and box.numel() % (outer * inner) == 0 and box.numel() > 0,
+           "box must hold outer * C * inner elements")
+    c = box.numel() // (outer * inner)
+    _check_index("cell", cell, torch.int64, dev, n)
+    _check_index("grid", grid, torch.int32, dev, outer * inner)
+    rows = torch.empty((n, c), dtype=box.dtype, device=dev)
+    with _on(dev):
+        _timed("dense_box_to_rows", dev, lambda: _lib.check(_lib.load().me_dense_box_to_rows(
+            _ptr(box), box.element_size(), _ptr(cell), _ptr(grid), n, outer, c, inner, _ptr(rows), int(policy),
+            _stream(dev))))
+    return rows
+
+
+def DenseOccupiedGPU(box, outer, inner, shape):
+    """-> (coordinates int32 [n, D+1], cell int64 [n]) of the cells of `box` ([outer, C, inner], contiguous) with a
+    channel that is not +-0, in ascending cell order over `shape` = (B, X1, .., XD).  One synchronisation (n)."""
+    _check_feat("box", box)
+    dev = box.device
+    outer, inner = int(outer), int(inner)
+    n_cells = outer * inner
+    _check(n_cells == _cells_of(shape), "shape must have outer * inner cells")
+    ncol = len(shape)
+    if n_cells == 0 or box.numel() == 0:
+        return (torch.empty((0, ncol), dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev))
+    _check(box.numel() % n_cells == 0, "box must hold outer * C * inner elements")
+    c = box.numel() // n_cells
+    lib = _lib.load()
+    ws = _workspace(int(lib.me_dense_occupied_workspace_bytes(n_cells)), dev)
+    count = ctypes.c_int64(0)
+    with _on(dev):
+        _lib.check(lib.me_dense_occupied_count(_ptr(box), box.element_size(), outer, c, inner, _ptr(ws), ws.numel(),
+                                               ctypes.byref(count), _stream(dev)))
+        n = int(count.value)
+        coords = torch.empty((n, ncol), dtype=torch.int32, device=dev)
+        cell = torch.empty(n, dtype=torch.int64, device=dev)
+        if n > 0:
+            _lib.check(lib.me_dense_occupied_fill(_ptr(ws), ws.numel(), ncol, _i64s(shape), _ptr(coords), _ptr(cell),
+                                                  _stream(dev)))
+    return coords, cell
+
+
+def DenseCoordinatesGPU(shape, device):
+    """-> int32 [cells, D+1]: the coordinates of every cell of `shape` = (B, X1, .., XD) in cell order"""
+    dev = torch.device(device)
+    _check(dev.type == "cuda", "DenseCoordinatesGPU generates on the GPU")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    coords = torch.empty((_cells_of(shape), len(shape)), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().me_dense_all_coords(len(shape), _i64s(shape), _ptr(coords), _stream(dev)))
+    return coords

@@ -547,6 +547,65 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           auto r = broadcast_backward(in_feat, glob, grad_out, to_int(mode), in_key, glob_key, mgr);
           return py::make_tuple(r.first, r.second);
         });
+  // dense <-> sparse conversion (csrc/dense.hip): torch indexing in the reference's Python (MinkowskiSparseTensor.py:460-557,
+  // MinkowskiOps.py:246-348), so these operator names are this package's own; the GIL is released around the launches
+  m.attr("DENSE_AUTO") = 0;
+  m.attr("DENSE_ROW_STATIONARY") = ME_DENSE_ROW_STATIONARY;
+  m.attr("DENSE_CELL_STATIONARY") = ME_DENSE_CELL_STATIONARY;
+  m.def("DensePolicy", &dense_policy, py::arg("n"), py::arg("n_cells"), py::arg("c"), py::arg("elem_bytes"),
+        py::arg("to_box"));
+  m.def("DenseCellIndexGPU",
+        [](const Tensor &coordinates, const ivec &min_coordinate, const ivec &divisor, const std::vector<int64_t> &shape,
+           bool want_grid) {
+          std::tuple<Tensor, Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = dense_cell_index(coordinates, min_coordinate, divisor, shape, want_grid);
+          }
+          return py::make_tuple(std::get<0>(r), opt_out(std::get<1>(r)), std::get<2>(r));
+        },
+        py::arg("coordinates"), py::arg("min_coordinate"), py::arg("divisor"), py::arg("shape"),
+        py::arg("want_grid") = true);
+  m.def("DenseGridGPU",
+        [](const Tensor &cell, int64_t n_cells) {
+          py::gil_scoped_release nogil;
+          return dense_grid(cell, n_cells);
+        },
+        py::arg("cell"), py::arg("n_cells"));
+  m.def("DenseRowsToBoxGPU",
+        [](const Tensor &rows, const py::object &cell, const py::object &grid, int64_t outer, int64_t inner,
+           int64_t policy) {
+          const Tensor c = opt_tensor(cell), g = opt_tensor(grid);
+          py::gil_scoped_release nogil;
+          return dense_rows_to_box(rows, c, g, outer, inner, policy);
+        },
+        py::arg("rows"), py::arg("cell"), py::arg("grid"), py::arg("outer"), py::arg("inner"), py::arg("policy") = 0);
+  m.def("DenseBoxToRowsGPU",
+        [](const Tensor &box, const py::object &cell, const py::object &grid, int64_t n, int64_t outer, int64_t inner,
+           int64_t policy) {
+          const Tensor c = opt_tensor(cell), g = opt_tensor(grid);
+          py::gil_scoped_release nogil;
+          return dense_box_to_rows(box, c, g, n, outer, inner, policy);
+        },
+        py::arg("box"), py::arg("cell"), py::arg("grid"), py::arg("n"), py::arg("outer"), py::arg("inner"),
+        py::arg("policy") = 0);
+  m.def("DenseOccupiedGPU",
+        [](const Tensor &box, int64_t outer, int64_t inner, const std::vector<int64_t> &shape) {
+          std::pair<Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = dense_occupied(box, outer, inner, shape);
+          }
+          return py::make_tuple(r.first, r.second);
+        },
+        py::arg("box"), py::arg("outer"), py::arg("inner"), py::arg("shape"));
+  m.def("DenseCoordinatesGPU",
+        [](const std::vector<int64_t> &shape, const py::object &device) {
+          const c10::Device dev = py::cast<c10::Device>(py::module_::import("torch").attr("device")(device));
+          py::gil_scoped_release nogil;
+          return dense_coordinates(shape, dev);
+        },
+        py::arg("shape"), py::arg("device"));
   m.def("PruningForwardGPU", &pruning_forward);
   m.def("PruningBackwardGPU", &pruning_backward);
 

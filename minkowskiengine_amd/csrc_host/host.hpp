@@ -325,6 +325,17 @@ std::tuple<Tensor, Tensor, Tensor> instance_norm_backward(const Tensor &in_feat,
                                                           const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key,
                                                           CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
                                                           bool need_grad_in, bool need_grad_weight, bool need_grad_bias);
+// dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU / DensePolicy)
+int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box);
+std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,
+                                                    const ivec &divisor, const std::vector<int64_t> &shape, bool want_grid);
+Tensor dense_grid(const Tensor &cell, int64_t n_cells);
+Tensor dense_rows_to_box(const Tensor &rows, const Tensor &cell, const Tensor &grid, int64_t outer, int64_t inner,
+                         int64_t policy);
+Tensor dense_box_to_rows(const Tensor &box, const Tensor &cell, const Tensor &grid, int64_t n, int64_t outer, int64_t inner,
+                         int64_t policy);
+std::pair<Tensor, Tensor> dense_occupied(const Tensor &box, int64_t outer, int64_t inner, const std::vector<int64_t> &shape);
+Tensor dense_coordinates(const std::vector<int64_t> &shape, c10::Device dev);
 // tensor fields (field.cpp; twin of backend.CsrFromCooGPU / CsrGatherGPU / Interpolation*GPU / coo_spmm*)
 std::tuple<Tensor, Tensor, Tensor> csr_from_coo(const Tensor &keys, int64_t n_rows, const Tensor &cols, const Tensor &vals);
 Tensor csr_gather(Tensor x, const Tensor &rowptr, const Tensor &col, const Tensor &w, const Tensor &scale);

@@ -1225,4 +1225,117 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> bn_backward(const Tensor &x, Tensor d
   return {dx, dskip, gg, gb};
 }
 
+// ---- dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU: the same C-ABI calls in the same order) -----------
+typedef std::vector<int64_t> lvec;
+
+static int64_t cells_of(const lvec &shape) {
+  int64_t n = 1;
+  for (int64_t s : shape) n *= s;
+  return n;
+}
+
+static void check_index(const char *name, const Tensor &t, at::ScalarType dtype, const c10::Device &dev, int64_t numel) {
+  check(!t.defined() || (t.is_cuda() && t.is_contiguous() && t.scalar_type() == dtype && t.device() == dev &&
+                         t.numel() == numel),
+        std::string(name) + " must be a contiguous GPU tensor of its index type on the device of the features, one value "
+                            "per row (cell) or per cell (grid)");
+}
+
+int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box) {
+  return me_dense_policy(n, n_cells, (int32_t)c, (int32_t)elem_bytes, to_box ? 1 : 0);
+}
+
+std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,
+                                                    const ivec &divisor, const lvec &shape, bool want_grid) {
+  check(coordinates.dim() == 2 && coordinates.is_cuda() && coordinates.scalar_type() == at::kInt &&
+            coordinates.is_contiguous(),
+        "coordinates must be a contiguous int32 [N, D+1] GPU tensor");
+  const int64_t n = coordinates.size(0), ncol = coordinates.size(1);
+  check((int64_t)min_coordinate.size() == ncol - 1 && (int64_t)divisor.size() == ncol - 1 && (int64_t)shape.size() == ncol,
+        "min_coordinate / divisor / shape must have D / D / D+1 values");
+  const c10::Device dev = coordinates.device();
+  const int64_t n_cells = cells_of(shape);
+  Tensor cell = at::empty({n}, at::TensorOptions().dtype(at::kLong).device(dev));
+  Tensor flag = empty_i32({1}, dev);
+  Tensor grid = want_grid ? empty_i32({n_cells}, dev) : Tensor();
+  c10::DeviceGuard guard(dev);
+  me_ok(me_dense_cell_index(ptr<int32_t>(coordinates), n, (int32_t)ncol, min_coordinate.data(), divisor.data(),
+                            shape.data(), ptr<int64_t>(cell), ptr<int32_t>(flag), stream_of(dev)));
+  if (want_grid) me_ok(me_dense_grid(ptr<int64_t>(cell), n, n_cells, ptr<int32_t>(grid), stream_of(dev)));
+  return {cell, grid, flag};
+}
+
+Tensor dense_grid(const Tensor &cell, int64_t n_cells) {
+  check(cell.is_cuda() && cell.scalar_type() == at::kLong && cell.is_contiguous() && cell.dim() == 1,
+        "cell must be a contiguous int64 GPU vector");
+  const c10::Device dev = cell.device();
+  Tensor grid = empty_i32({n_cells}, dev);
+  c10::DeviceGuard guard(dev);
+  me_ok(me_dense_grid(ptr<int64_t>(cell), cell.numel(), n_cells, ptr<int32_t>(grid), stream_of(dev)));
+  return grid;
+}
+
+Tensor dense_rows_to_box(const Tensor &rows, const Tensor &cell, const Tensor &grid, int64_t outer, int64_t inner,
+                         int64_t policy) {
+  check_feat("rows", rows);
+  check(rows.dim() == 2 && rows.size(1) > 0, "Invalid rows shape");
+  const c10::Device dev = rows.device();
+  const int64_t n = rows.size(0), c = rows.size(1);
+  check_index("cell", cell, at::kLong, dev, n);
+  check_index("grid", grid, at::kInt, dev, outer * inner);
+  Tensor box = at::empty({outer, c, inner}, rows.options());
+  c10::DeviceGuard guard(dev);
+  ScopedTimer tm("dense_rows_to_box", 0.0, stream_of(dev));
+  me_ok(me_dense_rows_to_box(rows.data_ptr(), (int32_t)rows.element_size(), ptr<int64_t>(cell), ptr<int32_t>(grid), n, outer,
+                             (int32_t)c, inner, box.data_ptr(), (int32_t)policy, stream_of(dev)));
+  return box;
+}
+
+Tensor dense_box_to_rows(const Tensor &box, const Tensor &cell, const Tensor &grid, int64_t n, int64_t outer, int64_t inner,
+                         int64_t policy) {
+  check_feat("box", box);
+  const c10::Device dev = box.device();
+  check(outer * inner > 0 && box.numel() > 0 && box.numel() % (outer * inner) == 0,
+        "box must hold outer * C * inner elements");
+  const int64_t c = box.numel() / (outer * inner);
+  check_index("cell", cell, at::kLong, dev, n);
+  check_index("grid", grid, at::kInt, dev, outer * inner);
+  Tensor rows = at::empty({n, c}, box.options());
+  c10::DeviceGuard guard(dev);
+  ScopedTimer tm("dense_box_to_rows", 0.0, stream_of(dev));
+  me_ok(me_dense_box_to_rows(box.data_ptr(), (int32_t)box.element_size(), ptr<int64_t>(cell), ptr<int32_t>(grid), n, outer,
+                             (int32_t)c, inner, rows.data_ptr(), (int32_t)policy, stream_of(dev)));
+  return rows;
+}
+
+std::pair<Tensor, Tensor> dense_occupied(const Tensor &box, int64_t outer, int64_t inner, const lvec &shape) {
+  check_feat("box", box);
+  const c10::Device dev = box.device();
+  const int64_t n_cells = outer * inner, ncol = (int64_t)shape.size();
+  check(n_cells == cells_of(shape), "shape must have outer * inner cells");
+  const auto lopt = at::TensorOptions().dtype(at::kLong).device(dev);
+  if (n_cells == 0 || box.numel() == 0) return {empty_i32({0, ncol}, dev), at::empty({0}, lopt)};
+  check(box.numel() % n_cells == 0, "box must hold outer * C * inner elements");
+  const int64_t c = box.numel() / n_cells;
+  Tensor ws = workspace(me_dense_occupied_workspace_bytes(n_cells), dev);
+  int64_t n = 0;
+  c10::DeviceGuard guard(dev);
+  me_ok(me_dense_occupied_count(box.data_ptr(), (int32_t)box.element_size(), outer, (int32_t)c, inner, vptr(ws), ws.numel(),
+                                &n, stream_of(dev)));
+  Tensor coords = empty_i32({n, ncol}, dev), cell = at::empty({n}, lopt);
+  if (n > 0)
+    me_ok(me_dense_occupied_fill(vptr(ws), ws.numel(), (int32_t)ncol, shape.data(), ptr<int32_t>(coords), ptr<int64_t>(cell),
+                                 stream_of(dev)));
+  return {coords, cell};
+}
+
+Tensor dense_coordinates(const lvec &shape, c10::Device dev) {
+  check(dev.is_cuda(), "DenseCoordinatesGPU generates on the GPU");
+  if (!dev.has_index()) dev = c10::Device(dev.type(), c10::hip::current_device());
+  Tensor coords = empty_i32({cells_of(shape), (int64_t)shape.size()}, dev);
+  c10::DeviceGuard guard(dev);
+  me_ok(me_dense_all_coords((int32_t)shape.size(), shape.data(), ptr<int32_t>(coords), stream_of(dev)));
+  return coords;
+}
+
 }  // namespace meh

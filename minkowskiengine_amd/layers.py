@@ -253,9 +253,9 @@ class MinkowskiLinear(nn.Module):
         return _rewrap(input, self.linear(input.F))
 
 
-def cat(*sparse_tensors):
-    """Concatenate the features of tensors that share one coordinate map (MinkowskiOps.py:141-158): sparse tensors,
-    or tensor fields on one field key."""
+def _tuple_operator(sparse_tensors, operator):
+    """`operator(list of feature matrices)` of tensors that share one coordinate map, re-wrapped on that map: sparse
+    tensors, or tensor fields on one field key (MinkowskiOps.py:70-138)."""
     if len(sparse_tensors) == 1 and isinstance(sparse_tensors[0], (list, tuple)):
         sparse_tensors = tuple(sparse_tensors[0])
     first = sparse_tensors[0]
@@ -264,9 +264,15 @@ def cat(*sparse_tensors):
             assert hasattr(s, "coordinate_field_map_key"), "Inputs must all be tensor fields."
             assert s._manager is first._manager, "coordinate managers must match"
             assert s.coordinate_field_map_key == first.coordinate_field_map_key, "cat needs a shared field key"
-        return _rewrap(first, torch.cat([s.F for s in sparse_tensors], dim=1))
+        return _rewrap(first, operator([s.F for s in sparse_tensors]))
     for s in sparse_tensors:
         assert isinstance(s, SparseTensor), "Inputs must be sparse tensors."
         assert s._manager is first._manager, "coordinate managers must match"
         assert s.coordinate_map_key == first.coordinate_map_key, "cat needs a shared coordinate map"
-    return _rewrap(first, torch.cat([s.F for s in sparse_tensors], dim=1))
+    return _rewrap(first, operator([s.F for s in sparse_tensors]))
+
+
+def cat(*sparse_tensors):
+    """Concatenate the features of tensors that share one coordinate map (MinkowskiOps.py:141-158): sparse tensors,
+    or tensor fields on one field key."""
+    return _tuple_operator(sparse_tensors, lambda xs: torch.cat(xs, dim=1))

@@ -209,9 +209,69 @@ class SparseTensor:
         self._F = self._F.float()
         return self
 
+    def double(self):
+        self._F = self._F.double()
+        return self
+
+    def get_device(self):
+        return self._F.get_device()
+
     def detach(self):
         return SparseTensor(self._F.detach(), coordinate_map_key=self.coordinate_map_key,
                             coordinate_manager=self._manager)
+
+    # ---- conversions (MinkowskiSparseTensor.py:348-557) ---------------------------------------------------------------
+    def dense(self, shape=None, min_coordinate=None, contract_stride=True):
+        """-> (tensor [B, C, X1, .., XD], min_coordinate, tensor_stride): the features at
+        `(coordinate - min_coordinate) // tensor_stride` (no division with contract_stride=False), zeros elsewhere;
+        gradients reach `self.F`.  `shape` (torch.Size; its channel count is corrected) and `min_coordinate` (an
+        IntTensor divisible by the stride, possibly negative; 0 = the origin; None = the per-axis minimum, which must
+        not be negative) default to the extent of the coordinates.  A coordinate outside the box raises IndexError, on
+        either side (the reference's torch indexing wraps a negative index round to the far side).  HIP kernels
+        (csrc/dense.hip); no CPU path."""
+        from .ops import sparse_tensor_to_dense
+        return sparse_tensor_to_dense(self, shape, min_coordinate, contract_stride)
+
+    def sparse(self, min_coords=None, max_coords=None, contract_coords=True):
+        """-> (torch sparse COO tensor [B, X1, .., XD, C], min_coords, tensor_stride); fp32 / float64 features.
+        min_coords / max_coords: IntTensors of D values divisible by the stride (max inclusive; gives the size)."""
+        D = self._D
+        if min_coords is not None:
+            assert isinstance(min_coords, torch.IntTensor)
+            assert min_coords.numel() == D
+        if max_coords is not None:
+            assert isinstance(max_coords, torch.IntTensor)
+            assert max_coords.numel() == D
+        if self._F.dtype not in (torch.float32, torch.float64):
+            raise ValueError("Feature type not supported.")
+        tensor_stride = torch.IntTensor(self.tensor_stride)
+        coords, batch_indices = self.C[:, 1:], self.C[:, :1]
+        if min_coords is None:
+            min_coords = coords.min(0, keepdim=True)[0].cpu()
+        elif min_coords.ndim == 1:
+            min_coords = min_coords.unsqueeze(0)
+        assert (min_coords % tensor_stride).sum() == 0, "The minimum coordinates must be divisible by the tensor stride."
+        if max_coords is not None:
+            if max_coords.ndim == 1:
+                max_coords = max_coords.unsqueeze(0)
+            assert (max_coords % tensor_stride).sum() == 0, \
+                "The maximum coordinates must be divisible by the tensor stride."
+        coords = coords - min_coords.to(coords.device)
+        if contract_coords:
+            coords = torch.div(coords, tensor_stride.to(coords.device), rounding_mode="floor")
+            if max_coords is not None:
+                max_coords = torch.div(max_coords, tensor_stride, rounding_mode="floor")
+            min_coords = torch.div(min_coords, tensor_stride, rounding_mode="floor")
+        new_coords = torch.cat((batch_indices, coords), dim=1).long()
+        size = None
+        if max_coords is not None:
+            extent = (max_coords - min_coords + 1).reshape(-1).tolist()      # inclusive
+            size = torch.Size([int(batch_indices.max()) + 1, *[int(v) for v in extent], self._F.size(1)])
+        if size is None:
+            sparse_tensor = torch.sparse_coo_tensor(new_coords.t(), self._F)
+        else:
+            sparse_tensor = torch.sparse_coo_tensor(new_coords.t(), self._F, size)
+        return sparse_tensor, min_coords, torch.IntTensor(self.tensor_stride)
 
     # ---- arithmetic between tensors that share a coordinate map (MinkowskiTensor.py:390-520) -----
     def _binary(self, other, op):
@@ -298,12 +358,32 @@ class SparseTensor:
         return [torch.nonzero(batch == b, as_tuple=False).flatten() for b in torch.unique(batch).tolist()]
 
     @property
+    def decomposition_permutations(self):
+        """per batch index, the rows of that batch: `decomposed_features[b] == F[decomposition_permutations[b]]`"""
+        return self._batchwise_row_indices
+
+    @property
     def decomposed_coordinates(self):
         return [self.C[idx, 1:] for idx in self._batchwise_row_indices]
 
     @property
     def decomposed_features(self):
         return [self._F[idx] for idx in self._batchwise_row_indices]
+
+    @property
+    def decomposed_coordinates_and_features(self):
+        rows = self._batchwise_row_indices
+        return [self.C[idx, 1:] for idx in rows], [self._F[idx] for idx in rows]
+
+    def coordinates_at(self, batch_index):
+        return self.C[self._batchwise_row_indices[batch_index], 1:]
+
+    def features_at(self, batch_index):
+        return self._F[self._batchwise_row_indices[batch_index]]
+
+    def coordinates_and_features_at(self, batch_index):
+        idx = self._batchwise_row_indices[batch_index]
+        return self.C[idx, 1:], self._F[idx]
 
     def __repr__(self):
         return (f"{self.__class__.__name__}(\n  coordinates={self.C}\n  features={self._F}\n  "

@@ -73,7 +73,9 @@ typedef struct me_region {
  *   1.9 (190)  round 9: instance normalisation: per-instance statistics, apply and backward (me_inorm_workspace_bytes,
  *              me_inorm_stats, me_inorm_apply, me_inorm_backward and their _f64 twins)
  *   1.10 (200) round 10: dense <-> sparse conversion: cell indices, the row grid, the two movers, occupied cells and all
- *              cells of a box (me_dense_*) */
+ *              cells of a box (me_dense_*)
+ *   1.11 (210) round 11: direct max pooling over an (in_map, out_map) pair list (me_direct_max_pool_*) and the origin-map
+ *              row table of a tensor field (me_field_origin_rows_f32) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -758,6 +760,11 @@ int me_field_interp_map_f64(const double *x_dev, int64_t n, int32_t ncol, const 
                             const uint64_t *table_dev, int64_t capacity, const int32_t *map_coords_dev,
                             int32_t *in_rows_dev, int32_t *out_rows_dev, double *weights_dev, int32_t *rowptr_dev,
                             int64_t *nnz, void *workspace_dev, int64_t workspace_bytes, void *stream);
+/* me_field_origin_rows_f32: rows[i] = row of the origin map (tensor stride 0; table / capacity / origin_coords as
+ *   me_coords_find) whose batch index is lrint(x[i, 0]), or -1: the row table of global pooling and broadcast over a
+ *   field (CoordinateMapManager::origin_field_map, src/coordinate_map_gpu.cu:894-975).  rows int32 [n].  No sync. */
+int me_field_origin_rows_f32(const float *x_dev, int64_t n, int32_t ncol, const uint64_t *table_dev, int64_t capacity,
+                             const int32_t *origin_coords_dev, int32_t *rows_dev, void *stream);
 int64_t me_csr_from_coo_workspace_bytes(int64_t nnz);
 int me_csr_from_coo(const int32_t *keys_dev, const int32_t *cols_dev, const void *vals_dev, int32_t val_bytes,
                     int64_t nnz, int64_t n_rows, int32_t *rowptr_dev, int32_t *cols_out_dev, void *vals_out_dev,
@@ -768,6 +775,46 @@ int me_csr_gather_bf16(const uint16_t *x_dev, int32_t c, const int32_t *rowptr_d
                        const float *w_dev, const float *scale_dev, int64_t n_rows, uint16_t *y_dev, void *stream);
 int me_csr_gather_f64(const double *x_dev, int32_t c, const int32_t *rowptr_dev, const int32_t *col_dev,
                       const double *w_dev, const double *scale_dev, int64_t n_rows, double *y_dev, void *stream);
+
+/* Direct max pooling (src/direct_max_pool.cpp, src/pooling_max_kernel.cu:55-234; ABI 1.11): entry e of the pair list says
+ * "row in_map[e] of in_feat [in_nrows, c] belongs to output row out_map[e]".  For every output row o with an entry and
+ * every channel: out_feat[o, ch] = max of in_feat[in_map[e], ch] over the entries with out_map[e] == o, compared as the
+ * reference does (`max < cur`, from the row's first entry, entries in map order: among equal values the first entry wins;
+ * bf16 compares in fp32 and stores the winner's bits), max_index[o, ch] = in_map[e*] * c + ch.  Rows without an entry:
+ * out_feat 0, max_index the index type's maximum (the reference's "unused" marker).
+ *   in_map / out_map: [nmap], both int32 (index_bytes 4) or both int64 (8); NOT written (the reference sorts them in
+ *   place).  max_index [out_nrows, c] has the index type.  is_sorted != 0: out_map is ascending, no sort (checked).
+ *   Errors: a map value outside [0, in_nrows) / [0, out_nrows) (this covers "more distinct outputs than out_nrows"),
+ *   out_map not ascending under is_sorted, in_nrows * c >= 2^31 with int32 maps.  nmap, in_nrows, out_nrows < 2^31.
+ *   SYNC (one 4-byte copy: the verdict of the map check).  Workspace: me_direct_max_pool_workspace_bytes(nmap, out_nrows).
+ * me_direct_max_pool_backward_*: grad_in [in_nrows, c] = 0, plus grad_out[o, ch] at every max_index[o, ch] in
+ *   [0, in_nrows * c) (anything else, the marker included, is skipped).  The flat indices are sorted (stable) and every run
+ *   of equal indices is summed in ascending (o, ch) order by one thread (fp32 sums for bf16, one rounding): no
+ *   floating-point atomics, bitwise reproducible.  out_nrows * c < 2^31, in_nrows * c < 2^32 - 1.  No sync.
+ *   Workspace: me_direct_max_pool_backward_workspace_bytes(out_nrows, c). */
+int64_t me_direct_max_pool_workspace_bytes(int64_t nmap, int64_t out_nrows);
+int me_direct_max_pool_f32(const float *in_feat_dev, int32_t c, const void *in_map_dev, const void *out_map_dev,
+                           int32_t index_bytes, int64_t nmap, int64_t in_nrows, int64_t out_nrows, int32_t is_sorted,
+                           float *out_feat_dev, void *max_index_dev, void *workspace_dev, int64_t workspace_bytes,
+                           void *stream);
+int me_direct_max_pool_bf16(const uint16_t *in_feat_dev, int32_t c, const void *in_map_dev, const void *out_map_dev,
+                            int32_t index_bytes, int64_t nmap, int64_t in_nrows, int64_t out_nrows, int32_t is_sorted,
+                            uint16_t *out_feat_dev, void *max_index_dev, void *workspace_dev, int64_t workspace_bytes,
+                            void *stream);
+int me_direct_max_pool_f64(const double *in_feat_dev, int32_t c, const void *in_map_dev, const void *out_map_dev,
+                           int32_t index_bytes, int64_t nmap, int64_t in_nrows, int64_t out_nrows, int32_t is_sorted,
+                           double *out_feat_dev, void *max_index_dev, void *workspace_dev, int64_t workspace_bytes,
+                           void *stream);
+int64_t me_direct_max_pool_backward_workspace_bytes(int64_t out_nrows, int32_t c);
+int me_direct_max_pool_backward_f32(const float *grad_out_dev, const void *max_index_dev, int32_t index_bytes,
+                                    int64_t out_nrows, int32_t c, int64_t in_nrows, float *grad_in_dev,
+                                    void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_direct_max_pool_backward_bf16(const uint16_t *grad_out_dev, const void *max_index_dev, int32_t index_bytes,
+                                     int64_t out_nrows, int32_t c, int64_t in_nrows, uint16_t *grad_in_dev,
+                                     void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_direct_max_pool_backward_f64(const double *grad_out_dev, const void *max_index_dev, int32_t index_bytes,
+                                    int64_t out_nrows, int32_t c, int64_t in_nrows, double *grad_in_dev,
+                                    void *workspace_dev, int64_t workspace_bytes, void *stream);
 
 /* Generative / expanding convolutions (CoordinateMapCPU::stride_region, src/coordinate_map_cpu.hpp:446-487;
  * manager: src/coordinate_map_manager.cpp:436-466): candidate output coordinates = every kernel offset of the

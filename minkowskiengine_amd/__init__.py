@@ -35,7 +35,7 @@ from .layers import (  # noqa: F401
     MinkowskiBatchNorm, MinkowskiDropout, MinkowskiELU, MinkowskiLeakyReLU, MinkowskiLinear, MinkowskiReLU,
     MinkowskiSigmoid, MinkowskiSyncBatchNorm, MinkowskiTanh, cat)
 from .pooling import (  # noqa: F401
-    MinkowskiAvgPooling, MinkowskiGlobalAvgPooling, MinkowskiGlobalMaxPooling, MinkowskiGlobalPooling,
+    MinkowskiAvgPooling, MinkowskiDirectMaxPoolingFunction, MinkowskiGlobalAvgPooling, MinkowskiGlobalMaxPooling, MinkowskiGlobalPooling,
     MinkowskiGlobalPoolingFunction, MinkowskiGlobalSumPooling, MinkowskiLocalPoolingFunction,
     MinkowskiLocalPoolingTransposeFunction, MinkowskiMaxPooling, MinkowskiPoolingTranspose, MinkowskiSumPooling)
 from .broadcast import (  # noqa: F401

@@ -238,6 +238,15 @@ SIGNATURES = {
                                                c_vp, c_vp, c_i64, c_vp]),
     "me_field_interp_map_f64": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                c_vp, c_vp, c_i64, c_vp]),
+    "me_field_origin_rows_f32": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "me_direct_max_pool_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "me_direct_max_pool_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_direct_max_pool_bf16": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_direct_max_pool_f64": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_direct_max_pool_backward_workspace_bytes": (c_i64, [c_i64, c_i32]),
+    "me_direct_max_pool_backward_f32": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "me_direct_max_pool_backward_bf16": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "me_direct_max_pool_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "me_csr_from_coo_workspace_bytes": (c_i64, [c_i64]),
     "me_csr_from_coo": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "me_csr_gather_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),

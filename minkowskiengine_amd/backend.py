@@ -707,6 +707,7 @@ class CoordinateMapManagerGPU_c10:
         self._fields = {}        # field key tuple -> fp32 coordinates [N, D+1]
         self._field_maps = {}    # (field key, sparse key) -> (unique_index, inverse_mapping): field_to_sparse_insert_and_map
         self._field_lookups = {}  # (field key, sparse key) -> (sparse rows, field rows): field_to_sparse_map
+        self._origin_field_maps = {}  # field key -> int32 [N] origin rows: origin_field_map
         # Not in the reference: the map-building requests this manager served on a cache miss, in order — strided
         # maps, kernel maps, tile-plan / weight-gradient configurations.  `prefetch(recipe)` replays such a list on a
         # NEW scene right after its coordinates are inserted, so that every host read-back of the build (output sizes,
@@ -1081,7 +1082,82 @@ class CoordinateMapManagerGPU_c10:
         return CoordinateMapKey(list(okey[0]), okey[1])
 
     def origin_map_size(self):
-        return self._get(self.origin()).n
+        return self._get(self.origin_field() if not self._maps else self.origin()).n
+
+    # ---- origin map of fields (src/coordinate_map_manager.cpp:516-560, 923-960) -------------------------------------
+    def _oldest_field(self):
+        _check(len(self._fields) > 0, "origin_field() needs at least one coordinate field")
+        return next(iter(self._fields))
+
+    def origin_field(self, field_key=None):
+        """CoordinateMapKey of the origin map, the SAME key `origin()` uses (the reference keeps both in one map
+        table).  When the map is absent it is built from the batch indices lrint(x0) of a field, sorted ascending — the
+        row order `origin()` documents: `field_key`, or the OLDEST field of the manager (insertion order; the
+        reference's pick is an accident of a loop that never updates its min_size).  Works on a manager that holds
+        only fields."""
+        fk = self._k(field_key) if field_key is not None else self._oldest_field()
+        x = self._field(fk)
+        okey = (tuple([0] * (x.shape[1] - 1)), "")
+        if okey not in self._maps:
+            batches = torch.unique(torch.round(x[:, 0]).to(torch.int32))          # sorted
+            oc = torch.zeros((batches.numel(), x.shape[1]), dtype=torch.int32, device=x.device)
+            oc[:, 0] = batches
+            cmap, _, _ = _insert(oc.contiguous(), okey[0])      # unique rows: insertion order = sorted order
+            self._maps[okey] = cmap
+        return CoordinateMapKey(list(okey[0]), okey[1])
+
+    def _origin_field_rows(self, field_key):
+        """int32 [N]: origin-map row of every point of the field (me_field_origin_rows: round the batch column, probe
+        the origin table), cached per field key; the same "every batch index" check as _origin_rows."""
+        fk = self._k(field_key)
+        x = self._field(fk)
+        okey = self._k(self.origin_field(fk))
+        rows = self._origin_field_maps.get(fk)
+        if rows is None:
+            omap = self._maps[okey]
+            lib = _lib.load()
+            dev = x.device
+            n = int(x.shape[0])
+            rows = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            with _on(dev):
+                _lib.check(lib.me_field_origin_rows_f32(_ptr(x), n, int(x.shape[1]), _ptr(omap.table), omap.capacity,
+                                                        _ptr(omap.coords), _ptr(rows), _stream(dev)))
+            rows = rows[:n]
+            _check(n == 0 or bool((rows >= 0).all()),
+                   "the origin map does not contain every batch index of this coordinate field")
+            self._origin_field_maps[fk] = rows
+        return rows
+
+    def origin_field_map(self, field_key):
+        """{0: int32 [2, N]} (row 0 = field rows, row 1 = origin rows): origin_map()'s layout for a field key."""
+        rows = self._origin_field_rows(field_key)
+        return {0: torch.stack((torch.arange(rows.numel(), dtype=torch.int32, device=rows.device), rows))}
+
+    def exists_field(self, key):
+        return self._k(key) in self._fields
+
+    def _is_field_input(self, key, n_rows):
+        """Does `key` with features of `n_rows` rows name a FIELD?  Field keys and sparse keys live in separate
+        namespaces and may be equal (a field and its stride-1 quantisation both get ([1]*D, "")): a sparse map wins
+        unless only the field has that many rows, so sparse-tensor behaviour is unchanged."""
+        k = self._k(key)
+        if k not in self._fields:
+            return False
+        if k not in self._maps:
+            return True
+        return int(self._fields[k].shape[0]) == int(n_rows) and self._maps[k].n != int(n_rows)
+
+    def _pool_rows(self, key, n_rows):
+        """-> (origin row of every input row, origin key): the row table of global pooling / broadcast for a sparse
+        key or a field key"""
+        if self._is_field_input(key, n_rows):
+            return self._origin_field_rows(key), self.origin_field(key)
+        return self._origin_rows(key), self.origin()
+
+    def _pool_size(self, key, n_rows):
+        if self._is_field_input(key, n_rows):
+            return int(self._field(key).shape[0])
+        return self.size(key)
 
     def _origin_rows(self, in_key):
         """int32 [n_in]: origin-map row (output row of a global pooling) of every row of `in_key`;
@@ -1189,7 +1265,8 @@ class CoordinateMapManagerGPU_c10:
                 for name in names:
                     if name not in ("_recipe", "in_map", "out_map"):
                         walk(getattr(o, name, None), depth + 1)
-        for store in (self._maps, self._kernel_maps, self._origin_maps, self._prune_rows, self._stride_maps):
+        for store in (self._maps, self._kernel_maps, self._origin_maps, self._origin_field_maps, self._prune_rows,
+                      self._stride_maps):
             walk(store)
         return out
 
@@ -2432,6 +2509,77 @@ def coo_spmm_average_int32(rows, cols, dim_i, dim_j, mat2, spmm_algorithm_id=1):
     return [out, row_of, c, scale[row_of.long()]]
 
 
+def _check_dpool_index(name, t):
+    _check(isinstance(t, torch.Tensor) and t.is_cuda, name, "must be a CUDA (ROCm) tensor — the MI355X path has no CPU "
+           "implementation")
+    _check(t.dtype in (torch.int32, torch.int64), name, "must be int32 or int64, got", t.dtype)
+
+
+def direct_max_pool_fw(in_map, out_map, in_feat, out_nrows, is_sorted=False):
+    """src/direct_max_pool.cpp:77-128 -> (out_feat [out_nrows, C], max_index [out_nrows, C], dtype of the maps):
+    per output row the channel-wise max of the rows in_feat[in_map[e]] with out_map[e] == row and the flat index
+    in_map[e] * C + c of the winner (first entry in map order among equals); rows without an entry hold 0 and the index
+    type's maximum.  The caller's maps are NOT sorted in place (the reference does).  csrc/direct_pool.hip."""
+    _check_dpool_index("in_map", in_map)
+    _check_dpool_index("out_map", out_map)
+    _check(in_map.dim() == 1 and out_map.dim() == 1 and in_map.numel() == out_map.numel(),
+           "in_map and out_map must be 1-D tensors of equal length")
+    _check(in_map.dtype == out_map.dtype, "in_map and out_map must have the same dtype")
+    if not in_feat.is_contiguous():
+        in_feat = in_feat.contiguous()
+    _check_feat("in_feat", in_feat)
+    _check(in_feat.dim() == 2, "Invalid in_feat.dim():", in_feat.dim())
+    dev = in_feat.device
+    _check(in_map.device == dev and out_map.device == dev, "all inputs must be on the same device")
+    in_map, out_map = in_map.contiguous(), out_map.contiguous()
+    out_nrows = int(out_nrows)
+    _check(out_nrows >= 0, "Invalid number of out nrows:", out_nrows)
+    n_in, c, nmap = int(in_feat.shape[0]), int(in_feat.shape[1]), int(in_map.numel())
+    out = torch.empty((out_nrows, c), dtype=in_feat.dtype, device=dev)
+    mask = torch.empty((out_nrows, c), dtype=in_map.dtype, device=dev)
+    if out_nrows == 0 or c == 0:
+        _check(nmap == 0 or c == 0, "Invalid number of out nrows:", out_nrows)
+        return out, mask
+    lib = _lib.load()
+    ws = _workspace(lib.me_direct_max_pool_workspace_bytes(nmap, out_nrows), dev)
+    fn = _by_dtype(lib, "direct_max_pool", in_feat)
+    with _on(dev):
+        _timed("direct_max_pool", dev, lambda: _lib.check(fn(
+            _ptr(in_feat), c, _ptr(in_map), _ptr(out_map), in_map.element_size(), nmap, n_in, out_nrows,
+            1 if is_sorted else 0, _ptr(out), _ptr(mask), _ptr(ws), ws.numel(), _stream(dev))))
+    return out, mask
+
+
+def direct_max_pool_bw(grad_out_feat, max_index, in_nrows):
+    """src/direct_max_pool.cpp:130-169 -> grad_in [in_nrows, C]: zeros plus grad_out[o, c] at every marked
+    max_index[o, c]; an input element that won in several output rows gets their sum, added in ascending output row by
+    one thread (no floating-point atomics: bitwise reproducible).  The grouping is rebuilt from the mask, so the
+    reference's three arguments are all it needs."""
+    _check_dpool_index("max_index", max_index)
+    if not grad_out_feat.is_contiguous():
+        grad_out_feat = grad_out_feat.contiguous()
+    _check_feat("grad_out_feat", grad_out_feat)
+    _check(grad_out_feat.dim() == 2 and tuple(max_index.shape) == tuple(grad_out_feat.shape),
+           "max_index must have the shape of grad_out_feat")
+    dev = grad_out_feat.device
+    _check(max_index.device == dev, "all inputs must be on the same device")
+    max_index = max_index.contiguous()
+    in_nrows = int(in_nrows)
+    _check(in_nrows >= 0, "Invalid number of in nrows:", in_nrows)
+    n_out, c = int(grad_out_feat.shape[0]), int(grad_out_feat.shape[1])
+    grad_in = torch.empty((in_nrows, c), dtype=grad_out_feat.dtype, device=dev)
+    if in_nrows == 0 or c == 0:
+        return grad_in
+    lib = _lib.load()
+    ws = _workspace(lib.me_direct_max_pool_backward_workspace_bytes(n_out, c), dev)
+    fn = _by_dtype(lib, "direct_max_pool_backward", grad_out_feat)
+    with _on(dev):
+        _timed("direct_max_pool_backward", dev, lambda: _lib.check(fn(
+            _ptr(grad_out_feat), _ptr(max_index), max_index.element_size(), n_out, c, in_nrows, _ptr(grad_in), _ptr(ws),
+            ws.numel(), _stream(dev))))
+    return grad_in
+
+
 _GLOBAL_SUM = (PoolingMode.GLOBAL_SUM_POOLING_DEFAULT, PoolingMode.GLOBAL_SUM_POOLING_KERNEL,
                PoolingMode.GLOBAL_SUM_POOLING_PYTORCH_INDEX)
 _GLOBAL_AVG = (PoolingMode.GLOBAL_AVG_POOLING_DEFAULT, PoolingMode.GLOBAL_AVG_POOLING_KERNEL,
@@ -2473,13 +2621,15 @@ def GlobalPoolingForwardGPU(in_feat, pooling_mode, in_key, out_key, manager):
     indices when the batch size is 1, global_pooling_cpu.cpp:99-101, and then mis-scatters them)."""
     _check_feat("in_feat", in_feat)
     _check(in_feat.dim() == 2, "Invalid in_feat.dim():", in_feat.dim())
-    _check(manager.exists(in_key), "coordinate map not found")
-    _check(in_feat.shape[0] == manager.size(in_key), "Invalid in_feat size")
+    _check(manager.exists(in_key) or manager.exists_field(in_key), "coordinate map not found")
+    _check(in_feat.shape[0] == manager._pool_size(in_key, in_feat.shape[0]), "Invalid in_feat size")
     mode = PoolingMode(int(pooling_mode))
     _check(mode in _GLOBAL_SUM + _GLOBAL_AVG + _GLOBAL_MAX, "Invalid pooling mode")
+    # a field key (src/global_pooling_gpu.cu:58, 74-85): the origin map comes from origin_field(), the row table from
+    # origin_field_map(); the kernels are the same
+    rows, okey = manager._pool_rows(in_key, in_feat.shape[0])
     if not out_key.is_key_set():
-        out_key.set_key(manager.origin().get_key())
-    rows = manager._origin_rows(in_key)
+        out_key.set_key(okey.get_key())
     n_batch = manager.size(out_key)
     m = 2 if mode in _GLOBAL_MAX else (1 if mode in _GLOBAL_AVG else 0)
     out, arg, cnt = _global_pool(in_feat, None, rows, n_batch, m)
@@ -2519,20 +2669,21 @@ def GlobalPoolingBackwardGPU(in_feat, grad_out_feat, num_nonzero, pooling_mode, 
     if mode in _GLOBAL_AVG:
         g = ((g if g.dtype == torch.float64 else g.float()) / num_nonzero.clamp_min(1.0)[:, None]) \
             .to(in_feat.dtype).contiguous()
-    rows = manager._origin_rows(in_key)
+    rows, _ = manager._pool_rows(in_key, n)
     return _broadcast(None, g, rows, n, c, False)
 
 
 def BroadcastForwardGPU(in_feat, in_feat_glob, broadcast_mode, in_key, glob_key, manager):
-    """src/broadcast_cpu.cpp:38-97: out[i] = in[i] (+ | *) glob[batch of i]."""
+    """src/broadcast_cpu.cpp:38-97: out[i] = in[i] (+ | *) glob[batch of i].  `in_key` may be a field key (an extension:
+    the reference's broadcast_gpu.cu only looks up origin_map): the per-cloud row goes back onto the points."""
     _check_feat("in_feat", in_feat)
     _check_feat("in_feat_glob", in_feat_glob)
     _same_dtype("in_feat_glob", in_feat_glob, in_feat)
     _check(in_feat.shape[1] == in_feat_glob.shape[1], "feature sizes must match")
-    _check(in_feat.shape[0] == manager.size(in_key), "Invalid in_feat size")
+    _check(in_feat.shape[0] == manager._pool_size(in_key, in_feat.shape[0]), "Invalid in_feat size")
+    rows, _ = manager._pool_rows(in_key, in_feat.shape[0])
     _check(in_feat_glob.shape[0] == manager.size(glob_key), "Invalid in_feat_glob size")
     op = BroadcastMode(int(broadcast_mode))
-    rows = manager._origin_rows(in_key)
     return _broadcast(in_feat, in_feat_glob, rows, int(in_feat.shape[0]), int(in_feat.shape[1]),
                       op == BroadcastMode.ELEMENTWISE_MULTIPLICATION)
 
@@ -2548,7 +2699,7 @@ def BroadcastBackwardGPU(in_feat, in_feat_glob, grad_out_feat, broadcast_mode, i
     if grad_out_feat.dtype != in_feat.dtype:
         grad_out_feat = grad_out_feat.to(in_feat.dtype)
     op = BroadcastMode(int(broadcast_mode))
-    rows = manager._origin_rows(in_key)
+    rows, _ = manager._pool_rows(in_key, in_feat.shape[0])
     n_batch = int(in_feat_glob.shape[0])
     if op == BroadcastMode.ELEMENTWISE_ADDITON:
         grad_in = grad_out_feat.clone()

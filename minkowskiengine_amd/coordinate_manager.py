@@ -181,6 +181,16 @@ class CoordinateManager:
     def origin_map(self, key):
         return self._manager.origin_map(key)
 
+    def origin_field(self, field_key=None):
+        """Key of the origin map (the key origin() returns), built from the batch indices of a field when absent:
+        `field_key`, or the oldest field of the manager (MinkowskiCoordinateManager.py:273)."""
+        return self._manager.origin_field(field_key)
+
+    def origin_field_map(self, key):
+        """{0: int32 [2, N]}: (field rows, origin rows) of a field key, origin_map()'s layout
+        (MinkowskiCoordinateManager.py:426)."""
+        return self._manager.origin_field_map(key)
+
     def origin_map_size(self):
         return self._manager.origin_map_size()
 

@@ -76,6 +76,21 @@ __global__ __launch_bounds__(256) void k_lookup_compact(const int32_t *__restric
   }
 }
 
+// rows[i] = row of the ORIGIN map (tensor stride 0: coordinates (batch, 0, .., 0)) of point i's batch index lrint(x_0),
+// or -1: the row table of global pooling / broadcast over a field.  Byte model: n * (ncol * 4 (one column used) + 4).
+template <int NCOL>
+__global__ __launch_bounds__(256) void k_origin_rows(const float *__restrict__ x, int64_t n,
+                                                    const uint64_t *__restrict__ table, uint32_t mask,
+                                                    const int32_t *__restrict__ map_coords, int32_t *__restrict__ rows) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int32_t key[NCOL];
+  key[0] = (int32_t)lrint(x[i * NCOL]);
+#pragma unroll
+  for (int j = 1; j < NCOL; ++j) key[j] = 0;
+  rows[i] = table_find<NCOL>(table, mask, map_coords, key);
+}
+
 // corner n of point x: bit (D - j) of n selects floor(x_j / s_j) * s_j + s_j in column j
 template <typename F, int NCOL>
 __device__ __forceinline__ void corner(const F (&xf)[NCOL], const Strides &st, int n, int32_t (&c)[NCOL]) {
@@ -444,6 +459,23 @@ int me_field_lookup_f64(const double *x, int64_t n, int32_t ncol, const int32_t 
                         int64_t *n_hit, void *ws, int64_t ws_bytes, void *stream) {
   return lookup<double>(x, n, ncol, ts, table, capacity, map_coords, sparse_rows, field_rows, n_hit, ws, ws_bytes,
                         (hipStream_t)stream);
+}
+
+int me_field_origin_rows_f32(const float *x, int64_t n, int32_t ncol, const uint64_t *table, int64_t capacity,
+                             const int32_t *origin_coords, int32_t *rows, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_CHECK(ncol >= 2 && ncol <= 8, "coordinate size (D+1) must be in [2, 8]");
+  ME_CHECK(capacity >= 64 && (capacity & (capacity - 1)) == 0, "capacity must be a power of two");
+  ME_CHECK(n >= 0 && n < (1ll << 31), "number of points must fit in int32");
+  ME_CHECK(ncol != 4 || (uintptr_t)origin_coords % 16 == 0, "coordinates with 4 columns must be 16-byte aligned");
+  if (n == 0) return 0;
+  ME_CHECK(x != nullptr && table != nullptr && origin_coords != nullptr && rows != nullptr, "null pointer");
+  const dim3 grid((unsigned)ceil_div(n, 256)), block(256);
+  const uint32_t mask = (uint32_t)(capacity - 1);
+  ME_DISPATCH_NCOL(ncol, hipLaunchKernelGGL((k_origin_rows<NCOL>), grid, block, 0, stream, x, n, table, mask,
+                                            origin_coords, rows));
+  ME_LAUNCH_CHECK();
+  return 0;
 }
 
 int64_t me_field_interp_workspace_bytes(int64_t n, int32_t ncol) {

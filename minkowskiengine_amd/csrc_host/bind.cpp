@@ -226,7 +226,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return py::make_tuple(r.first, r.second);
            })
       .def("origin", [](CoordinateMapManager &s) { return new_key(s.origin()); }, py::return_value_policy::take_ownership)
-      .def("origin_map_size", [](CoordinateMapManager &s) { return s.get(s.origin())->n; })
+      .def("origin_map_size",
+           [](CoordinateMapManager &s) { return s.get(s.maps.empty() ? s.origin_field(nullptr) : s.origin())->n; })
+      // origin map of fields (pybind/extern.hpp:791, 801): the key origin() uses, built from a field when absent
+      .def("origin_field",
+           [](CoordinateMapManager &s, const py::object &field_key) {
+             if (field_key.is_none()) return new_key(s.origin_field(nullptr));
+             const KeyT k = keyt(field_key.cast<const CoordinateMapKey *>());
+             return new_key(s.origin_field(&k));
+           },
+           py::arg("field_key") = py::none(), py::return_value_policy::take_ownership)
+      .def("origin_field_map",
+           [](CoordinateMapManager &s, const CoordinateMapKey *k) {
+             Tensor rows = s.origin_field_rows(keyt(k));
+             py::dict d;
+             d[py::int_(0)] = at::stack({at::arange(rows.numel(), rows.options()), rows});
+             return d;
+           })
+      .def("_origin_field_rows",
+           [](CoordinateMapManager &s, const CoordinateMapKey *k) { return s.origin_field_rows(keyt(k)); })
+      .def("exists_field", [](CoordinateMapManager &s, const CoordinateMapKey *k) { return k->key_set && s.exists_field(k->key); })
       .def("origin_map",
            [](CoordinateMapManager &s, const CoordinateMapKey *k) {
              Tensor rows = s.origin_rows(keyt(k));
@@ -525,6 +544,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            int64_t /*spmm_algorithm_id*/) { return coo_spmm_average(rows, cols, dim_i, dim_j, mat2); },
         py::arg("rows"), py::arg("cols"), py::arg("dim_i"), py::arg("dim_j"), py::arg("mat2"),
         py::arg("spmm_algorithm_id") = 1);
+  // direct max pooling (pybind/extern.hpp:654-656)
+  m.def("direct_max_pool_fw",
+        [](const Tensor &in_map, const Tensor &out_map, const Tensor &in_feat, int64_t out_nrows, bool is_sorted) {
+          auto r = direct_max_pool_fw(in_map, out_map, in_feat, out_nrows, is_sorted);
+          return py::make_tuple(r.first, r.second);
+        },
+        py::arg("in_map"), py::arg("out_map"), py::arg("in_feat"), py::arg("out_nrows"), py::arg("is_sorted") = false);
+  m.def("direct_max_pool_bw", &direct_max_pool_bw, py::arg("grad_out_feat"), py::arg("max_index"), py::arg("in_nrows"));
   m.def("GlobalPoolingForwardGPU",
         [](const Tensor &in_feat, const py::object &pooling_mode, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
            CoordinateMapManager *mgr) {

@@ -34,6 +34,7 @@ KeyT CoordinateMapManager::insert_field(const Tensor &coordinates, const ivec &t
   KeyT key(tensor_stride, string_id);
   for (int i = 0; fields.count(key); ++i) key = KeyT(tensor_stride, (string_id.empty() ? "" : string_id + "-") + "f" + std::to_string(i));
   fields[key] = coordinates.detach().to(at::kFloat).contiguous();
+  field_order.push_back(key);
   return key;
 }
 
@@ -84,6 +85,62 @@ std::pair<Tensor, Tensor> CoordinateMapManager::field_to_sparse_map(const KeyT &
   Tensor s64 = srow.narrow(0, 0, n_hit).to(at::kLong), f64 = frow.narrow(0, 0, n_hit).to(at::kLong);
   field_lookups[{field_key, sparse_key}] = {s64, f64};
   return {s64, f64};
+}
+
+// ---- origin map of fields (src/coordinate_map_manager.cpp:516-560, 923-960) ---------------------------------------------
+KeyT CoordinateMapManager::origin_field(const KeyT *field_key) {
+  check(field_key != nullptr || !field_order.empty(), "origin_field() needs at least one coordinate field");
+  const Tensor x = field(field_key != nullptr ? *field_key : field_order.front());   // default: the oldest field
+  KeyT okey(ivec((size_t)x.size(1) - 1, 0), "");
+  if (!maps.count(okey)) {
+    Tensor batches = std::get<0>(at::_unique(at::round(x.select(1, 0)).to(at::kInt), /*sorted=*/true));
+    Tensor oc = at::zeros({batches.numel(), x.size(1)}, i32(x.device()));
+    oc.select(1, 0).copy_(batches);
+    InsertResult r = insert_coords(oc.contiguous(), okey.first);   // unique rows: insertion order = sorted order
+    put(okey, r.map);
+  }
+  return okey;
+}
+
+Tensor CoordinateMapManager::origin_field_rows(const KeyT &field_key) {
+  const Tensor x = field(field_key);
+  const KeyT okey = origin_field(&field_key);
+  auto it = origin_field_rows_cache.find(field_key);
+  if (it != origin_field_rows_cache.end()) return it->second;
+  auto omap = get(okey);
+  const c10::Device dev = x.device();
+  const int64_t n = x.size(0);
+  Tensor rows = at::empty({n > 0 ? n : 1}, i32(dev));
+  {
+    c10::DeviceGuard guard(dev);
+    me_ok(me_field_origin_rows_f32(ptr<float>(x), n, (int)x.size(1), ptr<uint64_t>(omap->table), omap->capacity,
+                                   ptr<int32_t>(omap->coords), ptr<int32_t>(rows), stream_of(dev)));
+  }
+  rows = rows.narrow(0, 0, n);
+  check(n == 0 || rows.ge(0).all().item<bool>(),
+        "the origin map does not contain every batch index of this coordinate field");
+  origin_field_rows_cache[field_key] = rows;
+  return rows;
+}
+
+// a key may name a field and a sparse map at once (separate namespaces): the sparse map wins unless only the field has
+// that many rows (backend._is_field_input)
+bool CoordinateMapManager::is_field_input(const KeyT &k, int64_t n_rows) const {
+  auto f = fields.find(k);
+  if (f == fields.end()) return false;
+  auto m = maps.find(k);
+  if (m == maps.end()) return true;
+  return f->second.size(0) == n_rows && m->second->n != n_rows;
+}
+
+std::pair<Tensor, KeyT> CoordinateMapManager::pool_rows(const KeyT &k, int64_t n_rows) {
+  if (is_field_input(k, n_rows)) return {origin_field_rows(k), origin_field(&k)};
+  return {origin_rows(k), origin()};
+}
+
+int64_t CoordinateMapManager::pool_size(const KeyT &k, int64_t n_rows) const {
+  if (is_field_input(k, n_rows)) return field(k).size(0);
+  return get(k)->n;
 }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor> CoordinateMapManager::interpolation_map(const KeyT &in_key,
@@ -214,6 +271,77 @@ std::vector<Tensor> coo_spmm_average(const Tensor &rows, const Tensor &cols, int
   Tensor out = csr_gather(mat2, rowptr, std::get<1>(t), Tensor(), scale);
   Tensor row_of = at::repeat_interleave(at::arange(dim_i, i32(rowptr.device())), cnt.to(at::kLong));
   return {out, row_of, std::get<1>(t), scale.index({row_of.to(at::kLong)})};
+}
+
+// ---- direct max pooling (csrc/direct_pool.hip) ------------------------------------------------------------------------
+static void check_dpool_index(const char *name, const Tensor &t) {
+  check(t.is_cuda(), std::string(name) + " must be a CUDA (ROCm) tensor — the MI355X path has no CPU implementation");
+  check(t.scalar_type() == at::kInt || t.scalar_type() == at::kLong, std::string(name) + " must be int32 or int64");
+}
+
+std::pair<Tensor, Tensor> direct_max_pool_fw(const Tensor &in_map_, const Tensor &out_map_, Tensor in_feat,
+                                             int64_t out_nrows, bool is_sorted) {
+  check_dpool_index("in_map", in_map_);
+  check_dpool_index("out_map", out_map_);
+  check(in_map_.dim() == 1 && out_map_.dim() == 1 && in_map_.numel() == out_map_.numel(),
+        "in_map and out_map must be 1-D tensors of equal length");
+  check(in_map_.scalar_type() == out_map_.scalar_type(), "in_map and out_map must have the same dtype");
+  in_feat = in_feat.contiguous();
+  check_feat_f("in_feat", in_feat);
+  check(in_feat.dim() == 2, "Invalid in_feat.dim()");
+  const c10::Device dev = in_feat.device();
+  check(in_map_.device() == dev && out_map_.device() == dev, "all inputs must be on the same device");
+  const Tensor in_map = in_map_.contiguous(), out_map = out_map_.contiguous();
+  check(out_nrows >= 0, "Invalid number of out nrows");
+  const int64_t n_in = in_feat.size(0), nmap = in_map.numel();
+  const int c = (int)in_feat.size(1);
+  Tensor out = at::empty({out_nrows, (int64_t)c}, in_feat.options());
+  Tensor mask = at::empty({out_nrows, (int64_t)c}, in_map.options());
+  if (out_nrows == 0 || c == 0) {
+    check(nmap == 0 || c == 0, "Invalid number of out nrows");
+    return {out, mask};
+  }
+  Tensor ws = workspace(me_direct_max_pool_workspace_bytes(nmap, out_nrows), dev);
+  const int ib = (int)in_map.element_size(), sorted = is_sorted ? 1 : 0;
+  c10::DeviceGuard guard(dev);
+  if (in_feat.scalar_type() == at::kDouble)
+    me_ok(me_direct_max_pool_f64(ptr<double>(in_feat), c, vptr(in_map), vptr(out_map), ib, nmap, n_in, out_nrows, sorted,
+                                 ptr<double>(out), vptr(mask), vptr(ws), ws.numel(), stream_of(dev)));
+  else if (in_feat.scalar_type() == at::kBFloat16)
+    me_ok(me_direct_max_pool_bf16(ptr<uint16_t>(in_feat), c, vptr(in_map), vptr(out_map), ib, nmap, n_in, out_nrows,
+                                  sorted, ptr<uint16_t>(out), vptr(mask), vptr(ws), ws.numel(), stream_of(dev)));
+  else
+    me_ok(me_direct_max_pool_f32(ptr<float>(in_feat), c, vptr(in_map), vptr(out_map), ib, nmap, n_in, out_nrows, sorted,
+                                 ptr<float>(out), vptr(mask), vptr(ws), ws.numel(), stream_of(dev)));
+  return {out, mask};
+}
+
+Tensor direct_max_pool_bw(Tensor grad_out, const Tensor &max_index_, int64_t in_nrows) {
+  check_dpool_index("max_index", max_index_);
+  grad_out = grad_out.contiguous();
+  check_feat_f("grad_out_feat", grad_out);
+  check(grad_out.dim() == 2 && max_index_.sizes() == grad_out.sizes(), "max_index must have the shape of grad_out_feat");
+  const c10::Device dev = grad_out.device();
+  check(max_index_.device() == dev, "all inputs must be on the same device");
+  const Tensor max_index = max_index_.contiguous();
+  check(in_nrows >= 0, "Invalid number of in nrows");
+  const int64_t n_out = grad_out.size(0);
+  const int c = (int)grad_out.size(1);
+  Tensor grad_in = at::empty({in_nrows, (int64_t)c}, grad_out.options());
+  if (in_nrows == 0 || c == 0) return grad_in;
+  Tensor ws = workspace(me_direct_max_pool_backward_workspace_bytes(n_out, c), dev);
+  const int ib = (int)max_index.element_size();
+  c10::DeviceGuard guard(dev);
+  if (grad_out.scalar_type() == at::kDouble)
+    me_ok(me_direct_max_pool_backward_f64(ptr<double>(grad_out), vptr(max_index), ib, n_out, c, in_nrows,
+                                          ptr<double>(grad_in), vptr(ws), ws.numel(), stream_of(dev)));
+  else if (grad_out.scalar_type() == at::kBFloat16)
+    me_ok(me_direct_max_pool_backward_bf16(ptr<uint16_t>(grad_out), vptr(max_index), ib, n_out, c, in_nrows,
+                                           ptr<uint16_t>(grad_in), vptr(ws), ws.numel(), stream_of(dev)));
+  else
+    me_ok(me_direct_max_pool_backward_f32(ptr<float>(grad_out), vptr(max_index), ib, n_out, c, in_nrows,
+                                          ptr<float>(grad_in), vptr(ws), ws.numel(), stream_of(dev)));
+  return grad_in;
 }
 
 }  // namespace meh

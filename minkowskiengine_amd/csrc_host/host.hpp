@@ -247,6 +247,8 @@ struct CoordinateMapManager {
   std::map<KeyT, Tensor> fields;
   std::map<std::pair<KeyT, KeyT>, std::pair<Tensor, Tensor>> field_maps;
   std::map<std::pair<KeyT, KeyT>, std::pair<Tensor, Tensor>> field_lookups;
+  std::vector<KeyT> field_order;                  // insertion order (origin_field(): the oldest field)
+  std::map<KeyT, Tensor> origin_field_rows_cache;  // field key -> int32 [N] origin rows (origin_field_map)
 
   CoordinateMapManager(int algorithm_ = 0, int num_threads_ = 0) : algorithm(algorithm_), num_threads(num_threads_) {}
 
@@ -283,6 +285,13 @@ struct CoordinateMapManager {
   std::tuple<KeyT, Tensor, Tensor> field_to_sparse_insert_and_map(const KeyT &field_key, const ivec &tensor_stride,
                                                                   const std::string &string_id);
   std::pair<Tensor, Tensor> field_to_sparse_map(const KeyT &field_key, const KeyT &sparse_key);
+  // origin map of fields (twin of backend.origin_field / _origin_field_rows / _is_field_input / _pool_rows)
+  bool exists_field(const KeyT &k) const { return fields.count(k) != 0; }
+  KeyT origin_field(const KeyT *field_key);
+  Tensor origin_field_rows(const KeyT &field_key);
+  bool is_field_input(const KeyT &k, int64_t n_rows) const;
+  std::pair<Tensor, KeyT> pool_rows(const KeyT &k, int64_t n_rows);
+  int64_t pool_size(const KeyT &k, int64_t n_rows) const;
   // (in_map, out_map, weights, rowptr [N + 1] by sample)
   std::tuple<Tensor, Tensor, Tensor, Tensor> interpolation_map(const KeyT &in_key, const Tensor &samples);
 };
@@ -347,6 +356,10 @@ Tensor coo_spmm(const Tensor &rows, const Tensor &cols, const Tensor &vals, int6
                 const Tensor &mat2);
 std::vector<Tensor> coo_spmm_average(const Tensor &rows, const Tensor &cols, int64_t dim_i, int64_t dim_j,
                                      const Tensor &mat2);
+// direct max pooling (field.cpp over csrc/direct_pool.hip; twin of backend.direct_max_pool_fw / direct_max_pool_bw)
+std::pair<Tensor, Tensor> direct_max_pool_fw(const Tensor &in_map, const Tensor &out_map, Tensor in_feat, int64_t out_nrows,
+                                             bool is_sorted);
+Tensor direct_max_pool_bw(Tensor grad_out, const Tensor &max_index, int64_t in_nrows);
 std::pair<Tensor, Tensor> global_pooling_forward(const Tensor &in_feat, int pooling_mode, CoordinateMapKey *in_key,
                                                  CoordinateMapKey *out_key, CoordinateMapManager *mgr);
 Tensor global_pooling_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &num_nonzero, int pooling_mode,

@@ -1212,6 +1212,7 @@ std::vector<Tensor> CoordinateMapManager::device_tensors() {
     }
   }
   for (auto &kv : origin_rows_cache) collect(out, kv.second);
+  for (auto &kv : origin_field_rows_cache) collect(out, kv.second);
   for (auto &kv : prune_rows) collect(out, kv.second);
   for (auto &kv : stride_maps) {
     collect(out, kv.second.first);

@@ -885,14 +885,13 @@ std::pair<Tensor, Tensor> global_pooling_forward(const Tensor &in_feat, int pool
   check_feat("in_feat", in_feat);
   check(in_feat.dim() == 2, "Invalid in_feat.dim()");
   const KeyT &ik = in_key->get();
-  check(mgr->exists(ik), "coordinate map not found");
-  check(in_feat.size(0) == mgr->get(ik)->n, "Invalid in_feat size");
+  check(mgr->exists(ik) || mgr->exists_field(ik), "coordinate map not found");
+  check(in_feat.size(0) == mgr->pool_size(ik, in_feat.size(0)), "Invalid in_feat size");
   const int m = global_mode(pooling_mode);
-  if (!out_key->key_set) {
-    KeyT ok = mgr->origin();
-    out_key->set_key(ok.first, ok.second);
-  }
-  Tensor rows = mgr->origin_rows(ik);
+  // a field key (src/global_pooling_gpu.cu:58, 74-85): origin_field() and the field's row table; same kernels
+  auto pr = mgr->pool_rows(ik, in_feat.size(0));
+  if (!out_key->key_set) out_key->set_key(pr.second.first, pr.second.second);
+  Tensor rows = pr.first;
   const int64_t n_batch = mgr->get(out_key->get())->n;
   auto r = global_pool(in_feat, Tensor(), rows, n_batch, m);
   return {std::get<0>(r), m == 2 ? std::get<1>(r) : std::get<2>(r)};
@@ -936,7 +935,7 @@ Tensor global_pooling_backward(const Tensor &in_feat, Tensor grad_out, const Ten
   if (m == 1)
     g = ((g.scalar_type() == at::kDouble ? g : g.to(at::kFloat)) / num_nonzero.clamp_min(1.0).unsqueeze(1))
             .to(in_feat.scalar_type()).contiguous();
-  Tensor rows = mgr->origin_rows(in_key->get());
+  Tensor rows = mgr->pool_rows(in_key->get(), n).first;
   return broadcast(Tensor(), g, rows, n, c, false);
 }
 
@@ -946,9 +945,9 @@ Tensor broadcast_forward(const Tensor &in_feat, const Tensor &in_feat_glob, int 
   check_feat("in_feat_glob", in_feat_glob);
   check(in_feat_glob.scalar_type() == in_feat.scalar_type(), "in_feat_glob must have the dtype of the input features");
   check(in_feat.size(1) == in_feat_glob.size(1), "feature sizes must match");
-  check(in_feat.size(0) == mgr->get(in_key->get())->n, "Invalid in_feat size");
+  check(in_feat.size(0) == mgr->pool_size(in_key->get(), in_feat.size(0)), "Invalid in_feat size");
+  Tensor rows = mgr->pool_rows(in_key->get(), in_feat.size(0)).first;   // (a field key: an extension of the reference)
   check(in_feat_glob.size(0) == mgr->get(glob_key->get())->n, "Invalid in_feat_glob size");
-  Tensor rows = mgr->origin_rows(in_key->get());
   return broadcast(in_feat, in_feat_glob, rows, in_feat.size(0), (int)in_feat.size(1), broadcast_mode == 1);
 }
 
@@ -961,7 +960,7 @@ std::pair<Tensor, Tensor> broadcast_backward(const Tensor &in_feat, const Tensor
   grad_out = grad_out.contiguous();
   check_feat("grad_out_feat", grad_out);
   if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
-  Tensor rows = mgr->origin_rows(in_key->get());
+  Tensor rows = mgr->pool_rows(in_key->get(), in_feat.size(0)).first;
   const int64_t n_batch = in_feat_glob.size(0);
   if (broadcast_mode == 0) {
     Tensor grad_glob = std::get<0>(global_pool(grad_out, Tensor(), rows, n_batch, 0));

@@ -1,6 +1,8 @@
 """Local / global pooling modules and their autograd Functions (reference:
 MinkowskiEngine/MinkowskiPooling.py:40-780).  The Functions resolve `LocalPooling{Forward,Backward}GPU`,
-`LocalPoolingTranspose*GPU` and `GlobalPooling*GPU` in the backend by name, as the reference does."""
+`LocalPoolingTranspose*GPU` and `GlobalPooling*GPU` in the backend by name, as the reference does.  The global
+pooling modules also take a TensorField (one row per point cloud, on the origin key), and
+MinkowskiDirectMaxPoolingFunction pools over an explicit (in_map, out_map) pair list."""
 import torch
 from torch.autograd import Function
 from torch.nn import Module
@@ -190,9 +192,17 @@ class MinkowskiGlobalPooling(Module):
         self.pooling = MinkowskiGlobalPoolingFunction
 
     def forward(self, input, coordinates=None):
-        assert isinstance(input, SparseTensor)
-        out_coordinate_map_key = _get_coordinate_map_key(input, coordinates)
-        output = self.pooling.apply(input.F, self.pooling_mode, input.coordinate_map_key, out_coordinate_map_key,
+        from .tensor_field import TensorField
+        if isinstance(input, TensorField):
+            # MinkowskiPooling.py:729-733 does this for the max module only; here every global pooling module takes a
+            # field: its key goes in, an unset key comes back as origin_field()
+            in_coordinate_map_key = input.coordinate_field_map_key
+            out_coordinate_map_key = _host.key_like(in_coordinate_map_key)
+        else:
+            assert isinstance(input, SparseTensor)
+            in_coordinate_map_key = input.coordinate_map_key
+            out_coordinate_map_key = _get_coordinate_map_key(input, coordinates)
+        output = self.pooling.apply(input.F, self.pooling_mode, in_coordinate_map_key, out_coordinate_map_key,
                                     input._manager)
         return SparseTensor(output, coordinate_map_key=out_coordinate_map_key,
                             coordinate_manager=input.coordinate_manager)
@@ -214,3 +224,30 @@ class MinkowskiGlobalAvgPooling(MinkowskiGlobalPooling):
 class MinkowskiGlobalMaxPooling(MinkowskiGlobalPooling):
     def __init__(self, mode=PoolingMode.GLOBAL_MAX_POOLING_PYTORCH_INDEX):
         super().__init__(mode=mode)
+
+
+class MinkowskiDirectMaxPoolingFunction(Function):
+    """out_feat[o] = channel-wise max of in_feat[in_map[e]] over the entries with out_map[e] == o
+    (MinkowskiPooling.py:752-781; csrc/direct_pool.hip).  Rows without an entry are zero and take no gradient; the
+    caller's maps are left as they are.  Per-voxel max of a TensorField `f`:
+
+        key, (_, inverse) = f.coordinate_manager.field_to_sparse_insert_and_map(f.coordinate_field_map_key, stride)
+        feats = MinkowskiDirectMaxPoolingFunction.apply(torch.arange(len(f), device=f.device), inverse, f.F, n_voxels)
+        voxels = SparseTensor(feats, coordinate_map_key=key, coordinate_manager=f.coordinate_manager)
+    """
+
+    @staticmethod
+    def forward(ctx, in_map, out_map, in_feat, out_nrows, is_sorted=False):
+        B = _host.backend()
+        out_feat, max_mask = B.direct_max_pool_fw(in_map, out_map, in_feat, out_nrows, is_sorted)
+        ctx.in_nrows = in_feat.size(0)
+        ctx.backend = B
+        ctx.save_for_backward(max_mask)
+        return out_feat
+
+    @staticmethod
+    def backward(ctx, grad_out_feat):
+        grad_out_feat = grad_out_feat.contiguous()
+        max_mask = ctx.saved_tensors[0]
+        grad = ctx.backend.direct_max_pool_bw(grad_out_feat, max_mask, ctx.in_nrows)
+        return None, None, grad, None, None

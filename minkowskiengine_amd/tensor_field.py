@@ -140,6 +140,7 @@ class TensorField:
         self._inverse_mapping = {}
         self._voxel_csrs = {}       # sparse key -> (rowptr, cols): the points of each voxel in field order
         self._splat = {}
+        self._batch_rows = None
 
     # ---- accessors (MinkowskiTensorField.py:252-285) ------------------------------------------------------------------
     @property
@@ -219,8 +220,14 @@ class TensorField:
 
     @property
     def _batchwise_row_indices(self):
-        batch = self.C[:, 0].round().long()
-        return [torch.nonzero(batch == b, as_tuple=False).flatten() for b in torch.unique(batch).tolist()]
+        # MinkowskiTensorField.py:276-281: the rows of each origin row (= batch index, ascending) from origin_field_map
+        if self._batch_rows is None:
+            rows = self._manager.origin_field_map(self.coordinate_field_map_key)[0][1].long()
+            n_batch = self._manager.size(self._manager.origin_field(self.coordinate_field_map_key))
+            order = torch.argsort(rows, stable=True)
+            counts = torch.bincount(rows, minlength=n_batch).tolist()
+            self._batch_rows = list(torch.split(order, counts))
+        return self._batch_rows
 
     @property
     def decomposed_coordinates(self):
@@ -239,8 +246,13 @@ class TensorField:
         if quantization_mode is None:
             quantization_mode = self.quantization_mode
         if quantization_mode == SparseTensorQuantizationMode.MAX_POOL:
-            raise NotImplementedError("MAX_POOL quantisation of a TensorField needs MinkowskiDirectMaxPoolingFunction, "
-                                      "which minkowskiengine_amd does not provide")
+            raise NotImplementedError(
+                "MAX_POOL quantisation of a TensorField is not wired to MinkowskiDirectMaxPoolingFunction yet; call it "
+                "directly:\n"
+                "    key, (_, inv) = mgr.field_to_sparse_insert_and_map(field.coordinate_field_map_key, tensor_stride)\n"
+                "    F = ME.MinkowskiDirectMaxPoolingFunction.apply(torch.arange(len(field), device=field.device), inv, "
+                "field.F, mgr.size(key))\n"
+                "    voxels = ME.SparseTensor(F, coordinate_map_key=key, coordinate_manager=mgr)")
         assert quantization_mode != SparseTensorQuantizationMode.SPLAT_LINEAR_INTERPOLATION, \
             "Please use .splat() for splat quantization."
         mgr = self._manager

@@ -75,7 +75,9 @@ typedef struct me_region {
  *   1.10 (200) round 10: dense <-> sparse conversion: cell indices, the row grid, the two movers, occupied cells and all
  *              cells of a box (me_dense_*)
  *   1.11 (210) round 11: direct max pooling over an (in_map, out_map) pair list (me_direct_max_pool_*) and the origin-map
- *              row table of a tensor field (me_field_origin_rows_f32) */
+ *              row table of a tensor field (me_field_origin_rows_f32)
+ *   1.12 (220) round 12: arithmetic between two sparse tensors on different coordinate maps: the row tables of a union
+ *              (me_union_tables) and the fused one-write-per-row forward / gather backward (me_union_arith_*) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -815,6 +817,51 @@ int me_direct_max_pool_backward_bf16(const uint16_t *grad_out_dev, const void *m
 int me_direct_max_pool_backward_f64(const double *grad_out_dev, const void *max_index_dev, int32_t index_bytes,
                                     int64_t out_nrows, int32_t c, int64_t in_nrows, double *grad_in_dev,
                                     void *workspace_dev, int64_t workspace_bytes, void *stream);
+
+/* Arithmetic across coordinate maps (MinkowskiTensor._binary_functor, MinkowskiTensor.py:511-546; csrc/union_arith.hip,
+ * ABI 1.12): out [nu, c] = a [na, c] (op) b [nb, c] on the union of the two maps.  Row tables, all int32:
+ * a_of_u / b_of_u [nu] = the row of a / b that lies on union row u, -1 = none; u_of_a [na] / u_of_b [nb] = the union row of
+ * every input row.
+ *   me_union_tables:  builds the four tables from the union rows of the inputs as union_map returns them (int64 [na],
+ *                     [nb], values in [0, nu); coordinates unique within an input).  A value outside [0, nu) becomes -1
+ *                     in u_of_* and is not scattered.  No sync, no workspace.
+ *   me_union_arith_*: every row of out is written exactly once with vector stores (16 bytes along c when c and the
+ *                     pointers allow): fn(a, b) where both hold the row, the row of `a` unchanged where only a holds it
+ *                     (for * and / as well), fn(0, b) where only b holds it, which is b, -b, 0 * b, 0 / b (NaN where b
+ *                     is 0).  No zero fill, no atomics, independent of the launch geometry: bitwise reproducible.  bf16
+ *                     combines in fp32 and rounds once.  Traffic: (na + nb + nu) * c * sizeof + 8 * nu bytes.
+ *   me_union_arith_backward_*: grad_a [na, c] and / or grad_b [nb, c] (NULL: not wanted, no launch): a gather of
+ *                     grad_out [nu, c] through u_of_a / u_of_b times the local derivative.  grad_a = g, g, g * b, g / b
+ *                     on shared rows and g elsewhere; grad_b = g, -g, g * x, -g * ((x / b) / b) with x = a's row or 0.
+ *                     a / b / a_of_u / b_of_u are read only where the operator needs them (NULL allowed for + and -).
+ *   Row counts < 2^31.  No sync. */
+#define ME_UNION_ADD 0
+#define ME_UNION_SUB 1
+#define ME_UNION_MUL 2
+#define ME_UNION_DIV 3
+int me_union_tables(const int64_t *a_union_dev, int64_t na, const int64_t *b_union_dev, int64_t nb, int64_t nu,
+                    int32_t *u_of_a_dev, int32_t *u_of_b_dev, int32_t *a_of_u_dev, int32_t *b_of_u_dev, void *stream);
+int me_union_arith_f32(const float *a_dev, const float *b_dev, int32_t c, const int32_t *a_of_u_dev,
+                       const int32_t *b_of_u_dev, int64_t na, int64_t nb, int64_t nu, int32_t op, float *out_dev,
+                       void *stream);
+int me_union_arith_bf16(const uint16_t *a_dev, const uint16_t *b_dev, int32_t c, const int32_t *a_of_u_dev,
+                        const int32_t *b_of_u_dev, int64_t na, int64_t nb, int64_t nu, int32_t op, uint16_t *out_dev,
+                        void *stream);
+int me_union_arith_f64(const double *a_dev, const double *b_dev, int32_t c, const int32_t *a_of_u_dev,
+                       const int32_t *b_of_u_dev, int64_t na, int64_t nb, int64_t nu, int32_t op, double *out_dev,
+                       void *stream);
+int me_union_arith_backward_f32(const float *grad_out_dev, const float *a_dev, const float *b_dev, int32_t c,
+                                const int32_t *u_of_a_dev, const int32_t *u_of_b_dev, const int32_t *a_of_u_dev,
+                                const int32_t *b_of_u_dev, int64_t na, int64_t nb, int64_t nu, int32_t op,
+                                float *grad_a_dev, float *grad_b_dev, void *stream);
+int me_union_arith_backward_bf16(const uint16_t *grad_out_dev, const uint16_t *a_dev, const uint16_t *b_dev, int32_t c,
+                                 const int32_t *u_of_a_dev, const int32_t *u_of_b_dev, const int32_t *a_of_u_dev,
+                                 const int32_t *b_of_u_dev, int64_t na, int64_t nb, int64_t nu, int32_t op,
+                                 uint16_t *grad_a_dev, uint16_t *grad_b_dev, void *stream);
+int me_union_arith_backward_f64(const double *grad_out_dev, const double *a_dev, const double *b_dev, int32_t c,
+                                const int32_t *u_of_a_dev, const int32_t *u_of_b_dev, const int32_t *a_of_u_dev,
+                                const int32_t *b_of_u_dev, int64_t na, int64_t nb, int64_t nu, int32_t op,
+                                double *grad_a_dev, double *grad_b_dev, void *stream);
 
 /* Generative / expanding convolutions (CoordinateMapCPU::stride_region, src/coordinate_map_cpu.hpp:446-487;
  * manager: src/coordinate_map_manager.cpp:436-466): candidate output coordinates = every kernel offset of the

@@ -34,6 +34,13 @@ from .kernel_generator import KernelGenerator, get_kernel_volume  # noqa: F401
 from .layers import (  # noqa: F401
     MinkowskiBatchNorm, MinkowskiDropout, MinkowskiELU, MinkowskiLeakyReLU, MinkowskiLinear, MinkowskiReLU,
     MinkowskiSigmoid, MinkowskiSyncBatchNorm, MinkowskiTanh, cat)
+from .layers import (  # noqa: F401  (the rest of MinkowskiNonlinearity.py)
+    MinkowskiAdaptiveLogSoftmaxWithLoss, MinkowskiAlphaDropout, MinkowskiCELU, MinkowskiGELU, MinkowskiHardshrink,
+    MinkowskiHardsigmoid, MinkowskiHardswish, MinkowskiHardtanh, MinkowskiLogSigmoid, MinkowskiLogSoftmax, MinkowskiPReLU,
+    MinkowskiReLU6, MinkowskiRReLU, MinkowskiSELU, MinkowskiSiLU, MinkowskiSinusoidal, MinkowskiSoftmax, MinkowskiSoftmin,
+    MinkowskiSoftplus, MinkowskiSoftshrink, MinkowskiSoftsign, MinkowskiTanhshrink, MinkowskiThreshold)
+from . import MinkowskiFunctional  # noqa: F401
+from .arithmetic import MinkowskiUnionArithmeticFunction, union_arithmetic  # noqa: F401
 from .pooling import (  # noqa: F401
     MinkowskiAvgPooling, MinkowskiDirectMaxPoolingFunction, MinkowskiGlobalAvgPooling, MinkowskiGlobalMaxPooling, MinkowskiGlobalPooling,
     MinkowskiGlobalPoolingFunction, MinkowskiGlobalSumPooling, MinkowskiLocalPoolingFunction,

@@ -247,6 +247,13 @@ SIGNATURES = {
     "me_direct_max_pool_backward_f32": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "me_direct_max_pool_backward_bf16": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "me_direct_max_pool_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "me_union_tables": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "me_union_arith_f32": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    "me_union_arith_bf16": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    "me_union_arith_f64": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    "me_union_arith_backward_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "me_union_arith_backward_bf16": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "me_union_arith_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "me_csr_from_coo_workspace_bytes": (c_i64, [c_i64]),
     "me_csr_from_coo": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "me_csr_gather_f32": (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),

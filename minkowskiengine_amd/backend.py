@@ -703,6 +703,7 @@ class CoordinateMapManagerGPU_c10:
         self._kernel_maps = {}   # kernel_map_key (src/types.hpp:183-192) -> KernelMapGPU
         self._origin_maps = {}
         self._prune_rows = {}
+        self._union_arith = {}   # (key a, key b), ordered -> (union key, u_of_a, u_of_b, a_of_u, b_of_u): union_arith_maps
         self._stride_maps = {}
         self._fields = {}        # field key tuple -> fp32 coordinates [N, D+1]
         self._field_maps = {}    # (field key, sparse key) -> (unique_index, inverse_mapping): field_to_sparse_insert_and_map
@@ -927,6 +928,31 @@ class CoordinateMapManagerGPU_c10:
             out.append(torch.stack((rows, inverse[s0:s0 + m.n])))
             s0 += m.n
         return out
+
+    def union_arith_maps(self, key_a, key_b):
+        """-> (union key, u_of_a int32 [Na], u_of_b int32 [Nb], a_of_u int32 [Nu], b_of_u int32 [Nu]): the union of the
+        two maps (rows of `key_a` first, as union_map orders them) and the row tables of arithmetic across them
+        (me_union_tables): the union row of every input row and, per union row, the row of each input or -1.  Not in
+        the reference, which registers a fresh union map for every operator call: the map build is an insert of
+        Na + Nb coordinates, far dearer than the arithmetic, so the result is kept per ORDERED pair of keys and a
+        second `a (op) b` on the pair builds nothing and returns the same key."""
+        pair = (self._k(key_a), self._k(key_b))
+        hit = self._union_arith.get(pair)
+        if hit is not None:
+            return (CoordinateMapKey(list(hit[0][0]), hit[0][1]),) + hit[1:]
+        out_key = CoordinateMapKey(len(pair[0][0]) + 1)
+        ma, mb = self.union_map([key_a, key_b], out_key)
+        a_union, b_union = ma[1].contiguous(), mb[1].contiguous()
+        na, nb, nu = int(a_union.numel()), int(b_union.numel()), self.size(out_key)
+        dev = a_union.device
+        u_of_a, u_of_b, a_of_u, b_of_u = (torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+                                          for n in (na, nb, nu, nu))
+        lib = _lib.load()
+        with _on(dev):
+            _lib.check(lib.me_union_tables(_ptr(a_union), na, _ptr(b_union), nb, nu, _ptr(u_of_a), _ptr(u_of_b),
+                                           _ptr(a_of_u), _ptr(b_of_u), _stream(dev)))
+        self._union_arith[pair] = (self._k(out_key), u_of_a, u_of_b, a_of_u, b_of_u)
+        return out_key, u_of_a, u_of_b, a_of_u, b_of_u
 
     def get_coordinates(self, key):
         return self._get(key).coords
@@ -1266,7 +1292,7 @@ class CoordinateMapManagerGPU_c10:
                     if name not in ("_recipe", "in_map", "out_map"):
                         walk(getattr(o, name, None), depth + 1)
         for store in (self._maps, self._kernel_maps, self._origin_maps, self._origin_field_maps, self._prune_rows,
-                      self._stride_maps):
+                      self._stride_maps, self._union_arith):
             walk(store)
         return out
 
@@ -2578,6 +2604,76 @@ def direct_max_pool_bw(grad_out_feat, max_index, in_nrows):
             _ptr(grad_out_feat), _ptr(max_index), max_index.element_size(), n_out, c, in_nrows, _ptr(grad_in), _ptr(ws),
             ws.numel(), _stream(dev))))
     return grad_in
+
+
+UNION_ARITH_OPS = {"add": 0, "sub": 1, "mul": 2, "div": 3}     # ME_UNION_ADD .. ME_UNION_DIV (include/me_amd.h)
+
+
+def _check_union_table(name, t, n, dev):
+    _check(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous(),
+           name, "must be a contiguous 1-D int32 CUDA (ROCm) tensor")
+    _check(t.numel() == n and t.device == dev, name, "must have", n, "rows on the device of the features")
+
+
+def _union_arith_op(op):
+    _check(op in UNION_ARITH_OPS, "op must be one of", sorted(UNION_ARITH_OPS), "got", op)
+    return UNION_ARITH_OPS[op]
+
+
+def union_arith_fw(a_feat, b_feat, a_of_u, b_of_u, op):
+    """MinkowskiTensor.py:511-546 in one pass (csrc/union_arith.hip) -> out [Nu, C]: fn(a, b) on the rows both tensors
+    hold, a's row unchanged where only a holds it, fn(0, b) where only b does.  a_of_u / b_of_u: int32 [Nu], the row of
+    each input on every union row or -1 (union_arith_maps).  `op`: "add" | "sub" | "mul" | "div"."""
+    code = _union_arith_op(op)
+    a_feat, b_feat = a_feat.contiguous(), b_feat.contiguous()
+    _check_feat("a_feat", a_feat)
+    _check_feat("b_feat", b_feat)
+    _check(a_feat.dim() == 2 and b_feat.dim() == 2, "features must be 2-D")
+    _check(a_feat.shape[1] == b_feat.shape[1], "channel counts differ:", a_feat.shape[1], b_feat.shape[1])
+    _check(a_feat.dtype == b_feat.dtype, "feature dtypes differ:", a_feat.dtype, b_feat.dtype)
+    dev = a_feat.device
+    _check(b_feat.device == dev, "all inputs must be on the same device")
+    nu = int(a_of_u.numel())
+    _check_union_table("a_of_u", a_of_u, nu, dev)
+    _check_union_table("b_of_u", b_of_u, nu, dev)
+    na, nb, c = int(a_feat.shape[0]), int(b_feat.shape[0]), int(a_feat.shape[1])
+    out = torch.empty((nu, c), dtype=a_feat.dtype, device=dev)
+    if nu == 0 or c == 0:
+        return out
+    lib = _lib.load()
+    fn = _by_dtype(lib, "union_arith", a_feat)
+    with _on(dev):
+        _timed("union_arith", dev, lambda: _lib.check(fn(_ptr(a_feat), _ptr(b_feat), c, _ptr(a_of_u), _ptr(b_of_u), na,
+                                                         nb, nu, code, _ptr(out), _stream(dev))))
+    return out
+
+
+def union_arith_bw(grad_out, a_feat, b_feat, u_of_a, u_of_b, a_of_u, b_of_u, op, need_grad_a=True, need_grad_b=True):
+    """-> (grad_a [Na, C] | None, grad_b [Nb, C] | None): each wanted gradient is one gather of grad_out through the
+    input's union rows times the local derivative (one launch each; nothing is summed)."""
+    code = _union_arith_op(op)
+    grad_out, a_feat, b_feat = grad_out.contiguous(), a_feat.contiguous(), b_feat.contiguous()
+    for name, t in (("grad_out", grad_out), ("a_feat", a_feat), ("b_feat", b_feat)):
+        _check_feat(name, t)
+        _check(t.dim() == 2 and t.shape[1] == grad_out.shape[1] and t.dtype == grad_out.dtype
+               and t.device == grad_out.device, name, "must match grad_out in channels, dtype and device")
+    dev = grad_out.device
+    na, nb, nu, c = int(a_feat.shape[0]), int(b_feat.shape[0]), int(grad_out.shape[0]), int(grad_out.shape[1])
+    _check_union_table("u_of_a", u_of_a, na, dev)
+    _check_union_table("u_of_b", u_of_b, nb, dev)
+    _check_union_table("a_of_u", a_of_u, nu, dev)
+    _check_union_table("b_of_u", b_of_u, nu, dev)
+    grad_a = torch.empty_like(a_feat) if need_grad_a else None
+    grad_b = torch.empty_like(b_feat) if need_grad_b else None
+    if c == 0 or not (need_grad_a or need_grad_b):
+        return grad_a, grad_b
+    lib = _lib.load()
+    fn = _by_dtype(lib, "union_arith_backward", grad_out)
+    with _on(dev):
+        _timed("union_arith_backward", dev, lambda: _lib.check(fn(
+            _ptr(grad_out), _ptr(a_feat), _ptr(b_feat), c, _ptr(u_of_a), _ptr(u_of_b), _ptr(a_of_u), _ptr(b_of_u), na, nb,
+            nu, code, _ptr(grad_a) if need_grad_a else None, _ptr(grad_b) if need_grad_b else None, _stream(dev))))
+    return grad_a, grad_b
 
 
 _GLOBAL_SUM = (PoolingMode.GLOBAL_SUM_POOLING_DEFAULT, PoolingMode.GLOBAL_SUM_POOLING_KERNEL,

@@ -330,6 +330,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              for (auto *k : in_keys) ks.push_back(keyt(k));
              return s.union_map(ks, out_key);
            })
+      .def("union_arith_maps",
+           [](CoordinateMapManager &s, const CoordinateMapKey *key_a, const CoordinateMapKey *key_b) {
+             const auto &r = s.union_arith_maps(keyt(key_a), keyt(key_b));
+             return py::make_tuple(py::cast(new_key(r.first), py::return_value_policy::take_ownership), r.second[0],
+                                   r.second[1], r.second[2], r.second[3]);
+           })
       .def("prune", [](CoordinateMapManager &s, const CoordinateMapKey *k, const Tensor &keep) {
              return new_key(s.prune(keyt(k), keep));
            }, py::return_value_policy::take_ownership)
@@ -552,6 +558,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         },
         py::arg("in_map"), py::arg("out_map"), py::arg("in_feat"), py::arg("out_nrows"), py::arg("is_sorted") = false);
   m.def("direct_max_pool_bw", &direct_max_pool_bw, py::arg("grad_out_feat"), py::arg("max_index"), py::arg("in_nrows"));
+  m.def("union_arith_fw", &union_arith_fw, py::arg("a_feat"), py::arg("b_feat"), py::arg("a_of_u"), py::arg("b_of_u"),
+        py::arg("op"));
+  m.def("union_arith_bw",
+        [](const Tensor &grad_out, const Tensor &a_feat, const Tensor &b_feat, const Tensor &u_of_a, const Tensor &u_of_b,
+           const Tensor &a_of_u, const Tensor &b_of_u, const std::string &op, bool need_grad_a, bool need_grad_b) {
+          auto r = union_arith_bw(grad_out, a_feat, b_feat, u_of_a, u_of_b, a_of_u, b_of_u, op, need_grad_a, need_grad_b);
+          return py::make_tuple(r.first.defined() ? py::cast(r.first) : py::none(),
+                                r.second.defined() ? py::cast(r.second) : py::none());
+        },
+        py::arg("grad_out"), py::arg("a_feat"), py::arg("b_feat"), py::arg("u_of_a"), py::arg("u_of_b"), py::arg("a_of_u"),
+        py::arg("b_of_u"), py::arg("op"), py::arg("need_grad_a") = true, py::arg("need_grad_b") = true);
   m.def("GlobalPoolingForwardGPU",
         [](const Tensor &in_feat, const py::object &pooling_mode, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
            CoordinateMapManager *mgr) {

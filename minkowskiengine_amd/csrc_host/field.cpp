@@ -344,4 +344,94 @@ Tensor direct_max_pool_bw(Tensor grad_out, const Tensor &max_index_, int64_t in_
   return grad_in;
 }
 
+// ---- arithmetic across coordinate maps (csrc/union_arith.hip) ----------------------------------------------------------
+int union_arith_op(const std::string &op) {
+  if (op == "add") return ME_UNION_ADD;
+  if (op == "sub") return ME_UNION_SUB;
+  if (op == "mul") return ME_UNION_MUL;
+  check(op == "div", "op must be one of add, sub, mul, div");
+  return ME_UNION_DIV;
+}
+
+static void check_union_table(const char *name, const Tensor &t, int64_t n, const c10::Device &dev) {
+  check(t.defined() && t.is_cuda() && t.scalar_type() == at::kInt && t.dim() == 1 && t.is_contiguous(),
+        std::string(name) + " must be a contiguous 1-D int32 CUDA (ROCm) tensor");
+  check(t.numel() == n && t.device() == dev,
+        std::string(name) + " must have " + std::to_string(n) + " rows on the device of the features");
+}
+
+Tensor union_arith_fw(Tensor a_feat, Tensor b_feat, const Tensor &a_of_u, const Tensor &b_of_u, const std::string &op) {
+  const int code = union_arith_op(op);
+  a_feat = a_feat.contiguous();
+  b_feat = b_feat.contiguous();
+  check_feat_f("a_feat", a_feat);
+  check_feat_f("b_feat", b_feat);
+  check(a_feat.dim() == 2 && b_feat.dim() == 2, "features must be 2-D");
+  check(a_feat.size(1) == b_feat.size(1), "channel counts differ");
+  check(a_feat.scalar_type() == b_feat.scalar_type(), "feature dtypes differ");
+  const c10::Device dev = a_feat.device();
+  check(b_feat.device() == dev, "all inputs must be on the same device");
+  const int64_t nu = a_of_u.defined() ? a_of_u.numel() : 0;
+  check_union_table("a_of_u", a_of_u, nu, dev);
+  check_union_table("b_of_u", b_of_u, nu, dev);
+  const int64_t na = a_feat.size(0), nb = b_feat.size(0);
+  const int c = (int)a_feat.size(1);
+  Tensor out = at::empty({nu, (int64_t)c}, a_feat.options());
+  if (nu == 0 || c == 0) return out;
+  c10::DeviceGuard guard(dev);
+  if (a_feat.scalar_type() == at::kDouble)
+    me_ok(me_union_arith_f64(ptr<double>(a_feat), ptr<double>(b_feat), c, ptr<int32_t>(a_of_u), ptr<int32_t>(b_of_u), na,
+                             nb, nu, code, ptr<double>(out), stream_of(dev)));
+  else if (a_feat.scalar_type() == at::kBFloat16)
+    me_ok(me_union_arith_bf16(ptr<uint16_t>(a_feat), ptr<uint16_t>(b_feat), c, ptr<int32_t>(a_of_u), ptr<int32_t>(b_of_u),
+                              na, nb, nu, code, ptr<uint16_t>(out), stream_of(dev)));
+  else
+    me_ok(me_union_arith_f32(ptr<float>(a_feat), ptr<float>(b_feat), c, ptr<int32_t>(a_of_u), ptr<int32_t>(b_of_u), na, nb,
+                             nu, code, ptr<float>(out), stream_of(dev)));
+  return out;
+}
+
+std::pair<Tensor, Tensor> union_arith_bw(Tensor grad_out, Tensor a_feat, Tensor b_feat, const Tensor &u_of_a,
+                                         const Tensor &u_of_b, const Tensor &a_of_u, const Tensor &b_of_u,
+                                         const std::string &op, bool need_grad_a, bool need_grad_b) {
+  const int code = union_arith_op(op);
+  grad_out = grad_out.contiguous();
+  a_feat = a_feat.contiguous();
+  b_feat = b_feat.contiguous();
+  check_feat_f("grad_out", grad_out);
+  check(grad_out.dim() == 2, "grad_out must be 2-D");
+  for (const Tensor *t : {&a_feat, &b_feat}) {
+    check_feat_f("a_feat / b_feat", *t);
+    check(t->dim() == 2 && t->size(1) == grad_out.size(1) && t->scalar_type() == grad_out.scalar_type() &&
+              t->device() == grad_out.device(),
+          "a_feat and b_feat must match grad_out in channels, dtype and device");
+  }
+  const c10::Device dev = grad_out.device();
+  const int64_t na = a_feat.size(0), nb = b_feat.size(0), nu = grad_out.size(0);
+  const int c = (int)grad_out.size(1);
+  check_union_table("u_of_a", u_of_a, na, dev);
+  check_union_table("u_of_b", u_of_b, nb, dev);
+  check_union_table("a_of_u", a_of_u, nu, dev);
+  check_union_table("b_of_u", b_of_u, nu, dev);
+  Tensor grad_a, grad_b;
+  if (need_grad_a) grad_a = at::empty_like(a_feat);
+  if (need_grad_b) grad_b = at::empty_like(b_feat);
+  if (c == 0 || !(need_grad_a || need_grad_b)) return {grad_a, grad_b};
+  c10::DeviceGuard guard(dev);
+  if (grad_out.scalar_type() == at::kDouble)
+    me_ok(me_union_arith_backward_f64(ptr<double>(grad_out), ptr<double>(a_feat), ptr<double>(b_feat), c,
+                                      ptr<int32_t>(u_of_a), ptr<int32_t>(u_of_b), ptr<int32_t>(a_of_u), ptr<int32_t>(b_of_u),
+                                      na, nb, nu, code, ptr<double>(grad_a), ptr<double>(grad_b), stream_of(dev)));
+  else if (grad_out.scalar_type() == at::kBFloat16)
+    me_ok(me_union_arith_backward_bf16(ptr<uint16_t>(grad_out), ptr<uint16_t>(a_feat), ptr<uint16_t>(b_feat), c,
+                                       ptr<int32_t>(u_of_a), ptr<int32_t>(u_of_b), ptr<int32_t>(a_of_u),
+                                       ptr<int32_t>(b_of_u), na, nb, nu, code, ptr<uint16_t>(grad_a), ptr<uint16_t>(grad_b),
+                                       stream_of(dev)));
+  else
+    me_ok(me_union_arith_backward_f32(ptr<float>(grad_out), ptr<float>(a_feat), ptr<float>(b_feat), c, ptr<int32_t>(u_of_a),
+                                      ptr<int32_t>(u_of_b), ptr<int32_t>(a_of_u), ptr<int32_t>(b_of_u), na, nb, nu, code,
+                                      ptr<float>(grad_a), ptr<float>(grad_b), stream_of(dev)));
+  return {grad_a, grad_b};
+}
+
 }  // namespace meh

@@ -241,6 +241,8 @@ struct CoordinateMapManager {
   std::map<KeyT, Tensor> origin_rows_cache;
   std::map<std::pair<KeyT, KeyT>, Tensor> prune_rows;
   std::map<std::pair<KeyT, KeyT>, std::pair<Tensor, Tensor>> stride_maps;
+  // arithmetic across maps: ORDERED (key a, key b) -> union key and {u_of_a, u_of_b, a_of_u, b_of_u} (union_arith_maps)
+  std::map<std::pair<KeyT, KeyT>, std::pair<KeyT, std::vector<Tensor>>> union_arith;
   // tensor fields (field.cpp): fp32 coordinates per field key (a namespace of its own, as in the reference) and the
   // field -> sparse maps per (field key, sparse key): field_maps (unique_index, inverse_mapping) of
   // field_to_sparse_insert_and_map, field_lookups (sparse rows, field rows) of field_to_sparse_map, kept apart
@@ -267,6 +269,9 @@ struct CoordinateMapManager {
   KeyT prune(const KeyT &in_key, const Tensor &keep);
   Tensor pruning_rows(const KeyT &in_key, const KeyT &out_key);
   std::vector<Tensor> union_map(const std::vector<KeyT> &in_keys, CoordinateMapKey *out_key);
+  // union of two maps and the int32 row tables of arithmetic across them, cached per ordered pair (twin of
+  // backend.union_arith_maps; not in the reference, which registers a fresh union map on every operator call)
+  const std::pair<KeyT, std::vector<Tensor>> &union_arith_maps(const KeyT &key_a, const KeyT &key_b);
   KeyT origin();
   Tensor origin_rows(const KeyT &in_key);
   std::shared_ptr<KernelMap> kernel_map(const KeyT &in_key, const KeyT &out_key, const ivec &kernel_size,
@@ -360,6 +365,12 @@ std::vector<Tensor> coo_spmm_average(const Tensor &rows, const Tensor &cols, int
 std::pair<Tensor, Tensor> direct_max_pool_fw(const Tensor &in_map, const Tensor &out_map, Tensor in_feat, int64_t out_nrows,
                                              bool is_sorted);
 Tensor direct_max_pool_bw(Tensor grad_out, const Tensor &max_index, int64_t in_nrows);
+// arithmetic across coordinate maps (field.cpp over csrc/union_arith.hip; twin of backend.union_arith_fw / union_arith_bw)
+int union_arith_op(const std::string &op);
+Tensor union_arith_fw(Tensor a_feat, Tensor b_feat, const Tensor &a_of_u, const Tensor &b_of_u, const std::string &op);
+std::pair<Tensor, Tensor> union_arith_bw(Tensor grad_out, Tensor a_feat, Tensor b_feat, const Tensor &u_of_a,
+                                         const Tensor &u_of_b, const Tensor &a_of_u, const Tensor &b_of_u,
+                                         const std::string &op, bool need_grad_a, bool need_grad_b);
 std::pair<Tensor, Tensor> global_pooling_forward(const Tensor &in_feat, int pooling_mode, CoordinateMapKey *in_key,
                                                  CoordinateMapKey *out_key, CoordinateMapManager *mgr);
 Tensor global_pooling_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &num_nonzero, int pooling_mode,

@@ -956,6 +956,24 @@ std::vector<Tensor> CoordinateMapManager::union_map(const std::vector<KeyT> &in_
   return out;
 }
 
+const std::pair<KeyT, std::vector<Tensor>> &CoordinateMapManager::union_arith_maps(const KeyT &key_a, const KeyT &key_b) {
+  auto it = union_arith.find({key_a, key_b});
+  if (it != union_arith.end()) return it->second;
+  CoordinateMapKey out_key((int)key_a.first.size() + 1);
+  std::vector<Tensor> ms = union_map({key_a, key_b}, &out_key);
+  const Tensor a_union = ms[0].select(0, 1).contiguous(), b_union = ms[1].select(0, 1).contiguous();
+  const int64_t na = a_union.numel(), nb = b_union.numel(), nu = get(out_key.get())->n;
+  const c10::Device dev = a_union.device();
+  std::vector<Tensor> t;
+  for (int64_t n : {na, nb, nu, nu}) t.push_back(empty_i32({n > 0 ? n : 1}, dev).narrow(0, 0, n));
+  {
+    c10::DeviceGuard guard(dev);
+    me_ok(me_union_tables(ptr<int64_t>(a_union), na, ptr<int64_t>(b_union), nb, nu, ptr<int32_t>(t[0]), ptr<int32_t>(t[1]),
+                          ptr<int32_t>(t[2]), ptr<int32_t>(t[3]), stream_of(dev)));
+  }
+  return union_arith[{key_a, key_b}] = {out_key.get(), t};
+}
+
 KeyT CoordinateMapManager::origin() {
   check(!maps.empty(), "origin() needs at least one coordinate map");
   const size_t D = map_order.front().first.size();
@@ -1214,6 +1232,8 @@ std::vector<Tensor> CoordinateMapManager::device_tensors() {
   for (auto &kv : origin_rows_cache) collect(out, kv.second);
   for (auto &kv : origin_field_rows_cache) collect(out, kv.second);
   for (auto &kv : prune_rows) collect(out, kv.second);
+  for (auto &kv : union_arith)
+    for (const Tensor &t : kv.second.second) collect(out, t);
   for (auto &kv : stride_maps) {
     collect(out, kv.second.first);
     collect(out, kv.second.second);

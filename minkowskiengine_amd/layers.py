@@ -244,6 +244,39 @@ class MinkowskiDropout(_Elementwise):
     MODULE = nn.Dropout
 
 
+# The rest of MinkowskiNonlinearity.py: one class per torch module, applied to the feature matrix and re-wrapped on the
+# input's coordinates (thin torch wrappers as in the reference, no kernels of their own).  The wrapped module
+# is `self.module`, so state-dict keys are `module.*` as in the reference.  Modules with a `dim` (the softmax family)
+# see [N, C]: dim=1 is the channel axis.
+def _elementwise(name, module):
+    return type(name, (_Elementwise,), {"MODULE": module, "__module__": __name__,
+                                        "__doc__": f"torch.nn.{module.__name__} on the features"})
+
+
+_NONLINEARITIES = ("PReLU", "ReLU6", "RReLU", "SELU", "CELU", "GELU", "SiLU", "Hardshrink", "Hardsigmoid", "Hardtanh",
+                   "Hardswish", "LogSigmoid", "Softplus", "Softshrink", "Softsign", "Tanhshrink", "Threshold", "Softmin",
+                   "Softmax", "LogSoftmax", "AdaptiveLogSoftmaxWithLoss", "AlphaDropout")
+for _n in _NONLINEARITIES:
+    globals()["Minkowski" + _n] = _elementwise("Minkowski" + _n, getattr(nn, _n))
+del _n
+
+
+class MinkowskiSinusoidal(nn.Module):
+    """coef * sin(F @ kernel + bias): a learned sinusoidal embedding of the features (parameters `kernel`
+    [in_channel, out_channel], `bias` and `coef` [1, out_channel], uniform in [0, 1) as in the reference)."""
+
+    def __init__(self, in_channel, out_channel):
+        super().__init__()
+        self.in_channel = in_channel
+        self.out_channel = out_channel
+        self.kernel = nn.Parameter(torch.rand(in_channel, out_channel))
+        self.bias = nn.Parameter(torch.rand(1, out_channel))
+        self.coef = nn.Parameter(torch.rand(1, out_channel))
+
+    def forward(self, input):
+        return _rewrap(input, torch.sin(input.F.mm(self.kernel) + self.bias) * self.coef)
+
+
 class MinkowskiLinear(nn.Module):
     def __init__(self, in_features, out_features, bias=True):
         super().__init__()

@@ -273,13 +273,13 @@ class SparseTensor:
             sparse_tensor = torch.sparse_coo_tensor(new_coords.t(), self._F, size)
         return sparse_tensor, min_coords, torch.IntTensor(self.tensor_stride)
 
-    # ---- arithmetic between tensors that share a coordinate map (MinkowskiTensor.py:390-520) -----
+    # ---- arithmetic between tensors: on a shared coordinate map, or on the union of two (MinkowskiTensor.py:390-546) -----
     def _binary(self, other, op):
         if isinstance(other, SparseTensor):
             assert other._manager is self._manager, "coordinate managers must match"
             if self.coordinate_map_key != other.coordinate_map_key:
-                raise NotImplementedError("binary operations across different coordinate maps (union maps) are "
-                                          "outside the hot path")
+                from .arithmetic import union_arithmetic      # the union of the two maps (csrc/union_arith.hip)
+                return union_arithmetic(self, other, op)
             return SparseTensor(op(self._F, other._F), coordinate_map_key=self.coordinate_map_key,
                                 coordinate_manager=self._manager)
         return SparseTensor(op(self._F, other), coordinate_map_key=self.coordinate_map_key,

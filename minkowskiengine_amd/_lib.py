@@ -289,6 +289,7 @@ DEBUG_SIGNATURES = {
     "me_debug_set_bf16_ws_depth": (None, [ctypes.c_int]),
     "me_debug_set_bf16_ws_ncw": (None, [ctypes.c_int]),
     "me_debug_set_rowwise_groups": (None, [ctypes.c_int]),
+    "me_debug_set_rowwise_items_per_wg": (None, [ctypes.c_int]),
     "me_debug_set_insert_fused": (None, [ctypes.c_int]),
     "me_debug_ws_timing": (ctypes.c_int, [c_vp, c_i32]),
     "me_debug_set_bf16_offsync": (None, [ctypes.c_int]),

@@ -431,7 +431,8 @@ class KernelMapGPU:
         self._launch_cache = {}               # per view: launch geometry and device addresses of the plans
         self._recipe, self._recipe_key = None, None   # the owning manager's request log (CoordinateMapManager.prefetch)
         # sides on which a row has AT MOST one pair by construction (bit 0: "in" rows, bit 1: "out" rows; csrc_host twin:
-        # KernelMap::one_pair_sides) — with n_pairs == rows of the side: exactly one -> row-wise launch (conv_rowwise.hip)
+        # KernelMap::one_pair_sides) for coordinates aligned to their tensor stride — with n_pairs == rows of the side
+        # and rows_are_permutation(): exactly one -> row-wise launch (conv_rowwise.hip)
         self.one_pair_sides = 0
 
     @property
@@ -467,6 +468,28 @@ class KernelMapGPU:
                           in_map=self.out_map, out_map=self.in_map)
         km.one_pair_sides = ((self.one_pair_sides & 1) << 1) | ((self.one_pair_sides >> 1) & 1)
         return km
+
+    def rows_are_permutation(self, target):
+        """Does the pair list name every row of the `target` side exactly once?  "At most one pair per row by
+        construction" (one_pair_sides) holds for coarse coordinates that are multiples of the coarse tensor stride, which
+        nothing enforces (SparseTensor(..., tensor_stride=2) takes odd coordinates, as the reference does): unaligned
+        windows overlap, and a row may have two pairs while another has none at n_pairs == rows.  Checked once per
+        (kernel map, side) on the device — a flag per row, scattered and reduced, one read-back where the first launch
+        waits for n_pairs anyway — and kept with the buffers both views share.  The K = 1 identity map is arange."""
+        if self.in_pairs_buf is self.out_pairs_buf:
+            return True
+        name = self._name("perm", target)
+        ok = self._store.get(name)
+        if ok is None:
+            rows = self.out_pairs if target == "out" else self.in_pairs
+            n_tgt = self.n_out if target == "out" else self.n_in
+            ok = rows.numel() == n_tgt
+            if ok and n_tgt:
+                seen = torch.zeros(n_tgt, dtype=torch.bool, device=rows.device)
+                seen[rows.long()] = True
+                ok = bool(seen.all())
+            self._store[name] = ok
+        return ok
 
     def table_pos(self, target):
         """(table, order): table [volume, n_tgt] of source ROWS indexed by target POSITION, order int32 [n_tgt]
@@ -1541,7 +1564,8 @@ def _rowwise_cfg(km, target, n_tgt, c_src, c_dst):
     cfg = km._launch_cache.get(ck)
     if cfg is None:
         lib = _lib.load()
-        ok = bool(lib.me_conv_rowwise_supported_bf16(km.volume, c_src, c_dst)) and km.n_pairs == n_tgt
+        ok = bool(lib.me_conv_rowwise_supported_bf16(km.volume, c_src, c_dst)) and km.n_pairs == n_tgt and \
+            km.rows_are_permutation(target)
         src_rows = km.in_pairs_buf if target == "out" else km.out_pairs_buf
         tgt_rows = km.out_pairs_buf if target == "out" else km.in_pairs_buf
         cfg = km._launch_cache[ck] = (src_rows, tgt_rows, int(lib.me_conv_packed_weight_elems_bf16(km.volume, c_src, c_dst))) \

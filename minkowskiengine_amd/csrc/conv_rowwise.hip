@@ -33,6 +33,36 @@ namespace me {
 
 constexpr int kRwMaxLds = 64 * 1024;  // W[k] of one column slab (policy: beyond it one workgroup per CU is left and the tile-plan kernel wins)
 
+// Element offset WITHIN ITS SOURCE ROW of the 16 bytes (8 channels) that lane quad q requests at ring position sp of an
+// item of `steps` real 32-channel steps, padded to steps_pad (a multiple of the ring depth): positions >= steps_pad are
+// the first steps of the NEXT item.  A padding step and channels beyond the row (c_src no multiple of 32) read the row's
+// first 16 bytes instead: a valid address whose value is never used / masked at use.
+constexpr __host__ __device__ int rw_x_offset(int c_src, int steps, int steps_pad, int q, int sp) {
+  const int s = sp >= steps_pad ? sp - steps_pad : sp;
+  const int o = s * 32 + q * 8;
+  return (s < steps && o < c_src) ? o : 0;
+}
+
+// every request stays inside its row: offset + 8 <= c_src for every supported c_src, every step count the LDS policy
+// admits (steps x 2 blocks x 1 KB <= kRwMaxLds), both ring depths and every ring position a workgroup asks for
+template <int Q>
+constexpr bool rw_x_offsets_in_row() {
+  for (int c_src = 8; c_src <= kRwMaxLds / 2048 * 32; c_src += 8)
+    for (int steps = (c_src + 31) / 32; steps <= kRwMaxLds / 2048; ++steps) {
+      const int d = steps <= 2 ? 2 : 4, steps_pad = (steps + d - 1) / d * d;
+      for (int sp = 0; sp < steps_pad + d; ++sp) {
+        const int o = rw_x_offset(c_src, steps, steps_pad, Q, sp);
+        if (o < 0 || o + 8 > c_src) return false;
+      }
+    }
+  return true;
+}
+// (one assertion per lane quad: each evaluation stays within the compiler's constexpr step budget)
+static_assert(rw_x_offsets_in_row<0>(), "k_conv_rowwise_bf16: a lane of quad 0 would load x beyond its source row");
+static_assert(rw_x_offsets_in_row<1>(), "k_conv_rowwise_bf16: a lane of quad 1 would load x beyond its source row");
+static_assert(rw_x_offsets_in_row<2>(), "k_conv_rowwise_bf16: a lane of quad 2 would load x beyond its source row");
+static_assert(rw_x_offsets_in_row<3>(), "k_conv_rowwise_bf16: a lane of quad 3 would load x beyond its source row");
+
 // D: 32-channel steps of x rows in flight per row group (the ring).
 // (No batch-norm statistics epilogue: built and measured — per-item butterflies, then running per-lane sums reduced once
 // per workgroup; a workgroup walks only 2 - 4 items, so either costs the K = 1 forward launch 13 - 20 us on 200k rows,
@@ -96,15 +126,14 @@ __global__ __launch_bounds__(256) void k_conv_rowwise_bf16(
   const __bf16 *xbase[G], *xbase_nxt[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    xbase[g] = src + (int64_t)srow[g] * c_src + q * 8;
-    xbase_nxt[g] = src + (int64_t)srow_nxt[g] * c_src + q * 8;
+    xbase[g] = src + (int64_t)srow[g] * c_src;           // (row starts: the lane's channel offset is rw_x_offset's)
+    xbase_nxt[g] = src + (int64_t)srow_nxt[g] * c_src;
   }
-  // step s' >= steps_pad: step s' - steps_pad of the NEXT item; a padding step / channels beyond the row: a valid
-  // address (offset 0), the value is never used / masked at use
+  // position sp >= steps_pad: step sp - steps_pad of the NEXT item; a padding step / channels beyond the row: the row's
+  // first 16 bytes (rw_x_offset), the value is never used / masked at use
   auto request = [&](int sp, int j) {
     const bool next = sp >= steps_pad;
-    const int s = next ? sp - steps_pad : sp;
-    const int off = (s < steps && s * 32 + q * 8 < c_src) ? s * 32 : 0;
+    const int off = rw_x_offset(c_src, steps, steps_pad, q, sp);
 #pragma unroll
     for (int g = 0; g < G; ++g) xr[j][g] = *reinterpret_cast<const bf16x8 *>((next ? xbase_nxt[g] : xbase[g]) + off);
   };
@@ -203,7 +232,7 @@ __global__ __launch_bounds__(256) void k_conv_rowwise_bf16(
       srow[g] = srow_nxt[g]; trow[g] = trow_nxt[g];
       srow_nxt[g] = srow_nn[g]; trow_nxt[g] = trow_nn[g];
       xbase[g] = xbase_nxt[g];
-      xbase_nxt[g] = src + (int64_t)srow_nxt[g] * c_src + q * 8;
+      xbase_nxt[g] = src + (int64_t)srow_nxt[g] * c_src;
     }
   }
 }
@@ -215,6 +244,7 @@ static int rowwise_ncb(int c_dst) {
 }
 
 int g_rw_groups = 0;   // me_debug_set_rowwise_groups: 0 policy, 1 / 2 row groups per wave (tuning)
+int g_rw_ipw = 0;      // me_debug_set_rowwise_items_per_wg: 0 policy, N >= 1 items per workgroup (tests: multi-item runs on small lists)
 
 // launch geometry of a row-wise launch: a pure function of the shape and the pair bound (the host sizes the statistics
 // partials by it before the launch)
@@ -243,7 +273,7 @@ static RwGeom rowwise_geom(int64_t volume, int c_src, int c_dst, int64_t n_pairs
   int occ = r.g == 1 ? 4 : (r.ncb <= 4 ? 3 : 2);
   occ = (int)std::max<int64_t>(1, std::min<int64_t>(occ, kLdsBudget / std::max(r.lds, 1)));
   const int64_t slots = (int64_t)device_cu_count() * occ;
-  r.ipw = std::max<int64_t>(1, ceil_div(r.items * r.slabs, slots));
+  r.ipw = g_rw_ipw ? g_rw_ipw : std::max<int64_t>(1, ceil_div(r.items * r.slabs, slots));
   r.grid_x = ceil_div(r.items, r.ipw);
   return r;
 }
@@ -255,6 +285,7 @@ using namespace me;
 extern "C" {
 
 void me_debug_set_rowwise_groups(int g) { g_rw_groups = (g == 1 || g == 2) ? g : 0; }
+void me_debug_set_rowwise_items_per_wg(int n) { g_rw_ipw = n >= 1 ? n : 0; }
 
 // 1: the row-wise kernel takes a (c_src, c_dst, volume) launch — whole 16-byte pieces of a source and of an output row, the offsets within one wave's scan, W[k] of one column slab within 64 KB of LDS
 int32_t me_conv_rowwise_supported_bf16(int64_t volume, int32_t c_src, int32_t c_dst) {

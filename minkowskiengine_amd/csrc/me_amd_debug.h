@@ -80,6 +80,8 @@ void me_debug_set_stem(int mode, int groups);   /* groups: 16-row groups per wav
 void me_debug_set_insert_fused(int on);
 /* row-wise kernel (conv_rowwise.hip): 16-row groups per wave, 0 policy | 1 | 2 */
 void me_debug_set_rowwise_groups(int groups);
+/* row-wise kernel: consecutive items a workgroup walks, 0 policy | N >= 1 (the grid follows; bit-identical results) */
+void me_debug_set_rowwise_items_per_wg(int items);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

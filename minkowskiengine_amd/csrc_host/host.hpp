@@ -191,6 +191,7 @@ struct KernelMapStore {   // buffers shared by a kernel map and its swapped view
   std::map<std::string, Tensor> t;
   std::map<std::string, std::shared_ptr<Plan>> plans;
   std::map<std::string, std::shared_ptr<HaloPlan>> halos;   // (a null entry: no spatial order for this side)
+  std::map<std::string, bool> perms;   // "perm_in" / "perm_out": the side's pair list is a permutation of its rows
 };
 
 struct KernelMap : std::enable_shared_from_this<KernelMap> {
@@ -201,7 +202,8 @@ struct KernelMap : std::enable_shared_from_this<KernelMap> {
   std::shared_ptr<KernelMapStore> store;
   bool flip = false;
   // sides on which a row has AT MOST one pair by construction (bit 0: "in" rows, bit 1: "out" rows): the 1x1 identity map
-  // (both), the fine side of a kernel_size == stride map.  With n_pairs == rows of the side: exactly one -> row-wise launch
+  // (both), the fine side of a kernel_size == stride map whose coordinates are aligned to their tensor stride.  With
+  // n_pairs == rows of the side and rows_are_permutation(): exactly one -> row-wise launch
   int one_pair_sides = 0;
   std::map<std::string, ConvCfg> conv_cfgs;
   std::map<std::string, WgradCfg> wgrad_cfgs;
@@ -216,6 +218,7 @@ struct KernelMap : std::enable_shared_from_this<KernelMap> {
   // (table, order): table [volume, n_tgt] of source ROWS indexed by target POSITION; order undefined when positions are rows
   std::pair<Tensor, Tensor> table_pos(const std::string &target);
   Tensor table(const std::string &target);      // row-space view
+  bool rows_are_permutation(const std::string &target);   // every row of the side has exactly one pair (checked once)
   std::string tile_order(const std::string &target, bool matrix_bound, int64_t src_bytes = 0);
   Tensor flat_order(const std::string &target, const std::string &tile_order);
   Tensor order(const std::string &target, const std::string &tile_order);

@@ -301,6 +301,30 @@ Tensor KernelMap::table(const std::string &target) {
   return store->t[nm];
 }
 
+// Does the pair list name every row of the `target` side exactly once?  "At most one pair per row by construction"
+// (one_pair_sides) holds for coarse coordinates that are multiples of the coarse tensor stride, which nothing enforces
+// (SparseTensor(..., tensor_stride=2) takes odd coordinates, as the reference does): unaligned windows overlap, and a row
+// may have two pairs while another has none at n_pairs == rows.  Checked once per (kernel map, side) on the device — a
+// flag per row, scattered and reduced, one read-back where the first launch waits for n_pairs anyway — and kept with the
+// buffers both views share.  The K = 1 identity map is arange.
+bool KernelMap::rows_are_permutation(const std::string &target) {
+  if (in_pairs_buf.is_same(out_pairs_buf)) return true;
+  const std::string nm = name("perm", target);
+  auto it = store->perms.find(nm);
+  if (it != store->perms.end()) return it->second;
+  const int64_t n_tgt = target == "out" ? n_out : n_in, np = n_pairs();
+  bool ok = np == n_tgt;
+  if (ok && n_tgt > 0) {
+    c10::DeviceGuard guard(device());
+    const Tensor rows = (target == "out" ? out_pairs_buf : in_pairs_buf).narrow(0, 0, np).to(at::kLong);
+    Tensor seen = at::zeros({n_tgt}, at::TensorOptions().dtype(at::kBool).device(device()));
+    seen.index_fill_(0, rows, true);
+    ok = seen.all().item<bool>();
+  }
+  store->perms[nm] = ok;
+  return ok;
+}
+
 std::string KernelMap::tile_order(const std::string &target, bool matrix_bound, int64_t src_bytes) {
   const Policy &p = Policy::get();
   if (p.tile_order != "auto") return p.tile_order;
@@ -562,8 +586,8 @@ const ConvCfg &KernelMap::conv_cfg(const std::string &target, int64_t n_tgt, int
   // the plan geometry depends on the pair count (density): the one host value a first launch on a new map waits for
   const int64_t np = n_pairs();
   if (bf16 && pol.rowwise && !no_rowwise && (one_pair_sides & (target == "in" ? 1 : 2)) && np == n_tgt &&
-      me_conv_rowwise_supported_bf16(volume, c_src, c_dst)) {
-    // every target row has exactly one pair (at most one by construction, and as many pairs as rows): no sum, no plan —
+      me_conv_rowwise_supported_bf16(volume, c_src, c_dst) && rows_are_permutation(target)) {
+    // every target row has exactly one pair (as many pairs as rows, and the pair list verified to name each once): no sum, no plan —
     // out[t] = src[s(t)] @ W[k(t)] straight off the pair lists (csrc/conv_rowwise.hip)
     ConvCfg c;
     c.tile_rows = 0;

@@ -51,21 +51,25 @@ def _cfg_is_rowwise(x_in, y_out, ks, stride, target, c_src, c_dst, transpose=Fal
 
 
 K1_CASES = [
-    # n, extent, cin, cout
-    (3000, 14, 32, 64),       # one 32-channel step, 64 columns
-    (3000, 14, 64, 128),      # eight column blocks
-    (2500, 14, 128, 96),      # MinkUNet decoder: six column blocks
-    (2500, 14, 96, 24),       # the segmentation head (20 classes padded to 24): two blocks, the second half empty
-    (2000, 12, 192, 128),     # 128-channel chunks, the second half full of padding
-    (1500, 10, 384, 256),     # twelve steps, two 128-column slabs
-    (1500, 10, 128, 256),
-    (70, 4, 32, 32),          # a single, partial item
-    (1, 2, 8, 8),
+    # n, extent, cin, cout, forward launch row-wise, input-gradient launch row-wise (written by hand: W[k] of one column
+    # slab — 32-channel steps x 16-column blocks of the slab x 1 KB — within the kernel's 64 KB of LDS)
+    (3000, 14, 32, 64, True, True),       # one 32-channel step, 64 columns
+    (3000, 14, 64, 128, True, True),      # eight column blocks
+    (2500, 14, 128, 96, True, True),      # MinkUNet decoder: six column blocks
+    (2500, 14, 96, 24, True, True),       # the segmentation head (20 classes padded to 24): two blocks, the second half empty
+    (2000, 12, 192, 128, True, True),     # 128-channel chunks, the second half full of padding
+    (1500, 10, 384, 256, False, True),    # forward: twelve steps x eight blocks = 96 KB, beyond the LDS limit -> tile plan;
+                                          # the input gradient (256 -> 384: eight steps, three 128-column slabs) is row-wise
+    (1500, 10, 128, 256, True, True),     # four steps, two full 128-column slabs ON the kernel
+    (1200, 10, 64, 136, True, True),      # two slabs, the second one 16-column block wide
+    (70, 4, 32, 32, True, True),          # a single, partial item
+    (1, 2, 8, 8, True, True),
 ]
 
 
-@pytest.mark.parametrize("n,extent,cin,cout", K1_CASES)
-def test_rowwise_k1_layer_vs_oracle(device, host_layer, n, extent, cin, cout):
+@pytest.mark.parametrize("n,extent,cin,cout,fwd_rowwise,dgrad_rowwise", K1_CASES,
+                         ids=["-".join(str(v) for v in c[:4]) for c in K1_CASES])
+def test_rowwise_k1_layer_vs_oracle(device, host_layer, n, extent, cin, cout, fwd_rowwise, dgrad_rowwise):
     """kernel_size = 1, stride 1: out = F @ W through the row-wise kernel, forward and input gradient; the weight gradient
     (pair-list kernel, unchanged) rides along"""
     import minkowskiengine_amd as ME
@@ -88,6 +92,8 @@ def test_rowwise_k1_layer_vs_oracle(device, host_layer, n, extent, cin, cout):
         "forward: row-wise kernel not taken / taken for an unsupported shape"
     assert _cfg_is_rowwise(x, y, 1, 1, "in", cout, cin) == bool(lib.me_conv_rowwise_supported_bf16(1, cout, cin)), \
         "input gradient: row-wise kernel not taken / taken for an unsupported shape"
+    assert _cfg_is_rowwise(x, y, 1, 1, "out", cin, cout) is fwd_rowwise, "forward: not on the kernel this case is meant for"
+    assert _cfg_is_rowwise(x, y, 1, 1, "in", cout, cin) is dgrad_rowwise, "input gradient: not on the kernel this case is meant for"
     w = conv.kernel.detach().float().cpu().numpy()
     f64 = feats.numpy().astype(np.float64)
     assert_bf16_close(y.F.detach().float().cpu().numpy(), f64 @ w.astype(np.float64), "forward")
@@ -96,18 +102,21 @@ def test_rowwise_k1_layer_vs_oracle(device, host_layer, n, extent, cin, cout):
 
 
 S2_CASES = [
-    # n, extent, c_fine, c_coarse
-    (3000, 20, 32, 32),       # MinkUNet conv1 / conv2: 32 -> 32 down
-    (3000, 20, 32, 64),
-    (2500, 16, 96, 128),      # decoder: 128 -> 96 up
-    (2000, 14, 128, 256),     # 256 -> 128 up, two slabs on the way down
-    (1500, 12, 256, 256),
-    (300, 40, 64, 64),        # sparse: one child per parent, offsets with a handful of pairs
+    # n (per batch, two batches), extent, c_fine, c_coarse, fine side row-wise (by hand, as above: c_coarse -> c_fine)
+    (3000, 20, 32, 32, True),       # MinkUNet conv1 / conv2: 32 -> 32 down
+    (3000, 20, 32, 64, True),
+    (2500, 16, 96, 128, True),      # decoder: 128 -> 96 up
+    (2000, 14, 128, 256, True),     # 256 -> 128 up, two slabs on the way down
+    (1500, 12, 256, 256, True),     # eight steps x eight blocks: exactly the LDS limit
+    (300, 40, 64, 64, True),        # sparse: one child per parent, offsets with a handful of pairs
+    (40000, 64, 32, 32, True),      # 80k fine rows, 8 offsets: more 64-pair items than the chip holds workgroups — the
+                                    # shipped policy gives a workgroup two consecutive items (no debug hook)
 ]
 
 
-@pytest.mark.parametrize("n,extent,c_fine,c_coarse", S2_CASES)
-def test_rowwise_stride2_down_dgrad_and_up_forward_vs_oracle(device, host_layer, n, extent, c_fine, c_coarse):
+@pytest.mark.parametrize("n,extent,c_fine,c_coarse,fine_rowwise", S2_CASES,
+                         ids=["-".join(str(v) for v in c[:4]) for c in S2_CASES])
+def test_rowwise_stride2_down_dgrad_and_up_forward_vs_oracle(device, host_layer, n, extent, c_fine, c_coarse, fine_rowwise):
     """k = 2, s = 2 down convolution followed by the transposed convolution back onto the input map: the FINE side of
     the shared kernel map has one pair per row — the up layer's forward launch and the down layer's input gradient run
     row-wise; the coarse side (down forward, up input gradient) stays on the tile-plan kernels.  All four against the
@@ -137,8 +146,12 @@ def test_rowwise_stride2_down_dgrad_and_up_forward_vs_oracle(device, host_layer,
     assert _cfg_is_rowwise(x, d, 2, 2, "in", c_coarse, c_fine) == sup, "down input gradient: row-wise kernel not taken"
     assert not _cfg_is_rowwise(x, d, 2, 2, "out", c_fine, c_coarse)
     assert _cfg_is_rowwise(d, u, 2, 2, "out", c_coarse, c_fine, transpose=True) == sup, "up forward: row-wise kernel not taken"
+    assert _cfg_is_rowwise(x, d, 2, 2, "in", c_coarse, c_fine) is fine_rowwise
+    assert _cfg_is_rowwise(d, u, 2, 2, "out", c_coarse, c_fine, transpose=True) is fine_rowwise
     in_c, mid_c = coords.numpy(), d.C.cpu().numpy()
     _, km = O.kernel_map(in_c, mid_c, O.make_region(3, 2, 1, 1))
+    if n >= 35000:
+        assert len(in_c) >= 70000 and len(km) == 8, "the large case must have 70k fine rows on 8 offsets"
     wd = down.kernel.detach().float().cpu().numpy()
     wu = up.kernel.detach().float().cpu().numpy()
     assert_bf16_close(d.F.detach().float().cpu().numpy(), O.conv_forward(feats.numpy(), wd, km, len(mid_c)), "down forward")
@@ -223,6 +236,70 @@ def test_rowwise_switch_and_fallbacks(device, host_layer, monkeypatch):
     ref_u = O.conv_forward(dp.F.detach().float().cpu().numpy(), up.kernel.detach().float().cpu().numpy(), kmt, len(coords))
     assert_bf16_close(u.F.detach().float().cpu().numpy(), ref_u, "up from a pruned map")
     assert (np.abs(ref_u).sum(1) == 0).any(), "the case must contain orphaned rows"
+
+
+def test_rowwise_unaligned_coarse_map_falls_back(device, host_layer):
+    """A coarse tensor built by hand with tensor_stride=2 and ODD coordinates (accepted, as by the reference): its 2^3
+    windows overlap.  Per motif j the fine map holds A = (0, 8j, 0), B = (1, 8j, 0), C = (5, 8j, 0), the coarse map
+    P = (0, 8j, 0), Q = (1, 8j, 0): three pairs on three fine rows (n_pairs == rows of the fine side), but B has TWO —
+    B = P W[(1,0,0)] + Q W[(0,0,0)] — and C none (zeros).  "One pair per row by construction" does not hold: the side must
+    stay on the tile-plan kernels (which sum and zero-fill), forward of the transposed layer and input gradient of the
+    strided one alike."""
+    import minkowskiengine_amd as ME
+    J = 200
+    j8 = 8 * torch.arange(J, dtype=torch.int32)
+
+    def pts(b, x):
+        return torch.stack([torch.full_like(j8, b), torch.full_like(j8, x), j8, torch.zeros_like(j8)], 1)
+    fine = torch.cat([pts(b, x) for b in (0, 1) for x in (0, 1, 5)]).int()
+    coarse = torch.cat([pts(b, x) for b in (0, 1) for x in (0, 1)]).int()
+    g = torch.Generator().manual_seed(11)
+    f_fine = bf16_round(torch.rand(len(fine), 32, generator=g) - 0.4)
+    f_coarse = bf16_round(torch.rand(len(coarse), 32, generator=g) - 0.4)
+    up = ME.MinkowskiConvolutionTranspose(32, 32, kernel_size=2, stride=2, dimension=3)
+    down = ME.MinkowskiConvolution(32, 32, kernel_size=2, stride=2, dimension=3)
+    with torch.no_grad():
+        for m in (up, down):
+            m.kernel.copy_(bf16_round((torch.rand(m.kernel.shape, generator=g) - 0.5) * 0.5))
+    up, down = up.to(device), down.to(device)
+    x = ME.SparseTensor(f_fine.to(device).to(torch.bfloat16), fine.to(device), requires_grad=True)
+    c = ME.SparseTensor(f_coarse.to(device).to(torch.bfloat16), coarse.to(device), tensor_stride=2,
+                        coordinate_manager=x.coordinate_manager, requires_grad=True)
+    fine_c, coarse_c = x.C.cpu().numpy(), c.C.cpu().numpy()
+    assert np.array_equal(fine_c, fine.numpy()) and np.array_equal(coarse_c, coarse.numpy())
+    _, km = O.kernel_map(fine_c, coarse_c, O.make_region(3, 2, 1, 1))          # fine -> coarse: the strided layer's map
+    kmt = {k: v[::-1].copy() for k, v in km.items()}                            # coarse -> fine: the transposed layer's
+    n_pairs = sum(v.shape[1] for v in km.values())
+    per_fine_row = np.bincount(np.concatenate([v[0] for v in km.values()]), minlength=len(fine_c))
+    assert n_pairs == len(fine_c) and per_fine_row.max() == 2 and per_fine_row.min() == 0, "the case must defeat the count check"
+    # ---- up: coarse -> fine, forward launch on the fine side ----
+    u = up(c, x.coordinate_map_key)
+    gu = bf16_round(torch.rand(u.F.shape, generator=g) - 0.5)
+    u.F.backward(gu.to(device).to(torch.bfloat16))
+    wu = up.kernel.detach().float().cpu().numpy()
+    ref_u = O.conv_forward(f_coarse.numpy(), wu, kmt, len(fine_c))
+    is_b, is_c = fine_c[:, 1] == 1, fine_c[:, 1] == 5
+    assert (np.abs(ref_u[is_c]).sum(1) == 0).all() and (per_fine_row[is_b] == 2).all()
+    got_u = u.F.detach().float().cpu().numpy()
+    assert_bf16_close(got_u[is_b], ref_u[is_b], "up forward, rows B (two pairs each)")
+    assert (got_u[is_c] == 0).all(), "up forward, rows C (no pair): not zero"
+    assert_bf16_close(got_u, ref_u, "up forward")
+    assert not _cfg_is_rowwise(c, u, 2, 2, "out", 32, 32, transpose=True), "a side with two pairs on a row went row-wise"
+    gi_u, gw_u = O.conv_backward(f_coarse.numpy(), gu.numpy(), wu, kmt)
+    assert_bf16_close(c.F.grad.float().cpu().numpy(), gi_u, "up grad_in")
+    assert_close(up.kernel.grad.cpu().numpy(), gw_u)
+    # ---- down: fine -> the same coarse map, input gradient on the fine side ----
+    d = down(x, c.coordinate_map_key)
+    gd = bf16_round(torch.rand(d.F.shape, generator=g) - 0.5)
+    d.F.backward(gd.to(device).to(torch.bfloat16))
+    wd = down.kernel.detach().float().cpu().numpy()
+    assert_bf16_close(d.F.detach().float().cpu().numpy(), O.conv_forward(f_fine.numpy(), wd, km, len(coarse_c)), "down forward")
+    gi_d, gw_d = O.conv_backward(f_fine.numpy(), gd.numpy(), wd, km)
+    got_gi = x.F.grad.float().cpu().numpy()
+    assert_bf16_close(got_gi[is_b], gi_d[is_b], "down grad_in, rows B (two pairs each)")
+    assert_bf16_close(got_gi, gi_d, "down grad_in")
+    assert not _cfg_is_rowwise(x, d, 2, 2, "in", 32, 32), "down input gradient: a side with two pairs on a row went row-wise"
+    assert_close(down.kernel.grad.cpu().numpy(), gw_d)
 
 
 def test_rowwise_k1_forward_with_wanted_statistics_policy(device, host_layer):

@@ -34,16 +34,24 @@ extern "C" {
 /* region types: src/types.hpp:148-152 (RegionType::HYPER_CUBE / HYPER_CROSS / CUSTOM) */
 #define ME_REGION_HYPER_CUBE 0
 #define ME_REGION_HYPER_CROSS 1
+#define ME_REGION_CUSTOM 2
 
 /* Kernel geometry of one layer; replaces gpu_kernel_region (src/kernel_region.hpp:283-398).
  * Neighbour offsets follow kernel_region.hpp:198-247 (axis 0 fastest; odd sizes centred, even
- * sizes start at 0; multiplied by dilation * tensor_stride). */
+ * sizes start at 0; multiplied by dilation * tensor_stride).
+ * ME_REGION_CUSTOM (the reference declares it and stops at `case CUSTOM: // TODO`; the semantics are this library's):
+ * tap k looks up u + offsets_dev[k] * dilation * tensor_stride per axis, so the offsets are in units of the tensor
+ * stride, as kernel_size is.  Rows may come in any order and need not hold the origin; kernel_size is ignored and the
+ * volume is n_offsets.  The table stays on the device for as long as a launch that got this region may run.  A
+ * `me_region r = {}` of a built-in type leaves both trailing fields zero. */
 typedef struct me_region {
   int32_t ncol;                    /* D + 1 */
   int32_t region_type;             /* ME_REGION_* */
   int32_t kernel_size[ME_MAX_DIM]; /* per spatial axis */
   int32_t dilation[ME_MAX_DIM];
   int32_t tensor_stride[ME_MAX_DIM]; /* tensor stride of the map that is LOOKED UP (the "in" map) */
+  int32_t n_offsets;               /* ME_REGION_CUSTOM: rows K of offsets_dev (ABI 1.13); 0 otherwise */
+  const int32_t *offsets_dev;      /* ME_REGION_CUSTOM: int32 [K, D] contiguous, on the device; NULL otherwise */
 } me_region;
 
 /* ---- library ------------------------------------------------------------------------------- */
@@ -77,14 +85,17 @@ typedef struct me_region {
  *   1.11 (210) round 11: direct max pooling over an (in_map, out_map) pair list (me_direct_max_pool_*) and the origin-map
  *              row table of a tensor field (me_field_origin_rows_f32)
  *   1.12 (220) round 12: arithmetic between two sparse tensors on different coordinate maps: the row tables of a union
- *              (me_union_tables) and the fused one-write-per-row forward / gather backward (me_union_arith_*) */
+ *              (me_union_tables) and the fused one-write-per-row forward / gather backward (me_union_arith_*)
+ *   1.13 (230) round 13: ME_REGION_CUSTOM: me_region grew two trailing fields (n_offsets, offsets_dev); every entry point
+ *              that takes a region accepts it, the LDS-bucketed probe declines it (me_kernel_map_probe_lds_bytes: -1) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
  * at the first launch from it, which put 88 ms into the first backward pass of a process.  The hosts call it at the first
  * map insert on a device, under that device's guard (code objects are per device) — not at import. */
 int me_preload(void);
-/* kernel volume of a region: src/kernel_region.hpp:250-270 (set_volume) */
+/* kernel volume of a region: src/kernel_region.hpp:250-270 (set_volume); n_offsets for ME_REGION_CUSTOM (host only:
+ * the table is not read); -1 for an invalid region */
 int64_t me_region_volume(const me_region *region);
 
 /* ---- coordinate hash map (replaces CoordinateMapGPU, src/coordinate_map_gpu.cuh:47-223) ------ */

@@ -30,7 +30,7 @@ from .sparse_matrix_functions import (  # noqa: F401
 from .union import MinkowskiUnion, MinkowskiUnionFunction  # noqa: F401
 from .coordinate_manager import (  # noqa: F401
     CoordinateManager, set_gpu_allocator, set_memory_manager_backend, set_map_prefetch, map_prefetch_enabled, map_prefetch_tag)
-from .kernel_generator import KernelGenerator, get_kernel_volume  # noqa: F401
+from .kernel_generator import KernelGenerator, get_kernel_volume, hybrid_region_offsets  # noqa: F401
 from .layers import (  # noqa: F401
     MinkowskiBatchNorm, MinkowskiDropout, MinkowskiELU, MinkowskiLeakyReLU, MinkowskiLinear, MinkowskiReLU,
     MinkowskiSigmoid, MinkowskiSyncBatchNorm, MinkowskiTanh, cat)

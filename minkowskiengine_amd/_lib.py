@@ -29,6 +29,8 @@ class MeRegion(ctypes.Structure):
         ("kernel_size", c_i32 * ME_MAX_DIM),
         ("dilation", c_i32 * ME_MAX_DIM),
         ("tensor_stride", c_i32 * ME_MAX_DIM),
+        ("n_offsets", c_i32),
+        ("offsets_dev", c_vp),
     ]
 
 
@@ -364,12 +366,29 @@ def check(rc):
         raise RuntimeError(msg.decode() if msg else f"libme_amd call failed with code {rc}")
 
 
-def make_region(ncol, region_type, kernel_size, dilation, tensor_stride):
+ME_REGION_CUSTOM = 2
+
+
+def make_region(ncol, region_type, kernel_size, dilation, tensor_stride, offsets=None, device=None):
+    """me_region of a layer.  ME_REGION_CUSTOM: `offsets` is the contiguous CPU int32 [K, D] table of the kernel
+    generator; it is uploaded to `device` here — once per map build — and the device copy is returned with the region
+    (`rg.offsets_tensor`): the caller keeps it for as long as launches that got the region may run.  device=None fills
+    the count only (me_region_volume, which reads no table)."""
     rg = MeRegion()
     rg.ncol = int(ncol)
     rg.region_type = int(region_type)
+    custom = rg.region_type == ME_REGION_CUSTOM
     for d in range(ME_MAX_DIM):
-        rg.kernel_size[d] = int(kernel_size[d]) if d < ncol - 1 else 1
+        rg.kernel_size[d] = int(kernel_size[d]) if d < ncol - 1 and not custom else 1
         rg.dilation[d] = int(dilation[d]) if d < ncol - 1 else 1
         rg.tensor_stride[d] = int(tensor_stride[d]) if d < ncol - 1 else 1
+    rg.offsets_tensor = None
+    if custom:
+        if offsets is None or offsets.dim() != 2 or offsets.shape[0] < 1 or offsets.shape[1] != ncol - 1:
+            raise ValueError(f"a CUSTOM region needs region offsets of shape [K >= 1, {ncol - 1}]")
+        rg.n_offsets = int(offsets.shape[0])
+        if device is not None:
+            import torch
+            rg.offsets_tensor = offsets.to(dtype=torch.int32).contiguous().to(device)
+            rg.offsets_dev = rg.offsets_tensor.data_ptr()
     return rg

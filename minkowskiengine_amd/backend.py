@@ -644,6 +644,31 @@ _TILE_ORDER_ROWS_MAX_BYTES = 32 << 20
 _TILE_SPATIAL_MIN_SRC_BYTES = int(os.environ.get("ME_AMD_TILE_SPATIAL_SRC_MB", "28")) << 20
 
 
+def normalize_region_offsets(region_offsets, dimension):
+    """RegionType.CUSTOM: the offsets of a layer as ONE contiguous CPU int32 tensor [K, D] (a list, an ndarray or an
+    integer tensor of any dtype on any device is accepted).  Tap k looks up u + offsets[k] * dilation * tensor_stride,
+    so the rows are in units of the tensor stride (one definition serves every level of a network); they may come in
+    any order and need not hold the origin.  Raises ValueError for an empty list, a wrong width or duplicate rows.  The
+    result carries its own cache-key form (a tuple of tuples) and passes through a second call unchanged."""
+    if getattr(region_offsets, "_me_offsets_key", None) is not None and region_offsets.shape[1] == dimension:
+        return region_offsets
+    t = torch.as_tensor(region_offsets) if region_offsets is not None else torch.IntTensor()
+    if t.dim() != 2 or t.shape[0] < 1:
+        raise ValueError("region_offsets must be a non-empty [K, D] integer tensor when region_type is CUSTOM, got shape "
+                         f"{tuple(t.shape)}")
+    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError(f"region_offsets must be integers, got {t.dtype}")
+    if t.shape[1] != dimension:
+        raise ValueError(f"region_offsets has {t.shape[1]} columns, the layer has dimension {dimension}")
+    # (a copy of its own: the key form below must not follow later writes to the caller's tensor or array)
+    t = t.detach().to(device="cpu", dtype=torch.int32, copy=True).contiguous()
+    key = tuple(tuple(int(v) for v in row) for row in t.tolist())
+    if len(set(key)) != len(key):
+        raise ValueError("region_offsets holds duplicate rows: every kernel tap needs its own offset")
+    t._me_offsets_key = key
+    return t
+
+
 def _build_kernel_map_lds(in_map, out_map, region, volume):
     """LDS-bucketed build (csrc/coords.hip k_kmap_probe_lds): the neighbour table comes out in the position space of
     the out map; no host synchronisation.  None when the pair of maps / the region is not eligible."""
@@ -686,7 +711,7 @@ def _build_kernel_map(in_map, out_map, region):
     dev = in_map.coords.device
     volume = int(lib.me_region_volume(ctypes.byref(region)))
     _check(volume > 0, "invalid kernel region")
-    km = _build_kernel_map_lds(in_map, out_map, region, volume)
+    km = _build_kernel_map_lds(in_map, out_map, region, volume)    # (declines CUSTOM regions)
     if km is not None:
         return km
     n_out, n_in = out_map.n, in_map.n
@@ -704,8 +729,11 @@ def _build_kernel_map(in_map, out_map, region):
         out_pairs = torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)
         _lib.check(lib.me_kernel_map_compact(_ptr(nbr), n_out, volume, _ptr(in_pairs), _ptr(out_pairs), _ptr(ws),
                                              ws.numel(), _stream(dev)))
+    store = {"nbr_out": nbr}
+    if getattr(region, "offsets_tensor", None) is not None:
+        store["region_offsets"] = region.offsets_tensor    # device table of a CUSTOM region: lives as long as the map
     return KernelMapGPU(volume, n_in, n_out, k_offsets, k_offsets_dev, in_pairs[:max(n_pairs, 0)],
-                        out_pairs[:max(n_pairs, 0)], store={"nbr_out": nbr}, in_map=in_map, out_map=out_map)
+                        out_pairs[:max(n_pairs, 0)], store=store, in_map=in_map, out_map=out_map)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -859,15 +887,15 @@ class CoordinateMapManagerGPU_c10:
         return key
 
     def stride_region(self, in_key, kernel_size, kernel_dilation, region_type, out_tensor_stride,
-                      expand_coordinates, is_transpose, region_tensor_stride=None):
+                      expand_coordinates, is_transpose, region_tensor_stride=None, offset=None):
         """src/coordinate_map_manager.cpp:436-466 -> (CoordinateMapKey, created): the map with
         `out_tensor_stride`; it is reused when it exists and `expand_coordinates` is false, otherwise generated
         from the kernel region around every input coordinate (CoordinateMapCPU::stride_region,
         src/coordinate_map_cpu.hpp:446-487): all of them for a transposed kernel, only those aligned to the out
-        tensor stride otherwise.  New rows are ordered by input row, then kernel offset."""
+        tensor stride otherwise.  New rows are ordered by input row, then kernel offset.  RegionType.CUSTOM: `offset`
+        is the [K, D] list; the candidates are c + offset[k] * dilation * region tensor stride."""
         ik = self._k(in_key)
         _check(ik in self._maps, "coordinate map not found", ik)
-        _check(int(region_type) != int(RegionType.CUSTOM), "Not implemented yet.")
         out_ts = tuple(int(t) for t in out_tensor_stride)
         ok = (out_ts, "")
         exists = ok in self._maps
@@ -880,9 +908,12 @@ class CoordinateMapManagerGPU_c10:
         # the offsets of a transposed kernel step by the OUT tensor stride (convolution_transpose_cpu.cpp:81-91),
         # those of a regular kernel by the IN tensor stride (convolution_cpu.cpp:88-98)
         rts = out_ts if region_tensor_stride is None else tuple(int(t) for t in region_tensor_stride)
+        custom = int(region_type) == int(RegionType.CUSTOM)
+        offs = normalize_region_offsets(offset, ncol - 1) if custom else None
         region = _lib.make_region(ncol, int(region_type), [int(v) for v in kernel_size],
-                                  [int(v) for v in kernel_dilation], rts)
+                                  [int(v) for v in kernel_dilation], rts, offs, dev)
         volume = int(lib.me_region_volume(ctypes.byref(region)))
+        _check(volume > 0, "invalid kernel region")
         cand = torch.empty((max(in_map.n * volume, 1), ncol), dtype=torch.int32, device=dev)
         aligned = None if is_transpose else torch.empty(max(in_map.n * volume, 1), dtype=torch.uint8, device=dev)
         ts_arr = (ctypes.c_int32 * len(out_ts))(*out_ts)
@@ -1244,20 +1275,32 @@ class CoordinateMapManagerGPU_c10:
     @_ranged("me:kernel_map")
     def _kernel_map(self, in_key, out_key, kernel_size, kernel_stride, kernel_dilation, region_type,
                     offset, is_transpose, is_pool):
-        """src/coordinate_map_manager.cpp:655-823 -> KernelMapGPU (cached)."""
-        _check(int(region_type) != int(RegionType.CUSTOM), "Not implemented yet.")
+        """src/coordinate_map_manager.cpp:655-823 -> KernelMapGPU (cached).  RegionType.CUSTOM: `offset` is the [K, D]
+        list (normalize_region_offsets); kernel_size is ignored and the cache key grows a ninth entry, the offsets as a
+        tuple of tuples — two layers with different lists on the same maps get different kernel maps."""
         ks = tuple(int(v) for v in kernel_size)
         st = tuple(int(v) for v in kernel_stride)
         dl = tuple(int(v) for v in kernel_dilation)
         _check(len(ks) == len(st) == len(dl), "kernel size mismatch")
         ik, ok = self._k(in_key), self._k(out_key)
-        key = (ik, ok, ks, st, dl, int(region_type), bool(is_transpose), bool(is_pool))
+        rt = int(region_type)
+        custom = rt == int(RegionType.CUSTOM)
+        offs, okey = None, ()
+        if custom:
+            offs = normalize_region_offsets(offset, len(ks))
+            okey = (offs._me_offsets_key,)
+            ks = (1,) * len(ks)          # (not part of a CUSTOM region: one canonical value in the key)
+        key = (ik, ok, ks, st, dl, rt, bool(is_transpose), bool(is_pool)) + okey
         km = self._kernel_maps.get(key)
         if km is not None:
             return km
         in_map, out_map = self._get(ik), self._get(ok)
         _check(len(ks) + 1 == in_map.coords.shape[1], "kernel size mismatch")
-        if ik == ok and all(k == 1 for k in ks):
+        dev = in_map.coords.device
+        # (geometry shortcuts: a CUSTOM list takes them only when its single offset is the origin — one non-zero
+        # offset is a shift)
+        single_origin = okey == (((0,) * len(ks),),) if custom else all(k == 1 for k in ks)
+        if ik == ok and single_origin:
             # a 1x1 kernel on one map: every row is paired with itself (volume-1 shortcut of
             # src/coordinate_map_cpu.hpp:605-616) — no probe, no host synchronisation
             n = in_map.n
@@ -1270,17 +1313,17 @@ class CoordinateMapManagerGPU_c10:
             return km
         if not is_transpose:
             # (pooling with stride == kernel uses the same generic path: the result is identical)
-            region = _lib.make_region(len(ks) + 1, int(region_type), ks, dl, in_map.tensor_stride)
+            region = _lib.make_region(len(ks) + 1, rt, ks, dl, in_map.tensor_stride, offs, dev)
             km = _build_kernel_map(in_map, out_map, region)
-            km.one_pair_sides = _one_pair_sides(ks, dl, int(region_type), in_map.tensor_stride, out_map.tensor_stride)
+            km.one_pair_sides = _one_pair_sides(ks, dl, rt, in_map.tensor_stride, out_map.tensor_stride, offs)
         else:
-            swapped_key = (ok, ik, ks, st, dl, int(region_type), False, bool(is_pool))
+            swapped_key = (ok, ik, ks, st, dl, rt, False, bool(is_pool)) + okey
             fwd = self._kernel_maps.get(swapped_key)
             if fwd is None:
                 # out -> in map with the (finer) out tensor stride, then swap
-                region = _lib.make_region(len(ks) + 1, int(region_type), ks, dl, out_map.tensor_stride)
+                region = _lib.make_region(len(ks) + 1, rt, ks, dl, out_map.tensor_stride, offs, dev)
                 fwd = _build_kernel_map(out_map, in_map, region)
-                fwd.one_pair_sides = _one_pair_sides(ks, dl, int(region_type), out_map.tensor_stride, in_map.tensor_stride)
+                fwd.one_pair_sides = _one_pair_sides(ks, dl, rt, out_map.tensor_stride, in_map.tensor_stride, offs)
             km = fwd.swapped()
         self._kernel_maps[key] = km
         km._recipe, km._recipe_key = self._recipe, key
@@ -1344,10 +1387,12 @@ class CoordinateMapManagerGPU_c10:
                         self.stride(CoordinateMapKey(list(ik[0]), ik[1]), list(stride), sid)
                         done += 1
                 elif op[0] == "kernel_map":
-                    ik, ok, ks, st, dl, rt, tr, pool = op[1]
+                    ik, ok, ks, st, dl, rt, tr, pool = op[1][:8]
+                    # (a CUSTOM map's key carries its offsets behind the eight entries)
+                    offs = torch.tensor(op[1][8], dtype=torch.int32) if len(op[1]) > 8 else None
                     if ik in self._maps and ok in self._maps:
                         self._kernel_map(CoordinateMapKey(list(ik[0]), ik[1]), CoordinateMapKey(list(ok[0]), ok[1]), ks,
-                                         st, dl, RegionType(rt), None, tr, pool)
+                                         st, dl, RegionType(rt), offs, tr, pool)
                         done += 1
                 elif op[0] == "conv_cfg":
                     _, key, target, c_src, c_dst, bf16 = op
@@ -1538,10 +1583,13 @@ def plan_config(n_tgt, volume, n_pairs, c_src, c_dst, bf16=False, split=False, w
     return out + (int(sk.value),) if with_split_k else out
 
 
-def _one_pair_sides(ks, dl, region_type, fine_ts, coarse_ts):
+def _one_pair_sides(ks, dl, region_type, fine_ts, coarse_ts, offsets=None):
     """Sides of a hyper-cube map (looked-up map at `fine_ts`, iterated map at `coarse_ts`) on which a row has at most ONE
     pair by construction (csrc_host/manager.cpp one_pair_sides_of): a single-offset kernel -> both (3); windows that tile
-    space without overlap (coarse stride = kernel_size x fine stride, no dilation) -> the fine ("in") side (1)."""
+    space without overlap (coarse stride = kernel_size x fine stride, no dilation) -> the fine ("in") side (1).  A
+    CUSTOM list: both for a single offset, else none — tiling is not proven for arbitrary lists."""
+    if offsets is not None:
+        return 3 if offsets.shape[0] == 1 else 0
     if all(k == 1 for k in ks):
         return 3
     tiling = region_type == 0 and len(fine_ts) == len(ks) == len(coarse_ts) and \
@@ -2148,7 +2196,7 @@ def _conv_backward(in_feat, grad_out, kernel, km, algo=None, need_grad_in=True):
 
 
 def _prepare_conv(in_feat, kernel, kernel_size, kernel_stride, kernel_dilation, region_type, expand_coordinates,
-                  in_key, out_key, manager, transpose):
+                  in_key, out_key, manager, transpose, offset=None):
     _check_feat("in_feat", in_feat)
     _check_feat("kernel", kernel)
     _check(in_feat.dim() == 2, "in_feat.dim():", in_feat.dim())
@@ -2167,7 +2215,7 @@ def _prepare_conv(in_feat, kernel, kernel_size, kernel_stride, kernel_dilation, 
             # output grid becomes an output voxel
             out_ts = [t * s for t, s in zip(ts, st)]
             key, _ = manager.stride_region(in_key, kernel_size, kernel_dilation, region_type, out_ts, True, False,
-                                           region_tensor_stride=ts)
+                                           region_tensor_stride=ts, offset=offset)
             out_key.set_key(key.get_key())
         else:
             out_key.set_key(manager.stride(in_key, kernel_stride).get_key())
@@ -2178,7 +2226,7 @@ def _prepare_conv(in_feat, kernel, kernel_size, kernel_stride, kernel_dilation, 
                "kernel stride:", st)
         out_ts = [t // s for t, s in zip(ts, st)]
         key, _ = manager.stride_region(in_key, kernel_size, kernel_dilation, region_type, out_ts,
-                                       bool(expand_coordinates), True)
+                                       bool(expand_coordinates), True, offset=offset)
         out_key.set_key(key.get_key())
 
 
@@ -2186,7 +2234,7 @@ def ConvolutionForwardGPU(in_feat, kernel, kernel_size, kernel_stride, kernel_di
                           expand_coordinates, convolution_mode, in_key, out_key, manager):
     """src/convolution_gpu.cu:45-159 (CPU twin src/convolution_cpu.cpp:42-135)."""
     _prepare_conv(in_feat, kernel, kernel_size, kernel_stride, kernel_dilation, region_type, expand_coordinates, in_key,
-                  out_key, manager, False)
+                  out_key, manager, False, offset)
     km = manager._kernel_map(in_key, out_key, kernel_size, kernel_stride, kernel_dilation, region_type, offset,
                              False, False)
     return _conv_forward(in_feat, kernel, km)
@@ -2213,7 +2261,7 @@ def ConvolutionTransposeForwardGPU(in_feat, kernel, kernel_size, kernel_stride, 
                                    offset, expand_coordinates, convolution_mode, in_key, out_key, manager):
     """src/convolution_transpose_gpu.cu (CPU twin src/convolution_transpose_cpu.cpp:41-125)."""
     _prepare_conv(in_feat, kernel, kernel_size, kernel_stride, kernel_dilation, region_type, expand_coordinates, in_key,
-                  out_key, manager, True)
+                  out_key, manager, True, offset)
     km = manager._kernel_map(in_key, out_key, kernel_size, kernel_stride, kernel_dilation, region_type, offset,
                              True, False)
     return _conv_forward(in_feat, kernel, km)

@@ -47,7 +47,7 @@ def _conv_apply(conv_fn, is_transpose, feats, kernel, kernel_generator, convolut
         return _host.native_module().conv_autograd(
             feats, kernel, kernel_generator.kernel_size, kernel_generator.kernel_stride, kernel_generator.kernel_dilation,
             int(kernel_generator.region_type), bool(kernel_generator.expand_coordinates), in_key, out_key,
-            manager._manager, bool(is_transpose))
+            manager._manager, bool(is_transpose), kernel_generator.region_offsets)
     from . import backend as _backend
     _backend.conv_bn_stats_hint(want_stats)
     return conv_fn.apply(feats, kernel, kernel_generator, convolution_mode, in_key, out_key, manager)
@@ -135,8 +135,11 @@ class MinkowskiConvolutionBase(MinkowskiModuleBase):
         self.out_channels = out_channels
         self.kernel_generator = kernel_generator
         self.dimension = dimension
-        # kernel volume 1 and all strides 1 -> a plain matrix product (MinkowskiConvolution.py:264-270)
-        self.use_mm = (kernel_generator.kernel_volume == 1 and kernel_generator.requires_strided_coordinates)
+        # kernel volume 1 and all strides 1 -> a plain matrix product (MinkowskiConvolution.py:264-270); a CUSTOM list
+        # only when its single offset is the origin (one non-zero offset is a shift: kernel [1, Cin, Cout])
+        self.use_mm = (kernel_generator.kernel_volume == 1 and kernel_generator.requires_strided_coordinates and
+                       (kernel_generator.region_type != RegionType.CUSTOM or
+                        not bool(kernel_generator.region_offsets.any())))
         if self.use_mm:
             kernel_shape = (in_channels, out_channels)
         else:

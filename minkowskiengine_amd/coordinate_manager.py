@@ -9,7 +9,8 @@ import weakref
 import torch
 
 from . import host as _host
-from .backend import CoordinateMapType, GPUMemoryAllocatorType, MinkowskiAlgorithm, RegionType
+from .backend import (CoordinateMapType, GPUMemoryAllocatorType, MinkowskiAlgorithm, RegionType,
+                      normalize_region_offsets)
 from .host import CoordinateMapKey
 from .common import convert_to_int_list
 
@@ -243,9 +244,12 @@ class CoordinateManager:
     # ---- kernel maps ----------------------------------------------------------------------------
     def kernel_map(self, in_key, out_key, stride=1, kernel_size=3, dilation=1, region_type=RegionType.HYPER_CUBE,
                    region_offset=None, is_transpose=False, is_pool=False):
-        """dict {k: int32 [2, n_k]}; MinkowskiCoordinateManager.py:377-421"""
+        """dict {k: int32 [2, n_k]}; MinkowskiCoordinateManager.py:377-421.  RegionType.CUSTOM: `region_offset` is the
+        [K, D] list of offsets in units of the tensor stride (kernel_size is not used)."""
         D = in_key.get_coordinate_size() - 1
-        if region_offset is None:
+        if int(region_type) == int(RegionType.CUSTOM):
+            region_offset = normalize_region_offsets(region_offset, D)      # (raises before any launch)
+        elif region_offset is None:
             region_offset = torch.IntTensor()
         return self._manager.kernel_map(in_key, out_key, convert_to_int_list(kernel_size, D),
                                         convert_to_int_list(stride, D), convert_to_int_list(dilation, D),

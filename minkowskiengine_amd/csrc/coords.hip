@@ -472,13 +472,20 @@ __global__ __launch_bounds__(256) void k_spatial_keys(const int32_t *__restrict_
 // =================================================================================================
 // kernel map
 // =================================================================================================
-// neighbour coordinate of offset k: src/kernel_region.hpp:198-247
-template <int NCOL>
+// neighbour coordinate of offset k: src/kernel_region.hpp:198-247.  CUSTOM (a launch of its own: the built-in regions'
+// code does not change): row k of the region's offset table, in units of dilation * tensor stride.  The D loads go
+// through the table pointer with compile-time indices; where k is wave-uniform (k_kmap_probe: blockIdx.y) so is their
+// address, and they are scalar loads.
+template <int NCOL, bool CUSTOM = false>
 __device__ __forceinline__ void region_coordinate_at(const me_region &rg, int32_t k,
                                                      const int32_t (&src)[NCOL],
                                                      int32_t (&dst)[NCOL]) {
   dst[0] = src[0];
-  if (rg.region_type == ME_REGION_HYPER_CUBE) {
+  if constexpr (CUSTOM) {
+    const int32_t *__restrict__ off = rg.offsets_dev + (int64_t)k * (NCOL - 1);
+#pragma unroll
+    for (int d = 0; d < NCOL - 1; ++d) dst[d + 1] = src[d + 1] + off[d] * (rg.dilation[d] * rg.tensor_stride[d]);
+  } else if (rg.region_type == ME_REGION_HYPER_CUBE) {
     int32_t rem = k;
 #pragma unroll
     for (int d = 0; d < NCOL - 1; ++d) {
@@ -514,7 +521,7 @@ __device__ __forceinline__ void region_coordinate_at(const me_region &rg, int32_
 // (row, k) is written at row * volume + k, so a first-occurrence dedup orders the new map by input row, then
 // kernel offset.  `aligned` (may be NULL): 1 where every spatial coordinate is a multiple of the region's
 // tensor stride times `align` (the non-transposed expand_coordinates case keeps only those).
-template <int NCOL>
+template <int NCOL, bool CUSTOM>
 __global__ __launch_bounds__(256) void k_expand_region(const int32_t *__restrict__ coords, int64_t n,
                                                       me_region rg, int32_t volume, StrideArg align,
                                                       int32_t *__restrict__ out, uint8_t *__restrict__ aligned) {
@@ -524,7 +531,7 @@ __global__ __launch_bounds__(256) void k_expand_region(const int32_t *__restrict
   const int32_t k = (int32_t)(idx % volume);
   int32_t src[NCOL], dst[NCOL];
   load_coords<NCOL>(coords, row, src);
-  region_coordinate_at<NCOL>(rg, k, src, dst);
+  region_coordinate_at<NCOL, CUSTOM>(rg, k, src, dst);   // (k is per thread here: ordinary loads of the table)
   store_coords<NCOL>(out, idx, dst);
   if (aligned != nullptr) {
     bool ok = true;
@@ -535,7 +542,7 @@ __global__ __launch_bounds__(256) void k_expand_region(const int32_t *__restrict
 }
 
 // one thread per (output row u, offset k = blockIdx.y); lanes = consecutive u
-template <int NCOL>
+template <int NCOL, bool CUSTOM>
 __global__ __launch_bounds__(256) void k_kmap_probe(const uint64_t *__restrict__ in_table,
                                                    uint32_t mask,
                                                    const int32_t *__restrict__ in_coords,
@@ -549,7 +556,7 @@ __global__ __launch_bounds__(256) void k_kmap_probe(const uint64_t *__restrict__
   if (u < n_out) {
     int32_t src[NCOL], key[NCOL];
     load_coords<NCOL>(out_coords, u, src);
-    region_coordinate_at<NCOL>(rg, k, src, key);
+    region_coordinate_at<NCOL, CUSTOM>(rg, k, src, key);
     r = table_find<NCOL>(in_table, mask, in_coords, key);
     nbr[(int64_t)k * n_out + u] = r;
   }
@@ -1387,7 +1394,7 @@ using namespace me;
 
 extern "C" {
 
-int me_version(void) { return 220; }   // 100 * major + 10 * minor: see the changelog in include/me_amd.h
+int me_version(void) { return 230; }   // 100 * major + 10 * minor: see the changelog in include/me_amd.h
 const char *me_last_error(void) { return g_last_error; }
 
 int64_t me_region_volume(const me_region *rg) {
@@ -1397,6 +1404,8 @@ int64_t me_region_volume(const me_region *rg) {
     for (int d = 0; d < rg->ncol - 1; ++d) v *= rg->kernel_size[d];
   } else if (rg->region_type == ME_REGION_HYPER_CROSS) {
     for (int d = 0; d < rg->ncol - 1; ++d) v += rg->kernel_size[d] - 1;
+  } else if (rg->region_type == ME_REGION_CUSTOM) {
+    v = rg->n_offsets >= 1 ? rg->n_offsets : -1;
   } else {
     return -1;
   }
@@ -1569,10 +1578,17 @@ int me_coords_expand_region(const int32_t *coords, int64_t n, int32_t ncol, cons
       arg.ts[d] = align_stride[d];
     }
   const me_region rg = *region;
+  const bool custom = rg.region_type == ME_REGION_CUSTOM;
+  ME_CHECK(!custom || rg.offsets_dev != nullptr, "a CUSTOM region needs its offset table (offsets_dev)");
   const dim3 grid((unsigned)ceil_div(n * volume, 256)), block(256);
-  ME_DISPATCH_NCOL(ncol, hipLaunchKernelGGL(k_expand_region<NCOL>, grid, block, 0, stream, coords, n, rg,
-                                            (int32_t)volume, arg, out_coords,
-                                            align_stride != nullptr ? aligned : nullptr));
+  uint8_t *aligned_out = align_stride != nullptr ? aligned : nullptr;
+  if (custom) {
+    ME_DISPATCH_NCOL(ncol, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_expand_region<NCOL, true>), grid, block, 0, stream, coords,
+                                              n, rg, (int32_t)volume, arg, out_coords, aligned_out));
+  } else {
+    ME_DISPATCH_NCOL(ncol, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_expand_region<NCOL, false>), grid, block, 0, stream,
+                                              coords, n, rg, (int32_t)volume, arg, out_coords, aligned_out));
+  }
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -1721,8 +1737,10 @@ int me_kernel_map_probe(const uint64_t *in_table, int64_t in_capacity, const int
   ME_CHECK(volume >= 1 && volume <= 65535, "kernel volume out of range");
   ME_CHECK(in_capacity >= 64 && (in_capacity & (in_capacity - 1)) == 0, "capacity must be a power of two");
   ME_CHECK(n_out >= 0 && n_out * volume < (1ll << 32), "n_out * volume must fit in 32 bits");
+  const bool custom = region->region_type == ME_REGION_CUSTOM;   // (kernel_size is not part of a CUSTOM region)
+  ME_CHECK(!custom || region->offsets_dev != nullptr, "a CUSTOM region needs its offset table (offsets_dev)");
   for (int d = 0; d < region->ncol - 1; ++d)
-    ME_CHECK(region->kernel_size[d] > 0 && region->dilation[d] > 0 && region->tensor_stride[d] > 0,
+    ME_CHECK((custom || region->kernel_size[d] > 0) && region->dilation[d] > 0 && region->tensor_stride[d] > 0,
              "kernel size, dilation and tensor stride must be positive");
   if (region->region_type == ME_REGION_HYPER_CROSS)
     for (int d = 0; d < region->ncol - 1; ++d)
@@ -1748,8 +1766,13 @@ int me_kernel_map_probe(const uint64_t *in_table, int64_t in_capacity, const int
   const dim3 grid((unsigned)ceil_div(n_out, 256), (unsigned)volume), block(256);
   const uint32_t mask = (uint32_t)(in_capacity - 1);
   const me_region rg = *region;
-  ME_DISPATCH_NCOL(ncol, hipLaunchKernelGGL(k_kmap_probe<NCOL>, grid, block, 0, stream, in_table, mask,
-                                            in_coords, out_coords, n_out, rg, nbr, wcount, nw));
+  if (custom) {
+    ME_DISPATCH_NCOL(ncol, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_kmap_probe<NCOL, true>), grid, block, 0, stream, in_table,
+                                              mask, in_coords, out_coords, n_out, rg, nbr, wcount, nw));
+  } else {
+    ME_DISPATCH_NCOL(ncol, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_kmap_probe<NCOL, false>), grid, block, 0, stream, in_table,
+                                              mask, in_coords, out_coords, n_out, rg, nbr, wcount, nw));
+  }
   ME_LAUNCH_CHECK();
   if (int rc = exclusive_scan_u32(wcount, wcount, volume * nw, total, scan_ws,
                                   scan_workspace_bytes(volume * nw), stream))

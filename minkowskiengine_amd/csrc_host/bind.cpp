@@ -20,6 +20,13 @@ int to_int(const py::object &o) { return py::cast<int>(py::int_(o)); }   // pybi
 
 KeyT keyt(const CoordinateMapKey *k) { return k->get(); }
 
+// the `offset` argument of an operator: the [K, D] list of a RegionType.CUSTOM layer (an integer tensor of any dtype, on
+// any device); the built-in regions do not read it
+ivec region_offsets(const py::object &offset, int region_type, const ivec &kernel_size) {
+  if (region_type != ME_REGION_CUSTOM || offset.is_none()) return ivec();
+  return offsets_of(py::cast<Tensor>(offset), (int64_t)kernel_size.size());
+}
+
 CoordinateMapKey *new_key(const KeyT &k) { return new CoordinateMapKey(k.first, k.second); }
 
 // ---- autograd: convolution ----------------------------------------------------------------------------------------------------
@@ -47,9 +54,11 @@ struct ConvFn : public torch::autograd::Function<ConvFn> {
 
 Tensor conv_autograd(const Tensor &in_feat, const Tensor &kernel, const ivec &kernel_size, const ivec &kernel_stride,
                      const ivec &kernel_dilation, const py::object &region_type, bool expand_coordinates,
-                     CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *manager, bool transpose) {
+                     CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *manager, bool transpose,
+                     const py::object &offset) {
   auto km = prepare_conv(in_feat, kernel, kernel_size, kernel_stride, kernel_dilation, to_int(region_type),
-                         expand_coordinates, in_key, out_key, manager, transpose);
+                         expand_coordinates, in_key, out_key, manager, transpose,
+                         region_offsets(offset, to_int(region_type), kernel_size));
   return ConvFn::apply(in_feat, kernel, km);
 }
 
@@ -341,9 +350,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            }, py::return_value_policy::take_ownership)
       .def("kernel_map",
            [](CoordinateMapManager &s, const CoordinateMapKey *ik, const CoordinateMapKey *ok, const ivec &ks,
-              const ivec &st, const ivec &dl, const py::object &region_type, const py::object & /*offset*/,
+              const ivec &st, const ivec &dl, const py::object &region_type, const py::object &offset,
               bool is_transpose, bool is_pool) {
-             return s.kernel_map(keyt(ik), keyt(ok), ks, st, dl, to_int(region_type), is_transpose, is_pool)->to_dict();
+             const int rt = to_int(region_type);
+             return s.kernel_map(keyt(ik), keyt(ok), ks, st, dl, rt, is_transpose, is_pool, region_offsets(offset, rt, ks))
+                 ->to_dict();
            })
       .def("kernel_map_pairs",    // (not in the reference) number of pairs of a cached / built kernel map
            [](CoordinateMapManager &s, const CoordinateMapKey *ik, const CoordinateMapKey *ok, const ivec &ks,
@@ -389,31 +400,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // ---- operators with the reference's signatures (pybind/extern.hpp:53-392, 515-646) ----
   m.def("ConvolutionForwardGPU",
         [](const Tensor &in_feat, const Tensor &kernel, const ivec &ks, const ivec &st, const ivec &dl,
-           const py::object &region_type, const py::object & /*offset*/, bool expand_coordinates,
+           const py::object &region_type, const py::object &offset, bool expand_coordinates,
            const py::object & /*convolution_mode*/, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
            CoordinateMapManager *mgr) {
-          auto km = prepare_conv(in_feat, kernel, ks, st, dl, to_int(region_type), expand_coordinates, in_key, out_key, mgr,
-                                 false);
+          const int rt = to_int(region_type);
+          auto km = prepare_conv(in_feat, kernel, ks, st, dl, rt, expand_coordinates, in_key, out_key, mgr, false,
+                                 region_offsets(offset, rt, ks));
           return conv_forward_km(in_feat, kernel, *km);
         });
   m.def("ConvolutionTransposeForwardGPU",
         [](const Tensor &in_feat, const Tensor &kernel, const ivec &ks, const ivec &st, const ivec &dl,
-           const py::object &region_type, const py::object & /*offset*/, bool expand_coordinates,
+           const py::object &region_type, const py::object &offset, bool expand_coordinates,
            const py::object & /*convolution_mode*/, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
            CoordinateMapManager *mgr) {
-          auto km = prepare_conv(in_feat, kernel, ks, st, dl, to_int(region_type), expand_coordinates, in_key, out_key, mgr,
-                                 true);
+          const int rt = to_int(region_type);
+          auto km = prepare_conv(in_feat, kernel, ks, st, dl, rt, expand_coordinates, in_key, out_key, mgr, true,
+                                 region_offsets(offset, rt, ks));
           return conv_forward_km(in_feat, kernel, *km);
         });
   auto conv_bwd = [](bool transpose) {
     return [transpose](const Tensor &in_feat, Tensor grad_out, const Tensor &kernel, const ivec &ks, const ivec &st,
-                       const ivec &dl, const py::object &region_type, const py::object & /*offset*/,
+                       const ivec &dl, const py::object &region_type, const py::object &offset,
                        const py::object & /*convolution_mode*/, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr, bool need_grad_in) {
       check(in_feat.size(1) == kernel.size(1), "Input feature size and kernel size mismatch");
       check(grad_out.size(1) == kernel.size(2), "Output feature size and kernel size mismatch");
       grad_out = grad_out.contiguous();
-      auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, to_int(region_type), transpose, false);
+      const int rt = to_int(region_type);
+      auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, rt, transpose, false, region_offsets(offset, rt, ks));
       check(grad_out.size(0) == km->n_out, "Invalid grad_out size");
       auto r = conv_backward_km(in_feat.contiguous(), grad_out, kernel, *km, need_grad_in);
       return py::make_tuple(opt_out(r.first), r.second);
@@ -430,57 +444,64 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 
   m.def("LocalPoolingForwardGPU",
         [](const Tensor &in_feat, const ivec &ks, const ivec &st, const ivec &dl, const py::object &region_type,
-           const py::object & /*offset*/, const py::object &pooling_mode, CoordinateMapKey *in_key,
+           const py::object &offset, const py::object &pooling_mode, CoordinateMapKey *in_key,
            CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
-          auto r = local_pooling_forward(in_feat, ks, st, dl, to_int(region_type), to_int(pooling_mode), in_key, out_key, mgr);
+          const int rt = to_int(region_type);
+          auto r = local_pooling_forward(in_feat, ks, st, dl, rt, to_int(pooling_mode), in_key, out_key, mgr,
+                                         region_offsets(offset, rt, ks));
           return py::make_tuple(r.first, r.second);
         });
   m.def("LocalPoolingBackwardGPU",
         [](const Tensor &in_feat, const Tensor &grad_out, const Tensor &num_nonzero, const ivec &ks, const ivec &st,
-           const ivec &dl, const py::object &region_type, const py::object & /*offset*/, const py::object &pooling_mode,
+           const ivec &dl, const py::object &region_type, const py::object &offset, const py::object &pooling_mode,
            CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
-          return local_pooling_backward(in_feat, grad_out, num_nonzero, ks, st, dl, to_int(region_type),
-                                        to_int(pooling_mode), in_key, out_key, mgr);
+          const int rt = to_int(region_type);
+          return local_pooling_backward(in_feat, grad_out, num_nonzero, ks, st, dl, rt, to_int(pooling_mode), in_key,
+                                        out_key, mgr, region_offsets(offset, rt, ks));
         });
   m.def("LocalPoolingTransposeForwardGPU",
         [](const Tensor &in_feat, const ivec &ks, const ivec &st, const ivec &dl, const py::object &region_type,
-           const py::object & /*offset*/, bool generate_new_coordinates, const py::object &pooling_mode,
+           const py::object &offset, bool generate_new_coordinates, const py::object &pooling_mode,
            CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
-          auto r = local_pooling_transpose_forward(in_feat, ks, st, dl, to_int(region_type), generate_new_coordinates,
-                                                   to_int(pooling_mode), in_key, out_key, mgr);
+          const int rt = to_int(region_type);
+          auto r = local_pooling_transpose_forward(in_feat, ks, st, dl, rt, generate_new_coordinates, to_int(pooling_mode),
+                                                   in_key, out_key, mgr, region_offsets(offset, rt, ks));
           return py::make_tuple(r.first, r.second);
         });
   m.def("LocalPoolingTransposeBackwardGPU",
         [](const Tensor &in_feat, const Tensor &grad_out, const Tensor &num_nonzero, const ivec &ks, const ivec &st,
-           const ivec &dl, const py::object &region_type, const py::object & /*offset*/, const py::object &pooling_mode,
+           const ivec &dl, const py::object &region_type, const py::object &offset, const py::object &pooling_mode,
            CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
-          return local_pooling_transpose_backward(in_feat, grad_out, num_nonzero, ks, st, dl, to_int(region_type),
-                                                  to_int(pooling_mode), in_key, out_key, mgr);
+          const int rt = to_int(region_type);
+          return local_pooling_transpose_backward(in_feat, grad_out, num_nonzero, ks, st, dl, rt, to_int(pooling_mode),
+                                                  in_key, out_key, mgr, region_offsets(offset, rt, ks));
         });
   // channelwise convolution: no reference native operator (MinkowskiChannelwiseConvolution.py runs in Python); the
   // names follow the package's <Op>{Forward,Backward}GPU convention.  The GIL is released around the map and launches.
   m.def("ChannelwiseConvolutionForwardGPU",
         [](const Tensor &in_feat, const Tensor &kernel, const py::object &bias, const ivec &ks, const ivec &st,
-           const ivec &dl, const py::object &region_type, const py::object & /*offset*/, CoordinateMapKey *in_key,
+           const ivec &dl, const py::object &region_type, const py::object &offset, CoordinateMapKey *in_key,
            CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
           const Tensor b = opt_tensor(bias);
           const int rt = to_int(region_type);
+          const ivec offs = region_offsets(offset, rt, ks);
           py::gil_scoped_release nogil;
-          return channelwise_forward(in_feat, kernel, b, ks, st, dl, rt, in_key, out_key, mgr);
+          return channelwise_forward(in_feat, kernel, b, ks, st, dl, rt, in_key, out_key, mgr, offs);
         },
         py::arg("in_feat"), py::arg("kernel"), py::arg("bias"), py::arg("kernel_size"), py::arg("kernel_stride"),
         py::arg("kernel_dilation"), py::arg("region_type"), py::arg("offset"), py::arg("in_key"), py::arg("out_key"),
         py::arg("manager"));
   m.def("ChannelwiseConvolutionBackwardGPU",
         [](const Tensor &in_feat, const Tensor &grad_out, const Tensor &kernel, const ivec &ks, const ivec &st,
-           const ivec &dl, const py::object &region_type, const py::object & /*offset*/, CoordinateMapKey *in_key,
+           const ivec &dl, const py::object &region_type, const py::object &offset, CoordinateMapKey *in_key,
            CoordinateMapKey *out_key, CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_bias) {
           const int rt = to_int(region_type);
+          const ivec offs = region_offsets(offset, rt, ks);
           std::tuple<Tensor, Tensor, Tensor> r;
           {
             py::gil_scoped_release nogil;
             r = channelwise_backward(in_feat, grad_out, kernel, ks, st, dl, rt, in_key, out_key, mgr, need_grad_in,
-                                     need_grad_bias);
+                                     need_grad_bias, offs);
           }
           return py::make_tuple(opt_out(std::get<0>(r)), std::get<1>(r), opt_out(std::get<2>(r)));
         },
@@ -669,7 +690,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // ---- autograd entry points (the Python modules call these; backward never enters Python) ----
   m.def("conv_autograd", &conv_autograd, py::arg("in_feat"), py::arg("kernel"), py::arg("kernel_size"),
         py::arg("kernel_stride"), py::arg("kernel_dilation"), py::arg("region_type"), py::arg("expand_coordinates"),
-        py::arg("in_key"), py::arg("out_key"), py::arg("manager"), py::arg("transpose"));
+        py::arg("in_key"), py::arg("out_key"), py::arg("manager"), py::arg("transpose"),
+        py::arg("region_offsets") = py::none());
   m.def("batch_norm_train", &batch_norm_train, py::arg("x"), py::arg("skip"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("relu"),
         py::arg("num_batches_tracked"));

@@ -230,11 +230,23 @@ struct KernelMap : std::enable_shared_from_this<KernelMap> {
 };
 
 std::shared_ptr<KernelMap> build_kernel_map(const std::shared_ptr<CoordMap> &in_map,
-                                            const std::shared_ptr<CoordMap> &out_map, const me_region &region);
+                                            const std::shared_ptr<CoordMap> &out_map, const me_region &region,
+                                            const Tensor &region_offsets = Tensor());
 me_region make_region(int ncol, int region_type, const ivec &kernel_size, const ivec &dilation, const ivec &tensor_stride);
+// RegionType.CUSTOM (ME_REGION_CUSTOM): the offsets of a layer travel through the host layer as a flat row-major [K, D]
+// vector (empty for the built-in regions).  custom_region() validates it (K >= 1, width D, no duplicate rows), uploads
+// it — once per map build — and returns the region together with the device table, which the caller keeps alive for
+// as long as launches that got the region may run (a kernel map's store: "region_offsets").
+// any integer dtype, any device -> flat int32 on the host (its width checked against `dimension`); undefined / empty -> {}
+ivec offsets_of(const Tensor &region_offsets, int64_t dimension);
+bool offsets_are_origin(const ivec &offsets);
+std::pair<me_region, Tensor> custom_region(int ncol, const ivec &dilation, const ivec &tensor_stride, const ivec &offsets,
+                                           const c10::Device &dev);
 
 // ---- CoordinateMapManager (src/coordinate_map_manager.{hpp,cpp,cu}) ---------------------------------------------------
-typedef std::tuple<KeyT, KeyT, ivec, ivec, ivec, int, bool, bool> KernelMapKeyT;   // src/types.hpp:183-192
+// src/types.hpp:183-192, and the offsets of a CUSTOM region (empty otherwise): two layers with different lists on the
+// same maps do not share a kernel map
+typedef std::tuple<KeyT, KeyT, ivec, ivec, ivec, int, bool, bool, ivec> KernelMapKeyT;
 
 struct CoordinateMapManager {
   int algorithm, num_threads;
@@ -268,7 +280,7 @@ struct CoordinateMapManager {
   std::pair<Tensor, Tensor> stride_map(const KeyT &in_key, const KeyT &strided_key);
   std::pair<KeyT, bool> stride_region(const KeyT &in_key, const ivec &kernel_size, const ivec &kernel_dilation,
                                       int region_type, const ivec &out_tensor_stride, bool expand_coordinates,
-                                      bool is_transpose, const ivec *region_tensor_stride);
+                                      bool is_transpose, const ivec *region_tensor_stride, const ivec &offsets = ivec());
   KeyT prune(const KeyT &in_key, const Tensor &keep);
   Tensor pruning_rows(const KeyT &in_key, const KeyT &out_key);
   std::vector<Tensor> union_map(const std::vector<KeyT> &in_keys, CoordinateMapKey *out_key);
@@ -279,7 +291,7 @@ struct CoordinateMapManager {
   Tensor origin_rows(const KeyT &in_key);
   std::shared_ptr<KernelMap> kernel_map(const KeyT &in_key, const KeyT &out_key, const ivec &kernel_size,
                                         const ivec &kernel_stride, const ivec &kernel_dilation, int region_type,
-                                        bool is_transpose, bool is_pool);
+                                        bool is_transpose, bool is_pool, const ivec &offsets = ivec());
   // every strided map, kernel map, tile plan and weight-gradient geometry a network asks for, built in ONE call for a
   // new scene (the replay of another scene's request log: docs/HISTORY.md 9.8, round-3 build recipe)
   std::shared_ptr<RecipeLog> recipe_log = std::make_shared<RecipeLog>();   // serialised requests
@@ -311,29 +323,33 @@ std::pair<Tensor, Tensor> conv_backward_km(const Tensor &in_feat, Tensor grad_ou
 std::shared_ptr<KernelMap> prepare_conv(const Tensor &in_feat, const Tensor &kernel, const ivec &kernel_size,
                                         const ivec &kernel_stride, const ivec &kernel_dilation, int region_type,
                                         bool expand_coordinates, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
-                                        CoordinateMapManager *manager, bool transpose);
+                                        CoordinateMapManager *manager, bool transpose, const ivec &offsets = ivec());
 
 std::pair<Tensor, Tensor> local_pooling_forward(const Tensor &in_feat, const ivec &ks, const ivec &st, const ivec &dl,
                                                 int region_type, int pooling_mode, CoordinateMapKey *in_key,
-                                                CoordinateMapKey *out_key, CoordinateMapManager *mgr);
+                                                CoordinateMapKey *out_key, CoordinateMapManager *mgr,
+                                                const ivec &offsets = ivec());
 Tensor local_pooling_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &num_nonzero, const ivec &ks,
                               const ivec &st, const ivec &dl, int region_type, int pooling_mode,
-                              CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr);
+                              CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr,
+                              const ivec &offsets = ivec());
 std::pair<Tensor, Tensor> local_pooling_transpose_forward(const Tensor &in_feat, const ivec &ks, const ivec &st,
                                                           const ivec &dl, int region_type, bool generate_new_coordinates,
                                                           int pooling_mode, CoordinateMapKey *in_key,
-                                                          CoordinateMapKey *out_key, CoordinateMapManager *mgr);
+                                                          CoordinateMapKey *out_key, CoordinateMapManager *mgr,
+                                                          const ivec &offsets = ivec());
 Tensor local_pooling_transpose_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &num_nonzero, const ivec &ks,
                                         const ivec &st, const ivec &dl, int region_type, int pooling_mode,
-                                        CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr);
+                                        CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr,
+                                        const ivec &offsets = ivec());
 Tensor channelwise_forward(const Tensor &in_feat, const Tensor &kernel, const Tensor &bias, const ivec &ks,
                            const ivec &st, const ivec &dl, int region_type, CoordinateMapKey *in_key,
-                           CoordinateMapKey *out_key, CoordinateMapManager *mgr);
+                           CoordinateMapKey *out_key, CoordinateMapManager *mgr, const ivec &offsets = ivec());
 std::tuple<Tensor, Tensor, Tensor> channelwise_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &kernel,
                                                         const ivec &ks, const ivec &st, const ivec &dl, int region_type,
                                                         CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                                                         CoordinateMapManager *mgr, bool need_grad_in,
-                                                        bool need_grad_bias);
+                                                        bool need_grad_bias, const ivec &offsets = ivec());
 // instance normalisation (csrc/instance_norm.hip; twin of backend.InstanceNorm{Forward,Backward}GPU)
 std::tuple<Tensor, Tensor, Tensor> instance_norm_forward(const Tensor &in_feat, const Tensor &weight, const Tensor &bias,
                                                          double eps, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,

@@ -117,7 +117,7 @@ std::string CoordinateMapKey::repr() const {
 
 me_region make_region(int ncol, int region_type, const ivec &kernel_size, const ivec &dilation,
                       const ivec &tensor_stride) {
-  me_region rg;
+  me_region rg = {};
   rg.ncol = ncol;
   rg.region_type = region_type;
   for (int d = 0; d < ME_MAX_DIM; ++d) {
@@ -126,6 +126,46 @@ me_region make_region(int ncol, int region_type, const ivec &kernel_size, const 
     rg.tensor_stride[d] = d < ncol - 1 ? tensor_stride[d] : 1;
   }
   return rg;
+}
+
+ivec offsets_of(const Tensor &region_offsets, int64_t dimension) {
+  if (!region_offsets.defined() || region_offsets.numel() == 0) return ivec();
+  check(at::isIntegralType(region_offsets.scalar_type(), /*includeBool=*/false), "region_offsets must be integers");
+  check(region_offsets.dim() == 2, "region_offsets must be a [K, D] tensor");
+  check(region_offsets.size(1) == dimension, "region_offsets has " + std::to_string(region_offsets.size(1)) +
+                                                 " columns, the layer has dimension " + std::to_string(dimension));
+  Tensor t = region_offsets.detach().to(at::kCPU, at::kInt).contiguous();
+  const int32_t *p = t.data_ptr<int32_t>();
+  return ivec(p, p + t.numel());
+}
+
+bool offsets_are_origin(const ivec &offsets) {
+  for (int32_t v : offsets)
+    if (v != 0) return false;
+  return true;
+}
+
+std::pair<me_region, Tensor> custom_region(int ncol, const ivec &dilation, const ivec &tensor_stride, const ivec &offsets,
+                                           const c10::Device &dev) {
+  const int64_t D = ncol - 1;
+  check(!offsets.empty(), "region_offsets must be non empty when region_type is CUSTOM");
+  check(D >= 1 && (int64_t)offsets.size() % D == 0,
+        "region_offsets must have one column per spatial dimension (" + std::to_string(D) + ")");
+  const int64_t K = (int64_t)offsets.size() / D;
+  std::set<ivec> rows;
+  for (int64_t k = 0; k < K; ++k) rows.insert(ivec(offsets.begin() + k * D, offsets.begin() + (k + 1) * D));
+  check((int64_t)rows.size() == K, "region_offsets holds duplicate rows: every kernel tap needs its own offset");
+  me_region rg = make_region(ncol, ME_REGION_CUSTOM, ivec(D, 1), dilation, tensor_stride);
+  Tensor host = at::empty({K, D}, at::TensorOptions().dtype(at::kInt));
+  std::memcpy(host.data_ptr<int32_t>(), offsets.data(), offsets.size() * sizeof(int32_t));
+  Tensor table;
+  {
+    c10::DeviceGuard guard(dev);
+    table = host.to(dev);      // (on the current stream, ahead of the launches that read it)
+  }
+  rg.n_offsets = (int32_t)K;
+  rg.offsets_dev = table.data_ptr<int32_t>();
+  return {rg, table};
 }
 
 // ---- coordinate maps --------------------------------------------------------------------------------------------------
@@ -722,7 +762,8 @@ static std::shared_ptr<KernelMap> build_kernel_map_lds(const std::shared_ptr<Coo
 
 // iterate OUT coordinates, look up the IN map (src/coordinate_map_cpu.hpp:569-670)
 std::shared_ptr<KernelMap> build_kernel_map(const std::shared_ptr<CoordMap> &in_map,
-                                            const std::shared_ptr<CoordMap> &out_map, const me_region &region) {
+                                            const std::shared_ptr<CoordMap> &out_map, const me_region &region,
+                                            const Tensor &region_offsets) {
   const int64_t volume = me_region_volume(&region);
   check(volume > 0, "invalid kernel region");
   RoctxRange rx("me:kernel_map");
@@ -757,6 +798,7 @@ std::shared_ptr<KernelMap> build_kernel_map(const std::shared_ptr<CoordMap> &in_
   km->out_pairs_buf = out_pairs;
   km->store = std::make_shared<KernelMapStore>();
   km->store->t["nbr_out"] = nbr;
+  if (region_offsets.defined()) km->store->t["region_offsets"] = region_offsets;   // device table of a CUSTOM region
   return km;
 }
 
@@ -835,6 +877,12 @@ static std::string vec_ser(const ivec &v) {
   return s;
 }
 
+// region field of a serialised kernel-map key: the type, and behind a ':' the flat offsets of a CUSTOM region — one
+// field, so that the fields behind it keep their positions
+static std::string region_ser(int region_type, const ivec &offsets) {
+  return std::to_string(region_type) + (offsets.empty() ? "" : ":" + vec_ser(offsets));
+}
+
 KeyT CoordinateMapManager::stride(const KeyT &in_key, const ivec &kernel_stride, const std::string &string_id) {
   RoctxRange rx("me:stride");
   check(maps.count(in_key), "coordinate map not found");
@@ -895,18 +943,25 @@ std::pair<Tensor, Tensor> CoordinateMapManager::stride_map(const KeyT &in_key, c
 std::pair<KeyT, bool> CoordinateMapManager::stride_region(const KeyT &in_key, const ivec &kernel_size,
                                                           const ivec &kernel_dilation, int region_type,
                                                           const ivec &out_tensor_stride, bool expand_coordinates,
-                                                          bool is_transpose, const ivec *region_tensor_stride) {
+                                                          bool is_transpose, const ivec *region_tensor_stride,
+                                                          const ivec &offsets) {
   // src/coordinate_map_manager.cpp:436-466, src/coordinate_map_cpu.hpp:446-487
   check(maps.count(in_key), "coordinate map not found");
-  check(region_type != 2, "Not implemented yet.");
   KeyT ok(out_tensor_stride, "");
   if (maps.count(ok) && !expand_coordinates) return {ok, false};
   auto in_map = maps[in_key];
   const c10::Device dev = in_map->coords.device();
   const int ncol = (int)out_tensor_stride.size() + 1;
   const ivec &rts = region_tensor_stride ? *region_tensor_stride : out_tensor_stride;
-  me_region region = make_region(ncol, region_type, kernel_size, kernel_dilation, rts);
+  me_region region;
+  Tensor table;   // (CUSTOM: freed on this stream, behind the launch that reads it)
+  if (region_type == ME_REGION_CUSTOM) {
+    std::tie(region, table) = custom_region(ncol, kernel_dilation, rts, offsets, dev);
+  } else {
+    region = make_region(ncol, region_type, kernel_size, kernel_dilation, rts);
+  }
   const int64_t volume = me_region_volume(&region);
+  check(volume > 0, "invalid kernel region");
   const int64_t total = std::max<int64_t>(in_map->n * volume, 1);
   Tensor cand = empty_i32({total, ncol}, dev);
   Tensor aligned;
@@ -1056,7 +1111,9 @@ Tensor CoordinateMapManager::origin_rows(const KeyT &in_key) {
 // no dilation) hold every fine voxel exactly once -> bit 0 (the "in" = fine side).  A single-offset kernel pairs a row
 // with at most one row on BOTH sides.
 static int one_pair_sides_of(const ivec &kernel_size, const ivec &dilation, int region_type, const ivec &fine_ts,
-                             const ivec &coarse_ts, bool) {
+                             const ivec &coarse_ts, bool, const ivec &offsets = ivec()) {
+  // (a CUSTOM list: both sides for a single offset, else none — tiling is not proven for arbitrary lists)
+  if (region_type == ME_REGION_CUSTOM) return offsets.size() == kernel_size.size() ? 3 : 0;
   bool single = true, tiling = region_type == 0 && fine_ts.size() == kernel_size.size() && coarse_ts.size() == kernel_size.size();
   for (size_t i = 0; i < kernel_size.size(); ++i) {
     single = single && kernel_size[i] == 1;
@@ -1066,20 +1123,27 @@ static int one_pair_sides_of(const ivec &kernel_size, const ivec &dilation, int 
 }
 
 std::shared_ptr<KernelMap> CoordinateMapManager::kernel_map(const KeyT &in_key, const KeyT &out_key,
-                                                            const ivec &kernel_size, const ivec &kernel_stride,
+                                                            const ivec &kernel_size_, const ivec &kernel_stride,
                                                             const ivec &kernel_dilation, int region_type,
-                                                            bool is_transpose, bool is_pool) {
+                                                            bool is_transpose, bool is_pool, const ivec &offsets_) {
   // src/coordinate_map_manager.cpp:655-823 (cached; transposed maps reuse the swapped forward map :763-774)
-  check(region_type != 2, "Not implemented yet.");
-  check(kernel_size.size() == kernel_stride.size() && kernel_size.size() == kernel_dilation.size(), "kernel size mismatch");
-  KernelMapKeyT key(in_key, out_key, kernel_size, kernel_stride, kernel_dilation, region_type, is_transpose, is_pool);
+  check(kernel_size_.size() == kernel_stride.size() && kernel_size_.size() == kernel_dilation.size(), "kernel size mismatch");
+  // RegionType.CUSTOM: the offsets are part of the key, kernel_size is not part of the region (one canonical value)
+  const bool custom = region_type == ME_REGION_CUSTOM;
+  const ivec kernel_size = custom ? ivec(kernel_size_.size(), 1) : kernel_size_;
+  const ivec offsets = custom ? offsets_ : ivec();
+  check(!custom || !offsets.empty(), "region_offsets must be non empty when region_type is CUSTOM");
+  KernelMapKeyT key(in_key, out_key, kernel_size, kernel_stride, kernel_dilation, region_type, is_transpose, is_pool,
+                    offsets);
   auto it = kernel_maps.find(key);
   if (it != kernel_maps.end()) return it->second;
   auto in_map = get(in_key), out_map = get(out_key);
   check((int64_t)kernel_size.size() + 1 == in_map->coords.size(1), "kernel size mismatch");
   std::shared_ptr<KernelMap> km;
+  // (geometry shortcut: a CUSTOM list takes it only when its single offset is the origin — one non-zero offset is a shift)
   bool all_one = true;
   for (int k : kernel_size) all_one = all_one && k == 1;
+  if (custom) all_one = offsets.size() == kernel_size.size() && offsets_are_origin(offsets);
   if (in_key == out_key && all_one) {
     // a 1x1 kernel on one map: every row is paired with itself (src/coordinate_map_cpu.hpp:605-616)
     const int64_t n = in_map->n;
@@ -1099,31 +1163,35 @@ std::shared_ptr<KernelMap> CoordinateMapManager::kernel_map(const KeyT &in_key, 
     kernel_maps[key] = km;
     return km;
   }
+  const int ncol = (int)kernel_size.size() + 1;
+  auto region_on = [&](const std::shared_ptr<CoordMap> &lookup) -> std::pair<me_region, Tensor> {
+    if (custom) return custom_region(ncol, kernel_dilation, lookup->tensor_stride, offsets, lookup->coords.device());
+    return {make_region(ncol, region_type, kernel_size, kernel_dilation, lookup->tensor_stride), Tensor()};
+  };
   if (!is_transpose) {
-    me_region region = make_region((int)kernel_size.size() + 1, region_type, kernel_size, kernel_dilation,
-                                   in_map->tensor_stride);
-    km = build_kernel_map(in_map, out_map, region);
+    auto region = region_on(in_map);
+    km = build_kernel_map(in_map, out_map, region.first, region.second);
     km->one_pair_sides = one_pair_sides_of(kernel_size, kernel_dilation, region_type, in_map->tensor_stride,
-                                           out_map->tensor_stride, false);
+                                           out_map->tensor_stride, false, offsets);
   } else {
-    KernelMapKeyT swapped_key(out_key, in_key, kernel_size, kernel_stride, kernel_dilation, region_type, false, is_pool);
+    KernelMapKeyT swapped_key(out_key, in_key, kernel_size, kernel_stride, kernel_dilation, region_type, false, is_pool,
+                              offsets);
     auto fit = kernel_maps.find(swapped_key);
     std::shared_ptr<KernelMap> fwd;
     if (fit != kernel_maps.end()) {
       fwd = fit->second;
     } else {
       // out -> in map with the (finer) out tensor stride, then swap
-      me_region region = make_region((int)kernel_size.size() + 1, region_type, kernel_size, kernel_dilation,
-                                     out_map->tensor_stride);
-      fwd = build_kernel_map(out_map, in_map, region);
+      auto region = region_on(out_map);
+      fwd = build_kernel_map(out_map, in_map, region.first, region.second);
       fwd->one_pair_sides = one_pair_sides_of(kernel_size, kernel_dilation, region_type, out_map->tensor_stride,
-                                              in_map->tensor_stride, false);
+                                              in_map->tensor_stride, false, offsets);
     }
     km = fwd->swapped();
   }
   kernel_maps[key] = km;
   km->log_key = key_ser(in_key) + ";" + key_ser(out_key) + ";" + vec_ser(kernel_size) + ";" + vec_ser(kernel_stride) +
-                ";" + vec_ser(kernel_dilation) + ";" + std::to_string(region_type) + ";" + (is_transpose ? "1" : "0") +
+                ";" + vec_ser(kernel_dilation) + ";" + region_ser(region_type, offsets) + ";" + (is_transpose ? "1" : "0") +
                 ";" + (is_pool ? "1" : "0");
   km->log = recipe_log;
   log_request("kernel_map;" + km->log_key);
@@ -1151,6 +1219,10 @@ static ivec vec_de(const std::string &s) {
   for (const auto &p : split(s, ',')) v.push_back(std::atoi(p.c_str()));
   return v;
 }
+static ivec region_offsets_de(const std::string &s) {   // see region_ser
+  const size_t colon = s.find(':');
+  return colon == std::string::npos ? ivec() : vec_de(s.substr(colon + 1));
+}
 static KeyT key_de(const std::string &s) {
   const size_t bar = s.find('|');
   return KeyT(vec_de(s.substr(0, bar)), s.substr(bar + 1));
@@ -1176,13 +1248,14 @@ int64_t CoordinateMapManager::prefetch(const std::vector<std::string> &recipe) {
     } else if (f[0] == "kernel_map" && f.size() >= 9) {
       const KeyT ik = key_de(f[1]), ok = key_de(f[2]);
       if (maps.count(ik) && maps.count(ok)) {
-        kernel_map(ik, ok, vec_de(f[3]), vec_de(f[4]), vec_de(f[5]), std::atoi(f[6].c_str()), f[7] == "1", f[8] == "1");
+        kernel_map(ik, ok, vec_de(f[3]), vec_de(f[4]), vec_de(f[5]), std::atoi(f[6].c_str()), f[7] == "1", f[8] == "1",
+                   region_offsets_de(f[6]));
         ++done;
       }
     } else if ((f[0] == "conv_cfg" && f.size() >= 13) || (f[0] == "wgrad_cfg" && f.size() >= 12)) {
       const KeyT ik = key_de(f[1]), ok = key_de(f[2]);
       KernelMapKeyT key(ik, ok, vec_de(f[3]), vec_de(f[4]), vec_de(f[5]), std::atoi(f[6].c_str()), f[7] == "1",
-                        f[8] == "1");
+                        f[8] == "1", region_offsets_de(f[6]));
       auto it = kernel_maps.find(key);
       if (it != kernel_maps.end()) cfgs.push_back({it->second, f});
     }

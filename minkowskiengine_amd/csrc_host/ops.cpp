@@ -595,7 +595,7 @@ std::pair<Tensor, Tensor> conv_backward_km(const Tensor &in_feat, Tensor grad_ou
 std::shared_ptr<KernelMap> prepare_conv(const Tensor &in_feat, const Tensor &kernel, const ivec &kernel_size,
                                         const ivec &kernel_stride, const ivec &kernel_dilation, int region_type,
                                         bool expand_coordinates, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
-                                        CoordinateMapManager *manager, bool transpose) {
+                                        CoordinateMapManager *manager, bool transpose, const ivec &offsets) {
   check_feat("in_feat", in_feat);
   check_feat("kernel", kernel);
   check(in_feat.dim() == 2, "in_feat.dim() must be 2");
@@ -611,7 +611,7 @@ std::shared_ptr<KernelMap> prepare_conv(const Tensor &in_feat, const Tensor &ker
         // src/convolution_cpu.cpp:79-103: every kernel offset around every input voxel that falls on the output grid
         ivec out_ts(ts.size());
         for (size_t i = 0; i < ts.size(); ++i) out_ts[i] = ts[i] * kernel_stride[i];
-        auto r = manager->stride_region(ik, kernel_size, kernel_dilation, region_type, out_ts, true, false, &ts);
+        auto r = manager->stride_region(ik, kernel_size, kernel_dilation, region_type, out_ts, true, false, &ts, offsets);
         out_key->set_key(r.first.first, r.first.second);
       } else {
         KeyT ok = manager->stride(ik, kernel_stride, "");
@@ -625,11 +625,12 @@ std::shared_ptr<KernelMap> prepare_conv(const Tensor &in_feat, const Tensor &ker
         out_ts[i] = ts[i] / kernel_stride[i];
       }
       auto r = manager->stride_region(ik, kernel_size, kernel_dilation, region_type, out_ts, expand_coordinates, true,
-                                      nullptr);
+                                      nullptr, offsets);
       out_key->set_key(r.first.first, r.first.second);
     }
   }
-  return manager->kernel_map(ik, out_key->get(), kernel_size, kernel_stride, kernel_dilation, region_type, transpose, false);
+  return manager->kernel_map(ik, out_key->get(), kernel_size, kernel_stride, kernel_dilation, region_type, transpose, false,
+                             offsets);
 }
 
 // ---- pooling / broadcast ----------------------------------------------------------------------------------------------------
@@ -684,9 +685,10 @@ static void prepare_pool(const Tensor &in_feat, const ivec &kernel_stride, Coord
 
 std::pair<Tensor, Tensor> local_pooling_forward(const Tensor &in_feat, const ivec &ks, const ivec &st, const ivec &dl,
                                                 int region_type, int pooling_mode, CoordinateMapKey *in_key,
-                                                CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
+                                                CoordinateMapKey *out_key, CoordinateMapManager *mgr,
+                                                const ivec &offsets) {
   prepare_pool(in_feat, st, in_key, out_key, mgr, false);
-  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, false, true);
+  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, false, true, offsets);
   if (pooling_mode == LOCAL_MAX) {
     const c10::Device dev = in_feat.device();
     const int c = (int)in_feat.size(1);
@@ -714,12 +716,13 @@ std::pair<Tensor, Tensor> local_pooling_forward(const Tensor &in_feat, const ive
 
 Tensor local_pooling_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &num_nonzero, const ivec &ks,
                               const ivec &st, const ivec &dl, int region_type, int pooling_mode,
-                              CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
+                              CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr,
+                              const ivec &offsets) {
   check_feat("in_feat", in_feat);
   grad_out = grad_out.contiguous();
   check_feat("grad_out_feat", grad_out);
   if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
-  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, false, true);
+  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, false, true, offsets);
   check(grad_out.size(0) == km->n_out, "Invalid grad_out size");
   if (pooling_mode == LOCAL_MAX) {
     const c10::Device dev = in_feat.device();
@@ -746,23 +749,25 @@ Tensor local_pooling_backward(const Tensor &in_feat, Tensor grad_out, const Tens
 std::pair<Tensor, Tensor> local_pooling_transpose_forward(const Tensor &in_feat, const ivec &ks, const ivec &st,
                                                           const ivec &dl, int region_type, bool generate_new_coordinates,
                                                           int pooling_mode, CoordinateMapKey *in_key,
-                                                          CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
+                                                          CoordinateMapKey *out_key, CoordinateMapManager *mgr,
+                                                          const ivec &offsets) {
   (void)pooling_mode;
   check(!generate_new_coordinates, "generate_new_coordinates (stride_region) is not part of the hot path yet");
   prepare_pool(in_feat, st, in_key, out_key, mgr, true);
-  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, true, true);
+  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, true, true, offsets);
   return pool_sum(in_feat, km->table("out"), km->n_out, km->volume, Tensor(), false, true);
 }
 
 Tensor local_pooling_transpose_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &num_nonzero, const ivec &ks,
                                         const ivec &st, const ivec &dl, int region_type, int pooling_mode,
-                                        CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
+                                        CoordinateMapKey *in_key, CoordinateMapKey *out_key, CoordinateMapManager *mgr,
+                                        const ivec &offsets) {
   (void)num_nonzero;
   (void)pooling_mode;
   grad_out = grad_out.contiguous();
   check_feat("grad_out_feat", grad_out);
   if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
-  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, true, true);
+  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, true, true, offsets);
   return pool_sum(grad_out, km->table("in"), km->n_in, km->volume, Tensor(), false, false).first;
 }
 
@@ -786,9 +791,9 @@ static void check_cw(const Tensor &in_feat, const Tensor &kernel, const Tensor &
 
 Tensor channelwise_forward(const Tensor &in_feat, const Tensor &kernel, const Tensor &bias, const ivec &ks,
                            const ivec &st, const ivec &dl, int region_type, CoordinateMapKey *in_key,
-                           CoordinateMapKey *out_key, CoordinateMapManager *mgr) {
+                           CoordinateMapKey *out_key, CoordinateMapManager *mgr, const ivec &offsets) {
   prepare_pool(in_feat, st, in_key, out_key, mgr, false);
-  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, false, false);
+  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, false, false, offsets);
   check_cw(in_feat, kernel, bias, km->volume);
   const c10::Device dev = in_feat.device();
   const int c = (int)in_feat.size(1);
@@ -811,13 +816,13 @@ std::tuple<Tensor, Tensor, Tensor> channelwise_backward(const Tensor &in_feat, T
                                                         const ivec &ks, const ivec &st, const ivec &dl, int region_type,
                                                         CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                                                         CoordinateMapManager *mgr, bool need_grad_in,
-                                                        bool need_grad_bias) {
+                                                        bool need_grad_bias, const ivec &offsets) {
   check_feat("in_feat", in_feat);
   grad_out = grad_out.contiguous();
   check_feat("grad_out_feat", grad_out);
   if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
   check(grad_out.dim() == 2 && grad_out.size(1) == in_feat.size(1), "Output feature size and kernel size mismatch");
-  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, false, false);
+  auto km = mgr->kernel_map(in_key->get(), out_key->get(), ks, st, dl, region_type, false, false, offsets);
   check_cw(in_feat, kernel, Tensor(), km->volume);
   check(in_feat.size(0) == km->n_in, "Invalid in_feat size");
   check(grad_out.size(0) == km->n_out, "Invalid grad_out size");

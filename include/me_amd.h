@@ -87,7 +87,11 @@ typedef struct me_region {
  *   1.12 (220) round 12: arithmetic between two sparse tensors on different coordinate maps: the row tables of a union
  *              (me_union_tables) and the fused one-write-per-row forward / gather backward (me_union_arith_*)
  *   1.13 (230) round 13: ME_REGION_CUSTOM: me_region grew two trailing fields (n_offsets, offsets_dev); every entry point
- *              that takes a region accepts it, the LDS-bucketed probe declines it (me_kernel_map_probe_lds_bytes: -1) */
+ *              that takes a region accepts it, the LDS-bucketed probe declines it (me_kernel_map_probe_lds_bytes: -1)
+ *   1.14 (240) round 14: synchronised batch norm on the batch-norm kernels: a rank's (count, mean, M2) record, the merge of
+ *              the ranks' records, backward sums without the apply, their sum in rank order and the apply with the global
+ *              row count (me_bn_moments_floats, me_bn_local_moments, me_bn_stats_from_moments, me_bn_backward_sums,
+ *              me_bn_backward_reduce, me_bn_backward_apply) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -942,6 +946,55 @@ int me_bn_backward_residual(const void *x_dev, const void *dy_dev, const void *y
                             int32_t c, const float *mean_dev, const float *rstd_dev, const float *gamma_dev,
                             const float *beta_dev, int32_t relu, void *dx_dev, void *dskip_dev, float *grad_gamma_dev,
                             float *grad_beta_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
+/* ---- synchronised batch norm (MinkowskiSyncBatchNorm, MinkowskiEngine/MinkowskiNormalization.py:85-191: batch statistics
+ *      over the rows of ALL ranks of a process group; ABI 1.14): the same row passes with one more level around them.  The caller
+ *      owns the exchange (one all-gather per direction); these entry points are what runs before and after it.
+ * A rank's RECORD is me_bn_moments_floats(c) = 2 + 2c floats: the int64 row count (its bit pattern in the first two
+ * floats — never a rounded float), mean[c], M2[c] = sum (x - mean)^2.  Records must be 8-byte aligned.
+ *   me_bn_local_moments:      the record of this rank's [n, c] matrix: k_bn_partial's chunks merged in me_bn_stats' fixed
+ *                             order.  Writes the record and nothing else (no rstd, no running statistics).  n = 0 is
+ *                             legal (an empty rank): no row kernel, count 0, mean 0, M2 0.
+ *   me_bn_stats_from_moments: moments_dev = the records of `world` ranks, [world][2 + 2c] floats in rank order (what an
+ *                             all-gather leaves).  me_bn_stats' merge with the ranks as chunks, each with the count of
+ *                             its record, shifted to the mean of the FIRST rank that has rows (an empty rank 0 must not
+ *                             turn the shift into 0: B - A^2 / N would cancel for |mean| >> std).  Outputs as me_bn_stats;
+ *                             the running statistics use the GLOBAL count (unbiased variance: N_total - 1); when no
+ *                             rank has a row they stay untouched and num_batches_tracked is not incremented.
+ *                             n_total_dev (may be NULL) receives the global row count.
+ *                             One wave per channel, lane l takes ranks l, l + 64, ..., then a fixed tree: every rank
+ *                             computes bit-identical mean / rstd.  One record gives the bits of me_bn_stats while the
+ *                             row count is exact in fp32 (n <= 2^24): beyond it me_bn_stats' sum of float chunk counts
+ *                             and the record's int64 count converted once may round differently.
+ *   me_bn_backward_sums:      sum_dy[c] = sum dy, sum_dyx[c] = sum dy * xhat over this rank's rows (dy masked first when
+ *                             relu != 0: by the output recomputed from x, or by yout_dev when it is given — the residual
+ *                             form), i.e. me_bn_backward / me_bn_backward_residual stopped before the apply.  These LOCAL
+ *                             sums are grad_beta / grad_gamma of the rank.  n = 0 writes zeros.
+ *   me_bn_backward_reduce:    sums_dev = [world][2][c] floats in rank order (each rank's sum_dy | sum_dyx, gathered);
+ *                             added per channel in rank order (lane l takes ranks l, l + 64, ..., fixed tree) — not an
+ *                             all-reduce, whose order is the backend's.
+ *   me_bn_backward_apply:     dx (and dskip, may be NULL) of this rank's n_local rows from the global sums:
+ *                             dx = gamma * rstd * (dy - sum_dy / N - xhat * sum_dyx / N) with N = *n_total_dev when that
+ *                             is given (the count me_bn_stats_from_moments left on the device), else n_total.
+ *                             yout_dev != NULL with relu != 0: the residual form.  n_local = 0 launches nothing.
+ * workspace bytes for me_bn_local_moments / me_bn_backward_sums: me_bn_workspace_bytes(n, c). */
+int64_t me_bn_moments_floats(int32_t c);
+int me_bn_local_moments(const void *x_dev, int32_t is_bf16, int64_t n, int32_t c, float *moments_dev,
+                        void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_bn_stats_from_moments(const float *moments_dev, int32_t world, int32_t c, float eps, float momentum,
+                             float *mean_dev, float *rstd_dev, float *running_mean_dev, float *running_var_dev,
+                             int64_t *num_batches_tracked_dev, int64_t *n_total_dev, void *stream);
+int me_bn_backward_sums(const void *x_dev, const void *dy_dev, const void *yout_dev, int32_t is_bf16, int64_t n,
+                        int32_t c, const float *mean_dev, const float *rstd_dev, const float *gamma_dev,
+                        const float *beta_dev, int32_t relu, float *sum_dy_dev, float *sum_dyx_dev,
+                        void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_bn_backward_reduce(const float *sums_dev, int32_t world, int32_t c, float *sum_dy_dev, float *sum_dyx_dev,
+                          void *stream);
+int me_bn_backward_apply(const void *x_dev, const void *dy_dev, const void *yout_dev, int32_t is_bf16, int64_t n_local,
+                         int64_t n_total, const int64_t *n_total_dev, int32_t c, const float *mean_dev,
+                         const float *rstd_dev, const float *gamma_dev, const float *beta_dev, int32_t relu,
+                         const float *sum_dy_dev, const float *sum_dyx_dev, void *dx_dev, void *dskip_dev,
+                         void *stream);
 
 /* ---- instance normalisation over feature rows (MinkowskiInstanceNorm / MinkowskiStableInstanceNorm,
  *      MinkowskiEngine/MinkowskiNormalization.py:194-399: there a chain of global poolings and broadcasts; here batch

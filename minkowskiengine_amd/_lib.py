@@ -132,6 +132,15 @@ SIGNATURES = {
     "me_bn_apply_residual": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "me_bn_backward_residual": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp,
                                                c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_bn_moments_floats": (c_i64, [c_i32]),
+    "me_bn_local_moments": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "me_bn_stats_from_moments": (ctypes.c_int, [c_vp, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_vp, c_vp, c_vp,
+                                                c_vp, c_vp, c_vp, c_vp]),
+    "me_bn_backward_sums": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp,
+                                           c_vp, c_vp, c_i64, c_vp]),
+    "me_bn_backward_reduce": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "me_bn_backward_apply": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                            c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "me_inorm_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "me_inorm_stats": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "me_inorm_apply": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

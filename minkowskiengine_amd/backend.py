@@ -3067,6 +3067,124 @@ def bn_backward(x, dy, mean, rstd, gamma, beta=None, relu=False):
     return dx, gg, gb
 
 
+# ---- synchronised batch norm: the two-level forms around one all-gather per direction (layers._SyncBatchNormFunction
+# owns the exchange; tests/test_gpu_sync_norm_kernels.py plays the ranks with row blocks of one matrix) ----
+def _bn_check_rows(x):
+    """as _bn_check, but a rank of a synchronised batch norm may hold no rows"""
+    _check(x.is_cuda and x.is_contiguous() and x.dim() == 2 and x.shape[1] > 0,
+           "batch norm input must be a contiguous GPU matrix")
+    _check(x.dtype in (torch.float32, torch.bfloat16), "batch norm input must be float32 or bfloat16, got", x.dtype)
+
+
+def bn_local_moments(x):
+    """-> this rank's record, float32 [2 + 2c]: the int64 row count (bit pattern), mean[c], M2[c] of the rows of x"""
+    _bn_check_rows(x)
+    lib = _lib.load()
+    dev = x.device
+    n, c = int(x.shape[0]), int(x.shape[1])
+    rec = torch.empty(int(lib.me_bn_moments_floats(c)), dtype=torch.float32, device=dev)
+    ws = _workspace(int(lib.me_bn_workspace_bytes(n, c)), dev)
+    with _on(dev):
+        _lib.check(lib.me_bn_local_moments(_ptr(x), 1 if x.dtype == torch.bfloat16 else 0, n, c, _ptr(rec), _ptr(ws),
+                                           ws.numel(), _stream(dev)))
+    return rec
+
+
+def bn_stats_from_moments(records, eps, momentum, running_mean=None, running_var=None, num_batches_tracked=None):
+    """records: float32 [world, 2 + 2c], the ranks' bn_local_moments in rank order -> (mean, rstd, n_total): the
+    statistics of all rows (bit-identical on every rank) and the global row count as an int64 GPU scalar.  Running
+    statistics as bn_stats (global count; float32 temporaries for buffers of another dtype)."""
+    _check(records.is_cuda and records.is_contiguous() and records.dtype == torch.float32 and records.dim() == 2
+           and records.shape[0] > 0 and records.shape[1] >= 4 and records.shape[1] % 2 == 0,
+           "records must be a contiguous float32 GPU matrix [world, 2 + 2c]")
+    lib = _lib.load()
+    dev = records.device
+    world, c = int(records.shape[0]), (int(records.shape[1]) - 2) // 2
+    _check((running_mean is None) == (running_var is None), "running_mean and running_var: both or none")
+    _check(running_mean is None or (running_mean.numel() == c and running_var.numel() == c),
+           "running statistics must hold one value per channel")
+    rm_user, rv_user = running_mean, running_var
+    direct = _bn_stat_ok(running_mean, c) and _bn_stat_ok(running_var, c)
+    if not direct:
+        running_mean = rm_user.to(device=dev, dtype=torch.float32).contiguous().clone()
+        running_var = rv_user.to(device=dev, dtype=torch.float32).contiguous().clone()
+    if num_batches_tracked is not None and not (num_batches_tracked.is_cuda and num_batches_tracked.dtype == torch.int64
+                                                and num_batches_tracked.numel() == 1):
+        num_batches_tracked.add_(1)
+        num_batches_tracked = None
+    mean = torch.empty(c, dtype=torch.float32, device=dev)
+    rstd = torch.empty(c, dtype=torch.float32, device=dev)
+    n_total = torch.empty((), dtype=torch.int64, device=dev)
+    with _on(dev):
+        _lib.check(lib.me_bn_stats_from_moments(_ptr(records), world, c, float(eps), float(momentum), _ptr(mean),
+                                                _ptr(rstd), _ptr(running_mean), _ptr(running_var),
+                                                _ptr(num_batches_tracked), _ptr(n_total), _stream(dev)))
+    if not direct:
+        rm_user.copy_(running_mean)
+        rv_user.copy_(running_var)
+    return mean, rstd, n_total
+
+
+def bn_backward_sums(x, dy, mean, rstd, gamma, beta=None, relu=False, yout=None):
+    """-> float32 [2, c]: sum dy | sum dy * xhat over the rows of x (the rank's grad_beta | grad_gamma); dy masked by the
+    fused ReLU first (`yout` given: the residual form, the mask is the stored output)"""
+    _bn_check_rows(x)
+    _bn_check_params(x, mean, rstd, gamma, beta)
+    lib = _lib.load()
+    dev = x.device
+    n, c = int(x.shape[0]), int(x.shape[1])
+    _check(dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous(), "dy must match x")
+    _check(yout is None or (yout.shape == x.shape and yout.dtype == x.dtype and yout.is_contiguous()),
+           "the stored output must match x")
+    sums = torch.empty(2, c, dtype=torch.float32, device=dev)
+    ws = _workspace(int(lib.me_bn_workspace_bytes(n, c)), dev)
+    with _on(dev):
+        _lib.check(lib.me_bn_backward_sums(_ptr(x), _ptr(dy), _ptr(yout), 1 if x.dtype == torch.bfloat16 else 0, n, c,
+                                           _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), 1 if relu else 0,
+                                           _ptr(sums[0]), _ptr(sums[1]), _ptr(ws), ws.numel(), _stream(dev)))
+    return sums
+
+
+def bn_backward_reduce(sums):
+    """sums: float32 [world, 2, c], the ranks' bn_backward_sums in rank order -> their sum [2, c], added in rank order"""
+    _check(sums.is_cuda and sums.is_contiguous() and sums.dtype == torch.float32 and sums.dim() == 3
+           and sums.shape[0] > 0 and sums.shape[1] == 2 and sums.shape[2] > 0,
+           "sums must be a contiguous float32 GPU tensor [world, 2, c]")
+    lib = _lib.load()
+    dev = sums.device
+    out = torch.empty(2, int(sums.shape[2]), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(lib.me_bn_backward_reduce(_ptr(sums), int(sums.shape[0]), int(sums.shape[2]), _ptr(out[0]),
+                                             _ptr(out[1]), _stream(dev)))
+    return out
+
+
+def bn_backward_apply(x, dy, n_total, mean, rstd, gamma, beta, sums, relu=False, yout=None, need_dskip=False):
+    """-> (dx, dskip) of the rows of x from `sums` [2, c] taken over n_total rows (a python int, or the int64 GPU
+    scalar of bn_stats_from_moments: no read-back).  dskip (residual form): the masked gradient, dy itself without ReLU."""
+    _bn_check_rows(x)
+    _bn_check_params(x, mean, rstd, gamma, beta)
+    lib = _lib.load()
+    dev = x.device
+    n, c = int(x.shape[0]), int(x.shape[1])
+    _check(dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous(), "dy must match x")
+    _check(yout is None or (yout.shape == x.shape and yout.dtype == x.dtype and yout.is_contiguous()),
+           "the stored output must match x")
+    _check(sums.is_cuda and sums.is_contiguous() and sums.dtype == torch.float32 and tuple(sums.shape) == (2, c),
+           "sums must be a contiguous float32 GPU matrix [2, c]")
+    on_device = torch.is_tensor(n_total)
+    _check(not on_device or (n_total.is_cuda and n_total.dtype == torch.int64 and n_total.numel() == 1),
+           "a global row count on the device must be an int64 GPU scalar")
+    dx = torch.empty_like(x)
+    dskip = torch.empty_like(x) if (need_dskip and relu) else None
+    with _on(dev):
+        _lib.check(lib.me_bn_backward_apply(_ptr(x), _ptr(dy), _ptr(yout), 1 if x.dtype == torch.bfloat16 else 0, n,
+                                            0 if on_device else int(n_total), _ptr(n_total) if on_device else None, c,
+                                            _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), 1 if relu else 0,
+                                            _ptr(sums[0]), _ptr(sums[1]), _ptr(dx), _ptr(dskip), _stream(dev)))
+    return dx, (dskip if relu else dy) if need_dskip else None
+
+
 # ------------------------------------------------------------------------------------------------
 # instance normalisation (csrc/instance_norm.hip; the reference's MinkowskiInstanceNorm is a chain of its global
 # pooling and broadcast operators, MinkowskiNormalization.py:194-399, and has no native operator of its own)

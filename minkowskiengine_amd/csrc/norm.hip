@@ -15,6 +15,11 @@
 //   backward    k_bn_bwd_partial / k_bn_bwd_final   sum dy, sum dy * xhat per channel (two levels, fixed order)
 //               k_bn_bwd_apply dx = a * (dy - sum_dy / n - xhat * sum_dy_xhat / n)
 // T = float or __bf16 rows; statistics and parameters are fp32.
+//
+// Synchronised batch norm (MinkowskiSyncBatchNorm) puts one more level around the same row passes: a rank merges its
+// chunks into ONE record (count, mean[c], M2[c]) (k_bn_final<kBnToRecord>), the ranks' records are gathered and merged
+// by every rank in rank order (k_bn_final<kBnFromRecords>), the backward sums stop before the apply, are gathered,
+// added in rank order (k_bn_bwd_final over the gathered rows) and applied with the global row count.
 #include "norm_common.hpp"
 
 namespace me {
@@ -100,15 +105,32 @@ __global__ __launch_bounds__(256) void k_bn_partial(const T *__restrict__ x, int
 
 // tile_rows > 0: the partials are those of a convolution's tiles (k_conv_tile_bf16's statistics epilogue: tile g
 // holds rows [g * tile_rows, min((g + 1) * tile_rows, n)), any number of tiles); 0: k_bn_partial's equal chunks.
+//
+// MODE selects where the partials come from and what is written; the merge itself is the same text for all three:
+//   kBnFromChunks   the above
+//   kBnToRecord     chunks as above, but the result is this rank's RECORD for synchronised batch norm: the row count
+//                   (int64, *count_out), mean (mean_out) and M2 (rstd_out) — no rstd, no running statistics
+//   kBnFromRecords  the "chunks" are the records of `chunks` ranks, [rank][kBnRecordHead + 2c] floats at part_mean in
+//                   rank order, each with its own count; the shift is the mean of the FIRST RANK THAT HAS ROWS (with
+//                   an empty rank 0 a shift of 0 would leave B - A^2 / N to cancel for |mean| >> std — the case the
+//                   shift exists for); the global count goes to *count_out when given.  Every rank runs this on the
+//                   same gathered bytes: bit-identical mean / rstd everywhere.
+enum { kBnFromChunks = 0, kBnToRecord = 1, kBnFromRecords = 2 };
+constexpr int kBnRecordHead = 2;   // floats in front of a record's mean: the int64 row count (its bit pattern, not a rounded float)
+
+template <int MODE>
 __global__ __launch_bounds__(256) void k_bn_final(const float *__restrict__ part_mean,
                                                  const float *__restrict__ part_m2, int64_t n, int c, int chunks,
                                                  float eps, float momentum, float *__restrict__ mean_out,
                                                  float *__restrict__ rstd_out, float *__restrict__ running_mean,
                                                  float *__restrict__ running_var,
-                                                 int64_t *__restrict__ num_batches_tracked, int tile_rows) {
+                                                 int64_t *__restrict__ num_batches_tracked, int tile_rows,
+                                                 int64_t *__restrict__ count_out) {
   const int lane = threadIdx.x & 63;
   const int ch = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (num_batches_tracked != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *num_batches_tracked += 1;
+  // (kBnFromRecords counts the step behind the merge: a step in which no rank has a row is not a tracked batch)
+  if (MODE != kBnFromRecords && num_batches_tracked != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
+    *num_batches_tracked += 1;
   if (ch >= c) return;  // whole wave
   float rm_old = 0.f, rv_old = 0.f;   // (requested with the partials, not behind the merge)
   if (running_mean != nullptr && lane == 0) {
@@ -125,22 +147,44 @@ __global__ __launch_bounds__(256) void k_bn_final(const float *__restrict__ part
   // one 64-bit division per thread instead of two per chunk
   const int64_t cq_rows = tile_rows > 0 ? 0 : n / chunks;
   const uint32_t rem = (uint32_t)(n - cq_rows * chunks), G = (uint32_t)chunks;
-  const float shift = part_mean[ch];     // chunk 0 (every lane reads the same word)
+  const int64_t rec = kBnRecordHead + 2 * (int64_t)c;   // floats per record (kBnFromRecords)
+  [[maybe_unused]] auto rec_count = [&](int64_t g) { return *reinterpret_cast<const int64_t *>(part_mean + g * rec); };
+  float shift;
+  if constexpr (MODE == kBnFromRecords) {
+    int first = chunks;                  // first rank with rows: lane-strided scan, then a min over the wave
+    for (int g = lane; g < chunks; g += 64) first = min(first, rec_count(g) > 0 ? g : chunks);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off, 64));
+    shift = first < chunks ? part_mean[first * rec + kBnRecordHead + ch] : 0.f;
+  } else {
+    shift = part_mean[ch];               // chunk 0 (every lane reads the same word)
+  }
   float sa = 0.f, sb = 0.f, sn = 0.f;
+  [[maybe_unused]] int64_t total = 0;    // (kBnFromRecords) exact global row count
   for (int g0 = 0; g0 < chunks; g0 += 64 * L) {   // one pass unless a convolution had more than 512 tiles
     float pm[L], pq[L];
+    int64_t pc[MODE == kBnFromRecords ? L : 1];
 #pragma unroll
     for (int i = 0; i < L; ++i) {
       const int g = g0 + lane + i * 64;
       const int64_t gc = min(g, chunks - 1);   // unconditional loads (a conditional one costs a branch and a full wait)
-      pm[i] = part_mean[gc * c + ch];
-      pq[i] = part_m2[gc * c + ch];
+      if constexpr (MODE == kBnFromRecords) {
+        pc[i] = rec_count(gc);
+        pm[i] = part_mean[gc * rec + kBnRecordHead + ch];
+        pq[i] = part_mean[gc * rec + kBnRecordHead + c + ch];
+      } else {
+        pm[i] = part_mean[gc * c + ch];
+        pq[i] = part_m2[gc * c + ch];
+      }
     }
 #pragma unroll
     for (int i = 0; i < L; ++i) {
       const int g = g0 + lane + i * 64;
       float bn;
-      if (tile_rows > 0) {
+      if constexpr (MODE == kBnFromRecords) {
+        bn = (float)pc[i];
+        total += g < chunks ? pc[i] : 0;
+      } else if (tile_rows > 0) {
         bn = (float)min((int64_t)tile_rows, n - (int64_t)g * tile_rows);
       } else {
         const uint32_t extra = ((uint32_t)(g + 1) * rem) / G - ((uint32_t)g * rem) / G;
@@ -162,15 +206,28 @@ __global__ __launch_bounds__(256) void k_bn_final(const float *__restrict__ part
       sn += tn;
     }
   }
+  if constexpr (MODE == kBnFromRecords) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) total += __shfl_down(total, off, 64);   // (integers: any order; lane 0 is exact)
+  }
   const float cn = sn;
   const float am = cn > 0.f ? sa / cn : 0.f;
   const float cm = shift + am;
   const float cq = fmaxf(sb - sa * am, 0.f);
   if (lane != 0) return;
+  if constexpr (MODE == kBnToRecord) {
+    mean_out[ch] = cm;
+    rstd_out[ch] = cq;
+    if (ch == 0) *count_out = n;
+    return;
+  }
+  if (MODE == kBnFromRecords && count_out != nullptr && ch == 0) *count_out = total;
+  if (MODE == kBnFromRecords && num_batches_tracked != nullptr && ch == 0 && cn > 0.f) *num_batches_tracked += 1;
   const float var = cn > 0.f ? cq / cn : 0.f;
   mean_out[ch] = cm;
   rstd_out[ch] = rsqrtf(var + eps);
-  if (running_mean != nullptr) {
+  // (kBnFromRecords: a step in which NO rank had a row leaves the running statistics and the batch counter alone)
+  if (running_mean != nullptr && (MODE != kBnFromRecords || cn > 0.f)) {
     const float unbiased = cn > 1.f ? cq / (cn - 1.f) : var;
     running_mean[ch] = (1.f - momentum) * rm_old + momentum * cm;
     running_var[ch] = (1.f - momentum) * rv_old + momentum * unbiased;
@@ -309,28 +366,33 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const T *__restrict__ x,
 }
 
 // sums of the chunks per channel in a fixed order: grad_beta = sum dy, grad_gamma = sum dy * xhat
-// (one wave per channel and a fixed shuffle tree, as k_bn_final)
+// (one wave per channel and a fixed shuffle tree, as k_bn_final).  Chunk g's sums are at part_*[g * stride + ch]:
+// stride = c for k_bn_bwd_partial's output, 2c for the gathered [rank][2][c] sums of synchronised batch norm (added in
+// rank order; one pass of the outer loop unless there are more than kBnMaxChunks ranks).
 __global__ __launch_bounds__(256) void k_bn_bwd_final(const float *__restrict__ part_dy,
                                                      const float *__restrict__ part_dyx, int c, int chunks,
-                                                     float *__restrict__ sum_dy, float *__restrict__ sum_dyx) {
+                                                     float *__restrict__ sum_dy, float *__restrict__ sum_dyx,
+                                                     int stride) {
   const int lane = threadIdx.x & 63;
   const int ch = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (ch >= c) return;  // whole wave
   float a = 0.f, b = 0.f;
   constexpr int L = kBnMaxChunks / 64;
-  float pa[L], pb[L];
+  for (int g0 = 0; g0 < chunks; g0 += 64 * L) {
+    float pa[L], pb[L];
 #pragma unroll
-  for (int i = 0; i < L; ++i) {
-    const int g = lane + i * 64;
-    const int64_t gc = min(g, chunks - 1);
-    pa[i] = part_dy[gc * c + ch];
-    pb[i] = part_dyx[gc * c + ch];
-  }
+    for (int i = 0; i < L; ++i) {
+      const int g = g0 + lane + i * 64;
+      const int64_t gc = min(g, chunks - 1);
+      pa[i] = part_dy[gc * stride + ch];
+      pb[i] = part_dyx[gc * stride + ch];
+    }
 #pragma unroll
-  for (int i = 0; i < L; ++i) {
-    if (lane + i * 64 < chunks) {
-      a += pa[i];
-      b += pb[i];
+    for (int i = 0; i < L; ++i) {
+      if (g0 + lane + i * 64 < chunks) {
+        a += pa[i];
+        b += pb[i];
+      }
     }
   }
 #pragma unroll
@@ -350,6 +412,8 @@ __global__ __launch_bounds__(256) void k_bn_bwd_final(const float *__restrict__ 
 // dx = gamma * rstd * (dy - sum_dy / n - xhat * sum_dyx / n) = dy * ca + x * cb + cc per channel
 // (thread layout and load-first structure of k_bn_apply).  YOUT: residual form (mask from the stored output);
 // dskip (optional, uniform): the masked gradient, i.e. the gradient of the residual branch.
+// n bounds the rows; the 1 / n of the formula is that of the rows the sums were taken over: n_total, or *n_total_dev
+// when given (synchronised batch norm: the rows of all ranks, counted on the device) — n itself for a local batch norm.
 template <typename T, int V, bool YOUT>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply(const T *__restrict__ x, const T *__restrict__ dy,
                                                      int64_t n, int c, const float *__restrict__ mean,
@@ -358,7 +422,8 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const T *__restrict__ x, c
                                                      const float *__restrict__ sum_dy,
                                                      const float *__restrict__ sum_dyx, T *__restrict__ dx,
                                                      const float *__restrict__ beta, int relu,
-                                                     const T *__restrict__ yout, T *__restrict__ dskip) {
+                                                     const T *__restrict__ yout, T *__restrict__ dskip,
+                                                     int64_t n_total, const int64_t *__restrict__ n_total_dev) {
   const int P = c / V;
   const int W = min(P, (int)blockDim.x);
   const int R = max(1, (int)blockDim.x / P);
@@ -366,7 +431,8 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const T *__restrict__ x, c
   constexpr int RB = kBnRowsPerThread;
   const int64_t r0 = (int64_t)blockIdx.x * R * RB;
   if (rl >= R) return;
-  const float inv_n = 1.f / (float)n;
+  if (n_total_dev != nullptr) n_total = *n_total_dev;   // (uniform)
+  const float inv_n = 1.f / (float)n_total;
   for (int p = (int)threadIdx.x % W; p < P; p += W) {
     Row<T, V> tx[RB], tg[RB], ty[YOUT ? RB : 1];
 #pragma unroll
@@ -414,10 +480,9 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const T *__restrict__ x, c
 }
 
 
+// k_bn_partial over the matrix -> ws = part_mean[chunks][c] | part_m2[chunks][c]; *chunks_out = chunks
 template <typename T>
-static int bn_stats(const T *x, int64_t n, int c, float eps, float momentum, float *mean, float *rstd,
-                    float *running_mean, float *running_var, int64_t *num_batches_tracked, float *ws,
-                    hipStream_t stream) {
+static int bn_partials(const T *x, int64_t n, int c, float *ws, int *chunks_out, hipStream_t stream) {
   constexpr int W = 16 / (int)sizeof(T);  // channels per 16-byte access
   const bool aligned = (uintptr_t)x % 16 == 0;
   const int v = (aligned && c % W == 0) ? W : ((aligned && c % 4 == 0) ? 4 : 1);
@@ -430,8 +495,32 @@ static int bn_stats(const T *x, int64_t n, int c, float eps, float momentum, flo
   if (v == W) hipLaunchKernelGGL((k_bn_partial<T, W>), dim3(chunks), dim3(256), lds, stream, x, n, c, chunks, pm, pq);
   else if (v == 4) hipLaunchKernelGGL((k_bn_partial<T, 4>), dim3(chunks), dim3(256), lds, stream, x, n, c, chunks, pm, pq);
   else hipLaunchKernelGGL((k_bn_partial<T, 1>), dim3(chunks), dim3(256), lds, stream, x, n, c, chunks, pm, pq);
-  hipLaunchKernelGGL(k_bn_final, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, pm, pq, n, c, chunks, eps,
-                     momentum, mean, rstd, running_mean, running_var, num_batches_tracked, 0);
+  *chunks_out = chunks;
+  return 0;
+}
+
+template <typename T>
+static int bn_stats(const T *x, int64_t n, int c, float eps, float momentum, float *mean, float *rstd,
+                    float *running_mean, float *running_var, int64_t *num_batches_tracked, float *ws,
+                    hipStream_t stream) {
+  int chunks = 0;
+  if (int rc = bn_partials<T>(x, n, c, ws, &chunks, stream)) return rc;
+  hipLaunchKernelGGL(k_bn_final<kBnFromChunks>, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, ws,
+                     ws + (int64_t)chunks * c, n, c, chunks, eps, momentum, mean, rstd, running_mean, running_var,
+                     num_batches_tracked, 0, (int64_t *)nullptr);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+// this rank's record (count, mean[c], M2[c]) of synchronised batch norm: the chunks merged as bn_stats merges them
+template <typename T>
+static int bn_local_moments(const T *x, int64_t n, int c, float *record, float *ws, hipStream_t stream) {
+  int chunks = 0;
+  if (int rc = bn_partials<T>(x, n, c, ws, &chunks, stream)) return rc;
+  hipLaunchKernelGGL(k_bn_final<kBnToRecord>, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, ws,
+                     ws + (int64_t)chunks * c, n, c, chunks, 0.f, 0.f, record + kBnRecordHead,
+                     record + kBnRecordHead + c, (float *)nullptr, (float *)nullptr, (int64_t *)nullptr, 0,
+                     reinterpret_cast<int64_t *>(record));
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -461,20 +550,18 @@ static int bn_apply(const T *x, int64_t n, int c, const float *mean, const float
   return 0;
 }
 
+// first half of the backward pass: sum dy and sum dy * xhat per channel over this matrix (two levels, fixed order)
 template <typename T>
-static int bn_backward(const T *x, const T *dy, int64_t n, int c, const float *mean, const float *rstd,
-                       const float *gamma, const float *beta, int relu, T *dx, float *grad_gamma, float *grad_beta,
-                       float *ws, hipStream_t stream, const T *yout = nullptr, T *dskip = nullptr) {
-  constexpr int W = 16 / (int)sizeof(T);
-  const bool vec = (c % 4) == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0 && (uintptr_t)dx % 16 == 0 &&
-                   (uintptr_t)yout % 16 == 0 && (uintptr_t)dskip % 16 == 0;
-  const int v = (vec && c % W == 0) ? W : (vec ? 4 : 1);
+static int bn_backward_sums(const T *x, const T *dy, int64_t n, int c, const float *mean, const float *rstd,
+                            const float *gamma, const float *beta, int relu, float *sum_dy, float *sum_dyx, float *ws,
+                            hipStream_t stream, const T *yout, int v) {
   const int P = c / v;
   const int R = P >= 256 ? 1 : 256 / P;
   const int chunks = bn_chunks(n, R, kBnRowsPerThread / 2);
   float *pa = ws, *pb = ws + (int64_t)chunks * c;
   const size_t lds = bn_partial_lds_bytes(c, R);
   ME_CHECK(lds <= 64 * 1024, "channel count too large for the batch-norm kernels");
+  constexpr int W = 16 / (int)sizeof(T);
 #define ME_BN_BWD_PARTIAL(VV)                                                                                      \
   do {                                                                                                             \
     if (yout != nullptr)                                                                                           \
@@ -488,18 +575,29 @@ static int bn_backward(const T *x, const T *dy, int64_t n, int c, const float *m
   else if (v == 4) ME_BN_BWD_PARTIAL(4);
   else ME_BN_BWD_PARTIAL(1);
 #undef ME_BN_BWD_PARTIAL
-  hipLaunchKernelGGL(k_bn_bwd_final, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, pa, pb, c, chunks,
-                     grad_beta, grad_gamma);
+  hipLaunchKernelGGL(k_bn_bwd_final, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, pa, pb, c, chunks, sum_dy,
+                     sum_dyx, c);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+// second half: dx (and dskip) of the n rows of this matrix from sums taken over n_total (or *n_total_dev) rows
+template <typename T>
+static int bn_backward_apply(const T *x, const T *dy, int64_t n, int c, const float *mean, const float *rstd,
+                             const float *gamma, const float *beta, int relu, const float *sum_dy,
+                             const float *sum_dyx, T *dx, hipStream_t stream, const T *yout, T *dskip, int v,
+                             int64_t n_total, const int64_t *n_total_dev) {
+  constexpr int W = 16 / (int)sizeof(T);
   const int pieces = c / v;
   const dim3 grid((unsigned)ceil_div(n, (int64_t)(pieces >= 256 ? 1 : 256 / pieces) * kBnRowsPerThread));
 #define ME_BN_BWD_APPLY(VV)                                                                                        \
   do {                                                                                                             \
     if (yout != nullptr)                                                                                           \
       hipLaunchKernelGGL((k_bn_bwd_apply<T, VV, true>), grid, dim3(256), 0, stream, x, dy, n, c, mean, rstd, gamma, \
-                         grad_beta, grad_gamma, dx, beta, relu, yout, dskip);                                      \
+                         sum_dy, sum_dyx, dx, beta, relu, yout, dskip, n_total, n_total_dev);                      \
     else                                                                                                           \
       hipLaunchKernelGGL((k_bn_bwd_apply<T, VV, false>), grid, dim3(256), 0, stream, x, dy, n, c, mean, rstd, gamma, \
-                         grad_beta, grad_gamma, dx, beta, relu, yout, dskip);                                      \
+                         sum_dy, sum_dyx, dx, beta, relu, yout, dskip, n_total, n_total_dev);                      \
   } while (0)
   if (v == W) ME_BN_BWD_APPLY(W);
   else if (v == 4) ME_BN_BWD_APPLY(4);
@@ -507,6 +605,28 @@ static int bn_backward(const T *x, const T *dy, int64_t n, int c, const float *m
 #undef ME_BN_BWD_APPLY
   ME_LAUNCH_CHECK();
   return 0;
+}
+
+// channels per access of the backward kernels: 16 bytes, 4 channels or 1, by the channel count and every pointer
+template <typename T>
+static int bn_backward_width(int c, const void *x, const void *dy, const void *dx, const void *yout,
+                             const void *dskip) {
+  constexpr int W = 16 / (int)sizeof(T);
+  const bool vec = (c % 4) == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0 && (uintptr_t)dx % 16 == 0 &&
+                   (uintptr_t)yout % 16 == 0 && (uintptr_t)dskip % 16 == 0;
+  return (vec && c % W == 0) ? W : (vec ? 4 : 1);
+}
+
+template <typename T>
+static int bn_backward(const T *x, const T *dy, int64_t n, int c, const float *mean, const float *rstd,
+                       const float *gamma, const float *beta, int relu, T *dx, float *grad_gamma, float *grad_beta,
+                       float *ws, hipStream_t stream, const T *yout = nullptr, T *dskip = nullptr) {
+  const int v = bn_backward_width<T>(c, x, dy, dx, yout, dskip);
+  if (int rc = bn_backward_sums<T>(x, dy, n, c, mean, rstd, gamma, beta, relu, grad_beta, grad_gamma, ws, stream,
+                                   yout, v))
+    return rc;
+  return bn_backward_apply<T>(x, dy, n, c, mean, rstd, gamma, beta, relu, grad_beta, grad_gamma, dx, stream, yout,
+                              dskip, v, n, nullptr);
 }
 
 }  // namespace me
@@ -541,9 +661,9 @@ int me_bn_stats_from_tiles(const float *part_mean, const float *part_m2, int64_t
   ME_CHECK(part_mean != nullptr && part_m2 != nullptr, "the tile partials must be given");
   const int64_t tiles = ceil_div(n, (int64_t)tile_rows);
   ME_CHECK(tiles < (1ll << 30), "too many tiles");
-  hipLaunchKernelGGL(k_bn_final, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, part_mean, part_m2, n, c,
-                     (int)tiles, eps, momentum, mean, rstd, running_mean, running_var, num_batches_tracked,
-                     (int)tile_rows);
+  hipLaunchKernelGGL(k_bn_final<kBnFromChunks>, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, part_mean,
+                     part_m2, n, c, (int)tiles, eps, momentum, mean, rstd, running_mean, running_var,
+                     num_batches_tracked, (int)tile_rows, (int64_t *)nullptr);
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -607,11 +727,94 @@ int me_bn_backward(const void *x, const void *dy, int32_t is_bf16, int64_t n, in
                             gamma, beta, relu, reinterpret_cast<float *>(dx), grad_gamma, grad_beta, ws, stream);
 }
 
+// ---- synchronised batch norm: the two-level forms (include/me_amd.h) ----
+int64_t me_bn_moments_floats(int32_t c) { return kBnRecordHead + 2 * (int64_t)c; }
+
+int me_bn_local_moments(const void *x, int32_t is_bf16, int64_t n, int32_t c, float *moments, void *workspace,
+                        int64_t workspace_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_CHECK(n >= 0 && c > 0 && moments != nullptr, "invalid row / channel count or missing record");
+  if (n == 0) {   // an empty rank: count 0, mean 0, M2 0 are all-zero bits
+    ME_HIP(hipMemsetAsync(moments, 0, (size_t)me_bn_moments_floats(c) * sizeof(float), stream));
+    return 0;
+  }
+  ME_CHECK(workspace_bytes >= me_bn_workspace_bytes(n, c), "workspace too small");
+  float *ws = reinterpret_cast<float *>(workspace);
+  if (is_bf16) return bn_local_moments<__bf16>(reinterpret_cast<const __bf16 *>(x), n, c, moments, ws, stream);
+  return bn_local_moments<float>(reinterpret_cast<const float *>(x), n, c, moments, ws, stream);
+}
+
+int me_bn_stats_from_moments(const float *moments, int32_t world, int32_t c, float eps, float momentum, float *mean,
+                             float *rstd, float *running_mean, float *running_var, int64_t *num_batches_tracked,
+                             int64_t *n_total, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_CHECK(world > 0 && c > 0 && moments != nullptr, "invalid rank / channel count or missing records");
+  ME_CHECK((uintptr_t)moments % 8 == 0, "the records must be 8-byte aligned (int64 row counts)");
+  hipLaunchKernelGGL(k_bn_final<kBnFromRecords>, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, moments,
+                     (const float *)nullptr, (int64_t)0, c, (int)world, eps, momentum, mean, rstd, running_mean,
+                     running_var, num_batches_tracked, 0, n_total);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+int me_bn_backward_sums(const void *x, const void *dy, const void *yout, int32_t is_bf16, int64_t n, int32_t c,
+                        const float *mean, const float *rstd, const float *gamma, const float *beta, int32_t relu,
+                        float *sum_dy, float *sum_dyx, void *workspace, int64_t workspace_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_CHECK(n >= 0 && c > 0 && sum_dy != nullptr && sum_dyx != nullptr, "invalid row / channel count or missing sums");
+  if (n == 0) {
+    ME_HIP(hipMemsetAsync(sum_dy, 0, (size_t)c * sizeof(float), stream));
+    ME_HIP(hipMemsetAsync(sum_dyx, 0, (size_t)c * sizeof(float), stream));
+    return 0;
+  }
+  ME_CHECK(workspace_bytes >= me_bn_workspace_bytes(n, c), "workspace too small");
+  float *ws = reinterpret_cast<float *>(workspace);
+  if (!relu) yout = nullptr;
+  if (is_bf16)
+    return bn_backward_sums<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), n, c,
+                                    mean, rstd, gamma, beta, relu, sum_dy, sum_dyx, ws, stream,
+                                    reinterpret_cast<const __bf16 *>(yout),
+                                    bn_backward_width<__bf16>(c, x, dy, nullptr, yout, nullptr));
+  return bn_backward_sums<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), n, c, mean,
+                                 rstd, gamma, beta, relu, sum_dy, sum_dyx, ws, stream,
+                                 reinterpret_cast<const float *>(yout),
+                                 bn_backward_width<float>(c, x, dy, nullptr, yout, nullptr));
+}
+
+int me_bn_backward_reduce(const float *sums, int32_t world, int32_t c, float *sum_dy, float *sum_dyx, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_CHECK(world > 0 && c > 0 && sums != nullptr, "invalid rank / channel count or missing sums");
+  hipLaunchKernelGGL(k_bn_bwd_final, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, sums, sums + c, c,
+                     (int)world, sum_dy, sum_dyx, 2 * c);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+int me_bn_backward_apply(const void *x, const void *dy, const void *yout, int32_t is_bf16, int64_t n_local,
+                         int64_t n_total, const int64_t *n_total_dev, int32_t c, const float *mean, const float *rstd,
+                         const float *gamma, const float *beta, int32_t relu, const float *sum_dy,
+                         const float *sum_dyx, void *dx, void *dskip, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_CHECK(n_local >= 0 && c > 0, "invalid row / channel count");
+  ME_CHECK(n_total_dev != nullptr || n_total >= n_local, "the global row count must cover the local rows");
+  if (n_local == 0) return 0;
+  if (!relu) yout = nullptr;
+  if (is_bf16)
+    return bn_backward_apply<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), n_local,
+                                     c, mean, rstd, gamma, beta, relu, sum_dy, sum_dyx, reinterpret_cast<__bf16 *>(dx),
+                                     stream, reinterpret_cast<const __bf16 *>(yout), reinterpret_cast<__bf16 *>(dskip),
+                                     bn_backward_width<__bf16>(c, x, dy, dx, yout, dskip), n_total, n_total_dev);
+  return bn_backward_apply<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), n_local, c,
+                                  mean, rstd, gamma, beta, relu, sum_dy, sum_dyx, reinterpret_cast<float *>(dx), stream,
+                                  reinterpret_cast<const float *>(yout), reinterpret_cast<float *>(dskip),
+                                  bn_backward_width<float>(c, x, dy, dx, yout, dskip), n_total, n_total_dev);
+}
+
 }  // extern "C"
 
 // code-object preload (me_preload, coords.hip): resolving one kernel of this translation unit makes the runtime load the
 // unit's whole code object now instead of at the first launch from it
 extern "C" __attribute__((visibility("hidden"))) void me_preload_norm(void) {
   hipFuncAttributes attr;
-  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&me::k_bn_final));
+  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&me::k_bn_final<me::kBnFromChunks>));
 }

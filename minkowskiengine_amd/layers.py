@@ -77,6 +77,65 @@ class _BatchNormResidualFunction(Function):
         return dx, dskip, gw, gbias, None, None, None, None, None, None
 
 
+def _all_gather_rows(t, group):
+    """-> [world, *t.shape]: `t` of every rank of `group` in rank order, one collective.  all_gather_into_tensor on
+    RCCL (backend "nccl"); every other backend takes all_gather into the rows of the result — gloo has no
+    all_gather_into_tensor and stages GPU tensors through the host, mpi / ucc may lack it too."""
+    import torch.distributed as dist
+    out = t.new_empty((dist.get_world_size(group),) + tuple(t.shape))
+    if dist.get_backend(group) == "nccl":
+        dist.all_gather_into_tensor(out, t, group)
+    else:
+        dist.all_gather(list(out.unbind(0)), t, group)
+    return out
+
+
+class _SyncBatchNormFunction(Function):
+    """Training-mode batch norm with statistics over the rows of ALL ranks of `group`, on the kernels of
+    csrc/norm.hip: y = [relu] (batch_norm(x) [+ skip]).  skip None: the plain form (_BatchNormTrainFunction with a
+    fused ReLU), else the residual form (_BatchNormResidualFunction).  One all-gather per direction: forward, each
+    rank's record (row count, mean, M2), merged by every rank in rank order — bit-identical statistics everywhere;
+    backward, each rank's [2c] sums, added in rank order (not an all-reduce, whose order is the backend's).  The
+    global row count stays on the device.  A rank without rows enters both collectives.  grad_weight / grad_bias are
+    the LOCAL sums, as in torch's SyncBatchNorm: DistributedDataParallel averages them.  One Python function for both
+    host layers: the path is bound by its exchange, not by its launches."""
+
+    @staticmethod
+    def forward(ctx, x, skip, weight, bias, running_mean, running_var, momentum, eps, relu, num_batches_tracked, group):
+        x = x.contiguous()
+        w32 = weight.float() if weight is not None else None
+        b32 = bias.float() if bias is not None else None
+        records = _all_gather_rows(MEB.bn_local_moments(x), group)
+        mean, rstd, n_total = MEB.bn_stats_from_moments(records, eps, momentum, running_mean, running_var,
+                                                        num_batches_tracked)
+        if x.shape[0] == 0:
+            y = torch.empty_like(x)
+        elif skip is None:
+            y = MEB.bn_apply(x, mean, rstd, w32, b32, relu)
+        else:
+            y = MEB.bn_apply_residual(x, skip.contiguous(), mean, rstd, w32, b32, relu)
+        # (residual form: the ReLU mask of the backward pass is the stored output, which also holds the skip branch)
+        ctx.save_for_backward(x, y if (relu and skip is not None) else None, mean, rstd, w32, b32, n_total)
+        ctx.param_dtype = weight.dtype if weight is not None else None
+        ctx.has_bias = bias is not None
+        ctx.relu = relu
+        ctx.residual = skip is not None
+        ctx.group = group
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, yout, mean, rstd, w32, b32, n_total = ctx.saved_tensors
+        dy = dy.to(x.dtype).contiguous()
+        local = MEB.bn_backward_sums(x, dy, mean, rstd, w32, b32, ctx.relu, yout)
+        sums = MEB.bn_backward_reduce(_all_gather_rows(local, ctx.group))
+        dx, dskip = MEB.bn_backward_apply(x, dy, n_total, mean, rstd, w32, b32, sums, ctx.relu, yout,
+                                          need_dskip=ctx.residual and ctx.needs_input_grad[1])
+        gw = local[1].to(ctx.param_dtype) if ctx.param_dtype is not None else None
+        gbias = local[0].to(ctx.param_dtype) if ctx.has_bias else None
+        return dx, dskip, gw, gbias, None, None, None, None, None, None, None
+
+
 class MinkowskiBatchNorm(nn.Module):
     """torch.nn.BatchNorm1d semantics on the feature matrix (MinkowskiNormalization.py:35-82).  The parameters
     and running statistics live in `self.bn` (same state-dict names as the reference); on the GPU the arithmetic
@@ -91,10 +150,12 @@ class MinkowskiBatchNorm(nn.Module):
         # that the following MinkowskiReLU passes it through; the results are those of the two separate layers.
         self.fuse_relu = False
 
-    def _native(self, f):
+    _TORCH_MODULE = nn.BatchNorm1d    # what `self.bn` is (a subclass of it keeps torch's arithmetic)
+
+    def _native(self, f, min_rows=2):
         bn = self.bn
-        return (not _TORCH_BN and type(bn) is nn.BatchNorm1d and f.is_cuda and f.dim() == 2 and f.shape[0] > 1
-                and f.dtype in (torch.float32, torch.bfloat16) and bn.momentum is not None
+        return (not _TORCH_BN and type(bn) is self._TORCH_MODULE and f.is_cuda and f.dim() == 2
+                and f.shape[0] >= min_rows and f.dtype in (torch.float32, torch.bfloat16) and bn.momentum is not None
                 and f.shape[1] <= 2048)
 
     def forward(self, input):
@@ -167,12 +228,58 @@ class MinkowskiBatchNorm(nn.Module):
 
 
 class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
+    """MinkowskiBatchNorm with batch statistics over all ranks of a process group (MinkowskiNormalization.py:85-191).
+    `self.bn` is a torch.nn.SyncBatchNorm (parameters, buffers, process group, state-dict names); in training mode on
+    the GPU the arithmetic runs on this package's kernels around one all-gather per direction
+    (_SyncBatchNormFunction), with `fuse_relu` and the fused `forward_residual` of the parent.  Without an exchange —
+    torch.distributed not initialised, a group of one rank, evaluation — it is the parent's local path, as torch's
+    module uses local statistics then.  momentum=None, CPU or non-2-D features, more than 2048 channels, float64 and
+    ME_AMD_TORCH_BN=1 go to `self.bn(f)`."""
+    _TORCH_MODULE = nn.SyncBatchNorm
+
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True,
                  process_group=None):
         nn.Module.__init__(self)
-        self.fuse_relu = False   # torch's SyncBatchNorm does the arithmetic: the following MinkowskiReLU rectifies
+        self.fuse_relu = False
         self.bn = nn.SyncBatchNorm(num_features, eps=eps, momentum=momentum, affine=affine,
                                    track_running_stats=track_running_stats, process_group=process_group)
+
+    def _exchange_group(self):
+        """the process group to exchange statistics with, None when torch's SyncBatchNorm would use local ones"""
+        import torch.distributed as dist
+        bn = self.bn
+        if not (bn.training and dist.is_available() and dist.is_initialized()):
+            return None
+        group = bn.process_group if bn.process_group else dist.group.WORLD
+        return group if dist.get_world_size(group) > 1 else None
+
+    def _train(self, f, skip, relu, group):
+        bn = self.bn
+        rm = bn.running_mean if bn.track_running_stats else None
+        rv = bn.running_var if bn.track_running_stats else None
+        nbt = bn.num_batches_tracked if rm is not None else None
+        return _SyncBatchNormFunction.apply(f, skip, bn.weight, bn.bias, rm, rv, bn.momentum, bn.eps, bool(relu), nbt,
+                                            group)
+
+    def forward(self, input):
+        group = self._exchange_group()
+        if group is None:
+            return super().forward(input)
+        f = input.F
+        if not self._native(f, min_rows=0):       # (a rank may hold no rows: it still enters the collectives)
+            return _rewrap(input, self.bn(f))
+        out = _rewrap(input, self._train(f, None, self.fuse_relu, group))
+        out._rectified = self.fuse_relu
+        return out
+
+    def forward_residual(self, input, skip, relu=True):
+        group = self._exchange_group()
+        f = input.F
+        if (group is None or not _FUSE_RESIDUAL or not self._native(f, min_rows=0) or skip.F.dtype != f.dtype
+                or skip.F.shape != f.shape):
+            return super().forward_residual(input, skip, relu)      # (the three operators around self.forward)
+        assert input.coordinate_map_key == skip.coordinate_map_key, "residual add needs a shared coordinate map"
+        return _rewrap(input, self._train(f, skip.F, relu, group))
 
     @classmethod
     def convert_sync_batchnorm(cls, module, process_group=None):
@@ -187,6 +294,7 @@ class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
         if isinstance(module, MinkowskiBatchNorm):
             out = cls(module.bn.num_features, module.bn.eps, module.bn.momentum, module.bn.affine,
                       module.bn.track_running_stats, process_group)
+            out.fuse_relu = module.fuse_relu      # (not in the reference: the fused ReLU survives the conversion)
             if module.bn.affine:          # the same Parameter objects, as the reference (:176-179)
                 out.bn.weight = module.bn.weight
                 out.bn.bias = module.bn.bias

@@ -97,7 +97,11 @@ __global__ __launch_bounds__(256) void k_pool_sum(const T *__restrict__ src, int
 }
 
 // dst[t][c] = max over k of src[tbl[k][t]][c], mask[t][c] = flat index (source row * C + c) of the
-// first maximum in k order, -FLT_MAX / -1 for rows without neighbours (src/pooling_max_kernel.hpp:36-96)
+// first maximum in k order (src/pooling_max_kernel.hpp:36-96).  The search starts from -FLT_MAX / -1 with a strict `<`,
+// so a (row, channel) without a winner — no neighbour, or every neighbour NaN, -inf or -FLT_MAX — keeps the start value
+// and mask -1, which the backward kernel matches with no input (the reference's CPU loop would index grad_in[-1]).
+// Stored start value: -FLT_MAX for float; for __bf16 the store converts (__bf16)(-FLT_MAX) with round-to-nearest-even,
+// which is -inf (0xff80: -FLT_MAX lies above the largest finite bf16 by more than half a bf16 ulp).
 template <typename T, int V>
 __global__ __launch_bounds__(256) void k_pool_max(const T *__restrict__ src, int c,
                                                  const int32_t *__restrict__ tbl, int64_t n_tgt, int volume,

@@ -189,6 +189,10 @@ def conv_backward(in_feat, grad_out, kernel, kmap, dtype=np.float64):
 
 
 # ---- pooling / broadcast (numpy restatement; float32 by default to follow the reference's arithmetic) --------
+def _all_distinct(rows):
+    return np.unique(rows).size == rows.size
+
+
 def pool_forward(in_feat, kmap, n_out, mode, dtype=np.float32):
     """mode "sum" | "avg" | "max" -> (out, num_nonzero | max_index).
     NonzeroAvgPoolingForwardKernelCPU (pooling_avg_kernel.hpp:41-108) / MaxPoolingForwardKernelCPU
@@ -199,7 +203,13 @@ def pool_forward(in_feat, kmap, n_out, mode, dtype=np.float32):
         out = np.full((n_out, c), -np.finfo(dtype).max, dtype)
         idx = np.full((n_out, c), -1, np.int32)
         for k in sorted(kmap):
-            for i, o in zip(*[np.asarray(a) for a in kmap[k]]):
+            i_k, o_k = [np.asarray(a) for a in kmap[k]]
+            if _all_distinct(o_k):      # one pair per output row: the whole list at once is the same sequence of updates
+                better = out[o_k] < x[i_k]
+                out[o_k] = np.where(better, x[i_k], out[o_k])
+                idx[o_k] = np.where(better, i_k[:, None] * c + np.arange(c), idx[o_k])
+                continue
+            for i, o in zip(i_k, o_k):
                 better = out[o] < x[i]
                 out[o] = np.where(better, x[i], out[o])
                 idx[o] = np.where(better, i * c + np.arange(c), idx[o])
@@ -207,7 +217,12 @@ def pool_forward(in_feat, kmap, n_out, mode, dtype=np.float32):
     out = np.zeros((n_out, c), dtype)
     cnt = np.zeros(n_out, dtype)
     for k in sorted(kmap):
-        for i, o in zip(*[np.asarray(a) for a in kmap[k]]):
+        i_k, o_k = [np.asarray(a) for a in kmap[k]]
+        if _all_distinct(o_k):
+            out[o_k] += x[i_k]
+            cnt[o_k] += 1
+            continue
+        for i, o in zip(i_k, o_k):
             out[o] += x[i]
             cnt[o] += 1
     if mode == "avg":
@@ -227,8 +242,17 @@ def pool_backward(grad_out, kmap, n_in, mode, aux, dtype=np.float32):
         m = np.asarray(aux).reshape(-1)
         np.add.at(flat, m[m >= 0], g.reshape(-1)[m >= 0])
         return grad_in
+    aux = np.asarray(aux)
     for k in sorted(kmap):
-        for i, o in zip(*[np.asarray(a) for a in kmap[k]]):
+        i_k, o_k = [np.asarray(a) for a in kmap[k]]
+        if _all_distinct(i_k):          # one pair per input row: no row is added to twice within the list
+            if mode == "avg":
+                nz = aux[o_k] > 0
+                grad_in[i_k[nz]] += g[o_k[nz]] / aux[o_k[nz]].astype(dtype)[:, None]
+            else:
+                grad_in[i_k] += g[o_k]
+            continue
+        for i, o in zip(i_k, o_k):
             if mode == "avg":
                 if aux[o] > 0:
                     grad_in[i] += g[o] / dtype(aux[o])

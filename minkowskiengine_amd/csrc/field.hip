@@ -505,11 +505,11 @@ int me_csr_from_coo(const int32_t *keys, const int32_t *cols, const void *vals, 
   ME_CHECK(nnz >= 0 && nnz < (1ll << 31) && n_rows >= 0 && n_rows < (1ll << 31), "sizes must fit in int32");
   ME_CHECK(val_bytes == 4 || val_bytes == 8 || vals == nullptr, "values must be 4 or 8 bytes");
   ME_CHECK(rowptr != nullptr && cols_out != nullptr, "rowptr and cols_out must be given");
-  ME_CHECK((vals == nullptr) == (vals_out == nullptr), "vals and vals_out go together");
-  if (nnz == 0) {
+  if (nnz == 0) {   // (an empty vals array has no address: nothing to pair with vals_out)
     ME_HIP(hipMemsetAsync(rowptr, 0, (size_t)(n_rows + 1) * 4, stream));
     return 0;
   }
+  ME_CHECK((vals == nullptr) == (vals_out == nullptr), "vals and vals_out go together");
   ME_CHECK(ws != nullptr && ws_bytes >= me_csr_from_coo_workspace_bytes(nnz), "workspace too small");
   char *p = reinterpret_cast<char *>(ws);
   const int64_t a = align_up(nnz * 4, 256);

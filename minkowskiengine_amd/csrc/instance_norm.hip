@@ -26,9 +26,12 @@
 
 namespace me {
 
-// LDS of the partial kernels: bn_partial_lds_bytes | 4 ints (range and per-instance scan of a chunk)
+// LDS of the partial kernels: bn_partial_lds_bytes.  The 4 ints of the range and per-instance scans of a chunk live in
+// s_tmp: bn_reduce_lanes alone writes s_tmp, after its leading barrier (every scan result has been read by then), and has
+// read it for the last time before its trailing barrier (the next scan starts after that).  5 c + 256 floats with one row
+// lane: rows of up to 3225 channels fit into 64 KiB.
 __host__ __device__ constexpr size_t in_partial_lds_bytes(int c, int row_lanes) {
-  return bn_partial_lds_bytes(c, row_lanes) + 4 * sizeof(int);
+  return bn_partial_lds_bytes(c, row_lanes);
 }
 
 template <int V>
@@ -47,6 +50,9 @@ __device__ __forceinline__ void load_f32(const float *__restrict__ p, float (&v)
     for (int j = 0; j < V; ++j) v[j] = p[j];
   }
 }
+
+// max(v, 0) that keeps a NaN (fmaxf returns the other operand): non-finite rows must reach rstd, as in the float64 twins
+__device__ __forceinline__ float clamp_neg(float v) { return v < 0.f ? 0.f : v; }
 
 __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll
@@ -132,7 +138,7 @@ __global__ __launch_bounds__(256) void k_in_partial(const T *__restrict__ x, con
   const int W = min(P, (int)blockDim.x);
   const int R = max(1, (int)blockDim.x / P);
   float *s_out = s_red + (size_t)R * 2 * c, *s_tmp = s_out + 2 * c, *s_shift = s_tmp + 256;
-  int *s_i = reinterpret_cast<int *>(s_shift + c);
+  int *s_i = reinterpret_cast<int *>(s_tmp);
   const int64_t r0 = chunk_begin(blockIdx.x, n, chunks), r1 = chunk_begin(blockIdx.x + 1, n, chunks);
   if (r0 >= r1) return;  // whole workgroup
   int bmin, bmax;
@@ -194,7 +200,7 @@ __global__ __launch_bounds__(256) void k_in_partial(const T *__restrict__ x, con
       const float a = s_out[ch], q = s_out[c + ch];
       const float m = a / cnt;
       part_mean[o + ch] = s_shift[ch] + m;
-      part_m2[o + ch] = fmaxf(q - a * m, 0.f);
+      part_m2[o + ch] = clamp_neg(q - a * m);
     }
     if (threadIdx.x == 0) part_cnt[(int64_t)blockIdx.x * n_batch + b] = cnt;
     __syncthreads();   // s_out / s_shift are rewritten for the next instance
@@ -259,7 +265,7 @@ __global__ __launch_bounds__(256) void k_in_final(const float *__restrict__ part
   }
   if (lane != 0) return;
   const float am = sa / sn;
-  const float var = fmaxf(sb - sa * am, 0.f) / sn;
+  const float var = clamp_neg(sb - sa * am) / sn;
   mean_out[idx] = shift + am;
   rstd_out[idx] = 1.f / sqrtf(var + eps);
 }
@@ -317,8 +323,8 @@ __global__ __launch_bounds__(256) void k_in_bwd_partial(const T *__restrict__ x,
   const int P = c / V;
   const int W = min(P, (int)blockDim.x);
   const int R = max(1, (int)blockDim.x / P);
-  float *s_out = s_red + (size_t)R * 2 * c, *s_tmp = s_out + 2 * c, *s_shift = s_tmp + 256;
-  int *s_i = reinterpret_cast<int *>(s_shift + c);
+  float *s_out = s_red + (size_t)R * 2 * c, *s_tmp = s_out + 2 * c;
+  int *s_i = reinterpret_cast<int *>(s_tmp);
   const int64_t r0 = chunk_begin(blockIdx.x, n, chunks), r1 = chunk_begin(blockIdx.x + 1, n, chunks);
   if (r0 >= r1) return;  // whole workgroup
   int bmin, bmax;

@@ -44,6 +44,8 @@ __device__ __forceinline__ void store_row(T *p, const Row<T, V> &r) {
 __device__ __forceinline__ int64_t chunk_begin(int64_t g, int64_t n, int64_t G) { return g * n / G; }
 
 // LDS of the partial kernels: s_red[R][2c] (one row of 2c sums per row lane) | s_out[2c] | s_tmp[256] | s_shift[c]
+// (s_tmp is bn_reduce_lanes' scratch; between two calls of it the instance-norm partial kernels keep the 4 ints of their
+// chunk scans in s_tmp[0..3], so bn_reduce_lanes must not touch s_tmp before its leading barrier or after its trailing one)
 __host__ __device__ constexpr size_t bn_partial_lds_bytes(int c, int row_lanes) {
   return ((size_t)row_lanes * 2 * c + 2 * c + 256 + c) * sizeof(float);
 }

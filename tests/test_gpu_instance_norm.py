@@ -199,6 +199,91 @@ def test_row_order(device, host_layer):
     assert_close(shuf[1], z["grad_in"][perm.numpy()], what="grad_in vs fixture")
 
 
+def _inputs(coords, c, seed):
+    """the fixtures' construction: per-(instance, channel) offsets in [-4, 4] + 0.3 randn, dy in [-0.5, 0.5]"""
+    g = torch.Generator().manual_seed(seed)
+    n, nb = coords.shape[0], int(coords[:, 0].max()) + 1
+    offset = torch.rand(nb, c, generator=g) * 8 - 4
+    return dict(coords=coords.numpy(), feats=(offset[coords[:, 0].long()] + 0.3 * torch.randn(n, c, generator=g)).numpy(),
+                weight=(torch.rand(1, c, generator=g) + 0.5).numpy(), bias=(torch.rand(1, c, generator=g) - 0.5).numpy(),
+                grad_out=(torch.rand(n, c, generator=g) - 0.5).numpy())
+
+
+def test_an_instance_pruned_away(device, host_layer):
+    """MinkowskiPruning removes every row of instance 1 of 3: the pruned map still has 3 instances on its origin map, one
+    of them without rows (mean 0, rstd 1 / sqrt(eps), no contribution to any gradient).  Output and all four gradients
+    against the float64 formula on the surviving rows; the removed rows get a zero gradient."""
+    import minkowskiengine_amd as ME
+    z = _inputs(make_cloud(400, 12, 3, seed=21, batch=3), 8, 21)
+    coords, feats = torch.from_numpy(z["coords"]), torch.from_numpy(z["feats"])
+    keep = coords[:, 0] != 1
+    assert 0 < int(keep.sum()) < coords.shape[0] and set(coords[keep][:, 0].tolist()) == {0, 2}
+    layer = ME.MinkowskiInstanceNorm(8).to(device)
+    with torch.no_grad():
+        layer.weight.copy_(torch.from_numpy(z["weight"]))
+        layer.bias.copy_(torch.from_numpy(z["bias"]))
+    x = ME.SparseTensor(feats.to(device), coords.to(device), requires_grad=True)
+    pruned = ME.MinkowskiPruning()(x, keep.to(device))
+    assert torch.equal(pruned.C.cpu(), coords[keep])
+    y = layer(pruned)
+    # the statistics keep a row for the instance that lost its rows: the origin map comes from the unpruned map
+    assert x.coordinate_manager.origin_map_size() == 3
+    assert y.F.shape == (int(keep.sum()), 8)
+    dy = torch.from_numpy(z["grad_out"])[keep]
+    y.F.backward(dy.to(device))
+    want = _formula(feats[keep], coords[keep][:, 0], torch.from_numpy(z["weight"]), torch.from_numpy(z["bias"]), dy, 1e-8)
+    got = (y.F.detach(), x.F.grad[keep.to(device)], layer.weight.grad, layer.bias.grad)
+    for g_, w, what in zip(got, want, NAMES):
+        assert bool(torch.isfinite(g_).all()), what
+        assert_close(g_, w, what=what)
+    assert bool((x.F.grad[~keep.to(device)] == 0).all())
+
+
+def test_many_small_instances(device, host_layer):
+    """40 instances of 5 - 60 points, c = 12: tens of batch indices in every chunk of the statistics kernels"""
+    import minkowskiengine_amd as ME
+    sizes = torch.randint(5, 61, (40,), generator=torch.Generator().manual_seed(40)).tolist()
+    assert min(sizes) >= 5 and max(sizes) <= 60
+    parts = []
+    for b, k in enumerate(sizes):
+        pts = make_cloud(k, 8, 3, seed=100 + b)
+        pts[:, 0] = b
+        parts.append(pts)
+    z = _inputs(torch.cat(parts, 0), 12, 40)
+    got = _run(ME, device, z, torch.float32)
+    want = _formula(torch.from_numpy(z["feats"]), torch.from_numpy(z["coords"][:, 0]), torch.from_numpy(z["weight"]),
+                    torch.from_numpy(z["bias"]), torch.from_numpy(z["grad_out"]), 1e-8)
+    for g_, w, what in zip(got, want, NAMES):
+        assert_close(g_, w, what=what)
+
+
+def test_shuffled_rows_over_several_chunks(device, host_layer):
+    """3 x 3000 points, c = 32 (R = 32: 36 chunks of 256 rows), the rows randomly permuted before the tensor is built, so
+    that every chunk mixes the three instances: against the float64 formula and, row by row, against the unpermuted
+    run, as test_row_order"""
+    import minkowskiengine_amd as ME
+    z = _inputs(make_cloud(3000, 24, 3, seed=13, batch=3), 32, 13)
+    n = z["feats"].shape[0]
+    assert n == 9000
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(13))
+    assert len(set(z["coords"][perm.numpy()][:256, 0].tolist())) == 3
+    base = _run(ME, device, z, torch.float32)
+    shuf = _run(ME, device, z, torch.float32, perm=perm)
+    want = _formula(torch.from_numpy(z["feats"]), torch.from_numpy(z["coords"][:, 0]), torch.from_numpy(z["weight"]),
+                    torch.from_numpy(z["bias"]), torch.from_numpy(z["grad_out"]), 1e-8)
+    p = perm.numpy()
+    for i, what in enumerate(NAMES):
+        assert_close(base[i], want[i], what=what + " (sorted rows)")
+    assert_close(shuf[0], want[0][p], what="out vs formula")
+    assert_close(shuf[1], want[1][p], what="grad_in vs formula")
+    assert_close(shuf[2], want[2], what="grad_weight vs formula")
+    assert_close(shuf[3], want[3], what="grad_bias vs formula")
+    assert_close(shuf[0], base[0].cpu()[perm], what="out")
+    assert_close(shuf[1], base[1].cpu()[perm], what="grad_in")
+    assert_close(shuf[2], base[2], what="grad_weight")
+    assert_close(shuf[3], base[3], what="grad_bias")
+
+
 def _composed(ME, x, weight, bias, eps):
     """the reference's operator chain (MinkowskiNormalization.py:204-251, 387-393) on this package's existing
     GlobalPoolingForwardGPU / BroadcastForwardGPU"""

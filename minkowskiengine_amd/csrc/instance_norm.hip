@@ -51,9 +51,6 @@ __device__ __forceinline__ void load_f32(const float *__restrict__ p, float (&v)
   }
 }
 
-// max(v, 0) that keeps a NaN (fmaxf returns the other operand): non-finite rows must reach rstd, as in the float64 twins
-__device__ __forceinline__ float clamp_neg(float v) { return v < 0.f ? 0.f : v; }
-
 __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) v = min(v, __shfl_xor(v, off, 64));

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void k_bn_partial(const T *__restrict__ x, int
     const float a = s_out[ch], b = s_out[c + ch];
     const float m = cnt > 0.f ? a / cnt : 0.f;
     part_mean[(int64_t)blockIdx.x * c + ch] = s_shift[ch] + m;
-    part_m2[(int64_t)blockIdx.x * c + ch] = cnt > 0.f ? fmaxf(b - a * m, 0.f) : 0.f;
+    part_m2[(int64_t)blockIdx.x * c + ch] = cnt > 0.f ? clamp_neg(b - a * m) : 0.f;
   }
 }
 
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void k_bn_final(const float *__restrict__ part
   const float cn = sn;
   const float am = cn > 0.f ? sa / cn : 0.f;
   const float cm = shift + am;
-  const float cq = fmaxf(sb - sa * am, 0.f);
+  const float cq = clamp_neg(sb - sa * am);
   if (lane != 0) return;
   if constexpr (MODE == kBnToRecord) {
     mean_out[ch] = cm;
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256) void k_bn_apply(const T *__restrict__ x, int64
         } else {
           t[i].v[j] = fmaf(t[i].v[j], a[j], b[j]);
         }
-        if (relu) t[i].v[j] = fmaxf(t[i].v[j], 0.f);
+        if (relu) t[i].v[j] = relu_keep_nan(t[i].v[j]);
       }
       if (r < n) store_row<T, V>(y + r * c + p * V, t[i]);
     }

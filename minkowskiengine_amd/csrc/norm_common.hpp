@@ -43,6 +43,12 @@ __device__ __forceinline__ void store_row(T *p, const Row<T, V> &r) {
 // rows of chunk g: [g * n / G, (g + 1) * n / G)
 __device__ __forceinline__ int64_t chunk_begin(int64_t g, int64_t n, int64_t G) { return g * n / G; }
 
+// max(v, 0) that keeps a NaN (fmaxf returns the other operand): a non-finite row must reach M2 and rstd, as it does in
+// torch and in the float64 twins of the instance norm, not come out as a variance of 0
+__device__ __forceinline__ float clamp_neg(float v) { return v < 0.f ? 0.f : v; }
+// the fused ReLU of the apply kernels: fmaxf(v, 0) for every number (the same bits), NaN for a NaN as torch's relu
+__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
 // LDS of the partial kernels: s_red[R][2c] (one row of 2c sums per row lane) | s_out[2c] | s_tmp[256] | s_shift[c]
 // (s_tmp is bn_reduce_lanes' scratch; between two calls of it the instance-norm partial kernels keep the 4 ints of their
 // chunk scans in s_tmp[0..3], so bn_reduce_lanes must not touch s_tmp before its leading barrier or after its trailing one)

@@ -91,7 +91,9 @@ typedef struct me_region {
  *   1.14 (240) round 14: synchronised batch norm on the batch-norm kernels: a rank's (count, mean, M2) record, the merge of
  *              the ranks' records, backward sums without the apply, their sum in rank order and the apply with the global
  *              row count (me_bn_moments_floats, me_bn_local_moments, me_bn_stats_from_moments, me_bn_backward_sums,
- *              me_bn_backward_reduce, me_bn_backward_apply) */
+ *              me_bn_backward_reduce, me_bn_backward_apply)
+ *   1.15 (250)  round 15: group normalisation per (instance, group of channels): statistics, apply and backward
+ *              (me_gnorm_workspace_bytes, me_gnorm_stats, me_gnorm_apply, me_gnorm_backward and their _f64 twins) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1032,6 +1034,49 @@ int me_inorm_apply_f64(const double *x_dev, const int32_t *batch_row_dev, int64_
                        double *y_dev, void *stream);
 int me_inorm_backward_f64(const double *x_dev, const double *dy_dev, const int32_t *batch_row_dev, int64_t n,
                           int32_t n_batch, int32_t c, const double *mean_dev, const double *rstd_dev,
+                          const double *gamma_dev, double *dx_dev, double *grad_gamma_dev, double *grad_beta_dev,
+                          void *workspace_dev, int64_t workspace_bytes, void *stream);
+
+/* ---- group normalisation over feature rows (MinkowskiGroupNorm; torch.nn.GroupNorm's arithmetic applied to every
+ *      instance of a sparse tensor on its own.  Instance norm's pipeline plus a merge over the channels of a group;
+ *      csrc/group_norm.hip, ABI 1.15) ----
+ * Arguments as for instance normalisation, plus `groups`: c % groups == 0, group g holds the cg = c / groups channels
+ * [g * cg, (g + 1) * cg).  mean / rstd: fp32 [n_batch, groups]; gamma / beta / grad_gamma / grad_beta: fp32 [c].
+ *   me_gnorm_stats:    mean[b, g] and rstd[b, g] = 1 / sqrt(biased variance + eps) over the n_b * cg values of instance b
+ *                      in group g.  Per (chunk of rows, instance, channel) count / mean / M2 from shifted sums, merged over
+ *                      the chunks with Chan's formula, then over the cg channel records of the group in ascending channel
+ *                      order (equal counts: M2_g = sum M2_c + n_b * sum (mean_c - mean_g)^2).  E[x^2] - E[x]^2 is never
+ *                      formed.  Fixed order, bitwise reproducible.  An instance without rows: mean = 0,
+ *                      rstd = 1 / sqrt(eps).
+ *   me_gnorm_apply:    y[i, ch] = (x[i, ch] - mean[b_i, g_ch]) * rstd[b_i, g_ch] * gamma[ch] + beta[ch]
+ *                      (gamma / beta may be NULL: 1 / 0)
+ *   me_gnorm_backward: with xhat = (x - mean) * rstd and m = n_b * cg: t1[b, ch] = sum_{i in b} dy, t2[b, ch] =
+ *                      sum_{i in b} dy * xhat, grad_beta = sum_b t1[b], grad_gamma = sum_b t2[b] (ascending b),
+ *                      T1[b, g] = sum_{ch in g} gamma[ch] * t1[b, ch], T2 likewise (ascending ch),
+ *                      dx[i, ch] = rstd[b, g] * (gamma[ch] * dy[i, ch] - T1[b, g] / m - xhat[i, ch] * T2[b, g] / m).
+ *                      gamma may be NULL (1); dx, grad_gamma and grad_beta may each be NULL (skipped).
+ * Host-side argument errors (non-zero return, message in me_last_error, nothing launched): groups <= 0 or
+ * c % groups != 0; a workspace smaller than me_gnorm_workspace_bytes(n, n_batch, c, groups); more than 3225 channels
+ * (the 64 KiB of LDS of the partial kernels; fp32 / bf16 entry points only).  The _f64 entry points are the same formulae
+ * in plain double (parameters and statistics double as well): the yardstick of gradcheck, not a hot path. */
+int64_t me_gnorm_workspace_bytes(int64_t n, int32_t n_batch, int32_t c, int32_t groups);
+int me_gnorm_stats(const void *x_dev, int32_t is_bf16, const int32_t *batch_row_dev, int64_t n, int32_t n_batch,
+                   int32_t c, int32_t groups, float eps, float *mean_dev, float *rstd_dev, void *workspace_dev,
+                   int64_t workspace_bytes, void *stream);
+int me_gnorm_apply(const void *x_dev, int32_t is_bf16, const int32_t *batch_row_dev, int64_t n, int32_t n_batch,
+                   int32_t c, int32_t groups, const float *mean_dev, const float *rstd_dev, const float *gamma_dev,
+                   const float *beta_dev, void *y_dev, void *stream);
+int me_gnorm_backward(const void *x_dev, const void *dy_dev, int32_t is_bf16, const int32_t *batch_row_dev, int64_t n,
+                      int32_t n_batch, int32_t c, int32_t groups, const float *mean_dev, const float *rstd_dev,
+                      const float *gamma_dev, void *dx_dev, float *grad_gamma_dev, float *grad_beta_dev,
+                      void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_gnorm_stats_f64(const double *x_dev, const int32_t *batch_row_dev, int64_t n, int32_t n_batch, int32_t c,
+                       int32_t groups, double eps, double *mean_dev, double *rstd_dev, void *stream);
+int me_gnorm_apply_f64(const double *x_dev, const int32_t *batch_row_dev, int64_t n, int32_t n_batch, int32_t c,
+                       int32_t groups, const double *mean_dev, const double *rstd_dev, const double *gamma_dev,
+                       const double *beta_dev, double *y_dev, void *stream);
+int me_gnorm_backward_f64(const double *x_dev, const double *dy_dev, const int32_t *batch_row_dev, int64_t n,
+                          int32_t n_batch, int32_t c, int32_t groups, const double *mean_dev, const double *rstd_dev,
                           const double *gamma_dev, double *dx_dev, double *grad_gamma_dev, double *grad_beta_dev,
                           void *workspace_dev, int64_t workspace_bytes, void *stream);
 

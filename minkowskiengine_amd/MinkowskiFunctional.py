@@ -1,7 +1,8 @@
 """Functional twins of torch.nn.functional on sparse tensors and tensor fields (the reference's MinkowskiFunctional.py):
 the torch function runs on the feature matrix `.F`.  Activations and the other feature-to-feature functions return a
 tensor of the input's kind on the input's coordinates (a TensorField stays a TensorField); losses take a torch target
-and return what torch returns.  No kernels of their own."""
+and return what torch returns.  No kernels of their own, except `group_norm`: torch's needs one dense tensor per
+sample, so it runs MinkowskiGroupNorm's operators (normalization.py, csrc/group_norm.hip)."""
 import torch.nn.functional as F
 
 from .layers import _rewrap
@@ -43,4 +44,18 @@ for _name in _LOSSES:
     globals()[_name] = _loss(_name)
 del _name
 
-__all__ = list(_FEATURE_FUNCTIONS + _LOSSES)
+
+
+def group_norm(input, num_groups, weight=None, bias=None, eps=1e-5):
+    """torch.nn.functional.group_norm on every instance (batch index) of a sparse tensor on its own: the statistics of a
+    group run over the rows of the instance and the channels of the group.  weight / bias: (C,) tensors of the parameter
+    dtype (fp32 for fp32 and bf16 features, float64 for float64) or None."""
+    from .normalization import MinkowskiGroupNormFunction
+    from .sparse_tensor import SparseTensor
+    assert isinstance(input, SparseTensor)
+    out = MinkowskiGroupNormFunction.apply(input.F, num_groups, weight, bias, eps, input.coordinate_map_key, None,
+                                           input._manager)
+    return SparseTensor(out, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
+
+
+__all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm"]

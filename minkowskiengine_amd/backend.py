@@ -3286,6 +3286,89 @@ def InstanceNormBackwardGPU(in_feat, grad_out_feat, weight, mean, rstd, in_key, 
 
 
 # ------------------------------------------------------------------------------------------------
+# group normalisation (csrc/group_norm.hip): torch.nn.GroupNorm's arithmetic on every instance of a sparse tensor; the
+# reference has no such layer.  Instance norm's segmentation (_inorm_prepare) plus a merge over the channels of a group.
+# ------------------------------------------------------------------------------------------------
+def _gnorm_groups(num_groups, c):
+    groups = int(num_groups)
+    _check(groups > 0 and c % groups == 0, "the channel count", c, "must be a multiple of num_groups", num_groups)
+    return groups
+
+
+def GroupNormForwardGPU(in_feat, num_groups, weight, bias, eps, in_key, glob_key, manager):
+    """-> (out_feat, mean, rstd): out[i, c] = (x[i, c] - mean[b_i, g_c]) * rstd[b_i, g_c] * weight[c] + bias[c] with the
+    mean and the biased variance over the rows of every instance (batch index) and the C / num_groups channels of every
+    group, rstd = 1 / sqrt(var + eps); mean / rstd: [batch, num_groups] in the parameter dtype (fp32 for fp32 and bf16
+    features, float64 for float64).  weight / bias: C values or None."""
+    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
+    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
+    groups = _gnorm_groups(num_groups, c)
+    _inorm_check_vec("weight", weight, in_feat, c)
+    _inorm_check_vec("bias", bias, in_feat, c)
+    lib = _lib.load()
+    dev = in_feat.device
+    pd = _inorm_param_dtype(in_feat)
+    mean = torch.empty((n_batch, groups), dtype=pd, device=dev)
+    rstd = torch.empty((n_batch, groups), dtype=pd, device=dev)
+    out = torch.empty_like(in_feat)
+    with _on(dev):
+        if in_feat.dtype == torch.float64:
+            _lib.check(lib.me_gnorm_stats_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, groups, float(eps), _ptr(mean),
+                                              _ptr(rstd), _stream(dev)))
+            _lib.check(lib.me_gnorm_apply_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, groups, _ptr(mean), _ptr(rstd),
+                                              _ptr(weight), _ptr(bias), _ptr(out), _stream(dev)))
+        else:
+            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
+            ws = _workspace(int(lib.me_gnorm_workspace_bytes(n, n_batch, c, groups)), dev)
+            _timed("gnorm_forward", dev, lambda: (
+                _lib.check(lib.me_gnorm_stats(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, groups, float(eps),
+                                              _ptr(mean), _ptr(rstd), _ptr(ws), ws.numel(), _stream(dev))),
+                _lib.check(lib.me_gnorm_apply(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, groups, _ptr(mean),
+                                              _ptr(rstd), _ptr(weight), _ptr(bias), _ptr(out), _stream(dev)))))
+    return out, mean, rstd
+
+
+def GroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, mean, rstd, in_key, glob_key, manager,
+                         need_grad_in=True, need_grad_weight=True, need_grad_bias=True):
+    """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None) from the statistics of the forward pass; the
+    parameter gradients have the parameter dtype (fp32 for bf16 features)."""
+    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
+    if not grad_out_feat.is_contiguous():
+        grad_out_feat = grad_out_feat.contiguous()
+    _check_feat("grad_out_feat", grad_out_feat)
+    if grad_out_feat.dtype != in_feat.dtype:
+        grad_out_feat = grad_out_feat.to(in_feat.dtype)
+    _check(tuple(grad_out_feat.shape) == tuple(in_feat.shape), "grad_out_feat must have the shape of in_feat")
+    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
+    groups = _gnorm_groups(num_groups, c)
+    _inorm_check_vec("weight", weight, in_feat, c)
+    _check(mean is not None and rstd is not None, "group norm backward needs mean and rstd")
+    _inorm_check_vec("mean", mean, in_feat, n_batch * groups)
+    _inorm_check_vec("rstd", rstd, in_feat, n_batch * groups)
+    lib = _lib.load()
+    dev = in_feat.device
+    pd = _inorm_param_dtype(in_feat)
+    grad_in = torch.empty_like(in_feat) if need_grad_in else None
+    grad_weight = torch.empty(c, dtype=pd, device=dev) if need_grad_weight else None
+    grad_bias = torch.empty(c, dtype=pd, device=dev) if need_grad_bias else None
+    if n == 0:
+        return grad_in, (None if grad_weight is None else grad_weight.zero_()), \
+            (None if grad_bias is None else grad_bias.zero_())
+    ws = _workspace(int(lib.me_gnorm_workspace_bytes(n, n_batch, c, groups)), dev)
+    with _on(dev):
+        if in_feat.dtype == torch.float64:
+            _lib.check(lib.me_gnorm_backward_f64(_ptr(in_feat), _ptr(grad_out_feat), _ptr(rows), n, n_batch, c, groups,
+                                                 _ptr(mean), _ptr(rstd), _ptr(weight), _ptr(grad_in), _ptr(grad_weight),
+                                                 _ptr(grad_bias), _ptr(ws), ws.numel(), _stream(dev)))
+        else:
+            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
+            _timed("gnorm_backward", dev, lambda: _lib.check(lib.me_gnorm_backward(
+                _ptr(in_feat), _ptr(grad_out_feat), bf, _ptr(rows), n, n_batch, c, groups, _ptr(mean), _ptr(rstd),
+                _ptr(weight), _ptr(grad_in), _ptr(grad_weight), _ptr(grad_bias), _ptr(ws), ws.numel(), _stream(dev))))
+    return grad_in, grad_weight, grad_bias
+
+
+# ------------------------------------------------------------------------------------------------
 # pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu)
 # ------------------------------------------------------------------------------------------------
 def PruningForwardGPU(in_feat, keep, in_key, out_key, manager):

@@ -1394,7 +1394,7 @@ using namespace me;
 
 extern "C" {
 
-int me_version(void) { return 240; }   // 100 * major + 10 * minor: see the changelog in include/me_amd.h
+int me_version(void) { return 250; }   // 100 * major + 10 * minor: see the changelog in include/me_amd.h
 const char *me_last_error(void) { return g_last_error; }
 
 int64_t me_region_volume(const me_region *rg) {
@@ -2234,11 +2234,12 @@ void me_preload_conv_halo(void); void me_preload_coords(void); void me_preload_n
 void me_preload_f64(void); void me_preload_pool(void); void me_preload_conv_stem(void); void me_preload_conv_rowwise(void);
 void me_preload_conv_channelwise(void); void me_preload_field(void); void me_preload_instance_norm(void);
 void me_preload_dense(void); void me_preload_direct_pool(void); void me_preload_union_arith(void);
+void me_preload_group_norm(void);
 int me_preload(void) {
   me_preload_coords(); me_preload_conv(); me_preload_conv_bf16(); me_preload_conv_bf16_ws(); me_preload_conv_f32x3();
   me_preload_conv_halo(); me_preload_conv_stem(); me_preload_conv_rowwise(); me_preload_norm(); me_preload_pack(); me_preload_pool(); me_preload_f64();
   me_preload_conv_channelwise(); me_preload_field(); me_preload_instance_norm(); me_preload_dense(); me_preload_direct_pool();
-  me_preload_union_arith();
+  me_preload_union_arith(); me_preload_group_norm();
   ME_HIP(hipGetLastError());
   return 0;
 }

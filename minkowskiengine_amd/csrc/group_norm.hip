@@ -1,0 +1,570 @@
+// Group normalisation over the rows of a sparse tensor's feature matrix [n, c] for gfx950 (MI355X): every instance
+// (batch index) b and every group g of cg = c / groups consecutive channels is normalised with the mean and the biased
+// variance of its n_b * cg values.  torch.nn.GroupNorm needs one dense tensor per sample; the rows of a sparse tensor are
+// segmented by batch_row[i] with segments of different lengths, which is the segmentation instance_norm.hip solves
+// (segment_norm.hpp), plus a merge over the channels of a group:
+//
+//   statistics  k_gn_partial      seg_partial: count / mean / M2 of (chunk, instance, channel) from shifted sums — the
+//                                 row pass does not know about groups
+//               k_gn_chan_final   one wave per (instance, channel): the chunks merged with Chan's formula relative to one
+//                                 shift, in a fixed order -> the channel record (rows, mean_c, M2_c)
+//               k_gn_group_final  one thread per (instance, group): the cg channel records in ascending channel order.
+//                                 Their counts are equal, so mean_g is the mean of the mean_c (taken relative to the first
+//                                 one) and M2_g = sum M2_c + n_b * sum (mean_c - mean_g)^2 -> mean, rstd [n_batch, groups]
+//   forward     k_gn_apply        y = (x - mean[b, g]) * rstd[b, g] * gamma + beta.  A thread owns a 16-byte channel piece,
+//                                 which may straddle groups (cg = 3 with 4 floats, cg = 6 with 8 bf16): the group of every
+//                                 element of the piece is computed once, outside the row loop; the coefficients of an
+//                                 instance are re-read only when the batch index changes between two rows of the thread
+//   backward    k_gn_bwd_partial / k_gn_bwd_final   t1[b, c] = sum dy, t2[b, c] = sum dy * xhat (seg_bwd_partial with the
+//                                 group's mean / rstd)
+//               k_gn_bwd_params   grad_beta = sum_b t1, grad_gamma = sum_b t2 (ascending b)
+//               k_gn_bwd_group    T1[b, g] = sum_{c in g} gamma[c] * t1[b, c], T2 likewise (ascending c)
+//               k_gn_bwd_apply    dx = rstd * (gamma * dy - T1 / m - xhat * T2 / m), m = n_b * cg
+// x is read twice and y written once forward; x and dy are read twice and dx written once backward, as instance norm.
+// No atomics on values, every sum in a fixed order: bitwise reproducible.  T = float or __bf16 rows; statistics and
+// parameters fp32.  The float64 twins at the end are the gradcheck yardstick (plain double, one thread per output).
+#include "segment_norm.hpp"
+
+namespace me {
+
+template <typename T, int V>
+__global__ __launch_bounds__(256) void k_gn_partial(const T *__restrict__ x, const int32_t *__restrict__ batch_row,
+                                                   int64_t n, int c, int chunks, int n_batch,
+                                                   float *__restrict__ part_mean, float *__restrict__ part_m2,
+                                                   float *__restrict__ part_cnt) {
+  extern __shared__ float s_red[];  // in_partial_lds_bytes
+  seg_partial<T, V>(s_red, x, batch_row, n, c, chunks, n_batch, part_mean, part_m2, part_cnt);
+}
+
+// One wave per (instance b, channel): the channel record cmean / cm2 [n_batch][c] and rows[b] (0 / 0 / 0 for an instance
+// without rows on this map, so that k_gn_group_final reads only words written here)
+__global__ __launch_bounds__(256) void k_gn_chan_final(const float *__restrict__ part_mean,
+                                                      const float *__restrict__ part_m2,
+                                                      const float *__restrict__ part_cnt, int chunks, int n_batch, int c,
+                                                      float *__restrict__ cmean, float *__restrict__ cm2,
+                                                      float *__restrict__ rows) {
+  const int lane = threadIdx.x & 63;
+  const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // (b, channel)
+  if (idx >= (int64_t)n_batch * c) return;  // whole wave
+  const int b = (int)(idx / c), ch = (int)(idx % c);
+  SegMerge m;
+  const bool have = seg_merge_chunks(part_mean, part_m2, part_cnt, chunks, n_batch, c, b, ch, m);   // uniform
+  if (lane != 0) return;
+  float mean = 0.f, m2 = 0.f, cnt = 0.f;
+  if (have) {
+    const float am = m.sa / m.sn;
+    mean = m.shift + am;
+    m2 = clamp_neg(m.sb - m.sa * am);
+    cnt = m.sn;
+  }
+  cmean[idx] = mean;
+  cm2[idx] = m2;
+  if (ch == 0) rows[b] = cnt;
+}
+
+// One thread per (instance b, group g): the cg channel records of the group, ascending.  An instance without rows:
+// mean = 0, rstd = 1 / sqrt(eps).
+__global__ __launch_bounds__(256) void k_gn_group_final(const float *__restrict__ cmean, const float *__restrict__ cm2,
+                                                       const float *__restrict__ rows, int n_batch, int c, int groups,
+                                                       float eps, float *__restrict__ mean_out,
+                                                       float *__restrict__ rstd_out) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // (b, g)
+  if (idx >= n_batch * groups) return;
+  const int b = idx / groups, g = idx % groups, cg = c / groups;
+  const float nb = rows[b];
+  if (!(nb > 0.f)) {
+    mean_out[idx] = 0.f;
+    rstd_out[idx] = 1.f / sqrtf(eps);
+    return;
+  }
+  const float *pm = cmean + (int64_t)b * c + g * cg, *pq = cm2 + (int64_t)b * c + g * cg;
+  const float m0 = pm[0];
+  float s = 0.f;
+  for (int k = 0; k < cg; ++k) s += pm[k] - m0;
+  const float mg = m0 + s / (float)cg;
+  float q1 = 0.f, q2 = 0.f;
+  for (int k = 0; k < cg; ++k) {
+    const float d = pm[k] - mg;
+    q1 += pq[k];
+    q2 = fmaf(d, d, q2);
+  }
+  const float var = clamp_neg(fmaf(nb, q2, q1)) / (nb * (float)cg);
+  mean_out[idx] = mg;
+  rstd_out[idx] = 1.f / sqrtf(var + eps);
+}
+
+// the group of each of the V channels from ch0: fixed for a thread's piece, computed outside its row loop
+template <int V>
+__device__ __forceinline__ void gn_piece_groups(int ch0, int cg, int (&grp)[V]) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) grp[j] = (ch0 + j) / cg;
+}
+
+// y = (x - mean[b, g]) * (rstd[b, g] * gamma) + beta, b = batch_row[row] clamped (gamma / beta may be NULL: 1 / 0).
+// k_in_apply's layout: all row loads of a thread first, unconditionally (rows clamped to the matrix), only the stores
+// predicated.  mean / rstd are read element by element ([n_batch, groups] floats, L2-resident, no alignment asked of them).
+template <typename T, int V>
+__global__ __launch_bounds__(256) void k_gn_apply(const T *__restrict__ x, const int32_t *__restrict__ batch_row,
+                                                 int64_t n, int c, int n_batch, int groups,
+                                                 const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                 const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                 T *__restrict__ y) {
+  const int P = c / V;
+  const int W = min(P, (int)blockDim.x);
+  const int R = max(1, (int)blockDim.x / P);
+  const int rl = (int)threadIdx.x / W;
+  const int cg = c / groups;
+  const int64_t r0 = (int64_t)blockIdx.x * R * kBnRowsPerThread;
+  if (rl >= R) return;
+  for (int p = (int)threadIdx.x % W; p < P; p += W) {
+    Row<T, V> t[kBnRowsPerThread];
+    int bi[kBnRowsPerThread];
+#pragma unroll
+    for (int i = 0; i < kBnRowsPerThread; ++i) {
+      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
+      t[i] = load_row<T, V>(x + r * c + p * V);
+      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
+    }
+    float ga[V], be[V], a[V], mu[V];
+    int grp[V];
+    load_affine<V>(gamma, beta, p * V, ga, be);
+    gn_piece_groups<V>(p * V, cg, grp);
+#pragma unroll
+    for (int i = 0; i < kBnRowsPerThread; ++i) {
+      const int64_t r = r0 + rl + (int64_t)i * R;
+      if (i == 0 || bi[i] != bi[i - 1]) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const int o = bi[i] * groups + grp[j];
+          mu[j] = mean[o];
+          a[j] = rstd[o] * ga[j];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < V; ++j) t[i].v[j] = fmaf(t[i].v[j] - mu[j], a[j], be[j]);
+      if (r < n) store_row<T, V>(y + r * c + p * V, t[i]);
+    }
+  }
+}
+
+// mean / rstd [n_batch][groups] of instance b for the V channels from ch0
+struct GnCoef {
+  const float *mean, *rstd;
+  int groups, cg;
+  template <int V>
+  __device__ __forceinline__ void operator()(int b, int ch0, float (&m)[V], float (&rs)[V]) const {
+    int grp[V];
+    gn_piece_groups<V>(ch0, cg, grp);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      m[j] = mean[b * groups + grp[j]];
+      rs[j] = rstd[b * groups + grp[j]];
+    }
+  }
+};
+
+// per (chunk, instance, channel): sum dy and sum dy * xhat with xhat = (x - mean[b, g]) * rstd[b, g]
+template <typename T, int V>
+__global__ __launch_bounds__(256) void k_gn_bwd_partial(const T *__restrict__ x, const T *__restrict__ dy,
+                                                       const int32_t *__restrict__ batch_row, int64_t n, int c,
+                                                       int chunks, int n_batch, int groups,
+                                                       const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                       float *__restrict__ part_dy, float *__restrict__ part_dyx,
+                                                       float *__restrict__ part_cnt) {
+  extern __shared__ float s_red[];  // in_partial_lds_bytes
+  seg_bwd_partial<T, V>(s_red, x, dy, batch_row, n, c, chunks, n_batch, GnCoef{mean, rstd, groups, c / groups}, part_dy,
+                        part_dyx, part_cnt);
+}
+
+// t1 = sum dy, t2 = sum dy * xhat per (instance, channel) and rows[b]: one wave each over the chunks, a fixed order
+__global__ __launch_bounds__(256) void k_gn_bwd_final(const float *__restrict__ part_dy,
+                                                     const float *__restrict__ part_dyx,
+                                                     const float *__restrict__ part_cnt, int chunks, int n_batch, int c,
+                                                     float *__restrict__ t1, float *__restrict__ t2,
+                                                     float *__restrict__ rows) {
+  seg_bwd_final(part_dy, part_dyx, part_cnt, chunks, n_batch, c, t1, t2, rows);
+}
+
+// grad_beta = sum over the instances (ascending) of t1, grad_gamma = of t2; either may be NULL
+template <typename F>
+__global__ __launch_bounds__(256) void k_gn_bwd_params(const F *__restrict__ t1, const F *__restrict__ t2, int n_batch,
+                                                      int c, F *__restrict__ grad_gamma, F *__restrict__ grad_beta) {
+  seg_bwd_params<F>(t1, t2, n_batch, c, grad_gamma, grad_beta);
+}
+
+// One thread per (instance b, group g): T1 = sum_{c in g} gamma[c] * t1[b, c], T2 = the same of t2, ascending c
+// (gamma may be NULL: 1)
+template <typename F>
+__global__ __launch_bounds__(256) void k_gn_bwd_group(const F *__restrict__ t1, const F *__restrict__ t2,
+                                                     const F *__restrict__ gamma, int n_batch, int c, int groups,
+                                                     F *__restrict__ g1, F *__restrict__ g2) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // (b, g)
+  if (idx >= n_batch * groups) return;
+  const int b = idx / groups, g = idx % groups, cg = c / groups;
+  F a = 0, q = 0;
+  for (int k = 0; k < cg; ++k) {
+    const int ch = g * cg + k;
+    const F w = gamma != nullptr ? gamma[ch] : (F)1;
+    a = fma(w, t1[(int64_t)b * c + ch], a);
+    q = fma(w, t2[(int64_t)b * c + ch], q);
+  }
+  g1[idx] = a;
+  g2[idx] = q;
+}
+
+// a * b rounded on its own, never contracted into an fma with a neighbouring add
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// dx = A * ((gamma * dy - k1) - (x - mean[b, g]) * k2) with A = rstd[b, g], k1 = T1[b, g] / m, k2 = T2[b, g] / m * A,
+// m = n_b * cg (layout and coefficient reuse of k_gn_apply).  gamma * dy is rounded on its own: with one value per
+// (instance, group) it equals k1 bit for bit and dx is exactly 0, which a contraction into one fma would lose.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void k_gn_bwd_apply(const T *__restrict__ x, const T *__restrict__ dy,
+                                                     const int32_t *__restrict__ batch_row, int64_t n, int c,
+                                                     int n_batch, int groups, const float *__restrict__ mean,
+                                                     const float *__restrict__ rstd, const float *__restrict__ gamma,
+                                                     const float *__restrict__ g1, const float *__restrict__ g2,
+                                                     const float *__restrict__ rows, T *__restrict__ dx) {
+  const int P = c / V;
+  const int W = min(P, (int)blockDim.x);
+  const int R = max(1, (int)blockDim.x / P);
+  const int rl = (int)threadIdx.x / W;
+  const int cg = c / groups;
+  constexpr int RB = kBnRowsPerThread;
+  const int64_t r0 = (int64_t)blockIdx.x * R * RB;
+  if (rl >= R) return;
+  for (int p = (int)threadIdx.x % W; p < P; p += W) {
+    Row<T, V> tx[RB], tg[RB];
+    int bi[RB];
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
+      tx[i] = load_row<T, V>(x + r * c + p * V);
+      tg[i] = load_row<T, V>(dy + r * c + p * V);
+      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
+    }
+    float ga[V], unused[V], A[V], k1[V], k2[V], mu[V];
+    int grp[V];
+    load_affine<V>(gamma, nullptr, p * V, ga, unused);
+    gn_piece_groups<V>(p * V, cg, grp);
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+      const int64_t r = r0 + rl + (int64_t)i * R;
+      if (i == 0 || bi[i] != bi[i - 1]) {
+        const float inv_m = 1.f / fmaxf(rows[bi[i]] * (float)cg, 1.f);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const int o = bi[i] * groups + grp[j];
+          mu[j] = mean[o];
+          A[j] = rstd[o];
+          k1[j] = g1[o] * inv_m;
+          k2[j] = g2[o] * inv_m * A[j];
+        }
+      }
+      Row<T, V> out;
+#pragma unroll
+      for (int j = 0; j < V; ++j)
+        out.v[j] = A[j] * ((mul_rounded(ga[j], tg[i].v[j]) - k1[j]) - (tx[i].v[j] - mu[j]) * k2[j]);
+      if (r < n) store_row<T, V>(dx + r * c + p * V, out);
+    }
+  }
+}
+
+// ---- float64: the same formulae in plain double, one thread per output (gradcheck yardstick, not a hot path) ----------
+// per (instance, group): mean, then M2 about it, rows ascending and the channels of the group ascending within a row
+__global__ __launch_bounds__(256) void k_gn_stats_f64(const double *__restrict__ x,
+                                                     const int32_t *__restrict__ batch_row, int64_t n, int n_batch,
+                                                     int c, int groups, double eps, double *__restrict__ mean,
+                                                     double *__restrict__ rstd) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_batch * groups) return;
+  const int b = idx / groups, g = idx % groups, cg = c / groups;
+  double s = 0.0, cnt = 0.0;
+  for (int64_t r = 0; r < n; ++r) {
+    if (batch_row[r] != b) continue;
+    for (int k = 0; k < cg; ++k) s += x[r * c + g * cg + k];
+    cnt += (double)cg;
+  }
+  const double m = cnt > 0.0 ? s / cnt : 0.0;
+  double q = 0.0;
+  for (int64_t r = 0; r < n; ++r) {
+    if (batch_row[r] != b) continue;
+    for (int k = 0; k < cg; ++k) {
+      const double d = x[r * c + g * cg + k] - m;
+      q = fma(d, d, q);
+    }
+  }
+  mean[idx] = m;
+  rstd[idx] = 1.0 / sqrt((cnt > 0.0 ? q / cnt : 0.0) + eps);
+}
+
+__global__ __launch_bounds__(256) void k_gn_apply_f64(const double *__restrict__ x,
+                                                     const int32_t *__restrict__ batch_row, int64_t n, int c,
+                                                     int n_batch, int groups, const double *__restrict__ mean,
+                                                     const double *__restrict__ rstd, const double *__restrict__ gamma,
+                                                     const double *__restrict__ beta, double *__restrict__ y) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * c) return;
+  const int ch = (int)(idx % c);
+  const int o = min(max(batch_row[idx / c], 0), n_batch - 1) * groups + ch / (c / groups);
+  const double v = (x[idx] - mean[o]) * rstd[o];
+  y[idx] = fma(v, gamma ? gamma[ch] : 1.0, beta ? beta[ch] : 0.0);
+}
+
+// t1[b, c] = sum dy, t2[b, c] = sum dy * xhat, rows[b]
+__global__ __launch_bounds__(256) void k_gn_bwd_sums_f64(const double *__restrict__ x, const double *__restrict__ dy,
+                                                        const int32_t *__restrict__ batch_row, int64_t n, int n_batch,
+                                                        int c, int groups, const double *__restrict__ mean,
+                                                        const double *__restrict__ rstd, double *__restrict__ t1,
+                                                        double *__restrict__ t2, double *__restrict__ rows) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)n_batch * c) return;
+  const int b = (int)(idx / c), ch = (int)(idx % c);
+  const double m = mean[b * groups + ch / (c / groups)], rs = rstd[b * groups + ch / (c / groups)];
+  double a = 0.0, q = 0.0, cnt = 0.0;
+  for (int64_t r = 0; r < n; ++r) {
+    if (batch_row[r] != b) continue;
+    const double g = dy[r * c + ch];
+    a += g;
+    q = fma(g, (x[r * c + ch] - m) * rs, q);
+    cnt += 1.0;
+  }
+  t1[idx] = a;
+  t2[idx] = q;
+  if (ch == 0) rows[b] = cnt;
+}
+
+__global__ __launch_bounds__(256) void k_gn_bwd_apply_f64(const double *__restrict__ x, const double *__restrict__ dy,
+                                                         const int32_t *__restrict__ batch_row, int64_t n, int c,
+                                                         int n_batch, int groups, const double *__restrict__ mean,
+                                                         const double *__restrict__ rstd,
+                                                         const double *__restrict__ gamma, const double *__restrict__ g1,
+                                                         const double *__restrict__ g2, const double *__restrict__ rows,
+                                                         double *__restrict__ dx) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * c) return;
+  const int ch = (int)(idx % c);
+  const int b = min(max(batch_row[idx / c], 0), n_batch - 1);
+  const int o = b * groups + ch / (c / groups);
+  const double inv_m = 1.0 / fmax(rows[b] * (double)(c / groups), 1.0);
+  const double xh = (x[idx] - mean[o]) * rstd[o];
+  dx[idx] = rstd[o] * ((gamma ? gamma[ch] : 1.0) * dy[idx] - g1[o] * inv_m - xh * g2[o] * inv_m);
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+// workspace: in_ws_layout_f32 | g1 | g2 [n_batch][groups] floats.  The statistics keep the channel records in t1 / t2.
+// float64: t1 | t2 [n_batch][c] | rows [n_batch] | g1 | g2 [n_batch][groups] doubles.  Every piece 256-byte aligned.
+struct GnWs {
+  InWs in;
+  float *g1, *g2;
+};
+struct GnWs64 {
+  double *t1, *t2, *rows, *g1, *g2;
+};
+static int64_t gn_ws_layout(int64_t n, int n_batch, int c, int groups, char *base, GnWs *w, GnWs64 *w64) {
+  const int64_t in32 = in_ws_layout_f32(n, n_batch, c, base, w != nullptr ? &w->in : nullptr);
+  const int64_t gs = align_up((int64_t)n_batch * groups * 4, 256);
+  if (w != nullptr) {
+    w->g1 = reinterpret_cast<float *>(base + in32);
+    w->g2 = reinterpret_cast<float *>(base + in32 + gs);
+  }
+  const int64_t t = align_up((int64_t)n_batch * c * 8, 256), rw = align_up((int64_t)n_batch * 8, 256);
+  const int64_t gs64 = align_up((int64_t)n_batch * groups * 8, 256);
+  if (w64 != nullptr) {
+    w64->t1 = reinterpret_cast<double *>(base);
+    w64->t2 = reinterpret_cast<double *>(base + t);
+    w64->rows = reinterpret_cast<double *>(base + 2 * t);
+    w64->g1 = reinterpret_cast<double *>(base + 2 * t + rw);
+    w64->g2 = reinterpret_cast<double *>(base + 2 * t + rw + gs64);
+  }
+  const int64_t f32 = in32 + 2 * gs, f64 = 2 * t + rw + 2 * gs64;
+  return f32 > f64 ? f32 : f64;
+}
+
+template <typename T>
+static int gn_stats(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups, float eps,
+                    float *mean, float *rstd, const GnWs &w, hipStream_t stream) {
+  const int v = in_piece<T>(c, {x});
+  const int P = c / v;
+  const int R = P >= 256 ? 1 : 256 / P;
+  const int chunks = bn_chunks(n, R, kBnRowsPerThread);
+  const size_t lds = in_partial_lds_bytes(c, R);
+  ME_CHECK(lds <= 64 * 1024, "channel count too large for the group-norm kernels");
+  ME_HIP(hipMemsetAsync(w.in.cnt, 0, (size_t)chunks * n_batch * 4, stream));
+  if (n > 0)
+    ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gn_partial<T, V>), dim3(chunks), dim3(256), lds, stream, x, batch_row, n,
+                                              c, chunks, n_batch, w.in.pa, w.in.pb, w.in.cnt));
+  hipLaunchKernelGGL(k_gn_chan_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.in.pa,
+                     w.in.pb, w.in.cnt, chunks, n_batch, c, w.in.t1, w.in.t2, w.in.rows);
+  hipLaunchKernelGGL(k_gn_group_final, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0, stream,
+                     w.in.t1, w.in.t2, w.in.rows, n_batch, c, groups, eps, mean, rstd);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
+static int gn_apply(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups, const float *mean,
+                    const float *rstd, const float *gamma, const float *beta, T *y, hipStream_t stream) {
+  const int v = in_piece<T>(c, {x, y});
+  const int P = c / v;
+  const dim3 grid((unsigned)ceil_div(n, (int64_t)(P >= 256 ? 1 : 256 / P) * kBnRowsPerThread));
+  ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gn_apply<T, V>), grid, dim3(256), 0, stream, x, batch_row, n, c, n_batch,
+                                            groups, mean, rstd, gamma, beta, y));
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
+static int gn_backward(const T *x, const T *dy, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups,
+                       const float *mean, const float *rstd, const float *gamma, T *dx, float *grad_gamma,
+                       float *grad_beta, const GnWs &w, hipStream_t stream) {
+  const int v = in_piece<T>(c, {x, dy, dx});
+  const int P = c / v;
+  const int R = P >= 256 ? 1 : 256 / P;
+  const int chunks = bn_chunks(n, R, kBnRowsPerThread / 2);
+  const size_t lds = in_partial_lds_bytes(c, R);
+  ME_CHECK(lds <= 64 * 1024, "channel count too large for the group-norm kernels");
+  ME_HIP(hipMemsetAsync(w.in.cnt, 0, (size_t)chunks * n_batch * 4, stream));
+  ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gn_bwd_partial<T, V>), dim3(chunks), dim3(256), lds, stream, x, dy,
+                                            batch_row, n, c, chunks, n_batch, groups, mean, rstd, w.in.pa, w.in.pb,
+                                            w.in.cnt));
+  hipLaunchKernelGGL(k_gn_bwd_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.in.pa,
+                     w.in.pb, w.in.cnt, chunks, n_batch, c, w.in.t1, w.in.t2, w.in.rows);
+  if (grad_gamma != nullptr || grad_beta != nullptr)
+    hipLaunchKernelGGL(k_gn_bwd_params<float>, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.in.t1, w.in.t2,
+                       n_batch, c, grad_gamma, grad_beta);
+  if (dx != nullptr) {
+    hipLaunchKernelGGL(k_gn_bwd_group<float>, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0,
+                       stream, w.in.t1, w.in.t2, gamma, n_batch, c, groups, w.g1, w.g2);
+    const dim3 grid((unsigned)ceil_div(n, (int64_t)R * kBnRowsPerThread));
+    ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gn_bwd_apply<T, V>), grid, dim3(256), 0, stream, x, dy, batch_row, n, c,
+                                              n_batch, groups, mean, rstd, gamma, w.g1, w.g2, w.in.rows, dx));
+  }
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace me
+
+using namespace me;
+
+// host-only argument checks: nothing is launched when one fails
+#define ME_GN_CHECK_ARGS()                                                                                       \
+  ME_CHECK(n >= 0 && c > 0 && n_batch > 0, "group norm needs a channel count and at least one instance");        \
+  ME_CHECK(groups > 0 && c % groups == 0, "group norm: the channel count must be a multiple of the groups");     \
+  ME_CHECK(n < (1ll << 40) && (int64_t)n_batch * c < (1ll << 31), "group norm: matrix or statistics too large")
+// the partial kernels' LDS with one row lane (5 c + 256 floats): rows of up to 3225 channels
+#define ME_GN_CHECK_WIDTH() \
+  ME_CHECK(in_partial_lds_bytes(c, 1) <= 64 * 1024, "channel count too large for the group-norm kernels")
+
+extern "C" {
+
+int64_t me_gnorm_workspace_bytes(int64_t n, int32_t n_batch, int32_t c, int32_t groups) {
+  if (n_batch <= 0 || c <= 0 || groups <= 0) return 0;
+  return gn_ws_layout(n < 0 ? 0 : n, n_batch, c, groups, nullptr, nullptr, nullptr);
+}
+
+int me_gnorm_stats(const void *x, int32_t is_bf16, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c,
+                   int32_t groups, float eps, float *mean, float *rstd, void *workspace, int64_t workspace_bytes,
+                   void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_GN_CHECK_ARGS();
+  ME_GN_CHECK_WIDTH();
+  ME_CHECK(workspace_bytes >= me_gnorm_workspace_bytes(n, n_batch, c, groups), "workspace too small");
+  GnWs w;
+  gn_ws_layout(n, n_batch, c, groups, reinterpret_cast<char *>(workspace), &w, nullptr);
+  if (is_bf16)
+    return gn_stats<__bf16>(reinterpret_cast<const __bf16 *>(x), batch_row, n, n_batch, c, groups, eps, mean, rstd, w,
+                            stream);
+  return gn_stats<float>(reinterpret_cast<const float *>(x), batch_row, n, n_batch, c, groups, eps, mean, rstd, w, stream);
+}
+
+int me_gnorm_apply(const void *x, int32_t is_bf16, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c,
+                   int32_t groups, const float *mean, const float *rstd, const float *gamma, const float *beta, void *y,
+                   void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_GN_CHECK_ARGS();
+  ME_GN_CHECK_WIDTH();
+  if (n == 0) return 0;
+  if (is_bf16)
+    return gn_apply<__bf16>(reinterpret_cast<const __bf16 *>(x), batch_row, n, n_batch, c, groups, mean, rstd, gamma,
+                            beta, reinterpret_cast<__bf16 *>(y), stream);
+  return gn_apply<float>(reinterpret_cast<const float *>(x), batch_row, n, n_batch, c, groups, mean, rstd, gamma, beta,
+                         reinterpret_cast<float *>(y), stream);
+}
+
+int me_gnorm_backward(const void *x, const void *dy, int32_t is_bf16, const int32_t *batch_row, int64_t n,
+                      int32_t n_batch, int32_t c, int32_t groups, const float *mean, const float *rstd,
+                      const float *gamma, void *dx, float *grad_gamma, float *grad_beta, void *workspace,
+                      int64_t workspace_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_GN_CHECK_ARGS();
+  ME_GN_CHECK_WIDTH();
+  ME_CHECK(n > 0, "group norm backward needs at least one row");
+  ME_CHECK(workspace_bytes >= me_gnorm_workspace_bytes(n, n_batch, c, groups), "workspace too small");
+  GnWs w;
+  gn_ws_layout(n, n_batch, c, groups, reinterpret_cast<char *>(workspace), &w, nullptr);
+  if (is_bf16)
+    return gn_backward<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), batch_row, n,
+                               n_batch, c, groups, mean, rstd, gamma, reinterpret_cast<__bf16 *>(dx), grad_gamma,
+                               grad_beta, w, stream);
+  return gn_backward<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), batch_row, n,
+                            n_batch, c, groups, mean, rstd, gamma, reinterpret_cast<float *>(dx), grad_gamma, grad_beta,
+                            w, stream);
+}
+
+int me_gnorm_stats_f64(const double *x, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c, int32_t groups,
+                       double eps, double *mean, double *rstd, void *stream_) {
+  ME_GN_CHECK_ARGS();
+  hipLaunchKernelGGL(k_gn_stats_f64, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0,
+                     (hipStream_t)stream_, x, batch_row, n, n_batch, c, groups, eps, mean, rstd);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+int me_gnorm_apply_f64(const double *x, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c, int32_t groups,
+                       const double *mean, const double *rstd, const double *gamma, const double *beta, double *y,
+                       void *stream_) {
+  ME_GN_CHECK_ARGS();
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_gn_apply_f64, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0, (hipStream_t)stream_, x,
+                     batch_row, n, c, n_batch, groups, mean, rstd, gamma, beta, y);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+int me_gnorm_backward_f64(const double *x, const double *dy, const int32_t *batch_row, int64_t n, int32_t n_batch,
+                          int32_t c, int32_t groups, const double *mean, const double *rstd, const double *gamma,
+                          double *dx, double *grad_gamma, double *grad_beta, void *workspace, int64_t workspace_bytes,
+                          void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_GN_CHECK_ARGS();
+  ME_CHECK(workspace_bytes >= me_gnorm_workspace_bytes(n, n_batch, c, groups), "workspace too small");
+  GnWs64 w;
+  gn_ws_layout(n, n_batch, c, groups, reinterpret_cast<char *>(workspace), nullptr, &w);
+  hipLaunchKernelGGL(k_gn_bwd_sums_f64, dim3((unsigned)ceil_div((int64_t)n_batch * c, 256)), dim3(256), 0, stream, x, dy,
+                     batch_row, n, n_batch, c, groups, mean, rstd, w.t1, w.t2, w.rows);
+  if (grad_gamma != nullptr || grad_beta != nullptr)
+    hipLaunchKernelGGL(k_gn_bwd_params<double>, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.t1, w.t2,
+                       n_batch, c, grad_gamma, grad_beta);
+  if (dx != nullptr && n > 0) {
+    hipLaunchKernelGGL(k_gn_bwd_group<double>, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0,
+                       stream, w.t1, w.t2, gamma, n_batch, c, groups, w.g1, w.g2);
+    hipLaunchKernelGGL(k_gn_bwd_apply_f64, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0, stream, x, dy, batch_row, n,
+                       c, n_batch, groups, mean, rstd, gamma, w.g1, w.g2, w.rows, dx);
+  }
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // extern "C"
+
+// code-object preload (me_preload, coords.hip): resolving one kernel of this translation unit makes the runtime load the
+// unit's whole code object now instead of at the first launch from it
+extern "C" __attribute__((visibility("hidden"))) void me_preload_group_norm(void) {
+  hipFuncAttributes attr;
+  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&me::k_gn_chan_final));
+}

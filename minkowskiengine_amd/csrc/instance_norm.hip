@@ -20,194 +20,22 @@
 //               k_in_bwd_apply    dx = gamma * rstd[b] * (dy - t1[b] / n_b - xhat * t2[b] / n_b)
 // No atomics on values, every sum in a fixed order: bitwise reproducible.  T = float or __bf16 rows; statistics and
 // parameters fp32.  The float64 twins at the end are the gradcheck yardstick (plain double, one thread per output).
-#include "norm_common.hpp"
-
-#include <limits.h>
+#include "segment_norm.hpp"
 
 namespace me {
 
-// LDS of the partial kernels: bn_partial_lds_bytes.  The 4 ints of the range and per-instance scans of a chunk live in
-// s_tmp: bn_reduce_lanes alone writes s_tmp, after its leading barrier (every scan result has been read by then), and has
-// read it for the last time before its trailing barrier (the next scan starts after that).  5 c + 256 floats with one row
-// lane: rows of up to 3225 channels fit into 64 KiB.
-__host__ __device__ constexpr size_t in_partial_lds_bytes(int c, int row_lanes) {
-  return bn_partial_lds_bytes(c, row_lanes);
-}
-
-template <int V>
-__device__ __forceinline__ void load_f32(const float *__restrict__ p, float (&v)[V]) {
-  if constexpr (V % 4 == 0) {
-#pragma unroll
-    for (int q = 0; q < V / 4; ++q) {
-      const f32x4 t = *reinterpret_cast<const f32x4 *>(p + 4 * q);
-      v[4 * q + 0] = t.x;
-      v[4 * q + 1] = t.y;
-      v[4 * q + 2] = t.z;
-      v[4 * q + 3] = t.w;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j) v[j] = p[j];
-  }
-}
-
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) v = min(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) v = max(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// smallest and largest batch index among rows [r0, r1), clamped to [0, n_batch) (an index outside it matches no instance
-// and is never used as an address).  s_i: 2 ints of LDS.  Integer min / max: the order of the LDS atomics does not matter.
-__device__ __forceinline__ void in_scan_range(const int32_t *__restrict__ batch_row, int64_t r0, int64_t r1, int n_batch,
-                                              int *s_i, int &bmin, int &bmax) {
-  if (threadIdx.x == 0) {
-    s_i[0] = INT_MAX;
-    s_i[1] = -1;
-  }
-  __syncthreads();
-  int lo = INT_MAX, hi = -1;
-  for (int64_t r = r0 + threadIdx.x; r < r1; r += blockDim.x) {
-    const int b = batch_row[r];
-    lo = min(lo, b);
-    hi = max(hi, b);
-  }
-  lo = wave_min(lo);
-  hi = wave_max(hi);
-  if ((threadIdx.x & 63) == 0) {
-    atomicMin(&s_i[0], lo);
-    atomicMax(&s_i[1], hi);
-  }
-  __syncthreads();
-  bmin = max(s_i[0], 0);
-  bmax = min(s_i[1], n_batch - 1);
-}
-
-// first row (relative to r0) and number of rows of batch index b among rows [r0, r1).  s_i: 2 ints of LDS; the caller
-// synchronises before it calls this again.
-__device__ __forceinline__ void in_scan_instance(const int32_t *__restrict__ batch_row, int64_t r0, int64_t r1, int b,
-                                                 int *s_i, int &first, int &count) {
-  if (threadIdx.x == 0) {
-    s_i[0] = INT_MAX;
-    s_i[1] = 0;
-  }
-  __syncthreads();
-  int f = INT_MAX, k = 0;
-  for (int64_t r = r0 + threadIdx.x; r < r1; r += blockDim.x) {
-    if (batch_row[r] == b) {
-      f = min(f, (int)(r - r0));
-      ++k;
-    }
-  }
-  f = wave_min(f);
-  k = wave_sum(k);
-  if ((threadIdx.x & 63) == 0) {
-    atomicMin(&s_i[0], f);
-    atomicAdd(&s_i[1], k);
-  }
-  __syncthreads();
-  first = s_i[0];
-  count = s_i[1];
-}
-
-// Per (chunk g, instance b, channel): count, mean and M2 = sum (x - mean)^2 of the rows of b in the chunk, from sums
-// shifted by the first such row.  part_mean / part_m2: [chunks][n_batch][c]; part_cnt: [chunks][n_batch], ZEROED by the
-// host — only the (g, b) with rows are written, and only those are read by k_in_final.
-// Thread layout and load-first structure of k_bn_partial (norm.hip): P = c / V pieces per row, R row lanes, every load of a
-// batch of rows unconditional (row clamped to the chunk) with the contribution selected afterwards.
+// The scans of a chunk, the bodies of the two-level reductions and the workspace are segment_norm.hpp's (shared with
+// group_norm.hip); the kernels here wrap them for one record per (instance, channel).
 template <typename T, int V>
 __global__ __launch_bounds__(256) void k_in_partial(const T *__restrict__ x, const int32_t *__restrict__ batch_row,
                                                    int64_t n, int c, int chunks, int n_batch,
                                                    float *__restrict__ part_mean, float *__restrict__ part_m2,
                                                    float *__restrict__ part_cnt) {
   extern __shared__ float s_red[];  // in_partial_lds_bytes
-  const int P = c / V;
-  const int W = min(P, (int)blockDim.x);
-  const int R = max(1, (int)blockDim.x / P);
-  float *s_out = s_red + (size_t)R * 2 * c, *s_tmp = s_out + 2 * c, *s_shift = s_tmp + 256;
-  int *s_i = reinterpret_cast<int *>(s_tmp);
-  const int64_t r0 = chunk_begin(blockIdx.x, n, chunks), r1 = chunk_begin(blockIdx.x + 1, n, chunks);
-  if (r0 >= r1) return;  // whole workgroup
-  int bmin, bmax;
-  in_scan_range(batch_row, r0, r1, n_batch, s_i, bmin, bmax);
-  const bool pure = bmin == bmax;
-  for (int b = bmin; b <= bmax; ++b) {   // (uniform: every thread sees the same range)
-    int first = 0, count = (int)(r1 - r0);
-    if (!pure) {
-      in_scan_instance(batch_row, r0, r1, b, s_i + 2, first, count);
-      if (count == 0) {   // uniform
-        __syncthreads();
-        continue;
-      }
-    }
-    for (int p0 = 0; p0 < P; p0 += blockDim.x) {  // one pass unless c / V > blockDim
-      const int p = p0 + (int)threadIdx.x % W;
-      const int rl = (int)threadIdx.x / W;
-      const bool active = rl < R && p < P;
-      float s1[V], s2[V], shift[V];
-#pragma unroll
-      for (int j = 0; j < V; ++j) s1[j] = s2[j] = shift[j] = 0.f;
-      if (active) {
-        const T *xp = x + p * V;
-        const Row<T, V> k = load_row<T, V>(xp + (r0 + first) * c);
-#pragma unroll
-        for (int j = 0; j < V; ++j) shift[j] = k.v[j];
-        for (int64_t rb = r0 + rl; rb < r1; rb += (int64_t)kBnRowsPerThread * R) {
-          Row<T, V> t[kBnRowsPerThread];
-          int bi[kBnRowsPerThread];
-#pragma unroll
-          for (int i = 0; i < kBnRowsPerThread; ++i) {
-            const int64_t r = min(rb + (int64_t)i * R, r1 - 1);
-            t[i] = load_row<T, V>(xp + r * c);
-            bi[i] = pure ? b : batch_row[r];
-          }
-#pragma unroll
-          for (int i = 0; i < kBnRowsPerThread; ++i) {
-            const bool take = rb + (int64_t)i * R < r1 && bi[i] == b;
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-              const float d = take ? t[i].v[j] - shift[j] : 0.f;
-              s1[j] += d;
-              s2[j] = fmaf(d, d, s2[j]);
-            }
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-          s_red[(rl * 2 + 0) * c + p * V + j] = s1[j];
-          s_red[(rl * 2 + 1) * c + p * V + j] = s2[j];
-          if (rl == 0) s_shift[p * V + j] = shift[j];
-        }
-      }
-    }
-    bn_reduce_lanes(s_red, s_out, s_tmp, c, R);
-    const float cnt = (float)count;
-    const int64_t o = ((int64_t)blockIdx.x * n_batch + b) * c;
-    for (int ch = (int)threadIdx.x; ch < c; ch += (int)blockDim.x) {
-      const float a = s_out[ch], q = s_out[c + ch];
-      const float m = a / cnt;
-      part_mean[o + ch] = s_shift[ch] + m;
-      part_m2[o + ch] = clamp_neg(q - a * m);
-    }
-    if (threadIdx.x == 0) part_cnt[(int64_t)blockIdx.x * n_batch + b] = cnt;
-    __syncthreads();   // s_out / s_shift are rewritten for the next instance
-  }
+  seg_partial<T, V>(s_red, x, batch_row, n, c, chunks, n_batch, part_mean, part_m2, part_cnt);
 }
 
-// One wave per (instance b, channel): lane l takes chunks l, l + 64, ... (kBnMaxChunks / 64 per lane, all requested before
-// use); only the chunks whose count for b is positive hold values (the others were never written: selected away, never
-// multiplied).  Every chunk mean is taken relative to ONE shift, the mean of the first chunk that holds rows of b, so the
-// merge is three weighted sums (k_bn_final's second form), added lane by lane and across lanes in a fixed shuffle tree.
+// One wave per (instance b, channel): seg_merge_chunks -> mean, rstd = 1 / sqrt(biased variance + eps).
 // An instance without rows on this map: mean = 0, rstd = 1 / sqrt(eps).
 __global__ __launch_bounds__(256) void k_in_final(const float *__restrict__ part_mean, const float *__restrict__ part_m2,
                                                  const float *__restrict__ part_cnt, int chunks, int n_batch, int c,
@@ -215,55 +43,18 @@ __global__ __launch_bounds__(256) void k_in_final(const float *__restrict__ part
   const int lane = threadIdx.x & 63;
   const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // (b, channel)
   if (idx >= (int64_t)n_batch * c) return;  // whole wave
-  const int b = (int)(idx / c), ch = (int)(idx % c);
-  constexpr int L = kBnMaxChunks / 64;
-  float pn[L], pm[L], pq[L];
-  int first = INT_MAX;
-#pragma unroll
-  for (int i = 0; i < L; ++i) {
-    const int g = lane + i * 64;
-    const int64_t gc = min(g, chunks - 1);
-    pn[i] = part_cnt[gc * n_batch + b];
-    pm[i] = part_mean[(gc * n_batch + b) * c + ch];
-    pq[i] = part_m2[(gc * n_batch + b) * c + ch];
-  }
-#pragma unroll
-  for (int i = 0; i < L; ++i) {
-    const int g = lane + i * 64;
-    if (g >= chunks) pn[i] = 0.f;
-    if (pn[i] > 0.f) first = min(first, g);
-  }
-  first = wave_min(first);
-  if (first == INT_MAX) {   // whole wave
+  SegMerge m;
+  if (!seg_merge_chunks(part_mean, part_m2, part_cnt, chunks, n_batch, c, (int)(idx / c), (int)(idx % c), m)) {
     if (lane == 0) {
       mean_out[idx] = 0.f;
       rstd_out[idx] = 1.f / sqrtf(eps);
     }
     return;
   }
-  const float shift = part_mean[((int64_t)first * n_batch + b) * c + ch];
-  float sa = 0.f, sb = 0.f, sn = 0.f;
-#pragma unroll
-  for (int i = 0; i < L; ++i) {
-    const bool have = pn[i] > 0.f;
-    const float d = have ? pm[i] - shift : 0.f;
-    sa = fmaf(pn[i], d, sa);
-    sb += have ? fmaf(pn[i] * d, d, pq[i]) : 0.f;
-    sn += pn[i];
-  }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {  // lane l absorbs lane l + off: a fixed tree
-    const float ta = __shfl_down(sa, off, 64), tb = __shfl_down(sb, off, 64), tn = __shfl_down(sn, off, 64);
-    if ((lane & (2 * off - 1)) == 0) {
-      sa += ta;
-      sb += tb;
-      sn += tn;
-    }
-  }
   if (lane != 0) return;
-  const float am = sa / sn;
-  const float var = clamp_neg(sb - sa * am) / sn;
-  mean_out[idx] = shift + am;
+  const float am = m.sa / m.sn;
+  const float var = clamp_neg(m.sb - m.sa * am) / m.sn;
+  mean_out[idx] = m.shift + am;
   rstd_out[idx] = 1.f / sqrtf(var + eps);
 }
 
@@ -309,6 +100,17 @@ __global__ __launch_bounds__(256) void k_in_apply(const T *__restrict__ x, const
   }
 }
 
+// mean / rstd of instance b for V channels from ch0: [n_batch][c]
+struct InCoef {
+  const float *mean, *rstd;
+  int c;
+  template <int V>
+  __device__ __forceinline__ void operator()(int b, int ch0, float (&m)[V], float (&rs)[V]) const {
+    load_f32<V>(mean + (int64_t)b * c + ch0, m);
+    load_f32<V>(rstd + (int64_t)b * c + ch0, rs);
+  }
+};
+
 // per (chunk, instance, channel): sum dy and sum dy * xhat (xhat = (x - mean[b]) * rstd[b]); layout of k_in_partial
 template <typename T, int V>
 __global__ __launch_bounds__(256) void k_in_bwd_partial(const T *__restrict__ x, const T *__restrict__ dy,
@@ -317,135 +119,24 @@ __global__ __launch_bounds__(256) void k_in_bwd_partial(const T *__restrict__ x,
                                                        const float *__restrict__ rstd, float *__restrict__ part_dy,
                                                        float *__restrict__ part_dyx, float *__restrict__ part_cnt) {
   extern __shared__ float s_red[];  // in_partial_lds_bytes
-  const int P = c / V;
-  const int W = min(P, (int)blockDim.x);
-  const int R = max(1, (int)blockDim.x / P);
-  float *s_out = s_red + (size_t)R * 2 * c, *s_tmp = s_out + 2 * c;
-  int *s_i = reinterpret_cast<int *>(s_tmp);
-  const int64_t r0 = chunk_begin(blockIdx.x, n, chunks), r1 = chunk_begin(blockIdx.x + 1, n, chunks);
-  if (r0 >= r1) return;  // whole workgroup
-  int bmin, bmax;
-  in_scan_range(batch_row, r0, r1, n_batch, s_i, bmin, bmax);
-  const bool pure = bmin == bmax;
-  constexpr int RB = kBnRowsPerThread / 2;   // rows in flight per thread (x and dy: 8 loads)
-  for (int b = bmin; b <= bmax; ++b) {
-    int first = 0, count = (int)(r1 - r0);
-    if (!pure) {
-      in_scan_instance(batch_row, r0, r1, b, s_i + 2, first, count);
-      if (count == 0) {   // uniform
-        __syncthreads();
-        continue;
-      }
-    }
-    for (int p0 = 0; p0 < P; p0 += blockDim.x) {
-      const int p = p0 + (int)threadIdx.x % W;
-      const int rl = (int)threadIdx.x / W;
-      const bool active = rl < R && p < P;
-      float s1[V], s2[V];
-#pragma unroll
-      for (int j = 0; j < V; ++j) s1[j] = s2[j] = 0.f;
-      if (active) {
-        float m[V], rs[V];
-        load_f32<V>(mean + (int64_t)b * c + p * V, m);
-        load_f32<V>(rstd + (int64_t)b * c + p * V, rs);
-        for (int64_t rb = r0 + rl; rb < r1; rb += (int64_t)RB * R) {
-          Row<T, V> tx[RB], tg[RB];
-          int bi[RB];
-#pragma unroll
-          for (int i = 0; i < RB; ++i) {
-            const int64_t r = min(rb + (int64_t)i * R, r1 - 1);
-            tx[i] = load_row<T, V>(x + r * c + p * V);
-            tg[i] = load_row<T, V>(dy + r * c + p * V);
-            bi[i] = pure ? b : batch_row[r];
-          }
-#pragma unroll
-          for (int i = 0; i < RB; ++i) {
-            const bool take = rb + (int64_t)i * R < r1 && bi[i] == b;
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-              const float xh = (tx[i].v[j] - m[j]) * rs[j];
-              const float g = take ? tg[i].v[j] : 0.f;
-              s1[j] += g;
-              s2[j] = fmaf(g, take ? xh : 0.f, s2[j]);
-            }
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-          s_red[(rl * 2 + 0) * c + p * V + j] = s1[j];
-          s_red[(rl * 2 + 1) * c + p * V + j] = s2[j];
-        }
-      }
-    }
-    bn_reduce_lanes(s_red, s_out, s_tmp, c, R);
-    const int64_t o = ((int64_t)blockIdx.x * n_batch + b) * c;
-    for (int ch = (int)threadIdx.x; ch < c; ch += (int)blockDim.x) {
-      part_dy[o + ch] = s_out[ch];
-      part_dyx[o + ch] = s_out[c + ch];
-    }
-    if (threadIdx.x == 0) part_cnt[(int64_t)blockIdx.x * n_batch + b] = (float)count;
-    __syncthreads();
-  }
+  seg_bwd_partial<T, V>(s_red, x, dy, batch_row, n, c, chunks, n_batch, InCoef{mean, rstd, c}, part_dy, part_dyx,
+                        part_cnt);
 }
 
-// sums of the chunks per (instance, channel) in a fixed order (one wave each, as k_in_final): t1 = sum dy,
-// t2 = sum dy * xhat, rows[b] = rows of the instance
+// t1 = sum dy, t2 = sum dy * xhat per (instance, channel) and rows[b]: one wave each over the chunks, a fixed order
 __global__ __launch_bounds__(256) void k_in_bwd_final(const float *__restrict__ part_dy,
                                                      const float *__restrict__ part_dyx,
                                                      const float *__restrict__ part_cnt, int chunks, int n_batch, int c,
                                                      float *__restrict__ t1, float *__restrict__ t2,
                                                      float *__restrict__ rows) {
-  const int lane = threadIdx.x & 63;
-  const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (idx >= (int64_t)n_batch * c) return;  // whole wave
-  const int b = (int)(idx / c), ch = (int)(idx % c);
-  constexpr int L = kBnMaxChunks / 64;
-  float pn[L], pa[L], pb[L];
-#pragma unroll
-  for (int i = 0; i < L; ++i) {
-    const int g = lane + i * 64;
-    const int64_t gc = min(g, chunks - 1);
-    pn[i] = part_cnt[gc * n_batch + b];
-    pa[i] = part_dy[(gc * n_batch + b) * c + ch];
-    pb[i] = part_dyx[(gc * n_batch + b) * c + ch];
-  }
-  float a = 0.f, q = 0.f, sn = 0.f;
-#pragma unroll
-  for (int i = 0; i < L; ++i) {
-    const bool have = lane + i * 64 < chunks && pn[i] > 0.f;
-    a += have ? pa[i] : 0.f;
-    q += have ? pb[i] : 0.f;
-    sn += have ? pn[i] : 0.f;
-  }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const float ta = __shfl_down(a, off, 64), tq = __shfl_down(q, off, 64), tn = __shfl_down(sn, off, 64);
-    if ((lane & (2 * off - 1)) == 0) {
-      a += ta;
-      q += tq;
-      sn += tn;
-    }
-  }
-  if (lane == 0) {
-    t1[idx] = a;
-    t2[idx] = q;
-    if (ch == 0) rows[b] = sn;
-  }
+  seg_bwd_final(part_dy, part_dyx, part_cnt, chunks, n_batch, c, t1, t2, rows);
 }
 
 // grad_beta = sum over the instances (ascending) of t1, grad_gamma = of t2; either may be NULL
 __global__ __launch_bounds__(256) void k_in_bwd_params(const float *__restrict__ t1, const float *__restrict__ t2,
                                                       int n_batch, int c, float *__restrict__ grad_gamma,
                                                       float *__restrict__ grad_beta) {
-  const int ch = blockIdx.x * blockDim.x + threadIdx.x;
-  if (ch >= c) return;
-  float a = 0.f, q = 0.f;
-  for (int b = 0; b < n_batch; ++b) {
-    a += t1[(int64_t)b * c + ch];
-    q += t2[(int64_t)b * c + ch];
-  }
-  if (grad_beta != nullptr) grad_beta[ch] = a;
-  if (grad_gamma != nullptr) grad_gamma[ch] = q;
+  seg_bwd_params<float>(t1, t2, n_batch, c, grad_gamma, grad_beta);
 }
 
 // dx = A * ((dy - k1) - (x - mean[b]) * k2) with A = gamma * rstd[b], k1 = t1[b] / n_b, k2 = t2[b] / n_b * rstd[b]
@@ -566,15 +257,7 @@ __global__ __launch_bounds__(256) void k_in_bwd_sums_f64(const double *__restric
 __global__ __launch_bounds__(256) void k_in_bwd_params_f64(const double *__restrict__ t1, const double *__restrict__ t2,
                                                           int n_batch, int c, double *__restrict__ grad_gamma,
                                                           double *__restrict__ grad_beta) {
-  const int ch = blockIdx.x * blockDim.x + threadIdx.x;
-  if (ch >= c) return;
-  double a = 0.0, q = 0.0;
-  for (int b = 0; b < n_batch; ++b) {
-    a += t1[(int64_t)b * c + ch];
-    q += t2[(int64_t)b * c + ch];
-  }
-  if (grad_beta != nullptr) grad_beta[ch] = a;
-  if (grad_gamma != nullptr) grad_gamma[ch] = q;
+  seg_bwd_params<double>(t1, t2, n_batch, c, grad_gamma, grad_beta);
 }
 
 __global__ __launch_bounds__(256) void k_in_bwd_apply_f64(const double *__restrict__ x, const double *__restrict__ dy,
@@ -595,44 +278,12 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply_f64(const double *__restri
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// workspace: part_a | part_b [chunks][n_batch][c] floats | part_cnt [chunks][n_batch] | t1 | t2 [n_batch][c] | rows [n_batch]
-// (every piece 256-byte aligned; the float64 entry points use t1 | t2 | rows as doubles at the start)
-struct InWs {
-  float *pa, *pb, *cnt, *t1, *t2, *rows;
-};
+// workspace: in_ws_layout_f32 (the float64 entry points use t1 | t2 | rows as doubles at the start)
 static int64_t in_ws_layout(int64_t n, int n_batch, int c, char *base, InWs *w) {
-  const int64_t chunks = bn_chunks_max(n);
-  const int64_t part = align_up(chunks * n_batch * c * 4, 256), pc = align_up(chunks * n_batch * 4, 256);
-  const int64_t t = align_up((int64_t)n_batch * c * 4, 256), rw = align_up((int64_t)n_batch * 4, 256);
-  if (w != nullptr) {
-    w->pa = reinterpret_cast<float *>(base);
-    w->pb = reinterpret_cast<float *>(base + part);
-    w->cnt = reinterpret_cast<float *>(base + 2 * part);
-    w->t1 = reinterpret_cast<float *>(base + 2 * part + pc);
-    w->t2 = reinterpret_cast<float *>(base + 2 * part + pc + t);
-    w->rows = reinterpret_cast<float *>(base + 2 * part + pc + 2 * t);
-  }
-  const int64_t f32 = 2 * part + pc + 2 * t + rw;
+  const int64_t f32 = in_ws_layout_f32(n, n_batch, c, base, w);
   const int64_t f64 = 2 * align_up((int64_t)n_batch * c * 8, 256) + align_up((int64_t)n_batch * 8, 256);
   return f32 > f64 ? f32 : f64;
 }
-
-// widest piece for rows of c channels of T when every address is 16-byte aligned (as bn_stats): 16 bytes, else 4 elements
-template <typename T>
-static int in_piece(int c, std::initializer_list<const void *> ptrs) {
-  constexpr int W = 16 / (int)sizeof(T);
-  bool aligned = true;
-  for (const void *p : ptrs) aligned = aligned && (uintptr_t)p % 16 == 0;
-  return (aligned && c % W == 0) ? W : ((aligned && c % 4 == 0) ? 4 : 1);
-}
-
-#define ME_IN_DISPATCH_V(T, v, ...)                            \
-  do {                                                         \
-    constexpr int W_ = 16 / (int)sizeof(T);                    \
-    if ((v) == W_) { constexpr int V = W_; __VA_ARGS__; }      \
-    else if ((v) == 4) { constexpr int V = 4; __VA_ARGS__; }   \
-    else { constexpr int V = 1; __VA_ARGS__; }                 \
-  } while (0)
 
 template <typename T>
 static int in_stats(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, float eps, float *mean,

@@ -539,6 +539,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("weight"), py::arg("mean"), py::arg("rstd"),
         py::arg("in_key"), py::arg("glob_key"), py::arg("manager"), py::arg("need_grad_in") = true,
         py::arg("need_grad_weight") = true, py::arg("need_grad_bias") = true);
+  // group normalisation: torch.nn.GroupNorm's arithmetic per instance of a sparse tensor (no reference operator); one
+  // fused operator pair on csrc/group_norm.hip
+  m.def("GroupNormForwardGPU",
+        [](const Tensor &in_feat, int64_t num_groups, const py::object &weight, const py::object &bias, double eps,
+           CoordinateMapKey *in_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+          const Tensor w = opt_tensor(weight), b = opt_tensor(bias);
+          std::tuple<Tensor, Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = group_norm_forward(in_feat, num_groups, w, b, eps, in_key, glob_key, mgr);
+          }
+          return py::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r));
+        },
+        py::arg("in_feat"), py::arg("num_groups"), py::arg("weight"), py::arg("bias"), py::arg("eps"), py::arg("in_key"),
+        py::arg("glob_key"), py::arg("manager"));
+  m.def("GroupNormBackwardGPU",
+        [](const Tensor &in_feat, const Tensor &grad_out, int64_t num_groups, const py::object &weight, const Tensor &mean,
+           const Tensor &rstd, CoordinateMapKey *in_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
+           bool need_grad_in, bool need_grad_weight, bool need_grad_bias) {
+          const Tensor w = opt_tensor(weight);
+          std::tuple<Tensor, Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = group_norm_backward(in_feat, grad_out, num_groups, w, mean, rstd, in_key, glob_key, mgr, need_grad_in,
+                                    need_grad_weight, need_grad_bias);
+          }
+          return py::make_tuple(opt_out(std::get<0>(r)), opt_out(std::get<1>(r)), opt_out(std::get<2>(r)));
+        },
+        py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("num_groups"), py::arg("weight"), py::arg("mean"),
+        py::arg("rstd"), py::arg("in_key"), py::arg("glob_key"), py::arg("manager"), py::arg("need_grad_in") = true,
+        py::arg("need_grad_weight") = true, py::arg("need_grad_bias") = true);
   // tensor fields (field.cpp): the reference's InterpolationForwardGPU / InterpolationBackwardGPU and coo_spmm_int32 /
   // coo_spmm_average_int32 (pybind/extern.hpp:497-506), plus the CSR building blocks the autograd functions cache
   m.def("CsrFromCooGPU",

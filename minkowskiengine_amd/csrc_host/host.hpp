@@ -358,6 +358,15 @@ std::tuple<Tensor, Tensor, Tensor> instance_norm_backward(const Tensor &in_feat,
                                                           const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key,
                                                           CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
                                                           bool need_grad_in, bool need_grad_weight, bool need_grad_bias);
+// group normalisation (csrc/group_norm.hip; twin of backend.GroupNorm{Forward,Backward}GPU)
+std::tuple<Tensor, Tensor, Tensor> group_norm_forward(const Tensor &in_feat, int64_t num_groups, const Tensor &weight,
+                                                      const Tensor &bias, double eps, CoordinateMapKey *in_key,
+                                                      CoordinateMapKey *glob_key, CoordinateMapManager *mgr);
+std::tuple<Tensor, Tensor, Tensor> group_norm_backward(const Tensor &in_feat, Tensor grad_out, int64_t num_groups,
+                                                       const Tensor &weight, const Tensor &mean, const Tensor &rstd,
+                                                       CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
+                                                       CoordinateMapManager *mgr, bool need_grad_in,
+                                                       bool need_grad_weight, bool need_grad_bias);
 // dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU / DensePolicy)
 int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box);
 std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,

@@ -1076,6 +1076,91 @@ std::tuple<Tensor, Tensor, Tensor> instance_norm_backward(const Tensor &in_feat,
   return {grad_in, grad_weight, grad_bias};
 }
 
+// ---- group normalisation (csrc/group_norm.hip; twin of backend.GroupNorm{Forward,Backward}GPU) ---------------------------------
+static int gnorm_groups(int64_t num_groups, int c) {
+  check(num_groups > 0 && c % num_groups == 0, "the channel count " + std::to_string(c) +
+                                                   " must be a multiple of num_groups " + std::to_string(num_groups));
+  return (int)num_groups;
+}
+
+std::tuple<Tensor, Tensor, Tensor> group_norm_forward(const Tensor &in_feat, int64_t num_groups, const Tensor &weight,
+                                                      const Tensor &bias, double eps, CoordinateMapKey *in_key,
+                                                      CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
+  const Tensor &rows = pr.first;
+  const int n_batch = (int)pr.second;
+  const int64_t n = in_feat.size(0);
+  const int c = (int)in_feat.size(1);
+  const int groups = gnorm_groups(num_groups, c);
+  inorm_check_vec("weight", weight, in_feat, c);
+  inorm_check_vec("bias", bias, in_feat, c);
+  const c10::Device dev = in_feat.device();
+  const bool f64 = in_feat.scalar_type() == at::kDouble;
+  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  Tensor mean = at::empty({n_batch, groups}, popt), rstd = at::empty({n_batch, groups}, popt);
+  Tensor out = at::empty_like(in_feat);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_gnorm_stats_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, groups, eps, ptr<double>(mean),
+                             ptr<double>(rstd), stream_of(dev)));
+    me_ok(me_gnorm_apply_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, groups, ptr<double>(mean),
+                             ptr<double>(rstd), ptr<double>(weight), ptr<double>(bias), ptr<double>(out), stream_of(dev)));
+    return {out, mean, rstd};
+  }
+  const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
+  Tensor ws = workspace(me_gnorm_workspace_bytes(n, n_batch, c, groups), dev);
+  me_ok(me_gnorm_stats(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups, (float)eps, ptr<float>(mean),
+                       ptr<float>(rstd), vptr(ws), ws.numel(), stream_of(dev)));
+  me_ok(me_gnorm_apply(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups, ptr<float>(mean),
+                       ptr<float>(rstd), ptr<float>(weight), ptr<float>(bias), out.data_ptr(), stream_of(dev)));
+  return {out, mean, rstd};
+}
+
+std::tuple<Tensor, Tensor, Tensor> group_norm_backward(const Tensor &in_feat, Tensor grad_out, int64_t num_groups,
+                                                       const Tensor &weight, const Tensor &mean, const Tensor &rstd,
+                                                       CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
+                                                       CoordinateMapManager *mgr, bool need_grad_in,
+                                                       bool need_grad_weight, bool need_grad_bias) {
+  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
+  const Tensor &rows = pr.first;
+  const int n_batch = (int)pr.second;
+  grad_out = grad_out.contiguous();
+  check_feat("grad_out_feat", grad_out);
+  if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
+  check(grad_out.sizes() == in_feat.sizes(), "grad_out_feat must have the shape of in_feat");
+  const int64_t n = in_feat.size(0);
+  const int c = (int)in_feat.size(1);
+  const int groups = gnorm_groups(num_groups, c);
+  inorm_check_vec("weight", weight, in_feat, c);
+  check(mean.defined() && rstd.defined(), "group norm backward needs mean and rstd");
+  inorm_check_vec("mean", mean, in_feat, (int64_t)n_batch * groups);
+  inorm_check_vec("rstd", rstd, in_feat, (int64_t)n_batch * groups);
+  const c10::Device dev = in_feat.device();
+  const bool f64 = in_feat.scalar_type() == at::kDouble;
+  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  Tensor grad_in = need_grad_in ? at::empty_like(in_feat) : Tensor();
+  Tensor grad_weight = need_grad_weight ? at::empty({c}, popt) : Tensor();
+  Tensor grad_bias = need_grad_bias ? at::empty({c}, popt) : Tensor();
+  if (n == 0) {
+    if (grad_weight.defined()) grad_weight.zero_();
+    if (grad_bias.defined()) grad_bias.zero_();
+    return {grad_in, grad_weight, grad_bias};
+  }
+  Tensor ws = workspace(me_gnorm_workspace_bytes(n, n_batch, c, groups), dev);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_gnorm_backward_f64(ptr<double>(in_feat), ptr<double>(grad_out), ptr<int32_t>(rows), n, n_batch, c, groups,
+                                ptr<double>(mean), ptr<double>(rstd), ptr<double>(weight), ptr<double>(grad_in),
+                                ptr<double>(grad_weight), ptr<double>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
+  } else {
+    const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
+    me_ok(me_gnorm_backward(in_feat.data_ptr(), grad_out.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups,
+                            ptr<float>(mean), ptr<float>(rstd), ptr<float>(weight), vptr(grad_in), ptr<float>(grad_weight),
+                            ptr<float>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
+  }
+  return {grad_in, grad_weight, grad_bias};
+}
+
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------
 Tensor pruning_forward(const Tensor &in_feat, const Tensor &keep, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr) {

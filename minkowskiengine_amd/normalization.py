@@ -1,4 +1,7 @@
-"""MinkowskiInstanceNorm, MinkowskiStableInstanceNorm and MinkowskiInstanceNormFunction (reference:
+"""Normalisations per instance of a sparse tensor: instance norm (the reference's) and group norm (torch.nn.GroupNorm's
+arithmetic; the reference has none).
+
+MinkowskiInstanceNorm, MinkowskiStableInstanceNorm and MinkowskiInstanceNormFunction (reference:
 MinkowskiEngine/MinkowskiNormalization.py:194-399).  The reference normalises every instance (batch index) with a chain
 of its global average pooling and broadcast operators plus torch element-wise ops; here one operator pair,
 `InstanceNorm{Forward,Backward}GPU`, resolved in the backend by name as the other operators are, runs the kernels of
@@ -6,7 +9,15 @@ csrc/instance_norm.hip: per instance b and channel
 
     out[i] = (x[i] - mean[b_i]) / sqrt(var[b_i] + eps) * weight + bias        (var: biased)
 
-in three passes over the feature matrix forward and five backward."""
+in three passes over the feature matrix forward and five backward.
+
+MinkowskiGroupNorm and MinkowskiGroupNormFunction run `GroupNorm{Forward,Backward}GPU` on csrc/group_norm.hip with the same
+pass counts: per instance b and group g of C / num_groups consecutive channels
+
+    out[i, c] = (x[i, c] - mean[b_i, g_c]) / sqrt(var[b_i, g_c] + eps) * weight[c] + bias[c]
+
+with mean / var over the n_b rows of the instance and the channels of the group — torch.nn.functional.group_norm applied
+to every instance's [1, C, n_b] tensor on its own."""
 import torch
 from torch.autograd import Function
 from torch.nn import Parameter
@@ -123,3 +134,79 @@ class MinkowskiStableInstanceNorm(_InstanceNormBase):
     def __init__(self, num_features):
         super().__init__(num_features)
         self.eps = 1e-6
+
+
+class MinkowskiGroupNormFunction(Function):
+    """Group normalisation of the feature rows of a coordinate map, every instance (batch index) on its own.  weight /
+    bias: (C,) tensors of the parameter dtype (fp32 for fp32 and bf16 features, float64 for float64) or None."""
+
+    @staticmethod
+    def forward(ctx, in_feat, num_groups, weight, bias, eps, in_coords_key, glob_coords_key=None, coords_manager=None):
+        if glob_coords_key is None:
+            glob_coords_key = _host.key_like(in_coords_key)
+        in_feat = in_feat.contiguous()
+        w = None if weight is None else weight.detach().reshape(-1).contiguous()
+        b = None if bias is None else bias.detach().reshape(-1).contiguous()
+        fw_fn = get_minkowski_function("GroupNormForward", in_feat, in_coords_key)
+        out, mean, rstd = fw_fn(in_feat, int(num_groups), w, b, float(eps), in_coords_key, glob_coords_key,
+                                coords_manager._manager)
+        ctx.save_for_backward(in_feat, w, mean, rstd)
+        ctx.misc = (int(num_groups), in_coords_key, glob_coords_key, coords_manager,
+                    None if weight is None else weight.shape, None if bias is None else bias.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        in_feat, w, mean, rstd = ctx.saved_tensors
+        num_groups, in_key, glob_key, coords_manager, w_shape, b_shape = ctx.misc
+        need_w = w_shape is not None and ctx.needs_input_grad[2]
+        need_b = b_shape is not None and ctx.needs_input_grad[3]
+        bw_fn = get_minkowski_function("GroupNormBackward", grad_out, in_key)
+        grad_in, grad_w, grad_b = bw_fn(in_feat, grad_out.contiguous(), num_groups, w, mean, rstd, in_key, glob_key,
+                                        coords_manager._manager, need_grad_in=ctx.needs_input_grad[0],
+                                        need_grad_weight=need_w, need_grad_bias=need_b)
+        return (grad_in, None, grad_w.view(w_shape) if need_w else None, grad_b.view(b_shape) if need_b else None,
+                None, None, None, None)
+
+
+class MinkowskiGroupNorm(MinkowskiModuleBase):
+    r"""torch.nn.GroupNorm for sparse tensors: every instance (batch index) is normalised per group of
+    `num_channels / num_groups` consecutive channels with the mean and the biased variance over its rows and the
+    channels of the group (eps inside the square root), then `* weight + bias` per channel.  `num_groups ==
+    num_channels` is instance normalisation; `num_groups == 1` normalises over all channels and rows of an instance.
+    Parameters `weight`, `bias` of shape (num_channels,), fp32, as torch.nn.GroupNorm's, so state dicts move between the
+    two strictly; `affine=False` registers both as None.  bf16 features run with the fp32 parameters and give bf16
+    outputs; float64 features need a `.double()` module."""
+
+    def __init__(self, num_groups, num_channels, eps=1e-5, affine=True):
+        super().__init__()
+        if num_channels % num_groups != 0:
+            raise ValueError("num_channels must be divisible by num_groups")
+        self.num_groups = num_groups
+        self.num_channels = num_channels
+        self.eps = eps
+        self.affine = affine
+        if affine:
+            self.weight = Parameter(torch.ones(num_channels, dtype=torch.float32))
+            self.bias = Parameter(torch.zeros(num_channels, dtype=torch.float32))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def __repr__(self):
+        return (self.__class__.__name__ +
+                f"({self.num_groups}, {self.num_channels}, eps={self.eps}, affine={self.affine})")
+
+    def reset_parameters(self):
+        if self.affine:
+            with torch.no_grad():
+                self.weight.fill_(1)
+                self.bias.zero_()
+
+    def forward(self, input):
+        assert isinstance(input, SparseTensor)
+        assert input.shape[1] == self.num_channels, f"Channel size mismatch {self.num_channels} != {input.shape[1]}"
+        output = MinkowskiGroupNormFunction.apply(input.F, self.num_groups, self.weight, self.bias, self.eps,
+                                                  input.coordinate_map_key, None, input._manager)
+        return SparseTensor(output, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)

@@ -93,7 +93,10 @@ typedef struct me_region {
  *              row count (me_bn_moments_floats, me_bn_local_moments, me_bn_stats_from_moments, me_bn_backward_sums,
  *              me_bn_backward_reduce, me_bn_backward_apply)
  *   1.15 (250)  round 15: group normalisation per (instance, group of channels): statistics, apply and backward
- *              (me_gnorm_workspace_bytes, me_gnorm_stats, me_gnorm_apply, me_gnorm_backward and their _f64 twins) */
+ *              (me_gnorm_workspace_bytes, me_gnorm_stats, me_gnorm_apply, me_gnorm_backward and their _f64 twins)
+ *   1.16 (260)  round 16: conditional group normalisation: a per-instance scale / shift folded into the affine map and a
+ *              fused SiLU (me_gnorm_cond_workspace_bytes, me_gnorm_cond_apply, me_gnorm_cond_backward and their _f64
+ *              twins) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1079,6 +1082,44 @@ int me_gnorm_backward_f64(const double *x_dev, const double *dy_dev, const int32
                           int32_t n_batch, int32_t c, int32_t groups, const double *mean_dev, const double *rstd_dev,
                           const double *gamma_dev, double *dx_dev, double *grad_gamma_dev, double *grad_beta_dev,
                           void *workspace_dev, int64_t workspace_bytes, void *stream);
+
+/* ---- conditional group normalisation (MinkowskiConditionalGroupNorm: AdaGN / FiLM; csrc/group_norm.hip, ABI 1.16) ----
+ * Group normalisation whose affine map is modulated per instance and followed by an optional SiLU.  The statistics are
+ * me_gnorm_stats' (mean / rstd [n_batch, groups]).  scale / shift: [n_batch, c] in the parameter type, row b for the
+ * instance b of batch_row; act: 0 identity, 1 SiLU.
+ *   ge[b, ch] = gamma[ch] * (1 + scale[b, ch]),  be[b, ch] = beta[ch] * (1 + scale[b, ch]) + shift[b, ch]
+ *   me_gnorm_cond_apply:    v = xhat * ge[b, ch] + be[b, ch], y = act(v)      (SiLU: v * sigmoid(v), in fp32)
+ *   me_gnorm_cond_backward: dv = dy * act'(v) with v recomputed from x; t1[b, ch] = sum_{i in b} dv, t2 = sum dv * xhat;
+ *                           grad_shift = t1, grad_scale = gamma * t2 + beta * t1, grad_beta = sum_b (1 + scale) * t1,
+ *                           grad_gamma = sum_b (1 + scale) * t2 (ascending b); T1[b, g] = sum_{ch in g} ge * t1, T2
+ *                           likewise (ascending ch); dx = rstd * (ge * dv - T1 / m - xhat * T2 / m), m = n_b * cg.
+ * gamma, beta, scale, shift (1 / 0 / 0 / 0) and dx and every gradient pointer (skipped) may be NULL; every requested word is
+ * written, the grad_scale / grad_shift rows of an instance without rows with exactly 0.  No atomics on values, fixed
+ * summation order.  ge / be live in the workspace (me_gnorm_cond_workspace_bytes >= me_gnorm_workspace_bytes), which the
+ * apply needs too.  Host-side argument errors (nothing launched): act other than 0 / 1; groups <= 0 or c % groups != 0; a
+ * short workspace; more than 3225 channels (fp32 / bf16 entry points).  The _f64 entry points: plain double, parameters,
+ * scale / shift and statistics double. */
+int64_t me_gnorm_cond_workspace_bytes(int64_t n, int32_t n_batch, int32_t c, int32_t groups);
+int me_gnorm_cond_apply(const void *x_dev, int32_t is_bf16, const int32_t *batch_row_dev, int64_t n, int32_t n_batch,
+                        int32_t c, int32_t groups, const float *mean_dev, const float *rstd_dev, const float *gamma_dev,
+                        const float *beta_dev, const float *scale_dev, const float *shift_dev, int32_t act, void *y_dev,
+                        void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_gnorm_cond_backward(const void *x_dev, const void *dy_dev, int32_t is_bf16, const int32_t *batch_row_dev,
+                           int64_t n, int32_t n_batch, int32_t c, int32_t groups, const float *mean_dev,
+                           const float *rstd_dev, const float *gamma_dev, const float *beta_dev, const float *scale_dev,
+                           const float *shift_dev, int32_t act, void *dx_dev, float *grad_gamma_dev, float *grad_beta_dev,
+                           float *grad_scale_dev, float *grad_shift_dev, void *workspace_dev, int64_t workspace_bytes,
+                           void *stream);
+int me_gnorm_cond_apply_f64(const double *x_dev, const int32_t *batch_row_dev, int64_t n, int32_t n_batch, int32_t c,
+                            int32_t groups, const double *mean_dev, const double *rstd_dev, const double *gamma_dev,
+                            const double *beta_dev, const double *scale_dev, const double *shift_dev, int32_t act,
+                            double *y_dev, void *stream);
+int me_gnorm_cond_backward_f64(const double *x_dev, const double *dy_dev, const int32_t *batch_row_dev, int64_t n,
+                               int32_t n_batch, int32_t c, int32_t groups, const double *mean_dev, const double *rstd_dev,
+                               const double *gamma_dev, const double *beta_dev, const double *scale_dev,
+                               const double *shift_dev, int32_t act, double *dx_dev, double *grad_gamma_dev,
+                               double *grad_beta_dev, double *grad_scale_dev, double *grad_shift_dev, void *workspace_dev,
+                               int64_t workspace_bytes, void *stream);
 
 /* ---- dense <-> sparse conversion (SparseTensor.dense, ME.to_sparse, ME.to_sparse_all, ME.dense_coordinates:
  *      MinkowskiEngine/MinkowskiSparseTensor.py:460-557 and MinkowskiOps.py:246-348, torch indexing there;

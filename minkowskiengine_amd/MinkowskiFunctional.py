@@ -1,8 +1,9 @@
 """Functional twins of torch.nn.functional on sparse tensors and tensor fields (the reference's MinkowskiFunctional.py):
 the torch function runs on the feature matrix `.F`.  Activations and the other feature-to-feature functions return a
 tensor of the input's kind on the input's coordinates (a TensorField stays a TensorField); losses take a torch target
-and return what torch returns.  No kernels of their own, except `group_norm`: torch's needs one dense tensor per
-sample, so it runs MinkowskiGroupNorm's operators (normalization.py, csrc/group_norm.hip)."""
+and return what torch returns.  No kernels of their own, except `group_norm` and `conditional_group_norm`:
+torch's needs one dense tensor per sample, so they run MinkowskiGroupNorm's and MinkowskiConditionalGroupNorm's operators
+(normalization.py, csrc/group_norm.hip)."""
 import torch.nn.functional as F
 
 from .layers import _rewrap
@@ -58,4 +59,16 @@ def group_norm(input, num_groups, weight=None, bias=None, eps=1e-5):
     return SparseTensor(out, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
 
 
-__all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm"]
+def conditional_group_norm(input, num_groups, weight=None, bias=None, scale=None, shift=None, activation=None, eps=1e-5):
+    """group_norm modulated per instance and followed by an optional SiLU: act(gn(x) * (1 + scale[b]) + shift[b]).
+    scale / shift: (instances, C) tensors of the parameter dtype or None, row j for the j-th smallest batch index;
+    activation: None or "silu" (MinkowskiConditionalGroupNorm's operators, csrc/group_norm.hip)."""
+    from .normalization import MinkowskiConditionalGroupNormFunction
+    from .sparse_tensor import SparseTensor
+    assert isinstance(input, SparseTensor)
+    out = MinkowskiConditionalGroupNormFunction.apply(input.F, num_groups, weight, bias, scale, shift, activation, eps,
+                                                      input.coordinate_map_key, None, input._manager)
+    return SparseTensor(out, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
+
+
+__all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm"]

@@ -21,8 +21,8 @@ from .convolution import (  # noqa: F401
     MinkowskiConvolutionTransposeFunction, MinkowskiGenerativeConvolutionTranspose)
 from .channelwise import MinkowskiChannelwiseConvolution, MinkowskiChannelwiseConvolutionFunction  # noqa: F401
 from .normalization import (  # noqa: F401
-    MinkowskiGroupNorm, MinkowskiGroupNormFunction, MinkowskiInstanceNorm, MinkowskiInstanceNormFunction,
-    MinkowskiStableInstanceNorm)
+    MinkowskiConditionalGroupNorm, MinkowskiConditionalGroupNormFunction, MinkowskiGroupNorm, MinkowskiGroupNormFunction,
+    MinkowskiInstanceNorm, MinkowskiInstanceNormFunction, MinkowskiStableInstanceNorm)
 from .pruning import MinkowskiPruning, MinkowskiPruningFunction  # noqa: F401
 from .tensor_field import TensorField, create_splat_coordinates  # noqa: F401
 from .interpolation import MinkowskiInterpolation, MinkowskiInterpolationFunction  # noqa: F401

@@ -160,6 +160,15 @@ SIGNATURES = {
     "me_gnorm_apply_f64": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "me_gnorm_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                              c_vp, c_vp, c_i64, c_vp]),
+    "me_gnorm_cond_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "me_gnorm_cond_apply": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "me_gnorm_cond_backward": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                              c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_gnorm_cond_apply_f64": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                               c_i32, c_vp, c_vp]),
+    "me_gnorm_cond_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                                  c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "me_dense_policy": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, c_i32]),
     "me_dense_cell_index": (ctypes.c_int, [c_vp, c_i64, c_i32, _P_I32, _P_I32, _P_I64, c_vp, c_vp, c_vp]),
     "me_dense_grid": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp]),

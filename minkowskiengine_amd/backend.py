@@ -3369,6 +3369,117 @@ def GroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, mean, rstd,
 
 
 # ------------------------------------------------------------------------------------------------
+# conditional group normalisation (csrc/group_norm.hip, k_gnc_*): group norm whose affine map is modulated by a scale and a
+# shift per instance (AdaGN / FiLM), with an optional fused SiLU.  The statistics are group norm's.
+# ------------------------------------------------------------------------------------------------
+_GNC_ACTIVATIONS = {None: 0, "silu": 1}
+
+
+def _gnorm_cond_act(activation):
+    _check(activation in _GNC_ACTIVATIONS, "activation must be None or 'silu', not", repr(activation))
+    return _GNC_ACTIVATIONS[activation]
+
+
+def _gnorm_cond_check_mod(name, t, in_feat, n_batch, c):
+    want = _inorm_param_dtype(in_feat)
+    _check(t is None or (t.is_cuda and t.is_contiguous() and t.dtype == want and tuple(t.shape) == (n_batch, c) and
+                         t.device == in_feat.device),
+           name, "must be a contiguous", want, "GPU tensor of shape", (n_batch, c), "(one row per instance) on the device of "
+           "the features")
+
+
+def ConditionalGroupNormForwardGPU(in_feat, num_groups, weight, bias, scale, shift, activation, eps, in_key, glob_key,
+                                   manager):
+    """-> (out_feat, mean, rstd): out = act(xhat * weight * (1 + scale[b]) + bias * (1 + scale[b]) + shift[b]) with
+    GroupNormForwardGPU's xhat, mean and rstd.  scale / shift: [manager.size(glob_key), C] in the parameter dtype or None,
+    row j for row j of the origin map (the j-th smallest batch index); activation: None or "silu"."""
+    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
+    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
+    groups = _gnorm_groups(num_groups, c)
+    act = _gnorm_cond_act(activation)
+    _inorm_check_vec("weight", weight, in_feat, c)
+    _inorm_check_vec("bias", bias, in_feat, c)
+    _gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c)
+    _gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c)
+    lib = _lib.load()
+    dev = in_feat.device
+    pd = _inorm_param_dtype(in_feat)
+    out = torch.empty_like(in_feat)
+    if n == 0:
+        return (out, torch.zeros((n_batch, groups), dtype=pd, device=dev),
+                torch.full((n_batch, groups), float(eps) ** -0.5, dtype=pd, device=dev))
+    mean = torch.empty((n_batch, groups), dtype=pd, device=dev)
+    rstd = torch.empty((n_batch, groups), dtype=pd, device=dev)
+    with _on(dev):
+        if in_feat.dtype == torch.float64:
+            _lib.check(lib.me_gnorm_stats_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, groups, float(eps), _ptr(mean),
+                                              _ptr(rstd), _stream(dev)))
+            _lib.check(lib.me_gnorm_cond_apply_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, groups, _ptr(mean),
+                                                   _ptr(rstd), _ptr(weight), _ptr(bias), _ptr(scale), _ptr(shift), act,
+                                                   _ptr(out), _stream(dev)))
+        else:
+            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
+            ws = _workspace(int(lib.me_gnorm_cond_workspace_bytes(n, n_batch, c, groups)), dev)
+            _timed("gnorm_cond_forward", dev, lambda: (
+                _lib.check(lib.me_gnorm_stats(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, groups, float(eps),
+                                              _ptr(mean), _ptr(rstd), _ptr(ws), ws.numel(), _stream(dev))),
+                _lib.check(lib.me_gnorm_cond_apply(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, groups, _ptr(mean),
+                                                   _ptr(rstd), _ptr(weight), _ptr(bias), _ptr(scale), _ptr(shift), act,
+                                                   _ptr(out), _ptr(ws), ws.numel(), _stream(dev)))))
+    return out, mean, rstd
+
+
+def ConditionalGroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, bias, scale, shift, activation, mean, rstd,
+                                    in_key, glob_key, manager, need_grad_in=True, need_grad_weight=True,
+                                    need_grad_bias=True, need_grad_scale=True, need_grad_shift=True):
+    """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None, grad_scale [batch, C] | None, grad_shift
+    [batch, C] | None) from the statistics of the forward pass, in the parameter dtype (fp32 for bf16 features).  The rows
+    of grad_scale / grad_shift of an instance without rows on this map are 0."""
+    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
+    if not grad_out_feat.is_contiguous():
+        grad_out_feat = grad_out_feat.contiguous()
+    _check_feat("grad_out_feat", grad_out_feat)
+    if grad_out_feat.dtype != in_feat.dtype:
+        grad_out_feat = grad_out_feat.to(in_feat.dtype)
+    _check(tuple(grad_out_feat.shape) == tuple(in_feat.shape), "grad_out_feat must have the shape of in_feat")
+    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
+    groups = _gnorm_groups(num_groups, c)
+    act = _gnorm_cond_act(activation)
+    _inorm_check_vec("weight", weight, in_feat, c)
+    _inorm_check_vec("bias", bias, in_feat, c)
+    _gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c)
+    _gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c)
+    _check(mean is not None and rstd is not None, "conditional group norm backward needs mean and rstd")
+    _inorm_check_vec("mean", mean, in_feat, n_batch * groups)
+    _inorm_check_vec("rstd", rstd, in_feat, n_batch * groups)
+    lib = _lib.load()
+    dev = in_feat.device
+    pd = _inorm_param_dtype(in_feat)
+    grad_in = torch.empty_like(in_feat) if need_grad_in else None
+    grad_weight = torch.empty(c, dtype=pd, device=dev) if need_grad_weight else None
+    grad_bias = torch.empty(c, dtype=pd, device=dev) if need_grad_bias else None
+    grad_scale = torch.empty((n_batch, c), dtype=pd, device=dev) if need_grad_scale else None
+    grad_shift = torch.empty((n_batch, c), dtype=pd, device=dev) if need_grad_shift else None
+    if n == 0:
+        return (grad_in,) + tuple(None if g is None else g.zero_()
+                                  for g in (grad_weight, grad_bias, grad_scale, grad_shift))
+    ws = _workspace(int(lib.me_gnorm_cond_workspace_bytes(n, n_batch, c, groups)), dev)
+    with _on(dev):
+        if in_feat.dtype == torch.float64:
+            _lib.check(lib.me_gnorm_cond_backward_f64(
+                _ptr(in_feat), _ptr(grad_out_feat), _ptr(rows), n, n_batch, c, groups, _ptr(mean), _ptr(rstd),
+                _ptr(weight), _ptr(bias), _ptr(scale), _ptr(shift), act, _ptr(grad_in), _ptr(grad_weight),
+                _ptr(grad_bias), _ptr(grad_scale), _ptr(grad_shift), _ptr(ws), ws.numel(), _stream(dev)))
+        else:
+            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
+            _timed("gnorm_cond_backward", dev, lambda: _lib.check(lib.me_gnorm_cond_backward(
+                _ptr(in_feat), _ptr(grad_out_feat), bf, _ptr(rows), n, n_batch, c, groups, _ptr(mean), _ptr(rstd),
+                _ptr(weight), _ptr(bias), _ptr(scale), _ptr(shift), act, _ptr(grad_in), _ptr(grad_weight),
+                _ptr(grad_bias), _ptr(grad_scale), _ptr(grad_shift), _ptr(ws), ws.numel(), _stream(dev))))
+    return grad_in, grad_weight, grad_bias, grad_scale, grad_shift
+
+
+# ------------------------------------------------------------------------------------------------
 # pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu)
 # ------------------------------------------------------------------------------------------------
 def PruningForwardGPU(in_feat, keep, in_key, out_key, manager):

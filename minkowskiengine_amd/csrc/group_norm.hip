@@ -447,6 +447,396 @@ static int gn_backward(const T *x, const T *dy, const int32_t *batch_row, int64_
   return 0;
 }
 
+// ---- conditional group norm (MinkowskiConditionalGroupNorm): per-instance scale / shift and a fused SiLU -------------
+//   v = xhat * ge[b, c] + be[b, c], ge = gamma * (1 + scale[b]), be = beta * (1 + scale[b]) + shift[b], y = act(v)
+// The statistics are k_gn_partial / k_gn_chan_final / k_gn_group_final, unchanged.  The modulation is an affine map per
+// (instance, channel): k_gnc_coef writes ge / be [n_batch][c] into the workspace once per call and every later kernel
+// reads them where the plain kernels read gamma / beta — at a change of the batch index in the apply kernels, once per
+// (instance, piece) in the partial kernel — so the row loops gain two coefficient loads and no arithmetic on
+// gamma / beta / scale / shift.  With scale = shift = NULL and the identity, ge = gamma and be = beta bit for bit and
+// every expression below is the plain kernel's.
+//   k_gnc_coef         one thread per (instance, channel)
+//   k_gnc_apply        k_gn_apply's layout; SiLU in fp32, one rounding at a bf16 store
+//   k_gnc_bwd_partial  seg_bwd_partial with dv = dy * act'(v) in place of dy, v recomputed from x
+//   k_gnc_bwd_params   one thread per channel, ascending b: grad_shift = t1, grad_scale = gamma * t2 + beta * t1,
+//                      grad_beta = sum_b (1 + scale) * t1, grad_gamma = sum_b (1 + scale) * t2
+//   k_gnc_bwd_group    k_gn_bwd_group with ge[b, c] in place of gamma[c]
+//   k_gnc_bwd_apply    k_gn_bwd_apply's layout with ge and dv
+// Pass counts of group norm: x twice and y once forward; x and dy twice and dx once backward.  No atomics on values.
+enum { kGncIdentity = 0, kGncSilu = 1 };
+
+// SiLU and its derivative from one sigmoid: s = 1 / (1 + exp(-v)); exp overflows to inf for v < -88, s = 0, both finite
+template <typename F>
+__device__ __forceinline__ F gnc_sigmoid(F v) {
+  if constexpr (sizeof(F) == 4) return 1.f / (1.f + expf(-v));
+  else return 1.0 / (1.0 + exp(-v));
+}
+template <typename F>
+__device__ __forceinline__ F gnc_silu(F v) {
+  return v * gnc_sigmoid<F>(v);
+}
+template <typename F>
+__device__ __forceinline__ F gnc_silu_grad(F v) {
+  const F s = gnc_sigmoid<F>(v);
+  return s * ((F)1 + v * ((F)1 - s));
+}
+
+// ge / be [n_batch][c] (any of gamma / beta [c], scale / shift [n_batch][c] may be NULL: 1 / 0 / 0 / 0)
+template <typename F>
+__global__ __launch_bounds__(256) void k_gnc_coef(const F *__restrict__ gamma, const F *__restrict__ beta,
+                                                 const F *__restrict__ scale, const F *__restrict__ shift, int n_batch,
+                                                 int c, F *__restrict__ ge, F *__restrict__ be) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_batch * c) return;
+  const int ch = idx % c;
+  const F one = (F)1 + (scale != nullptr ? scale[idx] : (F)0);
+  ge[idx] = (gamma != nullptr ? gamma[ch] : (F)1) * one;
+  be[idx] = fma(beta != nullptr ? beta[ch] : (F)0, one, shift != nullptr ? shift[idx] : (F)0);
+}
+
+template <typename T, int V, int ACT>
+__global__ __launch_bounds__(256) void k_gnc_apply(const T *__restrict__ x, const int32_t *__restrict__ batch_row,
+                                                  int64_t n, int c, int n_batch, int groups,
+                                                  const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                  const float *__restrict__ ge, const float *__restrict__ be_,
+                                                  T *__restrict__ y) {
+  const int P = c / V;
+  const int W = min(P, (int)blockDim.x);
+  const int R = max(1, (int)blockDim.x / P);
+  const int rl = (int)threadIdx.x / W;
+  const int cg = c / groups;
+  const int64_t r0 = (int64_t)blockIdx.x * R * kBnRowsPerThread;
+  if (rl >= R) return;
+  for (int p = (int)threadIdx.x % W; p < P; p += W) {
+    Row<T, V> t[kBnRowsPerThread];
+    int bi[kBnRowsPerThread];
+#pragma unroll
+    for (int i = 0; i < kBnRowsPerThread; ++i) {
+      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
+      t[i] = load_row<T, V>(x + r * c + p * V);
+      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
+    }
+    float ga[V], be[V], a[V], mu[V];
+    int grp[V];
+    gn_piece_groups<V>(p * V, cg, grp);
+#pragma unroll
+    for (int i = 0; i < kBnRowsPerThread; ++i) {
+      const int64_t r = r0 + rl + (int64_t)i * R;
+      if (i == 0 || bi[i] != bi[i - 1]) {
+        load_f32<V>(ge + (int64_t)bi[i] * c + p * V, ga);
+        load_f32<V>(be_ + (int64_t)bi[i] * c + p * V, be);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const int o = bi[i] * groups + grp[j];
+          mu[j] = mean[o];
+          a[j] = rstd[o] * ga[j];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float v = fmaf(t[i].v[j] - mu[j], a[j], be[j]);
+        t[i].v[j] = ACT == kGncSilu ? gnc_silu<float>(v) : v;
+      }
+      if (r < n) store_row<T, V>(y + r * c + p * V, t[i]);
+    }
+  }
+}
+
+// dv = dy * act'(v), v = (x - mean) * (rstd * ge) + be as the apply kernel forms it; the product is rounded on its own so
+// that the partial and the apply kernel hold the same dv bit for bit
+template <int ACT>
+struct GncGrad {
+  const float *ge, *be;
+  int c;
+  template <int V>
+  struct State {
+    float a[V], be[V];
+  };
+  template <int V>
+  __device__ __forceinline__ void load(int b, int ch0, const float (&rs)[V], State<V> &st) const {
+    if constexpr (ACT == kGncSilu) {
+      float g[V];
+      load_f32<V>(ge + (int64_t)b * c + ch0, g);
+      load_f32<V>(be + (int64_t)b * c + ch0, st.be);
+#pragma unroll
+      for (int j = 0; j < V; ++j) st.a[j] = rs[j] * g[j];
+    }
+  }
+  template <int V>
+  __device__ __forceinline__ float operator()(const State<V> &st, int j, float xc, float g) const {
+    if constexpr (ACT == kGncSilu) return mul_rounded(g, gnc_silu_grad<float>(fmaf(xc, st.a[j], st.be[j])));
+    else return g;
+  }
+};
+
+template <typename T, int V, int ACT>
+__global__ __launch_bounds__(256) void k_gnc_bwd_partial(const T *__restrict__ x, const T *__restrict__ dy,
+                                                        const int32_t *__restrict__ batch_row, int64_t n, int c,
+                                                        int chunks, int n_batch, int groups,
+                                                        const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                        const float *__restrict__ ge, const float *__restrict__ be,
+                                                        float *__restrict__ part_dy, float *__restrict__ part_dyx,
+                                                        float *__restrict__ part_cnt) {
+  extern __shared__ float s_red[];  // in_partial_lds_bytes
+  seg_bwd_partial<T, V>(s_red, x, dy, batch_row, n, c, chunks, n_batch, GnCoef{mean, rstd, groups, c / groups}, part_dy,
+                        part_dyx, part_cnt, GncGrad<ACT>{ge, be, c});
+}
+
+// One thread per channel, the instances ascending.  Every requested word is written; an instance without rows on this
+// map has t1 = t2 = 0 (seg_bwd_final), so its rows of grad_scale / grad_shift are exactly 0.
+template <typename F>
+__global__ __launch_bounds__(256) void k_gnc_bwd_params(const F *__restrict__ t1, const F *__restrict__ t2,
+                                                       const F *__restrict__ gamma, const F *__restrict__ beta,
+                                                       const F *__restrict__ scale, int n_batch, int c,
+                                                       F *__restrict__ grad_gamma, F *__restrict__ grad_beta,
+                                                       F *__restrict__ grad_scale, F *__restrict__ grad_shift) {
+  const int ch = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ch >= c) return;
+  const F ga = gamma != nullptr ? gamma[ch] : (F)1, be = beta != nullptr ? beta[ch] : (F)0;
+  F a = 0, q = 0;
+  for (int b = 0; b < n_batch; ++b) {
+    const int64_t o = (int64_t)b * c + ch;
+    const F one = (F)1 + (scale != nullptr ? scale[o] : (F)0);
+    const F u1 = t1[o], u2 = t2[o];
+    a = fma(one, u1, a);
+    q = fma(one, u2, q);
+    if (grad_shift != nullptr) grad_shift[o] = u1;
+    if (grad_scale != nullptr) grad_scale[o] = fma(ga, u2, be * u1);
+  }
+  if (grad_beta != nullptr) grad_beta[ch] = a;
+  if (grad_gamma != nullptr) grad_gamma[ch] = q;
+}
+
+// One thread per (instance b, group g): T1 = sum_{c in g} ge[b, c] * t1[b, c], T2 likewise, ascending c
+template <typename F>
+__global__ __launch_bounds__(256) void k_gnc_bwd_group(const F *__restrict__ t1, const F *__restrict__ t2,
+                                                      const F *__restrict__ ge, int n_batch, int c, int groups,
+                                                      F *__restrict__ g1, F *__restrict__ g2) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // (b, g)
+  if (idx >= n_batch * groups) return;
+  const int b = idx / groups, g = idx % groups, cg = c / groups;
+  F a = 0, q = 0;
+  for (int k = 0; k < cg; ++k) {
+    const int64_t o = (int64_t)b * c + g * cg + k;
+    const F w = ge[o];
+    a = fma(w, t1[o], a);
+    q = fma(w, t2[o], q);
+  }
+  g1[idx] = a;
+  g2[idx] = q;
+}
+
+// dx = A * ((ge * dv - k1) - (x - mean[b, g]) * k2), k_gn_bwd_apply with ge[b, c] and dv = dy * act'(v).  ge * dv is
+// rounded on its own: a one-row instance with cg = 1 gets dx == 0 exactly.
+template <typename T, int V, int ACT>
+__global__ __launch_bounds__(256) void k_gnc_bwd_apply(const T *__restrict__ x, const T *__restrict__ dy,
+                                                      const int32_t *__restrict__ batch_row, int64_t n, int c,
+                                                      int n_batch, int groups, const float *__restrict__ mean,
+                                                      const float *__restrict__ rstd, const float *__restrict__ ge,
+                                                      const float *__restrict__ be_, const float *__restrict__ g1,
+                                                      const float *__restrict__ g2, const float *__restrict__ rows,
+                                                      T *__restrict__ dx) {
+  const int P = c / V;
+  const int W = min(P, (int)blockDim.x);
+  const int R = max(1, (int)blockDim.x / P);
+  const int rl = (int)threadIdx.x / W;
+  const int cg = c / groups;
+  constexpr int RB = kBnRowsPerThread;
+  const int64_t r0 = (int64_t)blockIdx.x * R * RB;
+  if (rl >= R) return;
+  for (int p = (int)threadIdx.x % W; p < P; p += W) {
+    Row<T, V> tx[RB], tg[RB];
+    int bi[RB];
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
+      tx[i] = load_row<T, V>(x + r * c + p * V);
+      tg[i] = load_row<T, V>(dy + r * c + p * V);
+      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
+    }
+    float ga[V], be[V], a[V], A[V], k1[V], k2[V], mu[V];
+    int grp[V];
+    gn_piece_groups<V>(p * V, cg, grp);
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+      const int64_t r = r0 + rl + (int64_t)i * R;
+      if (i == 0 || bi[i] != bi[i - 1]) {
+        const float inv_m = 1.f / fmaxf(rows[bi[i]] * (float)cg, 1.f);
+        load_f32<V>(ge + (int64_t)bi[i] * c + p * V, ga);
+        if (ACT == kGncSilu) load_f32<V>(be_ + (int64_t)bi[i] * c + p * V, be);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const int o = bi[i] * groups + grp[j];
+          mu[j] = mean[o];
+          A[j] = rstd[o];
+          a[j] = A[j] * ga[j];
+          k1[j] = g1[o] * inv_m;
+          k2[j] = g2[o] * inv_m * A[j];
+        }
+      }
+      Row<T, V> out;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float xc = tx[i].v[j] - mu[j];
+        float dv = tg[i].v[j];
+        if (ACT == kGncSilu) dv = mul_rounded(dv, gnc_silu_grad<float>(fmaf(xc, a[j], be[j])));
+        out.v[j] = A[j] * ((mul_rounded(ga[j], dv) - k1[j]) - xc * k2[j]);
+      }
+      if (r < n) store_row<T, V>(dx + r * c + p * V, out);
+    }
+  }
+}
+
+// ---- float64 twins: plain double, one thread per output -----------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_gnc_apply_f64(const double *__restrict__ x,
+                                                      const int32_t *__restrict__ batch_row, int64_t n, int c,
+                                                      int n_batch, int groups, const double *__restrict__ mean,
+                                                      const double *__restrict__ rstd, const double *__restrict__ gamma,
+                                                      const double *__restrict__ beta, const double *__restrict__ scale,
+                                                      const double *__restrict__ shift, int act,
+                                                      double *__restrict__ y) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * c) return;
+  const int ch = (int)(idx % c);
+  const int b = min(max(batch_row[idx / c], 0), n_batch - 1);
+  const int o = b * groups + ch / (c / groups);
+  const int64_t e = (int64_t)b * c + ch;
+  const double one = 1.0 + (scale ? scale[e] : 0.0);
+  const double ge = (gamma ? gamma[ch] : 1.0) * one, be = fma(beta ? beta[ch] : 0.0, one, shift ? shift[e] : 0.0);
+  const double v = fma((x[idx] - mean[o]) * rstd[o], ge, be);
+  y[idx] = act == kGncSilu ? gnc_silu<double>(v) : v;
+}
+
+// t1[b, c] = sum dv, t2[b, c] = sum dv * xhat, rows[b]
+__global__ __launch_bounds__(256) void k_gnc_bwd_sums_f64(const double *__restrict__ x, const double *__restrict__ dy,
+                                                         const int32_t *__restrict__ batch_row, int64_t n, int n_batch,
+                                                         int c, int groups, const double *__restrict__ mean,
+                                                         const double *__restrict__ rstd, const double *__restrict__ ge,
+                                                         const double *__restrict__ be, int act,
+                                                         double *__restrict__ t1, double *__restrict__ t2,
+                                                         double *__restrict__ rows) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)n_batch * c) return;
+  const int b = (int)(idx / c), ch = (int)(idx % c);
+  const double m = mean[b * groups + ch / (c / groups)], rs = rstd[b * groups + ch / (c / groups)];
+  const double w = ge[idx], o = be[idx];
+  double a = 0.0, q = 0.0, cnt = 0.0;
+  for (int64_t r = 0; r < n; ++r) {
+    if (batch_row[r] != b) continue;
+    const double xh = (x[r * c + ch] - m) * rs;
+    double g = dy[r * c + ch];
+    if (act == kGncSilu) g *= gnc_silu_grad<double>(fma(xh, w, o));
+    a += g;
+    q = fma(g, xh, q);
+    cnt += 1.0;
+  }
+  t1[idx] = a;
+  t2[idx] = q;
+  if (ch == 0) rows[b] = cnt;
+}
+
+__global__ __launch_bounds__(256) void k_gnc_bwd_apply_f64(const double *__restrict__ x, const double *__restrict__ dy,
+                                                          const int32_t *__restrict__ batch_row, int64_t n, int c,
+                                                          int n_batch, int groups, const double *__restrict__ mean,
+                                                          const double *__restrict__ rstd, const double *__restrict__ ge,
+                                                          const double *__restrict__ be, int act,
+                                                          const double *__restrict__ g1, const double *__restrict__ g2,
+                                                          const double *__restrict__ rows, double *__restrict__ dx) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * c) return;
+  const int ch = (int)(idx % c);
+  const int b = min(max(batch_row[idx / c], 0), n_batch - 1);
+  const int o = b * groups + ch / (c / groups);
+  const int64_t e = (int64_t)b * c + ch;
+  const double inv_m = 1.0 / fmax(rows[b] * (double)(c / groups), 1.0);
+  const double xh = (x[idx] - mean[o]) * rstd[o];
+  double dv = dy[idx];
+  if (act == kGncSilu) dv *= gnc_silu_grad<double>(fma(xh, ge[e], be[e]));
+  dx[idx] = rstd[o] * (ge[e] * dv - g1[o] * inv_m - xh * g2[o] * inv_m);
+}
+
+// ---- host side: the group-norm workspace, then ge | be [n_batch][c] (floats, or doubles for the _f64 entry points) ------
+struct GncWs {
+  GnWs w;
+  GnWs64 w64;
+  char *ge, *be;
+};
+static int64_t gnc_ws_layout(int64_t n, int n_batch, int c, int groups, char *base, GncWs *w) {
+  const int64_t gn = align_up(gn_ws_layout(n, n_batch, c, groups, base, w != nullptr ? &w->w : nullptr,
+                                           w != nullptr ? &w->w64 : nullptr), 256);
+  const int64_t co = align_up((int64_t)n_batch * c * 8, 256);
+  if (w != nullptr) {
+    w->ge = base + gn;
+    w->be = base + gn + co;
+  }
+  return gn + 2 * co;
+}
+
+#define ME_GNC_DISPATCH_ACT(act, ...)                               \
+  do {                                                              \
+    if ((act) == kGncSilu) { constexpr int ACT = kGncSilu; __VA_ARGS__; } \
+    else { constexpr int ACT = kGncIdentity; __VA_ARGS__; }         \
+  } while (0)
+
+template <typename F>
+static void gnc_coef(const F *gamma, const F *beta, const F *scale, const F *shift, int n_batch, int c, const GncWs &w,
+                     hipStream_t stream) {
+  hipLaunchKernelGGL(k_gnc_coef<F>, dim3((unsigned)ceil_div((int64_t)n_batch * c, 256)), dim3(256), 0, stream, gamma, beta,
+                     scale, shift, n_batch, c, reinterpret_cast<F *>(w.ge), reinterpret_cast<F *>(w.be));
+}
+
+template <typename T>
+static int gnc_apply(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups, const float *mean,
+                     const float *rstd, const float *gamma, const float *beta, const float *scale, const float *shift,
+                     int act, T *y, const GncWs &w, hipStream_t stream) {
+  const float *ge = reinterpret_cast<const float *>(w.ge), *be = reinterpret_cast<const float *>(w.be);
+  gnc_coef<float>(gamma, beta, scale, shift, n_batch, c, w, stream);
+  const int v = in_piece<T>(c, {x, y});
+  const int P = c / v;
+  const dim3 grid((unsigned)ceil_div(n, (int64_t)(P >= 256 ? 1 : 256 / P) * kBnRowsPerThread));
+  ME_GNC_DISPATCH_ACT(act, ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gnc_apply<T, V, ACT>), grid, dim3(256), 0, stream,
+                                                                     x, batch_row, n, c, n_batch, groups, mean, rstd, ge,
+                                                                     be, y)));
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
+static int gnc_backward(const T *x, const T *dy, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups,
+                        const float *mean, const float *rstd, const float *gamma, const float *beta, const float *scale,
+                        const float *shift, int act, T *dx, float *grad_gamma, float *grad_beta, float *grad_scale,
+                        float *grad_shift, const GncWs &ws, hipStream_t stream) {
+  const GnWs &w = ws.w;
+  const float *ge = reinterpret_cast<const float *>(ws.ge), *be = reinterpret_cast<const float *>(ws.be);
+  const int v = in_piece<T>(c, {x, dy, dx});
+  const int P = c / v;
+  const int R = P >= 256 ? 1 : 256 / P;
+  const int chunks = bn_chunks(n, R, kBnRowsPerThread / 2);
+  const size_t lds = in_partial_lds_bytes(c, R);
+  ME_CHECK(lds <= 64 * 1024, "channel count too large for the group-norm kernels");
+  ME_HIP(hipMemsetAsync(w.in.cnt, 0, (size_t)chunks * n_batch * 4, stream));
+  gnc_coef<float>(gamma, beta, scale, shift, n_batch, c, ws, stream);
+  ME_GNC_DISPATCH_ACT(act, ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gnc_bwd_partial<T, V, ACT>), dim3(chunks),
+                                                                     dim3(256), lds, stream, x, dy, batch_row, n, c,
+                                                                     chunks, n_batch, groups, mean, rstd, ge, be, w.in.pa,
+                                                                     w.in.pb, w.in.cnt)));
+  hipLaunchKernelGGL(k_gn_bwd_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.in.pa,
+                     w.in.pb, w.in.cnt, chunks, n_batch, c, w.in.t1, w.in.t2, w.in.rows);
+  if (grad_gamma != nullptr || grad_beta != nullptr || grad_scale != nullptr || grad_shift != nullptr)
+    hipLaunchKernelGGL(k_gnc_bwd_params<float>, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.in.t1, w.in.t2,
+                       gamma, beta, scale, n_batch, c, grad_gamma, grad_beta, grad_scale, grad_shift);
+  if (dx != nullptr) {
+    hipLaunchKernelGGL(k_gnc_bwd_group<float>, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0,
+                       stream, w.in.t1, w.in.t2, ge, n_batch, c, groups, w.g1, w.g2);
+    const dim3 grid((unsigned)ceil_div(n, (int64_t)R * kBnRowsPerThread));
+    ME_GNC_DISPATCH_ACT(act, ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gnc_bwd_apply<T, V, ACT>), grid, dim3(256), 0,
+                                                                       stream, x, dy, batch_row, n, c, n_batch, groups,
+                                                                       mean, rstd, ge, be, w.g1, w.g2, w.in.rows, dx)));
+  }
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace me
 
 using namespace me;
@@ -555,6 +945,97 @@ int me_gnorm_backward_f64(const double *x, const double *dy, const int32_t *batc
                        stream, w.t1, w.t2, gamma, n_batch, c, groups, w.g1, w.g2);
     hipLaunchKernelGGL(k_gn_bwd_apply_f64, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0, stream, x, dy, batch_row, n,
                        c, n_batch, groups, mean, rstd, gamma, w.g1, w.g2, w.rows, dx);
+  }
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- conditional group norm ---------------------------------------------------------------------------------------------
+#define ME_GNC_CHECK_ACT() ME_CHECK(act == kGncIdentity || act == kGncSilu, "conditional group norm: act must be 0 (identity) or 1 (SiLU)")
+
+int64_t me_gnorm_cond_workspace_bytes(int64_t n, int32_t n_batch, int32_t c, int32_t groups) {
+  if (n_batch <= 0 || c <= 0 || groups <= 0) return 0;
+  return gnc_ws_layout(n < 0 ? 0 : n, n_batch, c, groups, nullptr, nullptr);
+}
+
+int me_gnorm_cond_apply(const void *x, int32_t is_bf16, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c,
+                        int32_t groups, const float *mean, const float *rstd, const float *gamma, const float *beta,
+                        const float *scale, const float *shift, int32_t act, void *y, void *workspace,
+                        int64_t workspace_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_GN_CHECK_ARGS();
+  ME_GNC_CHECK_ACT();
+  ME_GN_CHECK_WIDTH();
+  ME_CHECK(workspace_bytes >= me_gnorm_cond_workspace_bytes(n, n_batch, c, groups), "workspace too small");
+  if (n == 0) return 0;
+  GncWs w;
+  gnc_ws_layout(n, n_batch, c, groups, reinterpret_cast<char *>(workspace), &w);
+  if (is_bf16)
+    return gnc_apply<__bf16>(reinterpret_cast<const __bf16 *>(x), batch_row, n, n_batch, c, groups, mean, rstd, gamma,
+                             beta, scale, shift, act, reinterpret_cast<__bf16 *>(y), w, stream);
+  return gnc_apply<float>(reinterpret_cast<const float *>(x), batch_row, n, n_batch, c, groups, mean, rstd, gamma, beta,
+                          scale, shift, act, reinterpret_cast<float *>(y), w, stream);
+}
+
+int me_gnorm_cond_backward(const void *x, const void *dy, int32_t is_bf16, const int32_t *batch_row, int64_t n,
+                           int32_t n_batch, int32_t c, int32_t groups, const float *mean, const float *rstd,
+                           const float *gamma, const float *beta, const float *scale, const float *shift, int32_t act,
+                           void *dx, float *grad_gamma, float *grad_beta, float *grad_scale, float *grad_shift,
+                           void *workspace, int64_t workspace_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_GN_CHECK_ARGS();
+  ME_GNC_CHECK_ACT();
+  ME_GN_CHECK_WIDTH();
+  ME_CHECK(n > 0, "group norm backward needs at least one row");
+  ME_CHECK(workspace_bytes >= me_gnorm_cond_workspace_bytes(n, n_batch, c, groups), "workspace too small");
+  GncWs w;
+  gnc_ws_layout(n, n_batch, c, groups, reinterpret_cast<char *>(workspace), &w);
+  if (is_bf16)
+    return gnc_backward<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), batch_row, n,
+                                n_batch, c, groups, mean, rstd, gamma, beta, scale, shift, act,
+                                reinterpret_cast<__bf16 *>(dx), grad_gamma, grad_beta, grad_scale, grad_shift, w, stream);
+  return gnc_backward<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), batch_row, n,
+                             n_batch, c, groups, mean, rstd, gamma, beta, scale, shift, act,
+                             reinterpret_cast<float *>(dx), grad_gamma, grad_beta, grad_scale, grad_shift, w, stream);
+}
+
+int me_gnorm_cond_apply_f64(const double *x, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c,
+                            int32_t groups, const double *mean, const double *rstd, const double *gamma,
+                            const double *beta, const double *scale, const double *shift, int32_t act, double *y,
+                            void *stream_) {
+  ME_GN_CHECK_ARGS();
+  ME_GNC_CHECK_ACT();
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_gnc_apply_f64, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0, (hipStream_t)stream_, x,
+                     batch_row, n, c, n_batch, groups, mean, rstd, gamma, beta, scale, shift, act, y);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+int me_gnorm_cond_backward_f64(const double *x, const double *dy, const int32_t *batch_row, int64_t n, int32_t n_batch,
+                               int32_t c, int32_t groups, const double *mean, const double *rstd, const double *gamma,
+                               const double *beta, const double *scale, const double *shift, int32_t act, double *dx,
+                               double *grad_gamma, double *grad_beta, double *grad_scale, double *grad_shift,
+                               void *workspace, int64_t workspace_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_GN_CHECK_ARGS();
+  ME_GNC_CHECK_ACT();
+  ME_CHECK(workspace_bytes >= me_gnorm_cond_workspace_bytes(n, n_batch, c, groups), "workspace too small");
+  GncWs ws;
+  gnc_ws_layout(n, n_batch, c, groups, reinterpret_cast<char *>(workspace), &ws);
+  const GnWs64 &w = ws.w64;
+  const double *ge = reinterpret_cast<const double *>(ws.ge), *be = reinterpret_cast<const double *>(ws.be);
+  gnc_coef<double>(gamma, beta, scale, shift, n_batch, c, ws, stream);
+  hipLaunchKernelGGL(k_gnc_bwd_sums_f64, dim3((unsigned)ceil_div((int64_t)n_batch * c, 256)), dim3(256), 0, stream, x, dy,
+                     batch_row, n, n_batch, c, groups, mean, rstd, ge, be, act, w.t1, w.t2, w.rows);
+  if (grad_gamma != nullptr || grad_beta != nullptr || grad_scale != nullptr || grad_shift != nullptr)
+    hipLaunchKernelGGL(k_gnc_bwd_params<double>, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.t1, w.t2,
+                       gamma, beta, scale, n_batch, c, grad_gamma, grad_beta, grad_scale, grad_shift);
+  if (dx != nullptr && n > 0) {
+    hipLaunchKernelGGL(k_gnc_bwd_group<double>, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0,
+                       stream, w.t1, w.t2, ge, n_batch, c, groups, w.g1, w.g2);
+    hipLaunchKernelGGL(k_gnc_bwd_apply_f64, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0, stream, x, dy, batch_row,
+                       n, c, n_batch, groups, mean, rstd, ge, be, act, w.g1, w.g2, w.rows, dx);
   }
   ME_LAUNCH_CHECK();
   return 0;

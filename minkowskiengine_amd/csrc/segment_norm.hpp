@@ -245,13 +245,28 @@ __device__ __forceinline__ bool seg_merge_chunks(const float *__restrict__ part_
   return true;
 }
 
+// the gradient that seg_bwd_partial sums is dy itself (instance norm, group norm)
+struct SegGradPlain {
+  template <int V>
+  struct State {};
+  template <int V>
+  __device__ __forceinline__ void load(int, int, const float (&)[V], State<V> &) const {}
+  template <int V>
+  __device__ __forceinline__ float operator()(const State<V> &, int, float, float g) const {
+    return g;
+  }
+};
+
 // per (chunk, instance, channel): sum dy and sum dy * xhat (xhat = (x - mean) * rstd); layout of seg_partial.
 // coef(b, ch0, m, rs) loads the mean and rstd of instance b for the V channels from ch0, once per (instance, piece).
-template <typename T, int V, typename Coef>
+// grad maps dy to the gradient that is summed (default: dy): grad.load(b, ch0, rs, st) fills its coefficients of
+// (instance, piece) next to mean and rstd, grad(st, j, x - mean, dy) is the value of element j.
+template <typename T, int V, typename Coef, typename Grad = SegGradPlain>
 __device__ __forceinline__ void seg_bwd_partial(float *s_red, const T *__restrict__ x, const T *__restrict__ dy,
                                                 const int32_t *__restrict__ batch_row, int64_t n, int c, int chunks,
                                                 int n_batch, const Coef &coef, float *__restrict__ part_dy,
-                                                float *__restrict__ part_dyx, float *__restrict__ part_cnt) {
+                                                float *__restrict__ part_dyx, float *__restrict__ part_cnt,
+                                                const Grad &grad = Grad()) {
   const int P = c / V;
   const int W = min(P, (int)blockDim.x);
   const int R = max(1, (int)blockDim.x / P);
@@ -282,6 +297,8 @@ __device__ __forceinline__ void seg_bwd_partial(float *s_red, const T *__restric
       if (active) {
         float m[V], rs[V];
         coef(b, p * V, m, rs);
+        typename Grad::template State<V> st;
+        grad.template load<V>(b, p * V, rs, st);
         for (int64_t rb = r0 + rl; rb < r1; rb += (int64_t)RB * R) {
           Row<T, V> tx[RB], tg[RB];
           int bi[RB];
@@ -298,7 +315,7 @@ __device__ __forceinline__ void seg_bwd_partial(float *s_red, const T *__restric
 #pragma unroll
             for (int j = 0; j < V; ++j) {
               const float xh = (tx[i].v[j] - m[j]) * rs[j];
-              const float g = take ? tg[i].v[j] : 0.f;
+              const float g = take ? grad(st, j, tx[i].v[j] - m[j], tg[i].v[j]) : 0.f;
               s1[j] += g;
               s2[j] = fmaf(g, take ? xh : 0.f, s2[j]);
             }

@@ -110,6 +110,12 @@ Tensor batch_norm_train(const Tensor &x, const py::object &skip, const py::objec
 }
 
 py::object opt_out(const Tensor &t) { return t.defined() ? py::cast(t) : py::none(); }
+// the activation of ConditionalGroupNorm{Forward,Backward}GPU: None -> 0 (identity), "silu" -> 1 (me_gnorm_cond_*'s act)
+int gnorm_cond_act(const py::object &o) {
+  if (o.is_none()) return 0;
+  if (py::isinstance<py::str>(o) && py::cast<std::string>(o) == "silu") return 1;
+  throw std::runtime_error("activation must be None or 'silu', not " + py::cast<std::string>(py::repr(o)));
+}
 
 // enums of pybind/extern.hpp:669-741
 enum GPUMemoryAllocatorType { PYTORCH = 0, CUDA = 1 };
@@ -570,6 +576,43 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("num_groups"), py::arg("weight"), py::arg("mean"),
         py::arg("rstd"), py::arg("in_key"), py::arg("glob_key"), py::arg("manager"), py::arg("need_grad_in") = true,
         py::arg("need_grad_weight") = true, py::arg("need_grad_bias") = true);
+  // conditional group normalisation: group norm with a per-instance scale / shift and an optional fused SiLU
+  // (activation: None or "silu"), on the k_gnc_* kernels of csrc/group_norm.hip
+  m.def("ConditionalGroupNormForwardGPU",
+        [](const Tensor &in_feat, int64_t num_groups, const py::object &weight, const py::object &bias,
+           const py::object &scale, const py::object &shift, const py::object &activation, double eps,
+           CoordinateMapKey *in_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+          const Tensor w = opt_tensor(weight), b = opt_tensor(bias), sc = opt_tensor(scale), sh = opt_tensor(shift);
+          const int act = gnorm_cond_act(activation);
+          std::tuple<Tensor, Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = cond_group_norm_forward(in_feat, num_groups, w, b, sc, sh, act, eps, in_key, glob_key, mgr);
+          }
+          return py::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r));
+        },
+        py::arg("in_feat"), py::arg("num_groups"), py::arg("weight"), py::arg("bias"), py::arg("scale"), py::arg("shift"),
+        py::arg("activation"), py::arg("eps"), py::arg("in_key"), py::arg("glob_key"), py::arg("manager"));
+  m.def("ConditionalGroupNormBackwardGPU",
+        [](const Tensor &in_feat, const Tensor &grad_out, int64_t num_groups, const py::object &weight,
+           const py::object &bias, const py::object &scale, const py::object &shift, const py::object &activation,
+           const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
+           CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_weight, bool need_grad_bias, bool need_grad_scale,
+           bool need_grad_shift) {
+          const Tensor w = opt_tensor(weight), b = opt_tensor(bias), sc = opt_tensor(scale), sh = opt_tensor(shift);
+          const int act = gnorm_cond_act(activation);
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = cond_group_norm_backward(in_feat, grad_out, num_groups, w, b, sc, sh, act, mean, rstd, in_key, glob_key, mgr,
+                                         need_grad_in, need_grad_weight, need_grad_bias, need_grad_scale, need_grad_shift);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]), opt_out(r[3]), opt_out(r[4]));
+        },
+        py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("num_groups"), py::arg("weight"), py::arg("bias"),
+        py::arg("scale"), py::arg("shift"), py::arg("activation"), py::arg("mean"), py::arg("rstd"), py::arg("in_key"),
+        py::arg("glob_key"), py::arg("manager"), py::arg("need_grad_in") = true, py::arg("need_grad_weight") = true,
+        py::arg("need_grad_bias") = true, py::arg("need_grad_scale") = true, py::arg("need_grad_shift") = true);
   // tensor fields (field.cpp): the reference's InterpolationForwardGPU / InterpolationBackwardGPU and coo_spmm_int32 /
   // coo_spmm_average_int32 (pybind/extern.hpp:497-506), plus the CSR building blocks the autograd functions cache
   m.def("CsrFromCooGPU",

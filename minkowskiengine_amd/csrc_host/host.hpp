@@ -367,6 +367,17 @@ std::tuple<Tensor, Tensor, Tensor> group_norm_backward(const Tensor &in_feat, Te
                                                        CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
                                                        CoordinateMapManager *mgr, bool need_grad_in,
                                                        bool need_grad_weight, bool need_grad_bias);
+// conditional group normalisation (csrc/group_norm.hip, k_gnc_*; twin of backend.ConditionalGroupNorm{Forward,Backward}GPU)
+std::tuple<Tensor, Tensor, Tensor> cond_group_norm_forward(const Tensor &in_feat, int64_t num_groups, const Tensor &weight,
+                                                           const Tensor &bias, const Tensor &scale, const Tensor &shift,
+                                                           int act, double eps, CoordinateMapKey *in_key,
+                                                           CoordinateMapKey *glob_key, CoordinateMapManager *mgr);
+std::vector<Tensor> cond_group_norm_backward(const Tensor &in_feat, Tensor grad_out, int64_t num_groups,
+                                             const Tensor &weight, const Tensor &bias, const Tensor &scale,
+                                             const Tensor &shift, int act, const Tensor &mean, const Tensor &rstd,
+                                             CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
+                                             CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_weight,
+                                             bool need_grad_bias, bool need_grad_scale, bool need_grad_shift);
 // dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU / DensePolicy)
 int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box);
 std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,

@@ -1161,6 +1161,109 @@ std::tuple<Tensor, Tensor, Tensor> group_norm_backward(const Tensor &in_feat, Te
   return {grad_in, grad_weight, grad_bias};
 }
 
+// ---- conditional group normalisation (csrc/group_norm.hip, k_gnc_*; twin of backend.ConditionalGroupNorm{Forward,Backward}GPU)
+static void gnorm_cond_check_mod(const char *name, const Tensor &t, const Tensor &in_feat, int64_t n_batch, int64_t c) {
+  const at::ScalarType want = in_feat.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
+  check(!t.defined() || (t.is_cuda() && t.is_contiguous() && t.scalar_type() == want && t.dim() == 2 &&
+                         t.size(0) == n_batch && t.size(1) == c && t.device() == in_feat.device()),
+        std::string(name) + " must be a contiguous GPU tensor of the parameter dtype (float64 for float64 features, float32 "
+                            "otherwise) of shape [" + std::to_string(n_batch) + ", " + std::to_string(c) +
+                            "] (one row per instance), on the device of the features");
+}
+
+std::tuple<Tensor, Tensor, Tensor> cond_group_norm_forward(const Tensor &in_feat, int64_t num_groups, const Tensor &weight,
+                                                           const Tensor &bias, const Tensor &scale, const Tensor &shift,
+                                                           int act, double eps, CoordinateMapKey *in_key,
+                                                           CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
+  const Tensor &rows = pr.first;
+  const int n_batch = (int)pr.second;
+  const int64_t n = in_feat.size(0);
+  const int c = (int)in_feat.size(1);
+  const int groups = gnorm_groups(num_groups, c);
+  inorm_check_vec("weight", weight, in_feat, c);
+  inorm_check_vec("bias", bias, in_feat, c);
+  gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c);
+  gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c);
+  const c10::Device dev = in_feat.device();
+  const bool f64 = in_feat.scalar_type() == at::kDouble;
+  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  Tensor out = at::empty_like(in_feat);
+  if (n == 0) return {out, at::zeros({n_batch, groups}, popt), at::full({n_batch, groups}, 1.0 / std::sqrt(eps), popt)};
+  Tensor mean = at::empty({n_batch, groups}, popt), rstd = at::empty({n_batch, groups}, popt);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_gnorm_stats_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, groups, eps, ptr<double>(mean),
+                             ptr<double>(rstd), stream_of(dev)));
+    me_ok(me_gnorm_cond_apply_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, groups, ptr<double>(mean),
+                                  ptr<double>(rstd), ptr<double>(weight), ptr<double>(bias), ptr<double>(scale),
+                                  ptr<double>(shift), act, ptr<double>(out), stream_of(dev)));
+    return {out, mean, rstd};
+  }
+  const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
+  Tensor ws = workspace(me_gnorm_cond_workspace_bytes(n, n_batch, c, groups), dev);
+  me_ok(me_gnorm_stats(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups, (float)eps, ptr<float>(mean),
+                       ptr<float>(rstd), vptr(ws), ws.numel(), stream_of(dev)));
+  me_ok(me_gnorm_cond_apply(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups, ptr<float>(mean),
+                            ptr<float>(rstd), ptr<float>(weight), ptr<float>(bias), ptr<float>(scale), ptr<float>(shift),
+                            act, out.data_ptr(), vptr(ws), ws.numel(), stream_of(dev)));
+  return {out, mean, rstd};
+}
+
+std::vector<Tensor> cond_group_norm_backward(const Tensor &in_feat, Tensor grad_out, int64_t num_groups,
+                                             const Tensor &weight, const Tensor &bias, const Tensor &scale,
+                                             const Tensor &shift, int act, const Tensor &mean, const Tensor &rstd,
+                                             CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
+                                             CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_weight,
+                                             bool need_grad_bias, bool need_grad_scale, bool need_grad_shift) {
+  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
+  const Tensor &rows = pr.first;
+  const int n_batch = (int)pr.second;
+  grad_out = grad_out.contiguous();
+  check_feat("grad_out_feat", grad_out);
+  if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
+  check(grad_out.sizes() == in_feat.sizes(), "grad_out_feat must have the shape of in_feat");
+  const int64_t n = in_feat.size(0);
+  const int c = (int)in_feat.size(1);
+  const int groups = gnorm_groups(num_groups, c);
+  inorm_check_vec("weight", weight, in_feat, c);
+  inorm_check_vec("bias", bias, in_feat, c);
+  gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c);
+  gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c);
+  check(mean.defined() && rstd.defined(), "conditional group norm backward needs mean and rstd");
+  inorm_check_vec("mean", mean, in_feat, (int64_t)n_batch * groups);
+  inorm_check_vec("rstd", rstd, in_feat, (int64_t)n_batch * groups);
+  const c10::Device dev = in_feat.device();
+  const bool f64 = in_feat.scalar_type() == at::kDouble;
+  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  Tensor grad_in = need_grad_in ? at::empty_like(in_feat) : Tensor();
+  Tensor grad_weight = need_grad_weight ? at::empty({c}, popt) : Tensor();
+  Tensor grad_bias = need_grad_bias ? at::empty({c}, popt) : Tensor();
+  Tensor grad_scale = need_grad_scale ? at::empty({n_batch, c}, popt) : Tensor();
+  Tensor grad_shift = need_grad_shift ? at::empty({n_batch, c}, popt) : Tensor();
+  if (n == 0) {
+    for (Tensor *g : {&grad_weight, &grad_bias, &grad_scale, &grad_shift})
+      if (g->defined()) g->zero_();
+    return {grad_in, grad_weight, grad_bias, grad_scale, grad_shift};
+  }
+  Tensor ws = workspace(me_gnorm_cond_workspace_bytes(n, n_batch, c, groups), dev);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_gnorm_cond_backward_f64(ptr<double>(in_feat), ptr<double>(grad_out), ptr<int32_t>(rows), n, n_batch, c, groups,
+                                     ptr<double>(mean), ptr<double>(rstd), ptr<double>(weight), ptr<double>(bias),
+                                     ptr<double>(scale), ptr<double>(shift), act, ptr<double>(grad_in),
+                                     ptr<double>(grad_weight), ptr<double>(grad_bias), ptr<double>(grad_scale),
+                                     ptr<double>(grad_shift), vptr(ws), ws.numel(), stream_of(dev)));
+  } else {
+    const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
+    me_ok(me_gnorm_cond_backward(in_feat.data_ptr(), grad_out.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups,
+                                 ptr<float>(mean), ptr<float>(rstd), ptr<float>(weight), ptr<float>(bias), ptr<float>(scale),
+                                 ptr<float>(shift), act, vptr(grad_in), ptr<float>(grad_weight), ptr<float>(grad_bias),
+                                 ptr<float>(grad_scale), ptr<float>(grad_shift), vptr(ws), ws.numel(), stream_of(dev)));
+  }
+  return {grad_in, grad_weight, grad_bias, grad_scale, grad_shift};
+}
+
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------
 Tensor pruning_forward(const Tensor &in_feat, const Tensor &keep, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr) {

@@ -17,7 +17,14 @@ pass counts: per instance b and group g of C / num_groups consecutive channels
     out[i, c] = (x[i, c] - mean[b_i, g_c]) / sqrt(var[b_i, g_c] + eps) * weight[c] + bias[c]
 
 with mean / var over the n_b rows of the instance and the channels of the group — torch.nn.functional.group_norm applied
-to every instance's [1, C, n_b] tensor on its own."""
+to every instance's [1, C, n_b] tensor on its own.
+
+MinkowskiConditionalGroupNorm and MinkowskiConditionalGroupNormFunction (AdaGN / FiLM) run
+`ConditionalGroupNorm{Forward,Backward}GPU` on the k_gnc_* kernels of the same file, again with the same pass counts:
+
+    out[i, c] = act(group_norm(x)[i, c] * (1 + scale[b_i, c]) + shift[b_i, c]),        act: identity or SiLU
+
+with one row of scale / shift per instance."""
 import torch
 from torch.autograd import Function
 from torch.nn import Parameter
@@ -209,4 +216,104 @@ class MinkowskiGroupNorm(MinkowskiModuleBase):
         assert input.shape[1] == self.num_channels, f"Channel size mismatch {self.num_channels} != {input.shape[1]}"
         output = MinkowskiGroupNormFunction.apply(input.F, self.num_groups, self.weight, self.bias, self.eps,
                                                   input.coordinate_map_key, None, input._manager)
+        return SparseTensor(output, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
+
+
+class MinkowskiConditionalGroupNormFunction(Function):
+    """Group normalisation of the feature rows of a coordinate map, every instance (batch index) on its own, modulated per
+    instance and channel and followed by an optional SiLU: act(gn(x) * (1 + scale[b]) + shift[b]).  weight / bias: (C,)
+    tensors of the parameter dtype (fp32 for fp32 and bf16 features, float64 for float64) or None; scale / shift:
+    (instances, C) tensors of the parameter dtype or None, row j for row j of the origin map, that is for the j-th
+    smallest batch index (the batch index itself when the indices are 0..B-1); activation: None or "silu"."""
+
+    @staticmethod
+    def forward(ctx, in_feat, num_groups, weight, bias, scale, shift, activation, eps, in_coords_key,
+                glob_coords_key=None, coords_manager=None):
+        if glob_coords_key is None:
+            glob_coords_key = _host.key_like(in_coords_key)
+        in_feat = in_feat.contiguous()
+        w = None if weight is None else weight.detach().reshape(-1).contiguous()
+        b = None if bias is None else bias.detach().reshape(-1).contiguous()
+        sc = None if scale is None else scale.detach().contiguous()
+        sh = None if shift is None else shift.detach().contiguous()
+        fw_fn = get_minkowski_function("ConditionalGroupNormForward", in_feat, in_coords_key)
+        out, mean, rstd = fw_fn(in_feat, int(num_groups), w, b, sc, sh, activation, float(eps), in_coords_key,
+                                glob_coords_key, coords_manager._manager)
+        ctx.save_for_backward(in_feat, w, b, sc, sh, mean, rstd)
+        ctx.misc = (int(num_groups), activation, in_coords_key, glob_coords_key, coords_manager,
+                    None if weight is None else weight.shape, None if bias is None else bias.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        in_feat, w, b, sc, sh, mean, rstd = ctx.saved_tensors
+        num_groups, activation, in_key, glob_key, coords_manager, w_shape, b_shape = ctx.misc
+        need_w = w_shape is not None and ctx.needs_input_grad[2]
+        need_b = b_shape is not None and ctx.needs_input_grad[3]
+        need_sc = sc is not None and ctx.needs_input_grad[4]
+        need_sh = sh is not None and ctx.needs_input_grad[5]
+        bw_fn = get_minkowski_function("ConditionalGroupNormBackward", grad_out, in_key)
+        grad_in, grad_w, grad_b, grad_sc, grad_sh = bw_fn(
+            in_feat, grad_out.contiguous(), num_groups, w, b, sc, sh, activation, mean, rstd, in_key, glob_key,
+            coords_manager._manager, need_grad_in=ctx.needs_input_grad[0], need_grad_weight=need_w, need_grad_bias=need_b,
+            need_grad_scale=need_sc, need_grad_shift=need_sh)
+        return (grad_in, None, grad_w.view(w_shape) if need_w else None, grad_b.view(b_shape) if need_b else None,
+                grad_sc if need_sc else None, grad_sh if need_sh else None, None, None, None, None, None)
+
+
+_GNC_ACTIVATIONS = (None, "silu")
+
+
+class MinkowskiConditionalGroupNorm(MinkowskiModuleBase):
+    r"""MinkowskiGroupNorm modulated per instance (AdaGN / FiLM) with an optional fused SiLU, in the passes over the
+    feature matrix of the plain layer:
+
+        out = act(group_norm(x) * (1 + scale[b]) + shift[b])
+
+    `forward(input, scale=None, shift=None)`: scale / shift of shape (instances, num_channels) hold one row per instance —
+    row j belongs to row j of the origin map, that is to the j-th smallest batch index of the tensor; with batch indices
+    0..B-1 it is the batch index itself.  They are converted to the parameter dtype with `.to()`, so their gradients
+    flow back in the caller's dtype (for example to a bf16 `torch.nn.Linear` on a timestep embedding).  `activation`:
+    None or "silu".  Parameters `weight`, `bias` of shape (num_channels,), fp32, as torch.nn.GroupNorm's, so state dicts
+    move between the two strictly; `affine=False` registers both as None.  The gradients of scale and shift are
+    fixed-order sums (no atomics), bitwise reproducible."""
+
+    def __init__(self, num_groups, num_channels, eps=1e-5, affine=True, activation=None):
+        super().__init__()
+        if num_channels % num_groups != 0:
+            raise ValueError("num_channels must be divisible by num_groups")
+        if activation not in _GNC_ACTIVATIONS:
+            raise ValueError(f"activation must be None or 'silu', not {activation!r}")
+        self.num_groups = num_groups
+        self.num_channels = num_channels
+        self.eps = eps
+        self.affine = affine
+        self.activation = activation
+        if affine:
+            self.weight = Parameter(torch.ones(num_channels, dtype=torch.float32))
+            self.bias = Parameter(torch.zeros(num_channels, dtype=torch.float32))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def __repr__(self):
+        return (self.__class__.__name__ + f"({self.num_groups}, {self.num_channels}, eps={self.eps}, "
+                f"affine={self.affine}, activation={self.activation!r})")
+
+    def reset_parameters(self):
+        if self.affine:
+            with torch.no_grad():
+                self.weight.fill_(1)
+                self.bias.zero_()
+
+    def forward(self, input, scale=None, shift=None):
+        assert isinstance(input, SparseTensor)
+        assert input.shape[1] == self.num_channels, f"Channel size mismatch {self.num_channels} != {input.shape[1]}"
+        pd = self.weight.dtype if self.affine else (torch.float64 if input.F.dtype == torch.float64 else torch.float32)
+        scale = None if scale is None else scale.to(pd)
+        shift = None if shift is None else shift.to(pd)
+        output = MinkowskiConditionalGroupNormFunction.apply(
+            input.F, self.num_groups, self.weight, self.bias, scale, shift, self.activation, self.eps,
+            input.coordinate_map_key, None, input._manager)
         return SparseTensor(output, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)

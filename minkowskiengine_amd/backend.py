@@ -3214,6 +3214,24 @@ def _inorm_prepare(in_feat, in_key, glob_key, manager):
     return rows, manager.size(glob_key)
 
 
+def _norm_backward_prepare(in_feat, grad_out_feat, in_key, glob_key, manager, need_grad_in, need_grad_weight,
+                           need_grad_bias):
+    """The shared opening of the norm backward operators -> (batch_row, n_batch, grad_out_feat contiguous and in the dtype
+    of in_feat, grad_in | None, grad_weight [C] | None, grad_bias [C] | None), the gradients allocated, not yet written."""
+    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
+    if not grad_out_feat.is_contiguous():
+        grad_out_feat = grad_out_feat.contiguous()
+    _check_feat("grad_out_feat", grad_out_feat)
+    if grad_out_feat.dtype != in_feat.dtype:
+        grad_out_feat = grad_out_feat.to(in_feat.dtype)
+    _check(tuple(grad_out_feat.shape) == tuple(in_feat.shape), "grad_out_feat must have the shape of in_feat")
+    c, dev, pd = int(in_feat.shape[1]), in_feat.device, _inorm_param_dtype(in_feat)
+    grad_in = torch.empty_like(in_feat) if need_grad_in else None
+    grad_weight = torch.empty(c, dtype=pd, device=dev) if need_grad_weight else None
+    grad_bias = torch.empty(c, dtype=pd, device=dev) if need_grad_bias else None
+    return rows, n_batch, grad_out_feat, grad_in, grad_weight, grad_bias
+
+
 def InstanceNormForwardGPU(in_feat, weight, bias, eps, in_key, glob_key, manager):
     """-> (out_feat, mean, rstd): out[i] = (x[i] - mean[b_i]) * rstd[b_i] * weight + bias with the mean and the biased
     variance of every instance (batch index) per channel, rstd = 1 / sqrt(var + eps); mean / rstd: [batch, C] in the
@@ -3250,13 +3268,8 @@ def InstanceNormBackwardGPU(in_feat, grad_out_feat, weight, mean, rstd, in_key, 
                             need_grad_weight=True, need_grad_bias=True):
     """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None) from the statistics of the forward pass; the
     parameter gradients have the parameter dtype (fp32 for bf16 features)."""
-    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
-    if not grad_out_feat.is_contiguous():
-        grad_out_feat = grad_out_feat.contiguous()
-    _check_feat("grad_out_feat", grad_out_feat)
-    if grad_out_feat.dtype != in_feat.dtype:
-        grad_out_feat = grad_out_feat.to(in_feat.dtype)
-    _check(tuple(grad_out_feat.shape) == tuple(in_feat.shape), "grad_out_feat must have the shape of in_feat")
+    rows, n_batch, grad_out_feat, grad_in, grad_weight, grad_bias = _norm_backward_prepare(
+        in_feat, grad_out_feat, in_key, glob_key, manager, need_grad_in, need_grad_weight, need_grad_bias)
     n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
     _inorm_check_vec("weight", weight, in_feat, c)
     _check(mean is not None and rstd is not None, "instance norm backward needs mean and rstd")
@@ -3264,10 +3277,6 @@ def InstanceNormBackwardGPU(in_feat, grad_out_feat, weight, mean, rstd, in_key, 
     _inorm_check_vec("rstd", rstd, in_feat, n_batch * c)
     lib = _lib.load()
     dev = in_feat.device
-    pd = _inorm_param_dtype(in_feat)
-    grad_in = torch.empty_like(in_feat) if need_grad_in else None
-    grad_weight = torch.empty(c, dtype=pd, device=dev) if need_grad_weight else None
-    grad_bias = torch.empty(c, dtype=pd, device=dev) if need_grad_bias else None
     if n == 0:
         return grad_in, (None if grad_weight is None else grad_weight.zero_()), \
             (None if grad_bias is None else grad_bias.zero_())
@@ -3332,13 +3341,8 @@ def GroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, mean, rstd,
                          need_grad_in=True, need_grad_weight=True, need_grad_bias=True):
     """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None) from the statistics of the forward pass; the
     parameter gradients have the parameter dtype (fp32 for bf16 features)."""
-    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
-    if not grad_out_feat.is_contiguous():
-        grad_out_feat = grad_out_feat.contiguous()
-    _check_feat("grad_out_feat", grad_out_feat)
-    if grad_out_feat.dtype != in_feat.dtype:
-        grad_out_feat = grad_out_feat.to(in_feat.dtype)
-    _check(tuple(grad_out_feat.shape) == tuple(in_feat.shape), "grad_out_feat must have the shape of in_feat")
+    rows, n_batch, grad_out_feat, grad_in, grad_weight, grad_bias = _norm_backward_prepare(
+        in_feat, grad_out_feat, in_key, glob_key, manager, need_grad_in, need_grad_weight, need_grad_bias)
     n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
     groups = _gnorm_groups(num_groups, c)
     _inorm_check_vec("weight", weight, in_feat, c)
@@ -3347,10 +3351,6 @@ def GroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, mean, rstd,
     _inorm_check_vec("rstd", rstd, in_feat, n_batch * groups)
     lib = _lib.load()
     dev = in_feat.device
-    pd = _inorm_param_dtype(in_feat)
-    grad_in = torch.empty_like(in_feat) if need_grad_in else None
-    grad_weight = torch.empty(c, dtype=pd, device=dev) if need_grad_weight else None
-    grad_bias = torch.empty(c, dtype=pd, device=dev) if need_grad_bias else None
     if n == 0:
         return grad_in, (None if grad_weight is None else grad_weight.zero_()), \
             (None if grad_bias is None else grad_bias.zero_())
@@ -3435,13 +3435,8 @@ def ConditionalGroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, 
     """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None, grad_scale [batch, C] | None, grad_shift
     [batch, C] | None) from the statistics of the forward pass, in the parameter dtype (fp32 for bf16 features).  The rows
     of grad_scale / grad_shift of an instance without rows on this map are 0."""
-    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
-    if not grad_out_feat.is_contiguous():
-        grad_out_feat = grad_out_feat.contiguous()
-    _check_feat("grad_out_feat", grad_out_feat)
-    if grad_out_feat.dtype != in_feat.dtype:
-        grad_out_feat = grad_out_feat.to(in_feat.dtype)
-    _check(tuple(grad_out_feat.shape) == tuple(in_feat.shape), "grad_out_feat must have the shape of in_feat")
+    rows, n_batch, grad_out_feat, grad_in, grad_weight, grad_bias = _norm_backward_prepare(
+        in_feat, grad_out_feat, in_key, glob_key, manager, need_grad_in, need_grad_weight, need_grad_bias)
     n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
     groups = _gnorm_groups(num_groups, c)
     act = _gnorm_cond_act(activation)
@@ -3455,9 +3450,6 @@ def ConditionalGroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, 
     lib = _lib.load()
     dev = in_feat.device
     pd = _inorm_param_dtype(in_feat)
-    grad_in = torch.empty_like(in_feat) if need_grad_in else None
-    grad_weight = torch.empty(c, dtype=pd, device=dev) if need_grad_weight else None
-    grad_bias = torch.empty(c, dtype=pd, device=dev) if need_grad_bias else None
     grad_scale = torch.empty((n_batch, c), dtype=pd, device=dev) if need_grad_scale else None
     grad_shift = torch.empty((n_batch, c), dtype=pd, device=dev) if need_grad_shift else None
     if n == 0:

@@ -11,15 +11,19 @@
 //               k_gn_group_final  one thread per (instance, group): the cg channel records in ascending channel order.
 //                                 Their counts are equal, so mean_g is the mean of the mean_c (taken relative to the first
 //                                 one) and M2_g = sum M2_c + n_b * sum (mean_c - mean_g)^2 -> mean, rstd [n_batch, groups]
-//   forward     k_gn_apply        y = (x - mean[b, g]) * rstd[b, g] * gamma + beta.  A thread owns a 16-byte channel piece,
-//                                 which may straddle groups (cg = 3 with 4 floats, cg = 6 with 8 bf16): the group of every
-//                                 element of the piece is computed once, outside the row loop; the coefficients of an
-//                                 instance are re-read only when the batch index changes between two rows of the thread
+//   forward     k_seg_rows<GnFwd> y = (x - mean[b, g]) * rstd[b, g] * gamma + beta: the row tile seg_rows of
+//                                 segment_norm.hpp with the map GnFwd.  A thread owns a 16-byte channel piece, which may
+//                                 straddle groups (cg = 3 with 4 floats, cg = 6 with 8 bf16): the group of every element
+//                                 of the piece is computed once, outside the row loop; the coefficients of an instance
+//                                 are re-read only when the batch index changes between two rows of the thread
 //   backward    k_gn_bwd_partial / k_gn_bwd_final   t1[b, c] = sum dy, t2[b, c] = sum dy * xhat (seg_bwd_partial with the
 //                                 group's mean / rstd)
-//               k_gn_bwd_params   grad_beta = sum_b t1, grad_gamma = sum_b t2 (ascending b)
+//               k_gnc_bwd_params  grad_beta = sum_b t1, grad_gamma = sum_b t2 (ascending b): the conditional norm's kernel
+//                                 without modulation
 //               k_gn_bwd_group    T1[b, g] = sum_{c in g} gamma[c] * t1[b, c], T2 likewise (ascending c)
-//               k_gn_bwd_apply    dx = rstd * (gamma * dy - T1 / m - xhat * T2 / m), m = n_b * cg
+//               k_seg_rows<GnBwd> dx = rstd * (gamma * dy - T1 / m - xhat * T2 / m), m = n_b * cg
+// The maps are templated on the source of the affine map (GnPerChannel: gamma / beta here; GnPerInstance: the conditional
+// norm below) and on the activation; both norms share every kernel but k_gnc_coef.
 // x is read twice and y written once forward; x and dy are read twice and dx written once backward, as instance norm.
 // No atomics on values, every sum in a fixed order: bitwise reproducible.  T = float or __bf16 rows; statistics and
 // parameters fp32.  The float64 twins at the end are the gradcheck yardstick (plain double, one thread per output).
@@ -100,53 +104,6 @@ __device__ __forceinline__ void gn_piece_groups(int ch0, int cg, int (&grp)[V]) 
   for (int j = 0; j < V; ++j) grp[j] = (ch0 + j) / cg;
 }
 
-// y = (x - mean[b, g]) * (rstd[b, g] * gamma) + beta, b = batch_row[row] clamped (gamma / beta may be NULL: 1 / 0).
-// k_in_apply's layout: all row loads of a thread first, unconditionally (rows clamped to the matrix), only the stores
-// predicated.  mean / rstd are read element by element ([n_batch, groups] floats, L2-resident, no alignment asked of them).
-template <typename T, int V>
-__global__ __launch_bounds__(256) void k_gn_apply(const T *__restrict__ x, const int32_t *__restrict__ batch_row,
-                                                 int64_t n, int c, int n_batch, int groups,
-                                                 const float *__restrict__ mean, const float *__restrict__ rstd,
-                                                 const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                 T *__restrict__ y) {
-  const int P = c / V;
-  const int W = min(P, (int)blockDim.x);
-  const int R = max(1, (int)blockDim.x / P);
-  const int rl = (int)threadIdx.x / W;
-  const int cg = c / groups;
-  const int64_t r0 = (int64_t)blockIdx.x * R * kBnRowsPerThread;
-  if (rl >= R) return;
-  for (int p = (int)threadIdx.x % W; p < P; p += W) {
-    Row<T, V> t[kBnRowsPerThread];
-    int bi[kBnRowsPerThread];
-#pragma unroll
-    for (int i = 0; i < kBnRowsPerThread; ++i) {
-      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
-      t[i] = load_row<T, V>(x + r * c + p * V);
-      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
-    }
-    float ga[V], be[V], a[V], mu[V];
-    int grp[V];
-    load_affine<V>(gamma, beta, p * V, ga, be);
-    gn_piece_groups<V>(p * V, cg, grp);
-#pragma unroll
-    for (int i = 0; i < kBnRowsPerThread; ++i) {
-      const int64_t r = r0 + rl + (int64_t)i * R;
-      if (i == 0 || bi[i] != bi[i - 1]) {
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-          const int o = bi[i] * groups + grp[j];
-          mu[j] = mean[o];
-          a[j] = rstd[o] * ga[j];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < V; ++j) t[i].v[j] = fmaf(t[i].v[j] - mu[j], a[j], be[j]);
-      if (r < n) store_row<T, V>(y + r * c + p * V, t[i]);
-    }
-  }
-}
-
 // mean / rstd [n_batch][groups] of instance b for the V channels from ch0
 struct GnCoef {
   const float *mean, *rstd;
@@ -163,17 +120,17 @@ struct GnCoef {
   }
 };
 
-// per (chunk, instance, channel): sum dy and sum dy * xhat with xhat = (x - mean[b, g]) * rstd[b, g]
-template <typename T, int V>
+// per (chunk, instance, channel): sum g and sum g * xhat with xhat = (x - mean[b, g]) * rstd[b, g] and g the gradient
+// that Grad makes of dy: SegGradPlain (dy itself) for the plain and the conditional norm without activation, GncGrad with
+// the SiLU
+template <typename T, int V, typename Grad>
 __global__ __launch_bounds__(256) void k_gn_bwd_partial(const T *__restrict__ x, const T *__restrict__ dy,
                                                        const int32_t *__restrict__ batch_row, int64_t n, int c,
-                                                       int chunks, int n_batch, int groups,
-                                                       const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                       int chunks, int n_batch, const GnCoef coef, const Grad grad,
                                                        float *__restrict__ part_dy, float *__restrict__ part_dyx,
                                                        float *__restrict__ part_cnt) {
   extern __shared__ float s_red[];  // in_partial_lds_bytes
-  seg_bwd_partial<T, V>(s_red, x, dy, batch_row, n, c, chunks, n_batch, GnCoef{mean, rstd, groups, c / groups}, part_dy,
-                        part_dyx, part_cnt);
+  seg_bwd_partial<T, V>(s_red, x, dy, batch_row, n, c, chunks, n_batch, coef, part_dy, part_dyx, part_cnt, grad);
 }
 
 // t1 = sum dy, t2 = sum dy * xhat per (instance, channel) and rows[b]: one wave each over the chunks, a fixed order
@@ -185,28 +142,21 @@ __global__ __launch_bounds__(256) void k_gn_bwd_final(const float *__restrict__ 
   seg_bwd_final(part_dy, part_dyx, part_cnt, chunks, n_batch, c, t1, t2, rows);
 }
 
-// grad_beta = sum over the instances (ascending) of t1, grad_gamma = of t2; either may be NULL
-template <typename F>
-__global__ __launch_bounds__(256) void k_gn_bwd_params(const F *__restrict__ t1, const F *__restrict__ t2, int n_batch,
-                                                      int c, F *__restrict__ grad_gamma, F *__restrict__ grad_beta) {
-  seg_bwd_params<F>(t1, t2, n_batch, c, grad_gamma, grad_beta);
-}
-
-// One thread per (instance b, group g): T1 = sum_{c in g} gamma[c] * t1[b, c], T2 = the same of t2, ascending c
-// (gamma may be NULL: 1)
+// One thread per (instance b, group g): T1 = sum_{c in g} w[b, c] * t1[b, c], T2 = the same of t2, ascending c.  The
+// weight of (b, c) is w[b * w_stride + c]: w_stride = 0 for gamma[c], c for ge[b, c]; w may be NULL: 1
 template <typename F>
 __global__ __launch_bounds__(256) void k_gn_bwd_group(const F *__restrict__ t1, const F *__restrict__ t2,
-                                                     const F *__restrict__ gamma, int n_batch, int c, int groups,
-                                                     F *__restrict__ g1, F *__restrict__ g2) {
+                                                     const F *__restrict__ w, int w_stride, int n_batch, int c,
+                                                     int groups, F *__restrict__ g1, F *__restrict__ g2) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // (b, g)
   if (idx >= n_batch * groups) return;
   const int b = idx / groups, g = idx % groups, cg = c / groups;
   F a = 0, q = 0;
   for (int k = 0; k < cg; ++k) {
     const int ch = g * cg + k;
-    const F w = gamma != nullptr ? gamma[ch] : (F)1;
-    a = fma(w, t1[(int64_t)b * c + ch], a);
-    q = fma(w, t2[(int64_t)b * c + ch], q);
+    const F wt = w != nullptr ? w[(int64_t)b * w_stride + ch] : (F)1;
+    a = fma(wt, t1[(int64_t)b * c + ch], a);
+    q = fma(wt, t2[(int64_t)b * c + ch], q);
   }
   g1[idx] = a;
   g2[idx] = q;
@@ -216,61 +166,6 @@ __global__ __launch_bounds__(256) void k_gn_bwd_group(const F *__restrict__ t1, 
 __device__ __forceinline__ float mul_rounded(float a, float b) {
 #pragma clang fp contract(off)
   return a * b;
-}
-
-// dx = A * ((gamma * dy - k1) - (x - mean[b, g]) * k2) with A = rstd[b, g], k1 = T1[b, g] / m, k2 = T2[b, g] / m * A,
-// m = n_b * cg (layout and coefficient reuse of k_gn_apply).  gamma * dy is rounded on its own: with one value per
-// (instance, group) it equals k1 bit for bit and dx is exactly 0, which a contraction into one fma would lose.
-template <typename T, int V>
-__global__ __launch_bounds__(256) void k_gn_bwd_apply(const T *__restrict__ x, const T *__restrict__ dy,
-                                                     const int32_t *__restrict__ batch_row, int64_t n, int c,
-                                                     int n_batch, int groups, const float *__restrict__ mean,
-                                                     const float *__restrict__ rstd, const float *__restrict__ gamma,
-                                                     const float *__restrict__ g1, const float *__restrict__ g2,
-                                                     const float *__restrict__ rows, T *__restrict__ dx) {
-  const int P = c / V;
-  const int W = min(P, (int)blockDim.x);
-  const int R = max(1, (int)blockDim.x / P);
-  const int rl = (int)threadIdx.x / W;
-  const int cg = c / groups;
-  constexpr int RB = kBnRowsPerThread;
-  const int64_t r0 = (int64_t)blockIdx.x * R * RB;
-  if (rl >= R) return;
-  for (int p = (int)threadIdx.x % W; p < P; p += W) {
-    Row<T, V> tx[RB], tg[RB];
-    int bi[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
-      tx[i] = load_row<T, V>(x + r * c + p * V);
-      tg[i] = load_row<T, V>(dy + r * c + p * V);
-      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
-    }
-    float ga[V], unused[V], A[V], k1[V], k2[V], mu[V];
-    int grp[V];
-    load_affine<V>(gamma, nullptr, p * V, ga, unused);
-    gn_piece_groups<V>(p * V, cg, grp);
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-      const int64_t r = r0 + rl + (int64_t)i * R;
-      if (i == 0 || bi[i] != bi[i - 1]) {
-        const float inv_m = 1.f / fmaxf(rows[bi[i]] * (float)cg, 1.f);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-          const int o = bi[i] * groups + grp[j];
-          mu[j] = mean[o];
-          A[j] = rstd[o];
-          k1[j] = g1[o] * inv_m;
-          k2[j] = g2[o] * inv_m * A[j];
-        }
-      }
-      Row<T, V> out;
-#pragma unroll
-      for (int j = 0; j < V; ++j)
-        out.v[j] = A[j] * ((mul_rounded(ga[j], tg[i].v[j]) - k1[j]) - (tx[i].v[j] - mu[j]) * k2[j]);
-      if (r < n) store_row<T, V>(dx + r * c + p * V, out);
-    }
-  }
 }
 
 // ---- float64: the same formulae in plain double, one thread per output (gradcheck yardstick, not a hot path) ----------
@@ -299,19 +194,6 @@ __global__ __launch_bounds__(256) void k_gn_stats_f64(const double *__restrict__
   }
   mean[idx] = m;
   rstd[idx] = 1.0 / sqrt((cnt > 0.0 ? q / cnt : 0.0) + eps);
-}
-
-__global__ __launch_bounds__(256) void k_gn_apply_f64(const double *__restrict__ x,
-                                                     const int32_t *__restrict__ batch_row, int64_t n, int c,
-                                                     int n_batch, int groups, const double *__restrict__ mean,
-                                                     const double *__restrict__ rstd, const double *__restrict__ gamma,
-                                                     const double *__restrict__ beta, double *__restrict__ y) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n * c) return;
-  const int ch = (int)(idx % c);
-  const int o = min(max(batch_row[idx / c], 0), n_batch - 1) * groups + ch / (c / groups);
-  const double v = (x[idx] - mean[o]) * rstd[o];
-  y[idx] = fma(v, gamma ? gamma[ch] : 1.0, beta ? beta[ch] : 0.0);
 }
 
 // t1[b, c] = sum dy, t2[b, c] = sum dy * xhat, rows[b]
@@ -354,114 +236,21 @@ __global__ __launch_bounds__(256) void k_gn_bwd_apply_f64(const double *__restri
   dx[idx] = rstd[o] * ((gamma ? gamma[ch] : 1.0) * dy[idx] - g1[o] * inv_m - xh * g2[o] * inv_m);
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------
-// workspace: in_ws_layout_f32 | g1 | g2 [n_batch][groups] floats.  The statistics keep the channel records in t1 / t2.
-// float64: t1 | t2 [n_batch][c] | rows [n_batch] | g1 | g2 [n_batch][groups] doubles.  Every piece 256-byte aligned.
-struct GnWs {
-  InWs in;
-  float *g1, *g2;
-};
-struct GnWs64 {
-  double *t1, *t2, *rows, *g1, *g2;
-};
-static int64_t gn_ws_layout(int64_t n, int n_batch, int c, int groups, char *base, GnWs *w, GnWs64 *w64) {
-  const int64_t in32 = in_ws_layout_f32(n, n_batch, c, base, w != nullptr ? &w->in : nullptr);
-  const int64_t gs = align_up((int64_t)n_batch * groups * 4, 256);
-  if (w != nullptr) {
-    w->g1 = reinterpret_cast<float *>(base + in32);
-    w->g2 = reinterpret_cast<float *>(base + in32 + gs);
-  }
-  const int64_t t = align_up((int64_t)n_batch * c * 8, 256), rw = align_up((int64_t)n_batch * 8, 256);
-  const int64_t gs64 = align_up((int64_t)n_batch * groups * 8, 256);
-  if (w64 != nullptr) {
-    w64->t1 = reinterpret_cast<double *>(base);
-    w64->t2 = reinterpret_cast<double *>(base + t);
-    w64->rows = reinterpret_cast<double *>(base + 2 * t);
-    w64->g1 = reinterpret_cast<double *>(base + 2 * t + rw);
-    w64->g2 = reinterpret_cast<double *>(base + 2 * t + rw + gs64);
-  }
-  const int64_t f32 = in32 + 2 * gs, f64 = 2 * t + rw + 2 * gs64;
-  return f32 > f64 ? f32 : f64;
-}
-
-template <typename T>
-static int gn_stats(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups, float eps,
-                    float *mean, float *rstd, const GnWs &w, hipStream_t stream) {
-  const int v = in_piece<T>(c, {x});
-  const int P = c / v;
-  const int R = P >= 256 ? 1 : 256 / P;
-  const int chunks = bn_chunks(n, R, kBnRowsPerThread);
-  const size_t lds = in_partial_lds_bytes(c, R);
-  ME_CHECK(lds <= 64 * 1024, "channel count too large for the group-norm kernels");
-  ME_HIP(hipMemsetAsync(w.in.cnt, 0, (size_t)chunks * n_batch * 4, stream));
-  if (n > 0)
-    ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gn_partial<T, V>), dim3(chunks), dim3(256), lds, stream, x, batch_row, n,
-                                              c, chunks, n_batch, w.in.pa, w.in.pb, w.in.cnt));
-  hipLaunchKernelGGL(k_gn_chan_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.in.pa,
-                     w.in.pb, w.in.cnt, chunks, n_batch, c, w.in.t1, w.in.t2, w.in.rows);
-  hipLaunchKernelGGL(k_gn_group_final, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0, stream,
-                     w.in.t1, w.in.t2, w.in.rows, n_batch, c, groups, eps, mean, rstd);
-  ME_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename T>
-static int gn_apply(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups, const float *mean,
-                    const float *rstd, const float *gamma, const float *beta, T *y, hipStream_t stream) {
-  const int v = in_piece<T>(c, {x, y});
-  const int P = c / v;
-  const dim3 grid((unsigned)ceil_div(n, (int64_t)(P >= 256 ? 1 : 256 / P) * kBnRowsPerThread));
-  ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gn_apply<T, V>), grid, dim3(256), 0, stream, x, batch_row, n, c, n_batch,
-                                            groups, mean, rstd, gamma, beta, y));
-  ME_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename T>
-static int gn_backward(const T *x, const T *dy, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups,
-                       const float *mean, const float *rstd, const float *gamma, T *dx, float *grad_gamma,
-                       float *grad_beta, const GnWs &w, hipStream_t stream) {
-  const int v = in_piece<T>(c, {x, dy, dx});
-  const int P = c / v;
-  const int R = P >= 256 ? 1 : 256 / P;
-  const int chunks = bn_chunks(n, R, kBnRowsPerThread / 2);
-  const size_t lds = in_partial_lds_bytes(c, R);
-  ME_CHECK(lds <= 64 * 1024, "channel count too large for the group-norm kernels");
-  ME_HIP(hipMemsetAsync(w.in.cnt, 0, (size_t)chunks * n_batch * 4, stream));
-  ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gn_bwd_partial<T, V>), dim3(chunks), dim3(256), lds, stream, x, dy,
-                                            batch_row, n, c, chunks, n_batch, groups, mean, rstd, w.in.pa, w.in.pb,
-                                            w.in.cnt));
-  hipLaunchKernelGGL(k_gn_bwd_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.in.pa,
-                     w.in.pb, w.in.cnt, chunks, n_batch, c, w.in.t1, w.in.t2, w.in.rows);
-  if (grad_gamma != nullptr || grad_beta != nullptr)
-    hipLaunchKernelGGL(k_gn_bwd_params<float>, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.in.t1, w.in.t2,
-                       n_batch, c, grad_gamma, grad_beta);
-  if (dx != nullptr) {
-    hipLaunchKernelGGL(k_gn_bwd_group<float>, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0,
-                       stream, w.in.t1, w.in.t2, gamma, n_batch, c, groups, w.g1, w.g2);
-    const dim3 grid((unsigned)ceil_div(n, (int64_t)R * kBnRowsPerThread));
-    ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gn_bwd_apply<T, V>), grid, dim3(256), 0, stream, x, dy, batch_row, n, c,
-                                              n_batch, groups, mean, rstd, gamma, w.g1, w.g2, w.in.rows, dx));
-  }
-  ME_LAUNCH_CHECK();
-  return 0;
-}
-
 // ---- conditional group norm (MinkowskiConditionalGroupNorm): per-instance scale / shift and a fused SiLU -------------
 //   v = xhat * ge[b, c] + be[b, c], ge = gamma * (1 + scale[b]), be = beta * (1 + scale[b]) + shift[b], y = act(v)
 // The statistics are k_gn_partial / k_gn_chan_final / k_gn_group_final, unchanged.  The modulation is an affine map per
 // (instance, channel): k_gnc_coef writes ge / be [n_batch][c] into the workspace once per call and every later kernel
-// reads them where the plain kernels read gamma / beta — at a change of the batch index in the apply kernels, once per
+// reads them where the plain norm reads gamma / beta — at a change of the batch index in the row maps, once per
 // (instance, piece) in the partial kernel — so the row loops gain two coefficient loads and no arithmetic on
 // gamma / beta / scale / shift.  With scale = shift = NULL and the identity, ge = gamma and be = beta bit for bit and
-// every expression below is the plain kernel's.
-//   k_gnc_coef         one thread per (instance, channel)
-//   k_gnc_apply        k_gn_apply's layout; SiLU in fp32, one rounding at a bf16 store
-//   k_gnc_bwd_partial  seg_bwd_partial with dv = dy * act'(v) in place of dy, v recomputed from x
-//   k_gnc_bwd_params   one thread per channel, ascending b: grad_shift = t1, grad_scale = gamma * t2 + beta * t1,
-//                      grad_beta = sum_b (1 + scale) * t1, grad_gamma = sum_b (1 + scale) * t2
-//   k_gnc_bwd_group    k_gn_bwd_group with ge[b, c] in place of gamma[c]
-//   k_gnc_bwd_apply    k_gn_bwd_apply's layout with ge and dv
+// every expression is the plain norm's.
+//   k_gnc_coef                           one thread per (instance, channel)
+//   k_seg_rows<GnFwd<GnPerInstance, ACT>>  SiLU in fp32, one rounding at a bf16 store
+//   k_gn_bwd_partial<GncGrad>            with the SiLU: dv = dy * act'(v) in place of dy, v recomputed from x
+//   k_gnc_bwd_params                     one thread per channel, ascending b: grad_shift = t1, grad_scale = gamma * t2 +
+//                                        beta * t1, grad_beta = sum_b (1 + scale) * t1, grad_gamma = sum_b (1 + scale) * t2
+//   k_gn_bwd_group                       with ge[b, c] in place of gamma[c]
+//   k_seg_rows<GnBwd<GnPerInstance, ACT>>  with ge and dv
 // Pass counts of group norm: x twice and y once forward; x and dy twice and dx once backward.  No atomics on values.
 enum { kGncIdentity = 0, kGncSilu = 1 };
 
@@ -494,57 +283,9 @@ __global__ __launch_bounds__(256) void k_gnc_coef(const F *__restrict__ gamma, c
   be[idx] = fma(beta != nullptr ? beta[ch] : (F)0, one, shift != nullptr ? shift[idx] : (F)0);
 }
 
-template <typename T, int V, int ACT>
-__global__ __launch_bounds__(256) void k_gnc_apply(const T *__restrict__ x, const int32_t *__restrict__ batch_row,
-                                                  int64_t n, int c, int n_batch, int groups,
-                                                  const float *__restrict__ mean, const float *__restrict__ rstd,
-                                                  const float *__restrict__ ge, const float *__restrict__ be_,
-                                                  T *__restrict__ y) {
-  const int P = c / V;
-  const int W = min(P, (int)blockDim.x);
-  const int R = max(1, (int)blockDim.x / P);
-  const int rl = (int)threadIdx.x / W;
-  const int cg = c / groups;
-  const int64_t r0 = (int64_t)blockIdx.x * R * kBnRowsPerThread;
-  if (rl >= R) return;
-  for (int p = (int)threadIdx.x % W; p < P; p += W) {
-    Row<T, V> t[kBnRowsPerThread];
-    int bi[kBnRowsPerThread];
-#pragma unroll
-    for (int i = 0; i < kBnRowsPerThread; ++i) {
-      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
-      t[i] = load_row<T, V>(x + r * c + p * V);
-      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
-    }
-    float ga[V], be[V], a[V], mu[V];
-    int grp[V];
-    gn_piece_groups<V>(p * V, cg, grp);
-#pragma unroll
-    for (int i = 0; i < kBnRowsPerThread; ++i) {
-      const int64_t r = r0 + rl + (int64_t)i * R;
-      if (i == 0 || bi[i] != bi[i - 1]) {
-        load_f32<V>(ge + (int64_t)bi[i] * c + p * V, ga);
-        load_f32<V>(be_ + (int64_t)bi[i] * c + p * V, be);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-          const int o = bi[i] * groups + grp[j];
-          mu[j] = mean[o];
-          a[j] = rstd[o] * ga[j];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const float v = fmaf(t[i].v[j] - mu[j], a[j], be[j]);
-        t[i].v[j] = ACT == kGncSilu ? gnc_silu<float>(v) : v;
-      }
-      if (r < n) store_row<T, V>(y + r * c + p * V, t[i]);
-    }
-  }
-}
-
-// dv = dy * act'(v), v = (x - mean) * (rstd * ge) + be as the apply kernel forms it; the product is rounded on its own so
-// that the partial and the apply kernel hold the same dv bit for bit
-template <int ACT>
+// the gradient that the partial kernel sums with the SiLU: dv = dy * act'(v), v = (x - mean) * (rstd * ge) + be as the
+// forward map forms it; the product is rounded on its own so that the partial kernel and the backward map hold the same
+// dv bit for bit
 struct GncGrad {
   const float *ge, *be;
   int c;
@@ -554,33 +295,131 @@ struct GncGrad {
   };
   template <int V>
   __device__ __forceinline__ void load(int b, int ch0, const float (&rs)[V], State<V> &st) const {
-    if constexpr (ACT == kGncSilu) {
-      float g[V];
-      load_f32<V>(ge + (int64_t)b * c + ch0, g);
-      load_f32<V>(be + (int64_t)b * c + ch0, st.be);
+    float g[V];
+    load_f32<V>(ge + (int64_t)b * c + ch0, g);
+    load_f32<V>(be + (int64_t)b * c + ch0, st.be);
 #pragma unroll
-      for (int j = 0; j < V; ++j) st.a[j] = rs[j] * g[j];
-    }
+    for (int j = 0; j < V; ++j) st.a[j] = rs[j] * g[j];
   }
   template <int V>
   __device__ __forceinline__ float operator()(const State<V> &st, int j, float xc, float g) const {
-    if constexpr (ACT == kGncSilu) return mul_rounded(g, gnc_silu_grad<float>(fmaf(xc, st.a[j], st.be[j])));
-    else return g;
+    return mul_rounded(g, gnc_silu_grad<float>(fmaf(xc, st.a[j], st.be[j])));
   }
 };
 
-template <typename T, int V, int ACT>
-__global__ __launch_bounds__(256) void k_gnc_bwd_partial(const T *__restrict__ x, const T *__restrict__ dy,
-                                                        const int32_t *__restrict__ batch_row, int64_t n, int c,
-                                                        int chunks, int n_batch, int groups,
-                                                        const float *__restrict__ mean, const float *__restrict__ rstd,
-                                                        const float *__restrict__ ge, const float *__restrict__ be,
-                                                        float *__restrict__ part_dy, float *__restrict__ part_dyx,
-                                                        float *__restrict__ part_cnt) {
-  extern __shared__ float s_red[];  // in_partial_lds_bytes
-  seg_bwd_partial<T, V>(s_red, x, dy, batch_row, n, c, chunks, n_batch, GnCoef{mean, rstd, groups, c / groups}, part_dy,
-                        part_dyx, part_cnt, GncGrad<ACT>{ge, be, c});
-}
+// ---- the row maps of both group norms (seg_rows, segment_norm.hpp) -------------------------------------------------------
+// Where the affine map of (instance, channel) comes from.  BE: whether the additive term is wanted.
+// per channel: gamma / beta [c] (either may be NULL: 1 / 0), loaded once per piece, outside the row loop
+struct GnPerChannel {
+  const float *gamma, *beta;
+  template <int V, bool BE>
+  __device__ __forceinline__ void init(int ch0, float (&ga)[V], float (&be)[V]) const {
+    load_affine<V>(gamma, BE ? beta : nullptr, ch0, ga, be);
+  }
+  template <int V, bool BE>
+  __device__ __forceinline__ void load(int, int, float (&)[V], float (&)[V]) const {}
+  const float *weight() const { return gamma; }   // of k_gn_bwd_group
+  int weight_stride() const { return 0; }
+};
+// per (instance, channel): ge / be [n_batch][c] (k_gnc_coef), loaded at a change of the batch index
+struct GnPerInstance {
+  const float *ge, *be;
+  int c;
+  template <int V, bool BE>
+  __device__ __forceinline__ void init(int, float (&)[V], float (&)[V]) const {}
+  template <int V, bool BE>
+  __device__ __forceinline__ void load(int b, int ch0, float (&ga)[V], float (&bev)[V]) const {
+    load_f32<V>(ge + (int64_t)b * c + ch0, ga);
+    if constexpr (BE) load_f32<V>(be + (int64_t)b * c + ch0, bev);
+  }
+  const float *weight() const { return ge; }
+  int weight_stride() const { return c; }
+};
+
+// y = act((x - mean[b, g]) * (rstd[b, g] * ga) + be), ga / be from Aff; the activation in fp32, one rounding at a bf16
+// store.  A thread's piece may straddle groups (cg = 3 with 4 floats, cg = 6 with 8 bf16): the group of every element is
+// computed once per piece.  mean / rstd are read element by element ([n_batch, groups] floats, L2-resident, no alignment
+// asked of them).
+template <typename Aff, int ACT>
+struct GnFwd {
+  static constexpr bool kDy = false;
+  const float *mean, *rstd;
+  Aff aff;
+  int groups, cg;
+  template <int V>
+  struct Piece {
+    float ga[V], be[V], a[V], mu[V];
+    int grp[V];
+  };
+  template <int V>
+  __device__ __forceinline__ void init(int ch0, Piece<V> &pc) const {
+    aff.template init<V, true>(ch0, pc.ga, pc.be);
+    gn_piece_groups<V>(ch0, cg, pc.grp);
+  }
+  template <int V>
+  __device__ __forceinline__ void load(int b, int ch0, Piece<V> &pc) const {
+    aff.template load<V, true>(b, ch0, pc.ga, pc.be);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const int o = b * groups + pc.grp[j];
+      pc.mu[j] = mean[o];
+      pc.a[j] = rstd[o] * pc.ga[j];
+    }
+  }
+  template <int V>
+  __device__ __forceinline__ float value(const Piece<V> &pc, int j, float x) const {
+    const float v = fmaf(x - pc.mu[j], pc.a[j], pc.be[j]);
+    return ACT == kGncSilu ? gnc_silu<float>(v) : v;
+  }
+};
+
+// dx = A * ((ga * dv - k1) - (x - mean[b, g]) * k2) with A = rstd[b, g], k1 = T1[b, g] / m, k2 = T2[b, g] / m * A,
+// m = n_b * cg and dv = dy * act'(v).  ga * dv is rounded on its own: with one value per (instance, group) it equals k1
+// bit for bit and dx is exactly 0, which a contraction into one fma would lose.  be and a = A * ga serve the SiLU only.
+template <typename Aff, int ACT>
+struct GnBwd {
+  static constexpr bool kDy = true;
+  const float *mean, *rstd;
+  Aff aff;
+  const float *g1, *g2, *rows;
+  int groups, cg;
+  template <int V>
+  struct Piece {
+    float ga[V], be[V], a[V], A[V], k1[V], k2[V], mu[V];
+    int grp[V];
+  };
+  template <int V>
+  __device__ __forceinline__ void init(int ch0, Piece<V> &pc) const {
+    aff.template init<V, ACT == kGncSilu>(ch0, pc.ga, pc.be);
+    gn_piece_groups<V>(ch0, cg, pc.grp);
+  }
+  template <int V>
+  __device__ __forceinline__ void load(int b, int ch0, Piece<V> &pc) const {
+    const float inv_m = 1.f / fmaxf(rows[b] * (float)cg, 1.f);
+    aff.template load<V, ACT == kGncSilu>(b, ch0, pc.ga, pc.be);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const int o = b * groups + pc.grp[j];
+      pc.mu[j] = mean[o];
+      pc.A[j] = rstd[o];
+      if (ACT == kGncSilu) pc.a[j] = pc.A[j] * pc.ga[j];
+      pc.k1[j] = g1[o] * inv_m;
+      pc.k2[j] = g2[o] * inv_m * pc.A[j];
+    }
+  }
+  template <int V>
+  __device__ __forceinline__ float value(const Piece<V> &pc, int j, float x, float dy) const {
+    const float xc = x - pc.mu[j];
+    float dv = dy;
+    if (ACT == kGncSilu) dv = mul_rounded(dv, gnc_silu_grad<float>(fmaf(xc, pc.a[j], pc.be[j])));
+    return pc.A[j] * ((mul_rounded(pc.ga[j], dv) - pc.k1[j]) - xc * pc.k2[j]);
+  }
+  // what the partial kernel sums for this map
+  auto grad() const {
+    if constexpr (ACT == kGncSilu) return GncGrad{aff.ge, aff.be, aff.c};
+    else return SegGradPlain{};
+  }
+};
 
 // One thread per channel, the instances ascending.  Every requested word is written; an instance without rows on this
 // map has t1 = t2 = 0 (seg_bwd_final), so its rows of grad_scale / grad_shift are exactly 0.
@@ -605,86 +444,6 @@ __global__ __launch_bounds__(256) void k_gnc_bwd_params(const F *__restrict__ t1
   }
   if (grad_beta != nullptr) grad_beta[ch] = a;
   if (grad_gamma != nullptr) grad_gamma[ch] = q;
-}
-
-// One thread per (instance b, group g): T1 = sum_{c in g} ge[b, c] * t1[b, c], T2 likewise, ascending c
-template <typename F>
-__global__ __launch_bounds__(256) void k_gnc_bwd_group(const F *__restrict__ t1, const F *__restrict__ t2,
-                                                      const F *__restrict__ ge, int n_batch, int c, int groups,
-                                                      F *__restrict__ g1, F *__restrict__ g2) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // (b, g)
-  if (idx >= n_batch * groups) return;
-  const int b = idx / groups, g = idx % groups, cg = c / groups;
-  F a = 0, q = 0;
-  for (int k = 0; k < cg; ++k) {
-    const int64_t o = (int64_t)b * c + g * cg + k;
-    const F w = ge[o];
-    a = fma(w, t1[o], a);
-    q = fma(w, t2[o], q);
-  }
-  g1[idx] = a;
-  g2[idx] = q;
-}
-
-// dx = A * ((ge * dv - k1) - (x - mean[b, g]) * k2), k_gn_bwd_apply with ge[b, c] and dv = dy * act'(v).  ge * dv is
-// rounded on its own: a one-row instance with cg = 1 gets dx == 0 exactly.
-template <typename T, int V, int ACT>
-__global__ __launch_bounds__(256) void k_gnc_bwd_apply(const T *__restrict__ x, const T *__restrict__ dy,
-                                                      const int32_t *__restrict__ batch_row, int64_t n, int c,
-                                                      int n_batch, int groups, const float *__restrict__ mean,
-                                                      const float *__restrict__ rstd, const float *__restrict__ ge,
-                                                      const float *__restrict__ be_, const float *__restrict__ g1,
-                                                      const float *__restrict__ g2, const float *__restrict__ rows,
-                                                      T *__restrict__ dx) {
-  const int P = c / V;
-  const int W = min(P, (int)blockDim.x);
-  const int R = max(1, (int)blockDim.x / P);
-  const int rl = (int)threadIdx.x / W;
-  const int cg = c / groups;
-  constexpr int RB = kBnRowsPerThread;
-  const int64_t r0 = (int64_t)blockIdx.x * R * RB;
-  if (rl >= R) return;
-  for (int p = (int)threadIdx.x % W; p < P; p += W) {
-    Row<T, V> tx[RB], tg[RB];
-    int bi[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
-      tx[i] = load_row<T, V>(x + r * c + p * V);
-      tg[i] = load_row<T, V>(dy + r * c + p * V);
-      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
-    }
-    float ga[V], be[V], a[V], A[V], k1[V], k2[V], mu[V];
-    int grp[V];
-    gn_piece_groups<V>(p * V, cg, grp);
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-      const int64_t r = r0 + rl + (int64_t)i * R;
-      if (i == 0 || bi[i] != bi[i - 1]) {
-        const float inv_m = 1.f / fmaxf(rows[bi[i]] * (float)cg, 1.f);
-        load_f32<V>(ge + (int64_t)bi[i] * c + p * V, ga);
-        if (ACT == kGncSilu) load_f32<V>(be_ + (int64_t)bi[i] * c + p * V, be);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-          const int o = bi[i] * groups + grp[j];
-          mu[j] = mean[o];
-          A[j] = rstd[o];
-          a[j] = A[j] * ga[j];
-          k1[j] = g1[o] * inv_m;
-          k2[j] = g2[o] * inv_m * A[j];
-        }
-      }
-      Row<T, V> out;
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const float xc = tx[i].v[j] - mu[j];
-        float dv = tg[i].v[j];
-        if (ACT == kGncSilu) dv = mul_rounded(dv, gnc_silu_grad<float>(fmaf(xc, a[j], be[j])));
-        out.v[j] = A[j] * ((mul_rounded(ga[j], dv) - k1[j]) - xc * k2[j]);
-      }
-      if (r < n) store_row<T, V>(dx + r * c + p * V, out);
-    }
-  }
 }
 
 // ---- float64 twins: plain double, one thread per output -----------------------------------------------------------------
@@ -755,6 +514,36 @@ __global__ __launch_bounds__(256) void k_gnc_bwd_apply_f64(const double *__restr
   dx[idx] = rstd[o] * (ge[e] * dv - g1[o] * inv_m - xh * g2[o] * inv_m);
 }
 
+// ---- host side ------------------------------------------------------------------------------------------------------
+// workspace: in_ws_layout_f32 | g1 | g2 [n_batch][groups] floats.  The statistics keep the channel records in t1 / t2.
+// float64: t1 | t2 [n_batch][c] | rows [n_batch] | g1 | g2 [n_batch][groups] doubles.  Every piece 256-byte aligned.
+struct GnWs {
+  InWs in;
+  float *g1, *g2;
+};
+struct GnWs64 {
+  double *t1, *t2, *rows, *g1, *g2;
+};
+static int64_t gn_ws_layout(int64_t n, int n_batch, int c, int groups, char *base, GnWs *w, GnWs64 *w64) {
+  const int64_t in32 = in_ws_layout_f32(n, n_batch, c, base, w != nullptr ? &w->in : nullptr);
+  const int64_t gs = align_up((int64_t)n_batch * groups * 4, 256);
+  if (w != nullptr) {
+    w->g1 = reinterpret_cast<float *>(base + in32);
+    w->g2 = reinterpret_cast<float *>(base + in32 + gs);
+  }
+  const int64_t t = align_up((int64_t)n_batch * c * 8, 256), rw = align_up((int64_t)n_batch * 8, 256);
+  const int64_t gs64 = align_up((int64_t)n_batch * groups * 8, 256);
+  if (w64 != nullptr) {
+    w64->t1 = reinterpret_cast<double *>(base);
+    w64->t2 = reinterpret_cast<double *>(base + t);
+    w64->rows = reinterpret_cast<double *>(base + 2 * t);
+    w64->g1 = reinterpret_cast<double *>(base + 2 * t + rw);
+    w64->g2 = reinterpret_cast<double *>(base + 2 * t + rw + gs64);
+  }
+  const int64_t f32 = in32 + 2 * gs, f64 = 2 * t + rw + 2 * gs64;
+  return f32 > f64 ? f32 : f64;
+}
+
 // ---- host side: the group-norm workspace, then ge | be [n_batch][c] (floats, or doubles for the _f64 entry points) ------
 struct GncWs {
   GnWs w;
@@ -786,19 +575,84 @@ static void gnc_coef(const F *gamma, const F *beta, const F *scale, const F *shi
 }
 
 template <typename T>
+static int gn_stats(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups, float eps,
+                    float *mean, float *rstd, const GnWs &w, hipStream_t stream) {
+  const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread, {x});
+  ME_CHECK(pl.lds <= 64 * 1024, "channel count too large for the group-norm kernels");
+  ME_HIP(hipMemsetAsync(w.in.cnt, 0, (size_t)pl.chunks * n_batch * 4, stream));
+  if (n > 0)
+    ME_IN_DISPATCH_V(T, pl.v, hipLaunchKernelGGL((k_gn_partial<T, V>), dim3(pl.chunks), dim3(256), pl.lds, stream, x,
+                                                 batch_row, n, c, pl.chunks, n_batch, w.in.pa, w.in.pb, w.in.cnt));
+  hipLaunchKernelGGL(k_gn_chan_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.in.pa,
+                     w.in.pb, w.in.cnt, pl.chunks, n_batch, c, w.in.t1, w.in.t2, w.in.rows);
+  hipLaunchKernelGGL(k_gn_group_final, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0, stream,
+                     w.in.t1, w.in.t2, w.in.rows, n_batch, c, groups, eps, mean, rstd);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
+static int gn_apply(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups, const float *mean,
+                    const float *rstd, const float *gamma, const float *beta, T *y, hipStream_t stream) {
+  const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread, {x, y});
+  const GnFwd<GnPerChannel, kGncIdentity> map{mean, rstd, {gamma, beta}, groups, c / groups};
+  ME_SEG_ROWS(T, pl, stream, x, (const T *)nullptr, batch_row, n, c, n_batch, map, y);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
 static int gnc_apply(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups, const float *mean,
                      const float *rstd, const float *gamma, const float *beta, const float *scale, const float *shift,
                      int act, T *y, const GncWs &w, hipStream_t stream) {
   const float *ge = reinterpret_cast<const float *>(w.ge), *be = reinterpret_cast<const float *>(w.be);
   gnc_coef<float>(gamma, beta, scale, shift, n_batch, c, w, stream);
-  const int v = in_piece<T>(c, {x, y});
-  const int P = c / v;
-  const dim3 grid((unsigned)ceil_div(n, (int64_t)(P >= 256 ? 1 : 256 / P) * kBnRowsPerThread));
-  ME_GNC_DISPATCH_ACT(act, ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gnc_apply<T, V, ACT>), grid, dim3(256), 0, stream,
-                                                                     x, batch_row, n, c, n_batch, groups, mean, rstd, ge,
-                                                                     be, y)));
+  const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread, {x, y});
+  ME_GNC_DISPATCH_ACT(act, const GnFwd<GnPerInstance, ACT> map{mean, rstd, {ge, be, c}, groups, c / groups};
+                      ME_SEG_ROWS(T, pl, stream, x, (const T *)nullptr, batch_row, n, c, n_batch, map, y));
   ME_LAUNCH_CHECK();
   return 0;
+}
+
+// The backward launches of both group norms, from the backward map `map` (GnBwd): its gradient for the partial kernel, its
+// affine source as the weights of k_gn_bwd_group.  gamma / beta / scale: k_gnc_bwd_params' (NULL: 1 / 0 / 0).
+template <typename T, typename Map>
+static int gn_backward_run(const T *x, const T *dy, const int32_t *batch_row, int64_t n, int n_batch, int c,
+                           const Map &map, const float *gamma, const float *beta, const float *scale, T *dx,
+                           float *grad_gamma, float *grad_beta, float *grad_scale, float *grad_shift, const GnWs &w,
+                           hipStream_t stream) {
+  const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread / 2, {x, dy, dx});
+  ME_CHECK(pl.lds <= 64 * 1024, "channel count too large for the group-norm kernels");
+  ME_HIP(hipMemsetAsync(w.in.cnt, 0, (size_t)pl.chunks * n_batch * 4, stream));
+  const auto grad = map.grad();
+  const GnCoef coef{map.mean, map.rstd, map.groups, map.cg};
+  ME_IN_DISPATCH_V(T, pl.v, hipLaunchKernelGGL((k_gn_bwd_partial<T, V, std::decay_t<decltype(grad)>>), dim3(pl.chunks), dim3(256),
+                                               pl.lds, stream, x, dy, batch_row, n, c, pl.chunks, n_batch, coef, grad,
+                                               w.in.pa, w.in.pb, w.in.cnt));
+  hipLaunchKernelGGL(k_gn_bwd_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.in.pa,
+                     w.in.pb, w.in.cnt, pl.chunks, n_batch, c, w.in.t1, w.in.t2, w.in.rows);
+  if (grad_gamma != nullptr || grad_beta != nullptr || grad_scale != nullptr || grad_shift != nullptr)
+    hipLaunchKernelGGL(k_gnc_bwd_params<float>, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.in.t1, w.in.t2,
+                       gamma, beta, scale, n_batch, c, grad_gamma, grad_beta, grad_scale, grad_shift);
+  if (dx != nullptr) {
+    hipLaunchKernelGGL(k_gn_bwd_group<float>, dim3((unsigned)ceil_div((int64_t)n_batch * map.groups, 256)), dim3(256), 0,
+                       stream, w.in.t1, w.in.t2, map.aff.weight(), map.aff.weight_stride(), n_batch, c, map.groups, w.g1,
+                       w.g2);
+    ME_SEG_ROWS(T, pl, stream, x, dy, batch_row, n, c, n_batch, map, dx);
+  }
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+// plain group norm: grad_beta = sum_b t1 and grad_gamma = sum_b t2 are k_gnc_bwd_params' sums without modulation
+// (fma(1, u, a) is a + u)
+template <typename T>
+static int gn_backward(const T *x, const T *dy, const int32_t *batch_row, int64_t n, int n_batch, int c, int groups,
+                       const float *mean, const float *rstd, const float *gamma, T *dx, float *grad_gamma,
+                       float *grad_beta, const GnWs &w, hipStream_t stream) {
+  const GnBwd<GnPerChannel, kGncIdentity> map{mean, rstd, {gamma, nullptr}, w.g1, w.g2, w.in.rows, groups, c / groups};
+  return gn_backward_run<T>(x, dy, batch_row, n, n_batch, c, map, nullptr, nullptr, nullptr, dx, grad_gamma, grad_beta,
+                            nullptr, nullptr, w, stream);
 }
 
 template <typename T>
@@ -808,33 +662,11 @@ static int gnc_backward(const T *x, const T *dy, const int32_t *batch_row, int64
                         float *grad_shift, const GncWs &ws, hipStream_t stream) {
   const GnWs &w = ws.w;
   const float *ge = reinterpret_cast<const float *>(ws.ge), *be = reinterpret_cast<const float *>(ws.be);
-  const int v = in_piece<T>(c, {x, dy, dx});
-  const int P = c / v;
-  const int R = P >= 256 ? 1 : 256 / P;
-  const int chunks = bn_chunks(n, R, kBnRowsPerThread / 2);
-  const size_t lds = in_partial_lds_bytes(c, R);
-  ME_CHECK(lds <= 64 * 1024, "channel count too large for the group-norm kernels");
-  ME_HIP(hipMemsetAsync(w.in.cnt, 0, (size_t)chunks * n_batch * 4, stream));
   gnc_coef<float>(gamma, beta, scale, shift, n_batch, c, ws, stream);
-  ME_GNC_DISPATCH_ACT(act, ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gnc_bwd_partial<T, V, ACT>), dim3(chunks),
-                                                                     dim3(256), lds, stream, x, dy, batch_row, n, c,
-                                                                     chunks, n_batch, groups, mean, rstd, ge, be, w.in.pa,
-                                                                     w.in.pb, w.in.cnt)));
-  hipLaunchKernelGGL(k_gn_bwd_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.in.pa,
-                     w.in.pb, w.in.cnt, chunks, n_batch, c, w.in.t1, w.in.t2, w.in.rows);
-  if (grad_gamma != nullptr || grad_beta != nullptr || grad_scale != nullptr || grad_shift != nullptr)
-    hipLaunchKernelGGL(k_gnc_bwd_params<float>, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.in.t1, w.in.t2,
-                       gamma, beta, scale, n_batch, c, grad_gamma, grad_beta, grad_scale, grad_shift);
-  if (dx != nullptr) {
-    hipLaunchKernelGGL(k_gnc_bwd_group<float>, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0,
-                       stream, w.in.t1, w.in.t2, ge, n_batch, c, groups, w.g1, w.g2);
-    const dim3 grid((unsigned)ceil_div(n, (int64_t)R * kBnRowsPerThread));
-    ME_GNC_DISPATCH_ACT(act, ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_gnc_bwd_apply<T, V, ACT>), grid, dim3(256), 0,
-                                                                       stream, x, dy, batch_row, n, c, n_batch, groups,
-                                                                       mean, rstd, ge, be, w.g1, w.g2, w.in.rows, dx)));
-  }
-  ME_LAUNCH_CHECK();
-  return 0;
+  ME_GNC_DISPATCH_ACT(act, const GnBwd<GnPerInstance, ACT> map{mean, rstd, {ge, be, c}, w.g1, w.g2, w.in.rows, groups,
+                                                               c / groups};
+                      return gn_backward_run<T>(x, dy, batch_row, n, n_batch, c, map, gamma, beta, scale, dx, grad_gamma,
+                                                grad_beta, grad_scale, grad_shift, w, stream));
 }
 
 }  // namespace me
@@ -866,10 +698,7 @@ int me_gnorm_stats(const void *x, int32_t is_bf16, const int32_t *batch_row, int
   ME_CHECK(workspace_bytes >= me_gnorm_workspace_bytes(n, n_batch, c, groups), "workspace too small");
   GnWs w;
   gn_ws_layout(n, n_batch, c, groups, reinterpret_cast<char *>(workspace), &w, nullptr);
-  if (is_bf16)
-    return gn_stats<__bf16>(reinterpret_cast<const __bf16 *>(x), batch_row, n, n_batch, c, groups, eps, mean, rstd, w,
-                            stream);
-  return gn_stats<float>(reinterpret_cast<const float *>(x), batch_row, n, n_batch, c, groups, eps, mean, rstd, w, stream);
+  ME_SEG_RETURN_T(is_bf16, gn_stats<T>((const T *)x, batch_row, n, n_batch, c, groups, eps, mean, rstd, w, stream));
 }
 
 int me_gnorm_apply(const void *x, int32_t is_bf16, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c,
@@ -879,11 +708,8 @@ int me_gnorm_apply(const void *x, int32_t is_bf16, const int32_t *batch_row, int
   ME_GN_CHECK_ARGS();
   ME_GN_CHECK_WIDTH();
   if (n == 0) return 0;
-  if (is_bf16)
-    return gn_apply<__bf16>(reinterpret_cast<const __bf16 *>(x), batch_row, n, n_batch, c, groups, mean, rstd, gamma,
-                            beta, reinterpret_cast<__bf16 *>(y), stream);
-  return gn_apply<float>(reinterpret_cast<const float *>(x), batch_row, n, n_batch, c, groups, mean, rstd, gamma, beta,
-                         reinterpret_cast<float *>(y), stream);
+  ME_SEG_RETURN_T(is_bf16, gn_apply<T>((const T *)x, batch_row, n, n_batch, c, groups, mean, rstd, gamma, beta, (T *)y,
+                                       stream));
 }
 
 int me_gnorm_backward(const void *x, const void *dy, int32_t is_bf16, const int32_t *batch_row, int64_t n,
@@ -897,13 +723,8 @@ int me_gnorm_backward(const void *x, const void *dy, int32_t is_bf16, const int3
   ME_CHECK(workspace_bytes >= me_gnorm_workspace_bytes(n, n_batch, c, groups), "workspace too small");
   GnWs w;
   gn_ws_layout(n, n_batch, c, groups, reinterpret_cast<char *>(workspace), &w, nullptr);
-  if (is_bf16)
-    return gn_backward<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), batch_row, n,
-                               n_batch, c, groups, mean, rstd, gamma, reinterpret_cast<__bf16 *>(dx), grad_gamma,
-                               grad_beta, w, stream);
-  return gn_backward<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), batch_row, n,
-                            n_batch, c, groups, mean, rstd, gamma, reinterpret_cast<float *>(dx), grad_gamma, grad_beta,
-                            w, stream);
+  ME_SEG_RETURN_T(is_bf16, gn_backward<T>((const T *)x, (const T *)dy, batch_row, n, n_batch, c, groups, mean, rstd, gamma,
+                                          (T *)dx, grad_gamma, grad_beta, w, stream));
 }
 
 int me_gnorm_stats_f64(const double *x, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c, int32_t groups,
@@ -920,8 +741,10 @@ int me_gnorm_apply_f64(const double *x, const int32_t *batch_row, int64_t n, int
                        void *stream_) {
   ME_GN_CHECK_ARGS();
   if (n == 0) return 0;
-  hipLaunchKernelGGL(k_gn_apply_f64, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0, (hipStream_t)stream_, x,
-                     batch_row, n, c, n_batch, groups, mean, rstd, gamma, beta, y);
+  // the conditional twin without modulation: gamma * 1.0 and fma(beta, 1.0, 0.0) are exact
+  hipLaunchKernelGGL(k_gnc_apply_f64, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0, (hipStream_t)stream_, x,
+                     batch_row, n, c, n_batch, groups, mean, rstd, gamma, beta, (const double *)nullptr,
+                     (const double *)nullptr, (int)kGncIdentity, y);
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -938,11 +761,12 @@ int me_gnorm_backward_f64(const double *x, const double *dy, const int32_t *batc
   hipLaunchKernelGGL(k_gn_bwd_sums_f64, dim3((unsigned)ceil_div((int64_t)n_batch * c, 256)), dim3(256), 0, stream, x, dy,
                      batch_row, n, n_batch, c, groups, mean, rstd, w.t1, w.t2, w.rows);
   if (grad_gamma != nullptr || grad_beta != nullptr)
-    hipLaunchKernelGGL(k_gn_bwd_params<double>, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.t1, w.t2,
-                       n_batch, c, grad_gamma, grad_beta);
+    hipLaunchKernelGGL(k_gnc_bwd_params<double>, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.t1, w.t2,
+                       (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, n_batch, c, grad_gamma,
+                       grad_beta, (double *)nullptr, (double *)nullptr);
   if (dx != nullptr && n > 0) {
     hipLaunchKernelGGL(k_gn_bwd_group<double>, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0,
-                       stream, w.t1, w.t2, gamma, n_batch, c, groups, w.g1, w.g2);
+                       stream, w.t1, w.t2, gamma, 0, n_batch, c, groups, w.g1, w.g2);
     hipLaunchKernelGGL(k_gn_bwd_apply_f64, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0, stream, x, dy, batch_row, n,
                        c, n_batch, groups, mean, rstd, gamma, w.g1, w.g2, w.rows, dx);
   }
@@ -970,11 +794,8 @@ int me_gnorm_cond_apply(const void *x, int32_t is_bf16, const int32_t *batch_row
   if (n == 0) return 0;
   GncWs w;
   gnc_ws_layout(n, n_batch, c, groups, reinterpret_cast<char *>(workspace), &w);
-  if (is_bf16)
-    return gnc_apply<__bf16>(reinterpret_cast<const __bf16 *>(x), batch_row, n, n_batch, c, groups, mean, rstd, gamma,
-                             beta, scale, shift, act, reinterpret_cast<__bf16 *>(y), w, stream);
-  return gnc_apply<float>(reinterpret_cast<const float *>(x), batch_row, n, n_batch, c, groups, mean, rstd, gamma, beta,
-                          scale, shift, act, reinterpret_cast<float *>(y), w, stream);
+  ME_SEG_RETURN_T(is_bf16, gnc_apply<T>((const T *)x, batch_row, n, n_batch, c, groups, mean, rstd, gamma, beta, scale,
+                                        shift, act, (T *)y, w, stream));
 }
 
 int me_gnorm_cond_backward(const void *x, const void *dy, int32_t is_bf16, const int32_t *batch_row, int64_t n,
@@ -990,13 +811,9 @@ int me_gnorm_cond_backward(const void *x, const void *dy, int32_t is_bf16, const
   ME_CHECK(workspace_bytes >= me_gnorm_cond_workspace_bytes(n, n_batch, c, groups), "workspace too small");
   GncWs w;
   gnc_ws_layout(n, n_batch, c, groups, reinterpret_cast<char *>(workspace), &w);
-  if (is_bf16)
-    return gnc_backward<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), batch_row, n,
-                                n_batch, c, groups, mean, rstd, gamma, beta, scale, shift, act,
-                                reinterpret_cast<__bf16 *>(dx), grad_gamma, grad_beta, grad_scale, grad_shift, w, stream);
-  return gnc_backward<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), batch_row, n,
-                             n_batch, c, groups, mean, rstd, gamma, beta, scale, shift, act,
-                             reinterpret_cast<float *>(dx), grad_gamma, grad_beta, grad_scale, grad_shift, w, stream);
+  ME_SEG_RETURN_T(is_bf16, gnc_backward<T>((const T *)x, (const T *)dy, batch_row, n, n_batch, c, groups, mean, rstd,
+                                           gamma, beta, scale, shift, act, (T *)dx, grad_gamma, grad_beta, grad_scale,
+                                           grad_shift, w, stream));
 }
 
 int me_gnorm_cond_apply_f64(const double *x, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c,
@@ -1032,8 +849,8 @@ int me_gnorm_cond_backward_f64(const double *x, const double *dy, const int32_t 
     hipLaunchKernelGGL(k_gnc_bwd_params<double>, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.t1, w.t2,
                        gamma, beta, scale, n_batch, c, grad_gamma, grad_beta, grad_scale, grad_shift);
   if (dx != nullptr && n > 0) {
-    hipLaunchKernelGGL(k_gnc_bwd_group<double>, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0,
-                       stream, w.t1, w.t2, ge, n_batch, c, groups, w.g1, w.g2);
+    hipLaunchKernelGGL(k_gn_bwd_group<double>, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0,
+                       stream, w.t1, w.t2, ge, c, n_batch, c, groups, w.g1, w.g2);
     hipLaunchKernelGGL(k_gnc_bwd_apply_f64, dim3((unsigned)ceil_div(n * c, 256)), dim3(256), 0, stream, x, dy, batch_row,
                        n, c, n_batch, groups, mean, rstd, ge, be, act, w.g1, w.g2, w.rows, dx);
   }

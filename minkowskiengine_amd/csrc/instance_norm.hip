@@ -13,19 +13,20 @@
 //                                 chunk of two consecutive instances reads its rows twice, from L2)
 //               k_in_final        one wave per (instance, channel): the chunks that hold rows of the instance combined
 //                                 with Chan's formula in a FIXED order -> mean, rstd = 1 / sqrt(biased variance + eps)
-//   forward     k_in_apply        y = (x - mean[b]) * rstd[b] * gamma + beta; the coefficients of an instance stay in
-//                                 registers while consecutive rows of the thread share the batch index
+//   forward     k_seg_rows<InFwd> y = (x - mean[b]) * rstd[b] * gamma + beta; the coefficients of an instance stay in
+//                                 registers while consecutive rows of the thread share the batch index (the row tile
+//                                 seg_rows of segment_norm.hpp with the map InFwd)
 //   backward    k_in_bwd_partial / k_in_bwd_final   t1[b] = sum dy, t2[b] = sum dy * xhat per (instance, channel)
 //               k_in_bwd_params   grad_beta = sum_b t1[b], grad_gamma = sum_b t2[b] (ascending b)
-//               k_in_bwd_apply    dx = gamma * rstd[b] * (dy - t1[b] / n_b - xhat * t2[b] / n_b)
+//               k_seg_rows<InBwd> dx = gamma * rstd[b] * (dy - t1[b] / n_b - xhat * t2[b] / n_b)
 // No atomics on values, every sum in a fixed order: bitwise reproducible.  T = float or __bf16 rows; statistics and
 // parameters fp32.  The float64 twins at the end are the gradcheck yardstick (plain double, one thread per output).
 #include "segment_norm.hpp"
 
 namespace me {
 
-// The scans of a chunk, the bodies of the two-level reductions and the workspace are segment_norm.hpp's (shared with
-// group_norm.hip); the kernels here wrap them for one record per (instance, channel).
+// The scans of a chunk, the bodies of the two-level reductions, the row tile and the workspace are segment_norm.hpp's
+// (shared with group_norm.hip); the kernels and maps here are theirs for one record per (instance, channel).
 template <typename T, int V>
 __global__ __launch_bounds__(256) void k_in_partial(const T *__restrict__ x, const int32_t *__restrict__ batch_row,
                                                    int64_t n, int c, int chunks, int n_batch,
@@ -58,47 +59,32 @@ __global__ __launch_bounds__(256) void k_in_final(const float *__restrict__ part
   rstd_out[idx] = 1.f / sqrtf(var + eps);
 }
 
-// y = (x - mean[b]) * (rstd[b] * gamma) + beta, b = batch_row[row] (gamma / beta may be NULL: 1 / 0).  k_bn_apply's
-// layout: all row loads of a thread first, unconditionally (rows clamped to the matrix), only the stores predicated.  The
-// statistics of an instance (a few KB in all, L2-resident) are re-read only when the batch index changes between two
-// consecutive rows of the thread.
-template <typename T, int V>
-__global__ __launch_bounds__(256) void k_in_apply(const T *__restrict__ x, const int32_t *__restrict__ batch_row,
-                                                 int64_t n, int c, int n_batch, const float *__restrict__ mean,
-                                                 const float *__restrict__ rstd, const float *__restrict__ gamma,
-                                                 const float *__restrict__ beta, T *__restrict__ y) {
-  const int P = c / V;
-  const int W = min(P, (int)blockDim.x);
-  const int R = max(1, (int)blockDim.x / P);
-  const int rl = (int)threadIdx.x / W;
-  const int64_t r0 = (int64_t)blockIdx.x * R * kBnRowsPerThread;
-  if (rl >= R) return;
-  for (int p = (int)threadIdx.x % W; p < P; p += W) {
-    Row<T, V> t[kBnRowsPerThread];
-    int bi[kBnRowsPerThread];
-#pragma unroll
-    for (int i = 0; i < kBnRowsPerThread; ++i) {
-      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
-      t[i] = load_row<T, V>(x + r * c + p * V);
-      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
-    }
+// y = (x - mean[b]) * (rstd[b] * gamma) + beta (gamma / beta may be NULL: 1 / 0): the forward map of seg_rows.
+// mean / rstd: [n_batch][c]
+struct InFwd {
+  static constexpr bool kDy = false;
+  const float *mean, *rstd, *gamma, *beta;
+  int c;
+  template <int V>
+  struct Piece {
     float ga[V], be[V], a[V], mu[V];
-    load_affine<V>(gamma, beta, p * V, ga, be);
-#pragma unroll
-    for (int i = 0; i < kBnRowsPerThread; ++i) {
-      const int64_t r = r0 + rl + (int64_t)i * R;
-      if (i == 0 || bi[i] != bi[i - 1]) {
-        load_f32<V>(mean + (int64_t)bi[i] * c + p * V, mu);
-        load_f32<V>(rstd + (int64_t)bi[i] * c + p * V, a);
-#pragma unroll
-        for (int j = 0; j < V; ++j) a[j] *= ga[j];
-      }
-#pragma unroll
-      for (int j = 0; j < V; ++j) t[i].v[j] = fmaf(t[i].v[j] - mu[j], a[j], be[j]);
-      if (r < n) store_row<T, V>(y + r * c + p * V, t[i]);
-    }
+  };
+  template <int V>
+  __device__ __forceinline__ void init(int ch0, Piece<V> &pc) const {
+    load_affine<V>(gamma, beta, ch0, pc.ga, pc.be);
   }
-}
+  template <int V>
+  __device__ __forceinline__ void load(int b, int ch0, Piece<V> &pc) const {
+    load_f32<V>(mean + (int64_t)b * c + ch0, pc.mu);
+    load_f32<V>(rstd + (int64_t)b * c + ch0, pc.a);
+#pragma unroll
+    for (int j = 0; j < V; ++j) pc.a[j] *= pc.ga[j];
+  }
+  template <int V>
+  __device__ __forceinline__ float value(const Piece<V> &pc, int j, float x) const {
+    return fmaf(x - pc.mu[j], pc.a[j], pc.be[j]);
+  }
+};
 
 // mean / rstd of instance b for V channels from ch0: [n_batch][c]
 struct InCoef {
@@ -139,58 +125,41 @@ __global__ __launch_bounds__(256) void k_in_bwd_params(const float *__restrict__
   seg_bwd_params<float>(t1, t2, n_batch, c, grad_gamma, grad_beta);
 }
 
-// dx = A * ((dy - k1) - (x - mean[b]) * k2) with A = gamma * rstd[b], k1 = t1[b] / n_b, k2 = t2[b] / n_b * rstd[b]
-// (layout and coefficient reuse of k_in_apply)
-template <typename T, int V>
-__global__ __launch_bounds__(256) void k_in_bwd_apply(const T *__restrict__ x, const T *__restrict__ dy,
-                                                     const int32_t *__restrict__ batch_row, int64_t n, int c,
-                                                     int n_batch, const float *__restrict__ mean,
-                                                     const float *__restrict__ rstd, const float *__restrict__ gamma,
-                                                     const float *__restrict__ t1, const float *__restrict__ t2,
-                                                     const float *__restrict__ rows, T *__restrict__ dx) {
-  const int P = c / V;
-  const int W = min(P, (int)blockDim.x);
-  const int R = max(1, (int)blockDim.x / P);
-  const int rl = (int)threadIdx.x / W;
-  constexpr int RB = kBnRowsPerThread;
-  const int64_t r0 = (int64_t)blockIdx.x * R * RB;
-  if (rl >= R) return;
-  for (int p = (int)threadIdx.x % W; p < P; p += W) {
-    Row<T, V> tx[RB], tg[RB];
-    int bi[RB];
+// dx = A * ((dy - k1) - (x - mean[b]) * k2) with A = gamma * rstd[b], k1 = t1[b] / n_b, k2 = t2[b] / n_b * rstd[b]: the
+// backward map of seg_rows
+struct InBwd {
+  static constexpr bool kDy = true;
+  const float *mean, *rstd, *gamma, *t1, *t2, *rows;
+  int c;
+  template <int V>
+  struct Piece {
+    float ga[V], A[V], k1[V], k2[V], mu[V];
+  };
+  template <int V>
+  __device__ __forceinline__ void init(int ch0, Piece<V> &pc) const {
+    float unused[V];
+    load_affine<V>(gamma, nullptr, ch0, pc.ga, unused);
+  }
+  template <int V>
+  __device__ __forceinline__ void load(int b, int ch0, Piece<V> &pc) const {
+    const int64_t o = (int64_t)b * c + ch0;
+    const float inv_n = 1.f / fmaxf(rows[b], 1.f);
+    load_f32<V>(mean + o, pc.mu);
+    load_f32<V>(rstd + o, pc.A);
+    load_f32<V>(t1 + o, pc.k1);
+    load_f32<V>(t2 + o, pc.k2);
 #pragma unroll
-    for (int i = 0; i < RB; ++i) {
-      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
-      tx[i] = load_row<T, V>(x + r * c + p * V);
-      tg[i] = load_row<T, V>(dy + r * c + p * V);
-      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
-    }
-    float ga[V], unused[V], A[V], k1[V], k2[V], mu[V];
-    load_affine<V>(gamma, nullptr, p * V, ga, unused);
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-      const int64_t r = r0 + rl + (int64_t)i * R;
-      if (i == 0 || bi[i] != bi[i - 1]) {
-        const int64_t o = (int64_t)bi[i] * c + p * V;
-        const float inv_n = 1.f / fmaxf(rows[bi[i]], 1.f);
-        load_f32<V>(mean + o, mu);
-        load_f32<V>(rstd + o, A);
-        load_f32<V>(t1 + o, k1);
-        load_f32<V>(t2 + o, k2);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-          k1[j] *= inv_n;
-          k2[j] *= inv_n * A[j];
-          A[j] *= ga[j];
-        }
-      }
-      Row<T, V> out;
-#pragma unroll
-      for (int j = 0; j < V; ++j) out.v[j] = A[j] * ((tg[i].v[j] - k1[j]) - (tx[i].v[j] - mu[j]) * k2[j]);
-      if (r < n) store_row<T, V>(dx + r * c + p * V, out);
+    for (int j = 0; j < V; ++j) {
+      pc.k1[j] *= inv_n;
+      pc.k2[j] *= inv_n * pc.A[j];
+      pc.A[j] *= pc.ga[j];
     }
   }
-}
+  template <int V>
+  __device__ __forceinline__ float value(const Piece<V> &pc, int j, float x, float dy) const {
+    return pc.A[j] * ((dy - pc.k1[j]) - (x - pc.mu[j]) * pc.k2[j]);
+  }
+};
 
 // ---- float64: the same formulae in plain double, one thread per output (gradcheck yardstick, not a hot path) ----------
 // per (instance, channel): mean, then M2 about it, rows in ascending order
@@ -288,18 +257,14 @@ static int64_t in_ws_layout(int64_t n, int n_batch, int c, char *base, InWs *w) 
 template <typename T>
 static int in_stats(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, float eps, float *mean,
                     float *rstd, const InWs &w, hipStream_t stream) {
-  const int v = in_piece<T>(c, {x});
-  const int P = c / v;
-  const int R = P >= 256 ? 1 : 256 / P;
-  const int chunks = bn_chunks(n, R, kBnRowsPerThread);
-  const size_t lds = in_partial_lds_bytes(c, R);
-  ME_CHECK(lds <= 64 * 1024, "channel count too large for the instance-norm kernels");
-  ME_HIP(hipMemsetAsync(w.cnt, 0, (size_t)chunks * n_batch * 4, stream));
+  const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread, {x});
+  ME_CHECK(pl.lds <= 64 * 1024, "channel count too large for the instance-norm kernels");
+  ME_HIP(hipMemsetAsync(w.cnt, 0, (size_t)pl.chunks * n_batch * 4, stream));
   if (n > 0)
-    ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_in_partial<T, V>), dim3(chunks), dim3(256), lds, stream, x, batch_row, n,
-                                              c, chunks, n_batch, w.pa, w.pb, w.cnt));
+    ME_IN_DISPATCH_V(T, pl.v, hipLaunchKernelGGL((k_in_partial<T, V>), dim3(pl.chunks), dim3(256), pl.lds, stream, x,
+                                                 batch_row, n, c, pl.chunks, n_batch, w.pa, w.pb, w.cnt));
   hipLaunchKernelGGL(k_in_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.pa, w.pb,
-                     w.cnt, chunks, n_batch, c, eps, mean, rstd);
+                     w.cnt, pl.chunks, n_batch, c, eps, mean, rstd);
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -307,11 +272,9 @@ static int in_stats(const T *x, const int32_t *batch_row, int64_t n, int n_batch
 template <typename T>
 static int in_apply(const T *x, const int32_t *batch_row, int64_t n, int n_batch, int c, const float *mean,
                     const float *rstd, const float *gamma, const float *beta, T *y, hipStream_t stream) {
-  const int v = in_piece<T>(c, {x, y, mean, rstd});
-  const int P = c / v;
-  const dim3 grid((unsigned)ceil_div(n, (int64_t)(P >= 256 ? 1 : 256 / P) * kBnRowsPerThread));
-  ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_in_apply<T, V>), grid, dim3(256), 0, stream, x, batch_row, n, c, n_batch,
-                                            mean, rstd, gamma, beta, y));
+  const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread, {x, y, mean, rstd});
+  const InFwd map{mean, rstd, gamma, beta, c};
+  ME_SEG_ROWS(T, pl, stream, x, (const T *)nullptr, batch_row, n, c, n_batch, map, y);
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -320,24 +283,19 @@ template <typename T>
 static int in_backward(const T *x, const T *dy, const int32_t *batch_row, int64_t n, int n_batch, int c,
                        const float *mean, const float *rstd, const float *gamma, T *dx, float *grad_gamma,
                        float *grad_beta, const InWs &w, hipStream_t stream) {
-  const int v = in_piece<T>(c, {x, dy, dx, mean, rstd});
-  const int P = c / v;
-  const int R = P >= 256 ? 1 : 256 / P;
-  const int chunks = bn_chunks(n, R, kBnRowsPerThread / 2);
-  const size_t lds = in_partial_lds_bytes(c, R);
-  ME_CHECK(lds <= 64 * 1024, "channel count too large for the instance-norm kernels");
-  ME_HIP(hipMemsetAsync(w.cnt, 0, (size_t)chunks * n_batch * 4, stream));
-  ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_in_bwd_partial<T, V>), dim3(chunks), dim3(256), lds, stream, x, dy,
-                                            batch_row, n, c, chunks, n_batch, mean, rstd, w.pa, w.pb, w.cnt));
+  const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread / 2, {x, dy, dx, mean, rstd});
+  ME_CHECK(pl.lds <= 64 * 1024, "channel count too large for the instance-norm kernels");
+  ME_HIP(hipMemsetAsync(w.cnt, 0, (size_t)pl.chunks * n_batch * 4, stream));
+  ME_IN_DISPATCH_V(T, pl.v, hipLaunchKernelGGL((k_in_bwd_partial<T, V>), dim3(pl.chunks), dim3(256), pl.lds, stream, x,
+                                               dy, batch_row, n, c, pl.chunks, n_batch, mean, rstd, w.pa, w.pb, w.cnt));
   hipLaunchKernelGGL(k_in_bwd_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.pa, w.pb,
-                     w.cnt, chunks, n_batch, c, w.t1, w.t2, w.rows);
+                     w.cnt, pl.chunks, n_batch, c, w.t1, w.t2, w.rows);
   if (grad_gamma != nullptr || grad_beta != nullptr)
     hipLaunchKernelGGL(k_in_bwd_params, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, stream, w.t1, w.t2, n_batch, c,
                        grad_gamma, grad_beta);
   if (dx != nullptr) {
-    const dim3 grid((unsigned)ceil_div(n, (int64_t)R * kBnRowsPerThread));
-    ME_IN_DISPATCH_V(T, v, hipLaunchKernelGGL((k_in_bwd_apply<T, V>), grid, dim3(256), 0, stream, x, dy, batch_row, n, c,
-                                              n_batch, mean, rstd, gamma, w.t1, w.t2, w.rows, dx));
+    const InBwd map{mean, rstd, gamma, w.t1, w.t2, w.rows, c};
+    ME_SEG_ROWS(T, pl, stream, x, dy, batch_row, n, c, n_batch, map, dx);
   }
   ME_LAUNCH_CHECK();
   return 0;
@@ -364,9 +322,7 @@ int me_inorm_stats(const void *x, int32_t is_bf16, const int32_t *batch_row, int
   ME_CHECK(workspace_bytes >= me_inorm_workspace_bytes(n, n_batch, c), "workspace too small");
   InWs w;
   in_ws_layout(n, n_batch, c, reinterpret_cast<char *>(workspace), &w);
-  if (is_bf16)
-    return in_stats<__bf16>(reinterpret_cast<const __bf16 *>(x), batch_row, n, n_batch, c, eps, mean, rstd, w, stream);
-  return in_stats<float>(reinterpret_cast<const float *>(x), batch_row, n, n_batch, c, eps, mean, rstd, w, stream);
+  ME_SEG_RETURN_T(is_bf16, in_stats<T>((const T *)x, batch_row, n, n_batch, c, eps, mean, rstd, w, stream));
 }
 
 int me_inorm_apply(const void *x, int32_t is_bf16, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c,
@@ -375,11 +331,7 @@ int me_inorm_apply(const void *x, int32_t is_bf16, const int32_t *batch_row, int
   hipStream_t stream = (hipStream_t)stream_;
   ME_IN_CHECK_ARGS();
   if (n == 0) return 0;
-  if (is_bf16)
-    return in_apply<__bf16>(reinterpret_cast<const __bf16 *>(x), batch_row, n, n_batch, c, mean, rstd, gamma, beta,
-                            reinterpret_cast<__bf16 *>(y), stream);
-  return in_apply<float>(reinterpret_cast<const float *>(x), batch_row, n, n_batch, c, mean, rstd, gamma, beta,
-                         reinterpret_cast<float *>(y), stream);
+  ME_SEG_RETURN_T(is_bf16, in_apply<T>((const T *)x, batch_row, n, n_batch, c, mean, rstd, gamma, beta, (T *)y, stream));
 }
 
 int me_inorm_backward(const void *x, const void *dy, int32_t is_bf16, const int32_t *batch_row, int64_t n,
@@ -391,13 +343,8 @@ int me_inorm_backward(const void *x, const void *dy, int32_t is_bf16, const int3
   ME_CHECK(workspace_bytes >= me_inorm_workspace_bytes(n, n_batch, c), "workspace too small");
   InWs w;
   in_ws_layout(n, n_batch, c, reinterpret_cast<char *>(workspace), &w);
-  if (is_bf16)
-    return in_backward<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), batch_row, n,
-                               n_batch, c, mean, rstd, gamma, reinterpret_cast<__bf16 *>(dx), grad_gamma, grad_beta, w,
-                               stream);
-  return in_backward<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), batch_row, n,
-                            n_batch, c, mean, rstd, gamma, reinterpret_cast<float *>(dx), grad_gamma, grad_beta, w,
-                            stream);
+  ME_SEG_RETURN_T(is_bf16, in_backward<T>((const T *)x, (const T *)dy, batch_row, n, n_batch, c, mean, rstd, gamma,
+                                          (T *)dx, grad_gamma, grad_beta, w, stream));
 }
 
 int me_inorm_stats_f64(const double *x, const int32_t *batch_row, int64_t n, int32_t n_batch, int32_t c, double eps,

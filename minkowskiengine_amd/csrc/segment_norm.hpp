@@ -1,7 +1,9 @@
 // Shared by the normalisations whose statistics are SEGMENTED by the batch index of each row (instance_norm.hip: one
 // record per (instance, channel); group_norm.hip: the channel records of a group merged into one): the scans of a chunk
-// of rows, the bodies of the two-level reductions over (chunk, instance, channel) and the workspace they use.  A
-// translation unit wraps each body in a __global__ kernel of its own.
+// of rows, the bodies of the two-level reductions over (chunk, instance, channel) and the workspace they use — a
+// translation unit wraps each body in a __global__ kernel of its own — and seg_rows / k_seg_rows, the row tile of every
+// apply and backward-apply kernel, which a translation unit instantiates with its maps.  Host side: the workspace, the
+// launch plan (SegPlan) and the dispatch over the piece width and the row type.
 #pragma once
 #include "norm_common.hpp"
 
@@ -397,6 +399,62 @@ __device__ __forceinline__ void seg_bwd_params(const F *__restrict__ t1, const F
   if (grad_gamma != nullptr) grad_gamma[ch] = q;
 }
 
+// The row tile of every kernel that maps rows to rows with coefficients per instance (the apply and the backward-apply
+// kernels): out[r] = map(x[r][, dy[r]]) with the coefficients of b = batch_row[r].  k_bn_apply's layout: a thread owns a
+// piece of V channels and kBnRowsPerThread rows; ALL its row loads are issued first and unconditionally (rows clamped to
+// the matrix), only the stores are predicated.  The batch index is clamped to [0, n_batch) before anything is addressed
+// with it.  The coefficients of an instance (a few KB in all, L2-resident) are re-read only when the batch index changes
+// between two consecutive rows of the thread.  Map (passed by value as a kernel argument) provides
+//   kDy                       whether the map reads dy next to x
+//   Piece<V>                  the registers of a thread's piece
+//   init(ch0, pc)             once per piece, outside the row loop: what depends on the channels only
+//   load(b, ch0, pc)          at a change of the batch index: the coefficients of instance b
+//   value(pc, j, x[, dy])     element j of the piece
+template <typename T, int V, typename Map>
+__device__ __forceinline__ void seg_rows(const T *__restrict__ x, const T *__restrict__ dy,
+                                         const int32_t *__restrict__ batch_row, int64_t n, int c, int n_batch,
+                                         const Map &map, T *__restrict__ out) {
+  const int P = c / V;
+  const int W = min(P, (int)blockDim.x);
+  const int R = max(1, (int)blockDim.x / P);
+  const int rl = (int)threadIdx.x / W;
+  constexpr int RB = kBnRowsPerThread;
+  const int64_t r0 = (int64_t)blockIdx.x * R * RB;
+  if (rl >= R) return;
+  for (int p = (int)threadIdx.x % W; p < P; p += W) {
+    Row<T, V> tx[RB], tg[Map::kDy ? RB : 1];
+    int bi[RB];
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+      const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
+      tx[i] = load_row<T, V>(x + r * c + p * V);
+      if constexpr (Map::kDy) tg[i] = load_row<T, V>(dy + r * c + p * V);
+      bi[i] = min(max(batch_row[r], 0), n_batch - 1);
+    }
+    typename Map::template Piece<V> pc;
+    map.template init<V>(p * V, pc);
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+      const int64_t r = r0 + rl + (int64_t)i * R;
+      if (i == 0 || bi[i] != bi[i - 1]) map.template load<V>(bi[i], p * V, pc);
+      Row<T, V> o;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        if constexpr (Map::kDy) o.v[j] = map.template value<V>(pc, j, tx[i].v[j], tg[i].v[j]);
+        else o.v[j] = map.template value<V>(pc, j, tx[i].v[j]);
+      }
+      if (r < n) store_row<T, V>(out + r * c + p * V, o);
+    }
+  }
+}
+// dy is NULL for a map that does not read it
+template <typename T, int V, typename Map>
+__global__ __launch_bounds__(256) void k_seg_rows(const T *__restrict__ x, const T *__restrict__ dy,
+                                                 const int32_t *__restrict__ batch_row, int64_t n, int c, int n_batch,
+                                                 const Map map, T *__restrict__ out) {
+  seg_rows<T, V, Map>(x, dy, batch_row, n, c, n_batch, map, out);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 // workspace: part_a | part_b [chunks][n_batch][c] floats | part_cnt [chunks][n_batch] | t1 | t2 [n_batch][c] | rows [n_batch]
 // (every piece 256-byte aligned).  -> bytes of the fp32 layout
@@ -427,12 +485,48 @@ static int in_piece(int c, std::initializer_list<const void *> ptrs) {
   return (aligned && c % W == 0) ? W : ((aligned && c % 4 == 0) ? 4 : 1);
 }
 
+// The launch of the kernels over rows of c channels of T: v channels per piece (in_piece of the pointers whose alignment
+// counts), P pieces per row, R row lanes per workgroup; `chunks` workgroups of `lds` bytes for a partial kernel with
+// `rows_in_flight` rows per thread, `grid` workgroups for a row kernel (seg_rows)
+struct SegPlan {
+  int v, P, R, chunks;
+  size_t lds;
+  dim3 grid;
+};
+template <typename T>
+static SegPlan seg_plan(int64_t n, int c, int rows_in_flight, std::initializer_list<const void *> ptrs) {
+  SegPlan pl;
+  pl.v = in_piece<T>(c, ptrs);
+  pl.P = c / pl.v;
+  pl.R = pl.P >= 256 ? 1 : 256 / pl.P;
+  pl.chunks = bn_chunks(n, pl.R, rows_in_flight);
+  pl.lds = in_partial_lds_bytes(c, pl.R);
+  pl.grid = dim3((unsigned)ceil_div(n, (int64_t)pl.R * kBnRowsPerThread));
+  return pl;
+}
+
 #define ME_IN_DISPATCH_V(T, v, ...)                            \
   do {                                                         \
     constexpr int W_ = 16 / (int)sizeof(T);                    \
     if ((v) == W_) { constexpr int V = W_; __VA_ARGS__; }      \
     else if ((v) == 4) { constexpr int V = 4; __VA_ARGS__; }   \
     else { constexpr int V = 1; __VA_ARGS__; }                 \
+  } while (0)
+
+// seg_rows over the plan's grid with the map `map`; dy is NULL for a map that does not read it
+#define ME_SEG_ROWS(T, pl, stream, x, dy, batch_row, n, c, n_batch, map, out)                                          \
+  ME_IN_DISPATCH_V(T, (pl).v, hipLaunchKernelGGL((k_seg_rows<T, V, std::decay_t<decltype(map)>>), (pl).grid, dim3(256), 0,   \
+                                                 stream, x, dy, batch_row, n, c, n_batch, map, out))
+
+// the body of an extern "C" entry point whose rows are float or, with is_bf16, __bf16: `return call;` with T the row type
+#define ME_SEG_RETURN_T(is_bf16, ...)          \
+  do {                                         \
+    if (is_bf16) {                             \
+      using T = __bf16;                        \
+      return __VA_ARGS__;                      \
+    }                                          \
+    using T = float;                           \
+    return __VA_ARGS__;                        \
   } while (0)
 
 }  // namespace me

@@ -1001,6 +1001,23 @@ static std::pair<Tensor, int64_t> inorm_prepare(const Tensor &in_feat, Coordinat
   return {rows, mgr->get(glob_key->get())->n};
 }
 
+// The shared opening of the norm backward operators (twin of backend._norm_backward_prepare): grad_out made contiguous and
+// cast to the dtype of in_feat -> (batch_row, n_batch, grad_in, grad_weight, grad_bias), allocated, not yet written
+static std::tuple<Tensor, int, Tensor, Tensor, Tensor> norm_backward_prepare(
+    const Tensor &in_feat, Tensor &grad_out, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
+    CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_weight, bool need_grad_bias) {
+  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
+  grad_out = grad_out.contiguous();
+  check_feat("grad_out_feat", grad_out);
+  if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
+  check(grad_out.sizes() == in_feat.sizes(), "grad_out_feat must have the shape of in_feat");
+  const auto popt = at::TensorOptions().dtype(in_feat.scalar_type() == at::kDouble ? at::kDouble : at::kFloat)
+                        .device(in_feat.device());
+  const int64_t c = in_feat.size(1);
+  return {pr.first, (int)pr.second, need_grad_in ? at::empty_like(in_feat) : Tensor(),
+          need_grad_weight ? at::empty({c}, popt) : Tensor(), need_grad_bias ? at::empty({c}, popt) : Tensor()};
+}
+
 std::tuple<Tensor, Tensor, Tensor> instance_norm_forward(const Tensor &in_feat, const Tensor &weight, const Tensor &bias,
                                                          double eps, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
                                                          CoordinateMapManager *mgr) {
@@ -1037,13 +1054,8 @@ std::tuple<Tensor, Tensor, Tensor> instance_norm_backward(const Tensor &in_feat,
                                                           const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key,
                                                           CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
                                                           bool need_grad_in, bool need_grad_weight, bool need_grad_bias) {
-  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
-  const Tensor &rows = pr.first;
-  const int n_batch = (int)pr.second;
-  grad_out = grad_out.contiguous();
-  check_feat("grad_out_feat", grad_out);
-  if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
-  check(grad_out.sizes() == in_feat.sizes(), "grad_out_feat must have the shape of in_feat");
+  auto [rows, n_batch, grad_in, grad_weight, grad_bias] =
+      norm_backward_prepare(in_feat, grad_out, in_key, glob_key, mgr, need_grad_in, need_grad_weight, need_grad_bias);
   const int64_t n = in_feat.size(0);
   const int c = (int)in_feat.size(1);
   inorm_check_vec("weight", weight, in_feat, c);
@@ -1052,10 +1064,6 @@ std::tuple<Tensor, Tensor, Tensor> instance_norm_backward(const Tensor &in_feat,
   inorm_check_vec("rstd", rstd, in_feat, (int64_t)n_batch * c);
   const c10::Device dev = in_feat.device();
   const bool f64 = in_feat.scalar_type() == at::kDouble;
-  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
-  Tensor grad_in = need_grad_in ? at::empty_like(in_feat) : Tensor();
-  Tensor grad_weight = need_grad_weight ? at::empty({c}, popt) : Tensor();
-  Tensor grad_bias = need_grad_bias ? at::empty({c}, popt) : Tensor();
   if (n == 0) {
     if (grad_weight.defined()) grad_weight.zero_();
     if (grad_bias.defined()) grad_bias.zero_();
@@ -1121,13 +1129,8 @@ std::tuple<Tensor, Tensor, Tensor> group_norm_backward(const Tensor &in_feat, Te
                                                        CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
                                                        CoordinateMapManager *mgr, bool need_grad_in,
                                                        bool need_grad_weight, bool need_grad_bias) {
-  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
-  const Tensor &rows = pr.first;
-  const int n_batch = (int)pr.second;
-  grad_out = grad_out.contiguous();
-  check_feat("grad_out_feat", grad_out);
-  if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
-  check(grad_out.sizes() == in_feat.sizes(), "grad_out_feat must have the shape of in_feat");
+  auto [rows, n_batch, grad_in, grad_weight, grad_bias] =
+      norm_backward_prepare(in_feat, grad_out, in_key, glob_key, mgr, need_grad_in, need_grad_weight, need_grad_bias);
   const int64_t n = in_feat.size(0);
   const int c = (int)in_feat.size(1);
   const int groups = gnorm_groups(num_groups, c);
@@ -1137,10 +1140,6 @@ std::tuple<Tensor, Tensor, Tensor> group_norm_backward(const Tensor &in_feat, Te
   inorm_check_vec("rstd", rstd, in_feat, (int64_t)n_batch * groups);
   const c10::Device dev = in_feat.device();
   const bool f64 = in_feat.scalar_type() == at::kDouble;
-  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
-  Tensor grad_in = need_grad_in ? at::empty_like(in_feat) : Tensor();
-  Tensor grad_weight = need_grad_weight ? at::empty({c}, popt) : Tensor();
-  Tensor grad_bias = need_grad_bias ? at::empty({c}, popt) : Tensor();
   if (n == 0) {
     if (grad_weight.defined()) grad_weight.zero_();
     if (grad_bias.defined()) grad_bias.zero_();
@@ -1216,13 +1215,8 @@ std::vector<Tensor> cond_group_norm_backward(const Tensor &in_feat, Tensor grad_
                                              CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
                                              CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_weight,
                                              bool need_grad_bias, bool need_grad_scale, bool need_grad_shift) {
-  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
-  const Tensor &rows = pr.first;
-  const int n_batch = (int)pr.second;
-  grad_out = grad_out.contiguous();
-  check_feat("grad_out_feat", grad_out);
-  if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
-  check(grad_out.sizes() == in_feat.sizes(), "grad_out_feat must have the shape of in_feat");
+  auto [rows, n_batch, grad_in, grad_weight, grad_bias] =
+      norm_backward_prepare(in_feat, grad_out, in_key, glob_key, mgr, need_grad_in, need_grad_weight, need_grad_bias);
   const int64_t n = in_feat.size(0);
   const int c = (int)in_feat.size(1);
   const int groups = gnorm_groups(num_groups, c);
@@ -1236,9 +1230,6 @@ std::vector<Tensor> cond_group_norm_backward(const Tensor &in_feat, Tensor grad_
   const c10::Device dev = in_feat.device();
   const bool f64 = in_feat.scalar_type() == at::kDouble;
   const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
-  Tensor grad_in = need_grad_in ? at::empty_like(in_feat) : Tensor();
-  Tensor grad_weight = need_grad_weight ? at::empty({c}, popt) : Tensor();
-  Tensor grad_bias = need_grad_bias ? at::empty({c}, popt) : Tensor();
   Tensor grad_scale = need_grad_scale ? at::empty({n_batch, c}, popt) : Tensor();
   Tensor grad_shift = need_grad_shift ? at::empty({n_batch, c}, popt) : Tensor();
   if (n == 0) {

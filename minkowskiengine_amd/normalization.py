@@ -176,14 +176,8 @@ class MinkowskiGroupNormFunction(Function):
                 None, None, None, None)
 
 
-class MinkowskiGroupNorm(MinkowskiModuleBase):
-    r"""torch.nn.GroupNorm for sparse tensors: every instance (batch index) is normalised per group of
-    `num_channels / num_groups` consecutive channels with the mean and the biased variance over its rows and the
-    channels of the group (eps inside the square root), then `* weight + bias` per channel.  `num_groups ==
-    num_channels` is instance normalisation; `num_groups == 1` normalises over all channels and rows of an instance.
-    Parameters `weight`, `bias` of shape (num_channels,), fp32, as torch.nn.GroupNorm's, so state dicts move between the
-    two strictly; `affine=False` registers both as None.  bf16 features run with the fp32 parameters and give bf16
-    outputs; float64 features need a `.double()` module."""
+class _GroupNormBase(MinkowskiModuleBase):
+    """what MinkowskiGroupNorm and MinkowskiConditionalGroupNorm share: torch.nn.GroupNorm's arguments and parameters"""
 
     def __init__(self, num_groups, num_channels, eps=1e-5, affine=True):
         super().__init__()
@@ -201,15 +195,25 @@ class MinkowskiGroupNorm(MinkowskiModuleBase):
             self.register_parameter("bias", None)
         self.reset_parameters()
 
-    def __repr__(self):
-        return (self.__class__.__name__ +
-                f"({self.num_groups}, {self.num_channels}, eps={self.eps}, affine={self.affine})")
-
     def reset_parameters(self):
         if self.affine:
             with torch.no_grad():
                 self.weight.fill_(1)
                 self.bias.zero_()
+
+
+class MinkowskiGroupNorm(_GroupNormBase):
+    r"""torch.nn.GroupNorm for sparse tensors: every instance (batch index) is normalised per group of
+    `num_channels / num_groups` consecutive channels with the mean and the biased variance over its rows and the
+    channels of the group (eps inside the square root), then `* weight + bias` per channel.  `num_groups ==
+    num_channels` is instance normalisation; `num_groups == 1` normalises over all channels and rows of an instance.
+    Parameters `weight`, `bias` of shape (num_channels,), fp32, as torch.nn.GroupNorm's, so state dicts move between the
+    two strictly; `affine=False` registers both as None.  bf16 features run with the fp32 parameters and give bf16
+    outputs; float64 features need a `.double()` module."""
+
+    def __repr__(self):
+        return (self.__class__.__name__ +
+                f"({self.num_groups}, {self.num_channels}, eps={self.eps}, affine={self.affine})")
 
     def forward(self, input):
         assert isinstance(input, SparseTensor)
@@ -264,7 +268,7 @@ class MinkowskiConditionalGroupNormFunction(Function):
 _GNC_ACTIVATIONS = (None, "silu")
 
 
-class MinkowskiConditionalGroupNorm(MinkowskiModuleBase):
+class MinkowskiConditionalGroupNorm(_GroupNormBase):
     r"""MinkowskiGroupNorm modulated per instance (AdaGN / FiLM) with an optional fused SiLU, in the passes over the
     feature matrix of the plain layer:
 
@@ -279,33 +283,14 @@ class MinkowskiConditionalGroupNorm(MinkowskiModuleBase):
     fixed-order sums (no atomics), bitwise reproducible."""
 
     def __init__(self, num_groups, num_channels, eps=1e-5, affine=True, activation=None):
-        super().__init__()
-        if num_channels % num_groups != 0:
-            raise ValueError("num_channels must be divisible by num_groups")
+        super().__init__(num_groups, num_channels, eps, affine)
         if activation not in _GNC_ACTIVATIONS:
             raise ValueError(f"activation must be None or 'silu', not {activation!r}")
-        self.num_groups = num_groups
-        self.num_channels = num_channels
-        self.eps = eps
-        self.affine = affine
         self.activation = activation
-        if affine:
-            self.weight = Parameter(torch.ones(num_channels, dtype=torch.float32))
-            self.bias = Parameter(torch.zeros(num_channels, dtype=torch.float32))
-        else:
-            self.register_parameter("weight", None)
-            self.register_parameter("bias", None)
-        self.reset_parameters()
 
     def __repr__(self):
         return (self.__class__.__name__ + f"({self.num_groups}, {self.num_channels}, eps={self.eps}, "
                 f"affine={self.affine}, activation={self.activation!r})")
-
-    def reset_parameters(self):
-        if self.affine:
-            with torch.no_grad():
-                self.weight.fill_(1)
-                self.bias.zero_()
 
     def forward(self, input, scale=None, shift=None):
         assert isinstance(input, SparseTensor)

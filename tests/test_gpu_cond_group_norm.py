@@ -158,20 +158,29 @@ def test_fp32_parity(device, host_layer, name, activation):
         assert_close(g, w, what=what)
 
 
-def test_plain_group_norm_is_a_special_case(device, host_layer):
+# plain against conditional group norm: (table, dtype); the bf16 case has 8-element pieces that straddle the groups of 6
+SPECIAL_CASES = {
+    "c12_g4_straddle": (FP32_CASES, torch.float32),
+    "sizes700_40_1_c24_g4_bf16": ({"sizes700_40_1_c24_g4_bf16": ((700, 40, 1), 24, 4, 3, False)}, torch.bfloat16),
+}
+
+
+@pytest.mark.parametrize("name", list(SPECIAL_CASES))
+def test_plain_group_norm_is_a_special_case(device, host_layer, name):
     """without an activation and without (or with a zero) modulation the layer is MinkowskiGroupNorm bit for bit"""
     import minkowskiengine_amd as ME
-    z = _case("c12_g4_straddle", activation=None, zero_mod=True)
-    plain = _layer(ME, device, z, torch.float32, cls=ME.MinkowskiGroupNorm)
-    x = ME.SparseTensor(z["feats"].to(device), z["coords"].to(device), requires_grad=True)
+    table, dtype = SPECIAL_CASES[name]
+    z = _case(name, table, bf16=dtype == torch.bfloat16, activation=None, zero_mod=True)
+    plain = _layer(ME, device, z, dtype, cls=ME.MinkowskiGroupNorm)
+    x = ME.SparseTensor(z["feats"].to(dtype).to(device), z["coords"].to(device), requires_grad=True)
     y = plain(x)
-    y.F.backward(z["grad_out"].to(device))
+    y.F.backward(z["grad_out"].to(dtype).to(device))
     want = (y.F.detach(), x.F.grad, plain.weight.grad, plain.bias.grad)
-    none = _run(ME, device, z, torch.float32, modulate=False)
-    zero = _run(ME, device, z, torch.float32)
+    none = _run(ME, device, z, dtype, modulate=False)
+    zero = _run(ME, device, z, dtype)
     for got in (none, zero):
         for g, w, what in zip(got, want, NAMES):
-            assert torch.equal(g, w), what
+            assert g.dtype == w.dtype and torch.equal(g, w), what
     assert none[4] is None and none[5] is None
     assert_close(zero[4], z["want"][4], what="grad_scale")
     assert_close(zero[5], z["want"][5], what="grad_shift")

@@ -25,60 +25,10 @@
 //
 // bf16 features take fp32 weights and bias (the fp32 master weights of convolution.py), accumulate in fp32 and round
 // once at the store; dW and db are fp32 for every feature type but double.
-#include "common.hpp"
-
-#include <initializer_list>
+#include "piece.hpp"
 
 namespace me {
 namespace cw {
-
-// V consecutive channels of one row in fp32 (T = float or __bf16); one access of V * sizeof(T) bytes
-template <int V>
-struct Piece {
-  float v[V];
-};
-template <typename T, int V>
-__device__ __forceinline__ Piece<V> load_piece(const T *p) {
-  Piece<V> r;
-  if constexpr (V == 1) {
-    r.v[0] = (float)*p;
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    const tvec t = *reinterpret_cast<const tvec *>(p);
-#pragma unroll
-    for (int j = 0; j < V; ++j) r.v[j] = (float)t[j];
-  }
-  return r;
-}
-template <typename T, int V>
-__device__ __forceinline__ void store_piece(T *p, const Piece<V> &r) {
-  if constexpr (V == 1) {
-    *p = (T)r.v[0];
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    tvec t;
-#pragma unroll
-    for (int j = 0; j < V; ++j) t[j] = (T)r.v[j];
-    *reinterpret_cast<tvec *>(p) = t;
-  }
-}
-// V fp32 weights (16-byte loads when V >= 4: the host checks the alignment)
-template <int V>
-__device__ __forceinline__ Piece<V> load_w(const float *p) {
-  Piece<V> r;
-  if constexpr (V == 1) {
-    r.v[0] = *p;
-  } else {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int q = 0; q < V / 4; ++q) {
-      const f32x4 t = *reinterpret_cast<const f32x4 *>(p + 4 * q);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) r.v[4 * q + j] = t[j];
-    }
-  }
-  return r;
-}
 
 // Offsets per batch of the gathers: the KB table entries of a batch are requested together, then the KB feature pieces
 // (an absent neighbour, -1, reads row 0 — a valid row whenever the source has one — and its value is not used), then
@@ -110,22 +60,21 @@ __global__ __launch_bounds__(256) void k_cw_forward(const T *__restrict__ src, i
 #pragma unroll
     for (int b = 0; b < KB; ++b) {
       if (k0 + b < vol && s[b] >= 0) {
-        const Piece<V> wk = load_w<V>(w + (int64_t)(k0 + b) * c + ch);
+        Piece<V> wk;
+        load_f32<V>(w + (int64_t)(k0 + b) * c + ch, wk.v);
 #pragma unroll
         for (int j = 0; j < V; ++j) acc.v[j] = fmaf(wk.v[j], x[b].v[j], acc.v[j]);
       }
     }
   }
   if (bias) {
-    const Piece<V> b = load_w<V>(bias + ch);
+    Piece<V> b;
+    load_f32<V>(bias + ch, b.v);
 #pragma unroll
     for (int j = 0; j < V; ++j) acc.v[j] += b.v[j];
   }
   store_piece<T, V>(dst + t * c + ch, acc);
 }
-
-// rows of chunk g of n rows split into G chunks: [g * n / G, (g + 1) * n / G)
-__device__ __forceinline__ int64_t chunk_begin(int64_t g, int64_t n, int64_t G) { return g * n / G; }
 
 // Workgroup (chunk g = blockIdx.x, k-group blockIdx.y: offsets [k0, k0 + KG) of the volume).  Pieces of a row:
 // P = c / V; the 256 threads are PB = min(P, 256) pieces x R = 256 / PB row lanes; lane rl takes rows r0 + rl,
@@ -194,7 +143,8 @@ __global__ __launch_bounds__(256) void k_cw_backward_partial(const T *__restrict
 #pragma unroll
                 for (int j = 0; j < V; ++j) acc[kb + b][j] = fmaf(xi.v[j], gy[b].v[j], acc[kb + b][j]);
                 if constexpr (DX) {
-                  const Piece<V> wk = load_w<V>(w + (int64_t)k * c + ch);
+                  Piece<V> wk;
+                  load_f32<V>(w + (int64_t)k * c + ch, wk.v);
 #pragma unroll
                   for (int j = 0; j < V; ++j) d.v[j] = fmaf(wk.v[j], gy[b].v[j], d.v[j]);
                 }
@@ -321,36 +271,14 @@ int64_t cw_chunks(int64_t n_in) {
   return g < kCwMaxChunks ? g : kCwMaxChunks;
 }
 
-bool aligned(std::initializer_list<const void *> ptrs, uintptr_t a) {
-  for (const void *p : ptrs)
-    if (p != nullptr && (uintptr_t)p % a != 0) return false;
-  return true;
-}
-
-// forward piece: 16 bytes of features (4 fp32 / 8 bf16) when c allows and every row start is aligned (weights and bias
-// are fp32: 16 bytes), 8 bytes of bf16, else one channel
-template <typename T>
-int fwd_piece(int c, const T *src, const T *dst, const float *w, const float *bias) {
-  constexpr int W = 16 / (int)sizeof(T);
-  if (c % W == 0 && aligned({src, dst}, 16) && aligned({w, bias}, 16)) return W;
-  if (sizeof(T) == 2 && c % 4 == 0 && aligned({src, dst}, 8) && aligned({w, bias}, 16)) return 4;
-  return 1;
-}
-
 template <typename T>
 int cw_launch_forward(const T *src, int c, const float *w, const float *bias, const int32_t *tbl, int64_t n_src,
                       int64_t n_tgt, int volume, T *dst, hipStream_t stream) {
-  const int v = fwd_piece<T>(c, src, dst, w, bias);
-  const int64_t total = n_tgt * (c / v);
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  if (v == 8) {
-    constexpr int V = sizeof(T) == 2 ? 8 : 4;
-    hipLaunchKernelGGL((k_cw_forward<T, V>), grid, block, 0, stream, src, c, w, bias, tbl, n_src, n_tgt, volume, dst);
-  } else if (v == 4) {
-    hipLaunchKernelGGL((k_cw_forward<T, 4>), grid, block, 0, stream, src, c, w, bias, tbl, n_src, n_tgt, volume, dst);
-  } else {
-    hipLaunchKernelGGL((k_cw_forward<T, 1>), grid, block, 0, stream, src, c, w, bias, tbl, n_src, n_tgt, volume, dst);
-  }
+  // 16 bytes of features (4 fp32 / 8 bf16) or 8 bytes of bf16; the weights and the bias are fp32: 16 bytes per piece
+  const int v = aligned({w, bias}, 16) ? piece_width<T>(kPieceBf16Half, c, {src, dst}) : 1;
+  const dim3 grid = piece_grid(n_tgt, c, v), block(256);
+  ME_PIECE_DISPATCH(T, kPieceBf16Half, v, hipLaunchKernelGGL((k_cw_forward<T, V>), grid, block, 0, stream, src, c, w, bias,
+                                                            tbl, n_src, n_tgt, volume, dst));
   ME_LAUNCH_CHECK();
   return 0;
 }

@@ -15,9 +15,8 @@
 //   * the backward groups the mask itself: the flat winner indices are sorted (stable, so ascending output row), the head
 //     of every run of equal indices sums its run in that order and writes one element.  No floating-point atomics: the
 //     gradient is bitwise reproducible, also where one input element wins in several output rows.
-#include "common.hpp"
+#include "piece.hpp"
 
-#include <initializer_list>
 #include <limits>
 
 namespace me {
@@ -69,36 +68,6 @@ __global__ __launch_bounds__(256) void k_permute(const uint32_t *__restrict__ or
   out[i] = vals[order[i]];
 }
 
-template <typename T, int V>
-struct Piece {
-  T v[V];
-};
-template <typename T, int V>
-__device__ __forceinline__ Piece<T, V> load_piece(const T *p) {
-  Piece<T, V> r;
-  if constexpr (V == 1) {
-    r.v[0] = *p;
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    const tvec t = *reinterpret_cast<const tvec *>(p);
-#pragma unroll
-    for (int j = 0; j < V; ++j) r.v[j] = t[j];
-  }
-  return r;
-}
-template <typename T, int V>
-__device__ __forceinline__ void store_piece(T *p, const Piece<T, V> &r) {
-  if constexpr (V == 1) {
-    *p = r.v[0];
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    tvec t;
-#pragma unroll
-    for (int j = 0; j < V; ++j) t[j] = r.v[j];
-    *reinterpret_cast<tvec *>(p) = t;
-  }
-}
-
 // A lane owns (output row, V channels).  Values are compared in A (fp32 for bf16: the conversion is exact, so the stored
 // winner has its own bits).  Byte model: e * C * (n_rows + n_distinct_in_rows) + sizeof(I) * C * n_rows + 4 * nnz.
 template <typename T, typename A, typename I, int V>
@@ -111,8 +80,8 @@ __global__ __launch_bounds__(256) void k_direct_max(const T *__restrict__ x, int
   const int64_t r = idx / pieces;
   const int ch = (int)(idx % pieces) * V;
   const int32_t e0 = rowptr[r], e1 = rowptr[r + 1];
-  Piece<T, V> best;
-  Piece<I, V> arg;
+  Piece<V, T> best;
+  Piece<V, I> arg;
   if (e0 >= e1) {
 #pragma unroll
     for (int j = 0; j < V; ++j) {
@@ -123,7 +92,7 @@ __global__ __launch_bounds__(256) void k_direct_max(const T *__restrict__ x, int
     int32_t src[V];
     {
       const int32_t s0 = col[e0];
-      best = load_piece<T, V>(x + (int64_t)s0 * c + ch);
+      best = load_piece<T, V, T>(x + (int64_t)s0 * c + ch);
 #pragma unroll
       for (int j = 0; j < V; ++j) src[j] = s0;
     }
@@ -131,9 +100,9 @@ __global__ __launch_bounds__(256) void k_direct_max(const T *__restrict__ x, int
       int32_t s[EB];
 #pragma unroll
       for (int b = 0; b < EB; ++b) s[b] = col[min(b0 + b, e1 - 1)];
-      Piece<T, V> xv[EB];
+      Piece<V, T> xv[EB];
 #pragma unroll
-      for (int b = 0; b < EB; ++b) xv[b] = load_piece<T, V>(x + (int64_t)s[b] * c + ch);
+      for (int b = 0; b < EB; ++b) xv[b] = load_piece<T, V, T>(x + (int64_t)s[b] * c + ch);
 #pragma unroll
       for (int b = 0; b < EB; ++b) {
         if (b0 + b < e1) {
@@ -150,14 +119,8 @@ __global__ __launch_bounds__(256) void k_direct_max(const T *__restrict__ x, int
 #pragma unroll
     for (int j = 0; j < V; ++j) arg.v[j] = (I)((int64_t)src[j] * c + ch + j);
   }
-  store_piece<T, V>(y + r * c + ch, best);
-  store_piece<I, V>(mask + r * c + ch, arg);
-}
-
-inline bool aligned(std::initializer_list<const void *> ps, uintptr_t a) {
-  for (const void *p : ps)
-    if (p != nullptr && (uintptr_t)p % a != 0) return false;
-  return true;
+  store_piece<T, V, T>(y + r * c + ch, best);
+  store_piece<I, V, I>(mask + r * c + ch, arg);
 }
 
 inline int bits_for(int64_t n) {
@@ -193,20 +156,13 @@ inline FwdWs fwd_ws(void *ws, int64_t nmap, int64_t out_nrows) {
 template <typename T, typename A, typename I>
 int launch_max(const T *x, int32_t c, const int32_t *rowptr, const int32_t *col, int64_t n_rows, T *y, I *mask,
                hipStream_t stream) {
-  // a piece is 16 bytes of features when c and the pointers allow (4 fp32, 8 bf16, 2 double), else 8 bytes, else one
-  // channel; the mask piece has the same channel count (V * sizeof(I) bytes, aligned to its size)
-  constexpr int W = 16 / (int)sizeof(T), H = 8 / (int)sizeof(T);
-  const int v = (c % W == 0 && aligned({x, y}, 16) && aligned({mask}, W * sizeof(I))) ? W
-                : (H > 1 && c % H == 0 && aligned({x, y}, 8) && aligned({mask}, H * sizeof(I))) ? H : 1;
-  const int64_t total = n_rows * (c / v);
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  if (v == W)
-    hipLaunchKernelGGL((k_direct_max<T, A, I, W>), grid, block, 0, stream, x, c, rowptr, col, n_rows, y, mask);
-  else if (H > 1 && v == H)
-    hipLaunchKernelGGL((k_direct_max<T, A, I, (H > 1 ? H : 1)>), grid, block, 0, stream, x, c, rowptr, col, n_rows, y,
-                       mask);
-  else
-    hipLaunchKernelGGL((k_direct_max<T, A, I, 1>), grid, block, 0, stream, x, c, rowptr, col, n_rows, y, mask);
+  // the mask piece has the channel count of the feature piece: V * sizeof(I) bytes, aligned to its size
+  int al = common_alignment({x, y});
+  while (al >= 8 && !aligned({mask}, al / sizeof(T) * sizeof(I))) al /= 2;
+  const int v = piece_width((int)sizeof(T), c, al, kPieceHalf);
+  const dim3 grid = piece_grid(n_rows, c, v), block(256);
+  ME_PIECE_DISPATCH(T, kPieceHalf, v, hipLaunchKernelGGL((k_direct_max<T, A, I, V>), grid, block, 0, stream, x, c, rowptr,
+                                                        col, n_rows, y, mask));
   ME_LAUNCH_CHECK();
   return 0;
 }

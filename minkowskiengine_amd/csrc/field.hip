@@ -12,9 +12,8 @@
 //   * every feature movement is k_csr_gather: y[r] = scale[r] * sum_{e in row r} w_e * x[col_e], row-stationary, sums in
 //     entry order (fp32 for fp32 and bf16 features, double for float64), each output row written once (empty rows: 0).
 // So every result is bitwise reproducible, as the convolution path is.
-#include "common.hpp"
+#include "piece.hpp"
 
-#include <initializer_list>
 #include <math.h>
 
 namespace me {
@@ -213,36 +212,6 @@ __global__ __launch_bounds__(256) void k_csr_permute(const uint32_t *__restrict_
 // (e = feature element size; the gathered rows are L2 / MALL hits after their first read).
 constexpr int EB = 8;
 
-template <int V, typename A>
-struct Piece {
-  A v[V];
-};
-template <typename T, int V, typename A>
-__device__ __forceinline__ Piece<V, A> load_piece(const T *p) {
-  Piece<V, A> r;
-  if constexpr (V == 1) {
-    r.v[0] = (A)*p;
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    const tvec t = *reinterpret_cast<const tvec *>(p);
-#pragma unroll
-    for (int j = 0; j < V; ++j) r.v[j] = (A)t[j];
-  }
-  return r;
-}
-template <typename T, int V, typename A>
-__device__ __forceinline__ void store_piece(T *p, const Piece<V, A> &r) {
-  if constexpr (V == 1) {
-    *p = (T)r.v[0];
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    tvec t;
-#pragma unroll
-    for (int j = 0; j < V; ++j) t[j] = (T)r.v[j];
-    *reinterpret_cast<tvec *>(p) = t;
-  }
-}
-
 template <typename T, typename A, int V>
 __global__ __launch_bounds__(256) void k_csr_gather(const T *__restrict__ x, int c, const int32_t *__restrict__ rowptr,
                                                    const int32_t *__restrict__ col, const A *__restrict__ w,
@@ -289,12 +258,6 @@ __global__ __launch_bounds__(256) void k_csr_gather(const T *__restrict__ x, int
   store_piece<T, V, A>(y + r * c + ch, acc);
 }
 
-inline bool aligned(std::initializer_list<const void *> ps, uintptr_t a) {
-  for (const void *p : ps)
-    if (p != nullptr && (uintptr_t)p % a != 0) return false;
-  return true;
-}
-
 template <typename T, typename A>
 int csr_gather(const T *x, int32_t c, const int32_t *rowptr, const int32_t *col, const A *w, const A *scale,
                int64_t n_rows, T *y, hipStream_t stream) {
@@ -302,19 +265,10 @@ int csr_gather(const T *x, int32_t c, const int32_t *rowptr, const int32_t *col,
   ME_CHECK(n_rows >= 0, "invalid row count");
   if (n_rows == 0) return 0;
   ME_CHECK(rowptr != nullptr && y != nullptr, "rowptr and y must be given");
-  // a piece is 16 bytes of features when c and the row starts allow (4 fp32, 8 bf16, 2 double), else 8 bytes (2 fp32,
-  // 4 bf16: bf16 rows of 20 channels are 40 bytes), else one channel
-  constexpr int W = 16 / (int)sizeof(T), H = 8 / (int)sizeof(T);
-  const int v = (c % W == 0 && aligned({x, y}, 16)) ? W : (H > 1 && c % H == 0 && aligned({x, y}, 8)) ? H : 1;
-  const int64_t total = n_rows * (c / v);
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  if (v == W)
-    hipLaunchKernelGGL((k_csr_gather<T, A, W>), grid, block, 0, stream, x, c, rowptr, col, w, scale, n_rows, y);
-  else if (H > 1 && v == H)
-    hipLaunchKernelGGL((k_csr_gather<T, A, (H > 1 ? H : 1)>), grid, block, 0, stream, x, c, rowptr, col, w, scale,
-                       n_rows, y);
-  else
-    hipLaunchKernelGGL((k_csr_gather<T, A, 1>), grid, block, 0, stream, x, c, rowptr, col, w, scale, n_rows, y);
+  const int v = piece_width<T>(kPieceHalf, c, {x, y});   // (the 8-byte piece: bf16 rows of 20 channels are 40 bytes)
+  const dim3 grid = piece_grid(n_rows, c, v), block(256);
+  ME_PIECE_DISPATCH(T, kPieceHalf, v, hipLaunchKernelGGL((k_csr_gather<T, A, V>), grid, block, 0, stream, x, c, rowptr, col,
+                                                        w, scale, n_rows, y));
   ME_LAUNCH_CHECK();
   return 0;
 }

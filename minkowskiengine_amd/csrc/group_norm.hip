@@ -581,8 +581,9 @@ static int gn_stats(const T *x, const int32_t *batch_row, int64_t n, int n_batch
   ME_CHECK(pl.lds <= 64 * 1024, "channel count too large for the group-norm kernels");
   ME_HIP(hipMemsetAsync(w.in.cnt, 0, (size_t)pl.chunks * n_batch * 4, stream));
   if (n > 0)
-    ME_IN_DISPATCH_V(T, pl.v, hipLaunchKernelGGL((k_gn_partial<T, V>), dim3(pl.chunks), dim3(256), pl.lds, stream, x,
-                                                 batch_row, n, c, pl.chunks, n_batch, w.in.pa, w.in.pb, w.in.cnt));
+    ME_PIECE_DISPATCH(T, kPieceNorm, pl.v,
+                      hipLaunchKernelGGL((k_gn_partial<T, V>), dim3(pl.chunks), dim3(256), pl.lds, stream, x, batch_row, n,
+                                         c, pl.chunks, n_batch, w.in.pa, w.in.pb, w.in.cnt));
   hipLaunchKernelGGL(k_gn_chan_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.in.pa,
                      w.in.pb, w.in.cnt, pl.chunks, n_batch, c, w.in.t1, w.in.t2, w.in.rows);
   hipLaunchKernelGGL(k_gn_group_final, dim3((unsigned)ceil_div((int64_t)n_batch * groups, 256)), dim3(256), 0, stream,
@@ -626,9 +627,10 @@ static int gn_backward_run(const T *x, const T *dy, const int32_t *batch_row, in
   ME_HIP(hipMemsetAsync(w.in.cnt, 0, (size_t)pl.chunks * n_batch * 4, stream));
   const auto grad = map.grad();
   const GnCoef coef{map.mean, map.rstd, map.groups, map.cg};
-  ME_IN_DISPATCH_V(T, pl.v, hipLaunchKernelGGL((k_gn_bwd_partial<T, V, std::decay_t<decltype(grad)>>), dim3(pl.chunks), dim3(256),
-                                               pl.lds, stream, x, dy, batch_row, n, c, pl.chunks, n_batch, coef, grad,
-                                               w.in.pa, w.in.pb, w.in.cnt));
+  ME_PIECE_DISPATCH(T, kPieceNorm, pl.v,
+                    hipLaunchKernelGGL((k_gn_bwd_partial<T, V, std::decay_t<decltype(grad)>>), dim3(pl.chunks), dim3(256),
+                                       pl.lds, stream, x, dy, batch_row, n, c, pl.chunks, n_batch, coef, grad, w.in.pa,
+                                       w.in.pb, w.in.cnt));
   hipLaunchKernelGGL(k_gn_bwd_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.in.pa,
                      w.in.pb, w.in.cnt, pl.chunks, n_batch, c, w.in.t1, w.in.t2, w.in.rows);
   if (grad_gamma != nullptr || grad_beta != nullptr || grad_scale != nullptr || grad_shift != nullptr)

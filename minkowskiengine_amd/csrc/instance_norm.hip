@@ -261,8 +261,9 @@ static int in_stats(const T *x, const int32_t *batch_row, int64_t n, int n_batch
   ME_CHECK(pl.lds <= 64 * 1024, "channel count too large for the instance-norm kernels");
   ME_HIP(hipMemsetAsync(w.cnt, 0, (size_t)pl.chunks * n_batch * 4, stream));
   if (n > 0)
-    ME_IN_DISPATCH_V(T, pl.v, hipLaunchKernelGGL((k_in_partial<T, V>), dim3(pl.chunks), dim3(256), pl.lds, stream, x,
-                                                 batch_row, n, c, pl.chunks, n_batch, w.pa, w.pb, w.cnt));
+    ME_PIECE_DISPATCH(T, kPieceNorm, pl.v,
+                      hipLaunchKernelGGL((k_in_partial<T, V>), dim3(pl.chunks), dim3(256), pl.lds, stream, x, batch_row, n,
+                                         c, pl.chunks, n_batch, w.pa, w.pb, w.cnt));
   hipLaunchKernelGGL(k_in_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.pa, w.pb,
                      w.cnt, pl.chunks, n_batch, c, eps, mean, rstd);
   ME_LAUNCH_CHECK();
@@ -286,8 +287,9 @@ static int in_backward(const T *x, const T *dy, const int32_t *batch_row, int64_
   const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread / 2, {x, dy, dx, mean, rstd});
   ME_CHECK(pl.lds <= 64 * 1024, "channel count too large for the instance-norm kernels");
   ME_HIP(hipMemsetAsync(w.cnt, 0, (size_t)pl.chunks * n_batch * 4, stream));
-  ME_IN_DISPATCH_V(T, pl.v, hipLaunchKernelGGL((k_in_bwd_partial<T, V>), dim3(pl.chunks), dim3(256), pl.lds, stream, x,
-                                               dy, batch_row, n, c, pl.chunks, n_batch, mean, rstd, w.pa, w.pb, w.cnt));
+  ME_PIECE_DISPATCH(T, kPieceNorm, pl.v,
+                    hipLaunchKernelGGL((k_in_bwd_partial<T, V>), dim3(pl.chunks), dim3(256), pl.lds, stream, x, dy,
+                                       batch_row, n, c, pl.chunks, n_batch, mean, rstd, w.pa, w.pb, w.cnt));
   hipLaunchKernelGGL(k_in_bwd_final, dim3((unsigned)ceil_div((int64_t)n_batch * c, 4)), dim3(256), 0, stream, w.pa, w.pb,
                      w.cnt, pl.chunks, n_batch, c, w.t1, w.t2, w.rows);
   if (grad_gamma != nullptr || grad_beta != nullptr)

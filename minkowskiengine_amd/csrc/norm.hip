@@ -50,11 +50,11 @@ __global__ __launch_bounds__(256) void k_bn_partial(const T *__restrict__ x, int
     if (active && r0 < r1) {
       const T *xp = x + p * V;
       int64_t rb = r0 + rl;
-      Row<T, V> t[kBnRowsPerThread];
+      Piece<V> t[kBnRowsPerThread];
       auto load_batch = [&]() {
 #pragma unroll
         for (int i = 0; i < kBnRowsPerThread; ++i)
-          t[i] = load_row<T, V>(xp + min(rb + (int64_t)i * R, r1 - 1) * c);
+          t[i] = load_piece<T, V>(xp + min(rb + (int64_t)i * R, r1 - 1) * c);
       };
       auto add_batch = [&]() {
 #pragma unroll
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void k_bn_partial(const T *__restrict__ x, int
       };
       if (rb < r1) {   // first batch and the shift row in one round trip
         load_batch();
-        const Row<T, V> k = load_row<T, V>(xp + r0 * c);
+        const Piece<V> k = load_piece<T, V>(xp + r0 * c);
 #pragma unroll
         for (int j = 0; j < V; ++j) shift[j] = k.v[j];
         add_batch();
@@ -257,12 +257,12 @@ __global__ __launch_bounds__(256) void k_bn_apply(const T *__restrict__ x, int64
   const int64_t r0 = (int64_t)blockIdx.x * R * kBnRowsPerThread;
   if (rl >= R) return;
   for (int p = (int)threadIdx.x % W; p < P; p += W) {
-    Row<T, V> t[kBnRowsPerThread], sk[SKIP ? kBnRowsPerThread : 1];
+    Piece<V> t[kBnRowsPerThread], sk[SKIP ? kBnRowsPerThread : 1];
 #pragma unroll
     for (int i = 0; i < kBnRowsPerThread; ++i) {
       const int64_t off = min(r0 + rl + (int64_t)i * R, n - 1) * c + p * V;
-      t[i] = load_row<T, V>(x + off);
-      if constexpr (SKIP) sk[i] = load_row<T, V>(skip + off);
+      t[i] = load_piece<T, V>(x + off);
+      if constexpr (SKIP) sk[i] = load_piece<T, V>(skip + off);
     }
     float a[V], b[V];
     load_affine<V>(gamma, beta, p * V, a, b);
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256) void k_bn_apply(const T *__restrict__ x, int64
         }
         if (relu) t[i].v[j] = relu_keep_nan(t[i].v[j]);
       }
-      if (r < n) store_row<T, V>(y + r * c + p * V, t[i]);
+      if (r < n) store_piece<T, V>(y + r * c + p * V, t[i]);
     }
   }
 }
@@ -317,13 +317,13 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const T *__restrict__ x,
       float m[V], rs[V], ga[V], be[V];
       bool first = true;
       for (int64_t rb = r0 + rl; rb < r1; rb += (int64_t)RB * R) {
-        Row<T, V> tx[RB], tg[RB], ty[YOUT ? RB : 1];
+        Piece<V> tx[RB], tg[RB], ty[YOUT ? RB : 1];
 #pragma unroll
         for (int i = 0; i < RB; ++i) {
           const int64_t off = min(rb + (int64_t)i * R, r1 - 1) * c + p * V;
-          tx[i] = load_row<T, V>(x + off);
-          tg[i] = load_row<T, V>(dy + off);
-          if constexpr (YOUT) ty[i] = load_row<T, V>(yout + off);
+          tx[i] = load_piece<T, V>(x + off);
+          tg[i] = load_piece<T, V>(dy + off);
+          if constexpr (YOUT) ty[i] = load_piece<T, V>(yout + off);
         }
         if (first) {   // (behind the first batch of row loads: one round trip, not two)
           load_affine<V>(gamma, beta, p * V, ga, be);
@@ -434,13 +434,13 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const T *__restrict__ x, c
   if (n_total_dev != nullptr) n_total = *n_total_dev;   // (uniform)
   const float inv_n = 1.f / (float)n_total;
   for (int p = (int)threadIdx.x % W; p < P; p += W) {
-    Row<T, V> tx[RB], tg[RB], ty[YOUT ? RB : 1];
+    Piece<V> tx[RB], tg[RB], ty[YOUT ? RB : 1];
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
       const int64_t off = min(r0 + rl + (int64_t)i * R, n - 1) * c + p * V;
-      tx[i] = load_row<T, V>(x + off);
-      tg[i] = load_row<T, V>(dy + off);
-      if constexpr (YOUT) ty[i] = load_row<T, V>(yout + off);
+      tx[i] = load_piece<T, V>(x + off);
+      tg[i] = load_piece<T, V>(dy + off);
+      if constexpr (YOUT) ty[i] = load_piece<T, V>(yout + off);
     }
     float ca[V], cb[V], cc[V], za[V], zb[V];
     load_affine<V>(gamma, beta, p * V, za, zb);
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const T *__restrict__ x, c
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
       const int64_t r = r0 + rl + (int64_t)i * R;
-      Row<T, V> out, gs;
+      Piece<V> out, gs;
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         bool pass;
@@ -472,8 +472,8 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const T *__restrict__ x, c
         out.v[j] = fmaf(g, ca[j], fmaf(tx[i].v[j], cb[j], cc[j]));
       }
       if (r < n) {
-        store_row<T, V>(dx + r * c + p * V, out);
-        if (dskip != nullptr) store_row<T, V>(dskip + r * c + p * V, gs);   // gradient of the residual branch
+        store_piece<T, V>(dx + r * c + p * V, out);
+        if (dskip != nullptr) store_piece<T, V>(dskip + r * c + p * V, gs);   // gradient of the residual branch
       }
     }
   }
@@ -483,19 +483,12 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const T *__restrict__ x, c
 // k_bn_partial over the matrix -> ws = part_mean[chunks][c] | part_m2[chunks][c]; *chunks_out = chunks
 template <typename T>
 static int bn_partials(const T *x, int64_t n, int c, float *ws, int *chunks_out, hipStream_t stream) {
-  constexpr int W = 16 / (int)sizeof(T);  // channels per 16-byte access
-  const bool aligned = (uintptr_t)x % 16 == 0;
-  const int v = (aligned && c % W == 0) ? W : ((aligned && c % 4 == 0) ? 4 : 1);
-  const int P = c / v;
-  const int R = P >= 256 ? 1 : 256 / P;
-  const int chunks = bn_chunks(n, R, kBnRowsPerThread);
-  float *pm = ws, *pq = ws + (int64_t)chunks * c;
-  const size_t lds = bn_partial_lds_bytes(c, R);
-  ME_CHECK(lds <= 64 * 1024, "channel count too large for the batch-norm kernels");
-  if (v == W) hipLaunchKernelGGL((k_bn_partial<T, W>), dim3(chunks), dim3(256), lds, stream, x, n, c, chunks, pm, pq);
-  else if (v == 4) hipLaunchKernelGGL((k_bn_partial<T, 4>), dim3(chunks), dim3(256), lds, stream, x, n, c, chunks, pm, pq);
-  else hipLaunchKernelGGL((k_bn_partial<T, 1>), dim3(chunks), dim3(256), lds, stream, x, n, c, chunks, pm, pq);
-  *chunks_out = chunks;
+  const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread, {x});
+  float *pm = ws, *pq = ws + (int64_t)pl.chunks * c;
+  ME_CHECK(pl.lds <= 64 * 1024, "channel count too large for the batch-norm kernels");
+  ME_PIECE_DISPATCH(T, kPieceNorm, pl.v, hipLaunchKernelGGL((k_bn_partial<T, V>), dim3(pl.chunks), dim3(256), pl.lds,
+                                                            stream, x, n, c, pl.chunks, pm, pq));
+  *chunks_out = pl.chunks;
   return 0;
 }
 
@@ -528,54 +521,35 @@ static int bn_local_moments(const T *x, int64_t n, int c, float *record, float *
 template <typename T>
 static int bn_apply(const T *x, int64_t n, int c, const float *mean, const float *rstd, const float *gamma,
                     const float *beta, T *y, int relu, hipStream_t stream, const T *skip = nullptr) {
-  constexpr int W = 16 / (int)sizeof(T);  // channels per 16-byte access
-  const bool aligned = (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)skip % 16 == 0;
-  const int v = (aligned && c % W == 0) ? W : ((aligned && c % 4 == 0) ? 4 : 1);
-  const int pieces = c / v;
-  const dim3 grid((unsigned)ceil_div(n, (int64_t)(pieces >= 256 ? 1 : 256 / pieces) * kBnRowsPerThread));
-#define ME_BN_APPLY(VV)                                                                                            \
-  do {                                                                                                             \
-    if (skip != nullptr)                                                                                           \
-      hipLaunchKernelGGL((k_bn_apply<T, VV, true>), grid, dim3(256), 0, stream, x, n, c, mean, rstd, gamma, beta, y, \
-                         relu, skip);                                                                              \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_bn_apply<T, VV, false>), grid, dim3(256), 0, stream, x, n, c, mean, rstd, gamma, beta, y, \
-                         relu, skip);                                                                              \
-  } while (0)
-  if (v == W) ME_BN_APPLY(W);
-  else if (v == 4) ME_BN_APPLY(4);
-  else ME_BN_APPLY(1);
-#undef ME_BN_APPLY
+  const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread, {x, y, skip});
+  ME_PIECE_DISPATCH(T, kPieceNorm, pl.v,
+                    if (skip != nullptr)
+                      hipLaunchKernelGGL((k_bn_apply<T, V, true>), pl.grid, dim3(256), 0, stream, x, n, c, mean, rstd,
+                                         gamma, beta, y, relu, skip);
+                    else
+                      hipLaunchKernelGGL((k_bn_apply<T, V, false>), pl.grid, dim3(256), 0, stream, x, n, c, mean, rstd,
+                                         gamma, beta, y, relu, skip));
   ME_LAUNCH_CHECK();
   return 0;
 }
 
-// first half of the backward pass: sum dy and sum dy * xhat per channel over this matrix (two levels, fixed order)
+// first half of the backward pass: sum dy and sum dy * xhat per channel over this matrix (two levels, fixed order).
+// pl: seg_plan with kBnRowsPerThread / 2 rows in flight, the one plan of both halves (its piece width by the channel
+// count and every pointer of the pass)
 template <typename T>
 static int bn_backward_sums(const T *x, const T *dy, int64_t n, int c, const float *mean, const float *rstd,
                             const float *gamma, const float *beta, int relu, float *sum_dy, float *sum_dyx, float *ws,
-                            hipStream_t stream, const T *yout, int v) {
-  const int P = c / v;
-  const int R = P >= 256 ? 1 : 256 / P;
-  const int chunks = bn_chunks(n, R, kBnRowsPerThread / 2);
-  float *pa = ws, *pb = ws + (int64_t)chunks * c;
-  const size_t lds = bn_partial_lds_bytes(c, R);
-  ME_CHECK(lds <= 64 * 1024, "channel count too large for the batch-norm kernels");
-  constexpr int W = 16 / (int)sizeof(T);
-#define ME_BN_BWD_PARTIAL(VV)                                                                                      \
-  do {                                                                                                             \
-    if (yout != nullptr)                                                                                           \
-      hipLaunchKernelGGL((k_bn_bwd_partial<T, VV, true>), dim3(chunks), dim3(256), lds, stream, x, dy, n, c, chunks, \
-                         mean, rstd, gamma, beta, relu, pa, pb, yout);                                             \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_bn_bwd_partial<T, VV, false>), dim3(chunks), dim3(256), lds, stream, x, dy, n, c, chunks, \
-                         mean, rstd, gamma, beta, relu, pa, pb, yout);                                             \
-  } while (0)
-  if (v == W) ME_BN_BWD_PARTIAL(W);
-  else if (v == 4) ME_BN_BWD_PARTIAL(4);
-  else ME_BN_BWD_PARTIAL(1);
-#undef ME_BN_BWD_PARTIAL
-  hipLaunchKernelGGL(k_bn_bwd_final, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, pa, pb, c, chunks, sum_dy,
+                            hipStream_t stream, const T *yout, const SegPlan &pl) {
+  float *pa = ws, *pb = ws + (int64_t)pl.chunks * c;
+  ME_CHECK(pl.lds <= 64 * 1024, "channel count too large for the batch-norm kernels");
+  ME_PIECE_DISPATCH(T, kPieceNorm, pl.v,
+                    if (yout != nullptr)
+                      hipLaunchKernelGGL((k_bn_bwd_partial<T, V, true>), dim3(pl.chunks), dim3(256), pl.lds, stream, x, dy,
+                                         n, c, pl.chunks, mean, rstd, gamma, beta, relu, pa, pb, yout);
+                    else
+                      hipLaunchKernelGGL((k_bn_bwd_partial<T, V, false>), dim3(pl.chunks), dim3(256), pl.lds, stream, x,
+                                         dy, n, c, pl.chunks, mean, rstd, gamma, beta, relu, pa, pb, yout));
+  hipLaunchKernelGGL(k_bn_bwd_final, dim3((unsigned)ceil_div(c, 4)), dim3(256), 0, stream, pa, pb, c, pl.chunks, sum_dy,
                      sum_dyx, c);
   ME_LAUNCH_CHECK();
   return 0;
@@ -585,48 +559,29 @@ static int bn_backward_sums(const T *x, const T *dy, int64_t n, int c, const flo
 template <typename T>
 static int bn_backward_apply(const T *x, const T *dy, int64_t n, int c, const float *mean, const float *rstd,
                              const float *gamma, const float *beta, int relu, const float *sum_dy,
-                             const float *sum_dyx, T *dx, hipStream_t stream, const T *yout, T *dskip, int v,
-                             int64_t n_total, const int64_t *n_total_dev) {
-  constexpr int W = 16 / (int)sizeof(T);
-  const int pieces = c / v;
-  const dim3 grid((unsigned)ceil_div(n, (int64_t)(pieces >= 256 ? 1 : 256 / pieces) * kBnRowsPerThread));
-#define ME_BN_BWD_APPLY(VV)                                                                                        \
-  do {                                                                                                             \
-    if (yout != nullptr)                                                                                           \
-      hipLaunchKernelGGL((k_bn_bwd_apply<T, VV, true>), grid, dim3(256), 0, stream, x, dy, n, c, mean, rstd, gamma, \
-                         sum_dy, sum_dyx, dx, beta, relu, yout, dskip, n_total, n_total_dev);                      \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_bn_bwd_apply<T, VV, false>), grid, dim3(256), 0, stream, x, dy, n, c, mean, rstd, gamma, \
-                         sum_dy, sum_dyx, dx, beta, relu, yout, dskip, n_total, n_total_dev);                      \
-  } while (0)
-  if (v == W) ME_BN_BWD_APPLY(W);
-  else if (v == 4) ME_BN_BWD_APPLY(4);
-  else ME_BN_BWD_APPLY(1);
-#undef ME_BN_BWD_APPLY
+                             const float *sum_dyx, T *dx, hipStream_t stream, const T *yout, T *dskip,
+                             const SegPlan &pl, int64_t n_total, const int64_t *n_total_dev) {
+  ME_PIECE_DISPATCH(T, kPieceNorm, pl.v,
+                    if (yout != nullptr)
+                      hipLaunchKernelGGL((k_bn_bwd_apply<T, V, true>), pl.grid, dim3(256), 0, stream, x, dy, n, c, mean,
+                                         rstd, gamma, sum_dy, sum_dyx, dx, beta, relu, yout, dskip, n_total, n_total_dev);
+                    else
+                      hipLaunchKernelGGL((k_bn_bwd_apply<T, V, false>), pl.grid, dim3(256), 0, stream, x, dy, n, c, mean,
+                                         rstd, gamma, sum_dy, sum_dyx, dx, beta, relu, yout, dskip, n_total, n_total_dev));
   ME_LAUNCH_CHECK();
   return 0;
-}
-
-// channels per access of the backward kernels: 16 bytes, 4 channels or 1, by the channel count and every pointer
-template <typename T>
-static int bn_backward_width(int c, const void *x, const void *dy, const void *dx, const void *yout,
-                             const void *dskip) {
-  constexpr int W = 16 / (int)sizeof(T);
-  const bool vec = (c % 4) == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0 && (uintptr_t)dx % 16 == 0 &&
-                   (uintptr_t)yout % 16 == 0 && (uintptr_t)dskip % 16 == 0;
-  return (vec && c % W == 0) ? W : (vec ? 4 : 1);
 }
 
 template <typename T>
 static int bn_backward(const T *x, const T *dy, int64_t n, int c, const float *mean, const float *rstd,
                        const float *gamma, const float *beta, int relu, T *dx, float *grad_gamma, float *grad_beta,
                        float *ws, hipStream_t stream, const T *yout = nullptr, T *dskip = nullptr) {
-  const int v = bn_backward_width<T>(c, x, dy, dx, yout, dskip);
+  const SegPlan pl = seg_plan<T>(n, c, kBnRowsPerThread / 2, {x, dy, dx, yout, dskip});
   if (int rc = bn_backward_sums<T>(x, dy, n, c, mean, rstd, gamma, beta, relu, grad_beta, grad_gamma, ws, stream,
-                                   yout, v))
+                                   yout, pl))
     return rc;
   return bn_backward_apply<T>(x, dy, n, c, mean, rstd, gamma, beta, relu, grad_beta, grad_gamma, dx, stream, yout,
-                              dskip, v, n, nullptr);
+                              dskip, pl, n, nullptr);
 }
 
 }  // namespace me
@@ -646,11 +601,8 @@ int me_bn_stats(const void *x, int32_t is_bf16, int64_t n, int32_t c, float eps,
   ME_CHECK(n > 0 && c > 0, "batch norm needs at least one row and one channel");
   ME_CHECK(workspace_bytes >= me_bn_workspace_bytes(n, c), "workspace too small");
   float *ws = reinterpret_cast<float *>(workspace);
-  if (is_bf16)
-    return bn_stats<__bf16>(reinterpret_cast<const __bf16 *>(x), n, c, eps, momentum, mean, rstd, running_mean,
-                            running_var, num_batches_tracked, ws, stream);
-  return bn_stats<float>(reinterpret_cast<const float *>(x), n, c, eps, momentum, mean, rstd, running_mean,
-                         running_var, num_batches_tracked, ws, stream);
+  ME_SEG_RETURN_T(is_bf16, bn_stats<T>((const T *)x, n, c, eps, momentum, mean, rstd, running_mean, running_var,
+                                       num_batches_tracked, ws, stream));
 }
 
 int me_bn_stats_from_tiles(const float *part_mean, const float *part_m2, int64_t n, int32_t c, int32_t tile_rows,
@@ -673,11 +625,7 @@ int me_bn_apply(const void *x, int32_t is_bf16, int64_t n, int32_t c, const floa
   hipStream_t stream = (hipStream_t)stream_;
   ME_CHECK(c > 0, "invalid channel count");
   if (n == 0) return 0;
-  if (is_bf16)
-    return bn_apply<__bf16>(reinterpret_cast<const __bf16 *>(x), n, c, mean, rstd, gamma, beta,
-                            reinterpret_cast<__bf16 *>(y), relu, stream);
-  return bn_apply<float>(reinterpret_cast<const float *>(x), n, c, mean, rstd, gamma, beta,
-                         reinterpret_cast<float *>(y), relu, stream);
+  ME_SEG_RETURN_T(is_bf16, bn_apply<T>((const T *)x, n, c, mean, rstd, gamma, beta, (T *)y, relu, stream));
 }
 
 int me_bn_apply_residual(const void *x, const void *skip, int32_t is_bf16, int64_t n, int32_t c, const float *mean,
@@ -686,11 +634,8 @@ int me_bn_apply_residual(const void *x, const void *skip, int32_t is_bf16, int64
   hipStream_t stream = (hipStream_t)stream_;
   ME_CHECK(c > 0 && skip != nullptr, "invalid channel count / missing residual branch");
   if (n == 0) return 0;
-  if (is_bf16)
-    return bn_apply<__bf16>(reinterpret_cast<const __bf16 *>(x), n, c, mean, rstd, gamma, beta,
-                            reinterpret_cast<__bf16 *>(y), relu, stream, reinterpret_cast<const __bf16 *>(skip));
-  return bn_apply<float>(reinterpret_cast<const float *>(x), n, c, mean, rstd, gamma, beta,
-                         reinterpret_cast<float *>(y), relu, stream, reinterpret_cast<const float *>(skip));
+  ME_SEG_RETURN_T(is_bf16,
+                  bn_apply<T>((const T *)x, n, c, mean, rstd, gamma, beta, (T *)y, relu, stream, (const T *)skip));
 }
 
 int me_bn_backward_residual(const void *x, const void *dy, const void *yout, int32_t is_bf16, int64_t n, int32_t c,
@@ -702,14 +647,9 @@ int me_bn_backward_residual(const void *x, const void *dy, const void *yout, int
   ME_CHECK(workspace_bytes >= me_bn_workspace_bytes(n, c), "workspace too small");
   ME_CHECK(!relu || yout != nullptr, "the fused ReLU of the residual form needs the forward output");
   float *ws = reinterpret_cast<float *>(workspace);
-  if (is_bf16)
-    return bn_backward<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), n, c, mean,
-                               rstd, gamma, beta, relu, reinterpret_cast<__bf16 *>(dx), grad_gamma, grad_beta, ws,
-                               stream, relu ? reinterpret_cast<const __bf16 *>(yout) : nullptr,
-                               reinterpret_cast<__bf16 *>(dskip));
-  return bn_backward<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), n, c, mean, rstd,
-                            gamma, beta, relu, reinterpret_cast<float *>(dx), grad_gamma, grad_beta, ws, stream,
-                            relu ? reinterpret_cast<const float *>(yout) : nullptr, reinterpret_cast<float *>(dskip));
+  if (!relu) yout = nullptr;
+  ME_SEG_RETURN_T(is_bf16, bn_backward<T>((const T *)x, (const T *)dy, n, c, mean, rstd, gamma, beta, relu, (T *)dx,
+                                          grad_gamma, grad_beta, ws, stream, (const T *)yout, (T *)dskip));
 }
 
 int me_bn_backward(const void *x, const void *dy, int32_t is_bf16, int64_t n, int32_t c, const float *mean,
@@ -719,12 +659,8 @@ int me_bn_backward(const void *x, const void *dy, int32_t is_bf16, int64_t n, in
   ME_CHECK(n > 0 && c > 0, "batch norm needs at least one row and one channel");
   ME_CHECK(workspace_bytes >= me_bn_workspace_bytes(n, c), "workspace too small");
   float *ws = reinterpret_cast<float *>(workspace);
-  if (is_bf16)
-    return bn_backward<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), n, c, mean,
-                               rstd, gamma, beta, relu, reinterpret_cast<__bf16 *>(dx), grad_gamma, grad_beta, ws,
-                               stream);
-  return bn_backward<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), n, c, mean, rstd,
-                            gamma, beta, relu, reinterpret_cast<float *>(dx), grad_gamma, grad_beta, ws, stream);
+  ME_SEG_RETURN_T(is_bf16, bn_backward<T>((const T *)x, (const T *)dy, n, c, mean, rstd, gamma, beta, relu, (T *)dx,
+                                          grad_gamma, grad_beta, ws, stream));
 }
 
 // ---- synchronised batch norm: the two-level forms (include/me_amd.h) ----
@@ -740,8 +676,7 @@ int me_bn_local_moments(const void *x, int32_t is_bf16, int64_t n, int32_t c, fl
   }
   ME_CHECK(workspace_bytes >= me_bn_workspace_bytes(n, c), "workspace too small");
   float *ws = reinterpret_cast<float *>(workspace);
-  if (is_bf16) return bn_local_moments<__bf16>(reinterpret_cast<const __bf16 *>(x), n, c, moments, ws, stream);
-  return bn_local_moments<float>(reinterpret_cast<const float *>(x), n, c, moments, ws, stream);
+  ME_SEG_RETURN_T(is_bf16, bn_local_moments<T>((const T *)x, n, c, moments, ws, stream));
 }
 
 int me_bn_stats_from_moments(const float *moments, int32_t world, int32_t c, float eps, float momentum, float *mean,
@@ -770,15 +705,9 @@ int me_bn_backward_sums(const void *x, const void *dy, const void *yout, int32_t
   ME_CHECK(workspace_bytes >= me_bn_workspace_bytes(n, c), "workspace too small");
   float *ws = reinterpret_cast<float *>(workspace);
   if (!relu) yout = nullptr;
-  if (is_bf16)
-    return bn_backward_sums<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), n, c,
-                                    mean, rstd, gamma, beta, relu, sum_dy, sum_dyx, ws, stream,
-                                    reinterpret_cast<const __bf16 *>(yout),
-                                    bn_backward_width<__bf16>(c, x, dy, nullptr, yout, nullptr));
-  return bn_backward_sums<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), n, c, mean,
-                                 rstd, gamma, beta, relu, sum_dy, sum_dyx, ws, stream,
-                                 reinterpret_cast<const float *>(yout),
-                                 bn_backward_width<float>(c, x, dy, nullptr, yout, nullptr));
+  ME_SEG_RETURN_T(is_bf16, bn_backward_sums<T>((const T *)x, (const T *)dy, n, c, mean, rstd, gamma, beta, relu, sum_dy,
+                                               sum_dyx, ws, stream, (const T *)yout,
+                                               seg_plan<T>(n, c, kBnRowsPerThread / 2, {x, dy, yout})));
 }
 
 int me_bn_backward_reduce(const float *sums, int32_t world, int32_t c, float *sum_dy, float *sum_dyx, void *stream_) {
@@ -799,15 +728,10 @@ int me_bn_backward_apply(const void *x, const void *dy, const void *yout, int32_
   ME_CHECK(n_total_dev != nullptr || n_total >= n_local, "the global row count must cover the local rows");
   if (n_local == 0) return 0;
   if (!relu) yout = nullptr;
-  if (is_bf16)
-    return bn_backward_apply<__bf16>(reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(dy), n_local,
-                                     c, mean, rstd, gamma, beta, relu, sum_dy, sum_dyx, reinterpret_cast<__bf16 *>(dx),
-                                     stream, reinterpret_cast<const __bf16 *>(yout), reinterpret_cast<__bf16 *>(dskip),
-                                     bn_backward_width<__bf16>(c, x, dy, dx, yout, dskip), n_total, n_total_dev);
-  return bn_backward_apply<float>(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(dy), n_local, c,
-                                  mean, rstd, gamma, beta, relu, sum_dy, sum_dyx, reinterpret_cast<float *>(dx), stream,
-                                  reinterpret_cast<const float *>(yout), reinterpret_cast<float *>(dskip),
-                                  bn_backward_width<float>(c, x, dy, dx, yout, dskip), n_total, n_total_dev);
+  ME_SEG_RETURN_T(is_bf16, bn_backward_apply<T>((const T *)x, (const T *)dy, n_local, c, mean, rstd, gamma, beta, relu,
+                                                sum_dy, sum_dyx, (T *)dx, stream, (const T *)yout, (T *)dskip,
+                                                seg_plan<T>(n_local, c, kBnRowsPerThread / 2, {x, dy, dx, yout, dskip}),
+                                                n_total, n_total_dev));
 }
 
 }  // extern "C"

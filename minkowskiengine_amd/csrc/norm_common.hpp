@@ -1,47 +1,15 @@
 // Shared by the normalisation translation units (norm.hip: batch norm over all rows, instance_norm.hip: the same
-// arithmetic segmented by the batch index of each row): row pieces widened to fp32, the chunking of the two-level
-// reductions and the fixed-order LDS combine of the row lanes.
+// arithmetic segmented by the batch index of each row): the chunking of the two-level reductions, the fixed-order LDS
+// combine of the row lanes, the launch plan (SegPlan) and the dispatch over the piece width and the row type.  Rows are
+// read as pieces widened to fp32 (piece.hpp), their width chosen by kPieceNorm.
 #pragma once
-#include "conv_common.hpp"
+#include "piece.hpp"
 
 namespace me {
 
 constexpr int kBnMaxChunks = 512;
 constexpr int kBnRowsPerThread = 8;   // fully unrolled: 8 rows in flight per thread (2 or 4 with more workgroups
                                       // measured 2x slower: the loads in flight per thread matter, not the grid size)
-
-template <typename T, int V>
-struct Row {
-  float v[V];
-};
-template <typename T, int V>
-__device__ __forceinline__ Row<T, V> load_row(const T *p) {
-  Row<T, V> r;
-  if constexpr (V == 1) {
-    r.v[0] = (float)p[0];
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    const tvec t = *reinterpret_cast<const tvec *>(p);
-#pragma unroll
-    for (int j = 0; j < V; ++j) r.v[j] = (float)t[j];
-  }
-  return r;
-}
-template <typename T, int V>
-__device__ __forceinline__ void store_row(T *p, const Row<T, V> &r) {
-  if constexpr (V == 1) {
-    p[0] = (T)r.v[0];
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    tvec t;
-#pragma unroll
-    for (int j = 0; j < V; ++j) t[j] = (T)r.v[j];
-    *reinterpret_cast<tvec *>(p) = t;
-  }
-}
-
-// rows of chunk g: [g * n / G, (g + 1) * n / G)
-__device__ __forceinline__ int64_t chunk_begin(int64_t g, int64_t n, int64_t G) { return g * n / G; }
 
 // max(v, 0) that keeps a NaN (fmaxf returns the other operand): a non-finite row must reach M2 and rstd, as it does in
 // torch and in the float64 twins of the instance norm, not come out as a variance of 0
@@ -117,5 +85,36 @@ static int bn_chunks(int64_t n, int row_lanes, int rows_per_thread) {
   return (int)g;
 }
 static int bn_chunks_max(int64_t n) { return bn_chunks(n, 1, kBnRowsPerThread / 2); }   // workspace bound
+
+// The launch of the kernels over rows of c channels of T: v channels per piece (kPieceNorm of the pointers whose
+// alignment counts), P pieces per row, R row lanes per workgroup; `chunks` workgroups of `lds` bytes for a partial kernel
+// with `rows_in_flight` rows per thread, `grid` workgroups for a row kernel (k_bn_apply, seg_rows)
+struct SegPlan {
+  int v, P, R, chunks;
+  size_t lds;
+  dim3 grid;
+};
+template <typename T>
+static SegPlan seg_plan(int64_t n, int c, int rows_in_flight, std::initializer_list<const void *> ptrs) {
+  SegPlan pl;
+  pl.v = piece_width<T>(kPieceNorm, c, ptrs);
+  pl.P = c / pl.v;
+  pl.R = pl.P >= 256 ? 1 : 256 / pl.P;
+  pl.chunks = bn_chunks(n, pl.R, rows_in_flight);
+  pl.lds = bn_partial_lds_bytes(c, pl.R);
+  pl.grid = dim3((unsigned)ceil_div(n, (int64_t)pl.R * kBnRowsPerThread));
+  return pl;
+}
+
+// the body of an extern "C" entry point whose rows are float or, with is_bf16, __bf16: `return call;` with T the row type
+#define ME_SEG_RETURN_T(is_bf16, ...)          \
+  do {                                         \
+    if (is_bf16) {                             \
+      using T = __bf16;                        \
+      return __VA_ARGS__;                      \
+    }                                          \
+    using T = float;                           \
+    return __VA_ARGS__;                        \
+  } while (0)
 
 }  // namespace me

@@ -11,47 +11,11 @@
 // once — no atomics, no zero-fill pass, and the summation order is the reference CPU order (k ascending),
 // so sums and averages are bitwise reproducible.  All of them are HBM-bound gathers:
 // bytes = 4*C*(pairs + targets) + 4*K*targets of table.
-#include "common.hpp"
+#include "piece.hpp"
 
 #include <float.h>
-#include <initializer_list>
 
 namespace me {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// V consecutive channels of one row, held in fp32 whatever the storage type T (float or __bf16: bf16 features are
-// summed / compared in fp32 and rounded once at the store, like the convolution kernels).  One access of
-// V * sizeof(T) bytes: 16 bytes for (float, 4) and (__bf16, 8), 8 bytes for (__bf16, 4), one element for V = 1.
-template <int V>
-struct Piece {
-  float v[V];
-};
-template <typename T, int V>
-__device__ __forceinline__ Piece<V> load_piece(const T *p) {
-  Piece<V> r;
-  if constexpr (V == 1) {
-    r.v[0] = (float)*p;
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    const tvec t = *reinterpret_cast<const tvec *>(p);
-#pragma unroll
-    for (int j = 0; j < V; ++j) r.v[j] = (float)t[j];
-  }
-  return r;
-}
-template <typename T, int V>
-__device__ __forceinline__ void store_piece(T *p, const Piece<V> &r) {
-  if constexpr (V == 1) {
-    *p = (T)r.v[0];
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    tvec t;
-#pragma unroll
-    for (int j = 0; j < V; ++j) t[j] = (T)r.v[j];
-    *reinterpret_cast<tvec *>(p) = t;
-  }
-}
 
 // dst[t] = sum over k of src[tbl[k][t]]            (src_count == nullptr)
 //        = sum over k of src[s] / src_count[s]      (src_count != nullptr: average-pooling backward,
@@ -404,39 +368,15 @@ using namespace me;
 
 namespace {
 
-// widest piece (elements) for rows of c channels of T at the given addresses: 16 bytes when everything is
-// 16-byte aligned, 8 bytes for bf16 rows of a multiple of 4 channels, else one element
-template <typename T>
-int piece_width(int c, std::initializer_list<const void *> ptrs) {
-  constexpr int W = 16 / (int)sizeof(T);
-  bool a16 = true, a8 = true;
-  for (const void *p : ptrs) {
-    if (p == nullptr) continue;
-    a16 = a16 && ((uintptr_t)p % 16 == 0);
-    a8 = a8 && ((uintptr_t)p % 8 == 0);
-  }
-  if (c % W == 0 && a16) return W;
-  if (sizeof(T) == 2 && c % 4 == 0 && a8) return 4;
-  return 1;
-}
-
-#define ME_POOL_DISPATCH_V(T, v, ...)                                                            \
-  do {                                                                                           \
-    if ((v) == 8) { constexpr int V = (sizeof(T) == 2 ? 8 : 4); __VA_ARGS__; }                   \
-    else if ((v) == 4) { constexpr int V = 4; __VA_ARGS__; }                                     \
-    else { constexpr int V = 1; __VA_ARGS__; }                                                   \
-  } while (0)
-
 template <typename T>
 int pool_sum(const T *src, int32_t c, const int32_t *tbl, int64_t n_tgt, int64_t volume, const float *src_count,
              int32_t average, T *dst, float *dst_count, hipStream_t stream) {
   ME_CHECK(c > 0 && volume >= 1 && volume <= 65535, "invalid channel count or kernel volume");
   if (n_tgt == 0) return 0;
-  const int v = piece_width<T>(c, {src, dst});
-  const int64_t total = n_tgt * (c / v);
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  ME_POOL_DISPATCH_V(T, v, hipLaunchKernelGGL((k_pool_sum<T, V>), grid, block, 0, stream, src, c, tbl, n_tgt,
-                                              (int)volume, src_count, average, dst, dst_count));
+  const int v = piece_width<T>(kPieceBf16Half, c, {src, dst});
+  const dim3 grid = piece_grid(n_tgt, c, v), block(256);
+  ME_PIECE_DISPATCH(T, kPieceBf16Half, v, hipLaunchKernelGGL((k_pool_sum<T, V>), grid, block, 0, stream, src, c, tbl,
+                                                            n_tgt, (int)volume, src_count, average, dst, dst_count));
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -446,11 +386,10 @@ int pool_max(const T *src, int32_t c, const int32_t *tbl, int64_t n_tgt, int64_t
              hipStream_t stream) {
   ME_CHECK(c > 0 && volume >= 1 && volume <= 65535, "invalid channel count or kernel volume");
   if (n_tgt == 0) return 0;
-  const int v = piece_width<T>(c, {src, dst});
-  const int64_t total = n_tgt * (c / v);
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  ME_POOL_DISPATCH_V(T, v, hipLaunchKernelGGL((k_pool_max<T, V>), grid, block, 0, stream, src, c, tbl, n_tgt,
-                                              (int)volume, dst, mask));
+  const int v = piece_width<T>(kPieceBf16Half, c, {src, dst});
+  const dim3 grid = piece_grid(n_tgt, c, v), block(256);
+  ME_PIECE_DISPATCH(T, kPieceBf16Half, v, hipLaunchKernelGGL((k_pool_max<T, V>), grid, block, 0, stream, src, c, tbl,
+                                                            n_tgt, (int)volume, dst, mask));
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -460,11 +399,10 @@ int pool_max_backward(const T *grad_out, int32_t c, const int32_t *tbl_in, int64
                       const int32_t *mask, T *grad_in, hipStream_t stream) {
   ME_CHECK(c > 0 && volume >= 1 && volume <= 65535, "invalid channel count or kernel volume");
   if (n_in == 0) return 0;
-  const int v = piece_width<T>(c, {grad_in});
-  const int64_t total = n_in * (c / v);
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  ME_POOL_DISPATCH_V(T, v, hipLaunchKernelGGL((k_pool_max_backward<T, V>), grid, block, 0, stream, grad_out, c,
-                                              tbl_in, n_in, (int)volume, mask, grad_in));
+  const int v = piece_width<T>(kPieceBf16Half, c, {grad_in});
+  const dim3 grid = piece_grid(n_in, c, v), block(256);
+  ME_PIECE_DISPATCH(T, kPieceBf16Half, v, hipLaunchKernelGGL((k_pool_max_backward<T, V>), grid, block, 0, stream,
+                                                            grad_out, c, tbl_in, n_in, (int)volume, mask, grad_in));
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -474,11 +412,10 @@ int broadcast(const T *in, const T *glob, const int32_t *batch_row, int64_t n, i
               hipStream_t stream) {
   ME_CHECK(c > 0, "invalid channel count");
   if (n == 0) return 0;
-  const int v = piece_width<T>(c, {glob, out, in});
-  const int64_t total = n * (c / v);
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  ME_POOL_DISPATCH_V(T, v, hipLaunchKernelGGL((k_broadcast<T, V>), grid, block, 0, stream, in, glob, batch_row, n, c,
-                                              multiply, out));
+  const int v = piece_width<T>(kPieceBf16Half, c, {glob, out, in});
+  const dim3 grid = piece_grid(n, c, v), block(256);
+  ME_PIECE_DISPATCH(T, kPieceBf16Half, v, hipLaunchKernelGGL((k_broadcast<T, V>), grid, block, 0, stream, in, glob,
+                                                            batch_row, n, c, multiply, out));
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -499,8 +436,7 @@ int global_pool(const T *src, const T *src2, int32_t c, const int32_t *batch_row
   float *partial_cnt = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + 2 * vsz);
   const int64_t total = (int64_t)n_batch * c;
   // a thread owns 4 channels (one 16-byte piece of a float row, 8 bytes of a bf16 row) or one channel
-  const bool vec = (c % 4) == 0 && c / 4 <= 256 && (uintptr_t)src % 16 == 0 &&
-                   (src2 == nullptr || (uintptr_t)src2 % 16 == 0);
+  const bool vec = (c % 4) == 0 && c / 4 <= 256 && aligned({src, src2}, 16);
   const int P = vec ? c / 4 : (c < 256 ? c : 256);
   const int R = 256 / P < 1 ? 1 : 256 / P;
   const size_t lds = (size_t)R * c * 4 * (mode == 2 ? 2 : 1);
@@ -607,7 +543,7 @@ int me_segment_sum_f32(const float *src, int32_t c, const int64_t *perm, const i
   hipStream_t stream = (hipStream_t)stream_;
   ME_CHECK(c > 0, "invalid channel count");
   if (n_seg == 0) return 0;
-  const bool vec = (c % 4) == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
+  const bool vec = (c % 4) == 0 && aligned({src, dst}, 16);
   const int64_t total = n_seg * (vec ? c / 4 : c);
   const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
   if (vec) hipLaunchKernelGGL(k_segment_sum<4>, grid, block, 0, stream, src, c, perm, seg_offsets, n_seg, average, dst);

@@ -2,8 +2,8 @@
 // record per (instance, channel); group_norm.hip: the channel records of a group merged into one): the scans of a chunk
 // of rows, the bodies of the two-level reductions over (chunk, instance, channel) and the workspace they use — a
 // translation unit wraps each body in a __global__ kernel of its own — and seg_rows / k_seg_rows, the row tile of every
-// apply and backward-apply kernel, which a translation unit instantiates with its maps.  Host side: the workspace, the
-// launch plan (SegPlan) and the dispatch over the piece width and the row type.
+// apply and backward-apply kernel, which a translation unit instantiates with its maps.  Host side: the workspace and
+// the launch of seg_rows over a plan (SegPlan, norm_common.hpp).
 #pragma once
 #include "norm_common.hpp"
 
@@ -17,23 +17,6 @@ namespace me {
 // lane: rows of up to 3225 channels fit into 64 KiB.
 __host__ __device__ constexpr size_t in_partial_lds_bytes(int c, int row_lanes) {
   return bn_partial_lds_bytes(c, row_lanes);
-}
-
-template <int V>
-__device__ __forceinline__ void load_f32(const float *__restrict__ p, float (&v)[V]) {
-  if constexpr (V % 4 == 0) {
-#pragma unroll
-    for (int q = 0; q < V / 4; ++q) {
-      const f32x4 t = *reinterpret_cast<const f32x4 *>(p + 4 * q);
-      v[4 * q + 0] = t.x;
-      v[4 * q + 1] = t.y;
-      v[4 * q + 2] = t.z;
-      v[4 * q + 3] = t.w;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j) v[j] = p[j];
-  }
 }
 
 __device__ __forceinline__ int wave_min(int v) {
@@ -144,16 +127,16 @@ __device__ __forceinline__ void seg_partial(float *s_red, const T *__restrict__ 
       for (int j = 0; j < V; ++j) s1[j] = s2[j] = shift[j] = 0.f;
       if (active) {
         const T *xp = x + p * V;
-        const Row<T, V> k = load_row<T, V>(xp + (r0 + first) * c);
+        const Piece<V> k = load_piece<T, V>(xp + (r0 + first) * c);
 #pragma unroll
         for (int j = 0; j < V; ++j) shift[j] = k.v[j];
         for (int64_t rb = r0 + rl; rb < r1; rb += (int64_t)kBnRowsPerThread * R) {
-          Row<T, V> t[kBnRowsPerThread];
+          Piece<V> t[kBnRowsPerThread];
           int bi[kBnRowsPerThread];
 #pragma unroll
           for (int i = 0; i < kBnRowsPerThread; ++i) {
             const int64_t r = min(rb + (int64_t)i * R, r1 - 1);
-            t[i] = load_row<T, V>(xp + r * c);
+            t[i] = load_piece<T, V>(xp + r * c);
             bi[i] = pure ? b : batch_row[r];
           }
 #pragma unroll
@@ -302,13 +285,13 @@ __device__ __forceinline__ void seg_bwd_partial(float *s_red, const T *__restric
         typename Grad::template State<V> st;
         grad.template load<V>(b, p * V, rs, st);
         for (int64_t rb = r0 + rl; rb < r1; rb += (int64_t)RB * R) {
-          Row<T, V> tx[RB], tg[RB];
+          Piece<V> tx[RB], tg[RB];
           int bi[RB];
 #pragma unroll
           for (int i = 0; i < RB; ++i) {
             const int64_t r = min(rb + (int64_t)i * R, r1 - 1);
-            tx[i] = load_row<T, V>(x + r * c + p * V);
-            tg[i] = load_row<T, V>(dy + r * c + p * V);
+            tx[i] = load_piece<T, V>(x + r * c + p * V);
+            tg[i] = load_piece<T, V>(dy + r * c + p * V);
             bi[i] = pure ? b : batch_row[r];
           }
 #pragma unroll
@@ -422,13 +405,13 @@ __device__ __forceinline__ void seg_rows(const T *__restrict__ x, const T *__res
   const int64_t r0 = (int64_t)blockIdx.x * R * RB;
   if (rl >= R) return;
   for (int p = (int)threadIdx.x % W; p < P; p += W) {
-    Row<T, V> tx[RB], tg[Map::kDy ? RB : 1];
+    Piece<V> tx[RB], tg[Map::kDy ? RB : 1];
     int bi[RB];
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
       const int64_t r = min(r0 + rl + (int64_t)i * R, n - 1);
-      tx[i] = load_row<T, V>(x + r * c + p * V);
-      if constexpr (Map::kDy) tg[i] = load_row<T, V>(dy + r * c + p * V);
+      tx[i] = load_piece<T, V>(x + r * c + p * V);
+      if constexpr (Map::kDy) tg[i] = load_piece<T, V>(dy + r * c + p * V);
       bi[i] = min(max(batch_row[r], 0), n_batch - 1);
     }
     typename Map::template Piece<V> pc;
@@ -437,13 +420,13 @@ __device__ __forceinline__ void seg_rows(const T *__restrict__ x, const T *__res
     for (int i = 0; i < RB; ++i) {
       const int64_t r = r0 + rl + (int64_t)i * R;
       if (i == 0 || bi[i] != bi[i - 1]) map.template load<V>(bi[i], p * V, pc);
-      Row<T, V> o;
+      Piece<V> o;
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         if constexpr (Map::kDy) o.v[j] = map.template value<V>(pc, j, tx[i].v[j], tg[i].v[j]);
         else o.v[j] = map.template value<V>(pc, j, tx[i].v[j]);
       }
-      if (r < n) store_row<T, V>(out + r * c + p * V, o);
+      if (r < n) store_piece<T, V>(out + r * c + p * V, o);
     }
   }
 }
@@ -476,57 +459,10 @@ static int64_t in_ws_layout_f32(int64_t n, int n_batch, int c, char *base, InWs 
   return 2 * part + pc + 2 * t + rw;
 }
 
-// widest piece for rows of c channels of T when every address is 16-byte aligned (as bn_stats): 16 bytes, else 4 elements
-template <typename T>
-static int in_piece(int c, std::initializer_list<const void *> ptrs) {
-  constexpr int W = 16 / (int)sizeof(T);
-  bool aligned = true;
-  for (const void *p : ptrs) aligned = aligned && (uintptr_t)p % 16 == 0;
-  return (aligned && c % W == 0) ? W : ((aligned && c % 4 == 0) ? 4 : 1);
-}
-
-// The launch of the kernels over rows of c channels of T: v channels per piece (in_piece of the pointers whose alignment
-// counts), P pieces per row, R row lanes per workgroup; `chunks` workgroups of `lds` bytes for a partial kernel with
-// `rows_in_flight` rows per thread, `grid` workgroups for a row kernel (seg_rows)
-struct SegPlan {
-  int v, P, R, chunks;
-  size_t lds;
-  dim3 grid;
-};
-template <typename T>
-static SegPlan seg_plan(int64_t n, int c, int rows_in_flight, std::initializer_list<const void *> ptrs) {
-  SegPlan pl;
-  pl.v = in_piece<T>(c, ptrs);
-  pl.P = c / pl.v;
-  pl.R = pl.P >= 256 ? 1 : 256 / pl.P;
-  pl.chunks = bn_chunks(n, pl.R, rows_in_flight);
-  pl.lds = in_partial_lds_bytes(c, pl.R);
-  pl.grid = dim3((unsigned)ceil_div(n, (int64_t)pl.R * kBnRowsPerThread));
-  return pl;
-}
-
-#define ME_IN_DISPATCH_V(T, v, ...)                            \
-  do {                                                         \
-    constexpr int W_ = 16 / (int)sizeof(T);                    \
-    if ((v) == W_) { constexpr int V = W_; __VA_ARGS__; }      \
-    else if ((v) == 4) { constexpr int V = 4; __VA_ARGS__; }   \
-    else { constexpr int V = 1; __VA_ARGS__; }                 \
-  } while (0)
-
 // seg_rows over the plan's grid with the map `map`; dy is NULL for a map that does not read it
-#define ME_SEG_ROWS(T, pl, stream, x, dy, batch_row, n, c, n_batch, map, out)                                          \
-  ME_IN_DISPATCH_V(T, (pl).v, hipLaunchKernelGGL((k_seg_rows<T, V, std::decay_t<decltype(map)>>), (pl).grid, dim3(256), 0,   \
-                                                 stream, x, dy, batch_row, n, c, n_batch, map, out))
-
-// the body of an extern "C" entry point whose rows are float or, with is_bf16, __bf16: `return call;` with T the row type
-#define ME_SEG_RETURN_T(is_bf16, ...)          \
-  do {                                         \
-    if (is_bf16) {                             \
-      using T = __bf16;                        \
-      return __VA_ARGS__;                      \
-    }                                          \
-    using T = float;                           \
-    return __VA_ARGS__;                        \
-  } while (0)
+#define ME_SEG_ROWS(T, pl, stream, x, dy, batch_row, n, c, n_batch, map, out)                                     \
+  ME_PIECE_DISPATCH(T, kPieceNorm, (pl).v,                                                                        \
+                    hipLaunchKernelGGL((k_seg_rows<T, V, std::decay_t<decltype(map)>>), (pl).grid, dim3(256), 0, \
+                                       stream, x, dy, batch_row, n, c, n_batch, map, out))
 
 }  // namespace me

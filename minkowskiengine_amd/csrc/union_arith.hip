@@ -16,9 +16,7 @@
 //   * k_union_bw_a / k_union_bw_b: every input row has exactly one union row, so a gradient row is a gather of dOut times
 //     the local derivative; nothing is reduced, nothing to order.  One launch per wanted gradient.
 // bf16 rows are widened to fp32, combined there and rounded once at the store.
-#include "common.hpp"
-
-#include <initializer_list>
+#include "piece.hpp"
 
 namespace me {
 namespace uarith {
@@ -39,37 +37,6 @@ __global__ __launch_bounds__(256) void k_tables(const int64_t *__restrict__ a_un
   const bool ok = u >= 0 && u < nu;
   (is_a ? u_of_a : u_of_b)[r] = ok ? (int32_t)u : -1;
   if (ok) (is_a ? a_of_u : b_of_u)[u] = (int32_t)r;
-}
-
-// ---- 16-byte pieces ------------------------------------------------------------------------------------------------------
-template <typename T, int V>
-struct Piece {
-  T v[V];
-};
-template <typename T, int V>
-__device__ __forceinline__ Piece<T, V> load_piece(const T *p) {
-  Piece<T, V> r;
-  if constexpr (V == 1) {
-    r.v[0] = *p;
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    const tvec t = *reinterpret_cast<const tvec *>(p);
-#pragma unroll
-    for (int j = 0; j < V; ++j) r.v[j] = t[j];
-  }
-  return r;
-}
-template <typename T, int V>
-__device__ __forceinline__ void store_piece(T *p, const Piece<T, V> &r) {
-  if constexpr (V == 1) {
-    *p = r.v[0];
-  } else {
-    typedef T tvec __attribute__((ext_vector_type(V)));
-    tvec t;
-#pragma unroll
-    for (int j = 0; j < V; ++j) t[j] = r.v[j];
-    *reinterpret_cast<tvec *>(p) = t;
-  }
 }
 
 template <int OP, typename A>
@@ -94,15 +61,15 @@ __global__ __launch_bounds__(256) void k_union_fw(const T *__restrict__ a, const
   const int ch = (int)(idx % pieces) * V;
   const int32_t ia = a_of_u[u], ib = b_of_u[u];
   const bool ha = ia >= 0 && ia < na, hb = ib >= 0 && ib < nb;
-  const Piece<T, V> av = load_piece<T, V>(a + (int64_t)(ha ? ia : 0) * c + ch);
-  const Piece<T, V> bv = load_piece<T, V>(b + (int64_t)(hb ? ib : 0) * c + ch);
-  Piece<T, V> o;
+  const Piece<V, T> av = load_piece<T, V, T>(a + (int64_t)(ha ? ia : 0) * c + ch);
+  const Piece<V, T> bv = load_piece<T, V, T>(b + (int64_t)(hb ? ib : 0) * c + ch);
+  Piece<V, T> o;
 #pragma unroll
   for (int j = 0; j < V; ++j) {
     const T x = ha ? av.v[j] : (T)0;
     o.v[j] = hb ? (T)apply<OP, A>((A)x, (A)bv.v[j]) : x;
   }
-  store_piece<T, V>(out + u * c + ch, o);
+  store_piece<T, V, T>(out + u * c + ch, o);
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------------
@@ -119,22 +86,22 @@ __global__ __launch_bounds__(256) void k_union_bw_a(const T *__restrict__ g, con
   const int ch = (int)(idx % pieces) * V;
   const int32_t u = u_of_a[i];
   const bool hu = u >= 0 && u < nu;
-  const Piece<T, V> gv = load_piece<T, V>(g + (int64_t)(hu ? u : 0) * c + ch);
-  Piece<T, V> o;
+  const Piece<V, T> gv = load_piece<T, V, T>(g + (int64_t)(hu ? u : 0) * c + ch);
+  Piece<V, T> o;
   if constexpr (OP == ME_UNION_ADD || OP == ME_UNION_SUB) {
 #pragma unroll
     for (int j = 0; j < V; ++j) o.v[j] = hu ? gv.v[j] : (T)0;
   } else {
     const int32_t ib = b_of_u[hu ? u : 0];
     const bool hb = hu && ib >= 0 && ib < nb;
-    const Piece<T, V> bv = load_piece<T, V>(b + (int64_t)(hb ? ib : 0) * c + ch);
+    const Piece<V, T> bv = load_piece<T, V, T>(b + (int64_t)(hb ? ib : 0) * c + ch);
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       const T gj = hu ? gv.v[j] : (T)0;
       o.v[j] = hb ? (T)apply<OP, A>((A)gj, (A)bv.v[j]) : gj;     // g * b, g / b
     }
   }
-  store_piece<T, V>(ga + i * c + ch, o);
+  store_piece<T, V, T>(ga + i * c + ch, o);
 }
 
 // grad_b[j] = dOut[u] * d fn(x, b) / d b with x = a's row, or 0 where a has none: g, -g, g * x, -g * ((x / b) / b) (the
@@ -151,8 +118,8 @@ __global__ __launch_bounds__(256) void k_union_bw_b(const T *__restrict__ g, con
   const int ch = (int)(idx % pieces) * V;
   const int32_t u = u_of_b[i];
   const bool hu = u >= 0 && u < nu;
-  const Piece<T, V> gv = load_piece<T, V>(g + (int64_t)(hu ? u : 0) * c + ch);
-  Piece<T, V> o;
+  const Piece<V, T> gv = load_piece<T, V, T>(g + (int64_t)(hu ? u : 0) * c + ch);
+  Piece<V, T> o;
   if constexpr (OP == ME_UNION_ADD) {
 #pragma unroll
     for (int j = 0; j < V; ++j) o.v[j] = hu ? gv.v[j] : (T)0;
@@ -162,9 +129,9 @@ __global__ __launch_bounds__(256) void k_union_bw_b(const T *__restrict__ g, con
   } else {
     const int32_t ia = a_of_u[hu ? u : 0];
     const bool ha = hu && ia >= 0 && ia < na;
-    const Piece<T, V> av = load_piece<T, V>(a + (int64_t)(ha ? ia : 0) * c + ch);
-    Piece<T, V> bv;
-    if constexpr (OP == ME_UNION_DIV) bv = load_piece<T, V>(b + i * c + ch);
+    const Piece<V, T> av = load_piece<T, V, T>(a + (int64_t)(ha ? ia : 0) * c + ch);
+    Piece<V, T> bv;
+    if constexpr (OP == ME_UNION_DIV) bv = load_piece<T, V, T>(b + i * c + ch);
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       const A gj = hu ? (A)gv.v[j] : (A)0, x = ha ? (A)av.v[j] : (A)0;
@@ -176,23 +143,10 @@ __global__ __launch_bounds__(256) void k_union_bw_b(const T *__restrict__ g, con
       }
     }
   }
-  store_piece<T, V>(gb + i * c + ch, o);
+  store_piece<T, V, T>(gb + i * c + ch, o);
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------
-inline bool aligned(std::initializer_list<const void *> ps, uintptr_t al) {
-  for (const void *p : ps)
-    if (p != nullptr && (uintptr_t)p % al != 0) return false;
-  return true;
-}
-
-// a piece is 16 bytes when c and the pointers allow (4 fp32, 8 bf16, 2 double), else 8 bytes, else one channel
-template <typename T>
-inline int piece_width(int32_t c, std::initializer_list<const void *> ps) {
-  constexpr int W = 16 / (int)sizeof(T), H = 8 / (int)sizeof(T);
-  return (c % W == 0 && aligned(ps, 16)) ? W : (H > 1 && c % H == 0 && aligned(ps, 8)) ? H : 1;
-}
-
 #define ME_UARITH_OP(op, ...)                                                                    \
   switch (op) {                                                                                  \
     case ME_UNION_ADD: { constexpr int OP = ME_UNION_ADD; __VA_ARGS__; break; }                  \
@@ -201,13 +155,6 @@ inline int piece_width(int32_t c, std::initializer_list<const void *> ps) {
     case ME_UNION_DIV: { constexpr int OP = ME_UNION_DIV; __VA_ARGS__; break; }                  \
     default: ME_FAIL("op must be ME_UNION_ADD, _SUB, _MUL or _DIV");                             \
   }
-#define ME_UARITH_WIDTH(T, v, ...)                                                               \
-  do {                                                                                           \
-    constexpr int W_ = 16 / (int)sizeof(T), H_ = (8 / (int)sizeof(T) > 1) ? 8 / (int)sizeof(T) : 1; \
-    if (v == W_) { constexpr int V = W_; __VA_ARGS__; }                                          \
-    else if (H_ > 1 && v == H_) { constexpr int V = H_; __VA_ARGS__; }                           \
-    else { constexpr int V = 1; __VA_ARGS__; }                                                   \
-  } while (0)
 
 inline int check_sizes(int32_t c, int64_t na, int64_t nb, int64_t nu, int32_t op) {
   ME_CHECK(c > 0, "invalid channel count");
@@ -228,12 +175,13 @@ int forward(const T *a, const T *b, int32_t c, const int32_t *a_of_u, const int3
   // an input without rows is never selected: any readable row stands in for it (nu > 0, so the other one has rows)
   if (na == 0) a = b;
   if (nb == 0) b = a;
-  const int v = piece_width<T>(c, {a, b, out});
+  const int v = piece_width<T>(kPieceHalf, c, {a, b, out});
   const int64_t total = nu * (c / v);
   ME_CHECK(ceil_div(total, 256) < (1ll << 31), "Nu * C too large for one launch");
   const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  ME_UARITH_OP(op, ME_UARITH_WIDTH(T, v, hipLaunchKernelGGL((k_union_fw<T, A, V, OP>), grid, block, 0, stream, a, b, c,
-                                                            a_of_u, b_of_u, na, nb, nu, out)));
+  ME_UARITH_OP(op, ME_PIECE_DISPATCH(T, kPieceHalf, v,
+                                     hipLaunchKernelGGL((k_union_fw<T, A, V, OP>), grid, block, 0, stream, a, b, c, a_of_u,
+                                                        b_of_u, na, nb, nu, out)));
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -249,12 +197,13 @@ int backward(const T *g, const T *a, const T *b, int32_t c, const int32_t *u_of_
     ME_CHECK(nu > 0 && u_of_a != nullptr, "u_of_a must be given");
     ME_CHECK(!mul_div || (b_of_u != nullptr && (nb == 0 || b != nullptr)), "b and b_of_u must be given for * and /");
     const T *bb = (mul_div && nb > 0) ? b : g;       // nb == 0: never selected
-    const int v = piece_width<T>(c, {g, bb, ga});
+    const int v = piece_width<T>(kPieceHalf, c, {g, bb, ga});
     const int64_t total = na * (c / v);
     ME_CHECK(ceil_div(total, 256) < (1ll << 31), "Na * C too large for one launch");
     const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-    ME_UARITH_OP(op, ME_UARITH_WIDTH(T, v, hipLaunchKernelGGL((k_union_bw_a<T, A, V, OP>), grid, block, 0, stream, g, bb,
-                                                              c, u_of_a, b_of_u, na, nb, nu, ga)));
+    ME_UARITH_OP(op, ME_PIECE_DISPATCH(T, kPieceHalf, v,
+                                       hipLaunchKernelGGL((k_union_bw_a<T, A, V, OP>), grid, block, 0, stream, g, bb, c,
+                                                          u_of_a, b_of_u, na, nb, nu, ga)));
     ME_LAUNCH_CHECK();
   }
   if (gb != nullptr && nb > 0) {
@@ -263,12 +212,13 @@ int backward(const T *g, const T *a, const T *b, int32_t c, const int32_t *u_of_
     ME_CHECK(op != ME_UNION_DIV || b != nullptr, "b must be given for /");
     const T *aa = (mul_div && na > 0) ? a : g;       // na == 0: never selected
     const T *bb = op == ME_UNION_DIV ? b : g;
-    const int v = piece_width<T>(c, {g, aa, bb, gb});
+    const int v = piece_width<T>(kPieceHalf, c, {g, aa, bb, gb});
     const int64_t total = nb * (c / v);
     ME_CHECK(ceil_div(total, 256) < (1ll << 31), "Nb * C too large for one launch");
     const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-    ME_UARITH_OP(op, ME_UARITH_WIDTH(T, v, hipLaunchKernelGGL((k_union_bw_b<T, A, V, OP>), grid, block, 0, stream, g, aa,
-                                                              bb, c, u_of_b, a_of_u, na, nb, nu, gb)));
+    ME_UARITH_OP(op, ME_PIECE_DISPATCH(T, kPieceHalf, v,
+                                       hipLaunchKernelGGL((k_union_bw_b<T, A, V, OP>), grid, block, 0, stream, g, aa, bb,
+                                                          c, u_of_b, a_of_u, na, nb, nu, gb)));
     ME_LAUNCH_CHECK();
   }
   return 0;

@@ -82,3 +82,17 @@ def row_mapping(coords_a, coords_b):
     m = np.empty(len(ra), np.int64)
     m[ra] = rb
     return m
+
+
+def placed(t, how):
+    """A copy of the contiguous tensor t at a chosen address: "alloc" from the allocator (aligned far beyond 16 bytes),
+    "8" a contiguous view that starts 8 bytes into its storage and ends at the storage's end, "1" one that starts one
+    element into its storage.  The vector width of a HIP kernel follows the address; its result must not."""
+    if how == "alloc":
+        return t.clone()
+    pad = 8 // t.element_size() if how == "8" else 1
+    buf = torch.empty(pad + t.numel(), dtype=t.dtype, device=t.device)
+    v = buf[pad:].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and buf.data_ptr() % 16 == 0 and v.data_ptr() == buf.data_ptr() + pad * t.element_size()
+    return v

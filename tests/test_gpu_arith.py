@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import assert_close, make_cloud, row_mapping
+from helpers import assert_close, make_cloud, placed, row_mapping
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,6 +122,66 @@ def test_channel_counts(c, dtype, host_layer, device):
         tol = {torch.float32: 1e-6, torch.float64: 1e-12, torch.bfloat16: 2 ** -7}[dtype]
         assert_close(xa.grad.double().cpu().numpy(), ra.grad.double().numpy(), tol, tol, f"{op} grad_a")
         assert_close(xb.grad.double().cpu().numpy(), rb.grad.double().numpy(), tol, tol, f"{op} grad_b")
+
+
+_WIDTH_CASES = [(torch.float32, 8), (torch.float32, 6), (torch.float32, 7), (torch.bfloat16, 16), (torch.bfloat16, 12),
+                (torch.bfloat16, 7), (torch.float64, 4), (torch.float64, 3)]
+
+
+@pytest.mark.parametrize("dtype,c", _WIDTH_CASES, ids=[f"{str(d)[6:]}-c{c}" for d, c in _WIDTH_CASES])
+def test_piece_widths_and_unaligned_views(dtype, c, device):
+    """The piece width of the forward and of both backward kernels follows c and the addresses (16 bytes, 8 bytes, one
+    channel: fp32 c = 8 / 6 / 7, bf16 16 / 12 / 7, float64 4 / 3); the operators are element-wise, so no address may
+    change a bit.  Every feature tensor of the C entry points (a, b, out; grad_out, a, b, grad_a, grad_b), one at a time
+    and all together, goes 8 bytes and one element into its storage: results and gradients bit-equal to the call on
+    allocator addresses, which is the backend's own."""
+    from minkowskiengine_amd import _lib, backend
+    lib = _lib.load()
+    sfx = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float64: "f64"}[dtype]
+    fw, bw = getattr(lib, "me_union_arith_" + sfx), getattr(lib, "me_union_arith_backward_" + sfx)
+    rng = np.random.default_rng(c)
+    na = nb = 600
+    nu = 900                                                # 300 rows of each input are the other's too
+    u_of_a = rng.permutation(nu)[:na]
+    b_only = np.setdiff1d(np.arange(nu), u_of_a)
+    u_of_b = rng.permutation(np.concatenate([b_only, rng.choice(u_of_a, nb - len(b_only), replace=False)]))
+    a_of_u, b_of_u = np.full(nu, -1), np.full(nu, -1)
+    a_of_u[u_of_a], b_of_u[u_of_b] = np.arange(na), np.arange(nb)
+    ua, ub, au, bu = (torch.from_numpy(v.astype(np.int32)).to(device) for v in (u_of_a, u_of_b, a_of_u, b_of_u))
+    g = torch.Generator().manual_seed(c)
+    a = torch.randn(na, c, generator=g).to(dtype).to(device)
+    b = (torch.rand(nb, c, generator=g) + 0.5).to(dtype).to(device)
+    go = torch.randn(nu, c, generator=g).to(dtype).to(device)
+    bits = lambda t: t.contiguous().view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])  # noqa: E731
+    stream = torch.cuda.current_stream(device).cuda_stream
+
+    def forward(code, how):
+        pa, pb, out = placed(a, how["a"]), placed(b, how["b"]), placed(torch.zeros_like(go), how["out"])
+        with torch.cuda.device(device):
+            _lib.check(fw(pa.data_ptr(), pb.data_ptr(), c, au.data_ptr(), bu.data_ptr(), na, nb, nu, code, out.data_ptr(),
+                          stream))
+        return [bits(out)]
+
+    def backward(code, how):
+        pg, pa, pb = placed(go, how["g"]), placed(a, how["a"]), placed(b, how["b"])
+        ga, gb = placed(torch.zeros_like(a), how["ga"]), placed(torch.zeros_like(b), how["gb"])
+        with torch.cuda.device(device):
+            _lib.check(bw(pg.data_ptr(), pa.data_ptr(), pb.data_ptr(), c, ua.data_ptr(), ub.data_ptr(), au.data_ptr(),
+                          bu.data_ptr(), na, nb, nu, code, ga.data_ptr(), gb.data_ptr(), stream))
+        return [bits(ga), bits(gb)]
+
+    for op in OPS:
+        code = backend._union_arith_op(op)
+        for run, names in ((forward, ("a", "b", "out")), (backward, ("g", "a", "b", "ga", "gb"))):
+            base = dict.fromkeys(names, "alloc")
+            want = run(code, base)
+            mine = [backend.union_arith_fw(a, b, au, bu, op)] if run is forward else \
+                backend.union_arith_bw(go, a, b, ua, ub, au, bu, op)
+            assert all(torch.equal(w, bits(m)) for w, m in zip(want, mine)), op
+            for off in ("8", "1"):
+                for how in [dict(base, **{n: off}) for n in names] + [dict.fromkeys(names, off)]:
+                    got = run(code, how)
+                    assert all(torch.equal(w, v) for w, v in zip(want, got)), (op, run.__name__, how)
 
 
 @pytest.mark.parametrize("op", list(OPS))

@@ -120,6 +120,55 @@ def test_negative_empty_ties_shared(itype, dtype, host_layer, device):
     assert bool((np.bincount(widx[widx < marker].astype(np.int64)) > 1).any())   # the case does hold shared winners
 
 
+_WIDTH_CASES = [(torch.float32, 8), (torch.float32, 6), (torch.float32, 7), (torch.bfloat16, 16), (torch.bfloat16, 12),
+                (torch.bfloat16, 7), (torch.float64, 4), (torch.float64, 3)]
+
+
+@pytest.mark.parametrize("itype", [torch.int32, torch.int64], ids=["i32", "i64"])
+@pytest.mark.parametrize("dtype,c", _WIDTH_CASES, ids=[f"{str(d)[6:]}-c{c}" for d, c in _WIDTH_CASES])
+def test_piece_widths_and_unaligned_views(dtype, c, itype, device):
+    """The piece of k_direct_max follows c and the addresses of in_feat, out_feat and max_index (16 bytes, 8 bytes, one
+    channel: fp32 c = 8 / 6 / 7, bf16 16 / 12 / 7, float64 4 / 3); a maximum and its index do not depend on the width.
+    in_feat and out_feat go 8 bytes and one element into their storage, one at a time and together; then, on allocator
+    addresses, max_index alone goes half a wide mask piece (and one element) into its storage, so that only the mask
+    forbids the wide piece.  Outputs and masks bit-equal to the call on allocator addresses, which is the backend's."""
+    from helpers import placed
+    from minkowskiengine_amd import _lib, backend
+    lib = _lib.load()
+    fn = getattr(lib, "me_direct_max_pool_" + {torch.float32: "f32", torch.bfloat16: "bf16", torch.float64: "f64"}[dtype])
+    rng = np.random.default_rng(c)
+    n_in, n_out = 700, 500
+    om = rng.permutation(np.repeat(np.arange(n_out), rng.integers(1, 5, n_out)))     # 1 to 4 inputs per output row
+    nmap = len(om)
+    im = torch.from_numpy(rng.integers(0, n_in, nmap)).to(itype).to(device)
+    om = torch.from_numpy(om).to(itype).to(device)
+    x = torch.from_numpy(rng.integers(-8, 9, (n_in, c)) / 4.0).to(dtype).to(device)   # exact in bf16, with ties
+    ws = torch.empty(lib.me_direct_max_pool_workspace_bytes(nmap, n_out), dtype=torch.uint8, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    bits = lambda t: t.contiguous().view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])  # noqa: E731
+
+    def run(hx="alloc", hy="alloc", mask_pad=0):
+        px, y = placed(x, hx), placed(torch.zeros(n_out, c, dtype=dtype, device=device), hy)
+        buf = torch.zeros(mask_pad + n_out * c, dtype=itype, device=device)
+        mask = buf[mask_pad:].view(n_out, c)
+        assert buf.data_ptr() % 64 == 0 and mask.data_ptr() == buf.data_ptr() + mask_pad * buf.element_size()
+        with torch.cuda.device(device):
+            _lib.check(fn(px.data_ptr(), c, im.data_ptr(), om.data_ptr(), im.element_size(), nmap, n_in, n_out, 0,
+                          y.data_ptr(), mask.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+        return bits(y), mask.clone()
+
+    want = run()
+    mine = backend.direct_max_pool_fw(im, om, x, n_out, False)
+    assert torch.equal(want[0], bits(mine[0])) and torch.equal(want[1], mine[1])
+    wide = 16 // x.element_size()
+    pads = sorted({wide // 2, 1} if c % wide == 0 else {1})  # half a wide mask piece: aligned for the 8-byte piece only
+    cases = [dict(hx=o) for o in ("8", "1")] + [dict(hy=o) for o in ("8", "1")] + [dict(hx=o, hy=o) for o in ("8", "1")] + \
+        [dict(mask_pad=p) for p in pads]
+    for how in cases:
+        got = run(**how)
+        assert torch.equal(want[0], got[0]) and torch.equal(want[1], got[1]), how
+
+
 def test_tie_first_entry_wins(host_layer, device):
     C = _C()
     f = torch.tensor([[1.0], [1.0], [1.0], [0.5]], device=device)

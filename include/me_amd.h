@@ -572,11 +572,13 @@ int me_conv_halo_bf16(const uint16_t *src_feat_dev, int64_t n_src, int32_t c_src
 /* ---- bf16 convolution with the offsets stacked into the MFMA reduction (csrc/conv_stem.hip, ABI 1.5) -------------
  * For layers with AT MOST 8 source channels (a network's stem: 3 -> 32 channels over 5^3 offsets): one MFMA step
  * multiplies FOUR offsets (4 x 8 channels = its 32-deep reduction), every neighbour row is one 16-byte load, a wave keeps
- * 32 target rows x all output columns in registers over all offsets; the weights are read from the layer's OWN kernel
+ * 16 G target rows (G = 4 under the policy: 64) x all output columns in registers over all offsets; the weights are read from the layer's OWN kernel
  * tensor (no packed image) and kept in LDS as MFMA fragments.  The reference runs one gather - GEMM - scatter launch per
  * offset (src/convolution_kernel.cu:320-496).  Semantics of me_conv_target_bf16 (weights rounded to bf16, exact products,
  * fp32 sums in a fixed order, one rounding); results are bitwise reproducible, not the bits of the tile-plan kernel.
- *   me_conv_stem_use_bf16   the policy both hosts follow: c_src <= 8, c_dst in {16, 32, 64}, volume >= 8 (ME_AMD_STEM=0 | 1)
+ *   me_conv_stem_use_bf16   the policy both hosts follow: c_src <= 8, c_dst in {16, 32, 64}, volume >= 8 (ME_AMD_STEM=0 | 1);
+ *                           the weight fragments of all offsets (volume rounded up to 16) share 80 KB of LDS with the
+ *                           statistics: volume <= 304 / 144 / 64 for c_dst = 16 / 32 / 64
  *   me_conv_stem_tile_rows  rows per tile (256): the tile of the batch-norm partials
  *   me_conv_stem_bf16       src_feat_dev bf16 [n_src, 8] (rows padded with zeros to 8 channels, 16-byte aligned; c_src
  *                           must be 8), w_dev the kernel [volume, 8, c_dst] (transposed != 0: [volume, c_dst, 8]) in

@@ -314,6 +314,7 @@ DEBUG_SIGNATURES = {
     "me_debug_set_halo": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "me_debug_halo_mode": (c_i32, []),
     "me_debug_set_stem": (None, [ctypes.c_int, ctypes.c_int]),
+    "me_debug_set_stem_tiles_per_wg": (None, [ctypes.c_int]),
     "me_debug_halo_timing": (ctypes.c_int, [c_vp, c_i32]),
     "me_debug_set_bf16_ws_fuse": (None, [ctypes.c_int]),
     "me_debug_set_bf16_ws_depth": (None, [ctypes.c_int]),

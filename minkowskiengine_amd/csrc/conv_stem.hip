@@ -29,7 +29,7 @@ __host__ __device__ constexpr int conv_stem_lds(int nq4, int cb) {
 }
 
 // W fragments of the whole kernel into LDS: fragment (j, cb), lane (i16, q) = W[4 j + q][0..7][cb * 16 + i16], zeros for the
-// offsets beyond `volume` (the walk runs over nq4 = a multiple of four quads and loads clamped neighbours there)
+// offsets beyond `volume` (the walk runs over nq4 = a multiple of four quads, loads clamped neighbours there and masks them)
 template <int CB, typename WT>
 __device__ __forceinline__ void stem_stage_weights(bf16x8 *s_w, const WT *__restrict__ w, int transposed, int volume, int nq4,
                                                    int tid) {
@@ -125,6 +125,9 @@ __global__ __launch_bounds__(64 * kStemWaves, 2) void k_conv_stem_bf16(
       }
     }
     uint32_t kq = (uint32_t)q * k_pitch;            // byte offset of offset 4 jj + q, clamped to the last offset below
+    // the rows of quad s are requested right before the indices of quad s + 4, at kq = (4 s + 16 + q) k_pitch: offset
+    // 4 s + q lies within the kernel while kq is below this bound (no wrap: stem_shape keeps (volume + 43) k_pitch in 32 bits)
+    const uint32_t kq_live = (uint32_t)(volume + 16) * k_pitch;
     auto issue_idx = [&](int32_t (&dst_ix)[G]) {
       const uint32_t kk = min(kq, k_last);
       kq += 4u * k_pitch;
@@ -133,9 +136,12 @@ __global__ __launch_bounds__(64 * kStemWaves, 2) void k_conv_stem_bf16(
         asm volatile("global_load_dword %0, %1, %2" : "+v"(dst_ix[g]) : "v"(kk + col4[g]), "s"(tbl) : "memory");
     };
     auto issue_rows = [&](const int32_t (&src_ix)[G], bf16x8 (&dst_x)[G], uint32_t (&dst_keep)[G]) {
+      // a slot beyond `volume` holds the clamped neighbour of the last offset: masked like an absent one — its weights are
+      // zero, and 0 x Inf would leave a NaN
+      const uint32_t live = kq < kq_live ? ~0u : 0u;
 #pragma unroll
       for (int g = 0; g < G; ++g) {
-        dst_keep[g] = ~(uint32_t)(src_ix[g] >> 31);
+        dst_keep[g] = ~(uint32_t)(src_ix[g] >> 31) & live;
         asm volatile("" : "+v"(dst_keep[g]));
         const uint32_t off = (uint32_t)max(src_ix[g], 0) << 4;
         asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(dst_x[g]) : "v"(off), "s"(src) : "memory");
@@ -251,11 +257,14 @@ __global__ __launch_bounds__(64 * kStemWaves, 2) void k_conv_stem_bf16(
 
 int g_stem_mode = -1;    // me_debug_set_stem: -1 policy (ME_AMD_STEM), 0 never, 1 wherever the shape is supported
 int g_stem_g = 0;        // 16-row groups per wave: 0 policy (4: tiles of 256 rows), 1 | 2 | 4
+int g_stem_tpw = 0;      // me_debug_set_stem_tiles_per_wg: 0 policy, N >= 1 tiles per workgroup (tests: multi-tile walks on small maps)
 
 // (MI355X, 200k voxels: 3 -> 32 over 5^3 offsets 58 / 45 / 40 us with 1 / 2 / 4 groups; profiles/r05_stem_sweep.txt)
 static int stem_groups() { return g_stem_g ? g_stem_g : 4; }
 
 static bool stem_shape(int64_t n_tgt, int64_t volume, int c_src, int c_dst) {
+  // (volume <= 512 only keeps the int arithmetic below small: the LDS clause binds first — the fragments of volume rounded
+  // up to 16 offsets, 1 KB per quad and column block, within 80 KB: volume <= 304 / 144 / 64 for c_dst = 16 / 32 / 64)
   return volume >= 1 && volume <= 512 && c_src == 8 && (c_dst == 16 || c_dst == 32 || c_dst == 64) &&
          conv_stem_lds((int)((volume + 15) / 16 * 4), c_dst / 16) <= kLdsBudget / 2 &&
          // 32-bit byte offsets into the neighbour table — of the clamped look-ahead as well: the walk counts up to offset
@@ -272,6 +281,7 @@ extern "C" void me_debug_set_stem(int mode, int groups) {
   g_stem_mode = mode;
   g_stem_g = (groups == 1 || groups == 2 || groups == 4) ? groups : 0;
 }
+extern "C" void me_debug_set_stem_tiles_per_wg(int n) { g_stem_tpw = n >= 1 ? n : 0; }
 
 // 1: this launch runs on the stacked-offset kernel (feature rows of exactly 8 channels — pad with zeros —, 16 / 32 / 64
 // output channels, bf16 features; ME_AMD_STEM=0 keeps the tile-plan kernels).  The policy both hosts follow.
@@ -324,7 +334,7 @@ extern "C" int me_conv_stem_bf16(const uint16_t *src_feat_dev, int64_t n_src, in
   const int64_t tiles = ceil_div(n_tgt, 16 * g * kStemWaves);
   // persistent workgroups (the weights are staged once per workgroup), two per CU; the same number of tiles for all
   const int64_t slots = (int64_t)device_cu_count() * 2;
-  const int64_t rounds = ceil_div(tiles, slots);
+  const int64_t rounds = g_stem_tpw ? g_stem_tpw : ceil_div(tiles, slots);
   const dim3 grid((unsigned)ceil_div(tiles, rounds));
   hipStream_t st = (hipStream_t)stream;
   const __bf16 *src = reinterpret_cast<const __bf16 *>(src_feat_dev);

@@ -265,6 +265,13 @@ def test_stem_policy_keeps_32_bit_table_offsets_in_range():
         assert (volume + 42) * (limit - 1) * 4 + (limit - 1) * 4 < (1 << 32)
     assert lib.me_conv_stem_use_bf16(200000, 125, 8, 128) == 0 and lib.me_conv_stem_use_bf16(200000, 125, 16, 32) == 0
     assert lib.me_conv_stem_tile_rows() == 256
+    # the volume limits are those of the LDS: the weight fragments of volume rounded up to 16 offsets (1 KB per offset quad
+    # and 16-column block) and the statistics (1152 bytes per block) within 80 KB — two workgroups per CU
+    for c_dst, limit in ((16, 304), (32, 144), (64, 64)):
+        blocks = c_dst // 16
+        assert blocks * (limit // 4 * 1024 + 1152) <= 80 * 1024 < blocks * ((limit + 16) // 4 * 1024 + 1152)
+        assert lib.me_conv_stem_use_bf16(200000, limit, 8, c_dst) == 1, c_dst
+        assert lib.me_conv_stem_use_bf16(200000, limit + 1, 8, c_dst) == 0, c_dst
 
 
 def test_halo_plan_waits_for_the_second_launch_on_a_side(monkeypatch):

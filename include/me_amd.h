@@ -613,6 +613,32 @@ int me_conv_target_f32x3(const float *src_feat_dev, int64_t n_src, int32_t c_src
                          const int32_t *order_dev, float *dst_feat_dev,
                          int64_t n_tgt, int32_t tile_rows, int32_t batch_groups, void *stream);
 
+/* ---- backward pass of a split-fp32 layer in two launches instead of three ---------------------------------------
+ * me_conv_wgrad_f32 is two launches (partial images per pair range, then their reduce into grad_w); the reduce is
+ * latency-bound and leaves the GPU almost idle.  Where the layer's weight gradient is the split kernel
+ * (me_conv_wgrad_is_split_f32) and its input gradient the wave-specialised me_conv_target_f32x3 kernel, the reduce
+ * can ride behind the tiles of the input-gradient launch instead, on the CUs that run out of tiles first:
+ *   1. me_conv_wgrad_partials_f32        (arguments of me_conv_wgrad_f32 without grad_w): the partial images only;
+ *   2. me_conv_dgrad_reduce_tail_f32x3   (arguments of me_conv_target_f32x3 for the input gradient — source dy with
+ *                                        c_out channels, target dx with c_in — then the pair offsets, the workspace of
+ *                                        step 1 and grad_w): dx, and grad_w bit-identical to me_conv_wgrad_f32's.
+ * Same stream, in this order; stream order is the only synchronisation.  n_in must be positive.
+ * me_conv_dgrad_reduce_tail_supported: 1 where both kernels exist for the layer AND the tail is short enough to pay
+ * (a tail workgroup owns a CU, so wide layers keep the separate reduce); 0: use the three launches. */
+int32_t me_conv_wgrad_is_split_f32(int32_t c_in, int32_t c_out);
+int me_conv_wgrad_partials_f32(const float *x_dev, int64_t n_in, int32_t c_in, const float *dy_dev, int64_t n_out,
+                               int32_t c_out, const int32_t *in_pairs_dev, const int32_t *out_pairs_dev,
+                               const int64_t *k_offsets /* host */, const int64_t *k_offsets_dev, int64_t volume,
+                               void *workspace_dev, int64_t workspace_bytes, void *stream);
+int32_t me_conv_dgrad_reduce_tail_supported(int32_t c_in, int32_t c_out, int64_t volume, int64_t n_pairs);
+int me_conv_dgrad_reduce_tail_f32x3(const float *dy_dev, int64_t n_out, int32_t c_out, const uint16_t *packed_w_dev,
+                                    int64_t volume, int32_t c_in, const int32_t *plan_src_dev,
+                                    const int32_t *plan_dst_dev, const int32_t *batch_desc_dev,
+                                    const int32_t *tile_bptr_dev, const int32_t *order_dev, float *dx_dev, int64_t n_in,
+                                    int32_t tile_rows, int32_t batch_groups, const int64_t *k_offsets /* host */,
+                                    const int64_t *k_offsets_dev, const void *workspace_dev, int64_t workspace_bytes,
+                                    float *grad_w_dev, void *stream);
+
 /* ---- weights of many layers packed by ONE launch (csrc/pack.hip) ------------------------------------------
  * The packed images above only change when the weights do (the optimizer step), not per activation: a network packs
  * all its (layer, direction) images at once instead of twice per layer and step (MinkUNet34C: 126 launches -> 1).

@@ -187,6 +187,14 @@ SIGNATURES = {
     "me_conv_pack_weights_f32x3": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "me_conv_target_f32x3": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_vp, c_i64, c_i32, c_i32, c_vp]),
+    # backward pass of a split-fp32 layer in two launches: partial images, then dgrad with the reduce as its tail
+    "me_conv_wgrad_is_split_f32": (c_i32, [c_i32, c_i32]),
+    "me_conv_wgrad_partials_f32": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, _P_I64, c_vp, c_i64,
+                                                  c_vp, c_i64, c_vp]),
+    "me_conv_dgrad_reduce_tail_supported": (c_i32, [c_i32, c_i32, c_i64, c_i64]),
+    "me_conv_dgrad_reduce_tail_f32x3": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                                       c_vp, c_vp, c_i64, c_i32, c_i32, _P_I64, c_vp, c_vp, c_i64, c_vp,
+                                                       c_vp]),
     "me_conv_stem_use_bf16": (c_i32, [c_i64, c_i64, c_i32, c_i32]),
     "me_conv_stem_tile_rows": (c_i32, []),
     "me_conv_stem_bf16": (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
@@ -303,6 +311,7 @@ DEBUG_SIGNATURES = {
     "me_debug_conv_timing_f32x3": (ctypes.c_int, [c_vp, c_i32]),
     "me_debug_set_wgrad_config": (None, [ctypes.c_int, ctypes.c_int]),
     "me_debug_set_wgrad_order": (None, [ctypes.c_int]),
+    "me_debug_set_dgrad_reduce_tail": (None, [ctypes.c_int]),
     "me_debug_set_wgrad_ws": (None, [ctypes.c_int]),
     "me_debug_set_tile_dispatch": (None, [ctypes.c_int]),
     "me_debug_set_wgrad_mb": (None, [ctypes.c_int]),

@@ -1546,6 +1546,8 @@ class KernelTimer:
 
 
 KERNEL_TIMER = None  # set to a KernelTimer() to time launches
+# (labels: in the two-launch backward order of _conv_backward "conv_wgrad" is the first pass of the weight gradient only;
+# its reduce is the tail of the input-gradient launch and counts under "conv_dgrad")
 
 
 def _timed(name, device, launch, flops=0.0):
@@ -1929,9 +1931,11 @@ def _packed_weights(kernel, mode, transposed, c_src, c_dst, elems):
     return pk.get(kernel, mode, transposed, c_src, c_dst, elems)
 
 
-def _conv_target(src_feat, kernel, km, target, n_tgt, name="conv_target", transposed=False):
+def _conv_target(src_feat, kernel, km, target, n_tgt, name="conv_target", transposed=False, tail=None):
     """dst[t] = sum over plan entries of src[s] @ W[k].
-    transposed=False: W[k] = kernel[k] ([c_src, c_dst]);  transposed=True (dgrad): W[k] = kernel[k]^T."""
+    transposed=False: W[k] = kernel[k] ([c_src, c_dst]);  transposed=True (dgrad): W[k] = kernel[k]^T.
+    tail = (host pair offsets, device pair offsets, workspace, grad_w): the launch is the input gradient of a split-fp32
+    layer and carries the reduce of that layer's weight gradient behind its tiles (_conv_backward's two-launch order)."""
     lib = _lib.load()
     dev = src_feat.device
     volume = int(kernel.shape[0])
@@ -2090,10 +2094,18 @@ def _conv_target(src_feat, kernel, km, target, n_tgt, name="conv_target", transp
                 packed = torch.empty(elems, dtype=torch.bfloat16, device=dev)
                 _lib.check(lib.me_conv_pack_weights_f32x3(kernel.data_ptr(), volume, c_src, c_dst,
                                                           1 if transposed else 0, packed.data_ptr(), stream))
+            if tail is not None:   # (the timer's "conv_dgrad" then includes the weight gradient's reduce)
+                koffs, p_koffs, ws, grad_w = tail
+                _timed(name, dev, lambda: _lib.check(lib.me_conv_dgrad_reduce_tail_f32x3(
+                    src_feat.data_ptr(), src_feat.shape[0], c_src, packed.data_ptr(), km.volume, c_dst, p_src, p_dst,
+                    p_desc, p_bptr, p_order, out.data_ptr(), n_tgt, tile_rows, batch_groups, koffs, p_koffs,
+                    ws.data_ptr(), ws.numel(), grad_w.data_ptr(), stream)), flops=flops)
+                return out
             _timed(name, dev, lambda: _lib.check(lib.me_conv_target_f32x3(
                 src_feat.data_ptr(), src_feat.shape[0], c_src, packed.data_ptr(), km.volume, c_dst, p_src, p_dst,
                 p_desc, p_bptr, p_order, out.data_ptr(), n_tgt, tile_rows, batch_groups, stream)), flops=flops)
             return out
+        _check(tail is None, "reduce tail on a launch that is not the split fp32 kernel")
         packed = torch.empty(elems, dtype=torch.float32, device=dev)
         _lib.check(lib.me_conv_pack_weights_f32(kernel.data_ptr(), volume, c_src, c_dst, 1 if transposed else 0,
                                                 packed.data_ptr(), stream))
@@ -2181,6 +2193,20 @@ def _conv_backward(in_feat, grad_out, kernel, km, algo=None, need_grad_in=True):
 
     side = _side_stream(dev) if (_WGRAD_STREAM and need_grad_in and km.n_pairs > 0 and
                                  max(km.n_in, km.n_out) <= _WGRAD_STREAM_MAX_ROWS) else None
+    # Two-launch order (split fp32 layers whose input gradient is the wave-specialised split kernel, both gradients
+    # wanted): the weight gradient's partial images FIRST, then the input gradient, whose trailing workgroups reduce the
+    # images into grad_w on CUs that have run out of tiles — no reduce launch.  Everything else: the launches below.
+    if (need_grad_in and side is None and not bf16 and kernel.dtype == torch.float32 and km.n_in > 0 and
+            _use_split(lib, c_out, c_in) and
+            lib.me_conv_dgrad_reduce_tail_supported(c_in, c_out, volume, km.n_pairs)):
+        with _on(dev):
+            stream = _stream(dev)
+            _timed("conv_wgrad", dev, lambda: _lib.check(lib.me_conv_wgrad_partials_f32(
+                in_feat.data_ptr(), in_feat.shape[0], c_in, grad_out.data_ptr(), grad_out.shape[0], c_out, p_in, p_out,
+                koffs, p_koffs, volume, ws.data_ptr(), ws.numel(), stream)), flops=2.0 * km.n_pairs * c_in * c_out)
+        grad_in = _conv_target(grad_out, kernel, km, "in", km.n_in, name="conv_dgrad", transposed=True,
+                               tail=(koffs, p_koffs, ws, grad_w))
+        return grad_in, grad_w
     if side is not None:
         main = torch.cuda.current_stream(dev)
         side.wait_stream(main)

@@ -22,6 +22,7 @@
 // dgrad is the same kernel with source = grad_out, W = per-offset transposed kernel and the plan
 // of the transposed neighbour table.  wgrad reduces over the per-offset pair lists in chunks.
 #include "conv_common.hpp"
+#include "wgrad_reduce.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -998,7 +999,8 @@ __global__ __launch_bounds__(256) void k_transpose_kernel(const float *__restric
 // Flushes go to workspace slot (range + k) — unique, because (range, k) only ever moves up a
 // staircase — as the raw register image (coalesced); k_wgrad_reduce sums the slots of each offset
 // in range order (fixed summation order -> bitwise reproducible) and undoes the channel interleave.
-constexpr int kWgMB = 4;  // 16-row MFMA blocks of input channels per wave (64 channels, one dwordx4 per lane)
+// (kWgMB — 16-row MFMA blocks of input channels per wave: 64 channels, one dwordx4 per lane — and the range
+// arithmetic wgrad_range_begin / wgrad_range_of_pair live in wgrad_reduce.hpp, next to the second pass that shares them)
 
 // Which range a workgroup takes (round 2).  All ranges are resident at once and every range walks its pairs in
 // ascending output row, so the ranges that started at the same FRACTION of their offset's list read the same dy rows
@@ -1020,18 +1022,6 @@ __device__ __forceinline__ int wgrad_locate_offset(const int64_t *__restrict__ k
     if (koffs[mid] <= e) lo = mid; else hi = mid;
   }
   return lo;
-}
-
-__host__ __device__ __forceinline__ int64_t wgrad_range_begin(int64_t r, int64_t n_pairs, int64_t n_ranges) {
-  return r * n_pairs / n_ranges;
-}
-
-// the range r with range_begin(r) <= e < range_begin(r + 1)
-__device__ __forceinline__ int64_t wgrad_range_of_pair(int64_t e, int64_t n_pairs, int64_t n_ranges) {
-  int64_t r = e * n_ranges / n_pairs;
-  while (r > 0 && wgrad_range_begin(r, n_pairs, n_ranges) > e) --r;
-  while (r + 1 < n_ranges && wgrad_range_begin(r + 1, n_pairs, n_ranges) <= e) ++r;
-  return r;
 }
 
 // One lane's V consecutive channels of a gathered row, always as unconditional loads (loads inside
@@ -2143,100 +2133,22 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_lds_f32(const float *__restric
 }
 #endif  // ME_DEBUG_VARIANTS
 
-// grad_w[k] = sum of the register images of the ranges that touch offset k, written back through the
-// channel interleave of k_wgrad_f32.  A block sums 64 consecutive image elements; its four waves take
-// the slots s = first + phase, + 4, ... (four independent loads in flight per thread: the loop is
-// latency-bound otherwise) and the four partial sums are combined in phase order, so the summation
-// order is fixed (bitwise reproducible).
-
-// grad_w[k] = sum of the register images of the ranges that touch offset k, written back through the
-// channel interleave of k_wgrad_f32.  A block sums 64 consecutive image elements; its four waves take
-// the slots s = first + phase, + 4, ... (four independent loads in flight per thread: the loop is
-// latency-bound otherwise) and the four partial sums are combined in phase order, so the summation
-// order is fixed (bitwise reproducible).
-// TR: the images come from k_wgrad_bf16 (MFMA row i of block m <-> input channel 16*m + i, column j of block
-// n <-> output channel 16*n + j) instead of k_wgrad_f32's interleave.
-constexpr int kWgReducePhases = 4;   // waves per block of k_wgrad_reduce (16 measured slower: most offsets own ~10
-                                     // slots, and 4x the waves cost more than the long chain of the centre offset saves)
-
+// grad_w[k] = sum of the register images of the ranges that touch offset k, written back through the channel
+// interleave of the kernel that made them: a launch of wgrad_reduce_group (wgrad_reduce.hpp, where the sums and their
+// order are defined), one group of 256 threads per workgroup.  blockIdx.y: offset, blockIdx.x: block of 256 floats.
+// Round 3: a thread owns FOUR consecutive floats of the register image (one 16-byte load per slot) and a block 256 of
+// them: a quarter of the blocks, waves and load instructions of the one-float version, which spent its time
+// dispatching 110k four-instruction waves on a 256 x 256 layer (33 us for 23 MB of partials, longer than the
+// weight-gradient kernel it follows: profiles/r03_pmc_bf16_layers.log).
 template <int NB, bool TR, int MB = kWgMB>
-__global__ __launch_bounds__(64 * kWgReducePhases) void k_wgrad_reduce(const float *__restrict__ partial,
+__global__ __launch_bounds__(kWgReduceGroup) void k_wgrad_reduce(const float *__restrict__ partial,
                                                      const int64_t *__restrict__ koffs, int volume,
                                                      int64_t n_pairs, int n_ranges, int n_cib, int n_cob,
                                                      int c_in, int c_out, float *__restrict__ grad_w) {
-  // Round 3: a thread owns FOUR consecutive floats of the register image (one 16-byte load per slot) and a block 256 of
-  // them: a quarter of the blocks, waves and load instructions of the one-float version, which spent its time
-  // dispatching 110k four-instruction waves on a 256 x 256 layer (33 us for 23 MB of partials, longer than the
-  // weight-gradient kernel it follows: profiles/r03_pmc_bf16_layers.log).  The sums are the same sums in the same
-  // order (per element: slots of a phase in ascending order, then the phases in order): bit-identical results.
-  static_assert(MB == 4 || MB == 8, "input-channel blocks per workgroup");
-  constexpr int kImage = MB * NB * 4 * 64;
-  constexpr int PH = kWgReducePhases;
   __shared__ int64_t s_r[2];
-  __shared__ f32x4 s_part[PH][64];
-  const int k = blockIdx.y;
-  const int64_t b = koffs[k], e = koffs[k + 1];
-  if (threadIdx.x == 0) {
-    s_r[0] = 0;
-    s_r[1] = -1;
-    if (e > b) {
-      s_r[0] = wgrad_range_of_pair(b, n_pairs, n_ranges) + k;
-      s_r[1] = wgrad_range_of_pair(e - 1, n_pairs, n_ranges) + k;
-    }
-  }
-  __syncthreads();
-  // the waves take the slots first + phase, + PH, ...; eight independent loads in flight per thread (the centre
-  // offset of a sparse map owns half of all slots: its block sets the kernel's duration, and the loop is latency-bound)
-  const int j = threadIdx.x & 63, phase = threadIdx.x >> 6;
-  const int64_t idx = ((int64_t)blockIdx.x * 64 + j) * 4;      // first of this thread's four floats (kImage % 256 == 0)
-  const int64_t per_slot = (int64_t)n_cib * n_cob * kImage;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (idx < per_slot) {
-    const int64_t first = s_r[0], last = s_r[1];
-    const float *p = partial + idx;
-    int64_t slot = first + phase;
-    for (; slot + 7 * PH <= last; slot += 8 * PH) {
-      f32x4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4 *>(p + (slot + u * PH) * per_slot);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; slot <= last; slot += PH) s += *reinterpret_cast<const f32x4 *>(p + slot * per_slot);
-  }
-  s_part[phase][j] = s;
-  __syncthreads();
-  if (phase != 0 || idx >= per_slot) return;
-  s = s_part[0][j];
-#pragma unroll
-  for (int ph = 1; ph < PH; ++ph) s += s_part[ph][j];   // fixed order: bitwise reproducible
-  // the four floats are four consecutive LANES of one register of the image (idx % 4 == 0, 64 lanes per register)
-  const int lane0 = (int)(idx % 64);
-  const int reg = (int)((idx / 64) % (MB * NB * 4));
-  const int cob = (int)((idx / kImage) % n_cob);
-  const int cib = (int)(idx / ((int64_t)kImage * n_cob));
-  const int r = reg % 4, n = (reg / 4) % NB, m = reg / (4 * NB);
-  const int q = lane0 >> 4;
-  const int ci = cib * (16 * MB) + (TR ? 16 * m + 4 * q + r : MB * (4 * q + r) + m);
-  if (ci >= c_in) return;
-  float *row = grad_w + ((int64_t)k * c_in + ci) * c_out;
-  if (TR) {
-    // co = cob * 16 * NB + 16 * n + i16 with i16 = lane & 15: four consecutive output channels
-    const int co = cob * (16 * NB) + 16 * n + (lane0 & 15);
-    if ((c_out % 4) == 0 && co + 3 < c_out) {
-      *reinterpret_cast<f32x4 *>(row + co) = s;
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (co + t < c_out) row[co + t] = s[t];
-    }
-  } else {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int co = cob * (16 * NB) + NB * ((lane0 + t) & 15) + n;
-      if (co < c_out) row[co] = s[t];
-    }
-  }
+  __shared__ f32x4 s_part[kWgReducePhases * 64];
+  const WgReduceArgs a = {partial, koffs, grad_w, n_pairs, volume, n_ranges, n_cib, n_cob, c_in, c_out};
+  wgrad_reduce_group<NB, TR, MB>(a, (int)blockIdx.y, (int)blockIdx.x, (int)threadIdx.x, true, s_r, s_part);
 }
 
 // =================================================================================================
@@ -2628,6 +2540,20 @@ static bool wgrad_use_split(int c_in, int c_out) {
   return g_wgrad_depth == 0 && c_in >= 32 && c_out >= 32;
 }
 
+// (wgrad_reduce.hpp) what the reduce of me_conv_wgrad_f32's split kernel reads and writes, for a launch that carries
+// the reduce as its tail; the geometry is the one wgrad_split_partials launched with
+bool wgrad_split_tail(const int64_t *k_offsets, const int64_t *k_offsets_dev, int64_t volume, int c_in, int c_out,
+                      const void *workspace, float *grad_w, WgTail *tail) {
+  if (!wgrad_use_split(c_in, c_out) || volume < 1 || volume > 65535) return false;
+  const int64_t n_pairs = k_offsets[volume];
+  const WgradGeom g = wgrad_geom_staged(n_pairs, c_in, c_out, 3);
+  tail->r = WgReduceArgs{reinterpret_cast<const float *>(workspace), k_offsets_dev, grad_w, n_pairs > 0 ? n_pairs : 1,
+                         (int)volume, (int)g.ranges, g.n_cib, g.n_cob, c_in, c_out};
+  tail->nb = g.nb;
+  tail->n_tiles = 0;
+  return true;
+}
+
 }  // namespace me
 
 using namespace me;
@@ -2929,6 +2855,40 @@ void me_debug_set_wgrad_config(int depth, int wgs_per_cu) {
   g_wgrad_wgs_per_cu = wgs_per_cu;
 }
 
+// first pass of the split fp32 weight gradient (k_wgrad_f32x3): the partial images of every range, no reduce
+static int wgrad_split_partials(const float *x, int32_t c_in, const float *dy, int32_t c_out, const int32_t *in_pairs,
+                                const int32_t *out_pairs, const int64_t *k_offsets, const int64_t *k_offsets_dev,
+                                int64_t volume, void *workspace, int64_t workspace_bytes, hipStream_t stream,
+                                WgradGeom *geom) {
+  ME_CHECK(volume >= 1 && volume <= 65535, "kernel volume out of range");
+  ME_CHECK((uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0, "feature pointers must be 16-byte aligned");
+  ME_CHECK(workspace_bytes >= me_conv_wgrad_workspace_bytes(k_offsets, volume, c_in, c_out), "workspace too small");
+  const int64_t n_pairs = k_offsets[volume];
+  const WgradGeom g = wgrad_geom_staged(n_pairs, c_in, c_out, 3);
+  float *partial = reinterpret_cast<float *>(workspace);
+  *geom = g;
+  if (n_pairs <= 0) return 0;
+  const WgRangeOrder order = wgrad_range_order(k_offsets, volume, n_pairs, g.ranges, (int64_t)g.n_cib * g.gz);
+  return g.nb == 1 ? launch_wgrad_f32x3<1>(g, x, c_in, dy, c_out, in_pairs, out_pairs, k_offsets_dev, (int)volume,
+                                           n_pairs, partial, order, stream)
+                   : launch_wgrad_f32x3<2>(g, x, c_in, dy, c_out, in_pairs, out_pairs, k_offsets_dev, (int)volume,
+                                           n_pairs, partial, order, stream);
+}
+
+int32_t me_conv_wgrad_is_split_f32(int32_t c_in, int32_t c_out) { return wgrad_use_split(c_in, c_out) ? 1 : 0; }
+
+int me_conv_wgrad_partials_f32(const float *x, int64_t n_in, int32_t c_in, const float *dy, int64_t n_out, int32_t c_out,
+                               const int32_t *in_pairs, const int32_t *out_pairs, const int64_t *k_offsets,
+                               const int64_t *k_offsets_dev, int64_t volume, void *workspace, int64_t workspace_bytes,
+                               void *stream_) {
+  (void)n_in;
+  (void)n_out;
+  ME_CHECK(wgrad_use_split(c_in, c_out), "not a split weight gradient (me_conv_wgrad_is_split_f32)");
+  WgradGeom g;
+  return wgrad_split_partials(x, c_in, dy, c_out, in_pairs, out_pairs, k_offsets, k_offsets_dev, volume, workspace,
+                              workspace_bytes, (hipStream_t)stream_, &g);
+}
+
 int me_conv_wgrad_f32(const float *x, int64_t n_in, int32_t c_in, const float *dy, int64_t n_out, int32_t c_out,
                       const int32_t *in_pairs,
                       const int32_t *out_pairs, const int64_t *k_offsets, const int64_t *k_offsets_dev,
@@ -2940,20 +2900,12 @@ int me_conv_wgrad_f32(const float *x, int64_t n_in, int32_t c_in, const float *d
   // the ~4 TB/s at which 640 MB of random rows arrive from beyond the L2s, not by how the matrix pipe is fed
   // (it is 13 % faster on sparse maps and 40 % slower on 32 -> 32, so it is not the default).
   if (wgrad_use_split(c_in, c_out)) {
-    ME_CHECK(volume >= 1 && volume <= 65535, "kernel volume out of range");
-    ME_CHECK((uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0, "feature pointers must be 16-byte aligned");
-    ME_CHECK(workspace_bytes >= me_conv_wgrad_workspace_bytes(k_offsets, volume, c_in, c_out), "workspace too small");
+    WgradGeom g;
+    const int rc = wgrad_split_partials(x, c_in, dy, c_out, in_pairs, out_pairs, k_offsets, k_offsets_dev, volume,
+                                        workspace, workspace_bytes, stream, &g);
+    if (rc != 0) return rc;
+    const float *partial = reinterpret_cast<const float *>(workspace);
     const int64_t n_pairs = k_offsets[volume];
-    const WgradGeom g = wgrad_geom_staged(n_pairs, c_in, c_out, 3);
-    float *partial = reinterpret_cast<float *>(workspace);
-    if (n_pairs > 0) {
-      const WgRangeOrder order = wgrad_range_order(k_offsets, volume, n_pairs, g.ranges, (int64_t)g.n_cib * g.gz);
-      const int rc = g.nb == 1 ? launch_wgrad_f32x3<1>(g, x, c_in, dy, c_out, in_pairs, out_pairs, k_offsets_dev,
-                                                        (int)volume, n_pairs, partial, order, stream)
-                               : launch_wgrad_f32x3<2>(g, x, c_in, dy, c_out, in_pairs, out_pairs, k_offsets_dev,
-                                                        (int)volume, n_pairs, partial, order, stream);
-      if (rc != 0) return rc;
-    }
     const dim3 rgrid((unsigned)ceil_div(g.slot_floats, 256), (unsigned)volume);
     if (g.nb == 1)
       hipLaunchKernelGGL((k_wgrad_reduce<1, true>), rgrid, dim3(64 * kWgReducePhases), 0, stream, partial, k_offsets_dev,

@@ -20,8 +20,10 @@
 // three LDS stage planes, and fp32 output.  The reference computes this path in fp32
 // (src/convolution_gpu.cu:137-155, AT_DISPATCH_FLOATING_TYPES).
 #include <type_traits>
+#include <vector>
 #include "conv_common.hpp"
 #include "conv_ws.hpp"
+#include "wgrad_reduce.hpp"
 
 namespace me {
 
@@ -460,6 +462,9 @@ __global__ __launch_bounds__(NC * 4 * x3_group_shares(NC), 1) void k_conv_tile_f
   }
 }
 
+template <typename T>
+__device__ __forceinline__ const T &only_arg(const T &t) { return t; }   // the one element of a parameter pack
+
 // =================================================================================================
 // wave-specialised variant (round 2, debug variant 31 until it is the default): k_conv_tile_f32x3_ws
 // =================================================================================================
@@ -475,12 +480,21 @@ __global__ __launch_bounds__(NC * 4 * x3_group_shares(NC), 1) void k_conv_tile_f
 // multipliers per SIMD next to the producer — the operand reads double again, but one multiplier's MFMAs cover the
 // other's waits: forward 64 -> 128 11 - 17 % faster (scripts/check_variant.py).  (Eight multipliers on a 64-column slab,
 // each taking one pass of a batch, were tried: KC = 128 no longer fits 168 registers, 64 -> 64 gains 3 %.)
-template <int NC, int KC, bool EXACT, bool SMALL, bool TIMED = false, int PRIO = 2, int ABL = 0, int NCW = 4>
+// TAIL (the input-gradient launch of a layer whose weight gradient is the split kernel, me_conv_dgrad_reduce_tail_f32x3):
+// the grid carries workgroups behind its tiles that do the REDUCE of that weight gradient (wgrad_reduce.hpp) instead
+// of a tile — they are dispatched last, onto CUs that have run out of tiles, so the reduce needs no launch of its own.
+// Stream order alone makes the partial images complete before this launch starts.  TAIL_ARG is then one WgTail (the
+// reduce's arguments and the tile count, which gridDim.x no longer is); without TAIL the pack is empty and the kernel
+// is, argument for argument and instruction for instruction, the one it was.
+template <int NC, int KC, bool EXACT, bool SMALL, bool TIMED = false, int PRIO = 2, int ABL = 0, int NCW = 4,
+          bool TAIL = false, typename... TAIL_ARG>
 __global__ __launch_bounds__((NCW + 4) * 64, 1) void k_conv_tile_f32x3_ws(
     const float *__restrict__ src, int c_src, const bf16x8 *__restrict__ wp, int c_dst,
     const int32_t *__restrict__ plan_src, const int32_t *__restrict__ plan_dst,
     const int32_t *__restrict__ batch_desc, const int32_t *__restrict__ tile_bptr,
-    const int32_t *__restrict__ order, float *__restrict__ dst, int64_t n_tgt, int tile_rows, int batch_groups) {
+    const int32_t *__restrict__ order, float *__restrict__ dst, int64_t n_tgt, int tile_rows, int batch_groups,
+    TAIL_ARG... tail) {
+  static_assert(sizeof...(TAIL_ARG) == (TAIL ? 1 : 0), "TAIL: exactly one WgTail argument");
   typedef int i32x2 __attribute__((ext_vector_type(2)));
   typedef StageLayout<KC> SL;
   static_assert(NC == 64 || NC == 128, "multiplier waves of 16 or 32 columns");
@@ -498,6 +512,16 @@ __global__ __launch_bounds__((NCW + 4) * 64, 1) void k_conv_tile_f32x3_ws(
   (void)batch_groups;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned n_tiles = gridDim.x;
+  if constexpr (TAIL) {
+    // the workgroups behind the tiles: the reduce (of the last slab row only), in the launch's LDS — they have no tile
+    const WgTail &t = only_arg(tail...);
+    n_tiles = (unsigned)t.n_tiles;
+    if (blockIdx.x >= n_tiles) {
+      if (blockIdx.y + 1 == gridDim.y) wgrad_reduce_tail<NT>(t.r, t.nb, (int)(blockIdx.x - n_tiles), smem);
+      return;
+    }
+  }
   float *s_acc = reinterpret_cast<float *>(smem);                              // [(tile_rows + 1) x ACC_LD]
   __bf16 *s_a = reinterpret_cast<__bf16 *>(s_acc + (tile_rows + 1) * ACC_LD);  // [2][3][64 x LD]
   int32_t *s_dst = reinterpret_cast<int32_t *>(s_a + 2 * 3 * PLANE);           // [2][64]
@@ -507,7 +531,7 @@ __global__ __launch_bounds__((NCW + 4) * 64, 1) void k_conv_tile_f32x3_ws(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i16 = lane & 15;
   const int q = lane >> 4;
-  const int tile = tile_bptr[gridDim.x + 1 + blockIdx.x];   // heaviest-first dispatch order (me_plan_build)
+  const int tile = tile_bptr[n_tiles + 1 + blockIdx.x];   // heaviest-first dispatch order (me_plan_build)
   const int col_base = blockIdx.y * NC;
   const int nchunks = (c_src + KC - 1) / KC;
   const int ncb = (c_dst + 15) / 16;
@@ -1459,8 +1483,9 @@ template <int NC, int KC>
 static int launch_conv_tile_f32x3(const float *src, int c_src, const bf16x8 *wp, int c_dst, int slabs,
                                   const int32_t *plan_src, const int32_t *plan_dst, const int32_t *batch_desc,
                                   const int32_t *tile_bptr, const int32_t *order, float *dst, int64_t n_tgt,
-                                  int tile_rows, int batch_groups, hipStream_t stream, bool small) {
-  const int lds = conv_f32x3_lds_bytes(NC, KC, tile_rows);
+                                  int tile_rows, int batch_groups, hipStream_t stream, bool small,
+                                  const WgTail *tail = nullptr) {
+  int lds = conv_f32x3_lds_bytes(NC, KC, tile_rows);
   ME_CHECK(lds <= kLdsBudget, "tile_rows too large for the LDS of one workgroup");
   const bool exact = (c_src % KC) == 0;
   // two instantiations per shape (round 6; four before): the fast one — source channels a multiple of the chunk AND 32-bit
@@ -1530,6 +1555,34 @@ static int launch_conv_tile_f32x3(const float *src, int c_src, const bf16x8 *wp,
       }
     }
 #endif
+    if (tail != nullptr) {
+      // the wave-specialised kernel with the reduce of the layer's weight gradient behind its tiles (TAIL): the
+      // same instantiation choice as below, n_tail more workgroups along grid.x
+      typedef void (*tail_kernel_t)(const float *, int, const bf16x8 *, int, const int32_t *, const int32_t *,
+                                    const int32_t *, const int32_t *, const int32_t *, float *, int64_t, int, int, WgTail);
+      constexpr int TNCW = NC == 128 ? 8 : 4;
+      constexpr int TNT = (TNCW + 4) * 64;
+      const tail_kernel_t tk = fast ? &k_conv_tile_f32x3_ws<NC, KC, true, true, false, 2, 0, TNCW, true, WgTail>
+                                    : &k_conv_tile_f32x3_ws<NC, KC, false, false, false, 2, 0, TNCW, true, WgTail>;
+      const int tail_lds = (TNT / kWgReduceGroup) * kWgReduceGroupLds;
+      if (lds < tail_lds) lds = tail_lds;
+      static bool tail_attr[2] = {false, false};
+      if (lds > 48 * 1024 && !tail_attr[fast ? 1 : 0]) {
+        ME_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(tk), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   kLdsBudget));
+        tail_attr[fast ? 1 : 0] = true;
+      }
+      WgTail t = *tail;
+      const int64_t n_tiles = ceil_div(n_tgt, tile_rows);
+      const int64_t n_tail = ceil_div(wgrad_tail_groups(t), (int64_t)(TNT / kWgReduceGroup));
+      ME_CHECK(n_tiles + n_tail < (1ll << 31), "grid too large");
+      t.n_tiles = (int)n_tiles;
+      hipLaunchKernelGGL(tk, dim3((unsigned)(n_tiles + n_tail), (unsigned)slabs), dim3(TNT), (size_t)lds, stream, src,
+                         c_src, wp, c_dst, plan_src, plan_dst, batch_desc, tile_bptr, order, dst, n_tgt, tile_rows,
+                         batch_groups, t);
+      ME_LAUNCH_CHECK();
+      return 0;
+    }
     if (!kHasPingPong || (g_conv_variant != 30 && g_conv_variant != 256)) {
       kernel_t ws;
       int wi = (small ? 2 : 0) + (exact ? 1 : 0);
@@ -1681,12 +1734,11 @@ int me_conv_pack_weights_f32x3(const float *w, int64_t volume, int32_t c_src, in
   return 0;
 }
 
-int me_conv_target_f32x3(const float *src, int64_t n_src, int32_t c_src, const uint16_t *wp_, int64_t volume,
-                         int32_t c_dst, const int32_t *plan_src, const int32_t *plan_dst, const int32_t *batch_desc,
-                         const int32_t *tile_bptr, const int32_t *order, float *dst, int64_t n_tgt, int32_t tile_rows,
-                         int32_t batch_groups, void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  (void)volume;
+// me_conv_target_f32x3, and — tail != nullptr — the same launch with the weight-gradient reduce behind its tiles
+static int conv_target_f32x3(const float *src, int64_t n_src, int32_t c_src, const uint16_t *wp_, int32_t c_dst,
+                             const int32_t *plan_src, const int32_t *plan_dst, const int32_t *batch_desc,
+                             const int32_t *tile_bptr, const int32_t *order, float *dst, int64_t n_tgt, int32_t tile_rows,
+                             int32_t batch_groups, hipStream_t stream, const WgTail *tail) {
   ME_CHECK(me_conv_f32x3_supported(c_src, c_dst), "source channels must be a positive multiple of 8 (me_conv_f32x3_supported)");
   const bool small = n_src > 0 && n_src < (1ll << 24) && n_src * c_src * 4 < (1ll << 32) && g_conv_variant != 6;
   ME_CHECK(tile_rows >= ME_GROUP_ROWS && tile_rows <= ME_MAX_TILE_ROWS, "tile_rows out of range");
@@ -1696,9 +1748,10 @@ int me_conv_target_f32x3(const float *src, int64_t n_src, int32_t c_src, const u
   if (n_tgt == 0) return 0;
   const bf16x8 *wp = reinterpret_cast<const bf16x8 *>(wp_);
   const ConvVariantX3 v = conv_variant_f32x3(c_src, c_dst);
+  ME_CHECK(tail == nullptr || v.nc == 64 || v.nc == 128, "no reduce tail on this slab width (me_conv_dgrad_reduce_tail_supported)");
 #define ME_CONV_CASE(NCV, KCV)                                                                                    \
   return launch_conv_tile_f32x3<NCV, KCV>(src, c_src, wp, c_dst, v.slabs, plan_src, plan_dst, batch_desc, tile_bptr, \
-                                          order, dst, n_tgt, tile_rows, batch_groups, stream, small)
+                                          order, dst, n_tgt, tile_rows, batch_groups, stream, small, tail)
   if (v.nc == 32) {
     if (v.kc == 128) ME_CONV_CASE(32, 128);
     if (v.kc == 96) ME_CONV_CASE(32, 96);
@@ -1719,6 +1772,61 @@ int me_conv_target_f32x3(const float *src, int64_t n_src, int32_t c_src, const u
     ME_CONV_CASE(128, 32);
   }
 #undef ME_CONV_CASE
+}
+
+int me_conv_target_f32x3(const float *src, int64_t n_src, int32_t c_src, const uint16_t *wp_, int64_t volume,
+                         int32_t c_dst, const int32_t *plan_src, const int32_t *plan_dst, const int32_t *batch_desc,
+                         const int32_t *tile_bptr, const int32_t *order, float *dst, int64_t n_tgt, int32_t tile_rows,
+                         int32_t batch_groups, void *stream_) {
+  (void)volume;
+  return conv_target_f32x3(src, n_src, c_src, wp_, c_dst, plan_src, plan_dst, batch_desc, tile_bptr, order, dst, n_tgt,
+                           tile_rows, batch_groups, (hipStream_t)stream_, nullptr);
+}
+
+// ---- input gradient with the weight-gradient reduce as its tail ------------------------------------------------------
+int g_dgrad_tail = 0;   // me_debug_set_dgrad_reduce_tail: 0 policy, 1 never (three launches), 2 wherever the kernels exist
+
+// A tail workgroup fills a CU on its own (the launch's LDS), so the tail runs 8 - 12 waves per CU where k_wgrad_reduce
+// runs 32: it pays while the tail is a few rounds of workgroups on CUs the tiles have left, not on wide layers whose
+// reduce is many rounds long.  Measured per shape on the headline scene (scripts/dgrad_tail_sweep.py,
+// profiles/r15_dgrad_reduce_tail_ab.md; tail workgroups, two-launch minus three-launch step): 64 -> 128 432, -8.5 us;
+// 128 -> 64 288, -2.3; 128 -> 128 576, -9.1; 128 -> 256 1152, -10.4; 256 -> 128 1152 behind TWO slab rows of tiles,
+// +5.2; 256 -> 256 2304, +27.4.  So: one slab row (c_in <= 128) and at most five rounds.
+constexpr int kTailMaxRounds = 5;
+
+int32_t me_conv_dgrad_reduce_tail_supported(int32_t c_in, int32_t c_out, int64_t volume, int64_t n_pairs) {
+  if (g_dgrad_tail == 1 || volume < 1 || volume > 65535 || (g_conv_variant != 0 && g_conv_variant != 6)) return 0;
+  if (!me_conv_f32x3_supported(c_out, c_in)) return 0;
+  const ConvVariantX3 v = conv_variant_f32x3(c_out, c_in);   // the input gradient: source dy (c_out), target dx (c_in)
+  if (v.nc != 64 && v.nc != 128) return 0;
+  std::vector<int64_t> koffs((size_t)volume + 1, 0);   // (the geometry depends on the pair count alone)
+  koffs[(size_t)volume] = n_pairs;
+  WgTail t;
+  if (!wgrad_split_tail(koffs.data(), nullptr, volume, c_in, c_out, nullptr, nullptr, &t)) return 0;
+  if (g_dgrad_tail == 2) return 1;
+  if (v.slabs != 1) return 0;
+  const int groups_per_wg = v.nc == 128 ? 3 : 2;
+  return ceil_div(wgrad_tail_groups(t), (int64_t)groups_per_wg) <= (int64_t)kTailMaxRounds * device_cu_count() ? 1 : 0;
+}
+
+void me_debug_set_dgrad_reduce_tail(int mode) { g_dgrad_tail = mode; }
+
+int me_conv_dgrad_reduce_tail_f32x3(const float *dy, int64_t n_out, int32_t c_out, const uint16_t *wp_, int64_t volume,
+                                    int32_t c_in, const int32_t *plan_src, const int32_t *plan_dst,
+                                    const int32_t *batch_desc, const int32_t *tile_bptr, const int32_t *order, float *dx,
+                                    int64_t n_in, int32_t tile_rows, int32_t batch_groups, const int64_t *k_offsets,
+                                    const int64_t *k_offsets_dev, const void *workspace, int64_t workspace_bytes,
+                                    float *grad_w, void *stream_) {
+  ME_CHECK(n_in > 0, "no input rows: nothing carries the tail (me_conv_wgrad_f32 handles empty maps)");
+  ME_CHECK(g_conv_variant == 0 || g_conv_variant == 6, "debug kernel variants have no reduce tail");
+  ME_CHECK(k_offsets != nullptr && k_offsets_dev != nullptr && workspace != nullptr && grad_w != nullptr,
+           "pair offsets, workspace and grad_w must not be null");
+  ME_CHECK(workspace_bytes >= me_conv_wgrad_workspace_bytes(k_offsets, volume, c_in, c_out), "workspace too small");
+  WgTail t;
+  ME_CHECK(wgrad_split_tail(k_offsets, k_offsets_dev, volume, c_in, c_out, workspace, grad_w, &t),
+           "not a split weight gradient (me_conv_dgrad_reduce_tail_supported)");
+  return conv_target_f32x3(dy, n_out, c_out, wp_, c_in, plan_src, plan_dst, batch_desc, tile_bptr, order, dx, n_in,
+                           tile_rows, batch_groups, (hipStream_t)stream_, &t);
 }
 
 }  // extern "C"

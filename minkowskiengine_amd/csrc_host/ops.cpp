@@ -224,6 +224,8 @@ std::vector<TimedLaunch> g_timed;
 
 struct ScopedTimer {   // records an event pair around the launches of its scope when timing is on; a roctx range always
   bool on;                // (when ME_AMD_ROCTX=1: "me:conv_forward" / "me:conv_dgrad" / "me:conv_wgrad")
+                          // In the two-launch backward order (conv_backward_km) "conv_wgrad" is the first pass of the weight
+                          // gradient only; its reduce is the tail of the input-gradient launch and counts under "conv_dgrad".
   TimedLaunch t;
   hipStream_t st;
   std::string rx_name;
@@ -371,8 +373,16 @@ Tensor grad_destination(const Tensor &param, at::IntArrayRef shape) {
 
 // ---- convolution ----------------------------------------------------------------------------------------------------------
 // dst[t] = sum over plan entries of src[s] @ W[k]; transposed (dgrad): W[k] = kernel[k]^T
+// tail (conv_backward_km's two-launch order): the launch is the input gradient of a split-fp32 layer and carries the
+// reduce of that layer's weight gradient behind its tiles (me_conv_dgrad_reduce_tail_f32x3)
+struct ReduceTail {
+  const int64_t *koffs;   // host pair offsets
+  Tensor ws;              // the partial images me_conv_wgrad_partials_f32 wrote
+  Tensor grad_w;
+};
+
 static Tensor conv_target(const Tensor &src, const Tensor &kernel, KernelMap &km, const std::string &target, int64_t n_tgt,
-                          bool transposed) {
+                          bool transposed, const ReduceTail *tail = nullptr) {
   const c10::Device dev = src.device();
   const int64_t volume = kernel.size(0);
   const int c_src = (int)(transposed ? kernel.size(2) : kernel.size(1));
@@ -529,13 +539,21 @@ static Tensor conv_target(const Tensor &src, const Tensor &kernel, KernelMap &km
       me_ok(me_conv_pack_weights_f32x3(ptr<float>(kernel), volume, c_src, c_dst, transposed ? 1 : 0, ptr<uint16_t>(packed),
                                        st));
     }
-    ScopedTimer tm(timed_name, flops, st);
-    me_ok(me_conv_target_f32x3(ptr<float>(src), src.size(0), c_src, ptr<uint16_t>(packed), km.volume, c_dst,
-                               ptr<int32_t>(p.plan_src), ptr<int32_t>(p.plan_dst), ptr<int32_t>(p.batch_desc),
-                               ptr<int32_t>(p.tile_bptr), ptr<int32_t>(cfg.order), ptr<float>(out), n_tgt, cfg.tile_rows,
-                               cfg.batch_groups, st));
+    ScopedTimer tm(timed_name, flops, st);   // (with a tail, "conv_dgrad" includes the weight gradient's reduce)
+    if (tail != nullptr)
+      me_ok(me_conv_dgrad_reduce_tail_f32x3(ptr<float>(src), src.size(0), c_src, ptr<uint16_t>(packed), km.volume, c_dst,
+                                            ptr<int32_t>(p.plan_src), ptr<int32_t>(p.plan_dst), ptr<int32_t>(p.batch_desc),
+                                            ptr<int32_t>(p.tile_bptr), ptr<int32_t>(cfg.order), ptr<float>(out), n_tgt,
+                                            cfg.tile_rows, cfg.batch_groups, tail->koffs, ptr<int64_t>(km.k_offsets_dev),
+                                            vptr(tail->ws), tail->ws.numel(), ptr<float>(tail->grad_w), st));
+    else
+      me_ok(me_conv_target_f32x3(ptr<float>(src), src.size(0), c_src, ptr<uint16_t>(packed), km.volume, c_dst,
+                                 ptr<int32_t>(p.plan_src), ptr<int32_t>(p.plan_dst), ptr<int32_t>(p.batch_desc),
+                                 ptr<int32_t>(p.tile_bptr), ptr<int32_t>(cfg.order), ptr<float>(out), n_tgt, cfg.tile_rows,
+                                 cfg.batch_groups, st));
     return out;
   }
+  check(tail == nullptr, "reduce tail on a launch that is not the split fp32 kernel");
   Tensor packed = at::empty({cfg.elems}, at::TensorOptions().dtype(at::kFloat).device(dev));
   me_ok(me_conv_pack_weights_f32(ptr<float>(kernel), volume, c_src, c_dst, transposed ? 1 : 0, ptr<float>(packed), st));
   ScopedTimer tm(timed_name, flops, st);
@@ -557,9 +575,19 @@ std::pair<Tensor, Tensor> conv_backward_km(const Tensor &in_feat, Tensor grad_ou
   const int c_in = (int)kernel.size(1), c_out = (int)kernel.size(2);
   if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
   const bool bf16 = in_feat.scalar_type() == at::kBFloat16;
+  // Two-launch order (split fp32 layers whose input gradient is the wave-specialised split kernel, both gradients
+  // wanted): the weight gradient's partial images FIRST, then the input gradient, whose trailing workgroups reduce
+  // the images into grad_w on CUs that have run out of tiles — no reduce launch.  Everything else: input gradient,
+  // weight gradient, reduce, as ever.
+  bool two_launch = false;
+  if (need_grad_in && in_feat.scalar_type() == at::kFloat && kernel.scalar_type() == at::kFloat && km.n_in > 0 &&
+      me_conv_dgrad_reduce_tail_supported(c_in, c_out, volume, km.n_pairs())) {
+    const ConvCfg &dc = km.conv_cfg("in", km.n_in, c_out, c_in, false);
+    two_launch = dc.split && !dc.rowwise && !dc.halo && dc.plan != nullptr;
+  }
   // dgrad: the same target-stationary kernel; the weights are packed transposed per offset
   Tensor grad_in;
-  if (need_grad_in) grad_in = conv_target(grad_out, kernel, km, "in", km.n_in, true);
+  if (need_grad_in && !two_launch) grad_in = conv_target(grad_out, kernel, km, "in", km.n_in, true);
   if (in_feat.scalar_type() == at::kDouble) {   // csrc/f64.hip: sequential double sums over the pairs of each offset
     check(kernel.scalar_type() == at::kDouble, "float64 features need a float64 kernel");
     Tensor gw = at::empty(kernel.sizes(), kernel.options());
@@ -575,6 +603,19 @@ std::pair<Tensor, Tensor> conv_backward_km(const Tensor &in_feat, Tensor grad_ou
   if (!grad_w.defined()) grad_w = at::empty(kernel.sizes(), at::TensorOptions().dtype(at::kFloat).device(dev));
   const WgradCfg &w = km.wgrad_cfg(c_in, c_out, bf16);
   Tensor ws = workspace(w.ws_bytes, dev);
+  if (two_launch) {
+    {
+      c10::DeviceGuard guard(dev);
+      void *st = stream_of(dev);
+      ScopedTimer tm("conv_wgrad", g_timing ? 2.0 * (double)km.n_pairs() * c_in * c_out : 0.0, st);
+      me_ok(me_conv_wgrad_partials_f32(ptr<float>(in_feat), in_feat.size(0), c_in, ptr<float>(grad_out), grad_out.size(0),
+                                       c_out, ptr<int32_t>(km.in_pairs_buf), ptr<int32_t>(km.out_pairs_buf), w.koffs.data(),
+                                       ptr<int64_t>(km.k_offsets_dev), volume, vptr(ws), ws.numel(), st));
+    }
+    const ReduceTail tail{w.koffs.data(), ws, grad_w};
+    grad_in = conv_target(grad_out, kernel, km, "in", km.n_in, true, &tail);
+    return {grad_in, grad_w};
+  }
   {
     c10::DeviceGuard guard(dev);
     void *st = stream_of(dev);

@@ -348,8 +348,8 @@ int me_conv_target_f32(const float *src_feat_dev, int64_t n_src, int32_t c_src,
  * sparse map's plan consists of — are staged and multiplied together, up to four offsets per barrier pair, each group
  * with its own offset's weight slice.  For maps with fewer than ~24 pairs per (tile, offset) item; fp32 results in a
  * fixed order (not bit-identical to me_conv_target_f32: the partial sums of a fused batch are added to the tile as a
- * whole).  Shapes without a fused instantiation (slabs of 96 columns, chunks of 96 channels, >= 4 GiB sources) run
- * the plain kernel. */
+ * whole).  Shapes without a fused instantiation (slabs of 96 columns, chunks of 96 channels, >= 4 GiB sources) and
+ * plans with batch_groups < 4 (the stage buffer must hold four groups) run the plain kernel. */
 int me_conv_target_f32_fused(const float *src_feat_dev, int64_t n_src, int32_t c_src, const float *packed_w_dev,
                              int64_t volume, int32_t c_dst, const int32_t *plan_src_dev, const int32_t *plan_dst_dev,
                              const int32_t *batch_desc_dev, const int32_t *tile_bptr_dev, const int32_t *order_dev,
@@ -407,7 +407,8 @@ int me_conv_target_bf16(const uint16_t *src_feat_dev, int64_t n_src, int32_t c_s
                         int64_t n_tgt, int32_t tile_rows, int32_t batch_groups, void *stream);
 /* The same operation, arguments and results (bit-identical) with BATCH FUSION: consecutive small batches of a tile —
  * up to four kernel offsets — are staged and multiplied per barrier pair.  For sparse maps, where most (tile, offset)
- * items hold a single 16-row group (a dense layer is 20 - 40 % faster on me_conv_target_bf16). */
+ * items hold a single 16-row group (a dense layer is 20 - 40 % faster on me_conv_target_bf16).  Fusion needs a stage
+ * buffer of four groups: a plan with batch_groups < 4 runs as me_conv_target_bf16 does. */
 int me_conv_target_bf16_fused(const uint16_t *src_feat_dev, int64_t n_src, int32_t c_src,
                               const uint16_t *packed_w_dev, int64_t volume, int32_t c_dst,
                               const int32_t *plan_src_dev, const int32_t *plan_dst_dev,
@@ -597,7 +598,10 @@ int me_conv_stem_bf16(const uint16_t *src_feat_dev, int64_t n_src, int32_t c_src
  * AT_DISPATCH_FLOATING_TYPES computes it), different arithmetic unit: every operand is split exactly into three
  * bf16 terms (a = a1 + a2 + a3) and the product is rebuilt from six v_mfma_f32_16x16x32_bf16 with fp32
  * accumulation; the dropped terms are < 2^-23 |a b| per product, i.e. below one fp32 rounding.  Fixed summation
- * order (bitwise reproducible).  An infinite input yields NaN (fp32 arithmetic would keep the infinity).
+ * order (bitwise reproducible).  A non-finite FEATURE value (gathered rows, upstream gradients, the x rows of the weight
+ * gradient) behaves as in fp32 arithmetic: +-inf times a weight keeps its sign, inf * 0 and opposite infinities in one
+ * sum give NaN, NaN stays NaN.  A non-finite WEIGHT-side value (packed weights, the dy rows of the weight gradient)
+ * makes every output it reaches NaN, where fp32 arithmetic would keep an infinity's sign (csrc/conv_common.hpp).
  * Needs c_src % 8 == 0 (me_conv_f32x3_supported); plans come from me_plan_build with the geometry of
  * me_conv_plan_config_f32x3; weights packed by me_conv_pack_weights_f32x3 (three bf16 planes). */
 int32_t me_conv_f32x3_supported(int32_t c_src, int32_t c_dst);

@@ -2712,6 +2712,9 @@ static int conv_target_f32(const float *src, int64_t n_src, int32_t c_src, const
   ME_CHECK((uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0 && (uintptr_t)wp % 16 == 0,
            "feature and weight pointers must be 16-byte aligned");
   if (n_tgt == 0) return 0;
+  // a multi-offset batch stages up to four single-group batches at once, and the stage buffer holds batch_groups groups:
+  // a plan of smaller batches runs the plain instantiation (the hosts' plans always have four)
+  if (batch_groups < ME_MAX_BATCH_GROUPS) fuse = false;
   const ConvVariant v = conv_variant(c_src, c_dst);
 #define ME_CONV_ARGS                                                                                         \
   src, c_src, wp, c_dst, v.slabs, plan_src, plan_dst, batch_desc, tile_bptr, order, dst, n_tgt, tile_rows, \

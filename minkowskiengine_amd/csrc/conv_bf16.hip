@@ -1340,6 +1340,9 @@ static int launch_conv_tile_bf16(const __bf16 *src, int c_src, const bf16x8 *wp,
   // two instantiations per shape and mode (round 6; four before): the fast one (exact chunk AND 32-bit gather offsets) and
   // the general one, which also serves the two mixed cases — same sums in the same order
   const bool fast = small && exact;
+  // a fused super-batch stages up to four single-group batches at once, and the stage buffer holds batch_groups groups:
+  // a plan of smaller batches runs the unfused instantiation (bit-identical; the hosts' plans always have four)
+  if (batch_groups < ME_MAX_BATCH_GROUPS) fuse = false;
   kernel_t fn = fast ? &k_conv_tile_bf16<NC, KC, true, true> : &k_conv_tile_bf16<NC, KC, false, false>;
   if constexpr (NC <= 96 && KC <= 128) {   // batch fusion: four- and six-wave workgroups (sparse maps of narrow layers)
     if (fuse) fn = fast ? &k_conv_tile_bf16<NC, KC, true, true, true> : &k_conv_tile_bf16<NC, KC, false, false, true>;

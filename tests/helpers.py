@@ -72,6 +72,109 @@ def assert_close(a, b, atol=1e-4, rtol=1e-4, what=""):
                              f"(|diff| {abs(a64[i] - b64[i]):.3e} = {ex:.2f} x tolerance {atol}+{rtol}|b|)")
 
 
+# ---- entry-point tests on synthetic tables (test_gpu_conv_tile_kernels.py, test_gpu_wgrad_kernels.py) ---------------------
+GUARD_PAD = 4096       # elements around every buffer (16-byte alignment kept; wider than any row of those tests)
+DEBUG_BUILD_ONLY = "only in a -DME_DEBUG_VARIANTS build (scripts/build_debug.sh)"
+
+
+def int_view(t):
+    """the bits of a 2- or 4-byte tensor"""
+    return t.view({2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def middle(n, dtype, device, fill, pad=GUARD_PAD):
+    """(big, view): n elements in the MIDDLE of a tensor of pad + n + pad, all of it `fill` (NaN around an input; for an
+    index array the index of a guard row)"""
+    big = torch.full((pad + n + pad,), fill, dtype=dtype, device=device)
+    return big, big[pad:pad + n]
+
+
+class Guarded:
+    """An output buffer of n 2- or 4-byte elements in the middle of a position-dependent bit pattern.  fill() puts a NaN
+    bit pattern inside before a launch; intact() says whether the surroundings still hold the pattern."""
+    NAN = {2: 0x7fc1, 4: 0x7fc00001}
+
+    def __init__(self, n, elem_bytes, device, base=0, pad=GUARD_PAD):
+        idt = {2: torch.int16, 4: torch.int32}[elem_bytes]
+        start = {2: 0x4000, 4: 0x40000000}[elem_bytes]
+        self.big = ((torch.arange(2 * pad + n, device=device) % 251) + start + base).to(idt)
+        self.bits = self.big[pad:pad + n]
+        self.before, self.after = self.big[:pad].clone(), self.big[pad + n:].clone()
+        self.nan = self.NAN[elem_bytes]
+        self.pad, self.n = pad, n
+        assert self.bits.data_ptr() % 16 == 0
+
+    def ptr(self):
+        return self.bits.data_ptr()
+
+    def fill(self):
+        self.bits.fill_(self.nan)
+
+    def untouched(self):
+        return bool((self.bits == self.nan).all())
+
+    def intact(self):
+        return torch.equal(self.big[:self.pad], self.before) and torch.equal(self.big[self.pad + self.n:], self.after)
+
+    def as_dtype(self, dtype, shape):
+        return self.bits.clone().view(dtype).reshape(shape)
+
+
+def exact_weights_bf16(rng, shape):
+    """fp32 weights that round (RNE) to multiples of 2^-6 in [-2, 2]: such a value plus a perturbation below a quarter of
+    a bf16 ulp, and a few exact ties (value + half an ulp away from zero, which round back to the even value).
+    Returns (fed, rounded) as torch tensors."""
+    m = rng.integers(-128, 129, size=shape)
+    w = (m / 64.0).astype(np.float32)
+    _, e = np.frexp(np.abs(w))
+    ulp = np.where(m != 0, np.ldexp(1.0, e - 8), 0.0)
+    pert = rng.uniform(-0.24, 0.24, size=w.shape) * ulp
+    ties = np.zeros(w.shape, bool)
+    nz = np.flatnonzero(m)
+    ties.reshape(-1)[rng.choice(nz, min(len(nz), max(3, w.size // 50)), replace=False)] = True
+    pert[ties] = (np.sign(w) * 0.5 * ulp)[ties]
+    fed = torch.from_numpy((w.astype(np.float64) + pert).astype(np.float32))
+    rounded = fed.to(torch.bfloat16).to(torch.float32)
+    assert torch.equal(rounded, torch.from_numpy(w)), "the perturbed weights must round to the multiples of 2^-6"
+    return fed, rounded
+
+
+def same_nonfinite_class(got, ref, what):
+    """NaN / +Inf / -Inf / finite at the same elements of both arrays"""
+    for name, sel in (("NaN", np.isnan), ("+Inf", np.isposinf), ("-Inf", np.isneginf), ("finite", np.isfinite)):
+        bad = sel(ref) != sel(got)
+        at = tuple(np.argwhere(bad)[0]) if bad.any() else None
+        assert at is None, (f"{what}: {int(bad.sum())} elements are {name} on one side only, e.g. {at}: "
+                            f"{got[at]} for {ref[at]}")
+
+
+def assert_tile_partials(stored, tile_rows, mean, m2, what):
+    """Batch-norm partials of a kernel that forms them as the tile kernels do — per tile and column, over the rows in tile
+    order (`stored`: float64 [n, c], the values actually stored), d = y - (the tile's first row), a = sum d, b = sum d^2 in
+    fp32, mean = shift + a / rows, M2 = max(b - a (a / rows), 0) — against the float64 mean and M2 of the same values:
+      |mean - ref| <= c 2^-24 (|shift| + max|d|)      |M2 - ref| <= c 2^-22 sum d^2      with c = rows + 4:
+    each d is exact (bf16 differences fit fp32), a sum of `rows` terms in any order is off by at most rows 2^-24 times the
+    sum of the magnitudes (<= rows max|d|, and a / rows brings that back to max|d|), the division and the shift added
+    back are two more roundings; b and a m are each at most sum d^2 (Cauchy-Schwarz) with the same relative error, and
+    their difference keeps the absolute one: four such terms -> 2^-22.  A tile of equal rows gives M2 == 0 exactly."""
+    n, c = stored.shape
+    tiles = -(-n // tile_rows)
+    assert mean.shape == (tiles, c) and m2.shape == (tiles, c), (what, mean.shape, (tiles, c))
+    assert np.isfinite(mean).all() and np.isfinite(m2).all() and (m2 >= 0).all(), f"{what}: partials not finite"
+    for t in range(tiles):
+        rows = stored[t * tile_rows:min((t + 1) * tile_rows, n)]
+        cnt = len(rows) + 4
+        d = rows - rows[0]
+        ref_mean = rows.mean(0)
+        ref_m2 = ((rows - ref_mean) ** 2).sum(0)
+        em, e2 = np.abs(mean[t] - ref_mean), np.abs(m2[t] - ref_m2)
+        tol_mean = cnt * 2.0 ** -24 * (np.abs(rows[0]) + np.abs(d).max(0))
+        tol_m2 = cnt * 2.0 ** -22 * (d * d).sum(0)
+        assert (em <= tol_mean).all(), f"{what}: tile {t} ({len(rows)} rows) mean off by {em.max():.3g}"
+        assert (e2 <= tol_m2).all(), f"{what}: tile {t} ({len(rows)} rows) M2 off by {e2.max():.3g}"
+        assert (m2[t][(d == 0).all(0)] == 0).all(), f"{what}: tile {t}: M2 of a constant column is not exactly 0"
+
+
 def row_mapping(coords_a, coords_b):
     """m with coords_b[m[i]] == coords_a[i] (same coordinate sets, different row order)."""
     from oracle import me_oracle as O

@@ -96,7 +96,10 @@ typedef struct me_region {
  *              (me_gnorm_workspace_bytes, me_gnorm_stats, me_gnorm_apply, me_gnorm_backward and their _f64 twins)
  *   1.16 (260)  round 16: conditional group normalisation: a per-instance scale / shift folded into the affine map and a
  *              fused SiLU (me_gnorm_cond_workspace_bytes, me_gnorm_cond_apply, me_gnorm_cond_backward and their _f64
- *              twins) */
+ *              twins)
+ *   1.17 (270)  round 17: per-instance multi-head attention over the rows of a coordinate map: forward and backward on
+ *              the MFMA pipe through per-instance row lists (me_attn_workspace_bytes, me_attn_forward, me_attn_backward
+ *              and the _f64 twins me_attn_forward_f64, me_attn_backward_f64) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1152,6 +1155,47 @@ int me_gnorm_cond_backward_f64(const double *x_dev, const double *dy_dev, const 
                                const double *shift_dev, int32_t act, double *dx_dev, double *grad_gamma_dev,
                                double *grad_beta_dev, double *grad_scale_dev, double *grad_shift_dev, void *workspace_dev,
                                int64_t workspace_bytes, void *stream);
+
+/* ---- per-instance multi-head attention (MinkowskiSelfAttention, MinkowskiFunctional.scaled_dot_product_attention;
+ *      csrc/attention.hip, ABI 1.17) ----
+ * q: [n_q, c] rows on map A; k, v: [n_kv, c] rows on map B; c = heads * d.  For query row i, head h and its instance b(i):
+ *   s_ij = scale * <q[i, h, :], k[j, h, :]> over the rows j of B with b(j) = b(i)
+ *   out[i, h, :] = sum_j softmax_j(s_ij) * v[j, h, :],   lse[i, h] = log sum_j exp(s_ij)   ([n_q, heads] fp32, contiguous)
+ * A query whose instance has no row on B: a zero output row, lse = -inf, zero gradients.  The rows of instance b are
+ * seg_rows[seg_ptr[b] .. seg_ptr[b + 1]) in ascending order (me_csr_from_coo of the origin rows of the map, n_batch rows);
+ * keys are summed in that order.  Every operand carries a row stride in elements: >= c, a multiple of 16 bytes, last
+ * dimension contiguous, base pointers 16-byte aligned (the column slices of one [n, 3 c] projection go in without copies).
+ * fp32 / bf16 entry points: d in {32, 64, 128}, softmax and statistics in fp32, P and dS rounded to bf16 on bf16 rows.
+ * me_attn_backward: dq / dk / dv may be NULL (not computed; the dK / dV launch is skipped when both are, the dQ launch when
+ * dq is); the workspace (me_attn_workspace_bytes) holds delta[i, h] = <dout_i, out_i>.  No atomics, fixed summation order:
+ * bitwise reproducible.  Host-side argument errors (nothing launched, reachable with NULL data pointers): c % heads != 0; a
+ * head dimension other than 32 / 64 / 128; a stride below c or not a multiple of 16 bytes; a short workspace; a missing
+ * table pointer.  The _f64 entry points: plain double, any head dimension, any stride >= c, lse double, no workspace. */
+int64_t me_attn_workspace_bytes(int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t heads);
+int me_attn_forward(const void *q_dev, const void *k_dev, const void *v_dev, int32_t is_bf16, int64_t q_stride,
+                    int64_t k_stride, int64_t v_stride, const int32_t *seg_ptr_q_dev, const int32_t *seg_rows_q_dev,
+                    const int32_t *seg_ptr_kv_dev, const int32_t *seg_rows_kv_dev, int64_t n_q, int64_t n_kv,
+                    int32_t n_batch, int32_t c, int32_t heads, float scale, void *out_dev, int64_t out_stride,
+                    float *lse_dev, void *stream);
+int me_attn_backward(const void *q_dev, const void *k_dev, const void *v_dev, const void *out_dev, const float *lse_dev,
+                     const void *dout_dev, int32_t is_bf16, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                     int64_t out_stride, int64_t dout_stride, const int32_t *seg_ptr_q_dev, const int32_t *seg_rows_q_dev,
+                     const int32_t *seg_ptr_kv_dev, const int32_t *seg_rows_kv_dev, int64_t n_q, int64_t n_kv,
+                     int32_t n_batch, int32_t c, int32_t heads, float scale, void *dq_dev, int64_t dq_stride, void *dk_dev,
+                     int64_t dk_stride, void *dv_dev, int64_t dv_stride, void *workspace_dev, int64_t workspace_bytes,
+                     void *stream);
+int me_attn_forward_f64(const double *q_dev, const double *k_dev, const double *v_dev, int64_t q_stride, int64_t k_stride,
+                        int64_t v_stride, const int32_t *seg_ptr_q_dev, const int32_t *seg_rows_q_dev,
+                        const int32_t *seg_ptr_kv_dev, const int32_t *seg_rows_kv_dev, int64_t n_q, int64_t n_kv,
+                        int32_t n_batch, int32_t c, int32_t heads, double scale, double *out_dev, int64_t out_stride,
+                        double *lse_dev, void *stream);
+int me_attn_backward_f64(const double *q_dev, const double *k_dev, const double *v_dev, const double *out_dev,
+                         const double *lse_dev, const double *dout_dev, int64_t q_stride, int64_t k_stride,
+                         int64_t v_stride, int64_t out_stride, int64_t dout_stride, const int32_t *seg_ptr_q_dev,
+                         const int32_t *seg_rows_q_dev, const int32_t *seg_ptr_kv_dev, const int32_t *seg_rows_kv_dev,
+                         int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads, double scale, double *dq_dev,
+                         int64_t dq_stride, double *dk_dev, int64_t dk_stride, double *dv_dev, int64_t dv_stride,
+                         void *stream);
 
 /* ---- dense <-> sparse conversion (SparseTensor.dense, ME.to_sparse, ME.to_sparse_all, ME.dense_coordinates:
  *      MinkowskiEngine/MinkowskiSparseTensor.py:460-557 and MinkowskiOps.py:246-348, torch indexing there;

@@ -3,7 +3,8 @@ the torch function runs on the feature matrix `.F`.  Activations and the other f
 tensor of the input's kind on the input's coordinates (a TensorField stays a TensorField); losses take a torch target
 and return what torch returns.  No kernels of their own, except `group_norm` and `conditional_group_norm`:
 torch's needs one dense tensor per sample, so they run MinkowskiGroupNorm's and MinkowskiConditionalGroupNorm's operators
-(normalization.py, csrc/group_norm.hip)."""
+(normalization.py, csrc/group_norm.hip); and `scaled_dot_product_attention`, which attends inside every instance on the
+operators of attention.py (csrc/attention.hip)."""
 import torch.nn.functional as F
 
 from .layers import _rewrap
@@ -71,4 +72,23 @@ def conditional_group_norm(input, num_groups, weight=None, bias=None, scale=None
     return SparseTensor(out, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
 
 
-__all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm"]
+def scaled_dot_product_attention(query, key, value, num_heads, scale=None):
+    """torch.nn.functional.scaled_dot_product_attention inside every instance (batch index): a row of `query` attends to
+    the rows of `key` / `value` with its own batch index.  `key` and `value` share a coordinate map of `query`'s manager
+    (it may be `query`'s map); the channels split into `num_heads` heads of 32, 64 or 128 (any size in float64); scale
+    defaults to 1 / sqrt(head size).  No mask, no dropout.  The result sits on `query`'s map."""
+    from .attention import MinkowskiAttentionFunction
+    from .sparse_tensor import SparseTensor
+    for name, t in (("query", query), ("key", key), ("value", value)):
+        if not isinstance(t, SparseTensor):
+            raise TypeError(f"scaled_dot_product_attention takes SparseTensors; {name} is a {type(t).__name__}")
+    if key.coordinate_map_key != value.coordinate_map_key or key._manager is not value._manager:
+        raise ValueError("key and value must share a coordinate map")
+    if key._manager is not query._manager:
+        raise ValueError("query and key / value must belong to the same coordinate manager")
+    out = MinkowskiAttentionFunction.apply(query.F, key.F, value.F, num_heads, scale, query.coordinate_map_key,
+                                           key.coordinate_map_key, None, query._manager)
+    return SparseTensor(out, coordinate_map_key=query.coordinate_map_key, coordinate_manager=query._manager)
+
+
+__all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention"]

@@ -753,6 +753,7 @@ class CoordinateMapManagerGPU_c10:
         self._maps = {}          # (tensor_stride tuple, string_id) -> _CoordinateMapGPU
         self._kernel_maps = {}   # kernel_map_key (src/types.hpp:183-192) -> KernelMapGPU
         self._origin_maps = {}
+        self._instance_rows_cache = {}
         self._prune_rows = {}
         self._union_arith = {}   # (key a, key b), ordered -> (union key, u_of_a, u_of_b, a_of_u, b_of_u): union_arith_maps
         self._stride_maps = {}
@@ -1263,6 +1264,18 @@ class CoordinateMapManagerGPU_c10:
             self._origin_maps[ik] = rows
         return rows
 
+    def _instance_rows(self, in_key):
+        """(seg_ptr int32 [n_batch + 1], seg_rows int32 [n_in]): the rows of `in_key` of every instance (row of the origin
+        map), ascending inside an instance — the stable me_csr_from_coo of _origin_rows.  Built once per map, no
+        read-back: the per-instance row lists of the attention kernels (csrc/attention.hip)."""
+        ik = self._k(in_key)
+        lists = self._instance_rows_cache.get(ik)
+        if lists is None:
+            rows = self._origin_rows(in_key)
+            seg_ptr, seg_rows, _ = CsrFromCooGPU(rows, self.size(self.origin()))
+            lists = self._instance_rows_cache[ik] = (seg_ptr, seg_rows)
+        return lists
+
     def origin_map(self, in_key):
         """{0: int32 [2, n_in]} (row 0 = in rows, row 1 = origin rows), the reference's origin_map_th layout."""
         rows = self._origin_rows(in_key)
@@ -1357,7 +1370,8 @@ class CoordinateMapManagerGPU_c10:
                 for name in names:
                     if name not in ("_recipe", "in_map", "out_map"):
                         walk(getattr(o, name, None), depth + 1)
-        for store in (self._maps, self._kernel_maps, self._origin_maps, self._origin_field_maps, self._prune_rows,
+        for store in (self._maps, self._kernel_maps, self._origin_maps, self._instance_rows_cache,
+                      self._origin_field_maps, self._prune_rows,
                       self._stride_maps, self._union_arith):
             walk(store)
         return out
@@ -3495,6 +3509,108 @@ def ConditionalGroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, 
                 _ptr(weight), _ptr(bias), _ptr(scale), _ptr(shift), act, _ptr(grad_in), _ptr(grad_weight),
                 _ptr(grad_bias), _ptr(grad_scale), _ptr(grad_shift), _ptr(ws), ws.numel(), _stream(dev))))
     return grad_in, grad_weight, grad_bias, grad_scale, grad_shift
+
+
+# ------------------------------------------------------------------------------------------------
+# per-instance multi-head attention (csrc/attention.hip; not in the reference): a query row of map A attends to the key /
+# value rows of map B with its own batch index.  The operands may be strided row views (column slices of one projection).
+# ------------------------------------------------------------------------------------------------
+def _attn_rows(name, t, ref=None):
+    """a 2-D CUDA operand with a contiguous last dimension (any row stride >= its width); anything else is copied"""
+    _check(t.is_cuda, name, "must be CUDA (ROCm) — the MI355X path has no CPU implementation")
+    _check(t.dim() == 2 and t.shape[1] > 0, "Invalid", name, "shape:", tuple(t.shape))
+    _check(t.dtype in (torch.float32, torch.bfloat16, torch.float64), name, "must be float32, bfloat16 or float64, got",
+           t.dtype)
+    if ref is not None:
+        _check(t.dtype == ref.dtype and t.device == ref.device and t.shape[1] == ref.shape[1], name,
+               "must have the dtype, device and channel count of q")
+    if t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    elif t.shape[0] <= 1 and not t.is_contiguous():
+        t = t.contiguous()
+    return t
+
+
+def _attn_stride(t):
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def _attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, manager):
+    q = _attn_rows("q", q)
+    k = _attn_rows("k", k, q)
+    v = _attn_rows("v", v, q)
+    _check(manager.exists(q_key) and manager.exists(kv_key), "coordinate map not found")
+    _check(q.shape[0] == manager.size(q_key), "Invalid q size", q.shape[0], "!=", manager.size(q_key))
+    _check(k.shape[0] == manager.size(kv_key) and v.shape[0] == k.shape[0], "Invalid k / v size", k.shape[0], v.shape[0],
+           "!=", manager.size(kv_key))
+    heads, c = int(num_heads), int(q.shape[1])
+    _check(heads > 0 and c % heads == 0, "the channel count", c, "must be a multiple of num_heads", heads)
+    if not glob_key.is_key_set():
+        glob_key.set_key(manager.origin().get_key())
+    seg_q = manager._instance_rows(q_key)
+    seg_kv = manager._instance_rows(kv_key)
+    return q, k, v, heads, c, seg_q, seg_kv, manager.size(glob_key)
+
+
+def AttentionForwardGPU(q, k, v, num_heads, scale, q_key, kv_key, glob_key, manager):
+    """-> (out [n_q, C], lse [n_q, heads]): out[i, h] = sum_j softmax_j(scale <q[i, h], k[j, h]>) v[j, h] over the rows j of
+    kv_key with the batch index of row i of q_key; lse = log sum_j exp(.) in fp32 (float64 for float64 features).  A query
+    whose instance has no key row: a zero row and lse = -inf."""
+    q, k, v, heads, c, seg_q, seg_kv, n_batch = _attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, manager)
+    lib = _lib.load()
+    dev = q.device
+    n_q, n_kv = int(q.shape[0]), int(k.shape[0])
+    out = torch.empty((n_q, c), dtype=q.dtype, device=dev)
+    lse = torch.empty((n_q, heads), dtype=_inorm_param_dtype(q), device=dev)
+    with _on(dev):
+        if q.dtype == torch.float64:
+            _lib.check(lib.me_attn_forward_f64(_ptr(q), _ptr(k), _ptr(v), _attn_stride(q), _attn_stride(k), _attn_stride(v),
+                                               _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]), _ptr(seg_kv[1]), n_q, n_kv,
+                                               n_batch, c, heads, float(scale), _ptr(out), c, _ptr(lse), _stream(dev)))
+        else:
+            bf = 1 if q.dtype == torch.bfloat16 else 0
+            _timed("attn_forward", dev, lambda: _lib.check(lib.me_attn_forward(
+                _ptr(q), _ptr(k), _ptr(v), bf, _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(seg_q[0]),
+                _ptr(seg_q[1]), _ptr(seg_kv[0]), _ptr(seg_kv[1]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(out), c,
+                _ptr(lse), _stream(dev))))
+    return out, lse
+
+
+def AttentionBackwardGPU(q, k, v, out, lse, grad_out, num_heads, scale, q_key, kv_key, glob_key, manager,
+                         need_grad_q=True, need_grad_k=True, need_grad_v=True):
+    """-> (grad_q | None, grad_k | None, grad_v | None), contiguous, from out and lse of the forward pass.  A gradient that
+    is not requested is not computed: no dK / dV launch when neither is wanted, no dQ launch when grad_q is not."""
+    q, k, v, heads, c, seg_q, seg_kv, n_batch = _attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, manager)
+    out = _attn_rows("out", out, q)
+    grad_out = _attn_rows("grad_out", grad_out.to(q.dtype))
+    _check(tuple(out.shape) == tuple(q.shape) and tuple(grad_out.shape) == tuple(q.shape),
+           "out and grad_out must have the shape of q")
+    _check(lse.is_cuda and lse.is_contiguous() and lse.dtype == _inorm_param_dtype(q) and
+           tuple(lse.shape) == (q.shape[0], heads), "lse must be the contiguous [n_q, heads] statistics of the forward pass")
+    lib = _lib.load()
+    dev = q.device
+    n_q, n_kv = int(q.shape[0]), int(k.shape[0])
+    grad_q = torch.empty((n_q, c), dtype=q.dtype, device=dev) if need_grad_q else None
+    grad_k = torch.empty((n_kv, c), dtype=q.dtype, device=dev) if need_grad_k else None
+    grad_v = torch.empty((n_kv, c), dtype=q.dtype, device=dev) if need_grad_v else None
+    if not (need_grad_q or need_grad_k or need_grad_v):
+        return None, None, None
+    with _on(dev):
+        if q.dtype == torch.float64:
+            _lib.check(lib.me_attn_backward_f64(
+                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), _attn_stride(q), _attn_stride(k),
+                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]),
+                _ptr(seg_kv[1]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(grad_q), c, _ptr(grad_k), c, _ptr(grad_v),
+                c, _stream(dev)))
+        else:
+            bf = 1 if q.dtype == torch.bfloat16 else 0
+            ws = _workspace(int(lib.me_attn_workspace_bytes(n_q, n_kv, n_batch, heads)), dev)
+            _timed("attn_backward", dev, lambda: _lib.check(lib.me_attn_backward(
+                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), bf, _attn_stride(q), _attn_stride(k),
+                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]),
+                _ptr(seg_kv[1]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(grad_q), c, _ptr(grad_k), c, _ptr(grad_v),
+                c, _ptr(ws), ws.numel(), _stream(dev))))
+    return grad_q, grad_k, grad_v
 
 
 # ------------------------------------------------------------------------------------------------

@@ -269,6 +269,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return d;
            })
       .def("_origin_rows", [](CoordinateMapManager &s, const CoordinateMapKey *k) { return s.origin_rows(keyt(k)); })
+      .def("_instance_rows",
+           [](CoordinateMapManager &s, const CoordinateMapKey *k) {
+             const auto &r = s.instance_rows(keyt(k));
+             return py::make_tuple(r.first, r.second);
+           })
       .def("get_coordinates", [](CoordinateMapManager &s, const CoordinateMapKey *k) { return s.get(keyt(k))->coords; })
       // tensor fields (pybind/extern.hpp:780-805; field.cpp)
       .def("insert_field",
@@ -613,6 +618,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"), py::arg("shift"), py::arg("activation"), py::arg("mean"), py::arg("rstd"), py::arg("in_key"),
         py::arg("glob_key"), py::arg("manager"), py::arg("need_grad_in") = true, py::arg("need_grad_weight") = true,
         py::arg("need_grad_bias") = true, py::arg("need_grad_scale") = true, py::arg("need_grad_shift") = true);
+  // per-instance multi-head attention on the kernels of csrc/attention.hip (strided row views go in without copies)
+  m.def("AttentionForwardGPU",
+        [](const Tensor &q, const Tensor &k, const Tensor &v, int64_t num_heads, double scale, CoordinateMapKey *q_key,
+           CoordinateMapKey *kv_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+          std::pair<Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = attention_forward(q, k, v, num_heads, scale, q_key, kv_key, glob_key, mgr);
+          }
+          return py::make_tuple(r.first, r.second);
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("num_heads"), py::arg("scale"), py::arg("q_key"),
+        py::arg("kv_key"), py::arg("glob_key"), py::arg("manager"));
+  m.def("AttentionBackwardGPU",
+        [](const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse, const Tensor &grad_out,
+           int64_t num_heads, double scale, CoordinateMapKey *q_key, CoordinateMapKey *kv_key, CoordinateMapKey *glob_key,
+           CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k, bool need_grad_v) {
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = attention_backward(q, k, v, out, lse, grad_out, num_heads, scale, q_key, kv_key, glob_key, mgr, need_grad_q,
+                                   need_grad_k, need_grad_v);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]));
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("grad_out"),
+        py::arg("num_heads"), py::arg("scale"), py::arg("q_key"), py::arg("kv_key"), py::arg("glob_key"),
+        py::arg("manager"), py::arg("need_grad_q") = true, py::arg("need_grad_k") = true, py::arg("need_grad_v") = true);
   // tensor fields (field.cpp): the reference's InterpolationForwardGPU / InterpolationBackwardGPU and coo_spmm_int32 /
   // coo_spmm_average_int32 (pybind/extern.hpp:497-506), plus the CSR building blocks the autograd functions cache
   m.def("CsrFromCooGPU",

@@ -254,6 +254,7 @@ struct CoordinateMapManager {
   std::vector<KeyT> map_order;      // insertion order (origin(): "any key"; __repr__)
   std::map<KernelMapKeyT, std::shared_ptr<KernelMap>> kernel_maps;
   std::map<KeyT, Tensor> origin_rows_cache;
+  std::map<KeyT, std::pair<Tensor, Tensor>> instance_rows_cache;   // per-instance row lists (seg_ptr, seg_rows)
   std::map<std::pair<KeyT, KeyT>, Tensor> prune_rows;
   std::map<std::pair<KeyT, KeyT>, std::pair<Tensor, Tensor>> stride_maps;
   // arithmetic across maps: ORDERED (key a, key b) -> union key and {u_of_a, u_of_b, a_of_u, b_of_u} (union_arith_maps)
@@ -289,6 +290,9 @@ struct CoordinateMapManager {
   const std::pair<KeyT, std::vector<Tensor>> &union_arith_maps(const KeyT &key_a, const KeyT &key_b);
   KeyT origin();
   Tensor origin_rows(const KeyT &in_key);
+  // (seg_ptr int32 [n_batch + 1], seg_rows int32 [n]): the rows of every instance, ascending (stable csr_from_coo of
+  // origin_rows), cached per map: the row lists of the attention kernels (twin of backend._instance_rows)
+  const std::pair<Tensor, Tensor> &instance_rows(const KeyT &in_key);
   std::shared_ptr<KernelMap> kernel_map(const KeyT &in_key, const KeyT &out_key, const ivec &kernel_size,
                                         const ivec &kernel_stride, const ivec &kernel_dilation, int region_type,
                                         bool is_transpose, bool is_pool, const ivec &offsets = ivec());
@@ -378,6 +382,14 @@ std::vector<Tensor> cond_group_norm_backward(const Tensor &in_feat, Tensor grad_
                                              CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
                                              CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_weight,
                                              bool need_grad_bias, bool need_grad_scale, bool need_grad_shift);
+// per-instance multi-head attention (csrc/attention.hip; twin of backend.Attention{Forward,Backward}GPU)
+std::pair<Tensor, Tensor> attention_forward(Tensor q, Tensor k, Tensor v, int64_t num_heads, double scale,
+                                            CoordinateMapKey *q_key, CoordinateMapKey *kv_key, CoordinateMapKey *glob_key,
+                                            CoordinateMapManager *mgr);
+std::vector<Tensor> attention_backward(Tensor q, Tensor k, Tensor v, Tensor out, const Tensor &lse, Tensor grad_out,
+                                       int64_t num_heads, double scale, CoordinateMapKey *q_key, CoordinateMapKey *kv_key,
+                                       CoordinateMapKey *glob_key, CoordinateMapManager *mgr, bool need_grad_q,
+                                       bool need_grad_k, bool need_grad_v);
 // dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU / DensePolicy)
 int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box);
 std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,

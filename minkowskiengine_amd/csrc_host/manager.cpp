@@ -1106,6 +1106,14 @@ Tensor CoordinateMapManager::origin_rows(const KeyT &in_key) {
   return rows;
 }
 
+const std::pair<Tensor, Tensor> &CoordinateMapManager::instance_rows(const KeyT &in_key) {
+  auto it = instance_rows_cache.find(in_key);
+  if (it != instance_rows_cache.end()) return it->second;
+  Tensor rows = origin_rows(in_key);
+  auto t = csr_from_coo(rows, get(origin())->n, Tensor(), Tensor());
+  return instance_rows_cache[in_key] = {std::get<0>(t), std::get<1>(t)};
+}
+
 // Sides of a hyper-cube map (looked-up map `fine_ts`, iterated map `coarse_ts`) on which a row has at most ONE pair by
 // construction: windows of kernel_size voxels that tile space without overlap (coarse stride = kernel_size x fine stride,
 // no dilation) hold every fine voxel exactly once -> bit 0 (the "in" = fine side).  A single-offset kernel pairs a row
@@ -1327,6 +1335,10 @@ std::vector<Tensor> CoordinateMapManager::device_tensors() {
     }
   }
   for (auto &kv : origin_rows_cache) collect(out, kv.second);
+  for (auto &kv : instance_rows_cache) {
+    collect(out, kv.second.first);
+    collect(out, kv.second.second);
+  }
   for (auto &kv : origin_field_rows_cache) collect(out, kv.second);
   for (auto &kv : prune_rows) collect(out, kv.second);
   for (auto &kv : union_arith)

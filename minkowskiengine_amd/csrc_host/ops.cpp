@@ -1296,6 +1296,113 @@ std::vector<Tensor> cond_group_norm_backward(const Tensor &in_feat, Tensor grad_
   return {grad_in, grad_weight, grad_bias, grad_scale, grad_shift};
 }
 
+// ---- per-instance multi-head attention (csrc/attention.hip; twin of backend.Attention{Forward,Backward}GPU) ------------------
+// a 2-D CUDA operand with a contiguous last dimension (any row stride >= its width); anything else is copied
+static Tensor attn_rows(const char *name, Tensor t, const Tensor *ref = nullptr) {
+  check(t.is_cuda(), std::string(name) + " must be CUDA (ROCm) — the MI355X path has no CPU implementation");
+  check(t.dim() == 2 && t.size(1) > 0, std::string("Invalid ") + name + " shape");
+  check(t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kDouble,
+        std::string(name) + " must be float32, bfloat16 or float64");
+  if (ref)
+    check(t.scalar_type() == ref->scalar_type() && t.device() == ref->device() && t.size(1) == ref->size(1),
+          std::string(name) + " must have the dtype, device and channel count of q");
+  if (t.size(0) > 1 ? (t.stride(1) != 1 || t.stride(0) < t.size(1)) : !t.is_contiguous()) t = t.contiguous();
+  return t;
+}
+static int64_t attn_stride(const Tensor &t) { return t.size(0) > 1 ? t.stride(0) : t.size(1); }
+
+struct AttnPrep {
+  int heads, c, n_batch;
+  std::pair<Tensor, Tensor> seg_q, seg_kv;
+};
+static AttnPrep attn_prepare(Tensor &q, Tensor &k, Tensor &v, int64_t num_heads, CoordinateMapKey *q_key,
+                             CoordinateMapKey *kv_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+  q = attn_rows("q", q);
+  k = attn_rows("k", k, &q);
+  v = attn_rows("v", v, &q);
+  const KeyT &qk = q_key->get(), &kk = kv_key->get();
+  check(mgr->exists(qk) && mgr->exists(kk), "coordinate map not found");
+  check(q.size(0) == mgr->get(qk)->n, "Invalid q size");
+  check(k.size(0) == mgr->get(kk)->n && v.size(0) == k.size(0), "Invalid k / v size");
+  const int64_t c = q.size(1);
+  check(num_heads > 0 && c % num_heads == 0, "the channel count " + std::to_string(c) +
+                                                 " must be a multiple of num_heads " + std::to_string(num_heads));
+  if (!glob_key->key_set) {
+    KeyT ok = mgr->origin();
+    glob_key->set_key(ok.first, ok.second);
+  }
+  AttnPrep p;
+  p.heads = (int)num_heads;
+  p.c = (int)c;
+  p.seg_q = mgr->instance_rows(qk);
+  p.seg_kv = mgr->instance_rows(kk);
+  p.n_batch = (int)mgr->get(glob_key->get())->n;
+  return p;
+}
+
+std::pair<Tensor, Tensor> attention_forward(Tensor q, Tensor k, Tensor v, int64_t num_heads, double scale,
+                                            CoordinateMapKey *q_key, CoordinateMapKey *kv_key, CoordinateMapKey *glob_key,
+                                            CoordinateMapManager *mgr) {
+  const AttnPrep p = attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, mgr);
+  const c10::Device dev = q.device();
+  const bool f64 = q.scalar_type() == at::kDouble;
+  const int64_t n_q = q.size(0), n_kv = k.size(0);
+  Tensor out = at::empty({n_q, p.c}, q.options());
+  Tensor lse = at::empty({n_q, p.heads}, at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev));
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_attn_forward_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), attn_stride(q), attn_stride(k),
+                              attn_stride(v), ptr<int32_t>(p.seg_q.first), ptr<int32_t>(p.seg_q.second),
+                              ptr<int32_t>(p.seg_kv.first), ptr<int32_t>(p.seg_kv.second), n_q, n_kv, p.n_batch, p.c,
+                              p.heads, scale, ptr<double>(out), p.c, ptr<double>(lse), stream_of(dev)));
+  } else {
+    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+    me_ok(me_attn_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v),
+                          ptr<int32_t>(p.seg_q.first), ptr<int32_t>(p.seg_q.second), ptr<int32_t>(p.seg_kv.first),
+                          ptr<int32_t>(p.seg_kv.second), n_q, n_kv, p.n_batch, p.c, p.heads, (float)scale, out.data_ptr(),
+                          p.c, ptr<float>(lse), stream_of(dev)));
+  }
+  return {out, lse};
+}
+
+std::vector<Tensor> attention_backward(Tensor q, Tensor k, Tensor v, Tensor out, const Tensor &lse, Tensor grad_out,
+                                       int64_t num_heads, double scale, CoordinateMapKey *q_key, CoordinateMapKey *kv_key,
+                                       CoordinateMapKey *glob_key, CoordinateMapManager *mgr, bool need_grad_q,
+                                       bool need_grad_k, bool need_grad_v) {
+  const AttnPrep p = attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, mgr);
+  out = attn_rows("out", out, &q);
+  grad_out = attn_rows("grad_out", grad_out.to(q.scalar_type()));
+  check(out.sizes() == q.sizes() && grad_out.sizes() == q.sizes(), "out and grad_out must have the shape of q");
+  const c10::Device dev = q.device();
+  const bool f64 = q.scalar_type() == at::kDouble;
+  check(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == (f64 ? at::kDouble : at::kFloat) && lse.dim() == 2 &&
+            lse.size(0) == q.size(0) && lse.size(1) == p.heads,
+        "lse must be the contiguous [n_q, heads] statistics of the forward pass");
+  const int64_t n_q = q.size(0), n_kv = k.size(0);
+  Tensor grad_q = need_grad_q ? at::empty({n_q, p.c}, q.options()) : Tensor();
+  Tensor grad_k = need_grad_k ? at::empty({n_kv, p.c}, q.options()) : Tensor();
+  Tensor grad_v = need_grad_v ? at::empty({n_kv, p.c}, q.options()) : Tensor();
+  if (!(need_grad_q || need_grad_k || need_grad_v)) return {grad_q, grad_k, grad_v};
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_attn_backward_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), ptr<double>(out), ptr<double>(lse),
+                               ptr<double>(grad_out), attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out),
+                               attn_stride(grad_out), ptr<int32_t>(p.seg_q.first), ptr<int32_t>(p.seg_q.second),
+                               ptr<int32_t>(p.seg_kv.first), ptr<int32_t>(p.seg_kv.second), n_q, n_kv, p.n_batch, p.c,
+                               p.heads, scale, ptr<double>(grad_q), p.c, ptr<double>(grad_k), p.c, ptr<double>(grad_v), p.c,
+                               stream_of(dev)));
+  } else {
+    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+    Tensor ws = workspace(me_attn_workspace_bytes(n_q, n_kv, p.n_batch, p.heads), dev);
+    me_ok(me_attn_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ptr<float>(lse), grad_out.data_ptr(),
+                           bf, attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out), attn_stride(grad_out),
+                           ptr<int32_t>(p.seg_q.first), ptr<int32_t>(p.seg_q.second), ptr<int32_t>(p.seg_kv.first),
+                           ptr<int32_t>(p.seg_kv.second), n_q, n_kv, p.n_batch, p.c, p.heads, (float)scale, vptr(grad_q),
+                           p.c, vptr(grad_k), p.c, vptr(grad_v), p.c, vptr(ws), ws.numel(), stream_of(dev)));
+  }
+  return {grad_q, grad_k, grad_v};
+}
+
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------
 Tensor pruning_forward(const Tensor &in_feat, const Tensor &keep, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr) {

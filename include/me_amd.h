@@ -99,7 +99,11 @@ typedef struct me_region {
  *              twins)
  *   1.17 (270)  round 17: per-instance multi-head attention over the rows of a coordinate map: forward and backward on
  *              the MFMA pipe through per-instance row lists (me_attn_workspace_bytes, me_attn_forward, me_attn_backward
- *              and the _f64 twins me_attn_forward_f64, me_attn_backward_f64) */
+ *              and the _f64 twins me_attn_forward_f64, me_attn_backward_f64)
+ *   1.18 (280)  round 18: local attention over a kernel map: every out row attends to the in rows of its kernel region,
+ *              with an optional per-head, per-offset bias; gather kernels on the neighbour tables, no atomics
+ *              (me_local_attn_workspace_bytes, me_local_attn_forward, me_local_attn_backward and the _f64 twins
+ *              me_local_attn_forward_f64, me_local_attn_backward_f64) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1196,6 +1200,52 @@ int me_attn_backward_f64(const double *q_dev, const double *k_dev, const double 
                          int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads, double scale, double *dq_dev,
                          int64_t dq_stride, double *dk_dev, int64_t dk_stride, double *dv_dev, int64_t dv_stride,
                          void *stream);
+
+/* ---- local attention over a kernel map (MinkowskiLocalSelfAttention, MinkowskiFunctional.local_attention;
+ *      csrc/local_attention.hip, ABI 1.18) ----
+ * q: [n_out, c] rows on the out map; k, v: [n_in, c] rows on the in map; c = heads * d.  nbr_out: int32 [volume, n_out],
+ * the in row of offset k of out row i or -1; nbr_in: int32 [volume, n_in], its transpose (the out row that sees in row j
+ * through offset k, or -1) — the dense tables of a pooling kernel map.  For out row i, head h and the offsets k in
+ * ascending order with j = nbr_out[k][i] >= 0:
+ *   s_ik = scale * <q[i, h, :], k[j, h, :]> + rel_pos_bias[h, k]      (rel_pos_bias: fp32 [heads, volume] or NULL = 0)
+ *   out[i, h, :] = sum_k softmax_k(s_ik) v[j, h, :],   lse[i, h] = log sum_k exp(s_ik)   ([n_out, heads] fp32, contiguous)
+ * lse_lo ([n_out, heads] fp32 or NULL): the residual (m + log l) - lse of the fp32 rounding of lse; the backward pass
+ * subtracts it too, so that the weights it recomputes add up to 1 like the forward ones when |lse| is in the hundreds.
+ * A row without a neighbour: a zero output row, lse = -inf, zero gradients.  A hole is never read as a value.  Every
+ * operand carries a row stride in elements: >= c, a multiple of 16 bytes, last dimension contiguous, base pointers 16-byte
+ * aligned (the column slices of one [n, 3 c] projection go in without copies).  fp32 / bf16 entry points: d a power of two
+ * from 8 to 128; scores, softmax and sums in fp32, one rounding at the store.  me_local_attn_backward: dq / dk / dv /
+ * grad_rel_pos_bias (fp32 [heads, volume]) may be NULL (not computed; the dK / dV launch is skipped when both are, the
+ * walk of the dQ launch when neither dq nor the bias gradient is wanted); the workspace
+ * (me_local_attn_workspace_bytes; with_bias: the bias gradient is wanted) holds delta[i, h] = <dout_i, out_i> and the
+ * per-workgroup sums of the bias gradient.  No atomics, fixed summation order: bitwise reproducible.  Host-side argument
+ * errors (nothing launched, reachable with NULL data pointers): c % heads != 0; a head dimension outside the rule; a stride
+ * below c or not a multiple of 16 bytes; a short workspace; a missing table pointer; volume < 1 or > 2^20; out rows
+ * without in rows.  The _f64 entry points: plain double, any head dimension, any stride >= c, lse, bias and its gradient
+ * double, no workspace. */
+int64_t me_local_attn_workspace_bytes(int64_t n_out, int32_t heads, int64_t volume, int32_t with_bias);
+int me_local_attn_forward(const void *q_dev, const void *k_dev, const void *v_dev, int32_t is_bf16, int64_t q_stride,
+                          int64_t k_stride, int64_t v_stride, const int32_t *nbr_out_dev, int64_t n_out, int64_t n_in,
+                          int64_t volume, int32_t c, int32_t heads, float scale, const float *rel_pos_bias_dev,
+                          void *out_dev, int64_t out_stride, float *lse_dev, float *lse_lo_dev, void *stream);
+int me_local_attn_backward(const void *q_dev, const void *k_dev, const void *v_dev, const void *out_dev,
+                           const float *lse_dev, const float *lse_lo_dev, const void *dout_dev, int32_t is_bf16, int64_t q_stride, int64_t k_stride,
+                           int64_t v_stride, int64_t out_stride, int64_t dout_stride, const int32_t *nbr_out_dev,
+                           const int32_t *nbr_in_dev, int64_t n_out, int64_t n_in, int64_t volume, int32_t c,
+                           int32_t heads, float scale, const float *rel_pos_bias_dev, void *dq_dev, int64_t dq_stride,
+                           void *dk_dev, int64_t dk_stride, void *dv_dev, int64_t dv_stride,
+                           float *grad_rel_pos_bias_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_local_attn_forward_f64(const double *q_dev, const double *k_dev, const double *v_dev, int64_t q_stride,
+                              int64_t k_stride, int64_t v_stride, const int32_t *nbr_out_dev, int64_t n_out, int64_t n_in,
+                              int64_t volume, int32_t c, int32_t heads, double scale, const double *rel_pos_bias_dev,
+                              double *out_dev, int64_t out_stride, double *lse_dev, void *stream);
+int me_local_attn_backward_f64(const double *q_dev, const double *k_dev, const double *v_dev, const double *out_dev,
+                               const double *lse_dev, const double *dout_dev, int64_t q_stride, int64_t k_stride,
+                               int64_t v_stride, int64_t out_stride, int64_t dout_stride, const int32_t *nbr_out_dev,
+                               const int32_t *nbr_in_dev, int64_t n_out, int64_t n_in, int64_t volume, int32_t c,
+                               int32_t heads, double scale, const double *rel_pos_bias_dev, double *dq_dev,
+                               int64_t dq_stride, double *dk_dev, int64_t dk_stride, double *dv_dev, int64_t dv_stride,
+                               double *grad_rel_pos_bias_dev, void *stream);
 
 /* ---- dense <-> sparse conversion (SparseTensor.dense, ME.to_sparse, ME.to_sparse_all, ME.dense_coordinates:
  *      MinkowskiEngine/MinkowskiSparseTensor.py:460-557 and MinkowskiOps.py:246-348, torch indexing there;

@@ -4,7 +4,8 @@ tensor of the input's kind on the input's coordinates (a TensorField stays a Ten
 and return what torch returns.  No kernels of their own, except `group_norm` and `conditional_group_norm`:
 torch's needs one dense tensor per sample, so they run MinkowskiGroupNorm's and MinkowskiConditionalGroupNorm's operators
 (normalization.py, csrc/group_norm.hip); and `scaled_dot_product_attention`, which attends inside every instance on the
-operators of attention.py (csrc/attention.hip)."""
+operators of attention.py (csrc/attention.hip); and `local_attention`, which attends inside a kernel region on the
+operators of local_attention.py (csrc/local_attention.hip)."""
 import torch.nn.functional as F
 
 from .layers import _rewrap
@@ -91,4 +92,37 @@ def scaled_dot_product_attention(query, key, value, num_heads, scale=None):
     return SparseTensor(out, coordinate_map_key=query.coordinate_map_key, coordinate_manager=query._manager)
 
 
-__all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention"]
+def local_attention(query, key, value, num_heads, kernel_size=3, dilation=1, kernel_generator=None, rel_pos_bias=None,
+                    scale=None):
+    """Multi-head attention of every row of `query` over the rows of `key` / `value` inside the kernel region around it
+    (`kernel_size`, `dilation`, or a `kernel_generator`, which RegionType.CUSTOM needs).  `key` and `value` share a
+    coordinate map of `query`'s manager; `query` may sit on that map or on a coarser one (attention pooling): the stride
+    is the ratio of the tensor strides.  rel_pos_bias: (num_heads, kernel volume) or None.  The channels split into
+    `num_heads` heads of 8, 16, 32, 64 or 128 (any size in float64); scale defaults to 1 / sqrt(head size).  No mask, no
+    dropout.  The result sits on `query`'s map."""
+    from .kernel_generator import KernelGenerator
+    from .local_attention import MinkowskiLocalAttentionFunction
+    from .sparse_tensor import SparseTensor
+    for name, t in (("query", query), ("key", key), ("value", value)):
+        if not isinstance(t, SparseTensor):
+            raise TypeError(f"local_attention takes SparseTensors; {name} is a {type(t).__name__}")
+    if key.coordinate_map_key != value.coordinate_map_key or key._manager is not value._manager:
+        raise ValueError("key and value must share a coordinate map")
+    if key._manager is not query._manager:
+        raise ValueError("query and key / value must belong to the same coordinate manager")
+    num_heads = int(num_heads)
+    if num_heads <= 0 or query.F.shape[1] % num_heads != 0:
+        raise ValueError(f"the channel count {query.F.shape[1]} must be a multiple of num_heads {num_heads}")
+    if kernel_generator is None:
+        ts_q, ts_kv = query.tensor_stride, key.tensor_stride
+        if any(a % b != 0 for a, b in zip(ts_q, ts_kv)):
+            raise ValueError(f"the tensor stride of query {ts_q} must be a multiple of that of key / value {ts_kv}")
+        kernel_generator = KernelGenerator(kernel_size=kernel_size, stride=[a // b for a, b in zip(ts_q, ts_kv)],
+                                           dilation=dilation, dimension=query.D)
+    out = MinkowskiLocalAttentionFunction.apply(query.F, key.F, value.F, rel_pos_bias, num_heads, scale, kernel_generator,
+                                                query.coordinate_map_key, key.coordinate_map_key, query._manager)
+    return SparseTensor(out, coordinate_map_key=query.coordinate_map_key, coordinate_manager=query._manager)
+
+
+__all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention",
+                                                "local_attention"]

@@ -3614,6 +3614,101 @@ def AttentionBackwardGPU(q, k, v, out, lse, grad_out, num_heads, scale, q_key, k
 
 
 # ------------------------------------------------------------------------------------------------
+# local attention over a kernel map (csrc/local_attention.hip; not in the reference): a query row of the out map attends
+# to the key / value rows of the in map inside its kernel region — local pooling whose weights are a softmax.  The
+# kernel map is the pooling one of the manager's cache; the operands may be strided row views.
+# ------------------------------------------------------------------------------------------------
+def _lattn_prepare(q, k, v, rel_pos_bias, num_heads, kernel_size, kernel_stride, kernel_dilation, region_type, offset,
+                   q_key, kv_key, manager):
+    q = _attn_rows("q", q)
+    k = _attn_rows("k", k, q)
+    v = _attn_rows("v", v, q)
+    _check(manager.exists(q_key) and manager.exists(kv_key), "coordinate map not found")
+    _check(q.shape[0] == manager.size(q_key), "Invalid q size", q.shape[0], "!=", manager.size(q_key))
+    _check(k.shape[0] == manager.size(kv_key) and v.shape[0] == k.shape[0], "Invalid k / v size", k.shape[0], v.shape[0],
+           "!=", manager.size(kv_key))
+    heads, c = int(num_heads), int(q.shape[1])
+    _check(heads > 0 and c % heads == 0, "the channel count", c, "must be a multiple of num_heads", heads)
+    km = manager._kernel_map(kv_key, q_key, kernel_size, kernel_stride, kernel_dilation, region_type, offset, False, True)
+    _check(km.n_out == q.shape[0] and km.n_in == k.shape[0], "the kernel map does not match q / k")
+    if rel_pos_bias is not None:
+        _check(rel_pos_bias.is_cuda and tuple(rel_pos_bias.shape) == (heads, km.volume),
+               "rel_pos_bias must be a CUDA tensor of shape (num_heads, kernel volume) =", (heads, km.volume), "not",
+               tuple(rel_pos_bias.shape))
+        rel_pos_bias = rel_pos_bias.detach().to(_inorm_param_dtype(q)).contiguous()
+    return q, k, v, rel_pos_bias, heads, c, km
+
+
+def LocalAttentionForwardGPU(q, k, v, rel_pos_bias, num_heads, scale, kernel_size, kernel_stride, kernel_dilation,
+                             region_type, offset, q_key, kv_key, manager):
+    """-> (out [n_out, C], lse [2, n_out, heads]): out[i, h] = sum_k softmax_k(scale <q[i, h], k[j, h]> + rel_pos_bias[h, k])
+    v[j, h] over the offsets k of the kernel map kv_key -> q_key with a row j = nbr[k, i]; lse[0] = log sum_k exp(.) in
+    fp32 (float64 for float64 features), lse[1] the residual of its rounding (zeros in float64), which the backward pass
+    subtracts too.  A query without a neighbour: a zero row and lse[0] = -inf."""
+    q, k, v, bias, heads, c, km = _lattn_prepare(q, k, v, rel_pos_bias, num_heads, kernel_size, kernel_stride,
+                                                 kernel_dilation, region_type, offset, q_key, kv_key, manager)
+    lib = _lib.load()
+    dev = q.device
+    out = torch.empty((km.n_out, c), dtype=q.dtype, device=dev)
+    lse = (torch.zeros if q.dtype == torch.float64 else torch.empty)((2, km.n_out, heads), dtype=_inorm_param_dtype(q),
+                                                                     device=dev)
+    tbl = km.table("out")
+    with _on(dev):
+        if q.dtype == torch.float64:
+            _lib.check(lib.me_local_attn_forward_f64(
+                _ptr(q), _ptr(k), _ptr(v), _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(tbl), km.n_out, km.n_in,
+                km.volume, c, heads, float(scale), _ptr(bias), _ptr(out), c, _ptr(lse), _stream(dev)))
+        else:
+            bf = 1 if q.dtype == torch.bfloat16 else 0
+            _timed("local_attn_forward", dev, lambda: _lib.check(lib.me_local_attn_forward(
+                _ptr(q), _ptr(k), _ptr(v), bf, _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(tbl), km.n_out,
+                km.n_in, km.volume, c, heads, float(scale), _ptr(bias), _ptr(out), c, _ptr(lse), _ptr(lse[1]), _stream(dev))))
+    return out, lse
+
+
+def LocalAttentionBackwardGPU(q, k, v, rel_pos_bias, out, lse, grad_out, num_heads, scale, kernel_size, kernel_stride,
+                              kernel_dilation, region_type, offset, q_key, kv_key, manager, need_grad_q=True,
+                              need_grad_k=True, need_grad_v=True, need_grad_bias=True):
+    """-> (grad_q | None, grad_k | None, grad_v | None, grad_rel_pos_bias | None) from out and lse of the forward pass; the
+    bias gradient is fp32 (float64 for float64 features).  A gradient that is not requested is not computed."""
+    q, k, v, bias, heads, c, km = _lattn_prepare(q, k, v, rel_pos_bias, num_heads, kernel_size, kernel_stride,
+                                                 kernel_dilation, region_type, offset, q_key, kv_key, manager)
+    out = _attn_rows("out", out, q)
+    grad_out = _attn_rows("grad_out", grad_out.to(q.dtype))
+    _check(tuple(out.shape) == tuple(q.shape) and tuple(grad_out.shape) == tuple(q.shape),
+           "out and grad_out must have the shape of q")
+    _check(lse.is_cuda and lse.is_contiguous() and lse.dtype == _inorm_param_dtype(q) and
+           tuple(lse.shape) == (2, q.shape[0], heads), "lse must be the contiguous [2, n_out, heads] statistics of the forward pass")
+    need_grad_bias = bool(need_grad_bias) and bias is not None
+    if not (need_grad_q or need_grad_k or need_grad_v or need_grad_bias):
+        return None, None, None, None
+    lib = _lib.load()
+    dev = q.device
+    grad_q = torch.empty((km.n_out, c), dtype=q.dtype, device=dev) if need_grad_q else None
+    grad_k = torch.empty((km.n_in, c), dtype=q.dtype, device=dev) if need_grad_k else None
+    grad_v = torch.empty((km.n_in, c), dtype=q.dtype, device=dev) if need_grad_v else None
+    grad_bias = torch.empty((heads, km.volume), dtype=_inorm_param_dtype(q), device=dev) if need_grad_bias else None
+    tbl_out, tbl_in = km.table("out"), km.table("in")
+    with _on(dev):
+        if q.dtype == torch.float64:
+            _lib.check(lib.me_local_attn_backward_f64(
+                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), _attn_stride(q), _attn_stride(k),
+                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(tbl_out), _ptr(tbl_in), km.n_out, km.n_in,
+                km.volume, c, heads, float(scale), _ptr(bias), _ptr(grad_q), c, _ptr(grad_k), c, _ptr(grad_v), c,
+                _ptr(grad_bias), _stream(dev)))
+        else:
+            bf = 1 if q.dtype == torch.bfloat16 else 0
+            ws = _workspace(int(lib.me_local_attn_workspace_bytes(km.n_out, heads, km.volume, 1 if need_grad_bias else 0)),
+                            dev)
+            _timed("local_attn_backward", dev, lambda: _lib.check(lib.me_local_attn_backward(
+                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(lse[1]), _ptr(grad_out), bf, _attn_stride(q),
+                _attn_stride(k), _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(tbl_out), _ptr(tbl_in), km.n_out, km.n_in,
+                km.volume, c, heads, float(scale), _ptr(bias), _ptr(grad_q), c, _ptr(grad_k), c, _ptr(grad_v), c,
+                _ptr(grad_bias), _ptr(ws), ws.numel(), _stream(dev))))
+    return grad_q, grad_k, grad_v, grad_bias
+
+
+# ------------------------------------------------------------------------------------------------
 # pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu)
 # ------------------------------------------------------------------------------------------------
 def PruningForwardGPU(in_feat, keep, in_key, out_key, manager):

@@ -646,6 +646,46 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("grad_out"),
         py::arg("num_heads"), py::arg("scale"), py::arg("q_key"), py::arg("kv_key"), py::arg("glob_key"),
         py::arg("manager"), py::arg("need_grad_q") = true, py::arg("need_grad_k") = true, py::arg("need_grad_v") = true);
+  // local attention over a kernel map on the kernels of csrc/local_attention.hip (strided row views go in without copies)
+  m.def("LocalAttentionForwardGPU",
+        [](const Tensor &q, const Tensor &k, const Tensor &v, const py::object &rel_pos_bias, int64_t num_heads,
+           double scale, const ivec &ks, const ivec &st, const ivec &dl, const py::object &region_type,
+           const py::object &offset, CoordinateMapKey *q_key, CoordinateMapKey *kv_key, CoordinateMapManager *mgr) {
+          const Tensor b = opt_tensor(rel_pos_bias);
+          const int rt = to_int(region_type);
+          const ivec offs = region_offsets(offset, rt, ks);
+          std::pair<Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = local_attention_forward(q, k, v, b, num_heads, scale, ks, st, dl, rt, q_key, kv_key, mgr, offs);
+          }
+          return py::make_tuple(r.first, r.second);
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("rel_pos_bias"), py::arg("num_heads"), py::arg("scale"),
+        py::arg("kernel_size"), py::arg("kernel_stride"), py::arg("kernel_dilation"), py::arg("region_type"),
+        py::arg("offset"), py::arg("q_key"), py::arg("kv_key"), py::arg("manager"));
+  m.def("LocalAttentionBackwardGPU",
+        [](const Tensor &q, const Tensor &k, const Tensor &v, const py::object &rel_pos_bias, const Tensor &out,
+           const Tensor &lse, const Tensor &grad_out, int64_t num_heads, double scale, const ivec &ks, const ivec &st,
+           const ivec &dl, const py::object &region_type, const py::object &offset, CoordinateMapKey *q_key,
+           CoordinateMapKey *kv_key, CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k, bool need_grad_v,
+           bool need_grad_bias) {
+          const Tensor b = opt_tensor(rel_pos_bias);
+          const int rt = to_int(region_type);
+          const ivec offs = region_offsets(offset, rt, ks);
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = local_attention_backward(q, k, v, b, out, lse, grad_out, num_heads, scale, ks, st, dl, rt, q_key, kv_key,
+                                         mgr, offs, need_grad_q, need_grad_k, need_grad_v, need_grad_bias);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]), opt_out(r[3]));
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("rel_pos_bias"), py::arg("out"), py::arg("lse"),
+        py::arg("grad_out"), py::arg("num_heads"), py::arg("scale"), py::arg("kernel_size"), py::arg("kernel_stride"),
+        py::arg("kernel_dilation"), py::arg("region_type"), py::arg("offset"), py::arg("q_key"), py::arg("kv_key"),
+        py::arg("manager"), py::arg("need_grad_q") = true, py::arg("need_grad_k") = true, py::arg("need_grad_v") = true,
+        py::arg("need_grad_bias") = true);
   // tensor fields (field.cpp): the reference's InterpolationForwardGPU / InterpolationBackwardGPU and coo_spmm_int32 /
   // coo_spmm_average_int32 (pybind/extern.hpp:497-506), plus the CSR building blocks the autograd functions cache
   m.def("CsrFromCooGPU",

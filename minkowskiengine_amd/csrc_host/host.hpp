@@ -390,6 +390,17 @@ std::vector<Tensor> attention_backward(Tensor q, Tensor k, Tensor v, Tensor out,
                                        int64_t num_heads, double scale, CoordinateMapKey *q_key, CoordinateMapKey *kv_key,
                                        CoordinateMapKey *glob_key, CoordinateMapManager *mgr, bool need_grad_q,
                                        bool need_grad_k, bool need_grad_v);
+// local attention over a kernel map (csrc/local_attention.hip; twin of backend.LocalAttention{Forward,Backward}GPU)
+std::pair<Tensor, Tensor> local_attention_forward(Tensor q, Tensor k, Tensor v, Tensor rel_pos_bias, int64_t num_heads,
+                                                  double scale, const ivec &ks, const ivec &st, const ivec &dl,
+                                                  int region_type, CoordinateMapKey *q_key, CoordinateMapKey *kv_key,
+                                                  CoordinateMapManager *mgr, const ivec &offsets);
+std::vector<Tensor> local_attention_backward(Tensor q, Tensor k, Tensor v, Tensor rel_pos_bias, Tensor out,
+                                             const Tensor &lse, Tensor grad_out, int64_t num_heads, double scale,
+                                             const ivec &ks, const ivec &st, const ivec &dl, int region_type,
+                                             CoordinateMapKey *q_key, CoordinateMapKey *kv_key, CoordinateMapManager *mgr,
+                                             const ivec &offsets, bool need_grad_q, bool need_grad_k, bool need_grad_v,
+                                             bool need_grad_bias);
 // dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU / DensePolicy)
 int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box);
 std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,

@@ -1403,6 +1403,109 @@ std::vector<Tensor> attention_backward(Tensor q, Tensor k, Tensor v, Tensor out,
   return {grad_q, grad_k, grad_v};
 }
 
+// ---- local attention over a kernel map (csrc/local_attention.hip; twin of backend.LocalAttention{Forward,Backward}GPU) ----
+struct LattnPrep {
+  int heads, c;
+  std::shared_ptr<KernelMap> km;
+};
+static LattnPrep lattn_prepare(Tensor &q, Tensor &k, Tensor &v, Tensor &bias, int64_t num_heads, const ivec &ks,
+                               const ivec &st, const ivec &dl, int region_type, CoordinateMapKey *q_key,
+                               CoordinateMapKey *kv_key, CoordinateMapManager *mgr, const ivec &offsets) {
+  q = attn_rows("q", q);
+  k = attn_rows("k", k, &q);
+  v = attn_rows("v", v, &q);
+  const KeyT &qk = q_key->get(), &kk = kv_key->get();
+  check(mgr->exists(qk) && mgr->exists(kk), "coordinate map not found");
+  check(q.size(0) == mgr->get(qk)->n, "Invalid q size");
+  check(k.size(0) == mgr->get(kk)->n && v.size(0) == k.size(0), "Invalid k / v size");
+  const int64_t c = q.size(1);
+  check(num_heads > 0 && c % num_heads == 0, "the channel count " + std::to_string(c) +
+                                                 " must be a multiple of num_heads " + std::to_string(num_heads));
+  LattnPrep p;
+  p.heads = (int)num_heads;
+  p.c = (int)c;
+  p.km = mgr->kernel_map(kk, qk, ks, st, dl, region_type, false, true, offsets);
+  check(p.km->n_out == q.size(0) && p.km->n_in == k.size(0), "the kernel map does not match q / k");
+  if (bias.defined()) {
+    check(bias.is_cuda() && bias.dim() == 2 && bias.size(0) == num_heads && bias.size(1) == p.km->volume,
+          "rel_pos_bias must be a CUDA tensor of shape (num_heads, kernel volume)");
+    bias = bias.detach().to(q.scalar_type() == at::kDouble ? at::kDouble : at::kFloat).contiguous();
+  }
+  return p;
+}
+
+std::pair<Tensor, Tensor> local_attention_forward(Tensor q, Tensor k, Tensor v, Tensor bias, int64_t num_heads,
+                                                  double scale, const ivec &ks, const ivec &st, const ivec &dl,
+                                                  int region_type, CoordinateMapKey *q_key, CoordinateMapKey *kv_key,
+                                                  CoordinateMapManager *mgr, const ivec &offsets) {
+  const LattnPrep p = lattn_prepare(q, k, v, bias, num_heads, ks, st, dl, region_type, q_key, kv_key, mgr, offsets);
+  const c10::Device dev = q.device();
+  const bool f64 = q.scalar_type() == at::kDouble;
+  const int64_t n_out = p.km->n_out, n_in = p.km->n_in, volume = p.km->volume;
+  Tensor out = at::empty({n_out, p.c}, q.options());
+  // lse[0]: the log-sum-exp; lse[1]: the residual of its fp32 rounding (zeros in float64)
+  const auto lse_opts = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  Tensor lse = f64 ? at::zeros({2, n_out, p.heads}, lse_opts) : at::empty({2, n_out, p.heads}, lse_opts);
+  Tensor tbl = p.km->table("out");
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_local_attn_forward_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), attn_stride(q), attn_stride(k),
+                                    attn_stride(v), ptr<int32_t>(tbl), n_out, n_in, volume, p.c, p.heads, scale,
+                                    ptr<double>(bias), ptr<double>(out), p.c, ptr<double>(lse), stream_of(dev)));
+  } else {
+    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+    me_ok(me_local_attn_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), bf, attn_stride(q), attn_stride(k),
+                                attn_stride(v), ptr<int32_t>(tbl), n_out, n_in, volume, p.c, p.heads, (float)scale,
+                                ptr<float>(bias), out.data_ptr(), p.c, ptr<float>(lse),
+                                ptr<float>(lse) + n_out * p.heads, stream_of(dev)));
+  }
+  return {out, lse};
+}
+
+std::vector<Tensor> local_attention_backward(Tensor q, Tensor k, Tensor v, Tensor bias, Tensor out, const Tensor &lse,
+                                             Tensor grad_out, int64_t num_heads, double scale, const ivec &ks,
+                                             const ivec &st, const ivec &dl, int region_type, CoordinateMapKey *q_key,
+                                             CoordinateMapKey *kv_key, CoordinateMapManager *mgr, const ivec &offsets,
+                                             bool need_grad_q, bool need_grad_k, bool need_grad_v, bool need_grad_bias) {
+  const LattnPrep p = lattn_prepare(q, k, v, bias, num_heads, ks, st, dl, region_type, q_key, kv_key, mgr, offsets);
+  out = attn_rows("out", out, &q);
+  grad_out = attn_rows("grad_out", grad_out.to(q.scalar_type()));
+  check(out.sizes() == q.sizes() && grad_out.sizes() == q.sizes(), "out and grad_out must have the shape of q");
+  const c10::Device dev = q.device();
+  const bool f64 = q.scalar_type() == at::kDouble;
+  check(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == (f64 ? at::kDouble : at::kFloat) && lse.dim() == 3 &&
+            lse.size(0) == 2 && lse.size(1) == q.size(0) && lse.size(2) == p.heads,
+        "lse must be the contiguous [2, n_out, heads] statistics of the forward pass");
+  need_grad_bias = need_grad_bias && bias.defined();
+  if (!(need_grad_q || need_grad_k || need_grad_v || need_grad_bias)) return {Tensor(), Tensor(), Tensor(), Tensor()};
+  const int64_t n_out = p.km->n_out, n_in = p.km->n_in, volume = p.km->volume;
+  Tensor grad_q = need_grad_q ? at::empty({n_out, p.c}, q.options()) : Tensor();
+  Tensor grad_k = need_grad_k ? at::empty({n_in, p.c}, q.options()) : Tensor();
+  Tensor grad_v = need_grad_v ? at::empty({n_in, p.c}, q.options()) : Tensor();
+  Tensor grad_bias = need_grad_bias ? at::empty({(int64_t)p.heads, volume},
+                                                at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev))
+                                    : Tensor();
+  Tensor tbl_out = p.km->table("out"), tbl_in = p.km->table("in");
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_local_attn_backward_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), ptr<double>(out), ptr<double>(lse),
+                                     ptr<double>(grad_out), attn_stride(q), attn_stride(k), attn_stride(v),
+                                     attn_stride(out), attn_stride(grad_out), ptr<int32_t>(tbl_out), ptr<int32_t>(tbl_in),
+                                     n_out, n_in, volume, p.c, p.heads, scale, ptr<double>(bias), ptr<double>(grad_q), p.c,
+                                     ptr<double>(grad_k), p.c, ptr<double>(grad_v), p.c, ptr<double>(grad_bias),
+                                     stream_of(dev)));
+  } else {
+    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+    Tensor ws = workspace(me_local_attn_workspace_bytes(n_out, p.heads, volume, need_grad_bias ? 1 : 0), dev);
+    me_ok(me_local_attn_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ptr<float>(lse),
+                                 ptr<float>(lse) + n_out * p.heads, grad_out.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out),
+                                 attn_stride(grad_out), ptr<int32_t>(tbl_out), ptr<int32_t>(tbl_in), n_out, n_in, volume,
+                                 p.c, p.heads, (float)scale, ptr<float>(bias), vptr(grad_q), p.c, vptr(grad_k), p.c,
+                                 vptr(grad_v), p.c, ptr<float>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
+  }
+  return {grad_q, grad_k, grad_v, grad_bias};
+}
+
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------
 Tensor pruning_forward(const Tensor &in_feat, const Tensor &keep, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr) {

@@ -165,8 +165,9 @@ def test_halo_conv_channel_chunks_agree(device, halo, kc):
 
 def test_halo_conv_overflowing_halo_takes_the_direct_path(device, halo):
     """a map whose tiles touch more source rows than the LDS image holds (dilation 3 on a dense cloud, row-ordered
-    target tiles): the kernel's direct-gather path — same sums in the same order, so the same bits as the staged path
-    of a geometry that fits"""
+    target tiles): the kernel's direct-gather path — the same products, but every offset summed in a fresh accumulator
+    that is then added to the tile's, where the staged path keeps one accumulator over all offsets: the same bits as the
+    staged path only on data whose fp32 sums are exact (tests/test_gpu_halo_kernel.py), the oracle's tolerance here"""
     from minkowskiengine_amd import backend as MEB
     coords = make_cloud(6000, 20, 3, seed=2)
     halo(1, 64, 0, 1)

@@ -103,7 +103,11 @@ typedef struct me_region {
  *   1.18 (280)  round 18: local attention over a kernel map: every out row attends to the in rows of its kernel region,
  *              with an optional per-head, per-offset bias; gather kernels on the neighbour tables, no atomics
  *              (me_local_attn_workspace_bytes, me_local_attn_forward, me_local_attn_backward and the _f64 twins
- *              me_local_attn_forward_f64, me_local_attn_backward_f64) */
+ *              me_local_attn_forward_f64, me_local_attn_backward_f64)
+ *   1.19 (290)  round 19: serialized patch attention: z-order / Hilbert keys, patch row lists with a block table, and the
+ *              attention kernels reading their block from that table instead of walking seg_ptr (me_coords_serial_keys,
+ *              me_attn_patch_lists_workspace_bytes, me_attn_patch_lists, me_attn_forward_tab, me_attn_backward_tab and
+ *              the _f64 twins me_attn_forward_tab_f64, me_attn_backward_tab_f64) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1246,6 +1250,73 @@ int me_local_attn_backward_f64(const double *q_dev, const double *k_dev, const d
                                int32_t heads, double scale, const double *rel_pos_bias_dev, double *dq_dev,
                                int64_t dq_stride, double *dk_dev, int64_t dk_stride, double *dv_dev, int64_t dv_stride,
                                double *grad_rel_pos_bias_dev, void *stream);
+
+/* ---- serialized patch attention (MinkowskiSerializedSelfAttention, MinkowskiFunctional.serialized_attention;
+ *      csrc/serial_attention.hip and csrc/attention.hip, ABI 1.19) ----
+ * The rows of every instance are ordered along a space-filling curve, cut into patches of at most patch_size rows, and
+ * the kernels of me_attn_forward / me_attn_backward attend inside every patch: a patch is a segment of their row lists.
+ *
+ * me_coords_serial_keys: keys[i] = ((uint32) coords[i, 0] << D * depth) | code(x), D = ncol - 1,
+ *   x_a = (coords[i, 1 + a] - bbox_min[a]) / tensor_stride[a] (exact on a map of that stride; x_a < 2^depth, so depth is
+ *   the bit count of the largest x_a of the map; tensor_stride and bbox_min: D host ints).  order:
+ *     0  z              bit l of axis a at code bit l * D + (D - 1 - a): axis 0 is the most significant of a level
+ *     2  hilbert        Skilling's AxesToTranspose (Programming the Hilbert curve, 2004) on x with depth bits, the
+ *                       transposed axes interleaved by the rule of z
+ *     1, 3  z_trans, hilbert_trans: the same codes with the spatial axes 0 and 1 exchanged beforehand (D >= 2)
+ *   Host-side error, nothing launched: D * depth > 63.
+ *
+ * me_attn_patch_lists: keys, the library's stable radix sort over the significant key bytes, and for an instance of n_b
+ * rows m_b = ceil(n_b / patch_size) patches, the row of serial rank r going to patch floor(r * m_b / n_b) (64-bit): sizes
+ * differ by at most one, none exceeds patch_size, no row is shared.  Outputs, with S = ceil(n / patch_size) + n_batch
+ * segments (an upper bound of the patch count; surplus segments are empty):
+ *   row_patch int32 [n]       the global patch of every row: patches are numbered by ascending batch index, then rank
+ *   seg_ptr   int32 [S + 1], seg_rows int32 [n]   me_csr_from_coo of row_patch: rows ascending inside a patch
+ *   blk_tab   int32 [2 * (ceil(n / 64) + S)]      for every 64-row block of every non-empty segment, in segment order,
+ *                                                (segment, first row in the segment); unused entries hold segment -1
+ * n_batch: the number of instances (at least the number of distinct batch indices); batch_max: the largest batch index
+ * (batch indices are >= 0).  No synchronisation, no read-back.  Host-side errors, nothing launched: patch_size < 1, an
+ * unknown order, D * depth + bits(max(batch_max, n_batch)) > 63, a short workspace.
+ *
+ * me_attn_forward_tab / me_attn_backward_tab (and _f64): me_attn_forward / me_attn_backward with n_batch read as the
+ * number of segments of any row lists, plus one optional block table per side (NULL: the workgroups walk seg_ptr, which
+ * is what me_attn_forward / me_attn_backward do).  A table belongs to its row lists and has ceil(n_side / 64) + n_batch
+ * pairs in the layout above; the q-side table is read by the forward and the dQ kernels, the kv-side table by the dK / dV
+ * kernel, and the float64 twins accept and ignore both.  Lists and table are generic: any partition of the rows into
+ * segments (patches here, windows elsewhere) is attended the same way.  Same arguments, errors and results otherwise. */
+int me_coords_serial_keys(const int32_t *coords_dev, int64_t n, int32_t ncol, const int32_t *tensor_stride,
+                          const int32_t *bbox_min, int32_t depth, int32_t order, uint64_t *keys_dev, void *stream);
+int64_t me_attn_patch_lists_workspace_bytes(int64_t n, int32_t n_batch, int64_t patch_size);
+int me_attn_patch_lists(const int32_t *coords_dev, int64_t n, int32_t ncol, const int32_t *tensor_stride,
+                        const int32_t *bbox_min, int32_t depth, int32_t batch_max, int32_t order, int32_t n_batch,
+                        int64_t patch_size, int32_t *seg_ptr_dev, int32_t *seg_rows_dev, int32_t *blk_tab_dev,
+                        int32_t *row_patch_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_attn_forward_tab(const void *q_dev, const void *k_dev, const void *v_dev, int32_t is_bf16, int64_t q_stride,
+                        int64_t k_stride, int64_t v_stride, const int32_t *seg_ptr_q_dev, const int32_t *seg_rows_q_dev,
+                        const int32_t *seg_ptr_kv_dev, const int32_t *seg_rows_kv_dev, const int32_t *blk_tab_q_dev,
+                        const int32_t *blk_tab_kv_dev, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c,
+                        int32_t heads, float scale, void *out_dev, int64_t out_stride, float *lse_dev, void *stream);
+int me_attn_backward_tab(const void *q_dev, const void *k_dev, const void *v_dev, const void *out_dev,
+                         const float *lse_dev, const void *dout_dev, int32_t is_bf16, int64_t q_stride, int64_t k_stride,
+                         int64_t v_stride, int64_t out_stride, int64_t dout_stride, const int32_t *seg_ptr_q_dev,
+                         const int32_t *seg_rows_q_dev, const int32_t *seg_ptr_kv_dev, const int32_t *seg_rows_kv_dev,
+                         const int32_t *blk_tab_q_dev, const int32_t *blk_tab_kv_dev, int64_t n_q, int64_t n_kv,
+                         int32_t n_batch, int32_t c, int32_t heads, float scale, void *dq_dev, int64_t dq_stride,
+                         void *dk_dev, int64_t dk_stride, void *dv_dev, int64_t dv_stride, void *workspace_dev,
+                         int64_t workspace_bytes, void *stream);
+int me_attn_forward_tab_f64(const double *q_dev, const double *k_dev, const double *v_dev, int64_t q_stride,
+                            int64_t k_stride, int64_t v_stride, const int32_t *seg_ptr_q_dev,
+                            const int32_t *seg_rows_q_dev, const int32_t *seg_ptr_kv_dev, const int32_t *seg_rows_kv_dev,
+                            const int32_t *blk_tab_q_dev, const int32_t *blk_tab_kv_dev, int64_t n_q, int64_t n_kv,
+                            int32_t n_batch, int32_t c, int32_t heads, double scale, double *out_dev, int64_t out_stride,
+                            double *lse_dev, void *stream);
+int me_attn_backward_tab_f64(const double *q_dev, const double *k_dev, const double *v_dev, const double *out_dev,
+                             const double *lse_dev, const double *dout_dev, int64_t q_stride, int64_t k_stride,
+                             int64_t v_stride, int64_t out_stride, int64_t dout_stride, const int32_t *seg_ptr_q_dev,
+                             const int32_t *seg_rows_q_dev, const int32_t *seg_ptr_kv_dev,
+                             const int32_t *seg_rows_kv_dev, const int32_t *blk_tab_q_dev, const int32_t *blk_tab_kv_dev,
+                             int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads, double scale,
+                             double *dq_dev, int64_t dq_stride, double *dk_dev, int64_t dk_stride, double *dv_dev,
+                             int64_t dv_stride, void *stream);
 
 /* ---- dense <-> sparse conversion (SparseTensor.dense, ME.to_sparse, ME.to_sparse_all, ME.dense_coordinates:
  *      MinkowskiEngine/MinkowskiSparseTensor.py:460-557 and MinkowskiOps.py:246-348, torch indexing there;

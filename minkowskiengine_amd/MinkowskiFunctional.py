@@ -5,7 +5,8 @@ and return what torch returns.  No kernels of their own, except `grou
 torch's needs one dense tensor per sample, so they run MinkowskiGroupNorm's and MinkowskiConditionalGroupNorm's operators
 (normalization.py, csrc/group_norm.hip); and `scaled_dot_product_attention`, which attends inside every instance on the
 operators of attention.py (csrc/attention.hip); and `local_attention`, which attends inside a kernel region on the
-operators of local_attention.py (csrc/local_attention.hip)."""
+operators of local_attention.py (csrc/local_attention.hip); and `serialized_attention`, which attends inside the patches
+of a space-filling curve on the operators of serialized_attention.py (csrc/serial_attention.hip)."""
 import torch.nn.functional as F
 
 from .layers import _rewrap
@@ -124,5 +125,23 @@ def local_attention(query, key, value, num_heads, kernel_size=3, dilation=1, ker
     return SparseTensor(out, coordinate_map_key=query.coordinate_map_key, coordinate_manager=query._manager)
 
 
+def serialized_attention(query, key, value, num_heads, patch_size, order="z", scale=None):
+    """Multi-head attention inside patches of at most `patch_size` rows along the space-filling curve `order` ("z",
+    "z_trans", "hilbert", "hilbert_trans") of every instance (MinkowskiSerializedSelfAttention without its projections).
+    `query`, `key` and `value` sit on ONE coordinate map; the channels split into `num_heads` heads of 32, 64 or 128 (any
+    size in float64); scale defaults to 1 / sqrt(head size).  No mask, no dropout.  The result sits on that map."""
+    from .serialized_attention import MinkowskiSerializedAttentionFunction
+    from .sparse_tensor import SparseTensor
+    for name, t in (("query", query), ("key", key), ("value", value)):
+        if not isinstance(t, SparseTensor):
+            raise TypeError(f"serialized_attention takes SparseTensors; {name} is a {type(t).__name__}")
+    for name, t in (("key", key), ("value", value)):
+        if t.coordinate_map_key != query.coordinate_map_key or t._manager is not query._manager:
+            raise ValueError(f"query, key and value must share one coordinate map; {name} sits on another")
+    out = MinkowskiSerializedAttentionFunction.apply(query.F, key.F, value.F, num_heads, scale, patch_size, order,
+                                                     query.coordinate_map_key, query._manager)
+    return SparseTensor(out, coordinate_map_key=query.coordinate_map_key, coordinate_manager=query._manager)
+
+
 __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention",
-                                                "local_attention"]
+                                                "local_attention", "serialized_attention"]

@@ -24,6 +24,8 @@ from .normalization import (  # noqa: F401
     MinkowskiConditionalGroupNorm, MinkowskiConditionalGroupNormFunction, MinkowskiGroupNorm, MinkowskiGroupNormFunction,
     MinkowskiInstanceNorm, MinkowskiInstanceNormFunction, MinkowskiStableInstanceNorm)
 from .attention import MinkowskiAttentionFunction, MinkowskiSelfAttention  # noqa: F401
+from .serialized_attention import (  # noqa: F401
+    MinkowskiSerializedAttentionFunction, MinkowskiSerializedSelfAttention)
 from .local_attention import MinkowskiLocalAttentionFunction, MinkowskiLocalSelfAttention  # noqa: F401
 from .pruning import MinkowskiPruning, MinkowskiPruningFunction  # noqa: F401
 from .tensor_field import TensorField, create_splat_coordinates  # noqa: F401

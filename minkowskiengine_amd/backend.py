@@ -754,6 +754,7 @@ class CoordinateMapManagerGPU_c10:
         self._kernel_maps = {}   # kernel_map_key (src/types.hpp:183-192) -> KernelMapGPU
         self._origin_maps = {}
         self._instance_rows_cache = {}
+        self._patch_rows_cache = {}     # (map key, patch size, order code) -> (seg_ptr, seg_rows, blk_tab, row_patch)
         self._prune_rows = {}
         self._union_arith = {}   # (key a, key b), ordered -> (union key, u_of_a, u_of_b, a_of_u, b_of_u): union_arith_maps
         self._stride_maps = {}
@@ -1276,6 +1277,48 @@ class CoordinateMapManagerGPU_c10:
             lists = self._instance_rows_cache[ik] = (seg_ptr, seg_rows)
         return lists
 
+    def _patch_rows(self, in_key, patch_size, order):
+        """(seg_ptr int32 [S + 1], seg_rows int32 [n], blk_tab int32 [2 (ceil(n / 64) + S)], row_patch int32 [n]) of
+        serialized patch attention: the rows of every instance along the curve `order` ("z", "z_trans", "hilbert",
+        "hilbert_trans"), cut into patches of at most `patch_size` rows (me_attn_patch_lists, csrc/serial_attention.hip);
+        S = ceil(n / patch_size) + n_batch.  Cached per (map, patch size, order).  The key geometry comes from the
+        bounding box an inserted map carries; a derived map takes one reduction and one read-back here."""
+        ik = self._k(in_key)
+        code, patch = serial_order_code(order), int(patch_size)
+        _check(patch >= 1, "patch_size must be at least 1, got", patch_size)
+        ck = (ik, patch, code)
+        lists = self._patch_rows_cache.get(ck)
+        if lists is None:
+            self._origin_rows(in_key)                   # (checks once that the origin map knows every batch index)
+            m = self._get(ik)
+            n, ncol = int(m.n), int(m.coords.shape[1])
+            n_batch = self.size(self.origin())
+            bbox = m.bbox
+            if n > 0 and (bbox is None or len(bbox) != 2 * ncol):
+                bbox = torch.cat((m.coords.amin(0), m.coords.amax(0))).tolist()
+            ts = [int(t) for t in m.tensor_stride]
+            lo = [int(bbox[1 + a]) if n > 0 else 0 for a in range(ncol - 1)]
+            depth = max([((int(bbox[ncol + 1 + a]) - lo[a]) // ts[a]).bit_length() for a in range(ncol - 1)]) if n > 0 else 0
+            batch_max = int(bbox[ncol]) if n > 0 else 0
+            _check(n == 0 or int(bbox[0]) >= 0, "batch indices must not be negative")
+            _check((ncol - 1) * depth + max(batch_max, n_batch).bit_length() <= 63, "the serialisation key of this map needs",
+                   (ncol - 1) * depth, "code bits and", max(batch_max, n_batch).bit_length(), "batch bits: more than 63")
+            lib = _lib.load()
+            dev = m.coords.device
+            n_seg = -(-n // patch) + n_batch
+            seg_ptr = torch.empty(n_seg + 1, dtype=torch.int32, device=dev)
+            seg_rows = torch.empty(n, dtype=torch.int32, device=dev)
+            blk_tab = torch.empty(2 * (-(-n // 64) + n_seg), dtype=torch.int32, device=dev)
+            row_patch = torch.empty(n, dtype=torch.int32, device=dev)
+            ws = _workspace(int(lib.me_attn_patch_lists_workspace_bytes(n, n_batch, patch)), dev)
+            c_ts, c_lo = (ctypes.c_int32 * (ncol - 1))(*ts), (ctypes.c_int32 * (ncol - 1))(*lo)
+            with _on(dev):
+                _lib.check(lib.me_attn_patch_lists(_ptr(m.coords), n, ncol, c_ts, c_lo, depth, batch_max, code, n_batch,
+                                                   patch, _ptr(seg_ptr), _ptr(seg_rows), _ptr(blk_tab), _ptr(row_patch),
+                                                   _ptr(ws), ws.numel(), _stream(dev)))
+            lists = self._patch_rows_cache[ck] = (seg_ptr, seg_rows, blk_tab, row_patch)
+        return lists
+
     def origin_map(self, in_key):
         """{0: int32 [2, n_in]} (row 0 = in rows, row 1 = origin rows), the reference's origin_map_th layout."""
         rows = self._origin_rows(in_key)
@@ -1370,7 +1413,7 @@ class CoordinateMapManagerGPU_c10:
                 for name in names:
                     if name not in ("_recipe", "in_map", "out_map"):
                         walk(getattr(o, name, None), depth + 1)
-        for store in (self._maps, self._kernel_maps, self._origin_maps, self._instance_rows_cache,
+        for store in (self._maps, self._kernel_maps, self._origin_maps, self._instance_rows_cache, self._patch_rows_cache,
                       self._origin_field_maps, self._prune_rows,
                       self._stride_maps, self._union_arith):
             walk(store)
@@ -3706,6 +3749,97 @@ def LocalAttentionBackwardGPU(q, k, v, rel_pos_bias, out, lse, grad_out, num_hea
                 km.volume, c, heads, float(scale), _ptr(bias), _ptr(grad_q), c, _ptr(grad_k), c, _ptr(grad_v), c,
                 _ptr(grad_bias), _ptr(ws), ws.numel(), _stream(dev))))
     return grad_q, grad_k, grad_v, grad_bias
+
+
+# ------------------------------------------------------------------------------------------------
+# serialized patch attention (csrc/serial_attention.hip + the _tab entry points of csrc/attention.hip; not in the
+# reference): the rows of every instance along a space-filling curve, cut into patches; a row attends inside its patch.
+# q, k, v sit on ONE map; the lists and the block table come from manager._patch_rows.
+# ------------------------------------------------------------------------------------------------
+SERIAL_ORDERS = ("z", "z_trans", "hilbert", "hilbert_trans")   # the order codes of me_coords_serial_keys
+
+
+def serial_order_code(order):
+    if order not in SERIAL_ORDERS:
+        raise ValueError(f"order must be one of {SERIAL_ORDERS}, not {order!r}")
+    return SERIAL_ORDERS.index(order)
+
+
+def _serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, manager):
+    q = _attn_rows("q", q)
+    k = _attn_rows("k", k, q)
+    v = _attn_rows("v", v, q)
+    _check(manager.exists(in_key), "coordinate map not found")
+    n = manager.size(in_key)
+    _check(q.shape[0] == n and k.shape[0] == n and v.shape[0] == n, "Invalid q / k / v size", q.shape[0], k.shape[0],
+           v.shape[0], "!=", n)
+    heads, c = int(num_heads), int(q.shape[1])
+    _check(heads > 0 and c % heads == 0, "the channel count", c, "must be a multiple of num_heads", heads)
+    seg_ptr, seg_rows, blk_tab, _ = manager._patch_rows(in_key, patch_size, order)
+    return q, k, v, heads, c, seg_ptr, seg_rows, blk_tab, int(seg_ptr.numel()) - 1
+
+
+def SerializedAttentionForwardGPU(q, k, v, num_heads, scale, patch_size, order, in_key, manager):
+    """-> (out [n, C], lse [n, heads]): out[i, h] = sum_j softmax_j(scale <q[i, h], k[j, h]>) v[j, h] over the rows j of the
+    patch of row i (manager._patch_rows(in_key, patch_size, order)); lse in fp32 (float64 for float64 features)."""
+    q, k, v, heads, c, seg_ptr, seg_rows, blk_tab, n_seg = _serial_attn_prepare(q, k, v, num_heads, patch_size, order,
+                                                                              in_key, manager)
+    lib = _lib.load()
+    dev = q.device
+    n = int(q.shape[0])
+    out = torch.empty((n, c), dtype=q.dtype, device=dev)
+    lse = torch.empty((n, heads), dtype=_inorm_param_dtype(q), device=dev)
+    with _on(dev):
+        if q.dtype == torch.float64:
+            _lib.check(lib.me_attn_forward_tab_f64(
+                _ptr(q), _ptr(k), _ptr(v), _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(seg_ptr), _ptr(seg_rows),
+                _ptr(seg_ptr), _ptr(seg_rows), _ptr(blk_tab), _ptr(blk_tab), n, n, n_seg, c, heads, float(scale), _ptr(out),
+                c, _ptr(lse), _stream(dev)))
+        else:
+            bf = 1 if q.dtype == torch.bfloat16 else 0
+            _timed("serial_attn_forward", dev, lambda: _lib.check(lib.me_attn_forward_tab(
+                _ptr(q), _ptr(k), _ptr(v), bf, _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(seg_ptr),
+                _ptr(seg_rows), _ptr(seg_ptr), _ptr(seg_rows), _ptr(blk_tab), _ptr(blk_tab), n, n, n_seg, c, heads,
+                float(scale), _ptr(out), c, _ptr(lse), _stream(dev))))
+    return out, lse
+
+
+def SerializedAttentionBackwardGPU(q, k, v, out, lse, grad_out, num_heads, scale, patch_size, order, in_key, manager,
+                                   need_grad_q=True, need_grad_k=True, need_grad_v=True):
+    """-> (grad_q | None, grad_k | None, grad_v | None), contiguous, from out and lse of the forward pass; a gradient that
+    is not requested is not computed (AttentionBackwardGPU's rule)."""
+    q, k, v, heads, c, seg_ptr, seg_rows, blk_tab, n_seg = _serial_attn_prepare(q, k, v, num_heads, patch_size, order,
+                                                                              in_key, manager)
+    out = _attn_rows("out", out, q)
+    grad_out = _attn_rows("grad_out", grad_out.to(q.dtype))
+    _check(tuple(out.shape) == tuple(q.shape) and tuple(grad_out.shape) == tuple(q.shape),
+           "out and grad_out must have the shape of q")
+    _check(lse.is_cuda and lse.is_contiguous() and lse.dtype == _inorm_param_dtype(q) and
+           tuple(lse.shape) == (q.shape[0], heads), "lse must be the contiguous [n, heads] statistics of the forward pass")
+    lib = _lib.load()
+    dev = q.device
+    n = int(q.shape[0])
+    grad_q = torch.empty((n, c), dtype=q.dtype, device=dev) if need_grad_q else None
+    grad_k = torch.empty((n, c), dtype=q.dtype, device=dev) if need_grad_k else None
+    grad_v = torch.empty((n, c), dtype=q.dtype, device=dev) if need_grad_v else None
+    if not (need_grad_q or need_grad_k or need_grad_v):
+        return None, None, None
+    with _on(dev):
+        if q.dtype == torch.float64:
+            _lib.check(lib.me_attn_backward_tab_f64(
+                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), _attn_stride(q), _attn_stride(k),
+                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_ptr), _ptr(seg_rows), _ptr(seg_ptr),
+                _ptr(seg_rows), _ptr(blk_tab), _ptr(blk_tab), n, n, n_seg, c, heads, float(scale), _ptr(grad_q), c,
+                _ptr(grad_k), c, _ptr(grad_v), c, _stream(dev)))
+        else:
+            bf = 1 if q.dtype == torch.bfloat16 else 0
+            ws = _workspace(int(lib.me_attn_workspace_bytes(n, n, n_seg, heads)), dev)
+            _timed("serial_attn_backward", dev, lambda: _lib.check(lib.me_attn_backward_tab(
+                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), bf, _attn_stride(q), _attn_stride(k),
+                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_ptr), _ptr(seg_rows), _ptr(seg_ptr),
+                _ptr(seg_rows), _ptr(blk_tab), _ptr(blk_tab), n, n, n_seg, c, heads, float(scale), _ptr(grad_q), c,
+                _ptr(grad_k), c, _ptr(grad_v), c, _ptr(ws), ws.numel(), _stream(dev))))
+    return grad_q, grad_k, grad_v
 
 
 # ------------------------------------------------------------------------------------------------

@@ -182,6 +182,13 @@ class CoordinateManager:
     def origin_map(self, key):
         return self._manager.origin_map(key)
 
+    def patch_rows(self, key, patch_size, order="z"):
+        """(seg_ptr, seg_rows, blk_tab, row_patch) of serialized patch attention on the map `key`: the rows of every
+        instance along the curve `order` ("z", "z_trans", "hilbert", "hilbert_trans") cut into patches of at most
+        `patch_size` rows.  row_patch int32 [N] is the patch of every row; seg_rows[seg_ptr[p] : seg_ptr[p + 1]] are the rows
+        of patch p, ascending; blk_tab is the block table of the attention kernels.  Cached per (map, size, order)."""
+        return self._manager._patch_rows(key, int(patch_size), order)
+
     def origin_field(self, field_key=None):
         """Key of the origin map (the key origin() returns), built from the batch indices of a field when absent:
         `field_key`, or the oldest field of the manager (MinkowskiCoordinateManager.py:273)."""

@@ -29,6 +29,9 @@
 //
 // Surplus workgroups: the grid holds ceil(n / block) + n_batch blocks per head, an upper bound of the blocks of all
 // instances; a workgroup finds its (instance, block) by walking seg_ptr and exits when there is none.  One launch per kernel.
+// The walk is O(instances) dependent loads: fine for a handful of scenes, not for the thousands of patches of serialized
+// patch attention (serial_attention.hip), whose lists come with a block table of one (segment, first row) pair per
+// workgroup; the _tab entry points take it and the kernels branch on the pointer at entry (k_attn_delta walks nothing).
 // The float64 twins at the end are the gradcheck yardstick (plain double, one thread per (row, head)).
 #include "common.hpp"
 
@@ -120,9 +123,19 @@ template <typename T> __device__ __forceinline__ float attn_exp(float x) {
   else return expf(x);
 }
 
-// (instance, block) of workgroup `blk`: the blocks of the instances in ascending instance order
-__device__ __forceinline__ bool attn_find_item(const int32_t *__restrict__ seg_ptr, int n_batch, int blk, int height,
-                                               int &b, int &t0, int &start, int &len) {
+// (instance, block) of workgroup `blk`: the blocks of the instances in ascending instance order.  With a block table
+// (int32 pairs (segment, first row in the segment), one per workgroup, segment -1: no block; me_attn_patch_lists) the item
+// is one 8-byte load; without one the workgroup walks seg_ptr.  `tab` is a kernel argument: the branch is wave-uniform.
+__device__ __forceinline__ bool attn_find_item(const int32_t *__restrict__ tab, const int32_t *__restrict__ seg_ptr,
+                                               int n_batch, int blk, int height, int &b, int &t0, int &start, int &len) {
+  if (tab != nullptr) {
+    b = tab[2 * blk];
+    if (b < 0) return false;
+    t0 = tab[2 * blk + 1];
+    start = seg_ptr[b];
+    len = seg_ptr[b + 1] - start;
+    return true;
+  }
   int acc = 0;
   for (b = 0; b < n_batch; ++b) {
     start = seg_ptr[b];
@@ -193,15 +206,16 @@ template <typename T, int D>
 __global__ __launch_bounds__(kAttnThreads) void k_attn_fwd(
     const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v, int64_t q_stride, int64_t k_stride,
     int64_t v_stride, const int32_t *__restrict__ seg_ptr_q, const int32_t *__restrict__ seg_rows_q,
-    const int32_t *__restrict__ seg_ptr_kv, const int32_t *__restrict__ seg_rows_kv, int n_batch, int heads, float scale,
-    T *__restrict__ out, int64_t out_stride, float *__restrict__ lse) {
+    const int32_t *__restrict__ seg_ptr_kv, const int32_t *__restrict__ seg_rows_kv,
+    const int32_t *__restrict__ blk_tab, int n_batch, int heads, float scale, T *__restrict__ out, int64_t out_stride,
+    float *__restrict__ lse) {
   constexpr int NC = D / 16, ND = D / 32, W = kAttnFwdWalk;
   constexpr int LDN = D + AttnT<T>::PADN, LDT = W + AttnT<T>::PADT;
   extern __shared__ __attribute__((aligned(16))) unsigned char s_attn[];
   T *s_k = reinterpret_cast<T *>(s_attn);   // [W][LDN]
   T *s_vt = s_k + W * LDN;                  // [D][LDT]
   int b, t0, startq, lenq;
-  if (!attn_find_item(seg_ptr_q, n_batch, blockIdx.x, kAttnBlock, b, t0, startq, lenq)) return;
+  if (!attn_find_item(blk_tab, seg_ptr_q, n_batch, blockIdx.x, kAttnBlock, b, t0, startq, lenq)) return;
   const int head = blockIdx.y;
   const int startk = seg_ptr_kv[b], lenk = seg_ptr_kv[b + 1] - startk;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -302,7 +316,8 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_bwd_q(
     const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v, const T *__restrict__ dout,
     int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t dout_stride, const int32_t *__restrict__ seg_ptr_q,
     const int32_t *__restrict__ seg_rows_q, const int32_t *__restrict__ seg_ptr_kv,
-    const int32_t *__restrict__ seg_rows_kv, int n_batch, int heads, float scale, const float *__restrict__ lse,
+    const int32_t *__restrict__ seg_rows_kv, const int32_t *__restrict__ blk_tab, int n_batch, int heads, float scale,
+    const float *__restrict__ lse,
     const float *__restrict__ delta, T *__restrict__ dq, int64_t dq_stride) {
   constexpr int NC = D / 16, ND = D / 32, W = kAttnBwdWalk;
   constexpr int LDN = D + AttnT<T>::PADN, LDT = W + AttnT<T>::PADT;
@@ -311,7 +326,7 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_bwd_q(
   T *s_v = s_k + W * LDN;                   // [W][LDN]
   T *s_kt = s_v + W * LDN;                  // [D][LDT]
   int b, t0, startq, lenq;
-  if (!attn_find_item(seg_ptr_q, n_batch, blockIdx.x, kAttnBlock, b, t0, startq, lenq)) return;
+  if (!attn_find_item(blk_tab, seg_ptr_q, n_batch, blockIdx.x, kAttnBlock, b, t0, startq, lenq)) return;
   const int head = blockIdx.y;
   const int startk = seg_ptr_kv[b], lenk = seg_ptr_kv[b + 1] - startk;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -371,7 +386,8 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_bwd_kv(
     const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v, const T *__restrict__ dout,
     int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t dout_stride, const int32_t *__restrict__ seg_ptr_q,
     const int32_t *__restrict__ seg_rows_q, const int32_t *__restrict__ seg_ptr_kv,
-    const int32_t *__restrict__ seg_rows_kv, int n_batch, int heads, float scale, const float *__restrict__ lse,
+    const int32_t *__restrict__ seg_rows_kv, const int32_t *__restrict__ blk_tab, int n_batch, int heads, float scale,
+    const float *__restrict__ lse,
     const float *__restrict__ delta, T *__restrict__ dk, int64_t dk_stride, T *__restrict__ dv, int64_t dv_stride) {
   constexpr int NC = D / 16, ND = D / 32, W = kAttnBwdWalk;
   constexpr int LDN = D + AttnT<T>::PADN, LDT = W + AttnT<T>::PADT;
@@ -383,7 +399,7 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_bwd_kv(
   float *s_lse = reinterpret_cast<float *>(s_gt + D * LDT);   // [W]
   float *s_delta = s_lse + W;                                 // [W]
   int b, t0, startk, lenk;
-  if (!attn_find_item(seg_ptr_kv, n_batch, blockIdx.x, kAttnBlock, b, t0, startk, lenk)) return;
+  if (!attn_find_item(blk_tab, seg_ptr_kv, n_batch, blockIdx.x, kAttnBlock, b, t0, startk, lenk)) return;
   const int head = blockIdx.y;
   const int startq = seg_ptr_q[b], lenq = seg_ptr_q[b + 1] - startq;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -472,6 +488,7 @@ struct AttnArgs {
   const void *q, *k, *v, *out, *dout;
   int64_t q_stride, k_stride, v_stride, out_stride, dout_stride, dq_stride, dk_stride, dv_stride;
   const int32_t *seg_ptr_q, *seg_rows_q, *seg_ptr_kv, *seg_rows_kv;
+  const int32_t *tab_q, *tab_kv;   // block tables of the q / kv lists (null: the workgroups walk seg_ptr)
   int64_t n_q, n_kv;
   int n_batch, heads;
   float scale;
@@ -496,7 +513,7 @@ static int attn_forward_t(const AttnArgs &a, hipStream_t stream) {
   ME_ATTN_LDS_ATTR((k_attn_fwd<T, D>), (attn_fwd_lds<T, D>()));
   k_attn_fwd<T, D><<<grid, kAttnThreads, attn_fwd_lds<T, D>(), stream>>>(
       (const T *)a.q, (const T *)a.k, (const T *)a.v, a.q_stride, a.k_stride, a.v_stride, a.seg_ptr_q, a.seg_rows_q,
-      a.seg_ptr_kv, a.seg_rows_kv, a.n_batch, a.heads, a.scale, (T *)a.out_w, a.out_stride, a.lse);
+      a.seg_ptr_kv, a.seg_rows_kv, a.tab_q, a.n_batch, a.heads, a.scale, (T *)a.out_w, a.out_stride, a.lse);
   ME_LAUNCH_CHECK();
   return 0;
 }
@@ -514,8 +531,8 @@ static int attn_backward_t(const AttnArgs &a, hipStream_t stream) {
     ME_ATTN_LDS_ATTR((k_attn_bwd_kv<T, D>), (attn_bwd_kv_lds<T, D>()));
     k_attn_bwd_kv<T, D><<<grid, kAttnThreads, attn_bwd_kv_lds<T, D>(), stream>>>(
         (const T *)a.q, (const T *)a.k, (const T *)a.v, (const T *)a.dout, a.q_stride, a.k_stride, a.v_stride,
-        a.dout_stride, a.seg_ptr_q, a.seg_rows_q, a.seg_ptr_kv, a.seg_rows_kv, a.n_batch, a.heads, a.scale, a.lse, a.delta,
-        (T *)a.dk, a.dk_stride, (T *)a.dv, a.dv_stride);
+        a.dout_stride, a.seg_ptr_q, a.seg_rows_q, a.seg_ptr_kv, a.seg_rows_kv, a.tab_kv, a.n_batch, a.heads, a.scale, a.lse,
+        a.delta, (T *)a.dk, a.dk_stride, (T *)a.dv, a.dv_stride);
     ME_LAUNCH_CHECK();
   }
   if (a.dq) {
@@ -523,8 +540,8 @@ static int attn_backward_t(const AttnArgs &a, hipStream_t stream) {
     ME_ATTN_LDS_ATTR((k_attn_bwd_q<T, D>), (attn_bwd_q_lds<T, D>()));
     k_attn_bwd_q<T, D><<<grid, kAttnThreads, attn_bwd_q_lds<T, D>(), stream>>>(
         (const T *)a.q, (const T *)a.k, (const T *)a.v, (const T *)a.dout, a.q_stride, a.k_stride, a.v_stride,
-        a.dout_stride, a.seg_ptr_q, a.seg_rows_q, a.seg_ptr_kv, a.seg_rows_kv, a.n_batch, a.heads, a.scale, a.lse, a.delta,
-        (T *)a.dq, a.dq_stride);
+        a.dout_stride, a.seg_ptr_q, a.seg_rows_q, a.seg_ptr_kv, a.seg_rows_kv, a.tab_q, a.n_batch, a.heads, a.scale, a.lse,
+        a.delta, (T *)a.dq, a.dq_stride);
     ME_LAUNCH_CHECK();
   }
   return 0;
@@ -691,10 +708,13 @@ int64_t me_attn_workspace_bytes(int64_t n_q, int64_t n_kv, int32_t n_batch, int3
   return align_up((n_q > 0 ? n_q : 0) * (int64_t)(heads > 0 ? heads : 0) * (int64_t)sizeof(float), 256);   // delta [n_q, heads]
 }
 
-int me_attn_forward(const void *q, const void *k, const void *v, int32_t is_bf16, int64_t q_stride, int64_t k_stride,
-                    int64_t v_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q, const int32_t *seg_ptr_kv,
-                    const int32_t *seg_rows_kv, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads,
-                    float scale, void *out, int64_t out_stride, float *lse, void *stream_) {
+// The _tab entry points are the implementation: me_attn_forward / me_attn_backward (below) pass null tables.  A table holds
+// ceil(n / 64) + n_batch int32 pairs (the grid of its side); blk_tab_kv is not read by the forward pass.
+int me_attn_forward_tab(const void *q, const void *k, const void *v, int32_t is_bf16, int64_t q_stride, int64_t k_stride,
+                        int64_t v_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q, const int32_t *seg_ptr_kv,
+                        const int32_t *seg_rows_kv, const int32_t *blk_tab_q, const int32_t *blk_tab_kv, int64_t n_q,
+                        int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads, float scale, void *out,
+                        int64_t out_stride, float *lse, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int unit = is_bf16 ? 8 : 4;
   ME_ATTN_CHECK_DIMS(unit);
@@ -712,17 +732,27 @@ int me_attn_forward(const void *q, const void *k, const void *v, int32_t is_bf16
   a.q = q; a.k = k; a.v = v;
   a.q_stride = q_stride; a.k_stride = k_stride; a.v_stride = v_stride; a.out_stride = out_stride;
   a.seg_ptr_q = seg_ptr_q; a.seg_rows_q = seg_rows_q; a.seg_ptr_kv = seg_ptr_kv; a.seg_rows_kv = seg_rows_kv;
+  a.tab_q = blk_tab_q; a.tab_kv = blk_tab_kv;
   a.n_q = n_q; a.n_kv = n_kv; a.n_batch = n_batch; a.heads = heads; a.scale = scale;
   a.out_w = out; a.lse = lse;
   ME_ATTN_DISPATCH(is_bf16, c / heads, attn_forward_t, a, stream);
 }
 
-int me_attn_backward(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout,
-                     int32_t is_bf16, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t out_stride,
-                     int64_t dout_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q, const int32_t *seg_ptr_kv,
-                     const int32_t *seg_rows_kv, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads,
-                     float scale, void *dq, int64_t dq_stride, void *dk, int64_t dk_stride, void *dv, int64_t dv_stride,
-                     void *workspace, int64_t workspace_bytes, void *stream_) {
+int me_attn_forward(const void *q, const void *k, const void *v, int32_t is_bf16, int64_t q_stride, int64_t k_stride,
+                    int64_t v_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q, const int32_t *seg_ptr_kv,
+                    const int32_t *seg_rows_kv, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads,
+                    float scale, void *out, int64_t out_stride, float *lse, void *stream_) {
+  return me_attn_forward_tab(q, k, v, is_bf16, q_stride, k_stride, v_stride, seg_ptr_q, seg_rows_q, seg_ptr_kv, seg_rows_kv,
+                             nullptr, nullptr, n_q, n_kv, n_batch, c, heads, scale, out, out_stride, lse, stream_);
+}
+
+int me_attn_backward_tab(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout,
+                         int32_t is_bf16, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t out_stride,
+                         int64_t dout_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q,
+                         const int32_t *seg_ptr_kv, const int32_t *seg_rows_kv, const int32_t *blk_tab_q,
+                         const int32_t *blk_tab_kv, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads,
+                         float scale, void *dq, int64_t dq_stride, void *dk, int64_t dk_stride, void *dv,
+                         int64_t dv_stride, void *workspace, int64_t workspace_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int unit = is_bf16 ? 8 : 4;
   ME_ATTN_CHECK_DIMS(unit);
@@ -759,7 +789,19 @@ int me_attn_backward(const void *q, const void *k, const void *v, const void *ou
   a.dq = dq; a.dk = dk; a.dv = dv;
   a.lse = const_cast<float *>(lse);
   a.delta = reinterpret_cast<float *>(workspace);
+  a.tab_q = blk_tab_q; a.tab_kv = blk_tab_kv;
   ME_ATTN_DISPATCH(is_bf16, c / heads, attn_backward_t, a, stream);
+}
+
+int me_attn_backward(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout,
+                     int32_t is_bf16, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t out_stride,
+                     int64_t dout_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q, const int32_t *seg_ptr_kv,
+                     const int32_t *seg_rows_kv, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads,
+                     float scale, void *dq, int64_t dq_stride, void *dk, int64_t dk_stride, void *dv, int64_t dv_stride,
+                     void *workspace, int64_t workspace_bytes, void *stream_) {
+  return me_attn_backward_tab(q, k, v, out, lse, dout, is_bf16, q_stride, k_stride, v_stride, out_stride, dout_stride,
+                              seg_ptr_q, seg_rows_q, seg_ptr_kv, seg_rows_kv, nullptr, nullptr, n_q, n_kv, n_batch, c, heads,
+                              scale, dq, dq_stride, dk, dk_stride, dv, dv_stride, workspace, workspace_bytes, stream_);
 }
 
 int me_attn_forward_f64(const double *q, const double *k, const double *v, int64_t q_stride, int64_t k_stride,
@@ -817,6 +859,32 @@ int me_attn_backward_f64(const double *q, const double *k, const double *v, cons
     ME_LAUNCH_CHECK();
   }
   return 0;
+}
+
+// The float64 twins take the tables for a uniform call and do not read them: a thread finds its segment from seg_ptr.
+int me_attn_forward_tab_f64(const double *q, const double *k, const double *v, int64_t q_stride, int64_t k_stride,
+                            int64_t v_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q,
+                            const int32_t *seg_ptr_kv, const int32_t *seg_rows_kv, const int32_t *blk_tab_q,
+                            const int32_t *blk_tab_kv, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c,
+                            int32_t heads, double scale, double *out, int64_t out_stride, double *lse, void *stream_) {
+  (void)blk_tab_q;
+  (void)blk_tab_kv;
+  return me_attn_forward_f64(q, k, v, q_stride, k_stride, v_stride, seg_ptr_q, seg_rows_q, seg_ptr_kv, seg_rows_kv, n_q,
+                             n_kv, n_batch, c, heads, scale, out, out_stride, lse, stream_);
+}
+
+int me_attn_backward_tab_f64(const double *q, const double *k, const double *v, const double *out, const double *lse,
+                             const double *dout, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t out_stride,
+                             int64_t dout_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q,
+                             const int32_t *seg_ptr_kv, const int32_t *seg_rows_kv, const int32_t *blk_tab_q,
+                             const int32_t *blk_tab_kv, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c,
+                             int32_t heads, double scale, double *dq, int64_t dq_stride, double *dk, int64_t dk_stride,
+                             double *dv, int64_t dv_stride, void *stream_) {
+  (void)blk_tab_q;
+  (void)blk_tab_kv;
+  return me_attn_backward_f64(q, k, v, out, lse, dout, q_stride, k_stride, v_stride, out_stride, dout_stride, seg_ptr_q,
+                              seg_rows_q, seg_ptr_kv, seg_rows_kv, n_q, n_kv, n_batch, c, heads, scale, dq, dq_stride, dk,
+                              dk_stride, dv, dv_stride, stream_);
 }
 
 }  // extern "C"

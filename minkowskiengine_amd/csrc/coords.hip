@@ -1385,6 +1385,42 @@ int radix_argsort_u32(const uint32_t *keys, int64_t n, int bits, uint32_t *sorte
   return 0;
 }
 
+// Stable argsort of uint64 keys by the 8-bit digits at `shifts` (ascending significance, np >= 1 of them: the bytes that
+// can differ), for serial_attention.hip: order[i] = position of the i-th smallest key; *sorted_keys = the buffer (keys or
+// keys_tmp, both [n], both overwritten) that holds the keys in that order.  Workspace: radix_argsort_u64_workspace_bytes(n).
+int64_t radix_argsort_u64_workspace_bytes(int64_t n) {
+  const int64_t m = n < 1 ? 1 : n, nb = ceil_div(m, kRsTile);
+  return align_up(m * 4, 256) + align_up(256 * nb * 4, 256) + 256 + scan_workspace_bytes(256 * nb);
+}
+int radix_argsort_u64(uint64_t *keys, uint64_t *keys_tmp, int64_t n, const int *shifts, int np, uint32_t *order,
+                      uint64_t **sorted_keys, void *ws, int64_t ws_bytes, hipStream_t stream) {
+  ME_CHECK(np >= 1 && ws_bytes >= radix_argsort_u64_workspace_bytes(n), "passes / workspace");
+  *sorted_keys = keys;
+  if (n <= 0) return 0;
+  const int64_t nb = ceil_div(n, kRsTile), vsz = align_up(n * 4, 256);
+  char *p = reinterpret_cast<char *>(ws);
+  uint32_t *vbuf = reinterpret_cast<uint32_t *>(p);
+  uint32_t *hist = reinterpret_cast<uint32_t *>(p + vsz);
+  uint32_t *hist_total = reinterpret_cast<uint32_t *>(p + vsz + align_up(256 * nb * 4, 256));
+  void *scan_ws = reinterpret_cast<char *>(hist_total) + 256;
+  uint64_t *kb[2] = {keys, keys_tmp};
+  int cur = 0;
+  for (int pass = 0; pass < np; ++pass) {   // the values ping-pong so that the last pass lands in `order`
+    uint32_t *v_out = ((np - 1 - pass) % 2 == 0) ? order : vbuf;
+    const uint32_t *v_in = pass == 0 ? nullptr : (v_out == order ? vbuf : order);
+    hipLaunchKernelGGL(k_rs_hist<uint64_t>, dim3((unsigned)nb), dim3(256), 0, stream, kb[cur], n, shifts[pass], nb, hist);
+    ME_LAUNCH_CHECK();
+    if (int rc = exclusive_scan_u32(hist, hist, 256 * nb, hist_total, scan_ws, scan_workspace_bytes(256 * nb), stream))
+      return rc;
+    hipLaunchKernelGGL(k_rs_scatter<uint64_t>, dim3((unsigned)nb), dim3(64), 0, stream, kb[cur], v_in, n, shifts[pass], nb,
+                       hist, kb[cur ^ 1], v_out);
+    ME_LAUNCH_CHECK();
+    cur ^= 1;
+  }
+  *sorted_keys = kb[cur];
+  return 0;
+}
+
 }  // namespace me
 
 // =================================================================================================
@@ -1394,7 +1430,7 @@ using namespace me;
 
 extern "C" {
 
-int me_version(void) { return 280; }   // 100 * major + 10 * minor: see the changelog in include/me_amd.h
+int me_version(void) { return 290; }   // 100 * major + 10 * minor: see the changelog in include/me_amd.h
 const char *me_last_error(void) { return g_last_error; }
 
 int64_t me_region_volume(const me_region *rg) {

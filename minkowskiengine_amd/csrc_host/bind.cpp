@@ -274,6 +274,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              const auto &r = s.instance_rows(keyt(k));
              return py::make_tuple(r.first, r.second);
            })
+      .def("_patch_rows",
+           [](CoordinateMapManager &s, const CoordinateMapKey *k, int64_t patch_size, const std::string &order) {
+             const auto &r = s.patch_rows(keyt(k), patch_size, serial_order_code(order));
+             return py::make_tuple(r[0], r[1], r[2], r[3]);
+           })
       .def("get_coordinates", [](CoordinateMapManager &s, const CoordinateMapKey *k) { return s.get(keyt(k))->coords; })
       // tensor fields (pybind/extern.hpp:780-805; field.cpp)
       .def("insert_field",
@@ -686,6 +691,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kernel_dilation"), py::arg("region_type"), py::arg("offset"), py::arg("q_key"), py::arg("kv_key"),
         py::arg("manager"), py::arg("need_grad_q") = true, py::arg("need_grad_k") = true, py::arg("need_grad_v") = true,
         py::arg("need_grad_bias") = true);
+  // serialized patch attention: the attention kernels on the patch lists and block table of csrc/serial_attention.hip
+  m.def("SerializedAttentionForwardGPU",
+        [](const Tensor &q, const Tensor &k, const Tensor &v, int64_t num_heads, double scale, int64_t patch_size,
+           const std::string &order, CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+          std::pair<Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = serialized_attention_forward(q, k, v, num_heads, scale, patch_size, order, in_key, mgr);
+          }
+          return py::make_tuple(r.first, r.second);
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("num_heads"), py::arg("scale"), py::arg("patch_size"),
+        py::arg("order"), py::arg("in_key"), py::arg("manager"));
+  m.def("SerializedAttentionBackwardGPU",
+        [](const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse, const Tensor &grad_out,
+           int64_t num_heads, double scale, int64_t patch_size, const std::string &order, CoordinateMapKey *in_key,
+           CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k, bool need_grad_v) {
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = serialized_attention_backward(q, k, v, out, lse, grad_out, num_heads, scale, patch_size, order, in_key, mgr,
+                                              need_grad_q, need_grad_k, need_grad_v);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]));
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("grad_out"),
+        py::arg("num_heads"), py::arg("scale"), py::arg("patch_size"), py::arg("order"), py::arg("in_key"),
+        py::arg("manager"), py::arg("need_grad_q") = true, py::arg("need_grad_k") = true, py::arg("need_grad_v") = true);
   // tensor fields (field.cpp): the reference's InterpolationForwardGPU / InterpolationBackwardGPU and coo_spmm_int32 /
   // coo_spmm_average_int32 (pybind/extern.hpp:497-506), plus the CSR building blocks the autograd functions cache
   m.def("CsrFromCooGPU",

@@ -255,6 +255,8 @@ struct CoordinateMapManager {
   std::map<KernelMapKeyT, std::shared_ptr<KernelMap>> kernel_maps;
   std::map<KeyT, Tensor> origin_rows_cache;
   std::map<KeyT, std::pair<Tensor, Tensor>> instance_rows_cache;   // per-instance row lists (seg_ptr, seg_rows)
+  // serialized patch attention: (map, patch size, order code) -> {seg_ptr, seg_rows, blk_tab, row_patch}
+  std::map<std::tuple<KeyT, int64_t, int>, std::vector<Tensor>> patch_rows_cache;
   std::map<std::pair<KeyT, KeyT>, Tensor> prune_rows;
   std::map<std::pair<KeyT, KeyT>, std::pair<Tensor, Tensor>> stride_maps;
   // arithmetic across maps: ORDERED (key a, key b) -> union key and {u_of_a, u_of_b, a_of_u, b_of_u} (union_arith_maps)
@@ -293,6 +295,9 @@ struct CoordinateMapManager {
   // (seg_ptr int32 [n_batch + 1], seg_rows int32 [n]): the rows of every instance, ascending (stable csr_from_coo of
   // origin_rows), cached per map: the row lists of the attention kernels (twin of backend._instance_rows)
   const std::pair<Tensor, Tensor> &instance_rows(const KeyT &in_key);
+  // {seg_ptr, seg_rows, blk_tab, row_patch} of serialized patch attention (me_attn_patch_lists), cached per (map, patch
+  // size, order code 0 z / 1 z_trans / 2 hilbert / 3 hilbert_trans): twin of backend._patch_rows
+  const std::vector<Tensor> &patch_rows(const KeyT &in_key, int64_t patch_size, int order);
   std::shared_ptr<KernelMap> kernel_map(const KeyT &in_key, const KeyT &out_key, const ivec &kernel_size,
                                         const ivec &kernel_stride, const ivec &kernel_dilation, int region_type,
                                         bool is_transpose, bool is_pool, const ivec &offsets = ivec());
@@ -401,6 +406,16 @@ std::vector<Tensor> local_attention_backward(Tensor q, Tensor k, Tensor v, Tenso
                                              CoordinateMapKey *q_key, CoordinateMapKey *kv_key, CoordinateMapManager *mgr,
                                              const ivec &offsets, bool need_grad_q, bool need_grad_k, bool need_grad_v,
                                              bool need_grad_bias);
+// serialized patch attention (csrc/serial_attention.hip; twin of backend.SerializedAttention{Forward,Backward}GPU)
+int serial_order_code(const std::string &order);
+std::pair<Tensor, Tensor> serialized_attention_forward(Tensor q, Tensor k, Tensor v, int64_t num_heads, double scale,
+                                                       int64_t patch_size, const std::string &order,
+                                                       CoordinateMapKey *in_key, CoordinateMapManager *mgr);
+std::vector<Tensor> serialized_attention_backward(Tensor q, Tensor k, Tensor v, Tensor out, const Tensor &lse,
+                                                  Tensor grad_out, int64_t num_heads, double scale, int64_t patch_size,
+                                                  const std::string &order, CoordinateMapKey *in_key,
+                                                  CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k,
+                                                  bool need_grad_v);
 // dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU / DensePolicy)
 int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box);
 std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,

@@ -1114,6 +1114,51 @@ const std::pair<Tensor, Tensor> &CoordinateMapManager::instance_rows(const KeyT 
   return instance_rows_cache[in_key] = {std::get<0>(t), std::get<1>(t)};
 }
 
+const std::vector<Tensor> &CoordinateMapManager::patch_rows(const KeyT &in_key, int64_t patch_size, int order) {
+  check(order >= 0 && order <= 3, "unknown serialisation order");
+  check(patch_size >= 1, "patch_size must be at least 1, got " + std::to_string(patch_size));
+  const auto ck = std::make_tuple(in_key, patch_size, order);
+  auto it = patch_rows_cache.find(ck);
+  if (it != patch_rows_cache.end()) return it->second;
+  origin_rows(in_key);   // (checks once that the origin map knows every batch index)
+  auto m = get(in_key);
+  const int64_t n = m->n;
+  const int ncol = (int)m->coords.size(1);
+  const int64_t n_batch = get(origin())->n;
+  std::vector<int64_t> bb(m->bbox.begin(), m->bbox.end());
+  if (n > 0 && (int)bb.size() != 2 * ncol) {   // a derived map: one reduction and one read-back
+    Tensor lohi = at::cat({m->coords.amin(0), m->coords.amax(0)}).to(at::kLong).cpu();
+    bb.assign(lohi.data_ptr<int64_t>(), lohi.data_ptr<int64_t>() + 2 * ncol);
+  }
+  auto bits = [](int64_t x) { int b = 0; while (x > 0) { ++b; x >>= 1; } return b; };
+  std::vector<int32_t> ts(ncol - 1), lo(ncol - 1, 0);
+  int depth = 0;
+  for (int a = 0; a < ncol - 1; ++a) {
+    ts[a] = (int32_t)m->tensor_stride[a];
+    if (n > 0) {
+      lo[a] = (int32_t)bb[1 + a];
+      depth = std::max(depth, bits((bb[ncol + 1 + a] - lo[a]) / ts[a]));
+    }
+  }
+  const int64_t batch_max = n > 0 ? bb[ncol] : 0;
+  check(n == 0 || bb[0] >= 0, "batch indices must not be negative");
+  const int batch_bits = bits(std::max<int64_t>(batch_max, n_batch));
+  check((ncol - 1) * depth + batch_bits <= 63, "the serialisation key of this map needs " +
+                                                   std::to_string((ncol - 1) * depth) + " code bits and " +
+                                                   std::to_string(batch_bits) + " batch bits: more than 63");
+  const c10::Device dev = m->coords.device();
+  const int64_t n_seg = (n + patch_size - 1) / patch_size + n_batch;
+  auto i32 = at::TensorOptions().dtype(at::kInt).device(dev);
+  Tensor seg_ptr = at::empty({n_seg + 1}, i32), seg_rows = at::empty({n}, i32);
+  Tensor blk_tab = at::empty({2 * ((n + 63) / 64 + n_seg)}, i32), row_patch = at::empty({n}, i32);
+  Tensor ws = workspace(me_attn_patch_lists_workspace_bytes(n, (int32_t)n_batch, patch_size), dev);
+  c10::DeviceGuard guard(dev);
+  me_ok(me_attn_patch_lists(ptr<int32_t>(m->coords), n, ncol, ts.data(), lo.data(), depth, (int32_t)batch_max, order,
+                            (int32_t)n_batch, patch_size, ptr<int32_t>(seg_ptr), ptr<int32_t>(seg_rows),
+                            ptr<int32_t>(blk_tab), ptr<int32_t>(row_patch), vptr(ws), ws.numel(), stream_of(dev)));
+  return patch_rows_cache[ck] = {seg_ptr, seg_rows, blk_tab, row_patch};
+}
+
 // Sides of a hyper-cube map (looked-up map `fine_ts`, iterated map `coarse_ts`) on which a row has at most ONE pair by
 // construction: windows of kernel_size voxels that tile space without overlap (coarse stride = kernel_size x fine stride,
 // no dilation) hold every fine voxel exactly once -> bit 0 (the "in" = fine side).  A single-offset kernel pairs a row
@@ -1339,6 +1384,8 @@ std::vector<Tensor> CoordinateMapManager::device_tensors() {
     collect(out, kv.second.first);
     collect(out, kv.second.second);
   }
+  for (auto &kv : patch_rows_cache)
+    for (auto &t : kv.second) collect(out, t);
   for (auto &kv : origin_field_rows_cache) collect(out, kv.second);
   for (auto &kv : prune_rows) collect(out, kv.second);
   for (auto &kv : union_arith)

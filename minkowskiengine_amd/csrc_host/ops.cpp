@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <stdexcept>
 
 namespace meh {
 
@@ -1504,6 +1505,106 @@ std::vector<Tensor> local_attention_backward(Tensor q, Tensor k, Tensor v, Tenso
                                  vptr(grad_v), p.c, ptr<float>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
   }
   return {grad_q, grad_k, grad_v, grad_bias};
+}
+
+// ---- serialized patch attention (csrc/serial_attention.hip + the _tab entry points of csrc/attention.hip; twin of
+// backend.SerializedAttention{Forward,Backward}GPU): q, k, v on ONE map, lists and block table from mgr->patch_rows -------
+int serial_order_code(const std::string &order) {
+  static const char *names[4] = {"z", "z_trans", "hilbert", "hilbert_trans"};
+  for (int i = 0; i < 4; ++i)
+    if (order == names[i]) return i;
+  throw std::invalid_argument("order must be one of ('z', 'z_trans', 'hilbert', 'hilbert_trans'), not '" + order + "'");
+}
+
+struct SerialAttnPrep {
+  int heads, c, n_seg;
+  Tensor seg_ptr, seg_rows, blk_tab;
+};
+static SerialAttnPrep serial_attn_prepare(Tensor &q, Tensor &k, Tensor &v, int64_t num_heads, int64_t patch_size,
+                                          const std::string &order, CoordinateMapKey *in_key,
+                                          CoordinateMapManager *mgr) {
+  q = attn_rows("q", q);
+  k = attn_rows("k", k, &q);
+  v = attn_rows("v", v, &q);
+  const KeyT &ik = in_key->get();
+  check(mgr->exists(ik), "coordinate map not found");
+  const int64_t n = mgr->get(ik)->n;
+  check(q.size(0) == n && k.size(0) == n && v.size(0) == n, "Invalid q / k / v size");
+  const int64_t c = q.size(1);
+  check(num_heads > 0 && c % num_heads == 0, "the channel count " + std::to_string(c) +
+                                                 " must be a multiple of num_heads " + std::to_string(num_heads));
+  const std::vector<Tensor> &l = mgr->patch_rows(ik, patch_size, serial_order_code(order));
+  SerialAttnPrep p;
+  p.heads = (int)num_heads;
+  p.c = (int)c;
+  p.seg_ptr = l[0];
+  p.seg_rows = l[1];
+  p.blk_tab = l[2];
+  p.n_seg = (int)l[0].numel() - 1;
+  return p;
+}
+
+std::pair<Tensor, Tensor> serialized_attention_forward(Tensor q, Tensor k, Tensor v, int64_t num_heads, double scale,
+                                                       int64_t patch_size, const std::string &order,
+                                                       CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+  const SerialAttnPrep p = serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, mgr);
+  const c10::Device dev = q.device();
+  const bool f64 = q.scalar_type() == at::kDouble;
+  const int64_t n = q.size(0);
+  Tensor out = at::empty({n, p.c}, q.options());
+  Tensor lse = at::empty({n, p.heads}, at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev));
+  const int32_t *sp = ptr<int32_t>(p.seg_ptr), *sr = ptr<int32_t>(p.seg_rows), *tab = ptr<int32_t>(p.blk_tab);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_attn_forward_tab_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), attn_stride(q), attn_stride(k),
+                                  attn_stride(v), sp, sr, sp, sr, tab, tab, n, n, p.n_seg, p.c, p.heads, scale,
+                                  ptr<double>(out), p.c, ptr<double>(lse), stream_of(dev)));
+  } else {
+    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+    me_ok(me_attn_forward_tab(q.data_ptr(), k.data_ptr(), v.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v),
+                              sp, sr, sp, sr, tab, tab, n, n, p.n_seg, p.c, p.heads, (float)scale, out.data_ptr(), p.c,
+                              ptr<float>(lse), stream_of(dev)));
+  }
+  return {out, lse};
+}
+
+std::vector<Tensor> serialized_attention_backward(Tensor q, Tensor k, Tensor v, Tensor out, const Tensor &lse,
+                                                  Tensor grad_out, int64_t num_heads, double scale, int64_t patch_size,
+                                                  const std::string &order, CoordinateMapKey *in_key,
+                                                  CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k,
+                                                  bool need_grad_v) {
+  const SerialAttnPrep p = serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, mgr);
+  out = attn_rows("out", out, &q);
+  grad_out = attn_rows("grad_out", grad_out.to(q.scalar_type()));
+  check(out.sizes() == q.sizes() && grad_out.sizes() == q.sizes(), "out and grad_out must have the shape of q");
+  const c10::Device dev = q.device();
+  const bool f64 = q.scalar_type() == at::kDouble;
+  check(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == (f64 ? at::kDouble : at::kFloat) && lse.dim() == 2 &&
+            lse.size(0) == q.size(0) && lse.size(1) == p.heads,
+        "lse must be the contiguous [n, heads] statistics of the forward pass");
+  const int64_t n = q.size(0);
+  Tensor grad_q = need_grad_q ? at::empty({n, p.c}, q.options()) : Tensor();
+  Tensor grad_k = need_grad_k ? at::empty({n, p.c}, q.options()) : Tensor();
+  Tensor grad_v = need_grad_v ? at::empty({n, p.c}, q.options()) : Tensor();
+  if (!(need_grad_q || need_grad_k || need_grad_v)) return {grad_q, grad_k, grad_v};
+  const int32_t *sp = ptr<int32_t>(p.seg_ptr), *sr = ptr<int32_t>(p.seg_rows), *tab = ptr<int32_t>(p.blk_tab);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_attn_backward_tab_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), ptr<double>(out), ptr<double>(lse),
+                                   ptr<double>(grad_out), attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out),
+                                   attn_stride(grad_out), sp, sr, sp, sr, tab, tab, n, n, p.n_seg, p.c, p.heads, scale,
+                                   ptr<double>(grad_q), p.c, ptr<double>(grad_k), p.c, ptr<double>(grad_v), p.c,
+                                   stream_of(dev)));
+  } else {
+    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+    Tensor ws = workspace(me_attn_workspace_bytes(n, n, p.n_seg, p.heads), dev);
+    me_ok(me_attn_backward_tab(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ptr<float>(lse),
+                               grad_out.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out),
+                               attn_stride(grad_out), sp, sr, sp, sr, tab, tab, n, n, p.n_seg, p.c, p.heads, (float)scale,
+                               vptr(grad_q), p.c, vptr(grad_k), p.c, vptr(grad_v), p.c, vptr(ws), ws.numel(),
+                               stream_of(dev)));
+  }
+  return {grad_q, grad_k, grad_v};
 }
 
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------

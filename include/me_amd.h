@@ -107,7 +107,11 @@ typedef struct me_region {
  *   1.19 (290)  round 19: serialized patch attention: z-order / Hilbert keys, patch row lists with a block table, and the
  *              attention kernels reading their block from that table instead of walking seg_ptr (me_coords_serial_keys,
  *              me_attn_patch_lists_workspace_bytes, me_attn_patch_lists, me_attn_forward_tab, me_attn_backward_tab and
- *              the _f64 twins me_attn_forward_tab_f64, me_attn_backward_tab_f64) */
+ *              the _f64 twins me_attn_forward_tab_f64, me_attn_backward_tab_f64)
+ *   1.20 (300)  round 20: cross-attention to a dense context: the row lists of a [B, L, C] context in one launch, and a
+ *              dK / dV pass split over the queries with a fixed-order reduce for few keys under many queries
+ *              (me_attn_context_lists, me_attn_kv_splits, me_attn_split_workspace_bytes, me_attn_backward_split and the
+ *              _f64 twin me_attn_backward_split_f64) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1317,6 +1321,61 @@ int me_attn_backward_tab_f64(const double *q_dev, const double *k_dev, const dou
                              int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads, double scale,
                              double *dq_dev, int64_t dq_stride, double *dk_dev, int64_t dk_stride, double *dv_dev,
                              int64_t dv_stride, void *stream);
+
+/* ---- cross-attention to a dense context (MinkowskiCrossAttention, MinkowskiFunctional.cross_attention;
+ *      csrc/attention.hip, ABI 1.20) ----
+ * The queries are the rows of a coordinate map, the keys / values the rows of a dense context [n_batch, tokens, c]: one
+ * more partition of rows into segments for me_attn_forward_tab and the dQ kernel of the backward pass.
+ *
+ * me_attn_context_lists: segment b holds the rows b * tokens + t for t < len_b, len_b = tokens when lengths_dev is NULL,
+ *   else lengths_dev[b] clamped on the device to [0, tokens].  One launch, no read-back.  seg_ptr int32 [n_batch + 1];
+ *   seg_rows int32 [n_batch * tokens], written up to seg_ptr[n_batch]; blk_tab int32 [2 * (ceil(n_batch * tokens / 64) +
+ *   n_batch)] in the layout of me_attn_patch_lists (unused entries hold segment -1).  A thread sums the lengths before its
+ *   instance itself (O(n_batch) loads).  Host-side errors, nothing launched: tokens < 1, n_batch < 0, n_batch * tokens
+ *   >= 2^31, a null output.
+ *
+ * me_attn_backward_split: me_attn_backward_tab whose dK / dV pass is cut into kv_splits query slices.  The dK / dV kernel
+ *   of me_attn_backward is key-stationary: (ceil(n_kv / 64) + n_batch) * heads workgroups, each walking every query of its
+ *   instance — a few dozen workgroups under tens of thousands of queries when the keys are a short context.  With
+ *   kv_splits = S > 1 slice s of an instance of nblk = ceil(len_q / 32) query blocks walks the blocks
+ *   [floor(s nblk / S), floor((s + 1) nblk / S)) (a slice may be empty) and writes unscaled fp32 partials of the wanted
+ *   gradients to the workspace [S][n_kv][c]; a reduce kernel sums them in ascending s, scales dK, rounds once and writes
+ *   every gradient row once — zeros into a key row that no list holds.  No atomics: bitwise reproducible for a given S.
+ *   kv_splits = 1 runs the launches of me_attn_backward_tab, bit for bit (which leave a key row on no list unwritten).
+ *   Host-side errors, nothing launched: kv_splits < 1 or > ME_ATTN_MAX_KV_SPLITS, a workspace below
+ *   me_attn_split_workspace_bytes, and the errors of me_attn_backward_tab.  The float64 twin accepts and ignores
+ *   kv_splits and the tables; it too leaves a key row on no list unwritten.
+ * me_attn_split_workspace_bytes: delta [n_q, heads] fp32, one int32 mark per key row, and the two partial images of
+ *   kv_splits * n_kv * c fp32 each (every part rounded up to 256 bytes); for every kv_splits >= 1.
+ * me_attn_kv_splits: the policy of the operators, a pure function of the shape (host only).  With wgs = (ceil(n_kv / 64) +
+ *   n_batch) * heads workgroups in the key-stationary grid, S = floor(512 / wgs): 512 workgroups are one round on the
+ *   chip (two on each of 256 CUs at one wave per SIMD), so the slices add no second round.  S = 1 as soon as wgs > 256 —
+ *   every self-attention shape with n_kv = n_q > 64 * 256 / heads.  Bounded by ME_ATTN_MAX_KV_SPLITS (32), by at least
+ *   256 queries of an average instance per slice (S <= n_q / n_batch / 256), and by 64 MiB of partial images
+ *   (2 * S * n_kv * c * 4 bytes); at least 1.  DESIGN.md 8.14 has the measurement behind the bounds. */
+#define ME_ATTN_MAX_KV_SPLITS 32
+int me_attn_context_lists(int32_t n_batch, int32_t tokens, const int32_t *lengths_dev, int32_t *seg_ptr_dev,
+                          int32_t *seg_rows_dev, int32_t *blk_tab_dev, void *stream);
+int32_t me_attn_kv_splits(int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads);
+int64_t me_attn_split_workspace_bytes(int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads,
+                                      int32_t kv_splits);
+int me_attn_backward_split(const void *q_dev, const void *k_dev, const void *v_dev, const void *out_dev,
+                           const float *lse_dev, const void *dout_dev, int32_t is_bf16, int64_t q_stride,
+                           int64_t k_stride, int64_t v_stride, int64_t out_stride, int64_t dout_stride,
+                           const int32_t *seg_ptr_q_dev, const int32_t *seg_rows_q_dev, const int32_t *seg_ptr_kv_dev,
+                           const int32_t *seg_rows_kv_dev, const int32_t *blk_tab_q_dev, const int32_t *blk_tab_kv_dev,
+                           int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads, float scale,
+                           void *dq_dev, int64_t dq_stride, void *dk_dev, int64_t dk_stride, void *dv_dev,
+                           int64_t dv_stride, void *workspace_dev, int64_t workspace_bytes, int32_t kv_splits,
+                           void *stream);
+int me_attn_backward_split_f64(const double *q_dev, const double *k_dev, const double *v_dev, const double *out_dev,
+                               const double *lse_dev, const double *dout_dev, int64_t q_stride, int64_t k_stride,
+                               int64_t v_stride, int64_t out_stride, int64_t dout_stride, const int32_t *seg_ptr_q_dev,
+                               const int32_t *seg_rows_q_dev, const int32_t *seg_ptr_kv_dev,
+                               const int32_t *seg_rows_kv_dev, const int32_t *blk_tab_q_dev,
+                               const int32_t *blk_tab_kv_dev, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c,
+                               int32_t heads, double scale, double *dq_dev, int64_t dq_stride, double *dk_dev,
+                               int64_t dk_stride, double *dv_dev, int64_t dv_stride, int32_t kv_splits, void *stream);
 
 /* ---- dense <-> sparse conversion (SparseTensor.dense, ME.to_sparse, ME.to_sparse_all, ME.dense_coordinates:
  *      MinkowskiEngine/MinkowskiSparseTensor.py:460-557 and MinkowskiOps.py:246-348, torch indexing there;

@@ -6,7 +6,8 @@ torch's needs one dense tensor per sample, so they run MinkowskiGroupNorm's and 
 (normalization.py, csrc/group_norm.hip); and `scaled_dot_product_attention`, which attends inside every instance on the
 operators of attention.py (csrc/attention.hip); and `local_attention`, which attends inside a kernel region on the
 operators of local_attention.py (csrc/local_attention.hip); and `serialized_attention`, which attends inside the patches
-of a space-filling curve on the operators of serialized_attention.py (csrc/serial_attention.hip)."""
+of a space-filling curve on the operators of serialized_attention.py (csrc/serial_attention.hip); and `cross_attention`,
+which attends from the rows of a sparse tensor to a dense context (attention.py, csrc/attention.hip)."""
 import torch.nn.functional as F
 
 from .layers import _rewrap
@@ -93,6 +94,25 @@ def scaled_dot_product_attention(query, key, value, num_heads, scale=None):
     return SparseTensor(out, coordinate_map_key=query.coordinate_map_key, coordinate_manager=query._manager)
 
 
+def cross_attention(query, key, value, num_heads, context_lengths=None, scale=None):
+    """Multi-head attention from the rows of the sparse tensor `query` to a dense context: `key` and `value` are
+    (instances, tokens, channels) tensors with one row per instance (row j for the j-th smallest batch index) and the
+    channels of `query`; context_lengths: None or one integer per instance, the tokens beyond it being masked.  The
+    channels split into `num_heads` heads of 32, 64 or 128 (any size in float64); scale defaults to 1 / sqrt(head size).
+    No dropout.  The result sits on `query`'s map."""
+    import torch
+    from .attention import MinkowskiCrossAttentionFunction
+    from .sparse_tensor import SparseTensor
+    if not isinstance(query, SparseTensor):
+        raise TypeError(f"cross_attention takes a SparseTensor as the query, not a {type(query).__name__}")
+    for name, t in (("key", key), ("value", value)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"cross_attention takes dense tensors as the context; {name} is a {type(t).__name__}")
+    out = MinkowskiCrossAttentionFunction.apply(query.F, key, value, context_lengths, num_heads, scale,
+                                                query.coordinate_map_key, query._manager)
+    return SparseTensor(out, coordinate_map_key=query.coordinate_map_key, coordinate_manager=query._manager)
+
+
 def local_attention(query, key, value, num_heads, kernel_size=3, dilation=1, kernel_generator=None, rel_pos_bias=None,
                     scale=None):
     """Multi-head attention of every row of `query` over the rows of `key` / `value` inside the kernel region around it
@@ -144,4 +164,4 @@ def serialized_attention(query, key, value, num_heads, patch_size, order="z", sc
 
 
 __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention",
-                                                "local_attention", "serialized_attention"]
+                                                "local_attention", "serialized_attention", "cross_attention"]

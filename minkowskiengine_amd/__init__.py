@@ -23,7 +23,8 @@ from .channelwise import MinkowskiChannelwiseConvolution, MinkowskiChannelwiseCo
 from .normalization import (  # noqa: F401
     MinkowskiConditionalGroupNorm, MinkowskiConditionalGroupNormFunction, MinkowskiGroupNorm, MinkowskiGroupNormFunction,
     MinkowskiInstanceNorm, MinkowskiInstanceNormFunction, MinkowskiStableInstanceNorm)
-from .attention import MinkowskiAttentionFunction, MinkowskiSelfAttention  # noqa: F401
+from .attention import (  # noqa: F401
+    MinkowskiAttentionFunction, MinkowskiCrossAttention, MinkowskiCrossAttentionFunction, MinkowskiSelfAttention)
 from .serialized_attention import (  # noqa: F401
     MinkowskiSerializedAttentionFunction, MinkowskiSerializedSelfAttention)
 from .local_attention import MinkowskiLocalAttentionFunction, MinkowskiLocalSelfAttention  # noqa: F401

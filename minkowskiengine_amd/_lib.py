@@ -206,6 +206,16 @@ SIGNATURES = {
     "me_attn_backward_tab_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp,
                                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32,
                                                 ctypes.c_double, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "me_attn_context_lists": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "me_attn_kv_splits": (c_i32, [c_i64, c_i64, c_i32, c_i32, c_i32]),
+    "me_attn_split_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32, c_i32, c_i32]),
+    "me_attn_backward_split": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                              c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32,
+                                              ctypes.c_float, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32,
+                                              c_vp]),
+    "me_attn_backward_split_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32,
+                                                  ctypes.c_double, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp]),
     "me_dense_policy": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, c_i32]),
     "me_dense_cell_index": (ctypes.c_int, [c_vp, c_i64, c_i32, _P_I32, _P_I32, _P_I64, c_vp, c_vp, c_vp]),
     "me_dense_grid": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp]),

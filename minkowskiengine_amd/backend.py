@@ -755,6 +755,7 @@ class CoordinateMapManagerGPU_c10:
         self._origin_maps = {}
         self._instance_rows_cache = {}
         self._patch_rows_cache = {}     # (map key, patch size, order code) -> (seg_ptr, seg_rows, blk_tab, row_patch)
+        self._context_rows_cache = {}   # (instances, tokens, device) -> (seg_ptr, seg_rows, blk_tab)
         self._prune_rows = {}
         self._union_arith = {}   # (key a, key b), ordered -> (union key, u_of_a, u_of_b, a_of_u, b_of_u): union_arith_maps
         self._stride_maps = {}
@@ -1319,6 +1320,35 @@ class CoordinateMapManagerGPU_c10:
             lists = self._patch_rows_cache[ck] = (seg_ptr, seg_rows, blk_tab, row_patch)
         return lists
 
+    def _context_rows(self, n_batch, tokens, device, lengths=None):
+        """(seg_ptr int32 [B + 1], seg_rows int32 [B L], blk_tab int32 [2 (ceil(B L / 64) + B)]) of a dense context of
+        B = n_batch instances of L = tokens rows (me_attn_context_lists, csrc/attention.hip): instance b holds the rows
+        b L + t, t < lengths[b] (int32 [B] on the device, clamped to [0, L]; None: L).  One launch, no read-back; cached
+        per (B, L, device) without lengths, built per call with them."""
+        n_batch, tokens = int(n_batch), int(tokens)
+        _check(n_batch >= 0 and tokens >= 1, "a context needs at least one token per instance, got", tokens)
+        ck = (n_batch, tokens, torch.device(device))
+        if lengths is None:
+            lists = self._context_rows_cache.get(ck)
+            if lists is not None:
+                return lists
+        else:
+            _check(lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous() and
+                   lengths.numel() == n_batch and lengths.device == ck[2],
+                   "context_lengths must hold one int32 per instance on the device of the features")
+        n = n_batch * tokens
+        seg_ptr = torch.empty(n_batch + 1, dtype=torch.int32, device=device)
+        seg_rows = torch.empty(n, dtype=torch.int32, device=device)
+        blk_tab = torch.empty(2 * (-(-n // 64) + n_batch), dtype=torch.int32, device=device)
+        lib = _lib.load()
+        with _on(ck[2]):
+            _lib.check(lib.me_attn_context_lists(n_batch, tokens, _ptr(lengths), _ptr(seg_ptr), _ptr(seg_rows),
+                                                 _ptr(blk_tab), _stream(ck[2])))
+        lists = (seg_ptr, seg_rows, blk_tab)
+        if lengths is None:
+            self._context_rows_cache[ck] = lists
+        return lists
+
     def origin_map(self, in_key):
         """{0: int32 [2, n_in]} (row 0 = in rows, row 1 = origin rows), the reference's origin_map_th layout."""
         rows = self._origin_rows(in_key)
@@ -1414,6 +1444,7 @@ class CoordinateMapManagerGPU_c10:
                     if name not in ("_recipe", "in_map", "out_map"):
                         walk(getattr(o, name, None), depth + 1)
         for store in (self._maps, self._kernel_maps, self._origin_maps, self._instance_rows_cache, self._patch_rows_cache,
+                      self._context_rows_cache,
                       self._origin_field_maps, self._prune_rows,
                       self._stride_maps, self._union_arith):
             walk(store)
@@ -3653,6 +3684,117 @@ def AttentionBackwardGPU(q, k, v, out, lse, grad_out, num_heads, scale, q_key, k
                 _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]),
                 _ptr(seg_kv[1]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(grad_q), c, _ptr(grad_k), c, _ptr(grad_v),
                 c, _ptr(ws), ws.numel(), _stream(dev))))
+    return grad_q, grad_k, grad_v
+
+
+# ------------------------------------------------------------------------------------------------
+# cross-attention to a dense context (csrc/attention.hip, ABI 1.20; not in the reference): the queries are the rows of a
+# coordinate map, the keys / values the rows of a context [B, L, C] with one instance per batch index (context row j
+# belongs to the instance with the j-th smallest batch index: the rows of the origin map).
+# ------------------------------------------------------------------------------------------------
+def _cross_attn_splits(lib, kv_splits, n_q, n_kv, n_batch, c, heads):
+    """the query slices of the dK / dV pass: the argument, else ME_AMD_ATTN_KV_SPLITS, else the library's policy"""
+    if kv_splits is None or int(kv_splits) == 0:
+        kv_splits = os.environ.get("ME_AMD_ATTN_KV_SPLITS") or 0
+    kv_splits = int(kv_splits)
+    return kv_splits if kv_splits != 0 else int(lib.me_attn_kv_splits(n_q, n_kv, n_batch, c, heads))
+
+
+def _cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key, manager):
+    q = _attn_rows("q", q)
+    _check(k.dim() in (2, 3) and v.dim() == k.dim() and tuple(k.shape[:-1]) == tuple(v.shape[:-1]),
+           "k and v must be [B, L, C] or [B * L, C] with the same leading shape, got", tuple(k.shape), tuple(v.shape))
+    if not glob_key.is_key_set():
+        glob_key.set_key(manager.origin().get_key())
+    n_batch = manager.size(glob_key)
+    if k.dim() == 3:
+        _check(k.shape[0] == n_batch, "the context holds", k.shape[0], "instances, the coordinate manager", n_batch)
+        k, v = k.reshape(-1, k.shape[-1]), v.reshape(-1, v.shape[-1])
+    k = _attn_rows("k", k, q)
+    v = _attn_rows("v", v, q)
+    _check(manager.exists(q_key), "coordinate map not found")
+    _check(q.shape[0] == manager.size(q_key), "Invalid q size", q.shape[0], "!=", manager.size(q_key))
+    _check(n_batch > 0 and k.shape[0] % n_batch == 0 and k.shape[0] >= n_batch,
+           "the context rows", k.shape[0], "must be a positive multiple of the instances", n_batch)
+    tokens = int(k.shape[0]) // n_batch
+    heads, c = int(num_heads), int(q.shape[1])
+    _check(heads > 0 and c % heads == 0, "the channel count", c, "must be a multiple of num_heads", heads)
+    if context_lengths is not None:
+        _check(isinstance(context_lengths, torch.Tensor) and context_lengths.dim() == 1 and
+               context_lengths.numel() == n_batch and not context_lengths.is_floating_point(),
+               "context_lengths must be an integer tensor with one length per instance")
+        context_lengths = context_lengths.to(device=q.device, dtype=torch.int32).contiguous()
+    seg_q = manager._instance_rows(q_key)
+    seg_kv = manager._context_rows(n_batch, tokens, q.device, context_lengths)
+    return q, k, v, heads, c, seg_q, seg_kv, n_batch
+
+
+def CrossAttentionForwardGPU(q, k, v, context_lengths, num_heads, scale, q_key, glob_key, manager):
+    """-> (out [n_q, C], lse [n_q, heads]): AttentionForwardGPU with the keys / values of instance b being the first
+    context_lengths[b] (None: all) of the L rows of context b; k, v: [B, L, C], or [B * L, C] row views of one projection.
+    Tokens beyond the length are not read as values.  An instance of length 0: zero rows and lse = -inf."""
+    q, k, v, heads, c, seg_q, seg_kv, n_batch = _cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key,
+                                                                    manager)
+    lib = _lib.load()
+    dev = q.device
+    n_q, n_kv = int(q.shape[0]), int(k.shape[0])
+    out = torch.empty((n_q, c), dtype=q.dtype, device=dev)
+    lse = torch.empty((n_q, heads), dtype=_inorm_param_dtype(q), device=dev)
+    with _on(dev):
+        if q.dtype == torch.float64:
+            _lib.check(lib.me_attn_forward_tab_f64(
+                _ptr(q), _ptr(k), _ptr(v), _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(seg_q[0]), _ptr(seg_q[1]),
+                _ptr(seg_kv[0]), _ptr(seg_kv[1]), None, _ptr(seg_kv[2]), n_q, n_kv, n_batch, c, heads, float(scale),
+                _ptr(out), c, _ptr(lse), _stream(dev)))
+        else:
+            bf = 1 if q.dtype == torch.bfloat16 else 0
+            _timed("cross_attn_forward", dev, lambda: _lib.check(lib.me_attn_forward_tab(
+                _ptr(q), _ptr(k), _ptr(v), bf, _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(seg_q[0]),
+                _ptr(seg_q[1]), _ptr(seg_kv[0]), _ptr(seg_kv[1]), None, _ptr(seg_kv[2]), n_q, n_kv, n_batch, c, heads,
+                float(scale), _ptr(out), c, _ptr(lse), _stream(dev))))
+    return out, lse
+
+
+def CrossAttentionBackwardGPU(q, k, v, context_lengths, out, lse, grad_out, num_heads, scale, q_key, glob_key, manager,
+                              need_grad_q=True, need_grad_k=True, need_grad_v=True, kv_splits=None):
+    """-> (grad_q | None, grad_k | None, grad_v | None), contiguous [n_q, C] and [B * L, C]; a gradient that is not
+    requested is not computed.  The dK / dV pass is cut into `kv_splits` query slices (None: ME_AMD_ATTN_KV_SPLITS, else
+    me_attn_kv_splits).  Tokens beyond an instance's length get exactly zero grad_k / grad_v."""
+    q, k, v, heads, c, seg_q, seg_kv, n_batch = _cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key,
+                                                                    manager)
+    out = _attn_rows("out", out, q)
+    grad_out = _attn_rows("grad_out", grad_out.to(q.dtype))
+    _check(tuple(out.shape) == tuple(q.shape) and tuple(grad_out.shape) == tuple(q.shape),
+           "out and grad_out must have the shape of q")
+    _check(lse.is_cuda and lse.is_contiguous() and lse.dtype == _inorm_param_dtype(q) and
+           tuple(lse.shape) == (q.shape[0], heads), "lse must be the contiguous [n_q, heads] statistics of the forward pass")
+    lib = _lib.load()
+    dev = q.device
+    n_q, n_kv = int(q.shape[0]), int(k.shape[0])
+    f64 = q.dtype == torch.float64
+    splits = _cross_attn_splits(lib, kv_splits, n_q, n_kv, n_batch, c, heads)
+    if not (need_grad_q or need_grad_k or need_grad_v):
+        return None, None, None
+    # the key-stationary kernel (one slice, float64) writes the listed rows only: the others are zeroed here
+    new_kv = torch.zeros if context_lengths is not None and (splits == 1 or f64) else torch.empty
+    grad_q = torch.empty((n_q, c), dtype=q.dtype, device=dev) if need_grad_q else None
+    grad_k = new_kv((n_kv, c), dtype=q.dtype, device=dev) if need_grad_k else None
+    grad_v = new_kv((n_kv, c), dtype=q.dtype, device=dev) if need_grad_v else None
+    with _on(dev):
+        if f64:
+            _lib.check(lib.me_attn_backward_split_f64(
+                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), _attn_stride(q), _attn_stride(k),
+                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]),
+                _ptr(seg_kv[1]), None, _ptr(seg_kv[2]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(grad_q), c,
+                _ptr(grad_k), c, _ptr(grad_v), c, splits, _stream(dev)))
+        else:
+            bf = 1 if q.dtype == torch.bfloat16 else 0
+            ws = _workspace(int(lib.me_attn_split_workspace_bytes(n_q, n_kv, n_batch, c, heads, max(splits, 1))), dev)
+            _timed("cross_attn_backward", dev, lambda: _lib.check(lib.me_attn_backward_split(
+                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), bf, _attn_stride(q), _attn_stride(k),
+                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]),
+                _ptr(seg_kv[1]), None, _ptr(seg_kv[2]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(grad_q), c,
+                _ptr(grad_k), c, _ptr(grad_v), c, _ptr(ws), ws.numel(), splits, _stream(dev))))
     return grad_q, grad_k, grad_v
 
 

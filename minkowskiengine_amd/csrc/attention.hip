@@ -35,6 +35,7 @@
 // The float64 twins at the end are the gradcheck yardstick (plain double, one thread per (row, head)).
 #include "common.hpp"
 
+#include <algorithm>
 #include <cmath>
 
 namespace me {
@@ -473,6 +474,173 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_bwd_kv(
   if (want_v) attn_store_rows<T, D>(dv, dv_stride, ki, head, av, 1.f, h);
 }
 
+// ---- backward: dK / dV split over the queries ------------------------------------------------------------------------
+// With few keys and many queries (cross-attention to a short context) the key-stationary grid is a handful of workgroups
+// that each walk every query of their instance.  k_attn_bwd_kv_split adds a grid dimension of S query slices: slice s of
+// an instance of nblk = ceil(len_q / 32) query blocks walks the blocks [floor(s nblk / S), floor((s + 1) nblk / S)) and
+// writes its unscaled fp32 partial of dK^T / dV^T (only the wanted ones; zeros from an empty slice) to row `key row` of
+// image s of part_k / part_v [S][n_kv][c].  The workgroups of slice 0, head 0 also mark their key rows in `listed`
+// (zeroed beforehand).  k_attn_kv_reduce then sums the S partials of every (key row, 4 channels) in ascending s, scales
+// dK, rounds once and writes the gradient row; a row that no list holds gets zeros.  No atomics: bitwise reproducible.
+// The walk repeats k_attn_bwd_kv's over a range of query blocks; that kernel keeps its text, and so its code object, for
+// kv_splits = 1 (sharing the walk through an inlined function changed its register allocation).
+template <typename T, int D>
+__global__ __launch_bounds__(kAttnThreads) void k_attn_bwd_kv_split(
+    const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v, const T *__restrict__ dout,
+    int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t dout_stride, const int32_t *__restrict__ seg_ptr_q,
+    const int32_t *__restrict__ seg_rows_q, const int32_t *__restrict__ seg_ptr_kv,
+    const int32_t *__restrict__ seg_rows_kv, const int32_t *__restrict__ blk_tab, int n_batch, int heads, float scale,
+    const float *__restrict__ lse, const float *__restrict__ delta, int64_t n_kv, float *__restrict__ part_k,
+    float *__restrict__ part_v, int32_t *__restrict__ listed) {
+  int b, t0, startk, lenk;
+  if (!attn_find_item(blk_tab, seg_ptr_kv, n_batch, blockIdx.x, kAttnBlock, b, t0, startk, lenk)) return;
+  const int head = blockIdx.y;
+  const int startq = seg_ptr_q[b], lenq = seg_ptr_q[b + 1] - startq;
+  const int64_t nblk = (lenq + kAttnBwdWalk - 1) / kAttnBwdWalk, slice = blockIdx.z, n_slices = gridDim.z;
+  const int q_lo = (int)(slice * nblk / n_slices) * kAttnBwdWalk, q_hi = (int)((slice + 1) * nblk / n_slices) * kAttnBwdWalk;
+  const bool want_k = part_k != nullptr, want_v = part_v != nullptr;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  at_f32x16 ak[D / 32], av[D / 32];
+  constexpr int NC = D / 16, ND = D / 32, W = kAttnBwdWalk;
+  constexpr int LDN = D + AttnT<T>::PADN, LDT = W + AttnT<T>::PADT;
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_attn[];
+  T *s_q = reinterpret_cast<T *>(s_attn);   // [W][LDN]
+  T *s_g = s_q + W * LDN;                   // [W][LDN]   dO
+  T *s_qt = s_g + W * LDN;                  // [D][LDT]
+  T *s_gt = s_qt + D * LDT;                 // [D][LDT]
+  float *s_lse = reinterpret_cast<float *>(s_gt + D * LDT);   // [W]
+  float *s_delta = s_lse + W;                                 // [W]
+  const int tk = t0 + wave * 32 + r;
+  const bool validk = tk < lenk, wave_on = t0 + wave * 32 < lenk;
+  const int64_t ki = seg_rows_kv[startk + min(tk, lenk - 1)];
+  AttnFrag<T> kf[NC], vf[NC];
+  {
+    const T *kp = k + ki * k_stride + (int64_t)head * D + 8 * h;
+    const T *vp = v + ki * v_stride + (int64_t)head * D + 8 * h;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      kf[c] = attn_load8(kp + 16 * c);
+      vf[c] = attn_load8(vp + 16 * c);
+    }
+  }
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { ak[dt][i] = 0.f; av[dt][i] = 0.f; }
+  for (int q0 = q_lo; q0 < q_hi; q0 += W) {
+    __syncthreads();
+    attn_stage<T, D, W>(q, q_stride, head, seg_rows_q, startq, lenq, q0, s_q, false, s_qt);
+    attn_stage<T, D, W>(dout, dout_stride, head, seg_rows_q, startq, lenq, q0, s_g, true, s_gt);
+    if (threadIdx.x < W) {
+      const int w = threadIdx.x;
+      const bool valid = q0 + w < lenq;
+      const int64_t row = seg_rows_q[startq + min(q0 + w, lenq - 1)];
+      s_lse[w] = lse[row * heads + head];
+      s_delta[w] = valid ? delta[row * heads + head] : 0.f;
+    }
+    __syncthreads();
+    if (!wave_on) continue;
+    at_f32x16 s, dp;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
+    const T *qp = s_q + r * LDN + 8 * h, *gp = s_g + r * LDN + 8 * h;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) attn_mma(s, attn_load8(qp + 16 * c), kf[c]);   // S[query][key]
+    if (want_k) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) attn_mma(dp, attn_load8(gp + 16 * c), vf[c]);   // dP[query][key]
+    }
+    float p[16], ds[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int w = attn_row(i, h);
+      p[i] = (q0 + w < lenq) ? attn_exp<T>(s[i] * scale - s_lse[w]) : 0.f;
+      ds[i] = p[i] * (dp[i] - s_delta[w]);
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      if (want_v) {
+        const AttnFrag<T> pf = attn_acc_frag<T>(p, s2);
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt)   // dV^T[channel][key] += dO^T[channel][query] P[query][key]
+          attn_mma(av[dt], attn_load44(s_gt + (dt * 32 + r) * LDT + 16 * s2 + 4 * h), pf);
+      }
+      if (want_k) {
+        const AttnFrag<T> df = attn_acc_frag<T>(ds, s2);
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt)   // dK^T[channel][key] += Q^T[channel][query] dS[query][key]
+          attn_mma(ak[dt], attn_load44(s_qt + (dt * 32 + r) * LDT + 16 * s2 + 4 * h), df);
+      }
+    }
+  }
+  if (!validk) return;
+  const int64_t c = (int64_t)heads * D, image = slice * n_kv * c;
+  if (want_k) attn_store_rows<float, D>(part_k + image, c, ki, head, ak, 1.f, h);
+  if (want_v) attn_store_rows<float, D>(part_v + image, c, ki, head, av, 1.f, h);
+  if (slice == 0 && head == 0 && h == 0) listed[ki] = 1;
+}
+
+// thread: (key row, 4 channels) of the gradient blockIdx.y (0 dK, 1 dV)
+template <typename T>
+__global__ __launch_bounds__(256) void k_attn_kv_reduce(const float *__restrict__ part_k, const float *__restrict__ part_v,
+                                                        const int32_t *__restrict__ listed, int64_t n_kv, int c,
+                                                        int n_slices, float scale, T *__restrict__ dk, int64_t dk_stride,
+                                                        T *__restrict__ dv, int64_t dv_stride) {
+  const bool is_k = blockIdx.y == 0;
+  const float *part = is_k ? part_k : part_v;
+  T *y = is_k ? dk : dv;
+  if (y == nullptr) return;
+  const int pieces = c / 4;
+  const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= n_kv * pieces) return;
+  const int64_t row = id / pieces;
+  const int col = (int)(id - row * pieces) * 4;
+  at_f32x4 acc;
+  acc[0] = acc[1] = acc[2] = acc[3] = 0.f;
+  if (listed[row]) {
+    const float *p = part + row * c + col;
+    for (int s = 0; s < n_slices; ++s) acc += *reinterpret_cast<const at_f32x4 *>(p + (int64_t)s * n_kv * c);
+  }
+  const float mul = is_k ? scale : 1.f;
+  attn_store4(y + row * (is_k ? dk_stride : dv_stride) + col, acc[0] * mul, acc[1] * mul, acc[2] * mul, acc[3] * mul);
+}
+
+// ---- row lists of a dense context [n_batch, tokens, c]: segment b = rows b tokens + t, t < len_b ------------------------
+// Thread i < n_batch * tokens places row i; thread i <= n_batch writes seg_ptr[i]; thread i < ceil(n_batch tokens / 64) +
+// n_batch writes pair i of the block table.  Each sums the clamped lengths before its instance itself: O(n_batch) loads,
+// a context batch being a handful of instances.  seg_rows past seg_ptr[n_batch] is not written.
+__device__ __forceinline__ int attn_context_len(const int32_t *__restrict__ lengths, int b, int tokens) {
+  return lengths ? min(max(lengths[b], 0), tokens) : tokens;
+}
+__global__ __launch_bounds__(256) void k_attn_context_lists(int n_batch, int tokens, const int32_t *__restrict__ lengths,
+                                                           int64_t n_entries, int32_t *__restrict__ seg_ptr,
+                                                           int32_t *__restrict__ seg_rows, int32_t *__restrict__ blk_tab) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (int64_t)n_batch * tokens) {
+    const int b = (int)(i / tokens), t = (int)(i - (int64_t)b * tokens);
+    if (t < attn_context_len(lengths, b, tokens)) {
+      int start = 0;
+      for (int j = 0; j < b; ++j) start += attn_context_len(lengths, j, tokens);
+      seg_rows[start + t] = (int32_t)i;
+    }
+  }
+  if (i <= n_batch) {
+    int start = 0;
+    for (int j = 0; j < i; ++j) start += attn_context_len(lengths, j, tokens);
+    seg_ptr[i] = start;
+  }
+  if (i < n_entries) {
+    int seg = -1, first = -1, acc = 0;
+    for (int b = 0; b < n_batch && seg < 0; ++b) {
+      const int nb = (attn_context_len(lengths, b, tokens) + kAttnBlock - 1) / kAttnBlock;
+      if (i < acc + nb) { seg = b; first = (int)(i - acc) * kAttnBlock; }
+      acc += nb;
+    }
+    blk_tab[2 * i] = seg;
+    blk_tab[2 * i + 1] = first;
+  }
+}
+
 template <typename T, int D> constexpr int attn_fwd_lds() {
   return (int)sizeof(T) * (kAttnFwdWalk * (D + AttnT<T>::PADN) + D * (kAttnFwdWalk + AttnT<T>::PADT));
 }
@@ -494,6 +662,9 @@ struct AttnArgs {
   float scale;
   void *out_w, *dq, *dk, *dv;
   float *lse, *delta;
+  int kv_splits;                   // > 1: dK / dV through k_attn_bwd_kv_split and k_attn_kv_reduce
+  float *part_k, *part_v;          // [kv_splits][n_kv][c] each
+  int32_t *listed;                 // [n_kv]
 };
 
 // more than 48 KiB of dynamic LDS has to be allowed per kernel, once
@@ -526,7 +697,21 @@ static int attn_backward_t(const AttnArgs &a, hipStream_t stream) {
                                                a.heads, a.delta);
     ME_LAUNCH_CHECK();
   }
-  if ((a.dk || a.dv) && a.n_kv > 0) {
+  if ((a.dk || a.dv) && a.n_kv > 0 && a.kv_splits > 1) {
+    const dim3 grid((unsigned)(ceil_div(a.n_kv, kAttnBlock) + a.n_batch), (unsigned)a.heads, (unsigned)a.kv_splits);
+    const int c = a.heads * D;
+    ME_HIP(hipMemsetAsync(a.listed, 0, (size_t)a.n_kv * sizeof(int32_t), stream));
+    ME_ATTN_LDS_ATTR((k_attn_bwd_kv_split<T, D>), (attn_bwd_kv_lds<T, D>()));
+    k_attn_bwd_kv_split<T, D><<<grid, kAttnThreads, attn_bwd_kv_lds<T, D>(), stream>>>(
+        (const T *)a.q, (const T *)a.k, (const T *)a.v, (const T *)a.dout, a.q_stride, a.k_stride, a.v_stride,
+        a.dout_stride, a.seg_ptr_q, a.seg_rows_q, a.seg_ptr_kv, a.seg_rows_kv, a.tab_kv, a.n_batch, a.heads, a.scale, a.lse,
+        a.delta, a.n_kv, a.dk ? a.part_k : nullptr, a.dv ? a.part_v : nullptr, a.listed);
+    ME_LAUNCH_CHECK();
+    const dim3 rgrid((unsigned)ceil_div(a.n_kv * (c / 4), 256), 2);
+    k_attn_kv_reduce<T><<<rgrid, 256, 0, stream>>>(a.part_k, a.part_v, a.listed, a.n_kv, c, a.kv_splits, a.scale,
+                                                   (T *)a.dk, a.dk_stride, (T *)a.dv, a.dv_stride);
+    ME_LAUNCH_CHECK();
+  } else if ((a.dk || a.dv) && a.n_kv > 0) {
     const dim3 grid((unsigned)(ceil_div(a.n_kv, kAttnBlock) + a.n_batch), (unsigned)a.heads);
     ME_ATTN_LDS_ATTR((k_attn_bwd_kv<T, D>), (attn_bwd_kv_lds<T, D>()));
     k_attn_bwd_kv<T, D><<<grid, kAttnThreads, attn_bwd_kv_lds<T, D>(), stream>>>(
@@ -574,6 +759,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd_f64(
   const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= n_q * heads) return;
   const int64_t t = id / heads;
+  if (t >= seg_ptr_q[n_batch]) return;   // a row that no list holds
   const int head = (int)(id - t * heads);
   const int b = attn_instance_of(seg_ptr_q, n_batch, t);
   const int64_t qi = seg_rows_q[t];
@@ -612,6 +798,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q_f64(
   const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= n_q * heads) return;
   const int64_t t = id / heads;
+  if (t >= seg_ptr_q[n_batch]) return;   // a row that no list holds
   const int head = (int)(id - t * heads);
   const int b = attn_instance_of(seg_ptr_q, n_batch, t);
   const int64_t qi = seg_rows_q[t];
@@ -649,6 +836,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv_f64(
   const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= n_kv * heads) return;
   const int64_t t = id / heads;
+  if (t >= seg_ptr_kv[n_batch]) return;   // a row that no list holds
   const int head = (int)(id - t * heads);
   const int b = attn_instance_of(seg_ptr_kv, n_batch, t);
   const int64_t ki = seg_rows_kv[t];
@@ -746,13 +934,57 @@ int me_attn_forward(const void *q, const void *k, const void *v, int32_t is_bf16
                              nullptr, nullptr, n_q, n_kv, n_batch, c, heads, scale, out, out_stride, lse, stream_);
 }
 
-int me_attn_backward_tab(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout,
-                         int32_t is_bf16, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t out_stride,
-                         int64_t dout_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q,
-                         const int32_t *seg_ptr_kv, const int32_t *seg_rows_kv, const int32_t *blk_tab_q,
-                         const int32_t *blk_tab_kv, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads,
-                         float scale, void *dq, int64_t dq_stride, void *dk, int64_t dk_stride, void *dv,
-                         int64_t dv_stride, void *workspace, int64_t workspace_bytes, void *stream_) {
+// the workspace of me_attn_backward_split: delta, the marks of the listed key rows, the partial images of dK and dV
+struct AttnSplitWs {
+  int64_t listed, part_k, part_v, bytes;   // byte offsets
+};
+static AttnSplitWs attn_split_ws(int64_t n_q, int64_t n_kv, int32_t c, int32_t heads, int32_t kv_splits) {
+  const int64_t nq = n_q > 0 ? n_q : 0, nk = n_kv > 0 ? n_kv : 0, ch = c > 0 ? c : 0, h = heads > 0 ? heads : 0;
+  const int64_t image = align_up((kv_splits > 0 ? kv_splits : 0) * nk * ch * (int64_t)sizeof(float), 256);
+  AttnSplitWs w;
+  w.listed = align_up(nq * h * (int64_t)sizeof(float), 256);
+  w.part_k = w.listed + align_up(nk * (int64_t)sizeof(int32_t), 256);
+  w.part_v = w.part_k + image;
+  w.bytes = w.part_v + image;
+  return w;
+}
+
+int64_t me_attn_split_workspace_bytes(int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads,
+                                      int32_t kv_splits) {
+  (void)n_batch;
+  return attn_split_ws(n_q, n_kv, c, heads, kv_splits).bytes;
+}
+
+// The policy of the cross-attention operators: how many query slices the dK / dV pass takes.  A pure function of the
+// shape.  The key-stationary grid has wgs = (ceil(n_kv / 64) + n_batch) * heads workgroups of two waves; at the one wave
+// per SIMD the kernels reach for d >= 64 a CU holds two of them, the chip kAttnSplitSlots = 512.  S = floor(512 / wgs):
+// the slices of all workgroups still run in ONE round, each walking 1 / S of the queries (a second round would give back
+// what the shorter walk wins: measured).  So S = 1 as soon as wgs > 256 — every self-attention shape of
+// scripts/attention_bench.py, where n_kv = n_q.  Bounded by ME_ATTN_MAX_KV_SPLITS, by kAttnSplitMinQueries queries of an
+// average instance per slice (the shortest measured, 156, still won) and by kAttnSplitMaxBytes of partial images.
+// Measurement: DESIGN 8.14.
+constexpr int64_t kAttnSplitSlots = 512;
+constexpr int64_t kAttnSplitMinQueries = 256;
+constexpr int64_t kAttnSplitMaxBytes = 64ll << 20;
+int32_t me_attn_kv_splits(int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads) {
+  if (n_q <= 0 || n_kv <= 0 || n_batch <= 0 || c <= 0 || heads <= 0) return 1;
+  const int64_t wgs = (ceil_div(n_kv, kAttnBlock) + n_batch) * heads;
+  int64_t s = kAttnSplitSlots / wgs;
+  s = std::min<int64_t>(s, ME_ATTN_MAX_KV_SPLITS);
+  s = std::min<int64_t>(s, n_q / n_batch / kAttnSplitMinQueries);
+  s = std::min<int64_t>(s, kAttnSplitMaxBytes / (2 * n_kv * c * (int64_t)sizeof(float)));
+  return (int32_t)std::max<int64_t>(s, 1);
+}
+
+// kv_splits 0: me_attn_backward_tab (the workspace holds delta only); >= 1: me_attn_backward_split
+static int attn_backward_entry(const void *q, const void *k, const void *v, const void *out, const float *lse,
+                               const void *dout, int32_t is_bf16, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                               int64_t out_stride, int64_t dout_stride, const int32_t *seg_ptr_q,
+                               const int32_t *seg_rows_q, const int32_t *seg_ptr_kv, const int32_t *seg_rows_kv,
+                               const int32_t *blk_tab_q, const int32_t *blk_tab_kv, int64_t n_q, int64_t n_kv,
+                               int32_t n_batch, int32_t c, int32_t heads, float scale, void *dq, int64_t dq_stride,
+                               void *dk, int64_t dk_stride, void *dv, int64_t dv_stride, void *workspace,
+                               int64_t workspace_bytes, int32_t kv_splits, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int unit = is_bf16 ? 8 : 4;
   ME_ATTN_CHECK_DIMS(unit);
@@ -764,7 +996,9 @@ int me_attn_backward_tab(const void *q, const void *k, const void *v, const void
   ME_CHECK(dq == nullptr || (dq_stride >= c && dq_stride % unit == 0), "dq: a row stride must be >= the channel count and a multiple of 16 bytes");
   ME_CHECK(dk == nullptr || (dk_stride >= c && dk_stride % unit == 0), "dk: a row stride must be >= the channel count and a multiple of 16 bytes");
   ME_CHECK(dv == nullptr || (dv_stride >= c && dv_stride % unit == 0), "dv: a row stride must be >= the channel count and a multiple of 16 bytes");
-  ME_CHECK(workspace_bytes >= me_attn_workspace_bytes(n_q, n_kv, n_batch, heads), "workspace too small");
+  ME_CHECK(workspace_bytes >= (kv_splits == 0 ? me_attn_workspace_bytes(n_q, n_kv, n_batch, heads)
+                                              : me_attn_split_workspace_bytes(n_q, n_kv, n_batch, c, heads, kv_splits)),
+           "workspace too small");
   ME_ATTN_CHECK_TABLES();
   if (n_batch == 0 || (n_q == 0 && n_kv == 0)) return 0;
   if (dq == nullptr && dk == nullptr && dv == nullptr) return 0;
@@ -790,7 +1024,61 @@ int me_attn_backward_tab(const void *q, const void *k, const void *v, const void
   a.lse = const_cast<float *>(lse);
   a.delta = reinterpret_cast<float *>(workspace);
   a.tab_q = blk_tab_q; a.tab_kv = blk_tab_kv;
+  a.kv_splits = kv_splits;
+  if (kv_splits > 1) {
+    const AttnSplitWs w = attn_split_ws(n_q, n_kv, c, heads, kv_splits);
+    char *base = reinterpret_cast<char *>(workspace);
+    a.listed = reinterpret_cast<int32_t *>(base + w.listed);
+    a.part_k = reinterpret_cast<float *>(base + w.part_k);
+    a.part_v = reinterpret_cast<float *>(base + w.part_v);
+  }
   ME_ATTN_DISPATCH(is_bf16, c / heads, attn_backward_t, a, stream);
+}
+
+int me_attn_backward_tab(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout,
+                         int32_t is_bf16, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t out_stride,
+                         int64_t dout_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q,
+                         const int32_t *seg_ptr_kv, const int32_t *seg_rows_kv, const int32_t *blk_tab_q,
+                         const int32_t *blk_tab_kv, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads,
+                         float scale, void *dq, int64_t dq_stride, void *dk, int64_t dk_stride, void *dv,
+                         int64_t dv_stride, void *workspace, int64_t workspace_bytes, void *stream_) {
+  return attn_backward_entry(q, k, v, out, lse, dout, is_bf16, q_stride, k_stride, v_stride, out_stride, dout_stride,
+                             seg_ptr_q, seg_rows_q, seg_ptr_kv, seg_rows_kv, blk_tab_q, blk_tab_kv, n_q, n_kv, n_batch, c,
+                             heads, scale, dq, dq_stride, dk, dk_stride, dv, dv_stride, workspace, workspace_bytes, 0,
+                             stream_);
+}
+
+// me_attn_backward_tab with the dK / dV pass cut into kv_splits query slices (1: the same launches, bit for bit)
+int me_attn_backward_split(const void *q, const void *k, const void *v, const void *out, const float *lse,
+                           const void *dout, int32_t is_bf16, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                           int64_t out_stride, int64_t dout_stride, const int32_t *seg_ptr_q, const int32_t *seg_rows_q,
+                           const int32_t *seg_ptr_kv, const int32_t *seg_rows_kv, const int32_t *blk_tab_q,
+                           const int32_t *blk_tab_kv, int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c,
+                           int32_t heads, float scale, void *dq, int64_t dq_stride, void *dk, int64_t dk_stride, void *dv,
+                           int64_t dv_stride, void *workspace, int64_t workspace_bytes, int32_t kv_splits, void *stream_) {
+  ME_CHECK(kv_splits >= 1 && kv_splits <= ME_ATTN_MAX_KV_SPLITS, "kv_splits must be between 1 and ME_ATTN_MAX_KV_SPLITS (32)");
+  return attn_backward_entry(q, k, v, out, lse, dout, is_bf16, q_stride, k_stride, v_stride, out_stride, dout_stride,
+                             seg_ptr_q, seg_rows_q, seg_ptr_kv, seg_rows_kv, blk_tab_q, blk_tab_kv, n_q, n_kv, n_batch, c,
+                             heads, scale, dq, dq_stride, dk, dk_stride, dv, dv_stride, workspace, workspace_bytes,
+                             kv_splits, stream_);
+}
+
+// the row lists and block table of a dense context of n_batch x tokens rows (k_attn_context_lists): one launch
+int me_attn_context_lists(int32_t n_batch, int32_t tokens, const int32_t *lengths, int32_t *seg_ptr, int32_t *seg_rows,
+                          int32_t *blk_tab, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_CHECK(n_batch >= 0, "n_batch must not be negative");
+  ME_CHECK(tokens >= 1, "tokens must be at least 1");
+  const int64_t n = (int64_t)n_batch * tokens;
+  ME_CHECK(n < (1ll << 31), "the context rows must fit in int32");
+  ME_CHECK(seg_ptr != nullptr && blk_tab != nullptr && (n_batch == 0 || seg_rows != nullptr),
+           "seg_ptr, seg_rows and blk_tab must be given");
+  const int64_t n_entries = ceil_div(n, kAttnBlock) + n_batch;
+  const int64_t threads = std::max<int64_t>(std::max<int64_t>(n, n_entries), n_batch + 1);
+  k_attn_context_lists<<<(unsigned)ceil_div(threads, 256), 256, 0, stream>>>(n_batch, tokens, lengths, n_entries, seg_ptr,
+                                                                             seg_rows, blk_tab);
+  ME_LAUNCH_CHECK();
+  return 0;
 }
 
 int me_attn_backward(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout,
@@ -882,6 +1170,22 @@ int me_attn_backward_tab_f64(const double *q, const double *k, const double *v, 
                              double *dv, int64_t dv_stride, void *stream_) {
   (void)blk_tab_q;
   (void)blk_tab_kv;
+  return me_attn_backward_f64(q, k, v, out, lse, dout, q_stride, k_stride, v_stride, out_stride, dout_stride, seg_ptr_q,
+                              seg_rows_q, seg_ptr_kv, seg_rows_kv, n_q, n_kv, n_batch, c, heads, scale, dq, dq_stride, dk,
+                              dk_stride, dv, dv_stride, stream_);
+}
+
+int me_attn_backward_split_f64(const double *q, const double *k, const double *v, const double *out, const double *lse,
+                               const double *dout, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                               int64_t out_stride, int64_t dout_stride, const int32_t *seg_ptr_q,
+                               const int32_t *seg_rows_q, const int32_t *seg_ptr_kv, const int32_t *seg_rows_kv,
+                               const int32_t *blk_tab_q, const int32_t *blk_tab_kv, int64_t n_q, int64_t n_kv,
+                               int32_t n_batch, int32_t c, int32_t heads, double scale, double *dq, int64_t dq_stride,
+                               double *dk, int64_t dk_stride, double *dv, int64_t dv_stride, int32_t kv_splits,
+                               void *stream_) {
+  (void)blk_tab_q;
+  (void)blk_tab_kv;
+  (void)kv_splits;
   return me_attn_backward_f64(q, k, v, out, lse, dout, q_stride, k_stride, v_stride, out_stride, dout_stride, seg_ptr_q,
                               seg_rows_q, seg_ptr_kv, seg_rows_kv, n_q, n_kv, n_batch, c, heads, scale, dq, dq_stride, dk,
                               dk_stride, dv, dv_stride, stream_);

@@ -279,6 +279,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              const auto &r = s.patch_rows(keyt(k), patch_size, serial_order_code(order));
              return py::make_tuple(r[0], r[1], r[2], r[3]);
            })
+      .def("_context_rows",
+           [](CoordinateMapManager &s, int64_t n_batch, int64_t tokens, const py::object &device,
+              const py::object &lengths) {
+             const c10::Device dev = py::cast<c10::Device>(py::module_::import("torch").attr("device")(device));
+             const auto r = s.context_rows(n_batch, tokens, dev, opt_tensor(lengths));
+             return py::make_tuple(r[0], r[1], r[2]);
+           },
+           py::arg("n_batch"), py::arg("tokens"), py::arg("device"), py::arg("lengths") = py::none())
       .def("get_coordinates", [](CoordinateMapManager &s, const CoordinateMapKey *k) { return s.get(keyt(k))->coords; })
       // tensor fields (pybind/extern.hpp:780-805; field.cpp)
       .def("insert_field",
@@ -651,6 +659,39 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("grad_out"),
         py::arg("num_heads"), py::arg("scale"), py::arg("q_key"), py::arg("kv_key"), py::arg("glob_key"),
         py::arg("manager"), py::arg("need_grad_q") = true, py::arg("need_grad_k") = true, py::arg("need_grad_v") = true);
+  // cross-attention to a dense context: the attention kernels on the context row lists, dK / dV split over the queries
+  m.def("CrossAttentionForwardGPU",
+        [](const Tensor &q, const Tensor &k, const Tensor &v, const py::object &context_lengths, int64_t num_heads,
+           double scale, CoordinateMapKey *q_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+          const Tensor len = opt_tensor(context_lengths);
+          std::pair<Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = cross_attention_forward(q, k, v, len, num_heads, scale, q_key, glob_key, mgr);
+          }
+          return py::make_tuple(r.first, r.second);
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("context_lengths"), py::arg("num_heads"), py::arg("scale"),
+        py::arg("q_key"), py::arg("glob_key"), py::arg("manager"));
+  m.def("CrossAttentionBackwardGPU",
+        [](const Tensor &q, const Tensor &k, const Tensor &v, const py::object &context_lengths, const Tensor &out,
+           const Tensor &lse, const Tensor &grad_out, int64_t num_heads, double scale, CoordinateMapKey *q_key,
+           CoordinateMapKey *glob_key, CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k, bool need_grad_v,
+           const py::object &kv_splits) {
+          const Tensor len = opt_tensor(context_lengths);
+          const int64_t splits = kv_splits.is_none() ? 0 : kv_splits.cast<int64_t>();
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = cross_attention_backward(q, k, v, len, out, lse, grad_out, num_heads, scale, q_key, glob_key, mgr,
+                                         need_grad_q, need_grad_k, need_grad_v, splits);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]));
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("context_lengths"), py::arg("out"), py::arg("lse"),
+        py::arg("grad_out"), py::arg("num_heads"), py::arg("scale"), py::arg("q_key"), py::arg("glob_key"),
+        py::arg("manager"), py::arg("need_grad_q") = true, py::arg("need_grad_k") = true, py::arg("need_grad_v") = true,
+        py::arg("kv_splits") = py::none());
   // local attention over a kernel map on the kernels of csrc/local_attention.hip (strided row views go in without copies)
   m.def("LocalAttentionForwardGPU",
         [](const Tensor &q, const Tensor &k, const Tensor &v, const py::object &rel_pos_bias, int64_t num_heads,

@@ -257,6 +257,8 @@ struct CoordinateMapManager {
   std::map<KeyT, std::pair<Tensor, Tensor>> instance_rows_cache;   // per-instance row lists (seg_ptr, seg_rows)
   // serialized patch attention: (map, patch size, order code) -> {seg_ptr, seg_rows, blk_tab, row_patch}
   std::map<std::tuple<KeyT, int64_t, int>, std::vector<Tensor>> patch_rows_cache;
+  // cross-attention: (instances, tokens, device index) -> {seg_ptr, seg_rows, blk_tab} of a dense context
+  std::map<std::tuple<int64_t, int64_t, int>, std::vector<Tensor>> context_rows_cache;
   std::map<std::pair<KeyT, KeyT>, Tensor> prune_rows;
   std::map<std::pair<KeyT, KeyT>, std::pair<Tensor, Tensor>> stride_maps;
   // arithmetic across maps: ORDERED (key a, key b) -> union key and {u_of_a, u_of_b, a_of_u, b_of_u} (union_arith_maps)
@@ -298,6 +300,10 @@ struct CoordinateMapManager {
   // {seg_ptr, seg_rows, blk_tab, row_patch} of serialized patch attention (me_attn_patch_lists), cached per (map, patch
   // size, order code 0 z / 1 z_trans / 2 hilbert / 3 hilbert_trans): twin of backend._patch_rows
   const std::vector<Tensor> &patch_rows(const KeyT &in_key, int64_t patch_size, int order);
+  // {seg_ptr, seg_rows, blk_tab} of a dense context of n_batch x tokens rows (me_attn_context_lists): cached per
+  // (n_batch, tokens, device) without lengths, built per call with them (int32 [n_batch] on the device): twin of
+  // backend._context_rows
+  std::vector<Tensor> context_rows(int64_t n_batch, int64_t tokens, const c10::Device &dev, const Tensor &lengths);
   std::shared_ptr<KernelMap> kernel_map(const KeyT &in_key, const KeyT &out_key, const ivec &kernel_size,
                                         const ivec &kernel_stride, const ivec &kernel_dilation, int region_type,
                                         bool is_transpose, bool is_pool, const ivec &offsets = ivec());
@@ -395,6 +401,17 @@ std::vector<Tensor> attention_backward(Tensor q, Tensor k, Tensor v, Tensor out,
                                        int64_t num_heads, double scale, CoordinateMapKey *q_key, CoordinateMapKey *kv_key,
                                        CoordinateMapKey *glob_key, CoordinateMapManager *mgr, bool need_grad_q,
                                        bool need_grad_k, bool need_grad_v);
+// cross-attention to a dense context (csrc/attention.hip; twin of backend.CrossAttention{Forward,Backward}GPU);
+// kv_splits 0: ME_AMD_ATTN_KV_SPLITS, else me_attn_kv_splits
+std::pair<Tensor, Tensor> cross_attention_forward(Tensor q, Tensor k, Tensor v, Tensor context_lengths, int64_t num_heads,
+                                                  double scale, CoordinateMapKey *q_key, CoordinateMapKey *glob_key,
+                                                  CoordinateMapManager *mgr);
+std::vector<Tensor> cross_attention_backward(Tensor q, Tensor k, Tensor v, Tensor context_lengths, Tensor out,
+                                             const Tensor &lse, Tensor grad_out, int64_t num_heads, double scale,
+                                             CoordinateMapKey *q_key, CoordinateMapKey *glob_key,
+                                             CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k,
+                                             bool need_grad_v, int64_t kv_splits);
+
 // local attention over a kernel map (csrc/local_attention.hip; twin of backend.LocalAttention{Forward,Backward}GPU)
 std::pair<Tensor, Tensor> local_attention_forward(Tensor q, Tensor k, Tensor v, Tensor rel_pos_bias, int64_t num_heads,
                                                   double scale, const ivec &ks, const ivec &st, const ivec &dl,

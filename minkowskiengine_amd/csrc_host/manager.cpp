@@ -1159,6 +1159,30 @@ const std::vector<Tensor> &CoordinateMapManager::patch_rows(const KeyT &in_key, 
   return patch_rows_cache[ck] = {seg_ptr, seg_rows, blk_tab, row_patch};
 }
 
+std::vector<Tensor> CoordinateMapManager::context_rows(int64_t n_batch, int64_t tokens, const c10::Device &dev,
+                                                       const Tensor &lengths) {
+  check(n_batch >= 0 && tokens >= 1, "a context needs at least one token per instance, got " + std::to_string(tokens));
+  const auto ck = std::make_tuple(n_batch, tokens, (int)dev.index());
+  if (!lengths.defined()) {
+    auto it = context_rows_cache.find(ck);
+    if (it != context_rows_cache.end()) return it->second;
+  } else {
+    check(lengths.is_cuda() && lengths.scalar_type() == at::kInt && lengths.is_contiguous() &&
+              lengths.numel() == n_batch && lengths.device() == dev,
+          "context_lengths must hold one int32 per instance on the device of the features");
+  }
+  const int64_t n = n_batch * tokens;
+  auto i32 = at::TensorOptions().dtype(at::kInt).device(dev);
+  Tensor seg_ptr = at::empty({n_batch + 1}, i32), seg_rows = at::empty({n}, i32);
+  Tensor blk_tab = at::empty({2 * ((n + 63) / 64 + n_batch)}, i32);
+  c10::DeviceGuard guard(dev);
+  me_ok(me_attn_context_lists((int32_t)n_batch, (int32_t)tokens, lengths.defined() ? ptr<int32_t>(lengths) : nullptr,
+                              ptr<int32_t>(seg_ptr), ptr<int32_t>(seg_rows), ptr<int32_t>(blk_tab), stream_of(dev)));
+  std::vector<Tensor> lists{seg_ptr, seg_rows, blk_tab};
+  if (!lengths.defined()) context_rows_cache[ck] = lists;
+  return lists;
+}
+
 // Sides of a hyper-cube map (looked-up map `fine_ts`, iterated map `coarse_ts`) on which a row has at most ONE pair by
 // construction: windows of kernel_size voxels that tile space without overlap (coarse stride = kernel_size x fine stride,
 // no dilation) hold every fine voxel exactly once -> bit 0 (the "in" = fine side).  A single-offset kernel pairs a row
@@ -1385,6 +1409,8 @@ std::vector<Tensor> CoordinateMapManager::device_tensors() {
     collect(out, kv.second.second);
   }
   for (auto &kv : patch_rows_cache)
+    for (auto &t : kv.second) collect(out, t);
+  for (auto &kv : context_rows_cache)
     for (auto &t : kv.second) collect(out, t);
   for (auto &kv : origin_field_rows_cache) collect(out, kv.second);
   for (auto &kv : prune_rows) collect(out, kv.second);

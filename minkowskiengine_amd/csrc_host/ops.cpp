@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdlib>
 #include <mutex>
 #include <stdexcept>
 
@@ -1400,6 +1401,130 @@ std::vector<Tensor> attention_backward(Tensor q, Tensor k, Tensor v, Tensor out,
                            ptr<int32_t>(p.seg_q.first), ptr<int32_t>(p.seg_q.second), ptr<int32_t>(p.seg_kv.first),
                            ptr<int32_t>(p.seg_kv.second), n_q, n_kv, p.n_batch, p.c, p.heads, (float)scale, vptr(grad_q),
                            p.c, vptr(grad_k), p.c, vptr(grad_v), p.c, vptr(ws), ws.numel(), stream_of(dev)));
+  }
+  return {grad_q, grad_k, grad_v};
+}
+
+// ---- cross-attention to a dense context (csrc/attention.hip, ABI 1.20; twin of backend.CrossAttention{Forward,Backward}GPU):
+// q on a map, k / v [B, L, C] or [B * L, C] row views, context row j in the instance with the j-th smallest batch index ------
+struct CrossAttnPrep {
+  int heads, c, n_batch;
+  std::pair<Tensor, Tensor> seg_q;
+  std::vector<Tensor> seg_kv;   // seg_ptr, seg_rows, blk_tab
+  bool with_lengths;
+};
+static CrossAttnPrep cross_attn_prepare(Tensor &q, Tensor &k, Tensor &v, Tensor lengths, int64_t num_heads,
+                                        CoordinateMapKey *q_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+  q = attn_rows("q", q);
+  check((k.dim() == 2 || k.dim() == 3) && v.dim() == k.dim() && k.sizes().slice(0, k.dim() - 1) == v.sizes().slice(0, k.dim() - 1),
+        "k and v must be [B, L, C] or [B * L, C] with the same leading shape");
+  if (!glob_key->key_set) {
+    KeyT ok = mgr->origin();
+    glob_key->set_key(ok.first, ok.second);
+  }
+  const int64_t n_batch = mgr->get(glob_key->get())->n;
+  if (k.dim() == 3) {
+    check(k.size(0) == n_batch, "the context holds " + std::to_string(k.size(0)) + " instances, the coordinate manager " +
+                                    std::to_string(n_batch));
+    k = k.reshape({-1, k.size(2)});
+    v = v.reshape({-1, v.size(2)});
+  }
+  k = attn_rows("k", k, &q);
+  v = attn_rows("v", v, &q);
+  const KeyT &qk = q_key->get();
+  check(mgr->exists(qk), "coordinate map not found");
+  check(q.size(0) == mgr->get(qk)->n, "Invalid q size");
+  check(n_batch > 0 && k.size(0) % n_batch == 0 && k.size(0) >= n_batch,
+        "the context rows " + std::to_string(k.size(0)) + " must be a positive multiple of the instances " +
+            std::to_string(n_batch));
+  const int64_t tokens = k.size(0) / n_batch, c = q.size(1);
+  check(num_heads > 0 && c % num_heads == 0, "the channel count " + std::to_string(c) +
+                                                 " must be a multiple of num_heads " + std::to_string(num_heads));
+  if (lengths.defined()) {
+    check(lengths.dim() == 1 && lengths.numel() == n_batch && at::isIntegralType(lengths.scalar_type(), false),
+          "context_lengths must be an integer tensor with one length per instance");
+    lengths = lengths.to(q.device(), at::kInt).contiguous();
+  }
+  CrossAttnPrep p;
+  p.heads = (int)num_heads;
+  p.c = (int)c;
+  p.n_batch = (int)n_batch;
+  p.seg_q = mgr->instance_rows(qk);
+  p.seg_kv = mgr->context_rows(n_batch, tokens, q.device(), lengths);
+  p.with_lengths = lengths.defined();
+  return p;
+}
+
+std::pair<Tensor, Tensor> cross_attention_forward(Tensor q, Tensor k, Tensor v, Tensor context_lengths, int64_t num_heads,
+                                                  double scale, CoordinateMapKey *q_key, CoordinateMapKey *glob_key,
+                                                  CoordinateMapManager *mgr) {
+  const CrossAttnPrep p = cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key, mgr);
+  const c10::Device dev = q.device();
+  const bool f64 = q.scalar_type() == at::kDouble;
+  const int64_t n_q = q.size(0), n_kv = k.size(0);
+  Tensor out = at::empty({n_q, p.c}, q.options());
+  Tensor lse = at::empty({n_q, p.heads}, at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev));
+  const int32_t *spq = ptr<int32_t>(p.seg_q.first), *srq = ptr<int32_t>(p.seg_q.second);
+  const int32_t *spk = ptr<int32_t>(p.seg_kv[0]), *srk = ptr<int32_t>(p.seg_kv[1]), *tab = ptr<int32_t>(p.seg_kv[2]);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_attn_forward_tab_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), attn_stride(q), attn_stride(k),
+                                  attn_stride(v), spq, srq, spk, srk, nullptr, tab, n_q, n_kv, p.n_batch, p.c, p.heads,
+                                  scale, ptr<double>(out), p.c, ptr<double>(lse), stream_of(dev)));
+  } else {
+    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+    me_ok(me_attn_forward_tab(q.data_ptr(), k.data_ptr(), v.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v),
+                              spq, srq, spk, srk, nullptr, tab, n_q, n_kv, p.n_batch, p.c, p.heads, (float)scale,
+                              out.data_ptr(), p.c, ptr<float>(lse), stream_of(dev)));
+  }
+  return {out, lse};
+}
+
+std::vector<Tensor> cross_attention_backward(Tensor q, Tensor k, Tensor v, Tensor context_lengths, Tensor out,
+                                             const Tensor &lse, Tensor grad_out, int64_t num_heads, double scale,
+                                             CoordinateMapKey *q_key, CoordinateMapKey *glob_key,
+                                             CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k,
+                                             bool need_grad_v, int64_t kv_splits) {
+  const CrossAttnPrep p = cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key, mgr);
+  out = attn_rows("out", out, &q);
+  grad_out = attn_rows("grad_out", grad_out.to(q.scalar_type()));
+  check(out.sizes() == q.sizes() && grad_out.sizes() == q.sizes(), "out and grad_out must have the shape of q");
+  const c10::Device dev = q.device();
+  const bool f64 = q.scalar_type() == at::kDouble;
+  check(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == (f64 ? at::kDouble : at::kFloat) && lse.dim() == 2 &&
+            lse.size(0) == q.size(0) && lse.size(1) == p.heads,
+        "lse must be the contiguous [n_q, heads] statistics of the forward pass");
+  const int64_t n_q = q.size(0), n_kv = k.size(0);
+  if (kv_splits == 0) {   // the argument, else the environment, else the library's policy
+    const char *env = std::getenv("ME_AMD_ATTN_KV_SPLITS");
+    if (env && *env) kv_splits = std::atoll(env);
+  }
+  if (kv_splits == 0) kv_splits = me_attn_kv_splits(n_q, n_kv, p.n_batch, p.c, p.heads);
+  if (!(need_grad_q || need_grad_k || need_grad_v)) return {Tensor(), Tensor(), Tensor()};
+  // the key-stationary kernel (one slice, float64) writes the listed rows only: the others are zeroed here
+  const bool zero_kv = p.with_lengths && (kv_splits == 1 || f64);
+  auto new_kv = [&]() { return zero_kv ? at::zeros({n_kv, p.c}, q.options()) : at::empty({n_kv, p.c}, q.options()); };
+  Tensor grad_q = need_grad_q ? at::empty({n_q, p.c}, q.options()) : Tensor();
+  Tensor grad_k = need_grad_k ? new_kv() : Tensor();
+  Tensor grad_v = need_grad_v ? new_kv() : Tensor();
+  const int32_t *spq = ptr<int32_t>(p.seg_q.first), *srq = ptr<int32_t>(p.seg_q.second);
+  const int32_t *spk = ptr<int32_t>(p.seg_kv[0]), *srk = ptr<int32_t>(p.seg_kv[1]), *tab = ptr<int32_t>(p.seg_kv[2]);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_attn_backward_split_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), ptr<double>(out), ptr<double>(lse),
+                                     ptr<double>(grad_out), attn_stride(q), attn_stride(k), attn_stride(v),
+                                     attn_stride(out), attn_stride(grad_out), spq, srq, spk, srk, nullptr, tab, n_q, n_kv,
+                                     p.n_batch, p.c, p.heads, scale, ptr<double>(grad_q), p.c, ptr<double>(grad_k), p.c,
+                                     ptr<double>(grad_v), p.c, (int32_t)kv_splits, stream_of(dev)));
+  } else {
+    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+    Tensor ws = workspace(me_attn_split_workspace_bytes(n_q, n_kv, p.n_batch, p.c, p.heads,
+                                                        (int32_t)std::max<int64_t>(kv_splits, 1)), dev);
+    me_ok(me_attn_backward_split(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ptr<float>(lse),
+                                 grad_out.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out),
+                                 attn_stride(grad_out), spq, srq, spk, srk, nullptr, tab, n_q, n_kv, p.n_batch, p.c, p.heads,
+                                 (float)scale, vptr(grad_q), p.c, vptr(grad_k), p.c, vptr(grad_v), p.c, vptr(ws),
+                                 ws.numel(), (int32_t)kv_splits, stream_of(dev)));
   }
   return {grad_q, grad_k, grad_v};
 }

@@ -1262,7 +1262,8 @@ int me_local_attn_backward_f64(const double *q_dev, const double *k_dev, const d
  *
  * me_coords_serial_keys: keys[i] = ((uint32) coords[i, 0] << D * depth) | code(x), D = ncol - 1,
  *   x_a = (coords[i, 1 + a] - bbox_min[a]) / tensor_stride[a] (exact on a map of that stride; x_a < 2^depth, so depth is
- *   the bit count of the largest x_a of the map; tensor_stride and bbox_min: D host ints).  order:
+ *   the bit count of the largest x_a of the map; tensor_stride and bbox_min: D host ints; the difference is taken in
+ *   uint32, so it is exact for every extent of an int32 map, 2^31 and more included).  order:
  *     0  z              bit l of axis a at code bit l * D + (D - 1 - a): axis 0 is the most significant of a level
  *     2  hilbert        Skilling's AxesToTranspose (Programming the Hilbert curve, 2004) on x with depth bits, the
  *                       transposed axes interleaved by the rule of z

@@ -51,8 +51,10 @@ __global__ __launch_bounds__(256) void k_serial_keys(const int32_t *__restrict__
   if (i >= n) return;
   const int32_t *c = coords + i * NCOL;
   uint32_t x[D];
+  // the difference in uint32: exact modulo 2^32, so exact for every extent an int32 map can have (an int32 difference
+  // wraps from an extent of 2^31 on, and the signed quotient is then wrong for a stride that is no power of two)
 #pragma unroll
-  for (int a = 0; a < D; ++a) x[a] = (uint32_t)((c[1 + a] - g.bbox_min[a]) / g.stride[a]);
+  for (int a = 0; a < D; ++a) x[a] = ((uint32_t)c[1 + a] - (uint32_t)g.bbox_min[a]) / (uint32_t)g.stride[a];
   if constexpr (D >= 2) {
     if (order & 1) { const uint32_t t = x[0]; x[0] = x[1]; x[1] = t; }
   }

@@ -15,6 +15,7 @@ import torch
 import minkowskiengine_amd as ME
 from minkowskiengine_amd import host as _host
 from test_gpu_attention_kernels import BK, FACTOR, draw, reference, torch_attention, within_bound  # noqa: F401
+from test_gpu_serialized_attention_kernels import lists_from_row_patch
 from test_serialized_attention_cpu import ORDERS, row_patches
 
 pytestmark = pytest.mark.gpu
@@ -163,6 +164,86 @@ def test_patches_stay_within_the_bound(device, host_layer, case, d, order, dtype
     q, k, v, dout = (draw(n, c, dtype, device, 10 * d + s) for s in range(4))
     r = run(x, q, k, v, dout, heads, P, order)
     within_bound(r, q, k, v, dout, patch, patch, heads, what=f"serial {case} d={d} {order} {dtype} {host_layer}")
+
+
+# ---- scenes beyond one sort tile's regime: deep keys, sparse and missing batch indices, long patches ----------------------------
+def scene_of(coords, device, stride=1):
+    """a sparse tensor on the given unique int rows [n, 1 + D]"""
+    coords = torch.as_tensor(np.asarray(coords)).int()
+    x = ME.SparseTensor(torch.zeros(coords.shape[0], 1), coordinates=coords, tensor_stride=stride, device=device)
+    assert x.F.shape[0] == coords.shape[0]
+    return x
+
+
+def check_lists(x, patch_size, order, n_batch):
+    """all four outputs of patch_rows against the yardstick on the rows of the map -> the patch of every row (int64)"""
+    seg_ptr, seg_rows, blk_tab, row_patch = (t.cpu().numpy() for t in lists(x, patch_size, order))
+    n = x.F.shape[0]
+    want = row_patches(x.C.cpu().numpy(), [int(t) for t in x.tensor_stride], order, patch_size)
+    assert np.array_equal(row_patch, want), f"{int((row_patch != want).sum())} of {n} rows in another patch"
+    want_lists = lists_from_row_patch(want, -(-n // patch_size) + n_batch)
+    assert np.array_equal(seg_ptr, want_lists["seg_ptr"]) and np.array_equal(seg_rows, want_lists["seg_rows"])
+    assert np.array_equal(blk_tab, want_lists["blk_tab"])
+    return torch.from_numpy(want).to(x.F.device)
+
+
+def step_within_bound(x, patch, patch_size, order, d, dtype, seed, what):
+    heads = 2
+    n, c = x.F.shape[0], heads * d
+    q, k, v, dout = (draw(n, c, dtype, x.F.device, seed + s) for s in range(4))
+    r = run(x, q, k, v, dout, heads, patch_size, order)
+    within_bound(r, q, k, v, dout, patch, patch, heads, what=what)
+
+
+def test_a_wide_scene(device, host_layer):
+    """600 voxels in two instances spread over [0, 2^17) in x and y and [0, 64) in z: depth 17, 51 code bits, seven radix
+    passes; the lists against the yardstick and one bf16 step within the bound"""
+    rng = np.random.default_rng(17)
+    rows = []
+    for b, m in enumerate((330, 270)):
+        pts = np.concatenate([rng.integers(0, 1 << 17, size=(2 * m, 2)), rng.integers(0, 64, size=(2 * m, 1))], 1)
+        pts = np.unique(pts, axis=0)
+        pts = pts[rng.permutation(pts.shape[0])[:m]]
+        if b == 0:
+            pts[0], pts[1] = (0, 0, 0), ((1 << 17) - 1, (1 << 17) - 1, 63)
+        rows.append(np.concatenate([np.full((m, 1), b), pts], 1))
+    coords = np.concatenate(rows)
+    x = scene_of(coords[rng.permutation(600)], device)
+    patch = check_lists(x, 48, "hilbert", 2)
+    step_within_bound(x, patch, 48, "hilbert", 64, torch.bfloat16, 170, f"serial wide scene bf16 {host_layer}")
+
+
+def test_batch_indices_with_a_gap(device, host_layer):
+    """instances with the batch indices 0, 2 and 5: the instances of the lists are the ranks of the indices"""
+    y = make_scene([70, 40, 90], device, seed=25)
+    coords = y.C.cpu().clone()
+    coords[:, 0] = torch.tensor([0, 2, 5])[coords[:, 0].long()]
+    x = scene_of(coords, device)
+    assert sorted(set(x.C[:, 0].tolist())) == [0, 2, 5]
+    patch = check_lists(x, 32, "z_trans", 3)
+    assert torch.bincount(patch).tolist() == [24, 23, 23, 20, 20, 30, 30, 30]
+    step_within_bound(x, patch, 32, "z_trans", 32, torch.float32, 250, f"serial batch gap fp32 {host_layer}")
+
+
+def test_an_instance_that_vanished(device, host_layer):
+    """three instances, every row of instance 1 pruned away: the origin still has three instances, the map two, so n_batch
+    exceeds the number of instances the sorted keys show and the last one is empty"""
+    x = make_scene([80, 50, 60], device, seed=26)
+    y = ME.MinkowskiPruning()(x, x.C[:, 0] != 1)
+    assert y.F.shape[0] == 140 and sorted(set(y.C[:, 0].tolist())) == [0, 2]
+    patch = check_lists(y, 32, "hilbert", 3)
+    assert torch.bincount(patch).tolist() == [27, 27, 26, 30, 30]
+    step_within_bound(y, patch, 32, "hilbert", 32, torch.float32, 260, f"serial vanished instance fp32 {host_layer}")
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=str)
+def test_long_patches(device, host_layer, dtype):
+    """instances of 700 and 301 rows, P = 300: patches of 233 / 234 and 150 / 151 rows, up to four 64-row blocks with the
+    last one partial"""
+    x = make_scene([700, 301], device, seed=27)
+    patch = lists(x, 300, "hilbert")[3].long()
+    assert sorted(torch.bincount(patch).tolist()) == [150, 151, 233, 233, 234]
+    step_within_bound(x, patch, 300, "hilbert", 64, dtype, 270, f"serial long patches {dtype} {host_layer}")
 
 
 # ---- exact ---------------------------------------------------------------------------------------------------------------------

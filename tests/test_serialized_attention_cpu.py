@@ -123,6 +123,84 @@ def test_consecutive_hilbert_cells_are_neighbours(side, D, order):
     assert (steps == 1).all()
 
 
+def _deinterleave(code, D, depth):
+    """the inverse of _interleave: code bit l * D + (D - 1 - a) is bit l of axis a"""
+    x = [0] * D
+    for l in range(depth):
+        for a in range(D):
+            x[a] |= ((code >> (l * D + (D - 1 - a))) & 1) << l
+    return x
+
+
+def _transpose_to_axes(x, depth):
+    """J. Skilling, Programming the Hilbert curve (2004): TransposeToAxes, the inverse of AxesToTranspose.  Its loops run
+    upwards from Q = 2 and it decodes the Gray code by one shift: it shares neither loop bounds nor the order of the steps
+    with _axes_to_transpose"""
+    x, n = [int(v) for v in x], len(x)
+    if depth == 0:
+        return x
+    top = 1 << depth
+    t = x[n - 1] >> 1                  # Gray decode
+    for i in range(n - 1, 0, -1):
+        x[i] ^= x[i - 1]
+    x[0] ^= t
+    q = 2
+    while q != top:                    # undo the excess work
+        p = q - 1
+        for i in range(n - 1, -1, -1):
+            if x[i] & q:
+                x[0] ^= p
+            else:
+                t = (x[0] ^ x[i]) & p
+                x[0] ^= t
+                x[i] ^= t
+        q <<= 1
+    return x
+
+
+def serial_decode(code, D, depth, order):
+    """the cell of a code: the inverse of serial_code"""
+    x = _deinterleave(int(code), D, depth)
+    if order.startswith("hilbert"):
+        x = _transpose_to_axes(x, depth)
+    if order.endswith("_trans") and D >= 2:
+        x[0], x[1] = x[1], x[0]
+    return x
+
+
+@pytest.mark.parametrize("order", ["hilbert", "hilbert_trans"])
+@pytest.mark.parametrize("D", [2, 3, 4])
+def test_deep_hilbert_codes_decode_to_neighbouring_cells(D, order):
+    """depth = min(31, 63 // D): 62, 63 and 60 code bits, where the GPU keys are compared with serial_code.  For 2000 random
+    codes h: serial_code(decode(h)) == h, and decode(h) and decode(h + 1) are one unit step apart on one axis — checked
+    through Skilling's inverse transform, so independent of the forward transform's loop bounds.  hilbert_trans decodes to
+    the cell of hilbert with the axes 0 and 1 exchanged, and has the same two properties"""
+    import random
+    depth = min(31, 63 // D)
+    rng = random.Random(1000 * D + len(order))
+    top = 1 << (D * depth)
+    codes = [0, top - 2, (top >> 1) - 1] + [rng.randrange(top - 1) for _ in range(2000)]
+    for h in codes:
+        a, b = serial_decode(h, D, depth, order), serial_decode(h + 1, D, depth, order)
+        assert all(0 <= v < (1 << depth) for v in a)
+        assert serial_code(a, depth, order) == h and serial_code(b, depth, order) == h + 1
+        assert sorted(abs(u - v) for u, v in zip(a, b)) == [0] * (D - 1) + [1], (h, a, b)
+        if order == "hilbert_trans":
+            plain = serial_decode(h, D, depth, "hilbert")
+            assert a == [plain[1], plain[0]] + plain[2:]
+
+
+@pytest.mark.parametrize("order", ["z", "z_trans"])
+def test_deep_z_codes_round_trip(order):
+    import random
+    rng = random.Random(7)
+    for D in (1, 2, 3, 4, 7):
+        depth = min(31, 63 // D)
+        for _ in range(300):
+            h = rng.randrange(1 << (D * depth))
+            assert serial_code(serial_decode(h, D, depth, order), depth, order) == h
+
+
 def test_z_is_explicit_bit_interleaving():
     for x, y, z in [(0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 0, 1), (5, 3, 6), (7, 7, 7)]:
         want = 0

@@ -120,6 +120,47 @@ class Guarded:
         return self.bits.clone().view(dtype).reshape(shape)
 
 
+class GuardedBytes:
+    """The byte-typed sibling of Guarded, for 8-byte arrays, byte flags and workspaces: `nbytes` bytes in the middle of a
+    position-dependent byte pattern (`pad` bytes on either side; the start keeps the allocation's alignment).  fill(word) repeats
+    a 32-bit word over the inside, holds(word) says whether it still does, view() reinterprets the inside."""
+
+    def __init__(self, nbytes, device, pad=GUARD_PAD):
+        assert pad % 256 == 0
+        band = ((torch.arange(pad, device=device) % 251) + 1).to(torch.uint8)
+        self.big = torch.zeros(2 * pad + nbytes, dtype=torch.uint8, device=device)
+        self.big[:pad] = band
+        self.big[pad + nbytes:] = band.flip(0)
+        self.bytes = self.big[pad:pad + nbytes]
+        self.before, self.after = self.big[:pad].clone(), self.big[pad + nbytes:].clone()
+        self.pad, self.n = pad, nbytes
+        assert self.bytes.data_ptr() % 16 == 0
+
+    def ptr(self):
+        return self.bytes.data_ptr()
+
+    def _pattern(self, word):
+        return torch.tensor(list(int(word).to_bytes(4, "little")), dtype=torch.uint8, device=self.big.device)
+
+    def fill(self, word):
+        whole = self.n // 4 * 4
+        self.bytes[:whole].view(torch.int32).fill_(int(word) - (1 << 32) if int(word) >= 1 << 31 else int(word))
+        if whole < self.n:
+            self.bytes[whole:] = self._pattern(word)[:self.n - whole]
+
+    def holds(self, word):
+        whole = self.n // 4 * 4
+        w = int(word) - (1 << 32) if int(word) >= 1 << 31 else int(word)
+        return bool((self.bytes[:whole].view(torch.int32) == w).all()) and \
+            torch.equal(self.bytes[whole:], self._pattern(word)[:self.n - whole])
+
+    def intact(self):
+        return torch.equal(self.big[:self.pad], self.before) and torch.equal(self.big[self.pad + self.n:], self.after)
+
+    def view(self, dtype, shape=(-1,)):
+        return self.bytes.view(dtype).reshape(shape)
+
+
 def exact_weights_bf16(rng, shape):
     """fp32 weights that round (RNE) to multiples of 2^-6 in [-2, 2]: such a value plus a perturbation below a quarter of
     a bf16 ulp, and a few exact ties (value + half an ulp away from zero, which round back to the even value).

@@ -3609,6 +3609,75 @@ def _attn_stride(t):
     return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
 
 
+def _attn_backward_operands(q, out, grad_out, lse, lse_shape, lse_name):
+    """-> (out, grad_out) as row operands of q's dtype and shape, after checking the forward statistics lse"""
+    out = _attn_rows("out", out, q)
+    grad_out = _attn_rows("grad_out", grad_out.to(q.dtype))
+    _check(tuple(out.shape) == tuple(q.shape) and tuple(grad_out.shape) == tuple(q.shape),
+           "out and grad_out must have the shape of q")
+    _check(lse.is_cuda and lse.is_contiguous() and lse.dtype == _inorm_param_dtype(q) and
+           tuple(lse.shape) == tuple(lse_shape), "lse must be the contiguous", lse_name, "statistics of the forward pass")
+    return out, grad_out
+
+
+def _list_attn_forward(name, q, k, v, lists_q, lists_kv, n_seg, heads, c, scale):
+    """-> (out, lse) of attention on row lists (me_attn_forward_tab): a list is (seg_ptr, seg_rows, blk_tab or None), a
+    query row attends to the key rows of its own segment; `name` is the _timed label."""
+    lib = _lib.load()
+    dev = q.device
+    n_q, n_kv = int(q.shape[0]), int(k.shape[0])
+    out = torch.empty((n_q, c), dtype=q.dtype, device=dev)
+    lse = torch.empty((n_q, heads), dtype=_inorm_param_dtype(q), device=dev)
+    tail = (_attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(lists_q[0]), _ptr(lists_q[1]), _ptr(lists_kv[0]),
+            _ptr(lists_kv[1]), _ptr(lists_q[2]), _ptr(lists_kv[2]), n_q, n_kv, n_seg, c, heads, float(scale), _ptr(out), c,
+            _ptr(lse), _stream(dev))
+    with _on(dev):
+        if q.dtype == torch.float64:
+            _lib.check(lib.me_attn_forward_tab_f64(_ptr(q), _ptr(k), _ptr(v), *tail))
+        else:
+            bf = 1 if q.dtype == torch.bfloat16 else 0
+            _timed(name, dev, lambda: _lib.check(lib.me_attn_forward_tab(_ptr(q), _ptr(k), _ptr(v), bf, *tail)))
+    return out, lse
+
+
+def _list_attn_backward(name, q, k, v, out, lse, grad_out, lists_q, lists_kv, n_seg, heads, c, scale, need_grad_q,
+                        need_grad_k, need_grad_v, kv_splits=None, zero_unlisted=False):
+    """-> (grad_q | None, grad_k | None, grad_v | None) of _list_attn_forward; a gradient that is not requested is neither
+    allocated nor computed.  kv_splits None: me_attn_backward_tab; else the query slices of me_attn_backward_split.
+    zero_unlisted: kv rows may sit in no segment; where the dK / dV pass writes the listed rows only (one slice, float64)
+    grad_k / grad_v start as zeros."""
+    if not (need_grad_q or need_grad_k or need_grad_v):
+        return None, None, None
+    lib = _lib.load()
+    dev = q.device
+    n_q, n_kv = int(q.shape[0]), int(k.shape[0])
+    f64 = q.dtype == torch.float64
+    new_kv = torch.zeros if zero_unlisted and (kv_splits == 1 or f64) else torch.empty
+    grad_q = torch.empty((n_q, c), dtype=q.dtype, device=dev) if need_grad_q else None
+    grad_k = new_kv((n_kv, c), dtype=q.dtype, device=dev) if need_grad_k else None
+    grad_v = new_kv((n_kv, c), dtype=q.dtype, device=dev) if need_grad_v else None
+    head = (_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out))
+    tail = (_attn_stride(q), _attn_stride(k), _attn_stride(v), _attn_stride(out), _attn_stride(grad_out),
+            _ptr(lists_q[0]), _ptr(lists_q[1]), _ptr(lists_kv[0]), _ptr(lists_kv[1]), _ptr(lists_q[2]), _ptr(lists_kv[2]),
+            n_q, n_kv, n_seg, c, heads, float(scale), _ptr(grad_q), c, _ptr(grad_k), c, _ptr(grad_v), c)
+    with _on(dev):
+        if f64 and kv_splits is None:
+            _lib.check(lib.me_attn_backward_tab_f64(*head, *tail, _stream(dev)))
+        elif f64:
+            _lib.check(lib.me_attn_backward_split_f64(*head, *tail, kv_splits, _stream(dev)))
+        else:
+            bf = 1 if q.dtype == torch.bfloat16 else 0
+            if kv_splits is None:
+                ws = _workspace(int(lib.me_attn_workspace_bytes(n_q, n_kv, n_seg, heads)), dev)
+                _timed(name, dev, lambda: _lib.check(lib.me_attn_backward_tab(
+                    *head, bf, *tail, _ptr(ws), ws.numel(), _stream(dev))))
+            else:
+                ws = _workspace(int(lib.me_attn_split_workspace_bytes(n_q, n_kv, n_seg, c, heads, max(kv_splits, 1))), dev)
+                _timed(name, dev, lambda: _lib.check(lib.me_attn_backward_split(
+                    *head, bf, *tail, _ptr(ws), ws.numel(), kv_splits, _stream(dev))))
+    return grad_q, grad_k, grad_v
+
+
 def _attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, manager):
     q = _attn_rows("q", q)
     k = _attn_rows("k", k, q)
@@ -3621,8 +3690,8 @@ def _attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, manager):
     _check(heads > 0 and c % heads == 0, "the channel count", c, "must be a multiple of num_heads", heads)
     if not glob_key.is_key_set():
         glob_key.set_key(manager.origin().get_key())
-    seg_q = manager._instance_rows(q_key)
-    seg_kv = manager._instance_rows(kv_key)
+    seg_q = manager._instance_rows(q_key) + (None,)     # no block tables: the workgroups walk seg_ptr
+    seg_kv = manager._instance_rows(kv_key) + (None,)
     return q, k, v, heads, c, seg_q, seg_kv, manager.size(glob_key)
 
 
@@ -3631,23 +3700,7 @@ def AttentionForwardGPU(q, k, v, num_heads, scale, q_key, kv_key, glob_key, mana
     kv_key with the batch index of row i of q_key; lse = log sum_j exp(.) in fp32 (float64 for float64 features).  A query
     whose instance has no key row: a zero row and lse = -inf."""
     q, k, v, heads, c, seg_q, seg_kv, n_batch = _attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, manager)
-    lib = _lib.load()
-    dev = q.device
-    n_q, n_kv = int(q.shape[0]), int(k.shape[0])
-    out = torch.empty((n_q, c), dtype=q.dtype, device=dev)
-    lse = torch.empty((n_q, heads), dtype=_inorm_param_dtype(q), device=dev)
-    with _on(dev):
-        if q.dtype == torch.float64:
-            _lib.check(lib.me_attn_forward_f64(_ptr(q), _ptr(k), _ptr(v), _attn_stride(q), _attn_stride(k), _attn_stride(v),
-                                               _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]), _ptr(seg_kv[1]), n_q, n_kv,
-                                               n_batch, c, heads, float(scale), _ptr(out), c, _ptr(lse), _stream(dev)))
-        else:
-            bf = 1 if q.dtype == torch.bfloat16 else 0
-            _timed("attn_forward", dev, lambda: _lib.check(lib.me_attn_forward(
-                _ptr(q), _ptr(k), _ptr(v), bf, _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(seg_q[0]),
-                _ptr(seg_q[1]), _ptr(seg_kv[0]), _ptr(seg_kv[1]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(out), c,
-                _ptr(lse), _stream(dev))))
-    return out, lse
+    return _list_attn_forward("attn_forward", q, k, v, seg_q, seg_kv, n_batch, heads, c, scale)
 
 
 def AttentionBackwardGPU(q, k, v, out, lse, grad_out, num_heads, scale, q_key, kv_key, glob_key, manager,
@@ -3655,36 +3708,9 @@ def AttentionBackwardGPU(q, k, v, out, lse, grad_out, num_heads, scale, q_key, k
     """-> (grad_q | None, grad_k | None, grad_v | None), contiguous, from out and lse of the forward pass.  A gradient that
     is not requested is not computed: no dK / dV launch when neither is wanted, no dQ launch when grad_q is not."""
     q, k, v, heads, c, seg_q, seg_kv, n_batch = _attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, manager)
-    out = _attn_rows("out", out, q)
-    grad_out = _attn_rows("grad_out", grad_out.to(q.dtype))
-    _check(tuple(out.shape) == tuple(q.shape) and tuple(grad_out.shape) == tuple(q.shape),
-           "out and grad_out must have the shape of q")
-    _check(lse.is_cuda and lse.is_contiguous() and lse.dtype == _inorm_param_dtype(q) and
-           tuple(lse.shape) == (q.shape[0], heads), "lse must be the contiguous [n_q, heads] statistics of the forward pass")
-    lib = _lib.load()
-    dev = q.device
-    n_q, n_kv = int(q.shape[0]), int(k.shape[0])
-    grad_q = torch.empty((n_q, c), dtype=q.dtype, device=dev) if need_grad_q else None
-    grad_k = torch.empty((n_kv, c), dtype=q.dtype, device=dev) if need_grad_k else None
-    grad_v = torch.empty((n_kv, c), dtype=q.dtype, device=dev) if need_grad_v else None
-    if not (need_grad_q or need_grad_k or need_grad_v):
-        return None, None, None
-    with _on(dev):
-        if q.dtype == torch.float64:
-            _lib.check(lib.me_attn_backward_f64(
-                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), _attn_stride(q), _attn_stride(k),
-                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]),
-                _ptr(seg_kv[1]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(grad_q), c, _ptr(grad_k), c, _ptr(grad_v),
-                c, _stream(dev)))
-        else:
-            bf = 1 if q.dtype == torch.bfloat16 else 0
-            ws = _workspace(int(lib.me_attn_workspace_bytes(n_q, n_kv, n_batch, heads)), dev)
-            _timed("attn_backward", dev, lambda: _lib.check(lib.me_attn_backward(
-                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), bf, _attn_stride(q), _attn_stride(k),
-                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]),
-                _ptr(seg_kv[1]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(grad_q), c, _ptr(grad_k), c, _ptr(grad_v),
-                c, _ptr(ws), ws.numel(), _stream(dev))))
-    return grad_q, grad_k, grad_v
+    out, grad_out = _attn_backward_operands(q, out, grad_out, lse, (q.shape[0], heads), "[n_q, heads]")
+    return _list_attn_backward("attn_backward", q, k, v, out, lse, grad_out, seg_q, seg_kv, n_batch, heads, c, scale,
+                               need_grad_q, need_grad_k, need_grad_v)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -3724,7 +3750,7 @@ def _cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key, ma
                context_lengths.numel() == n_batch and not context_lengths.is_floating_point(),
                "context_lengths must be an integer tensor with one length per instance")
         context_lengths = context_lengths.to(device=q.device, dtype=torch.int32).contiguous()
-    seg_q = manager._instance_rows(q_key)
+    seg_q = manager._instance_rows(q_key) + (None,)
     seg_kv = manager._context_rows(n_batch, tokens, q.device, context_lengths)
     return q, k, v, heads, c, seg_q, seg_kv, n_batch
 
@@ -3735,24 +3761,7 @@ def CrossAttentionForwardGPU(q, k, v, context_lengths, num_heads, scale, q_key, 
     Tokens beyond the length are not read as values.  An instance of length 0: zero rows and lse = -inf."""
     q, k, v, heads, c, seg_q, seg_kv, n_batch = _cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key,
                                                                     manager)
-    lib = _lib.load()
-    dev = q.device
-    n_q, n_kv = int(q.shape[0]), int(k.shape[0])
-    out = torch.empty((n_q, c), dtype=q.dtype, device=dev)
-    lse = torch.empty((n_q, heads), dtype=_inorm_param_dtype(q), device=dev)
-    with _on(dev):
-        if q.dtype == torch.float64:
-            _lib.check(lib.me_attn_forward_tab_f64(
-                _ptr(q), _ptr(k), _ptr(v), _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(seg_q[0]), _ptr(seg_q[1]),
-                _ptr(seg_kv[0]), _ptr(seg_kv[1]), None, _ptr(seg_kv[2]), n_q, n_kv, n_batch, c, heads, float(scale),
-                _ptr(out), c, _ptr(lse), _stream(dev)))
-        else:
-            bf = 1 if q.dtype == torch.bfloat16 else 0
-            _timed("cross_attn_forward", dev, lambda: _lib.check(lib.me_attn_forward_tab(
-                _ptr(q), _ptr(k), _ptr(v), bf, _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(seg_q[0]),
-                _ptr(seg_q[1]), _ptr(seg_kv[0]), _ptr(seg_kv[1]), None, _ptr(seg_kv[2]), n_q, n_kv, n_batch, c, heads,
-                float(scale), _ptr(out), c, _ptr(lse), _stream(dev))))
-    return out, lse
+    return _list_attn_forward("cross_attn_forward", q, k, v, seg_q, seg_kv, n_batch, heads, c, scale)
 
 
 def CrossAttentionBackwardGPU(q, k, v, context_lengths, out, lse, grad_out, num_heads, scale, q_key, glob_key, manager,
@@ -3762,40 +3771,11 @@ def CrossAttentionBackwardGPU(q, k, v, context_lengths, out, lse, grad_out, num_
     me_attn_kv_splits).  Tokens beyond an instance's length get exactly zero grad_k / grad_v."""
     q, k, v, heads, c, seg_q, seg_kv, n_batch = _cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key,
                                                                     manager)
-    out = _attn_rows("out", out, q)
-    grad_out = _attn_rows("grad_out", grad_out.to(q.dtype))
-    _check(tuple(out.shape) == tuple(q.shape) and tuple(grad_out.shape) == tuple(q.shape),
-           "out and grad_out must have the shape of q")
-    _check(lse.is_cuda and lse.is_contiguous() and lse.dtype == _inorm_param_dtype(q) and
-           tuple(lse.shape) == (q.shape[0], heads), "lse must be the contiguous [n_q, heads] statistics of the forward pass")
-    lib = _lib.load()
-    dev = q.device
-    n_q, n_kv = int(q.shape[0]), int(k.shape[0])
-    f64 = q.dtype == torch.float64
-    splits = _cross_attn_splits(lib, kv_splits, n_q, n_kv, n_batch, c, heads)
-    if not (need_grad_q or need_grad_k or need_grad_v):
-        return None, None, None
-    # the key-stationary kernel (one slice, float64) writes the listed rows only: the others are zeroed here
-    new_kv = torch.zeros if context_lengths is not None and (splits == 1 or f64) else torch.empty
-    grad_q = torch.empty((n_q, c), dtype=q.dtype, device=dev) if need_grad_q else None
-    grad_k = new_kv((n_kv, c), dtype=q.dtype, device=dev) if need_grad_k else None
-    grad_v = new_kv((n_kv, c), dtype=q.dtype, device=dev) if need_grad_v else None
-    with _on(dev):
-        if f64:
-            _lib.check(lib.me_attn_backward_split_f64(
-                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), _attn_stride(q), _attn_stride(k),
-                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]),
-                _ptr(seg_kv[1]), None, _ptr(seg_kv[2]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(grad_q), c,
-                _ptr(grad_k), c, _ptr(grad_v), c, splits, _stream(dev)))
-        else:
-            bf = 1 if q.dtype == torch.bfloat16 else 0
-            ws = _workspace(int(lib.me_attn_split_workspace_bytes(n_q, n_kv, n_batch, c, heads, max(splits, 1))), dev)
-            _timed("cross_attn_backward", dev, lambda: _lib.check(lib.me_attn_backward_split(
-                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), bf, _attn_stride(q), _attn_stride(k),
-                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_q[0]), _ptr(seg_q[1]), _ptr(seg_kv[0]),
-                _ptr(seg_kv[1]), None, _ptr(seg_kv[2]), n_q, n_kv, n_batch, c, heads, float(scale), _ptr(grad_q), c,
-                _ptr(grad_k), c, _ptr(grad_v), c, _ptr(ws), ws.numel(), splits, _stream(dev))))
-    return grad_q, grad_k, grad_v
+    out, grad_out = _attn_backward_operands(q, out, grad_out, lse, (q.shape[0], heads), "[n_q, heads]")
+    splits = _cross_attn_splits(_lib.load(), kv_splits, int(q.shape[0]), int(k.shape[0]), n_batch, c, heads)
+    return _list_attn_backward("cross_attn_backward", q, k, v, out, lse, grad_out, seg_q, seg_kv, n_batch, heads, c, scale,
+                               need_grad_q, need_grad_k, need_grad_v, kv_splits=splits,
+                               zero_unlisted=context_lengths is not None)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -3858,12 +3838,7 @@ def LocalAttentionBackwardGPU(q, k, v, rel_pos_bias, out, lse, grad_out, num_hea
     bias gradient is fp32 (float64 for float64 features).  A gradient that is not requested is not computed."""
     q, k, v, bias, heads, c, km = _lattn_prepare(q, k, v, rel_pos_bias, num_heads, kernel_size, kernel_stride,
                                                  kernel_dilation, region_type, offset, q_key, kv_key, manager)
-    out = _attn_rows("out", out, q)
-    grad_out = _attn_rows("grad_out", grad_out.to(q.dtype))
-    _check(tuple(out.shape) == tuple(q.shape) and tuple(grad_out.shape) == tuple(q.shape),
-           "out and grad_out must have the shape of q")
-    _check(lse.is_cuda and lse.is_contiguous() and lse.dtype == _inorm_param_dtype(q) and
-           tuple(lse.shape) == (2, q.shape[0], heads), "lse must be the contiguous [2, n_out, heads] statistics of the forward pass")
+    out, grad_out = _attn_backward_operands(q, out, grad_out, lse, (2, q.shape[0], heads), "[2, n_out, heads]")
     need_grad_bias = bool(need_grad_bias) and bias is not None
     if not (need_grad_q or need_grad_k or need_grad_v or need_grad_bias):
         return None, None, None, None
@@ -3917,71 +3892,25 @@ def _serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, manager)
            v.shape[0], "!=", n)
     heads, c = int(num_heads), int(q.shape[1])
     _check(heads > 0 and c % heads == 0, "the channel count", c, "must be a multiple of num_heads", heads)
-    seg_ptr, seg_rows, blk_tab, _ = manager._patch_rows(in_key, patch_size, order)
-    return q, k, v, heads, c, seg_ptr, seg_rows, blk_tab, int(seg_ptr.numel()) - 1
+    lists = manager._patch_rows(in_key, patch_size, order)[:3]
+    return q, k, v, heads, c, lists, int(lists[0].numel()) - 1
 
 
 def SerializedAttentionForwardGPU(q, k, v, num_heads, scale, patch_size, order, in_key, manager):
     """-> (out [n, C], lse [n, heads]): out[i, h] = sum_j softmax_j(scale <q[i, h], k[j, h]>) v[j, h] over the rows j of the
     patch of row i (manager._patch_rows(in_key, patch_size, order)); lse in fp32 (float64 for float64 features)."""
-    q, k, v, heads, c, seg_ptr, seg_rows, blk_tab, n_seg = _serial_attn_prepare(q, k, v, num_heads, patch_size, order,
-                                                                              in_key, manager)
-    lib = _lib.load()
-    dev = q.device
-    n = int(q.shape[0])
-    out = torch.empty((n, c), dtype=q.dtype, device=dev)
-    lse = torch.empty((n, heads), dtype=_inorm_param_dtype(q), device=dev)
-    with _on(dev):
-        if q.dtype == torch.float64:
-            _lib.check(lib.me_attn_forward_tab_f64(
-                _ptr(q), _ptr(k), _ptr(v), _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(seg_ptr), _ptr(seg_rows),
-                _ptr(seg_ptr), _ptr(seg_rows), _ptr(blk_tab), _ptr(blk_tab), n, n, n_seg, c, heads, float(scale), _ptr(out),
-                c, _ptr(lse), _stream(dev)))
-        else:
-            bf = 1 if q.dtype == torch.bfloat16 else 0
-            _timed("serial_attn_forward", dev, lambda: _lib.check(lib.me_attn_forward_tab(
-                _ptr(q), _ptr(k), _ptr(v), bf, _attn_stride(q), _attn_stride(k), _attn_stride(v), _ptr(seg_ptr),
-                _ptr(seg_rows), _ptr(seg_ptr), _ptr(seg_rows), _ptr(blk_tab), _ptr(blk_tab), n, n, n_seg, c, heads,
-                float(scale), _ptr(out), c, _ptr(lse), _stream(dev))))
-    return out, lse
+    q, k, v, heads, c, lists, n_seg = _serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, manager)
+    return _list_attn_forward("serial_attn_forward", q, k, v, lists, lists, n_seg, heads, c, scale)
 
 
 def SerializedAttentionBackwardGPU(q, k, v, out, lse, grad_out, num_heads, scale, patch_size, order, in_key, manager,
                                    need_grad_q=True, need_grad_k=True, need_grad_v=True):
     """-> (grad_q | None, grad_k | None, grad_v | None), contiguous, from out and lse of the forward pass; a gradient that
     is not requested is not computed (AttentionBackwardGPU's rule)."""
-    q, k, v, heads, c, seg_ptr, seg_rows, blk_tab, n_seg = _serial_attn_prepare(q, k, v, num_heads, patch_size, order,
-                                                                              in_key, manager)
-    out = _attn_rows("out", out, q)
-    grad_out = _attn_rows("grad_out", grad_out.to(q.dtype))
-    _check(tuple(out.shape) == tuple(q.shape) and tuple(grad_out.shape) == tuple(q.shape),
-           "out and grad_out must have the shape of q")
-    _check(lse.is_cuda and lse.is_contiguous() and lse.dtype == _inorm_param_dtype(q) and
-           tuple(lse.shape) == (q.shape[0], heads), "lse must be the contiguous [n, heads] statistics of the forward pass")
-    lib = _lib.load()
-    dev = q.device
-    n = int(q.shape[0])
-    grad_q = torch.empty((n, c), dtype=q.dtype, device=dev) if need_grad_q else None
-    grad_k = torch.empty((n, c), dtype=q.dtype, device=dev) if need_grad_k else None
-    grad_v = torch.empty((n, c), dtype=q.dtype, device=dev) if need_grad_v else None
-    if not (need_grad_q or need_grad_k or need_grad_v):
-        return None, None, None
-    with _on(dev):
-        if q.dtype == torch.float64:
-            _lib.check(lib.me_attn_backward_tab_f64(
-                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), _attn_stride(q), _attn_stride(k),
-                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_ptr), _ptr(seg_rows), _ptr(seg_ptr),
-                _ptr(seg_rows), _ptr(blk_tab), _ptr(blk_tab), n, n, n_seg, c, heads, float(scale), _ptr(grad_q), c,
-                _ptr(grad_k), c, _ptr(grad_v), c, _stream(dev)))
-        else:
-            bf = 1 if q.dtype == torch.bfloat16 else 0
-            ws = _workspace(int(lib.me_attn_workspace_bytes(n, n, n_seg, heads)), dev)
-            _timed("serial_attn_backward", dev, lambda: _lib.check(lib.me_attn_backward_tab(
-                _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(grad_out), bf, _attn_stride(q), _attn_stride(k),
-                _attn_stride(v), _attn_stride(out), _attn_stride(grad_out), _ptr(seg_ptr), _ptr(seg_rows), _ptr(seg_ptr),
-                _ptr(seg_rows), _ptr(blk_tab), _ptr(blk_tab), n, n, n_seg, c, heads, float(scale), _ptr(grad_q), c,
-                _ptr(grad_k), c, _ptr(grad_v), c, _ptr(ws), ws.numel(), _stream(dev))))
-    return grad_q, grad_k, grad_v
+    q, k, v, heads, c, lists, n_seg = _serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, manager)
+    out, grad_out = _attn_backward_operands(q, out, grad_out, lse, (q.shape[0], heads), "[n, heads]")
+    return _list_attn_backward("serial_attn_backward", q, k, v, out, lse, grad_out, lists, lists, n_seg, heads, c, scale,
+                               need_grad_q, need_grad_k, need_grad_v)
 
 
 # ------------------------------------------------------------------------------------------------

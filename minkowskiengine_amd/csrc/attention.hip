@@ -33,6 +33,7 @@
 // patch attention (serial_attention.hip), whose lists come with a block table of one (segment, first row) pair per
 // workgroup; the _tab entry points take it and the kernels branch on the pointer at entry (k_attn_delta walks nothing).
 // The float64 twins at the end are the gradcheck yardstick (plain double, one thread per (row, head)).
+#include "attn_block.hpp"
 #include "common.hpp"
 
 #include <algorithm>
@@ -46,7 +47,6 @@ typedef __bf16 at_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 at_bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kAttnThreads = 128;   // two waves, 32 stationary rows each
-constexpr int kAttnBlock = 64;      // stationary rows of a workgroup (BQ forward and dQ, BK of dK / dV)
 constexpr int kAttnFwdWalk = 64;    // key rows staged per step, forward
 constexpr int kAttnBwdWalk = 32;    // rows staged per step, backward kernels (two / four images instead of two)
 
@@ -125,8 +125,8 @@ template <typename T> __device__ __forceinline__ float attn_exp(float x) {
 }
 
 // (instance, block) of workgroup `blk`: the blocks of the instances in ascending instance order.  With a block table
-// (int32 pairs (segment, first row in the segment), one per workgroup, segment -1: no block; me_attn_patch_lists) the item
-// is one 8-byte load; without one the workgroup walks seg_ptr.  `tab` is a kernel argument: the branch is wave-uniform.
+// (attn_block.hpp) the item is one 8-byte load; without one the workgroup walks seg_ptr.  `tab` is a kernel argument: the
+// branch is wave-uniform.
 __device__ __forceinline__ bool attn_find_item(const int32_t *__restrict__ tab, const int32_t *__restrict__ seg_ptr,
                                                int n_batch, int blk, int height, int &b, int &t0, int &start, int &len) {
   if (tab != nullptr) {

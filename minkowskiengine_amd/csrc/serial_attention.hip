@@ -16,12 +16,12 @@
 //                   row_patch[row] = patch_base[b] + that, patch_base the exclusive scan of m_b in ascending batch order
 //   me_csr_from_coo(row_patch) -> seg_ptr [S + 1], seg_rows [n]: rows ascending inside a patch, the fixed summation order
 //   k_seg_blocks / k_blk_tab
-//                   the block table int32 [2 (ceil(n / 64) + S)]: for every 64-row block of every non-empty segment, in
-//                   segment order, (segment, first row in the segment); unused entries hold segment -1
+//                   the block table of the S segments (attn_block.hpp)
 // S = ceil(n / P) + n_batch is an upper bound of the patch count that the host knows without a read-back; surplus segments
 // are empty.  Everything runs on the caller's stream with no synchronisation.  Nothing here knows that the segments came
 // from a curve: any per-row segment id (a window partition, say) gives lists and a table the same way from step
 // me_csr_from_coo on.
+#include "attn_block.hpp"
 #include "common.hpp"
 
 namespace me {
@@ -29,8 +29,6 @@ namespace me {
 int64_t radix_argsort_u64_workspace_bytes(int64_t n);
 int radix_argsort_u64(uint64_t *keys, uint64_t *keys_tmp, int64_t n, const int *shifts, int np, uint32_t *order,
                       uint64_t **sorted_keys, void *ws, int64_t ws_bytes, hipStream_t stream);
-
-constexpr int kSerialBlockRows = 64;   // kAttnBlock of attention.hip: the stationary rows of a workgroup
 
 struct SerialGeom {
   int32_t bbox_min[ME_MAX_DIM];
@@ -134,7 +132,7 @@ __global__ __launch_bounds__(256) void k_seg_blocks(const int32_t *__restrict__ 
                                                    uint32_t *__restrict__ seg_nblk) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n_seg) return;
-  seg_nblk[s] = (uint32_t)((seg_ptr[s + 1] - seg_ptr[s] + kSerialBlockRows - 1) / kSerialBlockRows);
+  seg_nblk[s] = (uint32_t)((seg_ptr[s + 1] - seg_ptr[s] + kAttnBlock - 1) / kAttnBlock);
 }
 
 __global__ __launch_bounds__(256) void k_blk_tab(const int32_t *__restrict__ seg_ptr, const uint32_t *__restrict__ blk_base,
@@ -143,7 +141,7 @@ __global__ __launch_bounds__(256) void k_blk_tab(const int32_t *__restrict__ seg
   if (s >= n_seg) return;
   const int len = seg_ptr[s + 1] - seg_ptr[s];
   int64_t e = blk_base[s];
-  for (int t0 = 0; t0 < len && e < n_entries; t0 += kSerialBlockRows, ++e) {
+  for (int t0 = 0; t0 < len && e < n_entries; t0 += kAttnBlock, ++e) {
     tab[2 * e] = (int32_t)s;
     tab[2 * e + 1] = t0;
   }
@@ -233,7 +231,7 @@ int me_attn_patch_lists(const int32_t *coords, int64_t n, int32_t ncol, const in
   const int batch_bits = bits_of((uint64_t)(batch_max > n_batch ? batch_max : n_batch));
   ME_CHECK(D * depth + batch_bits <= 63, "the serialisation key (D * depth code bits + the batch bits) must fit in 63 bits");
   ME_CHECK(n == 0 || n_batch >= 1, "rows without an instance");
-  const int64_t n_seg = serial_n_seg(n, n_batch, patch_size), n_entries = ceil_div(n, kSerialBlockRows) + n_seg;
+  const int64_t n_seg = serial_n_seg(n, n_batch, patch_size), n_entries = ceil_div(n, kAttnBlock) + n_seg;
   ME_CHECK(n_seg < (1ll << 31), "too many segments");
   ME_CHECK(workspace_bytes >= me_attn_patch_lists_workspace_bytes(n, n_batch, patch_size), "workspace too small");
   ME_CHECK(seg_ptr != nullptr && blk_tab != nullptr, "seg_ptr and blk_tab must be given");

@@ -10,6 +10,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
 
 namespace meh {
@@ -1313,10 +1314,103 @@ static Tensor attn_rows(const char *name, Tensor t, const Tensor *ref = nullptr)
 }
 static int64_t attn_stride(const Tensor &t) { return t.size(0) > 1 ? t.stride(0) : t.size(1); }
 
-struct AttnPrep {
-  int heads, c, n_batch;
-  std::pair<Tensor, Tensor> seg_q, seg_kv;
+// a row list of the attention kernels; blk_tab undefined: no block table, the workgroups walk seg_ptr
+struct AttnList {
+  Tensor seg_ptr, seg_rows, blk_tab;
 };
+struct AttnPrep {
+  int heads, c, n_seg;
+  AttnList q, kv;
+};
+
+// out and grad_out as row operands of q's dtype and shape; lse: the statistics of the forward pass, of shape `lse_shape`
+static void attn_backward_operands(const Tensor &q, Tensor &out, Tensor &grad_out, const Tensor &lse,
+                                   at::IntArrayRef lse_shape, const char *lse_name) {
+  out = attn_rows("out", out, &q);
+  grad_out = attn_rows("grad_out", grad_out.to(q.scalar_type()));
+  check(out.sizes() == q.sizes() && grad_out.sizes() == q.sizes(), "out and grad_out must have the shape of q");
+  check(lse.is_cuda() && lse.is_contiguous() &&
+            lse.scalar_type() == (q.scalar_type() == at::kDouble ? at::kDouble : at::kFloat) && lse.sizes() == lse_shape,
+        std::string("lse must be the contiguous ") + lse_name + " statistics of the forward pass");
+}
+
+// attention on row lists (me_attn_forward_tab): a query row attends to the key rows of its own segment; twin of
+// backend._list_attn_forward
+static std::pair<Tensor, Tensor> list_attn_forward(const Tensor &q, const Tensor &k, const Tensor &v, const AttnPrep &p,
+                                                   double scale) {
+  const c10::Device dev = q.device();
+  const bool f64 = q.scalar_type() == at::kDouble;
+  const int64_t n_q = q.size(0), n_kv = k.size(0);
+  Tensor out = at::empty({n_q, p.c}, q.options());
+  Tensor lse = at::empty({n_q, p.heads}, at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev));
+  const int32_t *spq = ptr<int32_t>(p.q.seg_ptr), *srq = ptr<int32_t>(p.q.seg_rows), *tq = ptr<int32_t>(p.q.blk_tab);
+  const int32_t *spk = ptr<int32_t>(p.kv.seg_ptr), *srk = ptr<int32_t>(p.kv.seg_rows), *tk = ptr<int32_t>(p.kv.blk_tab);
+  c10::DeviceGuard guard(dev);
+  if (f64) {
+    me_ok(me_attn_forward_tab_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), attn_stride(q), attn_stride(k),
+                                  attn_stride(v), spq, srq, spk, srk, tq, tk, n_q, n_kv, p.n_seg, p.c, p.heads, scale,
+                                  ptr<double>(out), p.c, ptr<double>(lse), stream_of(dev)));
+  } else {
+    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+    me_ok(me_attn_forward_tab(q.data_ptr(), k.data_ptr(), v.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v),
+                              spq, srq, spk, srk, tq, tk, n_q, n_kv, p.n_seg, p.c, p.heads, (float)scale, out.data_ptr(),
+                              p.c, ptr<float>(lse), stream_of(dev)));
+  }
+  return {out, lse};
+}
+
+// The gradients of list_attn_forward (twin of backend._list_attn_backward); one that is not requested is neither allocated
+// nor computed.  No kv_splits: me_attn_backward_tab; else the query slices of me_attn_backward_split.  zero_unlisted: kv
+// rows may sit in no segment; where the dK / dV pass writes the listed rows only (one slice, float64) grad_k / grad_v start
+// as zeros.
+static std::vector<Tensor> list_attn_backward(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out,
+                                              const Tensor &lse, const Tensor &grad_out, const AttnPrep &p, double scale,
+                                              bool need_grad_q, bool need_grad_k, bool need_grad_v,
+                                              std::optional<int64_t> kv_splits = std::nullopt,
+                                              bool zero_unlisted = false) {
+  if (!(need_grad_q || need_grad_k || need_grad_v)) return {Tensor(), Tensor(), Tensor()};
+  const c10::Device dev = q.device();
+  const bool f64 = q.scalar_type() == at::kDouble;
+  const int64_t n_q = q.size(0), n_kv = k.size(0);
+  const bool zero_kv = zero_unlisted && (kv_splits == 1 || f64);
+  auto new_kv = [&]() { return zero_kv ? at::zeros({n_kv, p.c}, q.options()) : at::empty({n_kv, p.c}, q.options()); };
+  Tensor grad_q = need_grad_q ? at::empty({n_q, p.c}, q.options()) : Tensor();
+  Tensor grad_k = need_grad_k ? new_kv() : Tensor();
+  Tensor grad_v = need_grad_v ? new_kv() : Tensor();
+  const int32_t *spq = ptr<int32_t>(p.q.seg_ptr), *srq = ptr<int32_t>(p.q.seg_rows), *tq = ptr<int32_t>(p.q.blk_tab);
+  const int32_t *spk = ptr<int32_t>(p.kv.seg_ptr), *srk = ptr<int32_t>(p.kv.seg_rows), *tk = ptr<int32_t>(p.kv.blk_tab);
+  c10::DeviceGuard guard(dev);
+#define ME_LIST_ATTN_BWD_ARGS(P, SCALE)                                                                                 \
+  attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out), attn_stride(grad_out), spq, srq, spk, srk, tq, tk, \
+      n_q, n_kv, p.n_seg, p.c, p.heads, SCALE, P(grad_q), p.c, P(grad_k), p.c, P(grad_v), p.c
+  if (f64) {
+    const double *qd = ptr<double>(q), *kd = ptr<double>(k), *vd = ptr<double>(v), *od = ptr<double>(out),
+                 *ld = ptr<double>(lse), *gd = ptr<double>(grad_out);
+    if (!kv_splits)
+      me_ok(me_attn_backward_tab_f64(qd, kd, vd, od, ld, gd, ME_LIST_ATTN_BWD_ARGS(ptr<double>, scale),
+                                     stream_of(dev)));
+    else
+      me_ok(me_attn_backward_split_f64(qd, kd, vd, od, ld, gd, ME_LIST_ATTN_BWD_ARGS(ptr<double>, scale),
+                                       (int32_t)*kv_splits, stream_of(dev)));
+  } else {
+    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
+    if (!kv_splits) {
+      Tensor ws = workspace(me_attn_workspace_bytes(n_q, n_kv, p.n_seg, p.heads), dev);
+      me_ok(me_attn_backward_tab(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ptr<float>(lse),
+                                 grad_out.data_ptr(), bf, ME_LIST_ATTN_BWD_ARGS(vptr, (float)scale), vptr(ws),
+                                 ws.numel(), stream_of(dev)));
+    } else {
+      Tensor ws = workspace(me_attn_split_workspace_bytes(n_q, n_kv, p.n_seg, p.c, p.heads,
+                                                          (int32_t)std::max<int64_t>(*kv_splits, 1)), dev);
+      me_ok(me_attn_backward_split(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ptr<float>(lse),
+                                   grad_out.data_ptr(), bf, ME_LIST_ATTN_BWD_ARGS(vptr, (float)scale), vptr(ws),
+                                   ws.numel(), (int32_t)*kv_splits, stream_of(dev)));
+    }
+  }
+#undef ME_LIST_ATTN_BWD_ARGS
+  return {grad_q, grad_k, grad_v};
+}
+
 static AttnPrep attn_prepare(Tensor &q, Tensor &k, Tensor &v, int64_t num_heads, CoordinateMapKey *q_key,
                              CoordinateMapKey *kv_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
   q = attn_rows("q", q);
@@ -1333,38 +1427,16 @@ static AttnPrep attn_prepare(Tensor &q, Tensor &k, Tensor &v, int64_t num_heads,
     KeyT ok = mgr->origin();
     glob_key->set_key(ok.first, ok.second);
   }
-  AttnPrep p;
-  p.heads = (int)num_heads;
-  p.c = (int)c;
-  p.seg_q = mgr->instance_rows(qk);
-  p.seg_kv = mgr->instance_rows(kk);
-  p.n_batch = (int)mgr->get(glob_key->get())->n;
-  return p;
+  const auto &lq = mgr->instance_rows(qk), &lkv = mgr->instance_rows(kk);
+  return {(int)num_heads, (int)c, (int)mgr->get(glob_key->get())->n, {lq.first, lq.second, Tensor()},
+          {lkv.first, lkv.second, Tensor()}};
 }
 
 std::pair<Tensor, Tensor> attention_forward(Tensor q, Tensor k, Tensor v, int64_t num_heads, double scale,
                                             CoordinateMapKey *q_key, CoordinateMapKey *kv_key, CoordinateMapKey *glob_key,
                                             CoordinateMapManager *mgr) {
   const AttnPrep p = attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, mgr);
-  const c10::Device dev = q.device();
-  const bool f64 = q.scalar_type() == at::kDouble;
-  const int64_t n_q = q.size(0), n_kv = k.size(0);
-  Tensor out = at::empty({n_q, p.c}, q.options());
-  Tensor lse = at::empty({n_q, p.heads}, at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev));
-  c10::DeviceGuard guard(dev);
-  if (f64) {
-    me_ok(me_attn_forward_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), attn_stride(q), attn_stride(k),
-                              attn_stride(v), ptr<int32_t>(p.seg_q.first), ptr<int32_t>(p.seg_q.second),
-                              ptr<int32_t>(p.seg_kv.first), ptr<int32_t>(p.seg_kv.second), n_q, n_kv, p.n_batch, p.c,
-                              p.heads, scale, ptr<double>(out), p.c, ptr<double>(lse), stream_of(dev)));
-  } else {
-    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
-    me_ok(me_attn_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v),
-                          ptr<int32_t>(p.seg_q.first), ptr<int32_t>(p.seg_q.second), ptr<int32_t>(p.seg_kv.first),
-                          ptr<int32_t>(p.seg_kv.second), n_q, n_kv, p.n_batch, p.c, p.heads, (float)scale, out.data_ptr(),
-                          p.c, ptr<float>(lse), stream_of(dev)));
-  }
-  return {out, lse};
+  return list_attn_forward(q, k, v, p, scale);
 }
 
 std::vector<Tensor> attention_backward(Tensor q, Tensor k, Tensor v, Tensor out, const Tensor &lse, Tensor grad_out,
@@ -1372,49 +1444,14 @@ std::vector<Tensor> attention_backward(Tensor q, Tensor k, Tensor v, Tensor out,
                                        CoordinateMapKey *glob_key, CoordinateMapManager *mgr, bool need_grad_q,
                                        bool need_grad_k, bool need_grad_v) {
   const AttnPrep p = attn_prepare(q, k, v, num_heads, q_key, kv_key, glob_key, mgr);
-  out = attn_rows("out", out, &q);
-  grad_out = attn_rows("grad_out", grad_out.to(q.scalar_type()));
-  check(out.sizes() == q.sizes() && grad_out.sizes() == q.sizes(), "out and grad_out must have the shape of q");
-  const c10::Device dev = q.device();
-  const bool f64 = q.scalar_type() == at::kDouble;
-  check(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == (f64 ? at::kDouble : at::kFloat) && lse.dim() == 2 &&
-            lse.size(0) == q.size(0) && lse.size(1) == p.heads,
-        "lse must be the contiguous [n_q, heads] statistics of the forward pass");
-  const int64_t n_q = q.size(0), n_kv = k.size(0);
-  Tensor grad_q = need_grad_q ? at::empty({n_q, p.c}, q.options()) : Tensor();
-  Tensor grad_k = need_grad_k ? at::empty({n_kv, p.c}, q.options()) : Tensor();
-  Tensor grad_v = need_grad_v ? at::empty({n_kv, p.c}, q.options()) : Tensor();
-  if (!(need_grad_q || need_grad_k || need_grad_v)) return {grad_q, grad_k, grad_v};
-  c10::DeviceGuard guard(dev);
-  if (f64) {
-    me_ok(me_attn_backward_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), ptr<double>(out), ptr<double>(lse),
-                               ptr<double>(grad_out), attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out),
-                               attn_stride(grad_out), ptr<int32_t>(p.seg_q.first), ptr<int32_t>(p.seg_q.second),
-                               ptr<int32_t>(p.seg_kv.first), ptr<int32_t>(p.seg_kv.second), n_q, n_kv, p.n_batch, p.c,
-                               p.heads, scale, ptr<double>(grad_q), p.c, ptr<double>(grad_k), p.c, ptr<double>(grad_v), p.c,
-                               stream_of(dev)));
-  } else {
-    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
-    Tensor ws = workspace(me_attn_workspace_bytes(n_q, n_kv, p.n_batch, p.heads), dev);
-    me_ok(me_attn_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ptr<float>(lse), grad_out.data_ptr(),
-                           bf, attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out), attn_stride(grad_out),
-                           ptr<int32_t>(p.seg_q.first), ptr<int32_t>(p.seg_q.second), ptr<int32_t>(p.seg_kv.first),
-                           ptr<int32_t>(p.seg_kv.second), n_q, n_kv, p.n_batch, p.c, p.heads, (float)scale, vptr(grad_q),
-                           p.c, vptr(grad_k), p.c, vptr(grad_v), p.c, vptr(ws), ws.numel(), stream_of(dev)));
-  }
-  return {grad_q, grad_k, grad_v};
+  attn_backward_operands(q, out, grad_out, lse, {q.size(0), (int64_t)p.heads}, "[n_q, heads]");
+  return list_attn_backward(q, k, v, out, lse, grad_out, p, scale, need_grad_q, need_grad_k, need_grad_v);
 }
 
 // ---- cross-attention to a dense context (csrc/attention.hip, ABI 1.20; twin of backend.CrossAttention{Forward,Backward}GPU):
 // q on a map, k / v [B, L, C] or [B * L, C] row views, context row j in the instance with the j-th smallest batch index ------
-struct CrossAttnPrep {
-  int heads, c, n_batch;
-  std::pair<Tensor, Tensor> seg_q;
-  std::vector<Tensor> seg_kv;   // seg_ptr, seg_rows, blk_tab
-  bool with_lengths;
-};
-static CrossAttnPrep cross_attn_prepare(Tensor &q, Tensor &k, Tensor &v, Tensor lengths, int64_t num_heads,
-                                        CoordinateMapKey *q_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+static AttnPrep cross_attn_prepare(Tensor &q, Tensor &k, Tensor &v, Tensor lengths, int64_t num_heads,
+                                   CoordinateMapKey *q_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
   q = attn_rows("q", q);
   check((k.dim() == 2 || k.dim() == 3) && v.dim() == k.dim() && k.sizes().slice(0, k.dim() - 1) == v.sizes().slice(0, k.dim() - 1),
         "k and v must be [B, L, C] or [B * L, C] with the same leading shape");
@@ -1445,39 +1482,16 @@ static CrossAttnPrep cross_attn_prepare(Tensor &q, Tensor &k, Tensor &v, Tensor 
           "context_lengths must be an integer tensor with one length per instance");
     lengths = lengths.to(q.device(), at::kInt).contiguous();
   }
-  CrossAttnPrep p;
-  p.heads = (int)num_heads;
-  p.c = (int)c;
-  p.n_batch = (int)n_batch;
-  p.seg_q = mgr->instance_rows(qk);
-  p.seg_kv = mgr->context_rows(n_batch, tokens, q.device(), lengths);
-  p.with_lengths = lengths.defined();
-  return p;
+  const auto &lq = mgr->instance_rows(qk);
+  const std::vector<Tensor> lkv = mgr->context_rows(n_batch, tokens, q.device(), lengths);
+  return {(int)num_heads, (int)c, (int)n_batch, {lq.first, lq.second, Tensor()}, {lkv[0], lkv[1], lkv[2]}};
 }
 
 std::pair<Tensor, Tensor> cross_attention_forward(Tensor q, Tensor k, Tensor v, Tensor context_lengths, int64_t num_heads,
                                                   double scale, CoordinateMapKey *q_key, CoordinateMapKey *glob_key,
                                                   CoordinateMapManager *mgr) {
-  const CrossAttnPrep p = cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key, mgr);
-  const c10::Device dev = q.device();
-  const bool f64 = q.scalar_type() == at::kDouble;
-  const int64_t n_q = q.size(0), n_kv = k.size(0);
-  Tensor out = at::empty({n_q, p.c}, q.options());
-  Tensor lse = at::empty({n_q, p.heads}, at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev));
-  const int32_t *spq = ptr<int32_t>(p.seg_q.first), *srq = ptr<int32_t>(p.seg_q.second);
-  const int32_t *spk = ptr<int32_t>(p.seg_kv[0]), *srk = ptr<int32_t>(p.seg_kv[1]), *tab = ptr<int32_t>(p.seg_kv[2]);
-  c10::DeviceGuard guard(dev);
-  if (f64) {
-    me_ok(me_attn_forward_tab_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), attn_stride(q), attn_stride(k),
-                                  attn_stride(v), spq, srq, spk, srk, nullptr, tab, n_q, n_kv, p.n_batch, p.c, p.heads,
-                                  scale, ptr<double>(out), p.c, ptr<double>(lse), stream_of(dev)));
-  } else {
-    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
-    me_ok(me_attn_forward_tab(q.data_ptr(), k.data_ptr(), v.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v),
-                              spq, srq, spk, srk, nullptr, tab, n_q, n_kv, p.n_batch, p.c, p.heads, (float)scale,
-                              out.data_ptr(), p.c, ptr<float>(lse), stream_of(dev)));
-  }
-  return {out, lse};
+  const AttnPrep p = cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key, mgr);
+  return list_attn_forward(q, k, v, p, scale);
 }
 
 std::vector<Tensor> cross_attention_backward(Tensor q, Tensor k, Tensor v, Tensor context_lengths, Tensor out,
@@ -1485,48 +1499,15 @@ std::vector<Tensor> cross_attention_backward(Tensor q, Tensor k, Tensor v, Tenso
                                              CoordinateMapKey *q_key, CoordinateMapKey *glob_key,
                                              CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k,
                                              bool need_grad_v, int64_t kv_splits) {
-  const CrossAttnPrep p = cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key, mgr);
-  out = attn_rows("out", out, &q);
-  grad_out = attn_rows("grad_out", grad_out.to(q.scalar_type()));
-  check(out.sizes() == q.sizes() && grad_out.sizes() == q.sizes(), "out and grad_out must have the shape of q");
-  const c10::Device dev = q.device();
-  const bool f64 = q.scalar_type() == at::kDouble;
-  check(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == (f64 ? at::kDouble : at::kFloat) && lse.dim() == 2 &&
-            lse.size(0) == q.size(0) && lse.size(1) == p.heads,
-        "lse must be the contiguous [n_q, heads] statistics of the forward pass");
-  const int64_t n_q = q.size(0), n_kv = k.size(0);
+  const AttnPrep p = cross_attn_prepare(q, k, v, context_lengths, num_heads, q_key, glob_key, mgr);
+  attn_backward_operands(q, out, grad_out, lse, {q.size(0), (int64_t)p.heads}, "[n_q, heads]");
   if (kv_splits == 0) {   // the argument, else the environment, else the library's policy
     const char *env = std::getenv("ME_AMD_ATTN_KV_SPLITS");
     if (env && *env) kv_splits = std::atoll(env);
   }
-  if (kv_splits == 0) kv_splits = me_attn_kv_splits(n_q, n_kv, p.n_batch, p.c, p.heads);
-  if (!(need_grad_q || need_grad_k || need_grad_v)) return {Tensor(), Tensor(), Tensor()};
-  // the key-stationary kernel (one slice, float64) writes the listed rows only: the others are zeroed here
-  const bool zero_kv = p.with_lengths && (kv_splits == 1 || f64);
-  auto new_kv = [&]() { return zero_kv ? at::zeros({n_kv, p.c}, q.options()) : at::empty({n_kv, p.c}, q.options()); };
-  Tensor grad_q = need_grad_q ? at::empty({n_q, p.c}, q.options()) : Tensor();
-  Tensor grad_k = need_grad_k ? new_kv() : Tensor();
-  Tensor grad_v = need_grad_v ? new_kv() : Tensor();
-  const int32_t *spq = ptr<int32_t>(p.seg_q.first), *srq = ptr<int32_t>(p.seg_q.second);
-  const int32_t *spk = ptr<int32_t>(p.seg_kv[0]), *srk = ptr<int32_t>(p.seg_kv[1]), *tab = ptr<int32_t>(p.seg_kv[2]);
-  c10::DeviceGuard guard(dev);
-  if (f64) {
-    me_ok(me_attn_backward_split_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), ptr<double>(out), ptr<double>(lse),
-                                     ptr<double>(grad_out), attn_stride(q), attn_stride(k), attn_stride(v),
-                                     attn_stride(out), attn_stride(grad_out), spq, srq, spk, srk, nullptr, tab, n_q, n_kv,
-                                     p.n_batch, p.c, p.heads, scale, ptr<double>(grad_q), p.c, ptr<double>(grad_k), p.c,
-                                     ptr<double>(grad_v), p.c, (int32_t)kv_splits, stream_of(dev)));
-  } else {
-    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
-    Tensor ws = workspace(me_attn_split_workspace_bytes(n_q, n_kv, p.n_batch, p.c, p.heads,
-                                                        (int32_t)std::max<int64_t>(kv_splits, 1)), dev);
-    me_ok(me_attn_backward_split(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ptr<float>(lse),
-                                 grad_out.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out),
-                                 attn_stride(grad_out), spq, srq, spk, srk, nullptr, tab, n_q, n_kv, p.n_batch, p.c, p.heads,
-                                 (float)scale, vptr(grad_q), p.c, vptr(grad_k), p.c, vptr(grad_v), p.c, vptr(ws),
-                                 ws.numel(), (int32_t)kv_splits, stream_of(dev)));
-  }
-  return {grad_q, grad_k, grad_v};
+  if (kv_splits == 0) kv_splits = me_attn_kv_splits(q.size(0), k.size(0), p.n_seg, p.c, p.heads);
+  return list_attn_backward(q, k, v, out, lse, grad_out, p, scale, need_grad_q, need_grad_k, need_grad_v, kv_splits,
+                            context_lengths.defined());
 }
 
 // ---- local attention over a kernel map (csrc/local_attention.hip; twin of backend.LocalAttention{Forward,Backward}GPU) ----
@@ -1594,14 +1575,9 @@ std::vector<Tensor> local_attention_backward(Tensor q, Tensor k, Tensor v, Tenso
                                              CoordinateMapKey *kv_key, CoordinateMapManager *mgr, const ivec &offsets,
                                              bool need_grad_q, bool need_grad_k, bool need_grad_v, bool need_grad_bias) {
   const LattnPrep p = lattn_prepare(q, k, v, bias, num_heads, ks, st, dl, region_type, q_key, kv_key, mgr, offsets);
-  out = attn_rows("out", out, &q);
-  grad_out = attn_rows("grad_out", grad_out.to(q.scalar_type()));
-  check(out.sizes() == q.sizes() && grad_out.sizes() == q.sizes(), "out and grad_out must have the shape of q");
+  attn_backward_operands(q, out, grad_out, lse, {2, q.size(0), (int64_t)p.heads}, "[2, n_out, heads]");
   const c10::Device dev = q.device();
   const bool f64 = q.scalar_type() == at::kDouble;
-  check(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == (f64 ? at::kDouble : at::kFloat) && lse.dim() == 3 &&
-            lse.size(0) == 2 && lse.size(1) == q.size(0) && lse.size(2) == p.heads,
-        "lse must be the contiguous [2, n_out, heads] statistics of the forward pass");
   need_grad_bias = need_grad_bias && bias.defined();
   if (!(need_grad_q || need_grad_k || need_grad_v || need_grad_bias)) return {Tensor(), Tensor(), Tensor(), Tensor()};
   const int64_t n_out = p.km->n_out, n_in = p.km->n_in, volume = p.km->volume;
@@ -1641,13 +1617,8 @@ int serial_order_code(const std::string &order) {
   throw std::invalid_argument("order must be one of ('z', 'z_trans', 'hilbert', 'hilbert_trans'), not '" + order + "'");
 }
 
-struct SerialAttnPrep {
-  int heads, c, n_seg;
-  Tensor seg_ptr, seg_rows, blk_tab;
-};
-static SerialAttnPrep serial_attn_prepare(Tensor &q, Tensor &k, Tensor &v, int64_t num_heads, int64_t patch_size,
-                                          const std::string &order, CoordinateMapKey *in_key,
-                                          CoordinateMapManager *mgr) {
+static AttnPrep serial_attn_prepare(Tensor &q, Tensor &k, Tensor &v, int64_t num_heads, int64_t patch_size,
+                                    const std::string &order, CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
   q = attn_rows("q", q);
   k = attn_rows("k", k, &q);
   v = attn_rows("v", v, &q);
@@ -1659,38 +1630,15 @@ static SerialAttnPrep serial_attn_prepare(Tensor &q, Tensor &k, Tensor &v, int64
   check(num_heads > 0 && c % num_heads == 0, "the channel count " + std::to_string(c) +
                                                  " must be a multiple of num_heads " + std::to_string(num_heads));
   const std::vector<Tensor> &l = mgr->patch_rows(ik, patch_size, serial_order_code(order));
-  SerialAttnPrep p;
-  p.heads = (int)num_heads;
-  p.c = (int)c;
-  p.seg_ptr = l[0];
-  p.seg_rows = l[1];
-  p.blk_tab = l[2];
-  p.n_seg = (int)l[0].numel() - 1;
-  return p;
+  const AttnList lists{l[0], l[1], l[2]};
+  return {(int)num_heads, (int)c, (int)l[0].numel() - 1, lists, lists};
 }
 
 std::pair<Tensor, Tensor> serialized_attention_forward(Tensor q, Tensor k, Tensor v, int64_t num_heads, double scale,
                                                        int64_t patch_size, const std::string &order,
                                                        CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
-  const SerialAttnPrep p = serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, mgr);
-  const c10::Device dev = q.device();
-  const bool f64 = q.scalar_type() == at::kDouble;
-  const int64_t n = q.size(0);
-  Tensor out = at::empty({n, p.c}, q.options());
-  Tensor lse = at::empty({n, p.heads}, at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev));
-  const int32_t *sp = ptr<int32_t>(p.seg_ptr), *sr = ptr<int32_t>(p.seg_rows), *tab = ptr<int32_t>(p.blk_tab);
-  c10::DeviceGuard guard(dev);
-  if (f64) {
-    me_ok(me_attn_forward_tab_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), attn_stride(q), attn_stride(k),
-                                  attn_stride(v), sp, sr, sp, sr, tab, tab, n, n, p.n_seg, p.c, p.heads, scale,
-                                  ptr<double>(out), p.c, ptr<double>(lse), stream_of(dev)));
-  } else {
-    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
-    me_ok(me_attn_forward_tab(q.data_ptr(), k.data_ptr(), v.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v),
-                              sp, sr, sp, sr, tab, tab, n, n, p.n_seg, p.c, p.heads, (float)scale, out.data_ptr(), p.c,
-                              ptr<float>(lse), stream_of(dev)));
-  }
-  return {out, lse};
+  const AttnPrep p = serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, mgr);
+  return list_attn_forward(q, k, v, p, scale);
 }
 
 std::vector<Tensor> serialized_attention_backward(Tensor q, Tensor k, Tensor v, Tensor out, const Tensor &lse,
@@ -1698,38 +1646,9 @@ std::vector<Tensor> serialized_attention_backward(Tensor q, Tensor k, Tensor v, 
                                                   const std::string &order, CoordinateMapKey *in_key,
                                                   CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k,
                                                   bool need_grad_v) {
-  const SerialAttnPrep p = serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, mgr);
-  out = attn_rows("out", out, &q);
-  grad_out = attn_rows("grad_out", grad_out.to(q.scalar_type()));
-  check(out.sizes() == q.sizes() && grad_out.sizes() == q.sizes(), "out and grad_out must have the shape of q");
-  const c10::Device dev = q.device();
-  const bool f64 = q.scalar_type() == at::kDouble;
-  check(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == (f64 ? at::kDouble : at::kFloat) && lse.dim() == 2 &&
-            lse.size(0) == q.size(0) && lse.size(1) == p.heads,
-        "lse must be the contiguous [n, heads] statistics of the forward pass");
-  const int64_t n = q.size(0);
-  Tensor grad_q = need_grad_q ? at::empty({n, p.c}, q.options()) : Tensor();
-  Tensor grad_k = need_grad_k ? at::empty({n, p.c}, q.options()) : Tensor();
-  Tensor grad_v = need_grad_v ? at::empty({n, p.c}, q.options()) : Tensor();
-  if (!(need_grad_q || need_grad_k || need_grad_v)) return {grad_q, grad_k, grad_v};
-  const int32_t *sp = ptr<int32_t>(p.seg_ptr), *sr = ptr<int32_t>(p.seg_rows), *tab = ptr<int32_t>(p.blk_tab);
-  c10::DeviceGuard guard(dev);
-  if (f64) {
-    me_ok(me_attn_backward_tab_f64(ptr<double>(q), ptr<double>(k), ptr<double>(v), ptr<double>(out), ptr<double>(lse),
-                                   ptr<double>(grad_out), attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out),
-                                   attn_stride(grad_out), sp, sr, sp, sr, tab, tab, n, n, p.n_seg, p.c, p.heads, scale,
-                                   ptr<double>(grad_q), p.c, ptr<double>(grad_k), p.c, ptr<double>(grad_v), p.c,
-                                   stream_of(dev)));
-  } else {
-    const int bf = q.scalar_type() == at::kBFloat16 ? 1 : 0;
-    Tensor ws = workspace(me_attn_workspace_bytes(n, n, p.n_seg, p.heads), dev);
-    me_ok(me_attn_backward_tab(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ptr<float>(lse),
-                               grad_out.data_ptr(), bf, attn_stride(q), attn_stride(k), attn_stride(v), attn_stride(out),
-                               attn_stride(grad_out), sp, sr, sp, sr, tab, tab, n, n, p.n_seg, p.c, p.heads, (float)scale,
-                               vptr(grad_q), p.c, vptr(grad_k), p.c, vptr(grad_v), p.c, vptr(ws), ws.numel(),
-                               stream_of(dev)));
-  }
-  return {grad_q, grad_k, grad_v};
+  const AttnPrep p = serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, mgr);
+  attn_backward_operands(q, out, grad_out, lse, {q.size(0), (int64_t)p.heads}, "[n, heads]");
+  return list_attn_backward(q, k, v, out, lse, grad_out, p, scale, need_grad_q, need_grad_k, need_grad_v);
 }
 
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------

@@ -21,7 +21,7 @@ from minkowskiengine_amd import host as _host
 
 pytestmark = pytest.mark.gpu
 
-BQ = BK = 64   # kAttnBlock of csrc/attention.hip: the stationary rows of a workgroup, forward and backward
+BQ = BK = 64   # kAttnBlock of csrc/attn_block.hpp: the stationary rows of a workgroup, forward and backward
 # A blocked online softmax sums in another order than torch's single pass, and on draws of a hundred rows the error of
 # either fluctuates by about a factor of two: 4 covers both.  Measured ratios E_kernel / E_torch (one run, the maximum
 # over d, layouts and hosts; out / dq / dk / dv): block edges fp32 1.12 / 1.45 / 1.75 / 1.24, bf16 1.00 / 1.83 / 1.67 / 1.67;

@@ -111,7 +111,11 @@ typedef struct me_region {
  *   1.20 (300)  round 20: cross-attention to a dense context: the row lists of a [B, L, C] context in one launch, and a
  *              dK / dV pass split over the queries with a fixed-order reduce for few keys under many queries
  *              (me_attn_context_lists, me_attn_kv_splits, me_attn_split_workspace_bytes, me_attn_backward_split and the
- *              _f64 twin me_attn_backward_split_f64) */
+ *              _f64 twin me_attn_backward_split_f64)
+ *   1.21 (310)  round 21: shifted-window attention: the window of every row of a coordinate map (boxes of w cells on a grid
+ *              anchored at the origin and moved by a shift), and row lists with a block table from any segment id per row
+ *              (me_attn_window_ids_workspace_bytes, me_attn_window_ids, me_attn_segment_lists_workspace_bytes,
+ *              me_attn_segment_lists) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1322,6 +1326,47 @@ int me_attn_backward_tab_f64(const double *q_dev, const double *k_dev, const dou
                              int64_t n_q, int64_t n_kv, int32_t n_batch, int32_t c, int32_t heads, double scale,
                              double *dq_dev, int64_t dq_stride, double *dk_dev, int64_t dk_stride, double *dv_dev,
                              int64_t dv_stride, void *stream);
+
+/* ---- shifted-window attention (MinkowskiWindowSelfAttention, MinkowskiFunctional.window_attention;
+ *      csrc/serial_attention.hip, ABI 1.21) ----
+ * Space is cut into axis-aligned boxes of window_size[a] cells of the tensor stride per spatial axis a < D = ncol - 1, on a
+ * grid anchored at the origin of the coordinate system and moved by shift[a] cells; the kernels of me_attn_forward_tab /
+ * me_attn_backward_tab attend inside every box: a window is a segment of their row lists.  The window of the row
+ * (b, c_0 .. c_{D-1}) is (b, cell_0 .. cell_{D-1}) with
+ *   cell_a = floor((floor(c_a / t_a) + s_a) / w_a),   s_a = shift[a] modulo w_a in [0, w_a)
+ * both floors towards -inf, so negative coordinates are legal and shift and shift + window_size give the same partition.
+ * Nothing is padded, there is no cyclic wrap and no mask.
+ *
+ * me_attn_window_ids: row_window int32 [n], the window of every row, the windows numbered 0 .. W - 1 in ascending
+ *   lexicographic order of (b, cell_0 .. cell_{D-1}); *n_windows_dev (int32, device memory) = W.  tensor_stride,
+ *   window_size, shift, bbox_min, bbox_max: n_axes = D host ints each; bbox_min / bbox_max: the smallest and the largest
+ *   coordinate of every spatial axis (any box that holds every row will do); batch_min / batch_max: the smallest and the
+ *   largest batch index.  A key packs b above the fields of cell_a - cell_lo_a (cell_lo_a the cell of bbox_min[a], a field
+ *   the bit count of the largest difference in the box), the library's stable radix sort orders the significant key bytes,
+ *   and the rank of a row's key among the distinct keys is its window.  Difference and quotient are taken in 64 bits: exact
+ *   for every int32 coordinate and every extent, 2^31 and more included.  No synchronisation, no read-back.
+ *   Workspace: me_attn_window_ids_workspace_bytes(n).  Host-side errors, nothing launched: a window size below 1,
+ *   n_axes != D, window_size[a] * tensor_stride[a] >= 2^31, a negative batch index, the cell bits of all axes + the bits of
+ *   batch_max > 63, a short workspace.
+ *
+ * me_attn_segment_lists: the row lists and the block table of ANY segment id per row (row_segment int32 [n], every value
+ *   in [0, n_seg)), in the layout of me_attn_patch_lists:
+ *   seg_ptr   int32 [n_seg + 1], seg_rows int32 [n]   me_csr_from_coo of row_segment: rows ascending inside a segment
+ *   blk_tab   int32 [2 * (ceil(n / 64) + n_seg)]      for every 64-row block of every non-empty segment, in segment order,
+ *                                                    (segment, first row in the segment); unused entries hold segment -1
+ *   No synchronisation, no read-back.  Workspace: me_attn_segment_lists_workspace_bytes(n, n_seg).  Host-side errors,
+ *   nothing launched: n or n_seg beyond int32, rows with n_seg = 0, a short workspace, a null output.
+ * A caller that wants no surplus workgroups reads *n_windows_dev back once (4 bytes) and passes it as n_seg; without the
+ * read-back min(n, cells in the box) is the only bound the host knows. */
+int64_t me_attn_window_ids_workspace_bytes(int64_t n);
+int me_attn_window_ids(const int32_t *coords_dev, int64_t n, int32_t ncol, const int32_t *tensor_stride,
+                       const int32_t *window_size, const int32_t *shift, int32_t n_axes, const int32_t *bbox_min,
+                       const int32_t *bbox_max, int32_t batch_min, int32_t batch_max, int32_t *row_window_dev,
+                       int32_t *n_windows_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int64_t me_attn_segment_lists_workspace_bytes(int64_t n, int64_t n_seg);
+int me_attn_segment_lists(const int32_t *row_segment_dev, int64_t n, int64_t n_seg, int32_t *seg_ptr_dev,
+                          int32_t *seg_rows_dev, int32_t *blk_tab_dev, void *workspace_dev, int64_t workspace_bytes,
+                          void *stream);
 
 /* ---- cross-attention to a dense context (MinkowskiCrossAttention, MinkowskiFunctional.cross_attention;
  *      csrc/attention.hip, ABI 1.20) ----

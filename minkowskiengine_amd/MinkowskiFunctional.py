@@ -163,5 +163,25 @@ def serialized_attention(query, key, value, num_heads, patch_size, order="z", sc
     return SparseTensor(out, coordinate_map_key=query.coordinate_map_key, coordinate_manager=query._manager)
 
 
+def window_attention(query, key, value, num_heads, window_size, shift=0, scale=None):
+    """Multi-head attention inside axis-aligned windows of `window_size` voxels per axis (an int or one int per spatial axis,
+    in units of the tensor stride) on a grid anchored at the origin and moved by `shift` voxels
+    (MinkowskiWindowSelfAttention without its projections).  `query`, `key` and `value` sit on ONE coordinate map; the
+    channels split into `num_heads` heads of 32, 64 or 128 (any size in float64); scale defaults to 1 / sqrt(head size).
+    No mask, no dropout, no cyclic wrap.  The result sits on that map."""
+    from .window_attention import MinkowskiWindowAttentionFunction
+    from .sparse_tensor import SparseTensor
+    for name, t in (("query", query), ("key", key), ("value", value)):
+        if not isinstance(t, SparseTensor):
+            raise TypeError(f"window_attention takes SparseTensors; {name} is a {type(t).__name__}")
+    for name, t in (("key", key), ("value", value)):
+        if t.coordinate_map_key != query.coordinate_map_key or t._manager is not query._manager:
+            raise ValueError(f"query, key and value must share one coordinate map; {name} sits on another")
+    out = MinkowskiWindowAttentionFunction.apply(query.F, key.F, value.F, num_heads, scale, window_size, shift,
+                                                 query.coordinate_map_key, query._manager)
+    return SparseTensor(out, coordinate_map_key=query.coordinate_map_key, coordinate_manager=query._manager)
+
+
 __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention",
-                                                "local_attention", "serialized_attention", "cross_attention"]
+                                                "local_attention", "serialized_attention", "cross_attention",
+                                                "window_attention"]

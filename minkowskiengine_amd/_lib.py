@@ -206,6 +206,11 @@ SIGNATURES = {
     "me_attn_backward_tab_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp,
                                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32,
                                                 ctypes.c_double, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "me_attn_window_ids_workspace_bytes": (c_i64, [c_i64]),
+    "me_attn_window_ids": (ctypes.c_int, [c_vp, c_i64, c_i32, _P_I32, _P_I32, _P_I32, c_i32, _P_I32, _P_I32, c_i32, c_i32,
+                                          c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_attn_segment_lists_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "me_attn_segment_lists": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "me_attn_context_lists": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "me_attn_kv_splits": (c_i32, [c_i64, c_i64, c_i32, c_i32, c_i32]),
     "me_attn_split_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32, c_i32, c_i32]),

@@ -16,6 +16,7 @@ implementation here: CPU tensors are rejected (the reference's CPU path is the t
 """
 import ctypes
 import enum
+import operator
 import os
 import weakref
 import random
@@ -755,6 +756,7 @@ class CoordinateMapManagerGPU_c10:
         self._origin_maps = {}
         self._instance_rows_cache = {}
         self._patch_rows_cache = {}     # (map key, patch size, order code) -> (seg_ptr, seg_rows, blk_tab, row_patch)
+        self._window_rows_cache = {}    # (map key, window sizes, reduced shifts) -> (seg_ptr, seg_rows, blk_tab, row_window)
         self._context_rows_cache = {}   # (instances, tokens, device) -> (seg_ptr, seg_rows, blk_tab)
         self._prune_rows = {}
         self._union_arith = {}   # (key a, key b), ordered -> (union key, u_of_a, u_of_b, a_of_u, b_of_u): union_arith_maps
@@ -1320,6 +1322,57 @@ class CoordinateMapManagerGPU_c10:
             lists = self._patch_rows_cache[ck] = (seg_ptr, seg_rows, blk_tab, row_patch)
         return lists
 
+    def _window_rows(self, in_key, window_size, shift=0):
+        """(seg_ptr int32 [W + 1], seg_rows int32 [n], blk_tab int32 [2 (ceil(n / 64) + W)], row_window int32 [n]) of window
+        attention: the rows of `in_key` inside every axis-aligned box of `window_size` cells of the tensor stride, the grid
+        anchored at the origin and moved by `shift` cells (an int or one int per spatial axis each; shifts count modulo
+        the window).  cell_a = floor((c_a / t_a + s_a) / w_a); the W windows are numbered in ascending order of (batch,
+        cell_0 .. cell_{D-1}) (me_attn_window_ids, me_attn_segment_lists, csrc/serial_attention.hip).  Cached per (map,
+        window sizes, reduced shifts).  Building an entry reads W back (4 bytes, one synchronisation), so that the
+        attention launches carry no empty segments; a derived map takes one reduction and one more read-back for its
+        bounding box.  The attention calls read nothing back: build the lists BEFORE a graph capture."""
+        ik = self._k(in_key)
+        m = self._get(ik)
+        n, ncol = int(m.n), int(m.coords.shape[1])
+        ws_, sh_ = window_args(window_size, shift, ncol - 1)
+        ck = (ik, ws_, sh_)
+        lists = self._window_rows_cache.get(ck)
+        if lists is None:
+            self._origin_rows(in_key)                   # (checks once that the origin map knows every batch index)
+            bbox = m.bbox
+            if n > 0 and (bbox is None or len(bbox) != 2 * ncol):
+                bbox = torch.cat((m.coords.amin(0), m.coords.amax(0))).tolist()
+            ts = [int(t) for t in m.tensor_stride]
+            lo = [int(bbox[1 + a]) if n > 0 else 0 for a in range(ncol - 1)]
+            hi = [int(bbox[ncol + 1 + a]) if n > 0 else 0 for a in range(ncol - 1)]
+            batch_min, batch_max = (int(bbox[0]), int(bbox[ncol])) if n > 0 else (0, 0)
+            _check(batch_min >= 0, "batch indices must not be negative")
+            bits = batch_max.bit_length()
+            for a in range(ncol - 1):
+                wt, off = ws_[a] * ts[a], sh_[a] * ts[a]
+                _check(wt < (1 << 31), "window_size * tensor_stride must fit in int32, got", ws_[a], "*", ts[a])
+                bits += ((hi[a] + off) // wt - (lo[a] + off) // wt).bit_length()
+            _check(bits <= 63, "the window key of this map needs", bits, "bits (cells of every axis + batch): more than 63")
+            lib = _lib.load()
+            dev = m.coords.device
+            row_window = torch.empty(n, dtype=torch.int32, device=dev)
+            count = torch.zeros(1, dtype=torch.int32, device=dev)
+            i32s = lambda v: (ctypes.c_int32 * (ncol - 1))(*v)   # noqa: E731
+            ws = _workspace(int(lib.me_attn_window_ids_workspace_bytes(n)), dev)
+            with _on(dev):
+                _lib.check(lib.me_attn_window_ids(_ptr(m.coords), n, ncol, i32s(ts), i32s(ws_), i32s(sh_), ncol - 1,
+                                                  i32s(lo), i32s(hi), batch_min, batch_max, _ptr(row_window), _ptr(count),
+                                                  _ptr(ws), ws.numel(), _stream(dev)))
+                n_seg = int(count.item())               # the one read-back of an entry
+                seg_ptr = torch.empty(n_seg + 1, dtype=torch.int32, device=dev)
+                seg_rows = torch.empty(n, dtype=torch.int32, device=dev)
+                blk_tab = torch.empty(2 * (-(-n // 64) + n_seg), dtype=torch.int32, device=dev)
+                ws = _workspace(int(lib.me_attn_segment_lists_workspace_bytes(n, n_seg)), dev)
+                _lib.check(lib.me_attn_segment_lists(_ptr(row_window), n, n_seg, _ptr(seg_ptr), _ptr(seg_rows),
+                                                     _ptr(blk_tab), _ptr(ws), ws.numel(), _stream(dev)))
+            lists = self._window_rows_cache[ck] = (seg_ptr, seg_rows, blk_tab, row_window)
+        return lists
+
     def _context_rows(self, n_batch, tokens, device, lengths=None):
         """(seg_ptr int32 [B + 1], seg_rows int32 [B L], blk_tab int32 [2 (ceil(B L / 64) + B)]) of a dense context of
         B = n_batch instances of L = tokens rows (me_attn_context_lists, csrc/attention.hip): instance b holds the rows
@@ -1444,7 +1497,7 @@ class CoordinateMapManagerGPU_c10:
                     if name not in ("_recipe", "in_map", "out_map"):
                         walk(getattr(o, name, None), depth + 1)
         for store in (self._maps, self._kernel_maps, self._origin_maps, self._instance_rows_cache, self._patch_rows_cache,
-                      self._context_rows_cache,
+                      self._window_rows_cache, self._context_rows_cache,
                       self._origin_field_maps, self._prune_rows,
                       self._stride_maps, self._union_arith):
             walk(store)
@@ -3910,6 +3963,61 @@ def SerializedAttentionBackwardGPU(q, k, v, out, lse, grad_out, num_heads, scale
     q, k, v, heads, c, lists, n_seg = _serial_attn_prepare(q, k, v, num_heads, patch_size, order, in_key, manager)
     out, grad_out = _attn_backward_operands(q, out, grad_out, lse, (q.shape[0], heads), "[n, heads]")
     return _list_attn_backward("serial_attn_backward", q, k, v, out, lse, grad_out, lists, lists, n_seg, heads, c, scale,
+                               need_grad_q, need_grad_k, need_grad_v)
+
+
+# ------------------------------------------------------------------------------------------------
+# shifted-window attention (csrc/serial_attention.hip, ABI 1.21 + the _tab entry points of csrc/attention.hip; not in the
+# reference): space cut into axis-aligned boxes of window_size cells, the grid moved by shift cells; a row attends inside
+# its box.  q, k, v sit on ONE map; the lists and the block table come from manager._window_rows.
+# ------------------------------------------------------------------------------------------------
+def window_args(window_size, shift, dimension):
+    """-> (window sizes, shifts reduced modulo them): one int per spatial axis each, from an int (all axes) or one int per
+    axis"""
+    def per_axis(name, v):
+        try:
+            if not hasattr(v, "__len__"):
+                return [operator.index(v)] * dimension
+            v = [operator.index(e) for e in v]
+        except TypeError:
+            v = None
+        if v is None or len(v) != dimension:
+            raise ValueError(f"{name} must be an int or one int per spatial axis ({dimension}), got {v!r}")
+        return v
+    sizes, shifts = per_axis("window_size", window_size), per_axis("shift", shift)
+    if min(sizes) < 1:
+        raise ValueError(f"window_size must be at least 1, got {window_size!r}")
+    return tuple(sizes), tuple(s % w for s, w in zip(shifts, sizes))
+
+
+def _window_attn_prepare(q, k, v, num_heads, window_size, shift, in_key, manager):
+    q = _attn_rows("q", q)
+    k = _attn_rows("k", k, q)
+    v = _attn_rows("v", v, q)
+    _check(manager.exists(in_key), "coordinate map not found")
+    n = manager.size(in_key)
+    _check(q.shape[0] == n and k.shape[0] == n and v.shape[0] == n, "Invalid q / k / v size", q.shape[0], k.shape[0],
+           v.shape[0], "!=", n)
+    heads, c = int(num_heads), int(q.shape[1])
+    _check(heads > 0 and c % heads == 0, "the channel count", c, "must be a multiple of num_heads", heads)
+    lists = manager._window_rows(in_key, window_size, shift)[:3]
+    return q, k, v, heads, c, lists, int(lists[0].numel()) - 1
+
+
+def WindowAttentionForwardGPU(q, k, v, num_heads, scale, window_size, shift, in_key, manager):
+    """-> (out [n, C], lse [n, heads]): out[i, h] = sum_j softmax_j(scale <q[i, h], k[j, h]>) v[j, h] over the rows j of the
+    window of row i (manager._window_rows(in_key, window_size, shift)); lse in fp32 (float64 for float64 features)."""
+    q, k, v, heads, c, lists, n_seg = _window_attn_prepare(q, k, v, num_heads, window_size, shift, in_key, manager)
+    return _list_attn_forward("window_attn_forward", q, k, v, lists, lists, n_seg, heads, c, scale)
+
+
+def WindowAttentionBackwardGPU(q, k, v, out, lse, grad_out, num_heads, scale, window_size, shift, in_key, manager,
+                               need_grad_q=True, need_grad_k=True, need_grad_v=True):
+    """-> (grad_q | None, grad_k | None, grad_v | None), contiguous, from out and lse of the forward pass; a gradient that
+    is not requested is not computed (AttentionBackwardGPU's rule)."""
+    q, k, v, heads, c, lists, n_seg = _window_attn_prepare(q, k, v, num_heads, window_size, shift, in_key, manager)
+    out, grad_out = _attn_backward_operands(q, out, grad_out, lse, (q.shape[0], heads), "[n, heads]")
+    return _list_attn_backward("window_attn_backward", q, k, v, out, lse, grad_out, lists, lists, n_seg, heads, c, scale,
                                need_grad_q, need_grad_k, need_grad_v)
 
 

@@ -189,6 +189,18 @@ class CoordinateManager:
         of patch p, ascending; blk_tab is the block table of the attention kernels.  Cached per (map, size, order)."""
         return self._manager._patch_rows(key, int(patch_size), order)
 
+    def window_rows(self, key, window_size, shift=0):
+        """(seg_ptr, seg_rows, blk_tab, row_window) of window attention on the map `key`: space cut into axis-aligned boxes
+        of `window_size` cells of the tensor stride on a grid anchored at the origin and moved by `shift` cells (an int or
+        one int per spatial axis each; shifts count modulo the window).  row_window int32 [N] is the window of every row,
+        cell_a = floor((c_a / t_a + s_a) / w_a), the W windows numbered in ascending order of (batch, cell_0 ..
+        cell_{D-1}); seg_rows[seg_ptr[w] : seg_ptr[w + 1]] are the rows of window w, ascending; blk_tab is the block table
+        of the attention kernels.  Cached per (map, sizes, reduced shifts).  Building an entry reads W back (one
+        synchronisation): call this, or run one forward pass, before a graph capture."""
+        from .window_attention import _check_window
+        window_size, shift = _check_window(window_size, shift, self.D)
+        return self._manager._window_rows(key, window_size, shift)
+
     def origin_field(self, field_key=None):
         """Key of the origin map (the key origin() returns), built from the batch indices of a field when absent:
         `field_key`, or the oldest field of the manager (MinkowskiCoordinateManager.py:273)."""

@@ -97,6 +97,11 @@ struct BnFn : public torch::autograd::Function<BnFn> {
   }
 };
 
+// window_size / shift of window attention: an int (all axes) or one int per spatial axis
+ivec axes_arg(const py::object &o) {
+  if (py::isinstance<py::int_>(o)) return ivec{py::cast<int32_t>(o)};
+  return py::cast<ivec>(o);
+}
 Tensor opt_tensor(const py::object &o) { return o.is_none() ? Tensor() : py::cast<Tensor>(o); }
 c10::optional<Tensor> opt_opt(const py::object &o) {
   return o.is_none() ? c10::optional<Tensor>() : c10::optional<Tensor>(py::cast<Tensor>(o));
@@ -279,6 +284,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              const auto &r = s.patch_rows(keyt(k), patch_size, serial_order_code(order));
              return py::make_tuple(r[0], r[1], r[2], r[3]);
            })
+      .def("_window_rows",
+           [](CoordinateMapManager &s, const CoordinateMapKey *k, const py::object &window_size, const py::object &shift) {
+             const auto &r = s.window_rows(keyt(k), axes_arg(window_size), axes_arg(shift));
+             return py::make_tuple(r[0], r[1], r[2], r[3]);
+           },
+           py::arg("key"), py::arg("window_size"), py::arg("shift") = py::int_(0))
       .def("_context_rows",
            [](CoordinateMapManager &s, int64_t n_batch, int64_t tokens, const py::object &device,
               const py::object &lengths) {
@@ -759,6 +770,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         },
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("grad_out"),
         py::arg("num_heads"), py::arg("scale"), py::arg("patch_size"), py::arg("order"), py::arg("in_key"),
+        py::arg("manager"), py::arg("need_grad_q") = true, py::arg("need_grad_k") = true, py::arg("need_grad_v") = true);
+  // shifted-window attention: the attention kernels on the window lists and block table of csrc/serial_attention.hip
+  m.def("WindowAttentionForwardGPU",
+        [](const Tensor &q, const Tensor &k, const Tensor &v, int64_t num_heads, double scale, const py::object &window_size,
+           const py::object &shift, CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+          const ivec ws = axes_arg(window_size), sh = axes_arg(shift);
+          std::pair<Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = window_attention_forward(q, k, v, num_heads, scale, ws, sh, in_key, mgr);
+          }
+          return py::make_tuple(r.first, r.second);
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("num_heads"), py::arg("scale"), py::arg("window_size"),
+        py::arg("shift"), py::arg("in_key"), py::arg("manager"));
+  m.def("WindowAttentionBackwardGPU",
+        [](const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse, const Tensor &grad_out,
+           int64_t num_heads, double scale, const py::object &window_size, const py::object &shift,
+           CoordinateMapKey *in_key, CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k, bool need_grad_v) {
+          const ivec ws = axes_arg(window_size), sh = axes_arg(shift);
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = window_attention_backward(q, k, v, out, lse, grad_out, num_heads, scale, ws, sh, in_key, mgr, need_grad_q,
+                                          need_grad_k, need_grad_v);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]));
+        },
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("grad_out"),
+        py::arg("num_heads"), py::arg("scale"), py::arg("window_size"), py::arg("shift"), py::arg("in_key"),
         py::arg("manager"), py::arg("need_grad_q") = true, py::arg("need_grad_k") = true, py::arg("need_grad_v") = true);
   // tensor fields (field.cpp): the reference's InterpolationForwardGPU / InterpolationBackwardGPU and coo_spmm_int32 /
   // coo_spmm_average_int32 (pybind/extern.hpp:497-506), plus the CSR building blocks the autograd functions cache

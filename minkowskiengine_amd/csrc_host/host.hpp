@@ -257,6 +257,8 @@ struct CoordinateMapManager {
   std::map<KeyT, std::pair<Tensor, Tensor>> instance_rows_cache;   // per-instance row lists (seg_ptr, seg_rows)
   // serialized patch attention: (map, patch size, order code) -> {seg_ptr, seg_rows, blk_tab, row_patch}
   std::map<std::tuple<KeyT, int64_t, int>, std::vector<Tensor>> patch_rows_cache;
+  // window attention: (map, window sizes, reduced shifts) -> {seg_ptr, seg_rows, blk_tab, row_window}
+  std::map<std::tuple<KeyT, ivec, ivec>, std::vector<Tensor>> window_rows_cache;
   // cross-attention: (instances, tokens, device index) -> {seg_ptr, seg_rows, blk_tab} of a dense context
   std::map<std::tuple<int64_t, int64_t, int>, std::vector<Tensor>> context_rows_cache;
   std::map<std::pair<KeyT, KeyT>, Tensor> prune_rows;
@@ -300,6 +302,11 @@ struct CoordinateMapManager {
   // {seg_ptr, seg_rows, blk_tab, row_patch} of serialized patch attention (me_attn_patch_lists), cached per (map, patch
   // size, order code 0 z / 1 z_trans / 2 hilbert / 3 hilbert_trans): twin of backend._patch_rows
   const std::vector<Tensor> &patch_rows(const KeyT &in_key, int64_t patch_size, int order);
+  // {seg_ptr, seg_rows, blk_tab, row_window} of window attention (me_attn_window_ids, me_attn_segment_lists): the rows
+  // inside every box of window_size cells, the grid moved by shift cells (one value per spatial axis each); cached per
+  // (map, window sizes, shifts modulo them).  Building an entry reads the window count back once.  Twin of
+  // backend._window_rows
+  const std::vector<Tensor> &window_rows(const KeyT &in_key, const ivec &window_size, const ivec &shift);
   // {seg_ptr, seg_rows, blk_tab} of a dense context of n_batch x tokens rows (me_attn_context_lists): cached per
   // (n_batch, tokens, device) without lengths, built per call with them (int32 [n_batch] on the device): twin of
   // backend._context_rows
@@ -433,6 +440,15 @@ std::vector<Tensor> serialized_attention_backward(Tensor q, Tensor k, Tensor v, 
                                                   const std::string &order, CoordinateMapKey *in_key,
                                                   CoordinateMapManager *mgr, bool need_grad_q, bool need_grad_k,
                                                   bool need_grad_v);
+// shifted-window attention (csrc/serial_attention.hip; twin of backend.WindowAttention{Forward,Backward}GPU)
+std::pair<ivec, ivec> window_args(const ivec &window_size, const ivec &shift, int dimension);
+std::pair<Tensor, Tensor> window_attention_forward(Tensor q, Tensor k, Tensor v, int64_t num_heads, double scale,
+                                                   const ivec &window_size, const ivec &shift, CoordinateMapKey *in_key,
+                                                   CoordinateMapManager *mgr);
+std::vector<Tensor> window_attention_backward(Tensor q, Tensor k, Tensor v, Tensor out, const Tensor &lse, Tensor grad_out,
+                                              int64_t num_heads, double scale, const ivec &window_size, const ivec &shift,
+                                              CoordinateMapKey *in_key, CoordinateMapManager *mgr, bool need_grad_q,
+                                              bool need_grad_k, bool need_grad_v);
 // dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU / DensePolicy)
 int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box);
 std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,

@@ -1159,6 +1159,61 @@ const std::vector<Tensor> &CoordinateMapManager::patch_rows(const KeyT &in_key, 
   return patch_rows_cache[ck] = {seg_ptr, seg_rows, blk_tab, row_patch};
 }
 
+const std::vector<Tensor> &CoordinateMapManager::window_rows(const KeyT &in_key, const ivec &window_size,
+                                                             const ivec &shift) {
+  auto m = get(in_key);
+  const int64_t n = m->n;
+  const int ncol = (int)m->coords.size(1);
+  const auto args = window_args(window_size, shift, ncol - 1);
+  const auto ck = std::make_tuple(in_key, args.first, args.second);
+  auto it = window_rows_cache.find(ck);
+  if (it != window_rows_cache.end()) return it->second;
+  origin_rows(in_key);   // (checks once that the origin map knows every batch index)
+  std::vector<int64_t> bb(m->bbox.begin(), m->bbox.end());
+  if (n > 0 && (int)bb.size() != 2 * ncol) {   // a derived map: one reduction and one read-back
+    Tensor lohi = at::cat({m->coords.amin(0), m->coords.amax(0)}).to(at::kLong).cpu();
+    bb.assign(lohi.data_ptr<int64_t>(), lohi.data_ptr<int64_t>() + 2 * ncol);
+  }
+  auto bits = [](int64_t x) { int b = 0; while (x > 0) { ++b; x >>= 1; } return b; };
+  auto floor_div = [](int64_t a, int64_t b) { return a / b - ((a % b != 0) && ((a < 0) != (b < 0)) ? 1 : 0); };
+  std::vector<int32_t> ts(ncol - 1), ws(ncol - 1), sh(ncol - 1), lo(ncol - 1, 0), hi(ncol - 1, 0);
+  const int64_t batch_min = n > 0 ? bb[0] : 0, batch_max = n > 0 ? bb[ncol] : 0;
+  check(batch_min >= 0, "batch indices must not be negative");
+  int key_bits = bits(batch_max);
+  for (int a = 0; a < ncol - 1; ++a) {
+    ts[a] = (int32_t)m->tensor_stride[a];
+    const int64_t wt = args.first[a] * (int64_t)ts[a], off = args.second[a] * (int64_t)ts[a];
+    check(wt < (1ll << 31), "window_size * tensor_stride must fit in int32, got " + std::to_string(args.first[a]) + " * " +
+                                std::to_string(ts[a]));
+    ws[a] = (int32_t)args.first[a];
+    sh[a] = (int32_t)args.second[a];
+    if (n > 0) {
+      lo[a] = (int32_t)bb[1 + a];
+      hi[a] = (int32_t)bb[ncol + 1 + a];
+      key_bits += bits(floor_div(hi[a] + off, wt) - floor_div(lo[a] + off, wt));
+    }
+  }
+  check(key_bits <= 63, "the window key of this map needs " + std::to_string(key_bits) +
+                            " bits (cells of every axis + batch): more than 63");
+  const c10::Device dev = m->coords.device();
+  auto i32 = at::TensorOptions().dtype(at::kInt).device(dev);
+  Tensor row_window = at::empty({n}, i32), count = at::zeros({1}, i32);
+  c10::DeviceGuard guard(dev);
+  {
+    Tensor wsp = workspace(me_attn_window_ids_workspace_bytes(n), dev);
+    me_ok(me_attn_window_ids(ptr<int32_t>(m->coords), n, ncol, ts.data(), ws.data(), sh.data(), ncol - 1, lo.data(),
+                             hi.data(), (int32_t)batch_min, (int32_t)batch_max, ptr<int32_t>(row_window),
+                             ptr<int32_t>(count), vptr(wsp), wsp.numel(), stream_of(dev)));
+  }
+  const int64_t n_seg = count.item<int32_t>();   // the one read-back of an entry
+  Tensor seg_ptr = at::empty({n_seg + 1}, i32), seg_rows = at::empty({n}, i32);
+  Tensor blk_tab = at::empty({2 * ((n + 63) / 64 + n_seg)}, i32);
+  Tensor wsp = workspace(me_attn_segment_lists_workspace_bytes(n, n_seg), dev);
+  me_ok(me_attn_segment_lists(ptr<int32_t>(row_window), n, n_seg, ptr<int32_t>(seg_ptr), ptr<int32_t>(seg_rows),
+                              ptr<int32_t>(blk_tab), vptr(wsp), wsp.numel(), stream_of(dev)));
+  return window_rows_cache[ck] = {seg_ptr, seg_rows, blk_tab, row_window};
+}
+
 std::vector<Tensor> CoordinateMapManager::context_rows(int64_t n_batch, int64_t tokens, const c10::Device &dev,
                                                        const Tensor &lengths) {
   check(n_batch >= 0 && tokens >= 1, "a context needs at least one token per instance, got " + std::to_string(tokens));
@@ -1409,6 +1464,8 @@ std::vector<Tensor> CoordinateMapManager::device_tensors() {
     collect(out, kv.second.second);
   }
   for (auto &kv : patch_rows_cache)
+    for (auto &t : kv.second) collect(out, t);
+  for (auto &kv : window_rows_cache)
     for (auto &t : kv.second) collect(out, t);
   for (auto &kv : context_rows_cache)
     for (auto &t : kv.second) collect(out, t);

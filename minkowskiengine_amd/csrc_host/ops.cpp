@@ -1651,6 +1651,57 @@ std::vector<Tensor> serialized_attention_backward(Tensor q, Tensor k, Tensor v, 
   return list_attn_backward(q, k, v, out, lse, grad_out, p, scale, need_grad_q, need_grad_k, need_grad_v);
 }
 
+// ---- shifted-window attention (csrc/serial_attention.hip, ABI 1.21 + the _tab entry points of csrc/attention.hip; twin of
+// backend.WindowAttention{Forward,Backward}GPU): q, k, v on ONE map, lists and block table from mgr->window_rows ------------
+// (window sizes, shifts reduced modulo them), one value per spatial axis each, from one value (all axes) or one per axis
+std::pair<ivec, ivec> window_args(const ivec &window_size, const ivec &shift, int dimension) {
+  auto per_axis = [&](const char *name, const ivec &v) {
+    if ((int)v.size() == dimension) return v;
+    if (v.size() == 1) return ivec((size_t)dimension, v[0]);
+    throw std::invalid_argument(std::string(name) + " must be an int or one int per spatial axis (" +
+                                std::to_string(dimension) + "), got " + std::to_string(v.size()) + " values");
+  };
+  ivec sizes = per_axis("window_size", window_size), shifts = per_axis("shift", shift);
+  for (int a = 0; a < dimension; ++a) {
+    if (sizes[a] < 1) throw std::invalid_argument("window_size must be at least 1, got " + std::to_string(sizes[a]));
+    shifts[a] = (int32_t)((((int64_t)shifts[a] % sizes[a]) + sizes[a]) % sizes[a]);
+  }
+  return {sizes, shifts};
+}
+
+static AttnPrep window_attn_prepare(Tensor &q, Tensor &k, Tensor &v, int64_t num_heads, const ivec &window_size,
+                                    const ivec &shift, CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+  q = attn_rows("q", q);
+  k = attn_rows("k", k, &q);
+  v = attn_rows("v", v, &q);
+  const KeyT &ik = in_key->get();
+  check(mgr->exists(ik), "coordinate map not found");
+  const int64_t n = mgr->get(ik)->n;
+  check(q.size(0) == n && k.size(0) == n && v.size(0) == n, "Invalid q / k / v size");
+  const int64_t c = q.size(1);
+  check(num_heads > 0 && c % num_heads == 0, "the channel count " + std::to_string(c) +
+                                                 " must be a multiple of num_heads " + std::to_string(num_heads));
+  const std::vector<Tensor> &l = mgr->window_rows(ik, window_size, shift);
+  const AttnList lists{l[0], l[1], l[2]};
+  return {(int)num_heads, (int)c, (int)l[0].numel() - 1, lists, lists};
+}
+
+std::pair<Tensor, Tensor> window_attention_forward(Tensor q, Tensor k, Tensor v, int64_t num_heads, double scale,
+                                                   const ivec &window_size, const ivec &shift, CoordinateMapKey *in_key,
+                                                   CoordinateMapManager *mgr) {
+  const AttnPrep p = window_attn_prepare(q, k, v, num_heads, window_size, shift, in_key, mgr);
+  return list_attn_forward(q, k, v, p, scale);
+}
+
+std::vector<Tensor> window_attention_backward(Tensor q, Tensor k, Tensor v, Tensor out, const Tensor &lse, Tensor grad_out,
+                                              int64_t num_heads, double scale, const ivec &window_size, const ivec &shift,
+                                              CoordinateMapKey *in_key, CoordinateMapManager *mgr, bool need_grad_q,
+                                              bool need_grad_k, bool need_grad_v) {
+  const AttnPrep p = window_attn_prepare(q, k, v, num_heads, window_size, shift, in_key, mgr);
+  attn_backward_operands(q, out, grad_out, lse, {q.size(0), (int64_t)p.heads}, "[n, heads]");
+  return list_attn_backward(q, k, v, out, lse, grad_out, p, scale, need_grad_q, need_grad_k, need_grad_v);
+}
+
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------
 Tensor pruning_forward(const Tensor &in_feat, const Tensor &keep, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr) {

@@ -1,0 +1,27 @@
+"""Host-side checks of examples/window_attention_block.py: the stage is built from the package's layers, alternates shift 0
+and window_size // 2 over its blocks and carries MinkowskiSelfAttention's parameters (the GPU run:
+tests/test_gpu_window_attention.py)."""
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+
+
+def test_window_stage_is_conv_norm_window_attention_and_mlp_alternating_the_shift():
+    import minkowskiengine_amd as ME
+    import window_attention_block as WB
+    stage = WB.WindowStage(64, 2, depth=5, window_size=6)
+    assert [b.attn.shift for b in stage.blocks] == [0, 3, 0, 3, 0]
+    for block in stage.blocks:
+        assert isinstance(block.cpe, ME.MinkowskiConvolution) and block.cpe.kernel_generator.kernel_volume == 27
+        assert list(block.cpe.kernel_generator.kernel_stride) == [1, 1, 1]
+        assert isinstance(block.norm1, ME.MinkowskiGroupNorm) and isinstance(block.norm2, ME.MinkowskiGroupNorm)
+        assert isinstance(block.attn, ME.MinkowskiWindowSelfAttention)
+        assert (block.attn.embed_dim, block.attn.num_heads, block.attn.window_size) == (64, 2, 6)
+        assert isinstance(block.mlp[0], ME.MinkowskiLinear) and isinstance(block.mlp[2], ME.MinkowskiLinear)
+        assert (block.mlp[0].linear.out_features, block.mlp[2].linear.out_features) == (256, 64)
+    block = stage.blocks[1]
+    names = sorted(k for k, _ in block.named_parameters() if k.startswith("attn."))
+    assert names == ["attn.in_proj_bias", "attn.in_proj_weight", "attn.out_proj.bias", "attn.out_proj.weight"]
+    ME.MinkowskiSelfAttention(64, 2).load_state_dict(
+        {k[5:]: v for k, v in block.state_dict().items() if k.startswith("attn.")}, strict=True)

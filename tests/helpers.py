@@ -91,18 +91,19 @@ def middle(n, dtype, device, fill, pad=GUARD_PAD):
 
 class Guarded:
     """An output buffer of n 2- or 4-byte elements in the middle of a position-dependent bit pattern.  fill() puts a NaN
-    bit pattern inside before a launch; intact() says whether the surroundings still hold the pattern."""
+    bit pattern inside before a launch; intact() says whether the surroundings still hold the pattern.  `shift` elements
+    move the inside off its 16-byte boundary (a kernel whose vector width follows the address)."""
     NAN = {2: 0x7fc1, 4: 0x7fc00001}
 
-    def __init__(self, n, elem_bytes, device, base=0, pad=GUARD_PAD):
+    def __init__(self, n, elem_bytes, device, base=0, pad=GUARD_PAD, shift=0):
         idt = {2: torch.int16, 4: torch.int32}[elem_bytes]
         start = {2: 0x4000, 4: 0x40000000}[elem_bytes]
-        self.big = ((torch.arange(2 * pad + n, device=device) % 251) + start + base).to(idt)
-        self.bits = self.big[pad:pad + n]
-        self.before, self.after = self.big[:pad].clone(), self.big[pad + n:].clone()
+        self.big = ((torch.arange(2 * pad + shift + n, device=device) % 251) + start + base).to(idt)
+        self.bits = self.big[pad + shift:pad + shift + n]
+        self.before, self.after = self.big[:pad + shift].clone(), self.big[pad + shift + n:].clone()
         self.nan = self.NAN[elem_bytes]
-        self.pad, self.n = pad, n
-        assert self.bits.data_ptr() % 16 == 0
+        self.pad, self.n = pad + shift, n
+        assert (self.big.data_ptr() + pad * elem_bytes) % 16 == 0
 
     def ptr(self):
         return self.bits.data_ptr()

@@ -179,13 +179,14 @@ def test_channelwise_hosts_and_runs_bitwise_equal(device, dtype, C, ks, st):
         assert torch.equal(v, w), f"{name}: two runs differ"
 
 
-@pytest.mark.parametrize("C", [8, 17, 64])
-def test_channelwise_bf16(device, host_layer, C):
+# (kernel size 2: volume 8, one k-group of 4-channel pieces — the fused bf16 backward with dx)
+@pytest.mark.parametrize("C,ks", [(8, 3), (17, 3), (64, 3), (64, 2)], ids=["8", "17", "64", "64-k2"])
+def test_channelwise_bf16(device, host_layer, C, ks):
     import minkowskiengine_amd as ME
     coords = make_cloud(3000, 16, 3, seed=11, batch=2)
     g = torch.Generator().manual_seed(C)
     feats = (torch.rand(coords.shape[0], C, generator=g) - 0.5).bfloat16()
-    layer = ME.MinkowskiChannelwiseConvolution(C, kernel_size=3, bias=True, dimension=3).to(device)
+    layer = ME.MinkowskiChannelwiseConvolution(C, kernel_size=ks, bias=True, dimension=3).to(device)
     with torch.no_grad():
         layer.bias.uniform_(-0.5, 0.5)
     x = ME.SparseTensor(feats.to(device), coords.to(device), requires_grad=True)
@@ -194,7 +195,7 @@ def test_channelwise_bf16(device, host_layer, C):
     gy = (torch.rand(y.F.shape, generator=g) - 0.5).bfloat16()
     y.F.backward(gy.to(device))
     assert layer.kernel.grad.dtype == torch.float32 and layer.bias.grad.dtype == torch.float32
-    km = x.coordinate_manager.kernel_map(x.coordinate_map_key, y.coordinate_map_key, 1, 3, 1)
+    km = x.coordinate_manager.kernel_map(x.coordinate_map_key, y.coordinate_map_key, 1, ks, 1)
     x64 = feats.double().to(device).requires_grad_(True)
     w64 = layer.kernel.detach().double().requires_grad_(True)
     b64 = layer.bias.detach().double().requires_grad_(True)
@@ -250,7 +251,7 @@ def test_channelwise_rows_without_neighbours(device, host_layer, bias):
     assert torch.equal(y.F[lonely.to(device)], want)
 
 
-@pytest.mark.parametrize("C", [3, 17])
+@pytest.mark.parametrize("C", [3, 17, 8])      # (8: 4-channel pieces by c, one channel by the address)
 def test_channelwise_tight_feature_view(device, host_layer, C):
     """features and output gradient are views that end exactly at the end of their storage"""
     import minkowskiengine_amd as ME

@@ -115,7 +115,9 @@ typedef struct me_region {
  *   1.21 (310)  round 21: shifted-window attention: the window of every row of a coordinate map (boxes of w cells on a grid
  *              anchored at the origin and moved by a shift), and row lists with a block table from any segment id per row
  *              (me_attn_window_ids_workspace_bytes, me_attn_window_ids, me_attn_segment_lists_workspace_bytes,
- *              me_attn_segment_lists) */
+ *              me_attn_segment_lists)
+ *   1.22 (320)  round 22: rotary position embedding from voxel coordinates: the (cos, sin) table of a coordinate map and the
+ *              rotation of the channel pairs of strided rows, forward and backward (me_rope_table, me_rope_apply) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1367,6 +1369,49 @@ int64_t me_attn_segment_lists_workspace_bytes(int64_t n, int64_t n_seg);
 int me_attn_segment_lists(const int32_t *row_segment_dev, int64_t n, int64_t n_seg, int32_t *seg_ptr_dev,
                           int32_t *seg_rows_dev, int32_t *blk_tab_dev, void *workspace_dev, int64_t workspace_bytes,
                           void *stream);
+
+/* ---- rotary position embedding from voxel coordinates (MinkowskiRotaryEmbedding, MinkowskiFunctional.rotary_embedding,
+ *      the rope= argument of the self-attention modules; csrc/rope.hip, ABI 1.22) ----
+ * x is [n, heads * d] on a coordinate map with D = ncol - 1 spatial axes.  d is even and P = d / 2 >= D.  Pairs are
+ * interleaved: pair p of a head is the channels (2p, 2p + 1) of that head; every head takes the same angles.
+ *   m = P / D (integer division) frequencies per axis; pair p < D * m belongs to axis a = p / m and frequency j = p % m;
+ *   the P - D * m trailing pairs pass through unchanged (cos 1, sin 0).
+ *   omega_j = base^(-j / m), computed once per call on the host in double (pow), inside the library.
+ *   theta   = ((double)c_a / (double)u_a) * omega_j, evaluated in that order; u_a >= 1 is the unit of axis a (the host
+ *             layers pass the tensor stride of the map by default; no floor is taken, queries and keys on maps of
+ *             different strides take one common unit).
+ *   y[2p]     = x[2p] cos(theta) - s x[2p + 1] sin(theta)
+ *   y[2p + 1] = s x[2p] sin(theta) + x[2p + 1] cos(theta)        s = sign = +1 forward, -1 backward
+ * The rotation is orthogonal: the backward pass of the operator is the operator with sign = -1 applied to the gradient of
+ * the output.  After it <y_i, y_j> of two rows depends on c_i - c_j only.
+ *
+ * me_rope_table: table[n][P][2] = (cos theta, sin theta), float (table_f64 = 0; for fp32 and bf16 rows) or double
+ *   (table_f64 != 0; for float64 rows), 16-byte aligned.  Angle, range reduction and sin / cos are in double, the values
+ *   rounded once.  unit: D host ints.  One launch, no synchronisation, no read-back, no workspace.
+ *   Host-side errors, nothing launched: ncol outside [2, 8], d odd or below 2, d / 2 < D, d / 2 > ME_ROPE_MAX_PAIRS (the
+ *   angular frequencies travel in the kernel arguments), base not finite or <= 0, a unit below 1, n >= 2^31, a null coords
+ *   or table with n > 0, a table that is not 16-byte aligned.  n = 0 succeeds without a launch.
+ *
+ * me_rope_apply: y[i] = rotation of x[i] by sign * theta for the n rows; x and y are rows of heads * d elements of `dtype`
+ *   with the row strides x_stride, y_stride >= heads * d (in elements), so a column view of a wider matrix is taken as it
+ *   is; y may be x itself (a thread reads its piece before it writes it), any other overlap is undefined.  table: the
+ *   me_rope_table of the same map, d, base and unit, float for ME_ROPE_F32 / ME_ROPE_BF16 rows, double for ME_ROPE_F64.
+ *   bf16 rows are widened to fp32, rotated there and rounded once: the result equals the ME_ROPE_F32 result of the
+ *   widened rows, rounded to bf16, bit for bit.  Rows are moved in 16-byte pieces (8 bf16, 4 fp32, 2 double) when x, y
+ *   are 16-byte aligned and both strides and d are multiples of the piece; pair by pair otherwise, with the same bits.
+ *   One launch (at most 2048 workgroups, grid-stride), no LDS, no atomics, no synchronisation, no read-back, bitwise
+ *   reproducible.
+ *   Host-side errors, nothing launched: d odd or below 2, d / 2 > ME_ROPE_MAX_PAIRS, heads < 1, heads * d or n >= 2^31,
+ *   sign not +1 / -1, an unknown dtype, a row stride below heads * d, a null x, y or table with n > 0, x or y not aligned to
+ *   an element or a table not aligned to 16 bytes.  n = 0 succeeds without a launch. */
+#define ME_ROPE_MAX_PAIRS 128 /* P = d / 2 <= 128: heads of up to 256 channels */
+#define ME_ROPE_F32 0
+#define ME_ROPE_BF16 1
+#define ME_ROPE_F64 2
+int me_rope_table(const int32_t *coords_dev, int64_t n, int32_t ncol, const int32_t *unit, int32_t d, double base,
+                  int32_t table_f64, void *table_dev, void *stream);
+int me_rope_apply(const void *x_dev, int64_t x_stride, void *y_dev, int64_t y_stride, int64_t n, int32_t heads, int32_t d,
+                  const void *table_dev, int32_t sign, int32_t dtype, void *stream);
 
 /* ---- cross-attention to a dense context (MinkowskiCrossAttention, MinkowskiFunctional.cross_attention;
  *      csrc/attention.hip, ABI 1.20) ----

@@ -182,6 +182,19 @@ def window_attention(query, key, value, num_heads, window_size, shift=0, scale=N
     return SparseTensor(out, coordinate_map_key=query.coordinate_map_key, coordinate_manager=query._manager)
 
 
+def rotary_embedding(input, num_heads, base=10000.0, unit=None):
+    """Rotary position embedding from the voxel coordinates (MinkowskiRotaryEmbedding as a function): the channel pairs
+    (2p, 2p + 1) of each of the `num_heads` heads of `input` rotated by theta = (c_a / u_a) base^(-j / m), axis a = p // m,
+    frequency j = p % m, m = (d / 2) // D; `unit` u: None for the tensor stride of `input`, an int or one int per spatial
+    axis.  The result sits on the map of `input`."""
+    from .rotary import MinkowskiRotaryEmbeddingFunction
+    from .sparse_tensor import SparseTensor
+    if not isinstance(input, SparseTensor):
+        raise TypeError(f"rotary_embedding takes a SparseTensor, not a {type(input).__name__}")
+    out = MinkowskiRotaryEmbeddingFunction.apply(input.F, num_heads, base, unit, input.coordinate_map_key, input._manager)
+    return SparseTensor(out, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
+
+
 __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention",
                                                 "local_attention", "serialized_attention", "cross_attention",
-                                                "window_attention"]
+                                                "window_attention", "rotary_embedding"]

@@ -28,6 +28,7 @@ from .attention import (  # noqa: F401
 from .serialized_attention import (  # noqa: F401
     MinkowskiSerializedAttentionFunction, MinkowskiSerializedSelfAttention)
 from .window_attention import MinkowskiWindowAttentionFunction, MinkowskiWindowSelfAttention  # noqa: F401
+from .rotary import MinkowskiRotaryEmbedding, MinkowskiRotaryEmbeddingFunction  # noqa: F401
 from .local_attention import MinkowskiLocalAttentionFunction, MinkowskiLocalSelfAttention  # noqa: F401
 from .pruning import MinkowskiPruning, MinkowskiPruningFunction  # noqa: F401
 from .tensor_field import TensorField, create_splat_coordinates  # noqa: F401

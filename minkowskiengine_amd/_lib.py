@@ -211,6 +211,8 @@ SIGNATURES = {
                                           c_vp, c_vp, c_vp, c_i64, c_vp]),
     "me_attn_segment_lists_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "me_attn_segment_lists": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_rope_table": (ctypes.c_int, [c_vp, c_i64, c_i32, _P_I32, c_i32, ctypes.c_double, c_i32, c_vp, c_vp]),
+    "me_rope_apply": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
     "me_attn_context_lists": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "me_attn_kv_splits": (c_i32, [c_i64, c_i64, c_i32, c_i32, c_i32]),
     "me_attn_split_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32, c_i32, c_i32]),

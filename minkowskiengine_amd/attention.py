@@ -69,14 +69,23 @@ class MinkowskiSelfAttention(MinkowskiModuleBase):
     own scene.  The parameters are that module's — `in_proj_weight` (3C, C), `in_proj_bias` (3C,), `out_proj.weight`
     (C, C), `out_proj.bias` (C,), with the same initialisation — so state dicts load strictly in both directions.
     `embed_dim / num_heads` must be 32, 64 or 128 (any size after `.double()`); bf16 features run with bf16 parameters
-    (`.bfloat16()`), float64 features need `.double()`.  Sparse tensors only."""
+    (`.bfloat16()`), float64 features need `.double()`.  Sparse tensors only.
+    `rope=True` rotates q and k by the rotary position embedding of the voxel coordinates (rotary.py; frequencies from
+    `rope_base`, unit = the tensor stride of the input) before the scores are taken; it adds no parameter."""
 
-    def __init__(self, embed_dim, num_heads, bias=True):
+    def __init__(self, embed_dim, num_heads, bias=True, rope=False, rope_base=10000.0):
         super().__init__()
         if embed_dim <= 0 or num_heads <= 0:
             raise ValueError("embed_dim and num_heads must be greater than 0")
         if embed_dim % num_heads != 0:
             raise ValueError("embed_dim must be divisible by num_heads")
+        self.rope = bool(rope)
+        self.rope_base = float(rope_base)
+        if self.rope:
+            from .rotary import _check_rope
+            _check_rope(num_heads, rope_base, None)
+            if (embed_dim // num_heads) % 2 != 0:
+                raise ValueError(f"the head dimension must be even for rope=True, not {embed_dim // num_heads}")
         self.embed_dim = embed_dim
         self.num_heads = num_heads
         self.head_dim = embed_dim // num_heads
@@ -94,19 +103,33 @@ class MinkowskiSelfAttention(MinkowskiModuleBase):
             torch.nn.init.constant_(self.in_proj_bias, 0.0)
             torch.nn.init.constant_(self.out_proj.bias, 0.0)
 
+    def _rope_repr(self):
+        """the tail of repr(): nothing unless rope is set"""
+        if not self.rope:
+            return ""
+        return ", rope=True" + (f", rope_base={self.rope_base}" if self.rope_base != 10000.0 else "")
+
     def __repr__(self):
-        return self.__class__.__name__ + f"({self.embed_dim}, {self.num_heads}, bias={self.in_proj_bias is not None})"
+        return (self.__class__.__name__ + f"({self.embed_dim}, {self.num_heads}, bias={self.in_proj_bias is not None}"
+                + self._rope_repr() + ")")
+
+    def _qkv(self, input):
+        """(q, k, v) as column views of the projected matrix; with rope, q and k are the halves of ONE rotated [N, 2C]"""
+        c = self.embed_dim
+        qkv = torch.nn.functional.linear(input.F, self.in_proj_weight, self.in_proj_bias)
+        if self.rope:
+            from .rotary import rotate_qk
+            return rotate_qk(qkv, c, self.num_heads, self.rope_base, input.coordinate_map_key, input._manager)
+        return qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]
 
     def forward(self, input):
         if not isinstance(input, SparseTensor):
             raise TypeError(f"{self.__class__.__name__} takes a SparseTensor, not a {type(input).__name__} "
                             "(quantise a TensorField with .sparse() first)")
         assert input.shape[1] == self.embed_dim, f"Channel size mismatch {self.embed_dim} != {input.shape[1]}"
-        c = self.embed_dim
-        qkv = torch.nn.functional.linear(input.F, self.in_proj_weight, self.in_proj_bias)
+        q, k, v = self._qkv(input)
         key = input.coordinate_map_key
-        attn = MinkowskiAttentionFunction.apply(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], self.num_heads, None, key, key,
-                                                None, input._manager)
+        attn = MinkowskiAttentionFunction.apply(q, k, v, self.num_heads, None, key, key, None, input._manager)
         out = torch.nn.functional.linear(attn, self.out_proj.weight, self.out_proj.bias)
         return SparseTensor(out, coordinate_map_key=key, coordinate_manager=input._manager)
 

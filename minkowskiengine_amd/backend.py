@@ -757,6 +757,7 @@ class CoordinateMapManagerGPU_c10:
         self._instance_rows_cache = {}
         self._patch_rows_cache = {}     # (map key, patch size, order code) -> (seg_ptr, seg_rows, blk_tab, row_patch)
         self._window_rows_cache = {}    # (map key, window sizes, reduced shifts) -> (seg_ptr, seg_rows, blk_tab, row_window)
+        self._rope_table_cache = {}     # (map key, head size, base, units, float64 flag) -> table [n, d / 2, 2] (cos, sin)
         self._context_rows_cache = {}   # (instances, tokens, device) -> (seg_ptr, seg_rows, blk_tab)
         self._prune_rows = {}
         self._union_arith = {}   # (key a, key b), ordered -> (union key, u_of_a, u_of_b, a_of_u, b_of_u): union_arith_maps
@@ -1373,6 +1374,30 @@ class CoordinateMapManagerGPU_c10:
             lists = self._window_rows_cache[ck] = (seg_ptr, seg_rows, blk_tab, row_window)
         return lists
 
+    def _rope_table(self, in_key, d, base=10000.0, unit=None, f64=False):
+        """table [n, d / 2, 2] = (cos theta, sin theta) of rotary position embedding on the map `in_key` for heads of `d`
+        channels (me_rope_table, csrc/rope.hip; definition in include/me_amd.h): fp32, or float64 with `f64` (for float64
+        features).  `unit`: None for the map's tensor stride, an int or one int per spatial axis, each >= 1.  Cached per
+        (map, d, base, units, f64); one launch, nothing read back."""
+        ik = self._k(in_key)
+        m = self._get(ik)
+        n, ncol = int(m.n), int(m.coords.shape[1])
+        d, base, f64 = operator.index(d), float(base), bool(f64)
+        units = rope_units(unit, m.tensor_stride, ncol - 1)
+        ck = (ik, d, base, units, f64)
+        table = self._rope_table_cache.get(ck)
+        if table is None:
+            _check(d >= 2 and d % 2 == 0, "the head size must be even, got", d)
+            _check(d // 2 >= ncol - 1, "the head size", d, "must hold one pair per spatial axis:", ncol - 1)
+            lib = _lib.load()
+            dev = m.coords.device
+            table = torch.empty((n, d // 2, 2), dtype=torch.float64 if f64 else torch.float32, device=dev)
+            with _on(dev):
+                _lib.check(lib.me_rope_table(_ptr(m.coords), n, ncol, (ctypes.c_int32 * (ncol - 1))(*units), d, base,
+                                             int(f64), _ptr(table), _stream(dev)))
+            self._rope_table_cache[ck] = table
+        return table
+
     def _context_rows(self, n_batch, tokens, device, lengths=None):
         """(seg_ptr int32 [B + 1], seg_rows int32 [B L], blk_tab int32 [2 (ceil(B L / 64) + B)]) of a dense context of
         B = n_batch instances of L = tokens rows (me_attn_context_lists, csrc/attention.hip): instance b holds the rows
@@ -1497,7 +1522,7 @@ class CoordinateMapManagerGPU_c10:
                     if name not in ("_recipe", "in_map", "out_map"):
                         walk(getattr(o, name, None), depth + 1)
         for store in (self._maps, self._kernel_maps, self._origin_maps, self._instance_rows_cache, self._patch_rows_cache,
-                      self._window_rows_cache, self._context_rows_cache,
+                      self._window_rows_cache, self._rope_table_cache, self._context_rows_cache,
                       self._origin_field_maps, self._prune_rows,
                       self._stride_maps, self._union_arith):
             walk(store)
@@ -4019,6 +4044,61 @@ def WindowAttentionBackwardGPU(q, k, v, out, lse, grad_out, num_heads, scale, wi
     out, grad_out = _attn_backward_operands(q, out, grad_out, lse, (q.shape[0], heads), "[n, heads]")
     return _list_attn_backward("window_attn_backward", q, k, v, out, lse, grad_out, lists, lists, n_seg, heads, c, scale,
                                need_grad_q, need_grad_k, need_grad_v)
+
+
+# ------------------------------------------------------------------------------------------------
+# rotary position embedding from voxel coordinates (csrc/rope.hip, ABI 1.22; not in the reference): the channel pairs of
+# every head of a row are rotated by angles taken from the row's coordinates; the table comes from manager._rope_table.
+# ------------------------------------------------------------------------------------------------
+def rope_units(unit, tensor_stride, dimension):
+    """-> one int >= 1 per spatial axis: the tensor stride for None, else an int (all axes) or one int per axis"""
+    if unit is None:
+        return tuple(int(t) for t in tensor_stride)
+    try:
+        units = [operator.index(unit)] * dimension if not hasattr(unit, "__len__") else [operator.index(u) for u in unit]
+    except TypeError:
+        units = None
+    if units is None or len(units) != dimension:
+        raise ValueError(f"unit must be None, an int or one int per spatial axis ({dimension}), got {unit!r}")
+    if min(units) < 1:
+        raise ValueError(f"every unit must be at least 1, got {unit!r}")
+    return tuple(units)
+
+
+_ROPE_DTYPE = {torch.float32: 0, torch.bfloat16: 1, torch.float64: 2}      # ME_ROPE_F32, ME_ROPE_BF16, ME_ROPE_F64
+
+
+def _rope_apply(name, x, num_heads, base, unit, in_key, manager, sign):
+    x = _attn_rows("x", x)
+    _check(manager.exists(in_key), "coordinate map not found")
+    n = manager.size(in_key)
+    _check(x.shape[0] == n, "Invalid x size", x.shape[0], "!=", n)
+    heads, c = int(num_heads), int(x.shape[1])
+    _check(heads > 0 and c % heads == 0, "the channel count", c, "must be a multiple of num_heads", heads)
+    d = c // heads
+    table = manager._rope_table(in_key, d, base, unit, x.dtype == torch.float64)
+    y = torch.empty((n, c), dtype=x.dtype, device=x.device)
+    if n == 0:
+        return y
+    lib = _lib.load()
+    dev = x.device
+    with _on(dev):
+        _timed(name, dev, lambda: _lib.check(lib.me_rope_apply(_ptr(x), _attn_stride(x), _ptr(y), c, n, heads, d,
+                                                               _ptr(table), sign, _ROPE_DTYPE[x.dtype], _stream(dev))))
+    return y
+
+
+def RotaryEmbeddingForwardGPU(x, num_heads, base, unit, in_key, manager):
+    """-> y [n, C], contiguous: every channel pair (2p, 2p + 1) of every one of the `num_heads` heads of x [n, C] (a row
+    view with a row stride is taken as it is) rotated by the angle of pair p on the row's coordinates (me_rope_apply,
+    sign +1).  `unit`: None for the tensor stride of `in_key`, an int or one int per spatial axis."""
+    return _rope_apply("rope_forward", x, num_heads, base, unit, in_key, manager, 1)
+
+
+def RotaryEmbeddingBackwardGPU(grad_out, num_heads, base, unit, in_key, manager):
+    """-> grad_x [n, C], contiguous: the rotation is orthogonal, so the gradient is the output gradient rotated back
+    (me_rope_apply, sign -1): one launch."""
+    return _rope_apply("rope_backward", grad_out, num_heads, base, unit, in_key, manager, -1)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -201,6 +201,18 @@ class CoordinateManager:
         window_size, shift = _check_window(window_size, shift, self.D)
         return self._manager._window_rows(key, window_size, shift)
 
+    def rope_table(self, key, head_dim, base=10000.0, unit=None, dtype=torch.float32):
+        """table [N, head_dim / 2, 2] = (cos theta, sin theta) of rotary position embedding on the map `key` (rotary.py;
+        theta = (c_a / u_a) base^(-j / m) for pair p = a m + j, computed in double and rounded once): float32 (for fp32 and
+        bf16 features) or float64.  `unit`: None for the tensor stride of the map, an int or one int per spatial axis.
+        Cached per (map, head_dim, base, unit, dtype); nothing is read back."""
+        from .rotary import _check_head, _check_rope
+        _, base, unit = _check_rope(1, base, unit, self.D)
+        _check_head(int(head_dim), 1, self.D)
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"the table is float32 or float64, not {dtype}")
+        return self._manager._rope_table(key, int(head_dim), base, unit, dtype == torch.float64)
+
     def origin_field(self, field_key=None):
         """Key of the origin map (the key origin() returns), built from the batch indices of a field when absent:
         `field_key`, or the oldest field of the manager (MinkowskiCoordinateManager.py:273)."""

@@ -102,6 +102,13 @@ ivec axes_arg(const py::object &o) {
   if (py::isinstance<py::int_>(o)) return ivec{py::cast<int32_t>(o)};
   return py::cast<ivec>(o);
 }
+// unit of rotary position embedding: None (empty: the tensor stride of the map), an int or one int per spatial axis
+ivec unit_arg(const py::object &o) {
+  if (o.is_none()) return ivec{};
+  const ivec v = axes_arg(o);
+  if (v.empty()) throw std::invalid_argument("unit must be None, an int or one int per spatial axis, got no value");
+  return v;
+}
 Tensor opt_tensor(const py::object &o) { return o.is_none() ? Tensor() : py::cast<Tensor>(o); }
 c10::optional<Tensor> opt_opt(const py::object &o) {
   return o.is_none() ? c10::optional<Tensor>() : c10::optional<Tensor>(py::cast<Tensor>(o));
@@ -290,6 +297,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return py::make_tuple(r[0], r[1], r[2], r[3]);
            },
            py::arg("key"), py::arg("window_size"), py::arg("shift") = py::int_(0))
+      .def("_rope_table",
+           [](CoordinateMapManager &s, const CoordinateMapKey *k, int64_t d, double base, const py::object &unit,
+              bool f64) { return s.rope_table(keyt(k), d, base, unit_arg(unit), f64); },
+           py::arg("key"), py::arg("d"), py::arg("base") = 10000.0, py::arg("unit") = py::none(), py::arg("f64") = false)
       .def("_context_rows",
            [](CoordinateMapManager &s, int64_t n_batch, int64_t tokens, const py::object &device,
               const py::object &lengths) {
@@ -801,6 +812,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("grad_out"),
         py::arg("num_heads"), py::arg("scale"), py::arg("window_size"), py::arg("shift"), py::arg("in_key"),
         py::arg("manager"), py::arg("need_grad_q") = true, py::arg("need_grad_k") = true, py::arg("need_grad_v") = true);
+  // rotary position embedding from voxel coordinates: csrc/rope.hip on the manager's table
+  m.def("RotaryEmbeddingForwardGPU",
+        [](const Tensor &x, int64_t num_heads, double base, const py::object &unit, CoordinateMapKey *in_key,
+           CoordinateMapManager *mgr) {
+          const ivec u = unit_arg(unit);
+          py::gil_scoped_release nogil;
+          return rotary_embedding_forward(x, num_heads, base, u, in_key, mgr);
+        },
+        py::arg("x"), py::arg("num_heads"), py::arg("base"), py::arg("unit"), py::arg("in_key"), py::arg("manager"));
+  m.def("RotaryEmbeddingBackwardGPU",
+        [](const Tensor &grad_out, int64_t num_heads, double base, const py::object &unit, CoordinateMapKey *in_key,
+           CoordinateMapManager *mgr) {
+          const ivec u = unit_arg(unit);
+          py::gil_scoped_release nogil;
+          return rotary_embedding_backward(grad_out, num_heads, base, u, in_key, mgr);
+        },
+        py::arg("grad_out"), py::arg("num_heads"), py::arg("base"), py::arg("unit"), py::arg("in_key"),
+        py::arg("manager"));
   // tensor fields (field.cpp): the reference's InterpolationForwardGPU / InterpolationBackwardGPU and coo_spmm_int32 /
   // coo_spmm_average_int32 (pybind/extern.hpp:497-506), plus the CSR building blocks the autograd functions cache
   m.def("CsrFromCooGPU",

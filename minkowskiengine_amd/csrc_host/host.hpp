@@ -259,6 +259,8 @@ struct CoordinateMapManager {
   std::map<std::tuple<KeyT, int64_t, int>, std::vector<Tensor>> patch_rows_cache;
   // window attention: (map, window sizes, reduced shifts) -> {seg_ptr, seg_rows, blk_tab, row_window}
   std::map<std::tuple<KeyT, ivec, ivec>, std::vector<Tensor>> window_rows_cache;
+  // rotary position embedding: (map, head size, base, units, float64 flag) -> table [n, d / 2, 2] (cos, sin)
+  std::map<std::tuple<KeyT, int64_t, double, ivec, bool>, Tensor> rope_table_cache;
   // cross-attention: (instances, tokens, device index) -> {seg_ptr, seg_rows, blk_tab} of a dense context
   std::map<std::tuple<int64_t, int64_t, int>, std::vector<Tensor>> context_rows_cache;
   std::map<std::pair<KeyT, KeyT>, Tensor> prune_rows;
@@ -307,6 +309,10 @@ struct CoordinateMapManager {
   // (map, window sizes, shifts modulo them).  Building an entry reads the window count back once.  Twin of
   // backend._window_rows
   const std::vector<Tensor> &window_rows(const KeyT &in_key, const ivec &window_size, const ivec &shift);
+  // table [n, d / 2, 2] = (cos theta, sin theta) of rotary position embedding for heads of d channels (me_rope_table):
+  // fp32, or float64 with f64; unit: empty for the map's tensor stride, one value (all axes) or one per spatial axis;
+  // cached per (map, d, base, units, f64).  Twin of backend._rope_table
+  const Tensor &rope_table(const KeyT &in_key, int64_t d, double base, const ivec &unit, bool f64);
   // {seg_ptr, seg_rows, blk_tab} of a dense context of n_batch x tokens rows (me_attn_context_lists): cached per
   // (n_batch, tokens, device) without lengths, built per call with them (int32 [n_batch] on the device): twin of
   // backend._context_rows
@@ -449,6 +455,13 @@ std::vector<Tensor> window_attention_backward(Tensor q, Tensor k, Tensor v, Tens
                                               int64_t num_heads, double scale, const ivec &window_size, const ivec &shift,
                                               CoordinateMapKey *in_key, CoordinateMapManager *mgr, bool need_grad_q,
                                               bool need_grad_k, bool need_grad_v);
+// rotary position embedding from voxel coordinates (csrc/rope.hip; twin of backend.RotaryEmbedding{Forward,Backward}GPU);
+// unit: empty for the tensor stride of the map
+ivec rope_units(const ivec &unit, const ivec &tensor_stride, int dimension);
+Tensor rotary_embedding_forward(Tensor x, int64_t num_heads, double base, const ivec &unit, CoordinateMapKey *in_key,
+                                CoordinateMapManager *mgr);
+Tensor rotary_embedding_backward(Tensor grad_out, int64_t num_heads, double base, const ivec &unit,
+                                 CoordinateMapKey *in_key, CoordinateMapManager *mgr);
 // dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU / DensePolicy)
 int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box);
 std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,

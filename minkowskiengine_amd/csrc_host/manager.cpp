@@ -1214,6 +1214,25 @@ const std::vector<Tensor> &CoordinateMapManager::window_rows(const KeyT &in_key,
   return window_rows_cache[ck] = {seg_ptr, seg_rows, blk_tab, row_window};
 }
 
+const Tensor &CoordinateMapManager::rope_table(const KeyT &in_key, int64_t d, double base, const ivec &unit, bool f64) {
+  auto m = get(in_key);
+  const int64_t n = m->n;
+  const int ncol = (int)m->coords.size(1);
+  const ivec units = rope_units(unit, m->tensor_stride, ncol - 1);
+  const auto ck = std::make_tuple(in_key, d, base, units, f64);
+  auto it = rope_table_cache.find(ck);
+  if (it != rope_table_cache.end()) return it->second;
+  check(d >= 2 && d % 2 == 0, "the head size must be even, got " + std::to_string(d));
+  check(d / 2 >= ncol - 1, "the head size " + std::to_string(d) + " must hold one pair per spatial axis: " +
+                               std::to_string(ncol - 1));
+  const c10::Device dev = m->coords.device();
+  Tensor table = at::empty({n, d / 2, 2}, at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev));
+  c10::DeviceGuard guard(dev);
+  me_ok(me_rope_table(ptr<int32_t>(m->coords), n, ncol, units.data(), (int32_t)d, base, f64 ? 1 : 0, vptr(table),
+                      stream_of(dev)));
+  return rope_table_cache[ck] = table;
+}
+
 std::vector<Tensor> CoordinateMapManager::context_rows(int64_t n_batch, int64_t tokens, const c10::Device &dev,
                                                        const Tensor &lengths) {
   check(n_batch >= 0 && tokens >= 1, "a context needs at least one token per instance, got " + std::to_string(tokens));
@@ -1467,6 +1486,7 @@ std::vector<Tensor> CoordinateMapManager::device_tensors() {
     for (auto &t : kv.second) collect(out, t);
   for (auto &kv : window_rows_cache)
     for (auto &t : kv.second) collect(out, t);
+  for (auto &kv : rope_table_cache) collect(out, kv.second);
   for (auto &kv : context_rows_cache)
     for (auto &t : kv.second) collect(out, t);
   for (auto &kv : origin_field_rows_cache) collect(out, kv.second);

@@ -1702,6 +1702,52 @@ std::vector<Tensor> window_attention_backward(Tensor q, Tensor k, Tensor v, Tens
   return list_attn_backward(q, k, v, out, lse, grad_out, p, scale, need_grad_q, need_grad_k, need_grad_v);
 }
 
+// ---- rotary position embedding from voxel coordinates (csrc/rope.hip, ABI 1.22; twin of
+// backend.RotaryEmbedding{Forward,Backward}GPU): the channel pairs of every head rotated by the angles of mgr->rope_table -----
+// one unit >= 1 per spatial axis: the tensor stride for an empty `unit`, else one value (all axes) or one per axis
+ivec rope_units(const ivec &unit, const ivec &tensor_stride, int dimension) {
+  if (unit.empty()) return ivec(tensor_stride.begin(), tensor_stride.begin() + dimension);
+  ivec units = unit.size() == 1 ? ivec((size_t)dimension, unit[0]) : unit;
+  if ((int)units.size() != dimension)
+    throw std::invalid_argument("unit must be None, an int or one int per spatial axis (" + std::to_string(dimension) +
+                                "), got " + std::to_string(unit.size()) + " values");
+  for (int32_t u : units)
+    if (u < 1) throw std::invalid_argument("every unit must be at least 1, got " + std::to_string(u));
+  return units;
+}
+
+static Tensor rope_apply(Tensor x, int64_t num_heads, double base, const ivec &unit, CoordinateMapKey *in_key,
+                         CoordinateMapManager *mgr, int sign) {
+  x = attn_rows("x", x);
+  const KeyT &ik = in_key->get();
+  check(mgr->exists(ik), "coordinate map not found");
+  const int64_t n = mgr->get(ik)->n, c = x.size(1);
+  check(x.size(0) == n, "Invalid x size");
+  check(num_heads > 0 && c % num_heads == 0, "the channel count " + std::to_string(c) +
+                                                 " must be a multiple of num_heads " + std::to_string(num_heads));
+  const int64_t d = c / num_heads;
+  const at::ScalarType st = x.scalar_type();
+  const Tensor &table = mgr->rope_table(ik, d, base, unit, st == at::kDouble);
+  Tensor y = at::empty({n, c}, x.options());
+  if (n == 0) return y;
+  const c10::Device dev = x.device();
+  c10::DeviceGuard guard(dev);
+  me_ok(me_rope_apply(x.data_ptr(), attn_stride(x), y.data_ptr(), c, n, (int32_t)num_heads, (int32_t)d, table.data_ptr(),
+                      sign, st == at::kFloat ? ME_ROPE_F32 : st == at::kBFloat16 ? ME_ROPE_BF16 : ME_ROPE_F64,
+                      stream_of(dev)));
+  return y;
+}
+
+Tensor rotary_embedding_forward(Tensor x, int64_t num_heads, double base, const ivec &unit, CoordinateMapKey *in_key,
+                                CoordinateMapManager *mgr) {
+  return rope_apply(x, num_heads, base, unit, in_key, mgr, 1);
+}
+
+Tensor rotary_embedding_backward(Tensor grad_out, int64_t num_heads, double base, const ivec &unit,
+                                 CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+  return rope_apply(grad_out, num_heads, base, unit, in_key, mgr, -1);
+}
+
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------
 Tensor pruning_forward(const Tensor &in_feat, const Tensor &keep, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr) {

@@ -70,25 +70,24 @@ class MinkowskiSerializedSelfAttention(MinkowskiSelfAttention):
     initialisation are MinkowskiSelfAttention's (torch.nn.MultiheadAttention's), so state dicts load strictly in both
     directions.  `embed_dim / num_heads` must be 32, 64 or 128 (any size after `.double()`).  Sparse tensors only."""
 
-    def __init__(self, embed_dim, num_heads, patch_size=1024, order="z", bias=True):
+    def __init__(self, embed_dim, num_heads, patch_size=1024, order="z", bias=True, rope=False, rope_base=10000.0):
         _check_order(order, patch_size)
-        super().__init__(embed_dim, num_heads, bias=bias)
+        super().__init__(embed_dim, num_heads, bias=bias, rope=rope, rope_base=rope_base)
         self.patch_size = int(patch_size)
         self.order = order
 
     def __repr__(self):
         return (self.__class__.__name__ + f"({self.embed_dim}, {self.num_heads}, patch_size={self.patch_size}, "
-                f"order={self.order!r}, bias={self.in_proj_bias is not None})")
+                f"order={self.order!r}, bias={self.in_proj_bias is not None}" + self._rope_repr() + ")")
 
     def forward(self, input):
         if not isinstance(input, SparseTensor):
             raise TypeError(f"{self.__class__.__name__} takes a SparseTensor, not a {type(input).__name__} "
                             "(quantise a TensorField with .sparse() first)")
         assert input.shape[1] == self.embed_dim, f"Channel size mismatch {self.embed_dim} != {input.shape[1]}"
-        c = self.embed_dim
-        qkv = torch.nn.functional.linear(input.F, self.in_proj_weight, self.in_proj_bias)
+        q, k, v = self._qkv(input)
         key = input.coordinate_map_key
-        attn = MinkowskiSerializedAttentionFunction.apply(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], self.num_heads, None,
-                                                          self.patch_size, self.order, key, input._manager)
+        attn = MinkowskiSerializedAttentionFunction.apply(q, k, v, self.num_heads, None, self.patch_size, self.order, key,
+                                                          input._manager)
         out = torch.nn.functional.linear(attn, self.out_proj.weight, self.out_proj.bias)
         return SparseTensor(out, coordinate_map_key=key, coordinate_manager=input._manager)

@@ -149,7 +149,10 @@ def test_fixture(device, host_layer, path, dtype):
 # ---- round trips ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 @pytest.mark.parametrize("fmt,shape", [(None, (2, 5, 9, 12)), ("BCXX", (3, 1, 33, 35)), ("BXXXC", (2, 6, 5, 7, 17)),
-                                       ("BXCX", (2, 10, 16, 11)), ("BXXCXX", (2, 3, 4, 3, 5, 4)), ("BXC", (4, 70, 3))])
+                                       ("BXCX", (2, 10, 16, 11)), ("BXXCXX", (2, 3, 4, 3, 5, 4)), ("BXC", (4, 70, 3)),
+                                       # a second and a third pass of the channel loop: inner 60 (four cells per lane),
+                                       # inner 35 (cell fastest, scalar), channels-last (channel fastest)
+                                       (None, (2, 65, 6, 10)), (None, (1, 129, 5, 7)), ("BXXC", (2, 5, 7, 130))])
 def test_round_trip_every_format(device, host_layer, fmt, shape, dtype):
     import minkowskiengine_amd as ME
     g = torch.Generator().manual_seed(7)

@@ -21,6 +21,7 @@ import os
 import weakref
 import random
 import string
+import typing
 
 import threading
 
@@ -3378,8 +3379,10 @@ def bn_backward_apply(x, dy, n_total, mean, rstd, gamma, beta, sums, relu=False,
 
 
 # ------------------------------------------------------------------------------------------------
-# instance normalisation (csrc/instance_norm.hip; the reference's MinkowskiInstanceNorm is a chain of its global
-# pooling and broadcast operators, MinkowskiNormalization.py:194-399, and has no native operator of its own)
+# segmented normalisations: instance norm, group norm and conditional group norm are one algorithm in three sizes (rows
+# segmented by batch index, statistics per segment, a row map, a two-stage backward).  _seg_norm_forward /
+# _seg_norm_backward are that algorithm's host side; a _SegNorm says what tells an operator apart, and the six public
+# operators below pass theirs.  A further norm of this family is one more _SegNorm and one more wrapper pair.
 # ------------------------------------------------------------------------------------------------
 def _inorm_param_dtype(feat):
     """bf16 features take the fp32 parameters and statistics; fp32 / f64 take their own dtype"""
@@ -3406,164 +3409,12 @@ def _inorm_prepare(in_feat, in_key, glob_key, manager):
     return rows, manager.size(glob_key)
 
 
-def _norm_backward_prepare(in_feat, grad_out_feat, in_key, glob_key, manager, need_grad_in, need_grad_weight,
-                           need_grad_bias):
-    """The shared opening of the norm backward operators -> (batch_row, n_batch, grad_out_feat contiguous and in the dtype
-    of in_feat, grad_in | None, grad_weight [C] | None, grad_bias [C] | None), the gradients allocated, not yet written."""
-    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
-    if not grad_out_feat.is_contiguous():
-        grad_out_feat = grad_out_feat.contiguous()
-    _check_feat("grad_out_feat", grad_out_feat)
-    if grad_out_feat.dtype != in_feat.dtype:
-        grad_out_feat = grad_out_feat.to(in_feat.dtype)
-    _check(tuple(grad_out_feat.shape) == tuple(in_feat.shape), "grad_out_feat must have the shape of in_feat")
-    c, dev, pd = int(in_feat.shape[1]), in_feat.device, _inorm_param_dtype(in_feat)
-    grad_in = torch.empty_like(in_feat) if need_grad_in else None
-    grad_weight = torch.empty(c, dtype=pd, device=dev) if need_grad_weight else None
-    grad_bias = torch.empty(c, dtype=pd, device=dev) if need_grad_bias else None
-    return rows, n_batch, grad_out_feat, grad_in, grad_weight, grad_bias
-
-
-def InstanceNormForwardGPU(in_feat, weight, bias, eps, in_key, glob_key, manager):
-    """-> (out_feat, mean, rstd): out[i] = (x[i] - mean[b_i]) * rstd[b_i] * weight + bias with the mean and the biased
-    variance of every instance (batch index) per channel, rstd = 1 / sqrt(var + eps); mean / rstd: [batch, C] in the
-    parameter dtype (fp32 for fp32 and bf16 features, float64 for float64).  weight / bias: C values or None.  The
-    reference has no native operator of this name; it follows the package's `<Op>{Forward,Backward}GPU` convention."""
-    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
-    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
-    _inorm_check_vec("weight", weight, in_feat, c)
-    _inorm_check_vec("bias", bias, in_feat, c)
-    lib = _lib.load()
-    dev = in_feat.device
-    pd = _inorm_param_dtype(in_feat)
-    mean = torch.empty((n_batch, c), dtype=pd, device=dev)
-    rstd = torch.empty((n_batch, c), dtype=pd, device=dev)
-    out = torch.empty_like(in_feat)
-    with _on(dev):
-        if in_feat.dtype == torch.float64:
-            _lib.check(lib.me_inorm_stats_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, float(eps), _ptr(mean),
-                                              _ptr(rstd), _stream(dev)))
-            _lib.check(lib.me_inorm_apply_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, _ptr(mean), _ptr(rstd),
-                                              _ptr(weight), _ptr(bias), _ptr(out), _stream(dev)))
-        else:
-            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
-            ws = _workspace(int(lib.me_inorm_workspace_bytes(n, n_batch, c)), dev)
-            _timed("inorm_forward", dev, lambda: (
-                _lib.check(lib.me_inorm_stats(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, float(eps), _ptr(mean),
-                                              _ptr(rstd), _ptr(ws), ws.numel(), _stream(dev))),
-                _lib.check(lib.me_inorm_apply(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, _ptr(mean), _ptr(rstd),
-                                              _ptr(weight), _ptr(bias), _ptr(out), _stream(dev)))))
-    return out, mean, rstd
-
-
-def InstanceNormBackwardGPU(in_feat, grad_out_feat, weight, mean, rstd, in_key, glob_key, manager, need_grad_in=True,
-                            need_grad_weight=True, need_grad_bias=True):
-    """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None) from the statistics of the forward pass; the
-    parameter gradients have the parameter dtype (fp32 for bf16 features)."""
-    rows, n_batch, grad_out_feat, grad_in, grad_weight, grad_bias = _norm_backward_prepare(
-        in_feat, grad_out_feat, in_key, glob_key, manager, need_grad_in, need_grad_weight, need_grad_bias)
-    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
-    _inorm_check_vec("weight", weight, in_feat, c)
-    _check(mean is not None and rstd is not None, "instance norm backward needs mean and rstd")
-    _inorm_check_vec("mean", mean, in_feat, n_batch * c)
-    _inorm_check_vec("rstd", rstd, in_feat, n_batch * c)
-    lib = _lib.load()
-    dev = in_feat.device
-    if n == 0:
-        return grad_in, (None if grad_weight is None else grad_weight.zero_()), \
-            (None if grad_bias is None else grad_bias.zero_())
-    ws = _workspace(int(lib.me_inorm_workspace_bytes(n, n_batch, c)), dev)
-    with _on(dev):
-        if in_feat.dtype == torch.float64:
-            _lib.check(lib.me_inorm_backward_f64(_ptr(in_feat), _ptr(grad_out_feat), _ptr(rows), n, n_batch, c, _ptr(mean),
-                                                 _ptr(rstd), _ptr(weight), _ptr(grad_in), _ptr(grad_weight),
-                                                 _ptr(grad_bias), _ptr(ws), ws.numel(), _stream(dev)))
-        else:
-            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
-            _timed("inorm_backward", dev, lambda: _lib.check(lib.me_inorm_backward(
-                _ptr(in_feat), _ptr(grad_out_feat), bf, _ptr(rows), n, n_batch, c, _ptr(mean), _ptr(rstd), _ptr(weight),
-                _ptr(grad_in), _ptr(grad_weight), _ptr(grad_bias), _ptr(ws), ws.numel(), _stream(dev))))
-    return grad_in, grad_weight, grad_bias
-
-
-# ------------------------------------------------------------------------------------------------
-# group normalisation (csrc/group_norm.hip): torch.nn.GroupNorm's arithmetic on every instance of a sparse tensor; the
-# reference has no such layer.  Instance norm's segmentation (_inorm_prepare) plus a merge over the channels of a group.
-# ------------------------------------------------------------------------------------------------
 def _gnorm_groups(num_groups, c):
     groups = int(num_groups)
     _check(groups > 0 and c % groups == 0, "the channel count", c, "must be a multiple of num_groups", num_groups)
     return groups
 
 
-def GroupNormForwardGPU(in_feat, num_groups, weight, bias, eps, in_key, glob_key, manager):
-    """-> (out_feat, mean, rstd): out[i, c] = (x[i, c] - mean[b_i, g_c]) * rstd[b_i, g_c] * weight[c] + bias[c] with the
-    mean and the biased variance over the rows of every instance (batch index) and the C / num_groups channels of every
-    group, rstd = 1 / sqrt(var + eps); mean / rstd: [batch, num_groups] in the parameter dtype (fp32 for fp32 and bf16
-    features, float64 for float64).  weight / bias: C values or None."""
-    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
-    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
-    groups = _gnorm_groups(num_groups, c)
-    _inorm_check_vec("weight", weight, in_feat, c)
-    _inorm_check_vec("bias", bias, in_feat, c)
-    lib = _lib.load()
-    dev = in_feat.device
-    pd = _inorm_param_dtype(in_feat)
-    mean = torch.empty((n_batch, groups), dtype=pd, device=dev)
-    rstd = torch.empty((n_batch, groups), dtype=pd, device=dev)
-    out = torch.empty_like(in_feat)
-    with _on(dev):
-        if in_feat.dtype == torch.float64:
-            _lib.check(lib.me_gnorm_stats_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, groups, float(eps), _ptr(mean),
-                                              _ptr(rstd), _stream(dev)))
-            _lib.check(lib.me_gnorm_apply_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, groups, _ptr(mean), _ptr(rstd),
-                                              _ptr(weight), _ptr(bias), _ptr(out), _stream(dev)))
-        else:
-            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
-            ws = _workspace(int(lib.me_gnorm_workspace_bytes(n, n_batch, c, groups)), dev)
-            _timed("gnorm_forward", dev, lambda: (
-                _lib.check(lib.me_gnorm_stats(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, groups, float(eps),
-                                              _ptr(mean), _ptr(rstd), _ptr(ws), ws.numel(), _stream(dev))),
-                _lib.check(lib.me_gnorm_apply(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, groups, _ptr(mean),
-                                              _ptr(rstd), _ptr(weight), _ptr(bias), _ptr(out), _stream(dev)))))
-    return out, mean, rstd
-
-
-def GroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, mean, rstd, in_key, glob_key, manager,
-                         need_grad_in=True, need_grad_weight=True, need_grad_bias=True):
-    """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None) from the statistics of the forward pass; the
-    parameter gradients have the parameter dtype (fp32 for bf16 features)."""
-    rows, n_batch, grad_out_feat, grad_in, grad_weight, grad_bias = _norm_backward_prepare(
-        in_feat, grad_out_feat, in_key, glob_key, manager, need_grad_in, need_grad_weight, need_grad_bias)
-    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
-    groups = _gnorm_groups(num_groups, c)
-    _inorm_check_vec("weight", weight, in_feat, c)
-    _check(mean is not None and rstd is not None, "group norm backward needs mean and rstd")
-    _inorm_check_vec("mean", mean, in_feat, n_batch * groups)
-    _inorm_check_vec("rstd", rstd, in_feat, n_batch * groups)
-    lib = _lib.load()
-    dev = in_feat.device
-    if n == 0:
-        return grad_in, (None if grad_weight is None else grad_weight.zero_()), \
-            (None if grad_bias is None else grad_bias.zero_())
-    ws = _workspace(int(lib.me_gnorm_workspace_bytes(n, n_batch, c, groups)), dev)
-    with _on(dev):
-        if in_feat.dtype == torch.float64:
-            _lib.check(lib.me_gnorm_backward_f64(_ptr(in_feat), _ptr(grad_out_feat), _ptr(rows), n, n_batch, c, groups,
-                                                 _ptr(mean), _ptr(rstd), _ptr(weight), _ptr(grad_in), _ptr(grad_weight),
-                                                 _ptr(grad_bias), _ptr(ws), ws.numel(), _stream(dev)))
-        else:
-            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
-            _timed("gnorm_backward", dev, lambda: _lib.check(lib.me_gnorm_backward(
-                _ptr(in_feat), _ptr(grad_out_feat), bf, _ptr(rows), n, n_batch, c, groups, _ptr(mean), _ptr(rstd),
-                _ptr(weight), _ptr(grad_in), _ptr(grad_weight), _ptr(grad_bias), _ptr(ws), ws.numel(), _stream(dev))))
-    return grad_in, grad_weight, grad_bias
-
-
-# ------------------------------------------------------------------------------------------------
-# conditional group normalisation (csrc/group_norm.hip, k_gnc_*): group norm whose affine map is modulated by a scale and a
-# shift per instance (AdaGN / FiLM), with an optional fused SiLU.  The statistics are group norm's.
-# ------------------------------------------------------------------------------------------------
 _GNC_ACTIVATIONS = {None: 0, "silu": 1}
 
 
@@ -3580,45 +3431,164 @@ def _gnorm_cond_check_mod(name, t, in_feat, n_batch, c):
            "the features")
 
 
+class _SegNorm(typing.NamedTuple):
+    """what tells one segmented norm from the others"""
+    stats: str          # me_<stats>_stats[_f64] computes mean / rstd
+    apply: str          # me_<apply>_workspace_bytes, me_<apply>_apply[_f64] and me_<apply>_backward[_f64] do the rest
+    groups: bool        # the operator takes num_groups: mean / rstd are [batch, groups], else [batch, C]
+    cond: bool          # it takes scale / shift [batch, C] and an activation, returns their gradients, and its apply takes
+                        # the workspace too
+    label: str          # KernelTimer's <label>_forward / <label>_backward (its users key on them)
+    needs_stats: str    # the message of a backward call without mean / rstd
+    # forward on a map without rows.  True: mean = 0, rstd = eps ** -0.5 come from the host and nothing is launched.  False:
+    # the statistics kernels run on the empty matrix and write what they write for any instance without rows.  The
+    # operators differ as they were written (no reason is on record), and the routes do not give the same bits: the host
+    # rounds a double to fp32, the fp32 kernels compute in fp32 (eps = 1e-5: 316.22775 against 316.22778; 1e-6: 1000 against
+    # 999.99994; equal at 1e-8 and in float64, docs/HISTORY.md section 15).  So each operator keeps its own.
+    host_stats_when_empty: bool
+
+
+_INORM = _SegNorm("inorm", "inorm", False, False, "inorm", "instance norm backward needs mean and rstd", False)
+_GNORM = _SegNorm("gnorm", "gnorm", True, False, "gnorm", "group norm backward needs mean and rstd", False)
+_GNORM_COND = _SegNorm("gnorm", "gnorm_cond", True, True, "gnorm_cond",
+                       "conditional group norm backward needs mean and rstd", True)
+
+
+def _seg_norm_forward(op, in_feat, num_groups, weight, bias, scale, shift, activation, eps, in_key, glob_key, manager):
+    """-> (out_feat, mean, rstd) of the operator `op`; num_groups is read if op.groups, scale / shift / activation if
+    op.cond"""
+    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
+    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
+    groups = _gnorm_groups(num_groups, c) if op.groups else c           # instance norm: statistics per channel
+    act = _gnorm_cond_act(activation) if op.cond else 0
+    _inorm_check_vec("weight", weight, in_feat, c)
+    _inorm_check_vec("bias", bias, in_feat, c)
+    if op.cond:
+        _gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c)
+        _gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c)
+    lib = _lib.load()
+    dev = in_feat.device
+    pd = _inorm_param_dtype(in_feat)
+    out = torch.empty_like(in_feat)
+    if n == 0 and op.host_stats_when_empty:
+        return (out, torch.zeros((n_batch, groups), dtype=pd, device=dev),
+                torch.full((n_batch, groups), float(eps) ** -0.5, dtype=pd, device=dev))
+    mean = torch.empty((n_batch, groups), dtype=pd, device=dev)
+    rstd = torch.empty((n_batch, groups), dtype=pd, device=dev)
+    # the C signatures differ in the symbol prefix and in these pieces: no is_bf16 flag in the float64 twins, `groups` after
+    # c, the modulation after the affine parameters
+    f64 = in_feat.dtype == torch.float64
+    twin = "_f64" if f64 else ""
+    stats, apply = getattr(lib, f"me_{op.stats}_stats{twin}"), getattr(lib, f"me_{op.apply}_apply{twin}")
+    x = (_ptr(in_feat), _ptr(rows)) if f64 else (_ptr(in_feat), 1 if in_feat.dtype == torch.bfloat16 else 0, _ptr(rows))
+    shape = (n, n_batch, c, groups) if op.groups else (n, n_batch, c)
+    coef = (_ptr(mean), _ptr(rstd), _ptr(weight), _ptr(bias)) + ((_ptr(scale), _ptr(shift), act) if op.cond else ())
+    with _on(dev):
+        if f64:
+            _lib.check(stats(*x, *shape, float(eps), _ptr(mean), _ptr(rstd), _stream(dev)))
+            _lib.check(apply(*x, *shape, *coef, _ptr(out), _stream(dev)))
+        else:
+            ws = _workspace(int(getattr(lib, f"me_{op.apply}_workspace_bytes")(*shape)), dev)
+            ws_args = (_ptr(ws), ws.numel())
+            _timed(op.label + "_forward", dev, lambda: (
+                _lib.check(stats(*x, *shape, float(eps), _ptr(mean), _ptr(rstd), *ws_args, _stream(dev))),
+                _lib.check(apply(*x, *shape, *coef, _ptr(out), *(ws_args if op.cond else ()), _stream(dev)))))
+    return out, mean, rstd
+
+
+def _seg_norm_backward(op, in_feat, grad_out_feat, num_groups, weight, bias, scale, shift, activation, mean, rstd, in_key,
+                       glob_key, manager, need_grad):
+    """-> the gradients of (in_feat, weight, bias) or, if op.cond, of (in_feat, weight, bias, scale, shift): a tuple as long
+    as the booleans `need_grad`, None where not needed.  grad_out_feat is made contiguous and cast to the dtype of in_feat;
+    bias is read only if op.cond."""
+    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
+    if not grad_out_feat.is_contiguous():
+        grad_out_feat = grad_out_feat.contiguous()
+    _check_feat("grad_out_feat", grad_out_feat)
+    if grad_out_feat.dtype != in_feat.dtype:
+        grad_out_feat = grad_out_feat.to(in_feat.dtype)
+    _check(tuple(grad_out_feat.shape) == tuple(in_feat.shape), "grad_out_feat must have the shape of in_feat")
+    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
+    groups = _gnorm_groups(num_groups, c) if op.groups else c
+    act = _gnorm_cond_act(activation) if op.cond else 0
+    _inorm_check_vec("weight", weight, in_feat, c)
+    if op.cond:
+        _inorm_check_vec("bias", bias, in_feat, c)
+        _gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c)
+        _gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c)
+    _check(mean is not None and rstd is not None, op.needs_stats)
+    _inorm_check_vec("mean", mean, in_feat, n_batch * groups)
+    _inorm_check_vec("rstd", rstd, in_feat, n_batch * groups)
+    lib = _lib.load()
+    dev = in_feat.device
+    pd = _inorm_param_dtype(in_feat)
+    grads = [torch.empty_like(in_feat) if need_grad[0] else None]
+    for need, size in zip(need_grad[1:], ((c,), (c,), (n_batch, c), (n_batch, c))):
+        grads.append(torch.empty(size, dtype=pd, device=dev) if need else None)
+    if n == 0:
+        return (grads[0],) + tuple(None if g is None else g.zero_() for g in grads[1:])
+    shape = (n, n_batch, c, groups) if op.groups else (n, n_batch, c)
+    ws = _workspace(int(getattr(lib, f"me_{op.apply}_workspace_bytes")(*shape)), dev)
+    f64 = in_feat.dtype == torch.float64
+    backward = getattr(lib, f"me_{op.apply}_backward{'_f64' if f64 else ''}")
+    x = (_ptr(in_feat), _ptr(grad_out_feat)) + (() if f64 else (1 if in_feat.dtype == torch.bfloat16 else 0,))
+    coef = (_ptr(mean), _ptr(rstd), _ptr(weight)) + ((_ptr(bias), _ptr(scale), _ptr(shift), act) if op.cond else ())
+
+    def launch():
+        _lib.check(backward(*x, _ptr(rows), *shape, *coef, *map(_ptr, grads), _ptr(ws), ws.numel(), _stream(dev)))
+    with _on(dev):
+        if f64:
+            launch()
+        else:
+            _timed(op.label + "_backward", dev, launch)
+    return tuple(grads)
+
+
+# instance normalisation (csrc/instance_norm.hip; the reference's MinkowskiInstanceNorm is a chain of its global pooling
+# and broadcast operators, MinkowskiNormalization.py:194-399, and has no native operator of its own)
+def InstanceNormForwardGPU(in_feat, weight, bias, eps, in_key, glob_key, manager):
+    """-> (out_feat, mean, rstd): out[i] = (x[i] - mean[b_i]) * rstd[b_i] * weight + bias with the mean and the biased
+    variance of every instance (batch index) per channel, rstd = 1 / sqrt(var + eps); mean / rstd: [batch, C] in the
+    parameter dtype (fp32 for fp32 and bf16 features, float64 for float64).  weight / bias: C values or None.  The
+    reference has no native operator of this name; it follows the package's `<Op>{Forward,Backward}GPU` convention."""
+    return _seg_norm_forward(_INORM, in_feat, None, weight, bias, None, None, None, eps, in_key, glob_key, manager)
+
+
+def InstanceNormBackwardGPU(in_feat, grad_out_feat, weight, mean, rstd, in_key, glob_key, manager, need_grad_in=True,
+                            need_grad_weight=True, need_grad_bias=True):
+    """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None) from the statistics of the forward pass; the
+    parameter gradients have the parameter dtype (fp32 for bf16 features)."""
+    return _seg_norm_backward(_INORM, in_feat, grad_out_feat, None, weight, None, None, None, None, mean, rstd, in_key,
+                              glob_key, manager, (need_grad_in, need_grad_weight, need_grad_bias))
+
+
+# group normalisation (csrc/group_norm.hip): torch.nn.GroupNorm's arithmetic on every instance of a sparse tensor; the
+# reference has no such layer.  Instance norm's segmentation plus a merge over the channels of a group.
+def GroupNormForwardGPU(in_feat, num_groups, weight, bias, eps, in_key, glob_key, manager):
+    """-> (out_feat, mean, rstd): out[i, c] = (x[i, c] - mean[b_i, g_c]) * rstd[b_i, g_c] * weight[c] + bias[c] with the
+    mean and the biased variance over the rows of every instance (batch index) and the C / num_groups channels of every
+    group, rstd = 1 / sqrt(var + eps); mean / rstd: [batch, num_groups] in the parameter dtype (fp32 for fp32 and bf16
+    features, float64 for float64).  weight / bias: C values or None."""
+    return _seg_norm_forward(_GNORM, in_feat, num_groups, weight, bias, None, None, None, eps, in_key, glob_key, manager)
+
+
+def GroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, mean, rstd, in_key, glob_key, manager,
+                         need_grad_in=True, need_grad_weight=True, need_grad_bias=True):
+    """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None) from the statistics of the forward pass; the
+    parameter gradients have the parameter dtype (fp32 for bf16 features)."""
+    return _seg_norm_backward(_GNORM, in_feat, grad_out_feat, num_groups, weight, None, None, None, None, mean, rstd,
+                              in_key, glob_key, manager, (need_grad_in, need_grad_weight, need_grad_bias))
+
+
+# conditional group normalisation (csrc/group_norm.hip, k_gnc_*): group norm whose affine map is modulated by a scale and a
+# shift per instance (AdaGN / FiLM), with an optional fused SiLU.  The statistics are group norm's.
 def ConditionalGroupNormForwardGPU(in_feat, num_groups, weight, bias, scale, shift, activation, eps, in_key, glob_key,
                                    manager):
     """-> (out_feat, mean, rstd): out = act(xhat * weight * (1 + scale[b]) + bias * (1 + scale[b]) + shift[b]) with
     GroupNormForwardGPU's xhat, mean and rstd.  scale / shift: [manager.size(glob_key), C] in the parameter dtype or None,
     row j for row j of the origin map (the j-th smallest batch index); activation: None or "silu"."""
-    rows, n_batch = _inorm_prepare(in_feat, in_key, glob_key, manager)
-    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
-    groups = _gnorm_groups(num_groups, c)
-    act = _gnorm_cond_act(activation)
-    _inorm_check_vec("weight", weight, in_feat, c)
-    _inorm_check_vec("bias", bias, in_feat, c)
-    _gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c)
-    _gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c)
-    lib = _lib.load()
-    dev = in_feat.device
-    pd = _inorm_param_dtype(in_feat)
-    out = torch.empty_like(in_feat)
-    if n == 0:
-        return (out, torch.zeros((n_batch, groups), dtype=pd, device=dev),
-                torch.full((n_batch, groups), float(eps) ** -0.5, dtype=pd, device=dev))
-    mean = torch.empty((n_batch, groups), dtype=pd, device=dev)
-    rstd = torch.empty((n_batch, groups), dtype=pd, device=dev)
-    with _on(dev):
-        if in_feat.dtype == torch.float64:
-            _lib.check(lib.me_gnorm_stats_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, groups, float(eps), _ptr(mean),
-                                              _ptr(rstd), _stream(dev)))
-            _lib.check(lib.me_gnorm_cond_apply_f64(_ptr(in_feat), _ptr(rows), n, n_batch, c, groups, _ptr(mean),
-                                                   _ptr(rstd), _ptr(weight), _ptr(bias), _ptr(scale), _ptr(shift), act,
-                                                   _ptr(out), _stream(dev)))
-        else:
-            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
-            ws = _workspace(int(lib.me_gnorm_cond_workspace_bytes(n, n_batch, c, groups)), dev)
-            _timed("gnorm_cond_forward", dev, lambda: (
-                _lib.check(lib.me_gnorm_stats(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, groups, float(eps),
-                                              _ptr(mean), _ptr(rstd), _ptr(ws), ws.numel(), _stream(dev))),
-                _lib.check(lib.me_gnorm_cond_apply(_ptr(in_feat), bf, _ptr(rows), n, n_batch, c, groups, _ptr(mean),
-                                                   _ptr(rstd), _ptr(weight), _ptr(bias), _ptr(scale), _ptr(shift), act,
-                                                   _ptr(out), _ptr(ws), ws.numel(), _stream(dev)))))
-    return out, mean, rstd
+    return _seg_norm_forward(_GNORM_COND, in_feat, num_groups, weight, bias, scale, shift, activation, eps, in_key,
+                             glob_key, manager)
 
 
 def ConditionalGroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, bias, scale, shift, activation, mean, rstd,
@@ -3627,40 +3597,9 @@ def ConditionalGroupNormBackwardGPU(in_feat, grad_out_feat, num_groups, weight, 
     """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None, grad_scale [batch, C] | None, grad_shift
     [batch, C] | None) from the statistics of the forward pass, in the parameter dtype (fp32 for bf16 features).  The rows
     of grad_scale / grad_shift of an instance without rows on this map are 0."""
-    rows, n_batch, grad_out_feat, grad_in, grad_weight, grad_bias = _norm_backward_prepare(
-        in_feat, grad_out_feat, in_key, glob_key, manager, need_grad_in, need_grad_weight, need_grad_bias)
-    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
-    groups = _gnorm_groups(num_groups, c)
-    act = _gnorm_cond_act(activation)
-    _inorm_check_vec("weight", weight, in_feat, c)
-    _inorm_check_vec("bias", bias, in_feat, c)
-    _gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c)
-    _gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c)
-    _check(mean is not None and rstd is not None, "conditional group norm backward needs mean and rstd")
-    _inorm_check_vec("mean", mean, in_feat, n_batch * groups)
-    _inorm_check_vec("rstd", rstd, in_feat, n_batch * groups)
-    lib = _lib.load()
-    dev = in_feat.device
-    pd = _inorm_param_dtype(in_feat)
-    grad_scale = torch.empty((n_batch, c), dtype=pd, device=dev) if need_grad_scale else None
-    grad_shift = torch.empty((n_batch, c), dtype=pd, device=dev) if need_grad_shift else None
-    if n == 0:
-        return (grad_in,) + tuple(None if g is None else g.zero_()
-                                  for g in (grad_weight, grad_bias, grad_scale, grad_shift))
-    ws = _workspace(int(lib.me_gnorm_cond_workspace_bytes(n, n_batch, c, groups)), dev)
-    with _on(dev):
-        if in_feat.dtype == torch.float64:
-            _lib.check(lib.me_gnorm_cond_backward_f64(
-                _ptr(in_feat), _ptr(grad_out_feat), _ptr(rows), n, n_batch, c, groups, _ptr(mean), _ptr(rstd),
-                _ptr(weight), _ptr(bias), _ptr(scale), _ptr(shift), act, _ptr(grad_in), _ptr(grad_weight),
-                _ptr(grad_bias), _ptr(grad_scale), _ptr(grad_shift), _ptr(ws), ws.numel(), _stream(dev)))
-        else:
-            bf = 1 if in_feat.dtype == torch.bfloat16 else 0
-            _timed("gnorm_cond_backward", dev, lambda: _lib.check(lib.me_gnorm_cond_backward(
-                _ptr(in_feat), _ptr(grad_out_feat), bf, _ptr(rows), n, n_batch, c, groups, _ptr(mean), _ptr(rstd),
-                _ptr(weight), _ptr(bias), _ptr(scale), _ptr(shift), act, _ptr(grad_in), _ptr(grad_weight),
-                _ptr(grad_bias), _ptr(grad_scale), _ptr(grad_shift), _ptr(ws), ws.numel(), _stream(dev))))
-    return grad_in, grad_weight, grad_bias, grad_scale, grad_shift
+    return _seg_norm_backward(_GNORM_COND, in_feat, grad_out_feat, num_groups, weight, bias, scale, shift, activation, mean,
+                              rstd, in_key, glob_key, manager,
+                              (need_grad_in, need_grad_weight, need_grad_bias, need_grad_scale, need_grad_shift))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -128,6 +128,38 @@ int gnorm_cond_act(const py::object &o) {
   if (py::isinstance<py::str>(o) && py::cast<std::string>(o) == "silu") return 1;
   throw std::runtime_error("activation must be None or 'silu', not " + py::cast<std::string>(py::repr(o)));
 }
+// What the six segmented-norm operators share at the boundary: optional tensors in, the GIL released around the map
+// lookup and the launches, undefined results out as None.  An operator passes None for what it does not take.
+py::tuple seg_norm_forward_py(SegNorm op, const Tensor &in_feat, int64_t num_groups, const py::object &weight,
+                              const py::object &bias, const py::object &scale, const py::object &shift,
+                              const py::object &activation, double eps, CoordinateMapKey *in_key,
+                              CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+  const Tensor w = opt_tensor(weight), b = opt_tensor(bias), sc = opt_tensor(scale), sh = opt_tensor(shift);
+  const int act = gnorm_cond_act(activation);
+  std::tuple<Tensor, Tensor, Tensor> r;
+  {
+    py::gil_scoped_release nogil;
+    r = seg_norm_forward(op, in_feat, num_groups, w, b, sc, sh, act, eps, in_key, glob_key, mgr);
+  }
+  return py::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r));
+}
+py::tuple seg_norm_backward_py(SegNorm op, const Tensor &in_feat, const Tensor &grad_out, int64_t num_groups,
+                               const py::object &weight, const py::object &bias, const py::object &scale,
+                               const py::object &shift, const py::object &activation, const Tensor &mean,
+                               const Tensor &rstd, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
+                               CoordinateMapManager *mgr, const std::vector<bool> &need_grad) {
+  const Tensor w = opt_tensor(weight), b = opt_tensor(bias), sc = opt_tensor(scale), sh = opt_tensor(shift);
+  const int act = gnorm_cond_act(activation);
+  std::vector<Tensor> r;
+  {
+    py::gil_scoped_release nogil;
+    r = seg_norm_backward(op, in_feat, grad_out, num_groups, w, b, sc, sh, act, mean, rstd, in_key, glob_key, mgr,
+                          need_grad);
+  }
+  py::tuple out(r.size());
+  for (size_t i = 0; i < r.size(); i++) out[i] = opt_out(r[i]);
+  return out;
+}
 
 // enums of pybind/extern.hpp:669-741
 enum GPUMemoryAllocatorType { PYTORCH = 0, CUDA = 1 };
@@ -559,13 +591,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("InstanceNormForwardGPU",
         [](const Tensor &in_feat, const py::object &weight, const py::object &bias, double eps, CoordinateMapKey *in_key,
            CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
-          const Tensor w = opt_tensor(weight), b = opt_tensor(bias);
-          std::tuple<Tensor, Tensor, Tensor> r;
-          {
-            py::gil_scoped_release nogil;
-            r = instance_norm_forward(in_feat, w, b, eps, in_key, glob_key, mgr);
-          }
-          return py::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r));
+          const py::none no;
+          return seg_norm_forward_py(SegNorm::Instance, in_feat, 0, weight, bias, no, no, no, eps, in_key, glob_key, mgr);
         },
         py::arg("in_feat"), py::arg("weight"), py::arg("bias"), py::arg("eps"), py::arg("in_key"), py::arg("glob_key"),
         py::arg("manager"));
@@ -573,14 +600,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         [](const Tensor &in_feat, const Tensor &grad_out, const py::object &weight, const Tensor &mean, const Tensor &rstd,
            CoordinateMapKey *in_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr, bool need_grad_in,
            bool need_grad_weight, bool need_grad_bias) {
-          const Tensor w = opt_tensor(weight);
-          std::tuple<Tensor, Tensor, Tensor> r;
-          {
-            py::gil_scoped_release nogil;
-            r = instance_norm_backward(in_feat, grad_out, w, mean, rstd, in_key, glob_key, mgr, need_grad_in,
-                                       need_grad_weight, need_grad_bias);
-          }
-          return py::make_tuple(opt_out(std::get<0>(r)), opt_out(std::get<1>(r)), opt_out(std::get<2>(r)));
+          const py::none no;
+          return seg_norm_backward_py(SegNorm::Instance, in_feat, grad_out, 0, weight, no, no, no, no, mean, rstd, in_key,
+                                      glob_key, mgr, {need_grad_in, need_grad_weight, need_grad_bias});
         },
         py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("weight"), py::arg("mean"), py::arg("rstd"),
         py::arg("in_key"), py::arg("glob_key"), py::arg("manager"), py::arg("need_grad_in") = true,
@@ -590,13 +612,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("GroupNormForwardGPU",
         [](const Tensor &in_feat, int64_t num_groups, const py::object &weight, const py::object &bias, double eps,
            CoordinateMapKey *in_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
-          const Tensor w = opt_tensor(weight), b = opt_tensor(bias);
-          std::tuple<Tensor, Tensor, Tensor> r;
-          {
-            py::gil_scoped_release nogil;
-            r = group_norm_forward(in_feat, num_groups, w, b, eps, in_key, glob_key, mgr);
-          }
-          return py::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r));
+          const py::none no;
+          return seg_norm_forward_py(SegNorm::Group, in_feat, num_groups, weight, bias, no, no, no, eps, in_key, glob_key,
+                                     mgr);
         },
         py::arg("in_feat"), py::arg("num_groups"), py::arg("weight"), py::arg("bias"), py::arg("eps"), py::arg("in_key"),
         py::arg("glob_key"), py::arg("manager"));
@@ -604,14 +622,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         [](const Tensor &in_feat, const Tensor &grad_out, int64_t num_groups, const py::object &weight, const Tensor &mean,
            const Tensor &rstd, CoordinateMapKey *in_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
            bool need_grad_in, bool need_grad_weight, bool need_grad_bias) {
-          const Tensor w = opt_tensor(weight);
-          std::tuple<Tensor, Tensor, Tensor> r;
-          {
-            py::gil_scoped_release nogil;
-            r = group_norm_backward(in_feat, grad_out, num_groups, w, mean, rstd, in_key, glob_key, mgr, need_grad_in,
-                                    need_grad_weight, need_grad_bias);
-          }
-          return py::make_tuple(opt_out(std::get<0>(r)), opt_out(std::get<1>(r)), opt_out(std::get<2>(r)));
+          const py::none no;
+          return seg_norm_backward_py(SegNorm::Group, in_feat, grad_out, num_groups, weight, no, no, no, no, mean, rstd,
+                                      in_key, glob_key, mgr, {need_grad_in, need_grad_weight, need_grad_bias});
         },
         py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("num_groups"), py::arg("weight"), py::arg("mean"),
         py::arg("rstd"), py::arg("in_key"), py::arg("glob_key"), py::arg("manager"), py::arg("need_grad_in") = true,
@@ -622,14 +635,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         [](const Tensor &in_feat, int64_t num_groups, const py::object &weight, const py::object &bias,
            const py::object &scale, const py::object &shift, const py::object &activation, double eps,
            CoordinateMapKey *in_key, CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
-          const Tensor w = opt_tensor(weight), b = opt_tensor(bias), sc = opt_tensor(scale), sh = opt_tensor(shift);
-          const int act = gnorm_cond_act(activation);
-          std::tuple<Tensor, Tensor, Tensor> r;
-          {
-            py::gil_scoped_release nogil;
-            r = cond_group_norm_forward(in_feat, num_groups, w, b, sc, sh, act, eps, in_key, glob_key, mgr);
-          }
-          return py::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r));
+          return seg_norm_forward_py(SegNorm::CondGroup, in_feat, num_groups, weight, bias, scale, shift, activation, eps,
+                                     in_key, glob_key, mgr);
         },
         py::arg("in_feat"), py::arg("num_groups"), py::arg("weight"), py::arg("bias"), py::arg("scale"), py::arg("shift"),
         py::arg("activation"), py::arg("eps"), py::arg("in_key"), py::arg("glob_key"), py::arg("manager"));
@@ -639,15 +646,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
            CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_weight, bool need_grad_bias, bool need_grad_scale,
            bool need_grad_shift) {
-          const Tensor w = opt_tensor(weight), b = opt_tensor(bias), sc = opt_tensor(scale), sh = opt_tensor(shift);
-          const int act = gnorm_cond_act(activation);
-          std::vector<Tensor> r;
-          {
-            py::gil_scoped_release nogil;
-            r = cond_group_norm_backward(in_feat, grad_out, num_groups, w, b, sc, sh, act, mean, rstd, in_key, glob_key, mgr,
-                                         need_grad_in, need_grad_weight, need_grad_bias, need_grad_scale, need_grad_shift);
-          }
-          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]), opt_out(r[3]), opt_out(r[4]));
+          return seg_norm_backward_py(SegNorm::CondGroup, in_feat, grad_out, num_groups, weight, bias, scale, shift,
+                                      activation, mean, rstd, in_key, glob_key, mgr,
+                                      {need_grad_in, need_grad_weight, need_grad_bias, need_grad_scale, need_grad_shift});
         },
         py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("num_groups"), py::arg("weight"), py::arg("bias"),
         py::arg("scale"), py::arg("shift"), py::arg("activation"), py::arg("mean"), py::arg("rstd"), py::arg("in_key"),

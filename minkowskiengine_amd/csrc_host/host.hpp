@@ -378,34 +378,22 @@ std::tuple<Tensor, Tensor, Tensor> channelwise_backward(const Tensor &in_feat, T
                                                         CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                                                         CoordinateMapManager *mgr, bool need_grad_in,
                                                         bool need_grad_bias, const ivec &offsets = ivec());
-// instance normalisation (csrc/instance_norm.hip; twin of backend.InstanceNorm{Forward,Backward}GPU)
-std::tuple<Tensor, Tensor, Tensor> instance_norm_forward(const Tensor &in_feat, const Tensor &weight, const Tensor &bias,
-                                                         double eps, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
-                                                         CoordinateMapManager *mgr);
-std::tuple<Tensor, Tensor, Tensor> instance_norm_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &weight,
-                                                          const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key,
-                                                          CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
-                                                          bool need_grad_in, bool need_grad_weight, bool need_grad_bias);
-// group normalisation (csrc/group_norm.hip; twin of backend.GroupNorm{Forward,Backward}GPU)
-std::tuple<Tensor, Tensor, Tensor> group_norm_forward(const Tensor &in_feat, int64_t num_groups, const Tensor &weight,
-                                                      const Tensor &bias, double eps, CoordinateMapKey *in_key,
-                                                      CoordinateMapKey *glob_key, CoordinateMapManager *mgr);
-std::tuple<Tensor, Tensor, Tensor> group_norm_backward(const Tensor &in_feat, Tensor grad_out, int64_t num_groups,
-                                                       const Tensor &weight, const Tensor &mean, const Tensor &rstd,
-                                                       CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
-                                                       CoordinateMapManager *mgr, bool need_grad_in,
-                                                       bool need_grad_weight, bool need_grad_bias);
-// conditional group normalisation (csrc/group_norm.hip, k_gnc_*; twin of backend.ConditionalGroupNorm{Forward,Backward}GPU)
-std::tuple<Tensor, Tensor, Tensor> cond_group_norm_forward(const Tensor &in_feat, int64_t num_groups, const Tensor &weight,
-                                                           const Tensor &bias, const Tensor &scale, const Tensor &shift,
-                                                           int act, double eps, CoordinateMapKey *in_key,
-                                                           CoordinateMapKey *glob_key, CoordinateMapManager *mgr);
-std::vector<Tensor> cond_group_norm_backward(const Tensor &in_feat, Tensor grad_out, int64_t num_groups,
-                                             const Tensor &weight, const Tensor &bias, const Tensor &scale,
-                                             const Tensor &shift, int act, const Tensor &mean, const Tensor &rstd,
-                                             CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
-                                             CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_weight,
-                                             bool need_grad_bias, bool need_grad_scale, bool need_grad_shift);
+// segmented normalisations (twins of backend._seg_norm_forward / _seg_norm_backward, which serve
+// backend.{InstanceNorm,GroupNorm,ConditionalGroupNorm}{Forward,Backward}GPU): instance norm on csrc/instance_norm.hip,
+// group norm and conditional group norm (k_gnc_*) on csrc/group_norm.hip.  num_groups is read by the two group norms;
+// bias (backward), scale, shift and act by the conditional one.
+enum class SegNorm { Instance, Group, CondGroup };
+std::tuple<Tensor, Tensor, Tensor> seg_norm_forward(SegNorm op, const Tensor &in_feat, int64_t num_groups,
+                                                    const Tensor &weight, const Tensor &bias, const Tensor &scale,
+                                                    const Tensor &shift, int act, double eps, CoordinateMapKey *in_key,
+                                                    CoordinateMapKey *glob_key, CoordinateMapManager *mgr);
+// -> the gradients of (in_feat, weight, bias) or, for CondGroup, of (in_feat, weight, bias, scale, shift): one per entry of
+// need_grad, undefined where not needed
+std::vector<Tensor> seg_norm_backward(SegNorm op, const Tensor &in_feat, Tensor grad_out, int64_t num_groups,
+                                      const Tensor &weight, const Tensor &bias, const Tensor &scale, const Tensor &shift,
+                                      int act, const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key,
+                                      CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
+                                      const std::vector<bool> &need_grad);
 // per-instance multi-head attention (csrc/attention.hip; twin of backend.Attention{Forward,Backward}GPU)
 std::pair<Tensor, Tensor> attention_forward(Tensor q, Tensor k, Tensor v, int64_t num_heads, double scale,
                                             CoordinateMapKey *q_key, CoordinateMapKey *kv_key, CoordinateMapKey *glob_key,

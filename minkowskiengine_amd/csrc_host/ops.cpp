@@ -1020,7 +1020,9 @@ std::pair<Tensor, Tensor> broadcast_backward(const Tensor &in_feat, const Tensor
   return {grad_in, grad_glob};
 }
 
-// ---- instance normalisation (csrc/instance_norm.hip; twin of backend.InstanceNorm{Forward,Backward}GPU) ------------------------
+// ---- segmented normalisations: instance norm (csrc/instance_norm.hip), group norm and conditional group norm
+// (csrc/group_norm.hip, k_gnc_*); twins of backend._seg_norm_forward / _seg_norm_backward.  One algorithm in three sizes:
+// what the operators share is written once here, and a switch on SegNorm sits where the typed C-ABI calls are made -------
 static void inorm_check_vec(const char *name, const Tensor &t, const Tensor &in_feat, int64_t numel) {
   const at::ScalarType want = in_feat.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
   check(!t.defined() || (t.is_cuda() && t.is_contiguous() && t.scalar_type() == want && t.numel() == numel &&
@@ -1045,166 +1047,12 @@ static std::pair<Tensor, int64_t> inorm_prepare(const Tensor &in_feat, Coordinat
   return {rows, mgr->get(glob_key->get())->n};
 }
 
-// The shared opening of the norm backward operators (twin of backend._norm_backward_prepare): grad_out made contiguous and
-// cast to the dtype of in_feat -> (batch_row, n_batch, grad_in, grad_weight, grad_bias), allocated, not yet written
-static std::tuple<Tensor, int, Tensor, Tensor, Tensor> norm_backward_prepare(
-    const Tensor &in_feat, Tensor &grad_out, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
-    CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_weight, bool need_grad_bias) {
-  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
-  grad_out = grad_out.contiguous();
-  check_feat("grad_out_feat", grad_out);
-  if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
-  check(grad_out.sizes() == in_feat.sizes(), "grad_out_feat must have the shape of in_feat");
-  const auto popt = at::TensorOptions().dtype(in_feat.scalar_type() == at::kDouble ? at::kDouble : at::kFloat)
-                        .device(in_feat.device());
-  const int64_t c = in_feat.size(1);
-  return {pr.first, (int)pr.second, need_grad_in ? at::empty_like(in_feat) : Tensor(),
-          need_grad_weight ? at::empty({c}, popt) : Tensor(), need_grad_bias ? at::empty({c}, popt) : Tensor()};
-}
-
-std::tuple<Tensor, Tensor, Tensor> instance_norm_forward(const Tensor &in_feat, const Tensor &weight, const Tensor &bias,
-                                                         double eps, CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
-                                                         CoordinateMapManager *mgr) {
-  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
-  const Tensor &rows = pr.first;
-  const int n_batch = (int)pr.second;
-  const int64_t n = in_feat.size(0);
-  const int c = (int)in_feat.size(1);
-  inorm_check_vec("weight", weight, in_feat, c);
-  inorm_check_vec("bias", bias, in_feat, c);
-  const c10::Device dev = in_feat.device();
-  const bool f64 = in_feat.scalar_type() == at::kDouble;
-  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
-  Tensor mean = at::empty({n_batch, c}, popt), rstd = at::empty({n_batch, c}, popt);
-  Tensor out = at::empty_like(in_feat);
-  c10::DeviceGuard guard(dev);
-  if (f64) {
-    me_ok(me_inorm_stats_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, eps, ptr<double>(mean),
-                             ptr<double>(rstd), stream_of(dev)));
-    me_ok(me_inorm_apply_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, ptr<double>(mean), ptr<double>(rstd),
-                             ptr<double>(weight), ptr<double>(bias), ptr<double>(out), stream_of(dev)));
-    return {out, mean, rstd};
-  }
-  const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
-  Tensor ws = workspace(me_inorm_workspace_bytes(n, n_batch, c), dev);
-  me_ok(me_inorm_stats(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, (float)eps, ptr<float>(mean),
-                       ptr<float>(rstd), vptr(ws), ws.numel(), stream_of(dev)));
-  me_ok(me_inorm_apply(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, ptr<float>(mean), ptr<float>(rstd),
-                       ptr<float>(weight), ptr<float>(bias), out.data_ptr(), stream_of(dev)));
-  return {out, mean, rstd};
-}
-
-std::tuple<Tensor, Tensor, Tensor> instance_norm_backward(const Tensor &in_feat, Tensor grad_out, const Tensor &weight,
-                                                          const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key,
-                                                          CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
-                                                          bool need_grad_in, bool need_grad_weight, bool need_grad_bias) {
-  auto [rows, n_batch, grad_in, grad_weight, grad_bias] =
-      norm_backward_prepare(in_feat, grad_out, in_key, glob_key, mgr, need_grad_in, need_grad_weight, need_grad_bias);
-  const int64_t n = in_feat.size(0);
-  const int c = (int)in_feat.size(1);
-  inorm_check_vec("weight", weight, in_feat, c);
-  check(mean.defined() && rstd.defined(), "instance norm backward needs mean and rstd");
-  inorm_check_vec("mean", mean, in_feat, (int64_t)n_batch * c);
-  inorm_check_vec("rstd", rstd, in_feat, (int64_t)n_batch * c);
-  const c10::Device dev = in_feat.device();
-  const bool f64 = in_feat.scalar_type() == at::kDouble;
-  if (n == 0) {
-    if (grad_weight.defined()) grad_weight.zero_();
-    if (grad_bias.defined()) grad_bias.zero_();
-    return {grad_in, grad_weight, grad_bias};
-  }
-  Tensor ws = workspace(me_inorm_workspace_bytes(n, n_batch, c), dev);
-  c10::DeviceGuard guard(dev);
-  if (f64) {
-    me_ok(me_inorm_backward_f64(ptr<double>(in_feat), ptr<double>(grad_out), ptr<int32_t>(rows), n, n_batch, c,
-                                ptr<double>(mean), ptr<double>(rstd), ptr<double>(weight), ptr<double>(grad_in),
-                                ptr<double>(grad_weight), ptr<double>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
-  } else {
-    const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
-    me_ok(me_inorm_backward(in_feat.data_ptr(), grad_out.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c,
-                            ptr<float>(mean), ptr<float>(rstd), ptr<float>(weight), vptr(grad_in), ptr<float>(grad_weight),
-                            ptr<float>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
-  }
-  return {grad_in, grad_weight, grad_bias};
-}
-
-// ---- group normalisation (csrc/group_norm.hip; twin of backend.GroupNorm{Forward,Backward}GPU) ---------------------------------
 static int gnorm_groups(int64_t num_groups, int c) {
   check(num_groups > 0 && c % num_groups == 0, "the channel count " + std::to_string(c) +
                                                    " must be a multiple of num_groups " + std::to_string(num_groups));
   return (int)num_groups;
 }
 
-std::tuple<Tensor, Tensor, Tensor> group_norm_forward(const Tensor &in_feat, int64_t num_groups, const Tensor &weight,
-                                                      const Tensor &bias, double eps, CoordinateMapKey *in_key,
-                                                      CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
-  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
-  const Tensor &rows = pr.first;
-  const int n_batch = (int)pr.second;
-  const int64_t n = in_feat.size(0);
-  const int c = (int)in_feat.size(1);
-  const int groups = gnorm_groups(num_groups, c);
-  inorm_check_vec("weight", weight, in_feat, c);
-  inorm_check_vec("bias", bias, in_feat, c);
-  const c10::Device dev = in_feat.device();
-  const bool f64 = in_feat.scalar_type() == at::kDouble;
-  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
-  Tensor mean = at::empty({n_batch, groups}, popt), rstd = at::empty({n_batch, groups}, popt);
-  Tensor out = at::empty_like(in_feat);
-  c10::DeviceGuard guard(dev);
-  if (f64) {
-    me_ok(me_gnorm_stats_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, groups, eps, ptr<double>(mean),
-                             ptr<double>(rstd), stream_of(dev)));
-    me_ok(me_gnorm_apply_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, groups, ptr<double>(mean),
-                             ptr<double>(rstd), ptr<double>(weight), ptr<double>(bias), ptr<double>(out), stream_of(dev)));
-    return {out, mean, rstd};
-  }
-  const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
-  Tensor ws = workspace(me_gnorm_workspace_bytes(n, n_batch, c, groups), dev);
-  me_ok(me_gnorm_stats(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups, (float)eps, ptr<float>(mean),
-                       ptr<float>(rstd), vptr(ws), ws.numel(), stream_of(dev)));
-  me_ok(me_gnorm_apply(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups, ptr<float>(mean),
-                       ptr<float>(rstd), ptr<float>(weight), ptr<float>(bias), out.data_ptr(), stream_of(dev)));
-  return {out, mean, rstd};
-}
-
-std::tuple<Tensor, Tensor, Tensor> group_norm_backward(const Tensor &in_feat, Tensor grad_out, int64_t num_groups,
-                                                       const Tensor &weight, const Tensor &mean, const Tensor &rstd,
-                                                       CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
-                                                       CoordinateMapManager *mgr, bool need_grad_in,
-                                                       bool need_grad_weight, bool need_grad_bias) {
-  auto [rows, n_batch, grad_in, grad_weight, grad_bias] =
-      norm_backward_prepare(in_feat, grad_out, in_key, glob_key, mgr, need_grad_in, need_grad_weight, need_grad_bias);
-  const int64_t n = in_feat.size(0);
-  const int c = (int)in_feat.size(1);
-  const int groups = gnorm_groups(num_groups, c);
-  inorm_check_vec("weight", weight, in_feat, c);
-  check(mean.defined() && rstd.defined(), "group norm backward needs mean and rstd");
-  inorm_check_vec("mean", mean, in_feat, (int64_t)n_batch * groups);
-  inorm_check_vec("rstd", rstd, in_feat, (int64_t)n_batch * groups);
-  const c10::Device dev = in_feat.device();
-  const bool f64 = in_feat.scalar_type() == at::kDouble;
-  if (n == 0) {
-    if (grad_weight.defined()) grad_weight.zero_();
-    if (grad_bias.defined()) grad_bias.zero_();
-    return {grad_in, grad_weight, grad_bias};
-  }
-  Tensor ws = workspace(me_gnorm_workspace_bytes(n, n_batch, c, groups), dev);
-  c10::DeviceGuard guard(dev);
-  if (f64) {
-    me_ok(me_gnorm_backward_f64(ptr<double>(in_feat), ptr<double>(grad_out), ptr<int32_t>(rows), n, n_batch, c, groups,
-                                ptr<double>(mean), ptr<double>(rstd), ptr<double>(weight), ptr<double>(grad_in),
-                                ptr<double>(grad_weight), ptr<double>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
-  } else {
-    const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
-    me_ok(me_gnorm_backward(in_feat.data_ptr(), grad_out.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups,
-                            ptr<float>(mean), ptr<float>(rstd), ptr<float>(weight), vptr(grad_in), ptr<float>(grad_weight),
-                            ptr<float>(grad_bias), vptr(ws), ws.numel(), stream_of(dev)));
-  }
-  return {grad_in, grad_weight, grad_bias};
-}
-
-// ---- conditional group normalisation (csrc/group_norm.hip, k_gnc_*; twin of backend.ConditionalGroupNorm{Forward,Backward}GPU)
 static void gnorm_cond_check_mod(const char *name, const Tensor &t, const Tensor &in_feat, int64_t n_batch, int64_t c) {
   const at::ScalarType want = in_feat.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
   check(!t.defined() || (t.is_cuda() && t.is_contiguous() && t.scalar_type() == want && t.dim() == 2 &&
@@ -1214,89 +1062,168 @@ static void gnorm_cond_check_mod(const char *name, const Tensor &t, const Tensor
                             "] (one row per instance), on the device of the features");
 }
 
-std::tuple<Tensor, Tensor, Tensor> cond_group_norm_forward(const Tensor &in_feat, int64_t num_groups, const Tensor &weight,
-                                                           const Tensor &bias, const Tensor &scale, const Tensor &shift,
-                                                           int act, double eps, CoordinateMapKey *in_key,
-                                                           CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+static Tensor seg_norm_workspace(SegNorm op, int64_t n, int n_batch, int c, int groups, const c10::Device &dev) {
+  switch (op) {
+  case SegNorm::Instance: return workspace(me_inorm_workspace_bytes(n, n_batch, c), dev);
+  case SegNorm::Group: return workspace(me_gnorm_workspace_bytes(n, n_batch, c, groups), dev);
+  case SegNorm::CondGroup: return workspace(me_gnorm_cond_workspace_bytes(n, n_batch, c, groups), dev);
+  }
+  fail("unknown segmented norm");
+}
+
+std::tuple<Tensor, Tensor, Tensor> seg_norm_forward(SegNorm op, const Tensor &in_feat, int64_t num_groups,
+                                                    const Tensor &weight, const Tensor &bias, const Tensor &scale,
+                                                    const Tensor &shift, int act, double eps, CoordinateMapKey *in_key,
+                                                    CoordinateMapKey *glob_key, CoordinateMapManager *mgr) {
+  const bool cond = op == SegNorm::CondGroup;
   auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
-  const Tensor &rows = pr.first;
+  const int32_t *rows = ptr<int32_t>(pr.first);
   const int n_batch = (int)pr.second;
   const int64_t n = in_feat.size(0);
   const int c = (int)in_feat.size(1);
-  const int groups = gnorm_groups(num_groups, c);
+  const int groups = op == SegNorm::Instance ? c : gnorm_groups(num_groups, c);   // instance norm: statistics per channel
   inorm_check_vec("weight", weight, in_feat, c);
   inorm_check_vec("bias", bias, in_feat, c);
-  gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c);
-  gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c);
+  if (cond) {
+    gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c);
+    gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c);
+  }
   const c10::Device dev = in_feat.device();
   const bool f64 = in_feat.scalar_type() == at::kDouble;
   const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
   Tensor out = at::empty_like(in_feat);
-  if (n == 0) return {out, at::zeros({n_batch, groups}, popt), at::full({n_batch, groups}, 1.0 / std::sqrt(eps), popt)};
+  // a map without rows: only the conditional norm answers from the host without a launch, the other two run their
+  // statistics kernels on the empty matrix (backend._SegNorm.host_stats_when_empty says why both are kept)
+  if (n == 0 && cond) return {out, at::zeros({n_batch, groups}, popt), at::full({n_batch, groups}, 1.0 / std::sqrt(eps), popt)};
   Tensor mean = at::empty({n_batch, groups}, popt), rstd = at::empty({n_batch, groups}, popt);
   c10::DeviceGuard guard(dev);
+  void *stream = stream_of(dev);
   if (f64) {
-    me_ok(me_gnorm_stats_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, groups, eps, ptr<double>(mean),
-                             ptr<double>(rstd), stream_of(dev)));
-    me_ok(me_gnorm_cond_apply_f64(ptr<double>(in_feat), ptr<int32_t>(rows), n, n_batch, c, groups, ptr<double>(mean),
-                                  ptr<double>(rstd), ptr<double>(weight), ptr<double>(bias), ptr<double>(scale),
-                                  ptr<double>(shift), act, ptr<double>(out), stream_of(dev)));
+    const double *x = ptr<double>(in_feat), *w = ptr<double>(weight), *b = ptr<double>(bias);
+    double *m = ptr<double>(mean), *r = ptr<double>(rstd), *y = ptr<double>(out);
+    switch (op) {
+    case SegNorm::Instance:
+      me_ok(me_inorm_stats_f64(x, rows, n, n_batch, c, eps, m, r, stream));
+      me_ok(me_inorm_apply_f64(x, rows, n, n_batch, c, m, r, w, b, y, stream));
+      break;
+    case SegNorm::Group:
+      me_ok(me_gnorm_stats_f64(x, rows, n, n_batch, c, groups, eps, m, r, stream));
+      me_ok(me_gnorm_apply_f64(x, rows, n, n_batch, c, groups, m, r, w, b, y, stream));
+      break;
+    case SegNorm::CondGroup:
+      me_ok(me_gnorm_stats_f64(x, rows, n, n_batch, c, groups, eps, m, r, stream));
+      me_ok(me_gnorm_cond_apply_f64(x, rows, n, n_batch, c, groups, m, r, w, b, ptr<double>(scale), ptr<double>(shift), act,
+                                    y, stream));
+      break;
+    }
     return {out, mean, rstd};
   }
   const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
-  Tensor ws = workspace(me_gnorm_cond_workspace_bytes(n, n_batch, c, groups), dev);
-  me_ok(me_gnorm_stats(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups, (float)eps, ptr<float>(mean),
-                       ptr<float>(rstd), vptr(ws), ws.numel(), stream_of(dev)));
-  me_ok(me_gnorm_cond_apply(in_feat.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups, ptr<float>(mean),
-                            ptr<float>(rstd), ptr<float>(weight), ptr<float>(bias), ptr<float>(scale), ptr<float>(shift),
-                            act, out.data_ptr(), vptr(ws), ws.numel(), stream_of(dev)));
+  Tensor ws = seg_norm_workspace(op, n, n_batch, c, groups, dev);
+  const void *x = in_feat.data_ptr();
+  const float *w = ptr<float>(weight), *b = ptr<float>(bias);
+  float *m = ptr<float>(mean), *r = ptr<float>(rstd);
+  void *y = out.data_ptr();
+  switch (op) {
+  case SegNorm::Instance:
+    me_ok(me_inorm_stats(x, bf, rows, n, n_batch, c, (float)eps, m, r, vptr(ws), ws.numel(), stream));
+    me_ok(me_inorm_apply(x, bf, rows, n, n_batch, c, m, r, w, b, y, stream));
+    break;
+  case SegNorm::Group:
+    me_ok(me_gnorm_stats(x, bf, rows, n, n_batch, c, groups, (float)eps, m, r, vptr(ws), ws.numel(), stream));
+    me_ok(me_gnorm_apply(x, bf, rows, n, n_batch, c, groups, m, r, w, b, y, stream));
+    break;
+  case SegNorm::CondGroup:
+    me_ok(me_gnorm_stats(x, bf, rows, n, n_batch, c, groups, (float)eps, m, r, vptr(ws), ws.numel(), stream));
+    me_ok(me_gnorm_cond_apply(x, bf, rows, n, n_batch, c, groups, m, r, w, b, ptr<float>(scale), ptr<float>(shift), act, y,
+                              vptr(ws), ws.numel(), stream));
+    break;
+  }
   return {out, mean, rstd};
 }
 
-std::vector<Tensor> cond_group_norm_backward(const Tensor &in_feat, Tensor grad_out, int64_t num_groups,
-                                             const Tensor &weight, const Tensor &bias, const Tensor &scale,
-                                             const Tensor &shift, int act, const Tensor &mean, const Tensor &rstd,
-                                             CoordinateMapKey *in_key, CoordinateMapKey *glob_key,
-                                             CoordinateMapManager *mgr, bool need_grad_in, bool need_grad_weight,
-                                             bool need_grad_bias, bool need_grad_scale, bool need_grad_shift) {
-  auto [rows, n_batch, grad_in, grad_weight, grad_bias] =
-      norm_backward_prepare(in_feat, grad_out, in_key, glob_key, mgr, need_grad_in, need_grad_weight, need_grad_bias);
+std::vector<Tensor> seg_norm_backward(SegNorm op, const Tensor &in_feat, Tensor grad_out, int64_t num_groups,
+                                      const Tensor &weight, const Tensor &bias, const Tensor &scale, const Tensor &shift,
+                                      int act, const Tensor &mean, const Tensor &rstd, CoordinateMapKey *in_key,
+                                      CoordinateMapKey *glob_key, CoordinateMapManager *mgr,
+                                      const std::vector<bool> &need_grad) {
+  const bool cond = op == SegNorm::CondGroup;
+  check(need_grad.size() == (cond ? 5u : 3u), "one need_grad flag per gradient of the operator");
+  auto pr = inorm_prepare(in_feat, in_key, glob_key, mgr);
+  const int32_t *rows = ptr<int32_t>(pr.first);
+  const int n_batch = (int)pr.second;
+  grad_out = grad_out.contiguous();
+  check_feat("grad_out_feat", grad_out);
+  if (grad_out.scalar_type() != in_feat.scalar_type()) grad_out = grad_out.to(in_feat.scalar_type());
+  check(grad_out.sizes() == in_feat.sizes(), "grad_out_feat must have the shape of in_feat");
   const int64_t n = in_feat.size(0);
   const int c = (int)in_feat.size(1);
-  const int groups = gnorm_groups(num_groups, c);
+  const int groups = op == SegNorm::Instance ? c : gnorm_groups(num_groups, c);
   inorm_check_vec("weight", weight, in_feat, c);
-  inorm_check_vec("bias", bias, in_feat, c);
-  gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c);
-  gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c);
-  check(mean.defined() && rstd.defined(), "conditional group norm backward needs mean and rstd");
+  if (cond) {
+    inorm_check_vec("bias", bias, in_feat, c);
+    gnorm_cond_check_mod("scale", scale, in_feat, n_batch, c);
+    gnorm_cond_check_mod("shift", shift, in_feat, n_batch, c);
+  }
+  check(mean.defined() && rstd.defined(),
+        std::string(op == SegNorm::Instance ? "instance" : cond ? "conditional group" : "group") +
+            " norm backward needs mean and rstd");
   inorm_check_vec("mean", mean, in_feat, (int64_t)n_batch * groups);
   inorm_check_vec("rstd", rstd, in_feat, (int64_t)n_batch * groups);
   const c10::Device dev = in_feat.device();
   const bool f64 = in_feat.scalar_type() == at::kDouble;
   const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
-  Tensor grad_scale = need_grad_scale ? at::empty({n_batch, c}, popt) : Tensor();
-  Tensor grad_shift = need_grad_shift ? at::empty({n_batch, c}, popt) : Tensor();
+  std::vector<Tensor> g(need_grad.size());
+  if (need_grad[0]) g[0] = at::empty_like(in_feat);
+  for (size_t i = 1; i < g.size(); i++)
+    if (need_grad[i]) g[i] = i < 3 ? at::empty({c}, popt) : at::empty({n_batch, c}, popt);
   if (n == 0) {
-    for (Tensor *g : {&grad_weight, &grad_bias, &grad_scale, &grad_shift})
-      if (g->defined()) g->zero_();
-    return {grad_in, grad_weight, grad_bias, grad_scale, grad_shift};
+    for (size_t i = 1; i < g.size(); i++)
+      if (g[i].defined()) g[i].zero_();
+    return g;
   }
-  Tensor ws = workspace(me_gnorm_cond_workspace_bytes(n, n_batch, c, groups), dev);
+  Tensor ws = seg_norm_workspace(op, n, n_batch, c, groups, dev);
   c10::DeviceGuard guard(dev);
+  void *stream = stream_of(dev);
   if (f64) {
-    me_ok(me_gnorm_cond_backward_f64(ptr<double>(in_feat), ptr<double>(grad_out), ptr<int32_t>(rows), n, n_batch, c, groups,
-                                     ptr<double>(mean), ptr<double>(rstd), ptr<double>(weight), ptr<double>(bias),
-                                     ptr<double>(scale), ptr<double>(shift), act, ptr<double>(grad_in),
-                                     ptr<double>(grad_weight), ptr<double>(grad_bias), ptr<double>(grad_scale),
-                                     ptr<double>(grad_shift), vptr(ws), ws.numel(), stream_of(dev)));
-  } else {
-    const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
-    me_ok(me_gnorm_cond_backward(in_feat.data_ptr(), grad_out.data_ptr(), bf, ptr<int32_t>(rows), n, n_batch, c, groups,
-                                 ptr<float>(mean), ptr<float>(rstd), ptr<float>(weight), ptr<float>(bias), ptr<float>(scale),
-                                 ptr<float>(shift), act, vptr(grad_in), ptr<float>(grad_weight), ptr<float>(grad_bias),
-                                 ptr<float>(grad_scale), ptr<float>(grad_shift), vptr(ws), ws.numel(), stream_of(dev)));
+    const double *x = ptr<double>(in_feat), *dy = ptr<double>(grad_out), *m = ptr<double>(mean), *r = ptr<double>(rstd);
+    const double *w = ptr<double>(weight);
+    switch (op) {
+    case SegNorm::Instance:
+      me_ok(me_inorm_backward_f64(x, dy, rows, n, n_batch, c, m, r, w, ptr<double>(g[0]), ptr<double>(g[1]),
+                                  ptr<double>(g[2]), vptr(ws), ws.numel(), stream));
+      break;
+    case SegNorm::Group:
+      me_ok(me_gnorm_backward_f64(x, dy, rows, n, n_batch, c, groups, m, r, w, ptr<double>(g[0]), ptr<double>(g[1]),
+                                  ptr<double>(g[2]), vptr(ws), ws.numel(), stream));
+      break;
+    case SegNorm::CondGroup:
+      me_ok(me_gnorm_cond_backward_f64(x, dy, rows, n, n_batch, c, groups, m, r, w, ptr<double>(bias), ptr<double>(scale),
+                                       ptr<double>(shift), act, ptr<double>(g[0]), ptr<double>(g[1]), ptr<double>(g[2]),
+                                       ptr<double>(g[3]), ptr<double>(g[4]), vptr(ws), ws.numel(), stream));
+      break;
+    }
+    return g;
   }
-  return {grad_in, grad_weight, grad_bias, grad_scale, grad_shift};
+  const int bf = in_feat.scalar_type() == at::kBFloat16 ? 1 : 0;
+  const void *x = in_feat.data_ptr(), *dy = grad_out.data_ptr();
+  const float *m = ptr<float>(mean), *r = ptr<float>(rstd), *w = ptr<float>(weight);
+  switch (op) {
+  case SegNorm::Instance:
+    me_ok(me_inorm_backward(x, dy, bf, rows, n, n_batch, c, m, r, w, vptr(g[0]), ptr<float>(g[1]), ptr<float>(g[2]),
+                            vptr(ws), ws.numel(), stream));
+    break;
+  case SegNorm::Group:
+    me_ok(me_gnorm_backward(x, dy, bf, rows, n, n_batch, c, groups, m, r, w, vptr(g[0]), ptr<float>(g[1]), ptr<float>(g[2]),
+                            vptr(ws), ws.numel(), stream));
+    break;
+  case SegNorm::CondGroup:
+    me_ok(me_gnorm_cond_backward(x, dy, bf, rows, n, n_batch, c, groups, m, r, w, ptr<float>(bias), ptr<float>(scale),
+                                 ptr<float>(shift), act, vptr(g[0]), ptr<float>(g[1]), ptr<float>(g[2]), ptr<float>(g[3]),
+                                 ptr<float>(g[4]), vptr(ws), ws.numel(), stream));
+    break;
+  }
+  return g;
 }
 
 // ---- per-instance multi-head attention (csrc/attention.hip; twin of backend.Attention{Forward,Backward}GPU) ------------------

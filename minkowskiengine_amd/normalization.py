@@ -24,7 +24,11 @@ MinkowskiConditionalGroupNorm and MinkowskiConditionalGroupNormFunction (AdaGN /
 
     out[i, c] = act(group_norm(x)[i, c] * (1 + scale[b_i, c]) + shift[b_i, c]),        act: identity or SiLU
 
-with one row of scale / shift per instance."""
+with one row of scale / shift per instance.
+
+The three fused Functions (`_InstanceNormAffineFunction`, `MinkowskiGroupNormFunction`,
+`MinkowskiConditionalGroupNormFunction`) derive from `_SegNormFunction`, which holds what they share; a subclass only
+says which operator pair it is and where its gradients go among its inputs."""
 import torch
 from torch.autograd import Function
 from torch.nn import Parameter
@@ -36,36 +40,86 @@ from .convolution import MinkowskiModuleBase
 from .sparse_tensor import SparseTensor
 
 
-class _InstanceNormAffineFunction(Function):
-    """The fused form the modules use: normalisation and affine map in one operator.  weight / bias: (1, C) or (C,)
-    tensors of the parameter dtype (fp32 for fp32 and bf16 features, float64 for float64) or None."""
+_INSTANCE, _GROUP, _COND = "InstanceNorm", "GroupNorm", "ConditionalGroupNorm"     # <kind>{Forward,Backward}GPU
+
+
+class _SegNormFunction(Function):
+    """What the Functions of the three fused norms share: the preparation of the operands, what is kept for backward and
+    the shapes of the parameter gradients.  The operators are called where `kind` is tested, with the arguments each of
+    them takes, written out (a step of these layers is host-bound at small sizes: no argument lists are assembled here).
+    num_groups is read by the two group norms; scale, shift and activation by the conditional one."""
 
     @staticmethod
-    def forward(ctx, in_feat, weight, bias, eps, in_coords_key, glob_coords_key, coords_manager):
+    def _forward(ctx, kind, in_feat, num_groups, weight, bias, scale, shift, activation, eps, in_coords_key,
+                 glob_coords_key, coords_manager):
         if glob_coords_key is None:
             glob_coords_key = _host.key_like(in_coords_key)
         in_feat = in_feat.contiguous()
         w = None if weight is None else weight.detach().reshape(-1).contiguous()
         b = None if bias is None else bias.detach().reshape(-1).contiguous()
-        fw_fn = get_minkowski_function("InstanceNormForward", in_feat, in_coords_key)
-        out, mean, rstd = fw_fn(in_feat, w, b, float(eps), in_coords_key, glob_coords_key, coords_manager._manager)
-        ctx.save_for_backward(in_feat, w, mean, rstd)
-        ctx.misc = (in_coords_key, glob_coords_key, coords_manager,
-                    None if weight is None else weight.shape, None if bias is None else bias.shape)
+        w_shape, b_shape = None if weight is None else weight.shape, None if bias is None else bias.shape
+        fw_fn = get_minkowski_function(kind + "Forward", in_feat, in_coords_key)
+        manager = coords_manager._manager
+        if kind is _INSTANCE:
+            out, mean, rstd = fw_fn(in_feat, w, b, float(eps), in_coords_key, glob_coords_key, manager)
+            ctx.save_for_backward(in_feat, w, mean, rstd)
+            ctx.misc = (in_coords_key, glob_coords_key, coords_manager, w_shape, b_shape)
+        elif kind is _GROUP:
+            num_groups = int(num_groups)
+            out, mean, rstd = fw_fn(in_feat, num_groups, w, b, float(eps), in_coords_key, glob_coords_key, manager)
+            ctx.save_for_backward(in_feat, w, mean, rstd)
+            ctx.misc = (num_groups, in_coords_key, glob_coords_key, coords_manager, w_shape, b_shape)
+        else:
+            num_groups = int(num_groups)
+            sc = None if scale is None else scale.detach().contiguous()
+            sh = None if shift is None else shift.detach().contiguous()
+            out, mean, rstd = fw_fn(in_feat, num_groups, w, b, sc, sh, activation, float(eps), in_coords_key,
+                                    glob_coords_key, manager)
+            ctx.save_for_backward(in_feat, w, b, sc, sh, mean, rstd)
+            ctx.misc = (num_groups, activation, in_coords_key, glob_coords_key, coords_manager, w_shape, b_shape)
         return out
 
     @staticmethod
-    def backward(ctx, grad_out):
+    def _backward(ctx, kind, grad_out):
+        """-> (grad_in, grad_weight, grad_bias) and, for the conditional norm, (grad_scale, grad_shift) after them; None
+        where not needed"""
+        need = ctx.needs_input_grad
+        in_key, glob_key, coords_manager, w_shape, b_shape = ctx.misc[-5:]
+        i = 1 if kind is _INSTANCE else 2                       # where weight stands among forward's inputs
+        need_w, need_b = w_shape is not None and need[i], b_shape is not None and need[i + 1]
+        bw_fn = get_minkowski_function(kind + "Backward", grad_out, in_key)
+        grad_out, manager = grad_out.contiguous(), coords_manager._manager
+        if kind is _COND:
+            in_feat, w, b, sc, sh, mean, rstd = ctx.saved_tensors
+            need_sc, need_sh = sc is not None and need[4], sh is not None and need[5]
+            grad_in, grad_w, grad_b, grad_sc, grad_sh = bw_fn(
+                in_feat, grad_out, ctx.misc[0], w, b, sc, sh, ctx.misc[1], mean, rstd, in_key, glob_key, manager,
+                need_grad_in=need[0], need_grad_weight=need_w, need_grad_bias=need_b, need_grad_scale=need_sc,
+                need_grad_shift=need_sh)
+            return (grad_in, grad_w.view(w_shape) if need_w else None, grad_b.view(b_shape) if need_b else None,
+                    grad_sc if need_sc else None, grad_sh if need_sh else None)
         in_feat, w, mean, rstd = ctx.saved_tensors
-        in_key, glob_key, coords_manager, w_shape, b_shape = ctx.misc
-        need_w = w_shape is not None and ctx.needs_input_grad[1]
-        need_b = b_shape is not None and ctx.needs_input_grad[2]
-        bw_fn = get_minkowski_function("InstanceNormBackward", grad_out, in_key)
-        grad_in, grad_w, grad_b = bw_fn(in_feat, grad_out.contiguous(), w, mean, rstd, in_key, glob_key,
-                                        coords_manager._manager, need_grad_in=ctx.needs_input_grad[0],
-                                        need_grad_weight=need_w, need_grad_bias=need_b)
-        return (grad_in, grad_w.view(w_shape) if need_w else None, grad_b.view(b_shape) if need_b else None,
-                None, None, None, None)
+        if kind is _INSTANCE:
+            grad_in, grad_w, grad_b = bw_fn(in_feat, grad_out, w, mean, rstd, in_key, glob_key, manager,
+                                            need_grad_in=need[0], need_grad_weight=need_w, need_grad_bias=need_b)
+        else:
+            grad_in, grad_w, grad_b = bw_fn(in_feat, grad_out, ctx.misc[0], w, mean, rstd, in_key, glob_key, manager,
+                                            need_grad_in=need[0], need_grad_weight=need_w, need_grad_bias=need_b)
+        return grad_in, grad_w.view(w_shape) if need_w else None, grad_b.view(b_shape) if need_b else None
+
+
+class _InstanceNormAffineFunction(_SegNormFunction):
+    """The fused form the modules use: normalisation and affine map in one operator.  weight / bias: (1, C) or (C,)
+    tensors of the parameter dtype (fp32 for fp32 and bf16 features, float64 for float64) or None."""
+
+    @staticmethod
+    def forward(ctx, in_feat, weight, bias, eps, in_coords_key, glob_coords_key, coords_manager):
+        return _SegNormFunction._forward(ctx, _INSTANCE, in_feat, None, weight, bias, None, None, None, eps,
+                                         in_coords_key, glob_coords_key, coords_manager)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (*_SegNormFunction._backward(ctx, _INSTANCE, grad_out), None, None, None, None)
 
 
 class MinkowskiInstanceNormFunction(Function):
@@ -143,37 +197,19 @@ class MinkowskiStableInstanceNorm(_InstanceNormBase):
         self.eps = 1e-6
 
 
-class MinkowskiGroupNormFunction(Function):
+class MinkowskiGroupNormFunction(_SegNormFunction):
     """Group normalisation of the feature rows of a coordinate map, every instance (batch index) on its own.  weight /
     bias: (C,) tensors of the parameter dtype (fp32 for fp32 and bf16 features, float64 for float64) or None."""
 
     @staticmethod
     def forward(ctx, in_feat, num_groups, weight, bias, eps, in_coords_key, glob_coords_key=None, coords_manager=None):
-        if glob_coords_key is None:
-            glob_coords_key = _host.key_like(in_coords_key)
-        in_feat = in_feat.contiguous()
-        w = None if weight is None else weight.detach().reshape(-1).contiguous()
-        b = None if bias is None else bias.detach().reshape(-1).contiguous()
-        fw_fn = get_minkowski_function("GroupNormForward", in_feat, in_coords_key)
-        out, mean, rstd = fw_fn(in_feat, int(num_groups), w, b, float(eps), in_coords_key, glob_coords_key,
-                                coords_manager._manager)
-        ctx.save_for_backward(in_feat, w, mean, rstd)
-        ctx.misc = (int(num_groups), in_coords_key, glob_coords_key, coords_manager,
-                    None if weight is None else weight.shape, None if bias is None else bias.shape)
-        return out
+        return _SegNormFunction._forward(ctx, _GROUP, in_feat, num_groups, weight, bias, None, None, None, eps,
+                                         in_coords_key, glob_coords_key, coords_manager)
 
     @staticmethod
     def backward(ctx, grad_out):
-        in_feat, w, mean, rstd = ctx.saved_tensors
-        num_groups, in_key, glob_key, coords_manager, w_shape, b_shape = ctx.misc
-        need_w = w_shape is not None and ctx.needs_input_grad[2]
-        need_b = b_shape is not None and ctx.needs_input_grad[3]
-        bw_fn = get_minkowski_function("GroupNormBackward", grad_out, in_key)
-        grad_in, grad_w, grad_b = bw_fn(in_feat, grad_out.contiguous(), num_groups, w, mean, rstd, in_key, glob_key,
-                                        coords_manager._manager, need_grad_in=ctx.needs_input_grad[0],
-                                        need_grad_weight=need_w, need_grad_bias=need_b)
-        return (grad_in, None, grad_w.view(w_shape) if need_w else None, grad_b.view(b_shape) if need_b else None,
-                None, None, None, None)
+        grad_in, grad_w, grad_b = _SegNormFunction._backward(ctx, _GROUP, grad_out)
+        return grad_in, None, grad_w, grad_b, None, None, None, None
 
 
 class _GroupNormBase(MinkowskiModuleBase):
@@ -223,7 +259,7 @@ class MinkowskiGroupNorm(_GroupNormBase):
         return SparseTensor(output, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
 
 
-class MinkowskiConditionalGroupNormFunction(Function):
+class MinkowskiConditionalGroupNormFunction(_SegNormFunction):
     """Group normalisation of the feature rows of a coordinate map, every instance (batch index) on its own, modulated per
     instance and channel and followed by an optional SiLU: act(gn(x) * (1 + scale[b]) + shift[b]).  weight / bias: (C,)
     tensors of the parameter dtype (fp32 for fp32 and bf16 features, float64 for float64) or None; scale / shift:
@@ -233,36 +269,13 @@ class MinkowskiConditionalGroupNormFunction(Function):
     @staticmethod
     def forward(ctx, in_feat, num_groups, weight, bias, scale, shift, activation, eps, in_coords_key,
                 glob_coords_key=None, coords_manager=None):
-        if glob_coords_key is None:
-            glob_coords_key = _host.key_like(in_coords_key)
-        in_feat = in_feat.contiguous()
-        w = None if weight is None else weight.detach().reshape(-1).contiguous()
-        b = None if bias is None else bias.detach().reshape(-1).contiguous()
-        sc = None if scale is None else scale.detach().contiguous()
-        sh = None if shift is None else shift.detach().contiguous()
-        fw_fn = get_minkowski_function("ConditionalGroupNormForward", in_feat, in_coords_key)
-        out, mean, rstd = fw_fn(in_feat, int(num_groups), w, b, sc, sh, activation, float(eps), in_coords_key,
-                                glob_coords_key, coords_manager._manager)
-        ctx.save_for_backward(in_feat, w, b, sc, sh, mean, rstd)
-        ctx.misc = (int(num_groups), activation, in_coords_key, glob_coords_key, coords_manager,
-                    None if weight is None else weight.shape, None if bias is None else bias.shape)
-        return out
+        return _SegNormFunction._forward(ctx, _COND, in_feat, num_groups, weight, bias, scale, shift, activation, eps,
+                                         in_coords_key, glob_coords_key, coords_manager)
 
     @staticmethod
     def backward(ctx, grad_out):
-        in_feat, w, b, sc, sh, mean, rstd = ctx.saved_tensors
-        num_groups, activation, in_key, glob_key, coords_manager, w_shape, b_shape = ctx.misc
-        need_w = w_shape is not None and ctx.needs_input_grad[2]
-        need_b = b_shape is not None and ctx.needs_input_grad[3]
-        need_sc = sc is not None and ctx.needs_input_grad[4]
-        need_sh = sh is not None and ctx.needs_input_grad[5]
-        bw_fn = get_minkowski_function("ConditionalGroupNormBackward", grad_out, in_key)
-        grad_in, grad_w, grad_b, grad_sc, grad_sh = bw_fn(
-            in_feat, grad_out.contiguous(), num_groups, w, b, sc, sh, activation, mean, rstd, in_key, glob_key,
-            coords_manager._manager, need_grad_in=ctx.needs_input_grad[0], need_grad_weight=need_w, need_grad_bias=need_b,
-            need_grad_scale=need_sc, need_grad_shift=need_sh)
-        return (grad_in, None, grad_w.view(w_shape) if need_w else None, grad_b.view(b_shape) if need_b else None,
-                grad_sc if need_sc else None, grad_sh if need_sh else None, None, None, None, None, None)
+        grad_in, grad_w, grad_b, grad_sc, grad_sh = _SegNormFunction._backward(ctx, _COND, grad_out)
+        return grad_in, None, grad_w, grad_b, grad_sc, grad_sh, None, None, None, None, None
 
 
 _GNC_ACTIVATIONS = (None, "silu")

@@ -15,6 +15,7 @@ import torch
 from torch.autograd import gradcheck
 
 from helpers import assert_close, make_cloud
+from test_gpu_group_norm import OPERATOR_DTYPES, OPERATOR_SHAPES, check_hosts_and_runs_agree
 
 pytestmark = pytest.mark.gpu
 GC = dict(eps=1e-6, atol=1e-5, rtol=1e-3)     # MinkowskiEngine/utils/gradcheck.py:37-39
@@ -284,6 +285,15 @@ def test_row_order_and_bitwise_reproducibility(device):
     assert_close(shuf[1], z["want"][1][perm.numpy()], what="grad_in vs the expectation")
 
 
+@pytest.mark.parametrize("dtype", OPERATOR_DTYPES, ids=lambda d: str(d).split(".")[-1])
+@pytest.mark.parametrize("c,groups", OPERATOR_SHAPES)
+def test_operators_agree_across_hosts_and_runs(device, c, groups, dtype):
+    """ConditionalGroupNorm{Forward,Backward}GPU on the inputs of tests/test_gpu_group_norm.py's test of this name, with
+    scale / shift given and None and with and without the SiLU"""
+    import minkowskiengine_amd as ME
+    check_hosts_and_runs_agree(ME, device, ("ConditionalGroupNorm",), c, groups, dtype)
+
+
 def test_non_default_stream(device, host_layer):
     import minkowskiengine_amd as ME
     z = _case("c12_g4_straddle")
@@ -446,3 +456,10 @@ def test_api_errors(device, host_layer):
     with pytest.raises(RuntimeError):                                      # float64 features need a .double() module
         layer(ME.SparseTensor(x.F.double(), coordinate_map_key=x.coordinate_map_key,
                               coordinate_manager=x.coordinate_manager))
+    # a backward call without the statistics of the forward pass (the native binding refuses None for a tensor argument)
+    from minkowskiengine_amd import host
+    key, mgr = x.coordinate_map_key, x.coordinate_manager._manager
+    bw = ME.get_minkowski_function("ConditionalGroupNormBackward", x.F, key)
+    with pytest.raises(RuntimeError if host_layer == "python" else TypeError,
+                       match="conditional group norm backward needs mean and rstd" if host_layer == "python" else None):
+        bw(x.F, x.F, 2, None, None, None, None, None, None, None, key, host.key_like(key), mgr)

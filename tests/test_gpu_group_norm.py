@@ -192,6 +192,98 @@ def test_row_order_and_bitwise_reproducibility(device):
     assert_close(shuf[1], z["want"][1][perm.numpy()], what="grad_in vs the expectation")
 
 
+# The operators themselves, on every branch their shared host code owns.  (c, groups): 12 / 4 and 24 / 4 make a 16-byte
+# piece straddle groups in fp32 and in bf16; 16 / 16 is one channel per group, 8 / 1 one group.
+OPERATOR_SHAPES = ((12, 4), (24, 4), (16, 16), (8, 1))
+OPERATOR_DTYPES = (torch.float32, torch.bfloat16, torch.float64)
+OPERATORS = {"InstanceNorm": ((None, None),), "GroupNorm": ((None, None),),        # (modulated, activation)
+             "ConditionalGroupNorm": ((True, "silu"), (True, None), (False, "silu"), (False, None))}
+
+
+def operator_sweep(ME, device, kind, c, groups, dtype):
+    """One operator pair of the current host on seeded inputs -> [(label, tensor | None)], every returned tensor in a
+    fixed order.  310 rows with the batch indices 0, 1, 3, 6, the rows of index 3 pruned away, so that one instance of the
+    origin map has no rows on this map; weight / bias (and scale / shift) given and None; the need_grad_* combinations the
+    autograd Functions produce; grad_out contiguous, a transposed view, and of another dtype than the features."""
+    from minkowskiengine_amd import host
+    g = torch.Generator().manual_seed(1000 * c + groups)
+    sizes, ids = (90, 70, 60, 90), (0, 1, 3, 6)
+    coords = _scene(sizes, 3, False, 7)
+    coords[:, 0] = torch.repeat_interleave(torch.tensor(ids, dtype=coords.dtype), torch.tensor(sizes))
+    x = ME.SparseTensor(torch.randn(sum(sizes), c, generator=g).to(dtype).to(device), coords.to(device))
+    xp = ME.MinkowskiPruning()(x, (coords[:, 0] != 3).to(device))
+    feats, key, mgr = xp.F.detach().contiguous(), xp.coordinate_map_key, xp.coordinate_manager._manager
+    n, nb = feats.shape[0], len(ids)
+    assert n == 250 and sorted(set(xp.C[:, 0].tolist())) == [0, 1, 6]
+    pd = torch.float64 if dtype == torch.float64 else torch.float32
+    weight, bias = (torch.rand(c, generator=g) + 0.5).to(pd).to(device), (torch.rand(c, generator=g) - 0.5).to(pd).to(device)
+    scale = (0.5 * torch.randn(nb, c, generator=g)).to(pd).to(device)
+    shift = torch.randn(nb, c, generator=g).to(pd).to(device)
+    dy = (torch.rand(n, c, generator=g) - 0.5).to(dtype).to(device)
+    dy_t = (torch.rand(c, n, generator=g) - 0.5).to(dtype).to(device).t()
+    assert not dy_t.is_contiguous()
+    dy_other = dy.to(torch.bfloat16 if dtype == torch.float32 else torch.float32)
+    fw = ME.get_minkowski_function(kind + "Forward", feats, key)
+    bw = ME.get_minkowski_function(kind + "Backward", feats, key)
+    lead = () if kind == "InstanceNorm" else (groups,)
+    got = []
+    for affine in (True, False):
+        w, b = (weight, bias) if affine else (None, None)
+        for mod, act in OPERATORS[kind]:
+            cond = mod is not None
+            sc, sh = (scale, shift) if mod else (None, None)
+            glob = host.key_like(key)
+            out, mean, rstd = fw(feats, *lead, w, b, *((sc, sh, act) if cond else ()), EPS, key, glob, mgr)
+            assert mean.dtype == pd and tuple(mean.shape) == (nb, groups if lead else c) and out.dtype == dtype
+            tag = f"{kind} affine={affine} mod={mod} act={act}"
+            got += [(tag + " out", out), (tag + " mean", mean), (tag + " rstd", rstd)]
+            everything = (True, affine, affine) + ((bool(mod), bool(mod)) if cond else ())
+            runs = [(everything, dy), (everything, dy_t), (everything, dy_other),
+                    ((True,) + (False,) * (len(everything) - 1), dy), ((False,) + everything[1:], dy)]
+            if cond:
+                runs.append((everything[:3] + (False, False), dy))
+            for need, grad_out in runs:
+                names = ("need_grad_in", "need_grad_weight", "need_grad_bias", "need_grad_scale", "need_grad_shift")
+                grads = bw(feats, grad_out, *lead, w, *((b, sc, sh, act) if cond else ()), mean, rstd, key, glob, mgr,
+                           **dict(zip(names, need)))
+                assert len(grads) == len(need)
+                for i, (wanted, t) in enumerate(zip(need, grads)):
+                    assert (t is not None) == wanted, (tag, need, i)
+                    got.append((f"{tag} need={need} grad_out={tuple(grad_out.stride())}/{grad_out.dtype} grad[{i}]", t))
+    return got
+
+
+def assert_sweeps_equal(a, b, what):
+    assert [label for label, _ in a] == [label for label, _ in b]
+    for (label, s), (_, t) in zip(a, b):
+        assert (s is None) == (t is None), (what, label)
+        if s is not None:
+            assert s.dtype == t.dtype and s.shape == t.shape and torch.equal(s, t), (what, label)
+
+
+def check_hosts_and_runs_agree(ME, device, kinds, c, groups, dtype):
+    """every tensor an operator returns is the same bit for bit on the two host layers, and on a host's second run"""
+    prev = ME.get_host()
+    try:
+        sweeps = []
+        for host in ("python", "native", "python", "native"):
+            ME.set_host(host)
+            sweeps.append([t for kind in kinds for t in operator_sweep(ME, device, kind, c, groups, dtype)])
+    finally:
+        ME.set_host(prev)
+    assert all(bool(torch.isfinite(t).all()) for _, t in sweeps[0] if t is not None)
+    for i, what in ((1, "native against python"), (2, "python again"), (3, "native again")):
+        assert_sweeps_equal(sweeps[0], sweeps[i], what)
+
+
+@pytest.mark.parametrize("dtype", OPERATOR_DTYPES, ids=lambda d: str(d).split(".")[-1])
+@pytest.mark.parametrize("c,groups", OPERATOR_SHAPES)
+def test_operators_agree_across_hosts_and_runs(device, c, groups, dtype):
+    """InstanceNorm and GroupNorm {Forward,Backward}GPU (the conditional pair: tests/test_gpu_cond_group_norm.py)"""
+    import minkowskiengine_amd as ME
+    check_hosts_and_runs_agree(ME, device, ("InstanceNorm", "GroupNorm"), c, groups, dtype)
+
+
 @pytest.mark.parametrize("name", list(BF16_CASES))
 def test_bf16(device, host_layer, name):
     import minkowskiengine_amd as ME
@@ -311,6 +403,13 @@ def test_api_errors(device, host_layer):
     with pytest.raises(RuntimeError):                                      # float64 features need a .double() module
         ME.MinkowskiGroupNorm(2, 6).to(device)(ME.SparseTensor(x.F.double(), coordinate_map_key=x.coordinate_map_key,
                                                                coordinate_manager=x.coordinate_manager))
+    # a backward call without the statistics of the forward pass (the native binding refuses None for a tensor argument)
+    from minkowskiengine_amd import host
+    key, mgr = x.coordinate_map_key, x.coordinate_manager._manager
+    bw = ME.get_minkowski_function("GroupNormBackward", x.F, key)
+    with pytest.raises(RuntimeError if host_layer == "python" else TypeError,
+                       match="group norm backward needs mean and rstd" if host_layer == "python" else None):
+        bw(x.F, x.F, 2, None, None, None, key, host.key_like(key), mgr)
 
 
 def test_composition_on_a_pruned_generative_branch(device, host_layer):

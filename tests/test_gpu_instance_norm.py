@@ -347,6 +347,13 @@ def test_api_errors(device, host_layer):
     with pytest.raises(RuntimeError):                                      # float64 features need a .double() module
         ME.MinkowskiInstanceNorm(6).to(device)(ME.SparseTensor(x.F.double(), coordinate_map_key=x.coordinate_map_key,
                                                                coordinate_manager=x.coordinate_manager))
+    # a backward call without the statistics of the forward pass (the native binding refuses None for a tensor argument)
+    from minkowskiengine_amd import host
+    key, mgr = x.coordinate_map_key, x.coordinate_manager._manager
+    bw = ME.get_minkowski_function("InstanceNormBackward", x.F, key)
+    with pytest.raises(RuntimeError if host_layer == "python" else TypeError,
+                       match="instance norm backward needs mean and rstd" if host_layer == "python" else None):
+        bw(x.F, x.F, None, None, None, key, host.key_like(key), mgr)
 
 
 def test_strided_map_uses_its_own_rows(device, host_layer):

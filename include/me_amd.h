@@ -117,7 +117,11 @@ typedef struct me_region {
  *              (me_attn_window_ids_workspace_bytes, me_attn_window_ids, me_attn_segment_lists_workspace_bytes,
  *              me_attn_segment_lists)
  *   1.22 (320)  round 22: rotary position embedding from voxel coordinates: the (cos, sin) table of a coordinate map and the
- *              rotation of the channel pairs of strided rows, forward and backward (me_rope_table, me_rope_apply) */
+ *              rotation of the channel pairs of strided rows, forward and backward (me_rope_table, me_rope_apply)
+ *   1.23 (330)  round 23: layer norm and RMS norm over the channel axis of strided rows, with the residual add of a
+ *              pre-norm block folded into both directions; rows in the registers of lane teams, parameter gradients as
+ *              fixed-order sums (me_lnorm_chunks, me_lnorm_workspace_bytes, me_lnorm_forward, me_lnorm_backward and
+ *              the _f64 twins me_lnorm_forward_f64, me_lnorm_backward_f64) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1412,6 +1416,58 @@ int me_rope_table(const int32_t *coords_dev, int64_t n, int32_t ncol, const int3
                   int32_t table_f64, void *table_dev, void *stream);
 int me_rope_apply(const void *x_dev, int64_t x_stride, void *y_dev, int64_t y_stride, int64_t n, int32_t heads, int32_t d,
                   const void *table_dev, int32_t sign, int32_t dtype, void *stream);
+
+/* ---- layer norm and RMS norm over the channel axis (MinkowskiLayerNorm, MinkowskiRMSNorm, their forward_residual,
+ *      MinkowskiFunctional.layer_norm / rms_norm; csrc/layer_norm.hip, ABI 1.23) ----
+ * Rows of c elements (float, or __bf16 with is_bf16 != 0) with one row stride per operand, in elements, >= c: a column
+ * view of a wider matrix is taken as it is.  No coordinate map.  Per row, with s = x, or s = T(float(residual) + float(x))
+ * when a residual is given (the sum is rounded once to the row type, stored to stream_out, and everything below reads
+ * the rounded value — bit for bit the unfused addition followed by the plain call):
+ *   layer (rms = 0):  mean = sum(s) / c,  rstd = 1 / sqrt(sum((s - mean)^2) / c + eps),  y = (s - mean) rstd gamma + beta
+ *   RMS   (rms != 0): rstd = 1 / sqrt(sum(s^2) / c + eps),  y = s rstd gamma        (beta is applied when given)
+ * in fp32 with one rounded store; the variance is the centred sum of squares of the row held in registers (no
+ * E[x^2] - mean^2).  gamma / beta: c floats or NULL (1 / 0).  mean [n] (NULL for rms) and rstd [n] are fp32.
+ * Backward, with xhat = (s - mean) rstd, g = dy gamma, s1 = sum(g), s2 = sum(g xhat) (the fp32 / bf16 kernel centres the row
+ * again exactly as the forward pass did and so has the forward's xhat bit for bit; it does not read mean_dev, whose
+ * rounding would be large against a small deviation of a row around a large mean; the _f64 twin reads it):
+ *   dx = rstd (g - (s1 + xhat s2) / c)        (RMS: without s1)
+ * rounded to the row type; with dstream (the gradient arriving at stream_out) dx = T(float(dx) + float(dstream)), the two
+ * roundings of the gradient accumulation of the unfused graph.  That one dx is the gradient of x and of residual.
+ * grad_gamma = sum over rows of dy xhat, grad_beta = sum over rows of dy (fp32; NULL: not computed; both are computed
+ * for RMS too when asked for): the rows are cut into G = me_lnorm_chunks(n, c, elem_bytes) chunks [g n / G, (g + 1) n / G),
+ * a workgroup writes one record [2][c] of its chunk into the workspace [G][2][c] and a second kernel adds the records in
+ * ascending g.  No atomics; G depends on the three arguments only (no device query; at most 1024, at least 16 KiB of x a
+ * chunk), so the gradients do not depend on the device.
+ * Every sum over a row is one balanced tree over the channel index, whatever piece width (16 bytes where c, the strides
+ * and the addresses allow, 4 bf16 channels or single elements otherwise) and lane team serve the row: y, stream_out and
+ * dx of a view equal those of its contiguous copy bit for bit; the parameter gradients are bitwise reproducible per layout.
+ * One launch forward; one launch backward, two with a parameter gradient.  No synchronisation, no read-back.
+ * Host-side errors, nothing launched: c < 1, c > ME_LNORM_MAX_C (fp32 / bf16 entry points), n < 0 or n >= 2^31, a row
+ * stride below c, a residual without stream_out, a workspace below me_lnorm_workspace_bytes when a parameter gradient
+ * is wanted; then, with n > 0, a missing x, y / dy, rstd or (layer) mean.  n = 0 succeeds: nothing is read, and the wanted
+ * parameter gradients are written as zeros (by the reduce kernel over no records).
+ * The _f64 twins are the plain formulas in double for any c (one wave a row; parameter gradients one thread a channel
+ * over the rows in ascending order, no workspace): the gradcheck yardstick. */
+#define ME_LNORM_MAX_C 2048
+int32_t me_lnorm_chunks(int64_t n, int32_t c, int32_t elem_bytes);
+int64_t me_lnorm_workspace_bytes(int64_t n, int32_t c, int32_t elem_bytes);
+int me_lnorm_forward(const void *x_dev, const void *residual_dev, void *stream_out_dev, int32_t is_bf16, int64_t x_stride,
+                     int64_t residual_stride, int64_t stream_out_stride, int64_t n, int32_t c, int32_t rms,
+                     const float *gamma_dev, const float *beta_dev, float eps, void *y_dev, int64_t y_stride,
+                     float *mean_dev, float *rstd_dev, void *stream);
+int me_lnorm_backward(const void *x_dev, const void *dy_dev, const void *dstream_dev, int32_t is_bf16, int64_t x_stride,
+                      int64_t dy_stride, int64_t dstream_stride, int64_t n, int32_t c, int32_t rms,
+                      const float *gamma_dev, const float *mean_dev, const float *rstd_dev, void *dx_dev,
+                      int64_t dx_stride, float *grad_gamma_dev, float *grad_beta_dev, void *workspace_dev,
+                      int64_t workspace_bytes, void *stream);
+int me_lnorm_forward_f64(const double *x_dev, const double *residual_dev, double *stream_out_dev, int64_t x_stride,
+                         int64_t residual_stride, int64_t stream_out_stride, int64_t n, int32_t c, int32_t rms,
+                         const double *gamma_dev, const double *beta_dev, double eps, double *y_dev, int64_t y_stride,
+                         double *mean_dev, double *rstd_dev, void *stream);
+int me_lnorm_backward_f64(const double *x_dev, const double *dy_dev, const double *dstream_dev, int64_t x_stride,
+                          int64_t dy_stride, int64_t dstream_stride, int64_t n, int32_t c, int32_t rms,
+                          const double *gamma_dev, const double *mean_dev, const double *rstd_dev, double *dx_dev,
+                          int64_t dx_stride, double *grad_gamma_dev, double *grad_beta_dev, void *stream);
 
 /* ---- cross-attention to a dense context (MinkowskiCrossAttention, MinkowskiFunctional.cross_attention;
  *      csrc/attention.hip, ABI 1.20) ----

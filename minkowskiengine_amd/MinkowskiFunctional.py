@@ -7,7 +7,8 @@ torch's needs one dense tensor per sample, so they run MinkowskiGroupNorm's and 
 operators of attention.py (csrc/attention.hip); and `local_attention`, which attends inside a kernel region on the
 operators of local_attention.py (csrc/local_attention.hip); and `serialized_attention`, which attends inside the patches
 of a space-filling curve on the operators of serialized_attention.py (csrc/serial_attention.hip); and `cross_attention`,
-which attends from the rows of a sparse tensor to a dense context (attention.py, csrc/attention.hip)."""
+which attends from the rows of a sparse tensor to a dense context (attention.py, csrc/attention.hip); and `layer_norm` /
+`rms_norm`, which run MinkowskiLayerNorm's operators (normalization.py, csrc/layer_norm.hip)."""
 import torch.nn.functional as F
 
 from .layers import _rewrap
@@ -195,6 +196,20 @@ def rotary_embedding(input, num_heads, base=10000.0, unit=None):
     return SparseTensor(out, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
 
 
+def layer_norm(input, weight=None, bias=None, eps=1e-5):
+    """torch.nn.functional.layer_norm over the channel axis of the features of a SparseTensor or a TensorField
+    (MinkowskiLayerNorm as a function).  weight / bias: (C,) tensors or None."""
+    from .normalization import _row_norm
+    return _row_norm(input, None, weight, bias, eps, False)
+
+
+def rms_norm(input, weight=None, eps=None):
+    """torch.nn.functional.rms_norm over the channel axis of the features of a SparseTensor or a TensorField
+    (MinkowskiRMSNorm as a function).  weight: a (C,) tensor or None; eps=None: torch.finfo(features.dtype).eps."""
+    from .normalization import _row_norm
+    return _row_norm(input, None, weight, None, eps, True)
+
+
 __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention",
                                                 "local_attention", "serialized_attention", "cross_attention",
-                                                "window_attention", "rotary_embedding"]
+                                                "window_attention", "rotary_embedding", "layer_norm", "rms_norm"]

@@ -22,7 +22,8 @@ from .convolution import (  # noqa: F401
 from .channelwise import MinkowskiChannelwiseConvolution, MinkowskiChannelwiseConvolutionFunction  # noqa: F401
 from .normalization import (  # noqa: F401
     MinkowskiConditionalGroupNorm, MinkowskiConditionalGroupNormFunction, MinkowskiGroupNorm, MinkowskiGroupNormFunction,
-    MinkowskiInstanceNorm, MinkowskiInstanceNormFunction, MinkowskiStableInstanceNorm)
+    MinkowskiInstanceNorm, MinkowskiInstanceNormFunction, MinkowskiLayerNorm, MinkowskiLayerNormFunction, MinkowskiRMSNorm,
+    MinkowskiStableInstanceNorm)
 from .attention import (  # noqa: F401
     MinkowskiAttentionFunction, MinkowskiCrossAttention, MinkowskiCrossAttentionFunction, MinkowskiSelfAttention)
 from .serialized_attention import (  # noqa: F401

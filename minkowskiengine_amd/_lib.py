@@ -213,6 +213,16 @@ SIGNATURES = {
     "me_attn_segment_lists": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "me_rope_table": (ctypes.c_int, [c_vp, c_i64, c_i32, _P_I32, c_i32, ctypes.c_double, c_i32, c_vp, c_vp]),
     "me_rope_apply": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
+    "me_lnorm_chunks": (c_i32, [c_i64, c_i32, c_i32]),
+    "me_lnorm_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "me_lnorm_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                        ctypes.c_float, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "me_lnorm_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                         c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_lnorm_forward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                            ctypes.c_double, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "me_lnorm_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                             c_vp, c_i64, c_vp, c_vp, c_vp]),
     "me_attn_context_lists": (ctypes.c_int, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "me_attn_kv_splits": (c_i32, [c_i64, c_i64, c_i32, c_i32, c_i32]),
     "me_attn_split_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32, c_i32, c_i32]),

@@ -4041,6 +4041,91 @@ def RotaryEmbeddingBackwardGPU(grad_out, num_heads, base, unit, in_key, manager)
 
 
 # ------------------------------------------------------------------------------------------------
+# layer norm / RMS norm over the channel axis (csrc/layer_norm.hip, ABI 1.23; not in the reference): row-local, so the
+# operators take no coordinate map.  One pair serves both kinds (`rms`) and the residual form of a pre-norm block
+# (`residual` forward, `grad_stream` backward).  The operands may be strided row views.
+# ------------------------------------------------------------------------------------------------
+LNORM_MAX_C = 2048      # ME_LNORM_MAX_C: wider fp32 / bf16 rows are not served (the modules fall back to torch)
+
+
+def _lnorm_rows(name, t, like=None):
+    t = _attn_rows(name, t)
+    _check(like is None or (t.dtype == like.dtype and t.device == like.device and tuple(t.shape) == tuple(like.shape)),
+           name, "must have the dtype, device and shape of in_feat")
+    return t
+
+
+def LayerNormForwardGPU(in_feat, residual, weight, bias, eps, rms=False):
+    """-> (out_feat, stream | None, mean | None, rstd).  stream = residual + in_feat (rounded once to the feature dtype;
+    None without a residual), out = (s - mean) * rstd * weight + bias over the channels of every row s of the stream (of
+    in_feat without a residual); rms: out = s * rstd * weight with rstd = 1 / sqrt(mean(s^2) + eps) and no mean.  mean /
+    rstd: [n] in the parameter dtype (fp32 for fp32 and bf16 features, float64 for float64); weight / bias: C values of
+    that dtype or None.  One launch (me_lnorm_forward)."""
+    x = _lnorm_rows("in_feat", in_feat)
+    res = None if residual is None else _lnorm_rows("residual", residual, x)
+    n, c = int(x.shape[0]), int(x.shape[1])
+    _inorm_check_vec("weight", weight, x, c)
+    _inorm_check_vec("bias", bias, x, c)
+    f64 = x.dtype == torch.float64
+    _check(f64 or c <= LNORM_MAX_C, "rows of more than", LNORM_MAX_C, "channels are not served by the fp32 / bf16 kernels")
+    dev, pd = x.device, _inorm_param_dtype(x)
+    out = torch.empty((n, c), dtype=x.dtype, device=dev)
+    stream = None if res is None else torch.empty((n, c), dtype=x.dtype, device=dev)
+    mean = None if rms else torch.empty((n,), dtype=pd, device=dev)
+    rstd = torch.empty((n,), dtype=pd, device=dev)
+    if n == 0:
+        return out, stream, mean, rstd
+    lib = _lib.load()
+    strides = (_attn_stride(x), 0 if res is None else _attn_stride(res), c)
+    tail = (n, c, 1 if rms else 0, _ptr(weight), _ptr(bias), float(eps), _ptr(out), c, _ptr(mean), _ptr(rstd))
+    with _on(dev):
+        if f64:
+            _lib.check(lib.me_lnorm_forward_f64(_ptr(x), _ptr(res), _ptr(stream), *strides, *tail, _stream(dev)))
+        else:
+            _timed("lnorm_forward", dev, lambda: _lib.check(lib.me_lnorm_forward(
+                _ptr(x), _ptr(res), _ptr(stream), 1 if x.dtype == torch.bfloat16 else 0, *strides, *tail, _stream(dev))))
+    return out, stream, mean, rstd
+
+
+def LayerNormBackwardGPU(in_feat, grad_out_feat, grad_stream, weight, mean, rstd, rms=False, need_grad_in=True,
+                         need_grad_weight=True, need_grad_bias=True):
+    """-> (grad_in | None, grad_weight [C] | None, grad_bias [C] | None).  in_feat: the rows that were normalised (the
+    stream of the residual form); grad_stream: the gradient arriving at the stream output, or None — it is added to
+    grad_in, which then is the gradient of both in_feat and residual of the forward call.  The parameter gradients have the
+    parameter dtype and are fixed-order sums without atomics (me_lnorm_backward)."""
+    x = _lnorm_rows("in_feat", in_feat)
+    dy = _lnorm_rows("grad_out_feat", grad_out_feat.to(x.dtype), x)
+    ds = None if grad_stream is None else _lnorm_rows("grad_stream", grad_stream.to(x.dtype), x)
+    n, c = int(x.shape[0]), int(x.shape[1])
+    _inorm_check_vec("weight", weight, x, c)
+    _check(rstd is not None and (rms or mean is not None), "layer norm backward needs mean and rstd")
+    _inorm_check_vec("mean", mean, x, n)
+    _inorm_check_vec("rstd", rstd, x, n)
+    f64 = x.dtype == torch.float64
+    _check(f64 or c <= LNORM_MAX_C, "rows of more than", LNORM_MAX_C, "channels are not served by the fp32 / bf16 kernels")
+    dev, pd = x.device, _inorm_param_dtype(x)
+    grad_in = torch.empty((n, c), dtype=x.dtype, device=dev) if need_grad_in else None
+    grad_w = torch.empty((c,), dtype=pd, device=dev) if need_grad_weight else None
+    grad_b = torch.empty((c,), dtype=pd, device=dev) if need_grad_bias else None
+    if n == 0:
+        return grad_in, None if grad_w is None else grad_w.zero_(), None if grad_b is None else grad_b.zero_()
+    lib = _lib.load()
+    strides = (_attn_stride(x), _attn_stride(dy), 0 if ds is None else _attn_stride(ds))
+    body = (n, c, 1 if rms else 0, _ptr(weight), _ptr(mean), _ptr(rstd), _ptr(grad_in), c, _ptr(grad_w), _ptr(grad_b))
+    with _on(dev):
+        if f64:
+            _lib.check(lib.me_lnorm_backward_f64(_ptr(x), _ptr(dy), _ptr(ds), *strides, *body, _stream(dev)))
+        else:
+            elem = x.element_size()
+            ws = _workspace(int(lib.me_lnorm_workspace_bytes(n, c, elem)), dev) if (need_grad_weight or
+                                                                                   need_grad_bias) else None
+            _timed("lnorm_backward", dev, lambda: _lib.check(lib.me_lnorm_backward(
+                _ptr(x), _ptr(dy), _ptr(ds), 1 if x.dtype == torch.bfloat16 else 0, *strides, *body, _ptr(ws),
+                0 if ws is None else ws.numel(), _stream(dev))))
+    return grad_in, grad_w, grad_b
+
+
+# ------------------------------------------------------------------------------------------------
 # pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu)
 # ------------------------------------------------------------------------------------------------
 def PruningForwardGPU(in_feat, keep, in_key, out_key, manager):

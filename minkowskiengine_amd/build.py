@@ -18,6 +18,11 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=h
           "-Wno-unused-lambda-capture"]
 
 
+# per-file flags.  layer_norm.hip: no packed fp32 arithmetic (v_pk_{add,mul,fma}_f32) — its instantiations must round
+# alike, element by element, and new kernels of this library keep to the scalar fp32 forms
+FILE_FLAGS = {"layer_norm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
@@ -32,6 +37,7 @@ def _headers():
 def _compile_one(src, extra, verbose):
     obj = os.path.join(OBJ_DIR, os.path.splitext(os.path.basename(src))[0] + ".o")
     stamp = obj + ".flags"
+    extra = extra + FILE_FLAGS.get(os.path.basename(src), [])
     flags = " ".join(CFLAGS + extra)
     fresh = (os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == flags and
              all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in [src] + _headers()))

@@ -831,6 +831,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         },
         py::arg("grad_out"), py::arg("num_heads"), py::arg("base"), py::arg("unit"), py::arg("in_key"),
         py::arg("manager"));
+  // layer norm / RMS norm over the channel axis, with the residual add of a pre-norm block: csrc/layer_norm.hip
+  m.def("LayerNormForwardGPU",
+        [](const Tensor &in_feat, const py::object &residual, const py::object &weight, const py::object &bias, double eps,
+           bool rms) {
+          const Tensor res = opt_tensor(residual), w = opt_tensor(weight), b = opt_tensor(bias);
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = layer_norm_forward(in_feat, res, w, b, eps, rms);
+          }
+          return py::make_tuple(r[0], opt_out(r[1]), opt_out(r[2]), r[3]);
+        },
+        py::arg("in_feat"), py::arg("residual"), py::arg("weight"), py::arg("bias"), py::arg("eps"),
+        py::arg("rms") = false);
+  m.def("LayerNormBackwardGPU",
+        [](const Tensor &in_feat, const Tensor &grad_out, const py::object &grad_stream, const py::object &weight,
+           const py::object &mean, const Tensor &rstd, bool rms, bool need_grad_in, bool need_grad_weight,
+           bool need_grad_bias) {
+          const Tensor ds = opt_tensor(grad_stream), w = opt_tensor(weight), m = opt_tensor(mean);
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = layer_norm_backward(in_feat, grad_out, ds, w, m, rstd, rms, need_grad_in, need_grad_weight,
+                                    need_grad_bias);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]));
+        },
+        py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("grad_stream"), py::arg("weight"), py::arg("mean"),
+        py::arg("rstd"), py::arg("rms") = false, py::arg("need_grad_in") = true, py::arg("need_grad_weight") = true,
+        py::arg("need_grad_bias") = true);
   // tensor fields (field.cpp): the reference's InterpolationForwardGPU / InterpolationBackwardGPU and coo_spmm_int32 /
   // coo_spmm_average_int32 (pybind/extern.hpp:497-506), plus the CSR building blocks the autograd functions cache
   m.def("CsrFromCooGPU",

@@ -450,6 +450,13 @@ Tensor rotary_embedding_forward(Tensor x, int64_t num_heads, double base, const 
                                 CoordinateMapManager *mgr);
 Tensor rotary_embedding_backward(Tensor grad_out, int64_t num_heads, double base, const ivec &unit,
                                  CoordinateMapKey *in_key, CoordinateMapManager *mgr);
+// layer norm / RMS norm over the channel axis (csrc/layer_norm.hip; twin of backend.LayerNorm{Forward,Backward}GPU);
+// -> (out, stream | undefined, mean | undefined, rstd) and (grad_in, grad_weight, grad_bias), undefined where not wanted
+std::vector<Tensor> layer_norm_forward(const Tensor &in_feat, const Tensor &residual, const Tensor &weight,
+                                       const Tensor &bias, double eps, bool rms);
+std::vector<Tensor> layer_norm_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &grad_stream,
+                                        const Tensor &weight, const Tensor &mean, const Tensor &rstd, bool rms,
+                                        bool need_grad_in, bool need_grad_weight, bool need_grad_bias);
 // dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU / DensePolicy)
 int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box);
 std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,

@@ -1675,6 +1675,91 @@ Tensor rotary_embedding_backward(Tensor grad_out, int64_t num_heads, double base
   return rope_apply(grad_out, num_heads, base, unit, in_key, mgr, -1);
 }
 
+// ---- layer norm / RMS norm over the channel axis (csrc/layer_norm.hip, ABI 1.23; twin of
+// backend.LayerNorm{Forward,Backward}GPU): row-local, no coordinate map; strided row views go in as they are ------------------
+static Tensor lnorm_rows(const char *name, const Tensor &t, const Tensor *like = nullptr) {
+  Tensor r = attn_rows(name, t);
+  check(like == nullptr || (r.scalar_type() == like->scalar_type() && r.device() == like->device() &&
+                            r.sizes() == like->sizes()),
+        std::string(name) + " must have the dtype, device and shape of in_feat");
+  return r;
+}
+
+static void lnorm_check_width(const Tensor &x) {
+  check(x.scalar_type() == at::kDouble || x.size(1) <= ME_LNORM_MAX_C,
+        "rows of more than " + std::to_string(ME_LNORM_MAX_C) + " channels are not served by the fp32 / bf16 kernels");
+}
+
+std::vector<Tensor> layer_norm_forward(const Tensor &in_feat, const Tensor &residual, const Tensor &weight,
+                                       const Tensor &bias, double eps, bool rms) {
+  const Tensor x = lnorm_rows("in_feat", in_feat);
+  const Tensor res = residual.defined() ? lnorm_rows("residual", residual, &x) : Tensor();
+  const int64_t n = x.size(0);
+  const int c = (int)x.size(1);
+  inorm_check_vec("weight", weight, x, c);
+  inorm_check_vec("bias", bias, x, c);
+  lnorm_check_width(x);
+  const c10::Device dev = x.device();
+  const bool f64 = x.scalar_type() == at::kDouble;
+  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  Tensor out = at::empty({n, c}, x.options());
+  Tensor stream = res.defined() ? at::empty({n, c}, x.options()) : Tensor();
+  Tensor mean = rms ? Tensor() : at::empty({n}, popt), rstd = at::empty({n}, popt);
+  if (n == 0) return {out, stream, mean, rstd};
+  c10::DeviceGuard guard(dev);
+  const int64_t xs = attn_stride(x), rs = res.defined() ? attn_stride(res) : 0;
+  if (f64)
+    me_ok(me_lnorm_forward_f64(ptr<double>(x), ptr<double>(res), ptr<double>(stream), xs, rs, c, n, c, rms ? 1 : 0,
+                               ptr<double>(weight), ptr<double>(bias), eps, ptr<double>(out), c, ptr<double>(mean),
+                               ptr<double>(rstd), stream_of(dev)));
+  else
+    me_ok(me_lnorm_forward(vptr(x), vptr(res), vptr(stream), x.scalar_type() == at::kBFloat16 ? 1 : 0, xs, rs, c, n, c,
+                           rms ? 1 : 0, ptr<float>(weight), ptr<float>(bias), (float)eps, vptr(out), c, ptr<float>(mean),
+                           ptr<float>(rstd), stream_of(dev)));
+  return {out, stream, mean, rstd};
+}
+
+std::vector<Tensor> layer_norm_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &grad_stream,
+                                        const Tensor &weight, const Tensor &mean, const Tensor &rstd, bool rms,
+                                        bool need_grad_in, bool need_grad_weight, bool need_grad_bias) {
+  const Tensor x = lnorm_rows("in_feat", in_feat);
+  const Tensor dy = lnorm_rows("grad_out_feat", grad_out.to(x.scalar_type()), &x);
+  const Tensor ds = grad_stream.defined() ? lnorm_rows("grad_stream", grad_stream.to(x.scalar_type()), &x) : Tensor();
+  const int64_t n = x.size(0);
+  const int c = (int)x.size(1);
+  inorm_check_vec("weight", weight, x, c);
+  check(rstd.defined() && (rms || mean.defined()), "layer norm backward needs mean and rstd");
+  inorm_check_vec("mean", mean, x, n);
+  inorm_check_vec("rstd", rstd, x, n);
+  lnorm_check_width(x);
+  const c10::Device dev = x.device();
+  const bool f64 = x.scalar_type() == at::kDouble;
+  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  std::vector<Tensor> g(3);
+  if (need_grad_in) g[0] = at::empty({n, c}, x.options());
+  if (need_grad_weight) g[1] = at::empty({c}, popt);
+  if (need_grad_bias) g[2] = at::empty({c}, popt);
+  if (n == 0) {
+    for (size_t i = 1; i < 3; i++)
+      if (g[i].defined()) g[i].zero_();
+    return g;
+  }
+  c10::DeviceGuard guard(dev);
+  const int64_t xs = attn_stride(x), dys = attn_stride(dy), dss = ds.defined() ? attn_stride(ds) : 0;
+  if (f64) {
+    me_ok(me_lnorm_backward_f64(ptr<double>(x), ptr<double>(dy), ptr<double>(ds), xs, dys, dss, n, c, rms ? 1 : 0,
+                                ptr<double>(weight), ptr<double>(mean), ptr<double>(rstd), ptr<double>(g[0]), c,
+                                ptr<double>(g[1]), ptr<double>(g[2]), stream_of(dev)));
+    return g;
+  }
+  Tensor ws;
+  if (need_grad_weight || need_grad_bias) ws = workspace(me_lnorm_workspace_bytes(n, c, (int32_t)x.element_size()), dev);
+  me_ok(me_lnorm_backward(vptr(x), vptr(dy), vptr(ds), x.scalar_type() == at::kBFloat16 ? 1 : 0, xs, dys, dss, n, c,
+                          rms ? 1 : 0, ptr<float>(weight), ptr<float>(mean), ptr<float>(rstd), vptr(g[0]), c,
+                          ptr<float>(g[1]), ptr<float>(g[2]), vptr(ws), ws.defined() ? ws.numel() : 0, stream_of(dev)));
+  return g;
+}
+
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------
 Tensor pruning_forward(const Tensor &in_feat, const Tensor &keep, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr) {

@@ -28,8 +28,14 @@ with one row of scale / shift per instance.
 
 The three fused Functions (`_InstanceNormAffineFunction`, `MinkowskiGroupNormFunction`,
 `MinkowskiConditionalGroupNormFunction`) derive from `_SegNormFunction`, which holds what they share; a subclass only
-says which operator pair it is and where its gradients go among its inputs."""
+says which operator pair it is and where its gradients go among its inputs.
+
+MinkowskiLayerNorm, MinkowskiRMSNorm and MinkowskiLayerNormFunction normalise every ROW over its channels
+(torch.nn.LayerNorm / torch.nn.RMSNorm on the feature matrix): no instance, no coordinate map.  One operator pair,
+`LayerNorm{Forward,Backward}GPU` on csrc/layer_norm.hip, runs one pass forward and one pass plus a small merge backward,
+and takes the residual add of a pre-norm block into the same launches (`forward_residual`)."""
 import torch
+import torch.nn.functional as F
 from torch.autograd import Function
 from torch.nn import Parameter
 
@@ -37,6 +43,7 @@ from . import host as _host
 from .backend import PoolingMode
 from .common import get_minkowski_function
 from .convolution import MinkowskiModuleBase
+from .layers import _rewrap
 from .sparse_tensor import SparseTensor
 
 
@@ -315,3 +322,152 @@ class MinkowskiConditionalGroupNorm(_GroupNormBase):
             input.F, self.num_groups, self.weight, self.bias, scale, shift, self.activation, self.eps,
             input.coordinate_map_key, None, input._manager)
         return SparseTensor(output, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
+
+
+_LNORM_MAX_C = 2048     # ME_LNORM_MAX_C: the widest fp32 / bf16 row of csrc/layer_norm.hip
+
+
+class MinkowskiLayerNormFunction(Function):
+    """Layer norm (rms=False) or RMS norm (rms=True) of the rows of a feature matrix over their channels, on
+    `LayerNorm{Forward,Backward}GPU`.  weight / bias: (C,) tensors of the parameter dtype (fp32 for fp32 and bf16
+    features, float64 for float64) or None.  With `residual` (same dtype and shape as in_feat) the Function returns
+    (normed, stream): stream = residual + in_feat, normed = norm(stream), one launch per direction, bit-identical to the
+    addition followed by the plain call; its one input gradient is returned for in_feat and for residual, without a copy.
+    `owner`: a coordinate map key or manager of the call, which names the host layer that serves it."""
+
+    @staticmethod
+    def forward(ctx, in_feat, residual, weight, bias, eps, rms=False, owner=None):
+        fw_fn = get_minkowski_function("LayerNormForward", in_feat, owner)
+        w = None if weight is None else weight.detach().contiguous()
+        b = None if bias is None else bias.detach().contiguous()
+        out, stream, mean, rstd = fw_fn(in_feat, residual, w, b, float(eps), bool(rms))
+        ctx.save_for_backward(in_feat if residual is None else stream, w, mean, rstd)
+        ctx.misc = (bool(rms), owner, residual is not None, weight is not None, bias is not None)
+        ctx.set_materialize_grads(False)
+        return out if residual is None else (out, stream)
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_stream=None):
+        rms, owner, has_res, has_w, has_b = ctx.misc
+        x, w, mean, rstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_in, need_w, need_b = need[0] or (has_res and need[1]), has_w and need[2], has_b and need[3]
+        if grad_out is None:                  # only the stream was used: the add alone
+            return (grad_stream if need[0] else None, grad_stream if has_res and need[1] else None, None, None, None, None,
+                    None)
+        bw_fn = get_minkowski_function("LayerNormBackward", grad_out, owner)
+        grad_in, grad_w, grad_b = bw_fn(x, grad_out, grad_stream, w, mean, rstd, rms, need_grad_in=need_in,
+                                        need_grad_weight=need_w, need_grad_bias=need_b)
+        return (grad_in if need[0] else None, grad_in if has_res and need[1] else None, grad_w, grad_b, None, None, None)
+
+
+def _row_norm_key(input):
+    """the key that names the host layer of a SparseTensor or a TensorField"""
+    if isinstance(input, SparseTensor):
+        return input.coordinate_map_key
+    if hasattr(input, "coordinate_field_map_key"):
+        return input.coordinate_field_map_key
+    raise TypeError(f"a SparseTensor or a TensorField is expected, not a {type(input).__name__}")
+
+
+def _row_norm(input, residual, weight, bias, eps, rms):
+    """what the two modules and the two functionals run: features of `input` (plus those of `residual`) through the
+    Function, or through torch for the shapes the kernels do not serve; re-wrapped as the kind of `input`"""
+    key = _row_norm_key(input)
+    f = input.F
+    get_minkowski_function("LayerNormForward", f, key)              # (CPU features raise here, as everywhere)
+    pd = torch.float64 if f.dtype == torch.float64 else torch.float32
+    weight = weight if weight is None or weight.dtype == pd else weight.to(pd)
+    bias = bias if bias is None or bias.dtype == pd else bias.to(pd)
+    if eps is None:
+        eps = torch.finfo(f.dtype).eps
+    r = None
+    if residual is not None:
+        assert key == _row_norm_key(residual), "residual add needs a shared coordinate map"
+        r = residual.F
+        assert r.dtype == f.dtype and r.shape == f.shape, "input and residual must share dtype and shape"
+    if f.dim() != 2 or (f.dtype != torch.float64 and f.shape[1] > _LNORM_MAX_C):
+        stream = f if r is None else r + f
+        shape, w, b = (f.shape[-1],), None if weight is None else weight.to(f.dtype), None if bias is None else bias.to(f.dtype)
+        y = F.rms_norm(stream, shape, w, eps) if rms else F.layer_norm(stream, shape, w, b, eps)
+        return _rewrap(input, y) if r is None else (_rewrap(input, y), _rewrap(input, stream))
+    out = MinkowskiLayerNormFunction.apply(f, r, weight, bias, eps, rms, key)
+    return _rewrap(input, out) if r is None else (_rewrap(input, out[0]), _rewrap(input, out[1]))
+
+
+class _RowNormBase(MinkowskiModuleBase):
+    """what MinkowskiLayerNorm and MinkowskiRMSNorm share: the normalised shape, forward and forward_residual"""
+    _RMS = False
+
+    def _set_shape(self, normalized_shape):
+        shape = (normalized_shape,) if isinstance(normalized_shape, int) else tuple(normalized_shape)
+        if len(shape) != 1 or int(shape[0]) < 1:
+            raise ValueError(f"normalized_shape must be an int or a 1-tuple (the channel axis), got {normalized_shape!r}")
+        self.normalized_shape = (int(shape[0]),)
+
+    def _check(self, input):
+        _row_norm_key(input)
+        assert input.F.shape[-1] == self.normalized_shape[0], \
+            f"Channel size mismatch {self.normalized_shape[0]} != {input.F.shape[-1]}"
+
+    def forward(self, input):
+        self._check(input)
+        return _row_norm(input, None, self.weight, getattr(self, "bias", None), self.eps, self._RMS)
+
+    def forward_residual(self, input, residual):
+        """-> (normed, stream): stream = residual + input, normed = self(stream) — the tail of one half of a pre-norm
+        block and the head of the next, in one launch per direction, bit-identical to `stream = residual + input;
+        normed = self(stream)`.  Both inputs share a coordinate map key, dtype and shape."""
+        self._check(input)
+        return _row_norm(input, residual, self.weight, getattr(self, "bias", None), self.eps, self._RMS)
+
+
+class MinkowskiLayerNorm(_RowNormBase):
+    r"""torch.nn.LayerNorm over the channel axis of the feature matrix of a SparseTensor or a TensorField (the same kind
+    comes back): per row `(x - mean) / sqrt(var + eps) * weight + bias` with the biased variance over the channels.
+    `normalized_shape`: an int or a 1-tuple.  Parameters `weight`, `bias` of shape (C,), initialised and named as
+    torch.nn.LayerNorm's, so state dicts move between the two strictly (`bias=False`, `elementwise_affine=False`
+    included).  They stay fp32 for fp32 and bf16 features (bf16 rows are normalised in fp32 and rounded once) and become
+    float64 after `.double()`.  The parameter gradients are fixed-order sums, bitwise reproducible.  Fallback: rows wider
+    than 2048 channels in fp32 / bf16, and features that are not 2-D, go to torch.nn.functional.layer_norm."""
+
+    def __init__(self, normalized_shape, eps=1e-5, elementwise_affine=True, bias=True):
+        super().__init__()
+        self._set_shape(normalized_shape)
+        self.eps = eps
+        self.elementwise_affine = elementwise_affine
+        if elementwise_affine:
+            self.weight = Parameter(torch.ones(self.normalized_shape, dtype=torch.float32))
+            if bias:
+                self.bias = Parameter(torch.zeros(self.normalized_shape, dtype=torch.float32))
+            else:
+                self.register_parameter("bias", None)
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+
+    def __repr__(self):
+        return (self.__class__.__name__ + f"({self.normalized_shape[0]}, eps={self.eps}, "
+                f"elementwise_affine={self.elementwise_affine}, bias={self.bias is not None})")
+
+
+class MinkowskiRMSNorm(_RowNormBase):
+    r"""torch.nn.RMSNorm over the channel axis of the feature matrix of a SparseTensor or a TensorField: per row
+    `x / sqrt(mean(x^2) + eps) * weight`.  `eps=None` means torch.finfo(features.dtype).eps, as in torch.  Parameter
+    `weight` of shape (C,), named as torch.nn.RMSNorm's; dtypes, gradients and fallback (to
+    torch.nn.functional.rms_norm) as MinkowskiLayerNorm."""
+    _RMS = True
+
+    def __init__(self, normalized_shape, eps=None, elementwise_affine=True):
+        super().__init__()
+        self._set_shape(normalized_shape)
+        self.eps = eps
+        self.elementwise_affine = elementwise_affine
+        if elementwise_affine:
+            self.weight = Parameter(torch.ones(self.normalized_shape, dtype=torch.float32))
+        else:
+            self.register_parameter("weight", None)
+
+    def __repr__(self):
+        return (self.__class__.__name__ +
+                f"({self.normalized_shape[0]}, eps={self.eps}, elementwise_affine={self.elementwise_affine})")

@@ -121,7 +121,11 @@ typedef struct me_region {
  *   1.23 (330)  round 23: layer norm and RMS norm over the channel axis of strided rows, with the residual add of a
  *              pre-norm block folded into both directions; rows in the registers of lane teams, parameter gradients as
  *              fixed-order sums (me_lnorm_chunks, me_lnorm_workspace_bytes, me_lnorm_forward, me_lnorm_backward and
- *              the _f64 twins me_lnorm_forward_f64, me_lnorm_backward_f64) */
+ *              the _f64 twins me_lnorm_forward_f64, me_lnorm_backward_f64)
+ *   1.24 (340)  round 24: the two-layer MLP of a transformer block as fused MFMA kernels that never write the hidden
+ *              matrix: row-stationary forward and input gradient, hidden-stationary weight gradient with fixed-order
+ *              partial sums (me_ffn_supported, me_ffn_row_splits, me_ffn_workspace_bytes, me_ffn_forward,
+ *              me_ffn_backward) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1468,6 +1472,39 @@ int me_lnorm_backward_f64(const double *x_dev, const double *dy_dev, const doubl
                           int64_t dy_stride, int64_t dstream_stride, int64_t n, int32_t c, int32_t rms,
                           const double *gamma_dev, const double *mean_dev, const double *rstd_dev, double *dx_dev,
                           int64_t dx_stride, double *grad_gamma_dev, double *grad_beta_dev, void *stream);
+
+/* ---- fused two-layer MLP (MinkowskiFeedForward, MinkowskiFunctional.feed_forward; csrc/feed_forward.hip, ABI 1.24) ----
+ *   y = act(x w1^T + b1) w2^T + b2
+ * x [n, c], w1 [hd, c], b1 [hd] | NULL, w2 [cout, hd], b2 [cout] | NULL, y [n, cout]: contiguous, all float or all __bf16
+ * (is_bf16 != 0), torch.nn.Linear's layouts.  No coordinate map.  The hidden matrix [n, hd] is never written: every kernel
+ * recomputes the 32-wide chunk it needs.  fp32 accumulation on v_mfma_f32_32x32x2_f32 (fp32 rows, exact products) or
+ * v_mfma_f32_32x32x16_bf16 (bf16 rows: the hidden activation and its gradient are rounded once to bf16 where they become
+ * an MFMA operand); outputs are rounded once.  No atomics, fixed summation orders: bitwise reproducible.
+ * Widths (me_ffn_supported): c and cout multiples of 32 up to ME_FFN_MAX_WIDTH_BF16 / ME_FFN_MAX_WIDTH_F32, hd any multiple
+ * of 32.  A workgroup of the row kernels owns ME_FFN_ROWS rows.
+ * Backward recomputes the pre-activation from x: dx [n, c] (need_dx), dw1 [hd, c] and db1 [hd] | NULL (need_fc1), dw2
+ * [cout, hd] and db2 [cout] | NULL (need_fc2), in the dtype of the rows.  The weight gradients are summed per
+ * (32-wide hidden chunk, row split, wave) in registers, written as fp32 partial images and added in ascending order by a
+ * reduce kernel; me_ffn_row_splits(n, c, hd, cout, elem_bytes) is the number of row splits (whole blocks of ME_FFN_ROWS
+ * rows; a function of its arguments only, no device query).  The workspace also holds the transposed weights of the
+ * input-gradient kernel.  Launches: 1 forward; backward 1 transpose + (need_dx: 1 transpose + 1) + (weights: 2).
+ * Host-side errors, nothing launched: unsupported widths, an unknown activation, n < 0 or n >= 2^31, a needed output that is
+ * NULL, a workspace below me_ffn_workspace_bytes, operands not aligned to 16 bytes.  n = 0: forward does nothing, backward
+ * writes the wanted parameter gradients as zeros. */
+#define ME_FFN_MAX_WIDTH_BF16 256
+#define ME_FFN_MAX_WIDTH_F32 128
+#define ME_FFN_ROWS 128
+enum me_ffn_activation { ME_FFN_GELU = 0, ME_FFN_GELU_TANH = 1, ME_FFN_RELU = 2, ME_FFN_SILU = 3 };
+int32_t me_ffn_supported(int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes);
+int32_t me_ffn_row_splits(int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes);
+int64_t me_ffn_workspace_bytes(int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes);
+int me_ffn_forward(const void *x_dev, const void *w1_dev, const void *b1_dev, const void *w2_dev, const void *b2_dev,
+                   int32_t is_bf16, int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t activation, void *y_dev,
+                   void *stream);
+int me_ffn_backward(const void *x_dev, const void *dy_dev, const void *w1_dev, const void *b1_dev, const void *w2_dev,
+                    int32_t is_bf16, int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t activation,
+                    int32_t need_dx, int32_t need_fc1, int32_t need_fc2, void *dx_dev, void *dw1_dev, void *db1_dev,
+                    void *dw2_dev, void *db2_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
 /* ---- cross-attention to a dense context (MinkowskiCrossAttention, MinkowskiFunctional.cross_attention;
  *      csrc/attention.hip, ABI 1.20) ----

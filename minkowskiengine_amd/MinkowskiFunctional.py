@@ -8,7 +8,8 @@ operators of attention.py (csrc/attention.hip); and `local_attention`, which att
 operators of local_attention.py (csrc/local_attention.hip); and `serialized_attention`, which attends inside the patches
 of a space-filling curve on the operators of serialized_attention.py (csrc/serial_attention.hip); and `cross_attention`,
 which attends from the rows of a sparse tensor to a dense context (attention.py, csrc/attention.hip); and `layer_norm` /
-`rms_norm`, which run MinkowskiLayerNorm's operators (normalization.py, csrc/layer_norm.hip)."""
+`rms_norm`, which run MinkowskiLayerNorm's operators (normalization.py, csrc/layer_norm.hip); and `feed_forward`, the fused
+two-layer MLP of MinkowskiFeedForward (feed_forward.py, csrc/feed_forward.hip)."""
 import torch.nn.functional as F
 
 from .layers import _rewrap
@@ -210,6 +211,14 @@ def rms_norm(input, weight=None, eps=None):
     return _row_norm(input, None, weight, None, eps, True)
 
 
+def feed_forward(input, w1, b1, w2, b2, activation="gelu"):
+    """act(F w1^T + b1) w2^T + b2 over the features F of a SparseTensor or a TensorField (MinkowskiFeedForward as a
+    function).  w1 [hidden, C], w2 [C_out, hidden], b1 / b2 vectors or None; activation: gelu, gelu_tanh, relu or silu."""
+    from .feed_forward import feed_forward as _feed_forward
+    return _feed_forward(input, w1, b1, w2, b2, activation)
+
+
 __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention",
                                                 "local_attention", "serialized_attention", "cross_attention",
-                                                "window_attention", "rotary_embedding", "layer_norm", "rms_norm"]
+                                                "window_attention", "rotary_embedding", "layer_norm", "rms_norm",
+                                                "feed_forward"]

@@ -4126,6 +4126,101 @@ def LayerNormBackwardGPU(in_feat, grad_out_feat, grad_stream, weight, mean, rstd
 
 
 # ------------------------------------------------------------------------------------------------
+# fused two-layer MLP (csrc/feed_forward.hip, ABI 1.24; not in the reference): y = act(x w1^T + b1) w2^T + b2 without the
+# hidden matrix in memory.  Row-local, so the operators take no coordinate map.
+# ------------------------------------------------------------------------------------------------
+FFN_ACTIVATIONS = {"gelu": 0, "gelu_tanh": 1, "relu": 2, "silu": 3}     # enum me_ffn_activation
+FFN_MAX_WIDTH = {torch.bfloat16: 256, torch.float32: 128}               # ME_FFN_MAX_WIDTH_BF16 / _F32
+FFN_ROWS = 128                                                          # ME_FFN_ROWS: rows of a workgroup
+# the widest rows MinkowskiFeedForward sends to the kernels: above these the torch formulation was faster at both measured
+# row counts (profiles/r24_feed_forward_bench.log)
+FFN_FUSED_WIDTH = {torch.bfloat16: 128, torch.float32: 64}
+
+
+def feed_forward_supported(c, hd, cout, dtype):
+    """what the kernels can serve: fp32 / bf16, c and cout multiples of 32 up to FFN_MAX_WIDTH, hd a multiple of 32"""
+    top = FFN_MAX_WIDTH.get(dtype)
+    return (top is not None and c % 32 == 0 and 32 <= c <= top and cout % 32 == 0 and 32 <= cout <= top and
+            hd % 32 == 0 and hd >= 32)
+
+
+def feed_forward_fused(c, hd, cout, dtype):
+    """the width rule of MinkowskiFeedForward: widths the kernels serve and serve no slower than torch"""
+    return feed_forward_supported(c, hd, cout, dtype) and max(c, cout) <= FFN_FUSED_WIDTH[dtype]
+
+
+def feed_forward_row_splits(n, c, hd, cout, dtype):
+    """row splits of the weight-gradient kernel (me_ffn_row_splits)"""
+    return int(_lib.load().me_ffn_row_splits(n, c, hd, cout, torch.finfo(dtype).bits // 8))
+
+
+def _ffn_operands(in_feat, w1, b1, w2, b2, activation):
+    _check(activation in FFN_ACTIVATIONS, "activation must be one of", sorted(FFN_ACTIVATIONS), "not", repr(activation))
+    _check(in_feat.is_cuda, "in_feat must be CUDA (ROCm) — the MI355X path has no CPU implementation")
+    _check(in_feat.dim() == 2 and w1.dim() == 2 and w2.dim() == 2, "in_feat, w1 and w2 must be 2-D")
+    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
+    hd, cout = int(w1.shape[0]), int(w2.shape[0])
+    _check(w1.shape[1] == c and w2.shape[1] == hd, "channel mismatch: in_feat", tuple(in_feat.shape), "w1", tuple(w1.shape),
+           "w2", tuple(w2.shape))
+    _check(b1 is None or tuple(b1.shape) == (hd,), "b1 must have", hd, "values")
+    _check(b2 is None or tuple(b2.shape) == (cout,), "b2 must have", cout, "values")
+    for name, t in (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)):
+        _check(t is None or (t.dtype == in_feat.dtype and t.device == in_feat.device), name,
+               "must have the dtype and device of in_feat")
+    _check(feed_forward_supported(c, hd, cout, in_feat.dtype), "widths", (c, hd, cout), "of", in_feat.dtype,
+           "are not served by the feed-forward kernels")
+    ops = [t if t is None else t.detach().contiguous() for t in (in_feat, w1, b1, w2, b2)]
+    return ops, n, c, hd, cout
+
+
+def FeedForwardForwardGPU(in_feat, w1, b1, w2, b2, activation):
+    """-> out_feat [n, cout] = act(in_feat w1^T + b1) w2^T + b2 (w1 [hd, c], w2 [cout, hd], torch.nn.Linear's layouts; all
+    of one dtype, fp32 or bf16).  One launch (me_ffn_forward)."""
+    (x, w1, b1, w2, b2), n, c, hd, cout = _ffn_operands(in_feat, w1, b1, w2, b2, activation)
+    out = torch.empty((n, cout), dtype=x.dtype, device=x.device)
+    if n == 0:
+        return out
+    lib = _lib.load()
+    with _on(x.device):
+        _timed("ffn_forward", x.device, lambda: _lib.check(lib.me_ffn_forward(
+            _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), 1 if x.dtype == torch.bfloat16 else 0, n, c, hd, cout,
+            FFN_ACTIVATIONS[activation], _ptr(out), _stream(x.device))), 4.0 * n * hd * (c + cout) / 2)
+    return out
+
+
+def FeedForwardBackwardGPU(in_feat, grad_out_feat, w1, b1, w2, activation, need_grad_in=True, need_grad_fc1=True,
+                           need_grad_fc2=True):
+    """-> (grad_in, grad_w1, grad_b1, grad_w2, grad_b2), None where not wanted (grad_b1 also without b1; grad_b2 is
+    returned whenever fc2's gradients are wanted).  The pre-activation is recomputed from in_feat; the parameter gradients
+    are fixed-order sums without atomics, in the dtype of the rows (me_ffn_backward)."""
+    (x, w1, b1, w2, _), n, c, hd, cout = _ffn_operands(in_feat, w1, b1, w2, None, activation)
+    dy = grad_out_feat.detach().to(x.dtype).contiguous()
+    _check(tuple(dy.shape) == (n, cout) and dy.device == x.device, "grad_out_feat must be", (n, cout), "on the device of in_feat")
+    dev = x.device
+
+    def new(*shape, want=True):
+        return torch.empty(shape, dtype=x.dtype, device=dev) if want else None
+    dx = new(n, c, want=need_grad_in)
+    dw1, db1 = new(hd, c, want=need_grad_fc1), new(hd, want=need_grad_fc1 and b1 is not None)
+    dw2, db2 = new(cout, hd, want=need_grad_fc2), new(cout, want=need_grad_fc2)
+    if n == 0:
+        for t in (dw1, db1, dw2, db2):
+            if t is not None:
+                t.zero_()
+        return dx, dw1, db1, dw2, db2
+    if not (need_grad_in or need_grad_fc1 or need_grad_fc2):
+        return dx, dw1, db1, dw2, db2
+    lib = _lib.load()
+    with _on(dev):
+        ws = _workspace(int(lib.me_ffn_workspace_bytes(n, c, hd, cout, x.element_size())), dev)
+        _timed("ffn_backward", dev, lambda: _lib.check(lib.me_ffn_backward(
+            _ptr(x), _ptr(dy), _ptr(w1), _ptr(b1), _ptr(w2), 1 if x.dtype == torch.bfloat16 else 0, n, c, hd, cout,
+            FFN_ACTIVATIONS[activation], int(need_grad_in), int(need_grad_fc1), int(need_grad_fc2), _ptr(dx), _ptr(dw1),
+            _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ws), ws.numel(), _stream(dev))))
+    return dx, dw1, db1, dw2, db2
+
+
+# ------------------------------------------------------------------------------------------------
 # pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu)
 # ------------------------------------------------------------------------------------------------
 def PruningForwardGPU(in_feat, keep, in_key, out_key, manager):

@@ -1,0 +1,642 @@
+// Fused two-layer MLP over the rows of a feature matrix for gfx950 (MI355X): y = act(x W1^T + b1) W2^T + b2 with
+// x [n, C], W1 [Hd, C], W2 [Cout, Hd] (torch.nn.Linear's layouts).  The hidden matrix [n, Hd] never reaches memory, in
+// either direction: every kernel recomputes the 32-wide chunk of it that it needs from x.
+//
+//   k_ffn_fwd     row-stationary.  A workgroup of four waves owns 128 rows, a wave 32 of them; the wave's rows of x stay
+//                 in registers as B fragments, the accumulators of y stay in registers over the whole walk over Hd.
+//   k_ffn_bwd_x   the same body with one more first product: Z^T is recomputed, dH^T = W2^T[chunk, :] dY^T, dZ = dH act'(Z),
+//                 dX^T += W1^T[:, chunk] dZ^T.  The transposed weights come from k_ffn_transpose (one launch per backward).
+//   k_ffn_bwd_w   hidden-stationary.  A workgroup owns (32-wide hidden chunk, row split) and walks its rows 128 at a time,
+//                 a wave 32 of them; dW1[chunk, :], dW2[:, chunk] and db1[chunk] of the wave's rows stay in registers and
+//                 are written once as an fp32 partial image per (split, wave).  db2 rides in the chunk-0 workgroups.
+//   k_ffn_reduce  sums the partial images in ascending (split, wave) order and rounds once to the parameter type.
+//
+// One 32x32 MFMA shape serves both dtypes, as in attention.hip: v_mfma_f32_32x32x16_bf16 on bf16 rows, the exact
+// v_mfma_f32_32x32x2_f32 on fp32 rows; C/D lane map: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
+// The row-stationary kernels take every product transposed, so that a row of x is the COLUMN (lane & 31) of every tile:
+//   Z^T[32 hidden x 32 rows] = W1[chunk, :] X^T     A = W1's row-major rows from LDS, B = the wave's x fragments
+// and the 16 accumulator registers, after bias and activation in fp32, are the two k-steps of the B operand of
+//   Y^T[32 t .., rows] += W2[32 t .., chunk] H^T    A read from LDS in the permuted k order (ffn_load44)
+// with no lane movement and no LDS: registers 8 s .. 8 s + 7 are k-step s, element j of lane half h being hidden unit
+// 16 s + 8 (j >> 2) + 4 h + (j & 3).  The weight-gradient kernel sums over ROWS, so there the first products are taken
+// plain (Z[32 rows x 32 hidden] = X W1[chunk, :]^T, the hidden unit on the lane) and the same identity feeds
+//   dW1^T[32 t .., chunk] += X^T[32 t .., rows] dZ,   dW2[32 t .., chunk] += dY^T[32 t .., rows] H
+// whose A operands are read from a wave-private transposed LDS image of the wave's 32 rows.
+// The hidden activation (H, dZ) is rounded once to bf16 where it becomes an MFMA operand on bf16 rows and stays fp32 on fp32
+// rows; all accumulation is fp32; outputs are rounded once.  No atomics, fixed summation orders: bitwise reproducible.
+// The weight blocks of a chunk are staged into LDS in 16-byte pieces once per workgroup, double-buffered in the
+// row-stationary kernels (one barrier per chunk).  A partial last row block clamps the row index and masks the store (the
+// weight-gradient kernel zeroes the clamped rows of x and dy instead).
+// Widths: C and Cout multiples of 32 up to ME_FFN_MAX_WIDTH_BF16 / ME_FFN_MAX_WIDTH_F32, Hd any multiple of 32.  A kernel is
+// instantiated per (dtype, MT) with MT = 2 | 4 | 8 the register tiles that hold max(C, Cout) / 32; tiles beyond the actual
+// widths are skipped by wave-uniform branches.
+#include "common.hpp"
+
+#include <algorithm>
+
+namespace me {
+namespace ffn {
+
+typedef float ff_f32x16 __attribute__((ext_vector_type(16)));
+typedef float ff_f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 ff_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 ff_bf16x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kThreads = 256;            // four waves
+constexpr int kRows = ME_FFN_ROWS;       // rows of a workgroup (step), 32 per wave
+constexpr int kLdsBudget = 160 * 1024;
+constexpr int kBiasBytes = 2 * 32 * (int)sizeof(float);
+constexpr int kTargetGroups = 512;       // workgroups the weight-gradient grid aims for (two per CU)
+
+template <typename T> struct FfnT;
+template <> struct FfnT<__bf16> {
+  typedef ff_bf16x8 vec;            // a 16-byte piece
+  static constexpr int EPP = 8;     // elements of a 16-byte piece
+  static constexpr int PAD = 8;     // LDS rows: + 16 bytes
+};
+template <> struct FfnT<float> {
+  typedef ff_f32x4 vec;
+  static constexpr int EPP = 4;
+  static constexpr int PAD = 4;
+};
+
+// 8 k-values of one operand row (lane half h of a 16-wide k-step; eight 32x32x2 steps on fp32 rows)
+template <typename T> struct Frag;
+template <> struct Frag<__bf16> { ff_bf16x8 v; };
+template <> struct Frag<float> { float v[8]; };
+
+__device__ __forceinline__ void ffn_mma(ff_f32x16 &acc, const Frag<__bf16> &a, const Frag<__bf16> &b) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.v, acc, 0, 0, 0);
+}
+__device__ __forceinline__ void ffn_mma(ff_f32x16 &acc, const Frag<float> &a, const Frag<float> &b) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[j], b.v[j], acc, 0, 0, 0);
+}
+
+// 8 consecutive elements at p (16-byte aligned)
+__device__ __forceinline__ Frag<__bf16> ffn_load8(const __bf16 *p) {
+  Frag<__bf16> f;
+  f.v = *reinterpret_cast<const ff_bf16x8 *>(p);
+  return f;
+}
+__device__ __forceinline__ Frag<float> ffn_load8(const float *p) {
+  Frag<float> f;
+  const ff_f32x4 a = *reinterpret_cast<const ff_f32x4 *>(p), b = *reinterpret_cast<const ff_f32x4 *>(p + 4);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { f.v[j] = a[j]; f.v[4 + j] = b[j]; }
+  return f;
+}
+// elements 0..3 at p, 4..7 at p + 8: the k order of an accumulator used as an operand
+__device__ __forceinline__ Frag<__bf16> ffn_load44(const __bf16 *p) {
+  Frag<__bf16> f;
+  const ff_bf16x4 a = *reinterpret_cast<const ff_bf16x4 *>(p), b = *reinterpret_cast<const ff_bf16x4 *>(p + 8);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { f.v[j] = a[j]; f.v[4 + j] = b[j]; }
+  return f;
+}
+__device__ __forceinline__ Frag<float> ffn_load44(const float *p) {
+  Frag<float> f;
+  const ff_f32x4 a = *reinterpret_cast<const ff_f32x4 *>(p), b = *reinterpret_cast<const ff_f32x4 *>(p + 8);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { f.v[j] = a[j]; f.v[4 + j] = b[j]; }
+  return f;
+}
+// registers 8 s .. 8 s + 7 of a 32x32 tile as the fragment of k-step s (the one rounding of the hidden activation)
+template <typename T> __device__ __forceinline__ Frag<T> ffn_acc_frag(const float (&x)[16], int s) {
+  Frag<T> f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f.v[j] = (T)x[8 * s + j];
+  return f;
+}
+template <typename T> __device__ __forceinline__ Frag<T> ffn_zero_frag() {
+  Frag<T> f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f.v[j] = (T)0.f;
+  return f;
+}
+// row of register reg of a 32x32 C/D tile in lane half h
+__device__ __forceinline__ int ffn_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+
+__device__ __forceinline__ void ffn_zero(ff_f32x16 &a) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) a[i] = 0.f;
+}
+
+// 4 consecutive channels of one row
+__device__ __forceinline__ void ffn_store4(__bf16 *p, float a, float b, float c, float d) {
+  ff_bf16x4 v;
+  v[0] = (__bf16)a; v[1] = (__bf16)b; v[2] = (__bf16)c; v[3] = (__bf16)d;
+  *reinterpret_cast<ff_bf16x4 *>(p) = v;
+}
+__device__ __forceinline__ void ffn_store4(float *p, float a, float b, float c, float d) {
+  ff_f32x4 v;
+  v[0] = a; v[1] = b; v[2] = c; v[3] = d;
+  *reinterpret_cast<ff_f32x4 *>(p) = v;
+}
+
+// ---- activations, in fp32 --------------------------------------------------------------------------------------------
+template <int A> __device__ __forceinline__ float act_f(float v) {
+  if constexpr (A == ME_FFN_RELU) return v > 0.f ? v : 0.f;
+  else if constexpr (A == ME_FFN_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
+  else if constexpr (A == ME_FFN_GELU_TANH) {
+    const float u = 0.79788456080286536f * (v + 0.044715f * v * v * v);
+    return 0.5f * v * (1.f + tanhf(u));
+  } else return v / (1.f + expf(-v));
+}
+template <int A> __device__ __forceinline__ float act_g(float v) {
+  if constexpr (A == ME_FFN_RELU) return v > 0.f ? 1.f : 0.f;   // act'(0) = 0, as in torch
+  else if constexpr (A == ME_FFN_GELU)
+    return 0.5f * (1.f + erff(v * 0.70710678118654752f)) + v * 0.39894228040143268f * expf(-0.5f * v * v);
+  else if constexpr (A == ME_FFN_GELU_TANH) {
+    const float t = tanhf(0.79788456080286536f * (v + 0.044715f * v * v * v));
+    return 0.5f * (1.f + t) + 0.5f * v * (1.f - t * t) * 0.79788456080286536f * (1.f + 3.f * 0.044715f * v * v);
+  } else {
+    const float s = 1.f / (1.f + expf(-v));
+    return s * (1.f + v * (1.f - s));
+  }
+}
+// GRAD: hv = dh * act'(z + bias) and hact = act(z + bias); else hv = act(z + bias).  bias[i]: of register i.
+template <int A, bool GRAD>
+__device__ __forceinline__ void hidden_one(const ff_f32x16 &z, const ff_f32x16 &dh, const float (&bias)[16],
+                                           float (&hv)[16], float (&hact)[16]) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const float v = z[i] + bias[i];
+    if constexpr (GRAD) {
+      hv[i] = dh[i] * act_g<A>(v);
+      hact[i] = act_f<A>(v);
+    } else {
+      hv[i] = act_f<A>(v);
+    }
+  }
+}
+template <bool GRAD>
+__device__ __forceinline__ void hidden(int act, const ff_f32x16 &z, const ff_f32x16 &dh, const float (&bias)[16],
+                                       float (&hv)[16], float (&hact)[16]) {
+  switch (act) {   // wave-uniform
+    case ME_FFN_RELU: hidden_one<ME_FFN_RELU, GRAD>(z, dh, bias, hv, hact); break;
+    case ME_FFN_GELU: hidden_one<ME_FFN_GELU, GRAD>(z, dh, bias, hv, hact); break;
+    case ME_FFN_GELU_TANH: hidden_one<ME_FFN_GELU_TANH, GRAD>(z, dh, bias, hv, hact); break;
+    default: hidden_one<ME_FFN_SILU, GRAD>(z, dh, bias, hv, hact); break;
+  }
+}
+
+// rows x cols elements (cols a multiple of a piece) from src (row stride ld_src) into the LDS image dst (row stride ld_dst)
+template <typename T>
+__device__ __forceinline__ void stage(const T *__restrict__ src, int64_t ld_src, int rows, int cols, T *dst, int ld_dst) {
+  constexpr int EPP = FfnT<T>::EPP;
+  using vec = typename FfnT<T>::vec;
+  const int ppr = cols / EPP;
+  for (int p = threadIdx.x; p < rows * ppr; p += kThreads) {
+    const int rr = p / ppr, pc = p - rr * ppr;
+    *reinterpret_cast<vec *>(dst + rr * ld_dst + pc * EPP) =
+        *reinterpret_cast<const vec *>(src + (int64_t)rr * ld_src + pc * EPP);
+  }
+}
+
+// ---- row-stationary: forward and input gradient ----------------------------------------------------------------------
+// forward:  x, wa = W1 [hd, c], wc = W2 [cout, hd], b1, b2 -> out = y [n, cout]
+// backward: x, g = dy [n, cout], wa = W1, wb = W2^T [hd, cout], wc = W1^T [c, hd], b1 -> out = dx [n, c]
+template <typename T> struct RowsArgs {
+  const T *x, *g, *wa, *wb, *wc, *b1, *b2;
+  T *out;
+  int64_t n;
+  int c, hd, cout, act;
+};
+
+// LDS: the two bias chunks, then two buffers of [32][c + PAD] (wa), [32][cout + PAD] (wb, backward), [co][32 + PAD] (wc)
+static inline int64_t rows_lds_bytes(int elem, int c, int cout, bool bwd) {
+  const int pad = 16 / elem, co = bwd ? c : cout;
+  const int64_t buf = 32 * (c + pad) + (bwd ? 32 * (cout + pad) : 0) + (int64_t)co * (32 + pad);
+  return kBiasBytes + 2 * buf * elem;
+}
+
+template <typename T, int MT, bool BWD> __device__ __forceinline__ void ffn_rows(const RowsArgs<T> &a) {
+  constexpr int PAD = FfnT<T>::PAD;
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_ffn[];
+  float *s_bias = reinterpret_cast<float *>(s_ffn);   // [2][32]
+  T *s_buf = reinterpret_cast<T *>(s_ffn + kBiasBytes);
+  const int c = a.c, hd = a.hd, cout = a.cout, co = BWD ? c : cout;
+  const int lda = c + PAD, ldb = cout + PAD, ldc = 32 + PAD;
+  const int buf_elems = 32 * lda + (BWD ? 32 * ldb : 0) + co * ldc;
+  const int nka = c / 16, nkb = cout / 16, nto = co / 32, nchunks = hd / 32;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int64_t row = (int64_t)blockIdx.x * kRows + wave * 32 + r, rc = row < a.n ? row : a.n - 1;
+
+  Frag<T> xf[2 * MT], gf[BWD ? 2 * MT : 1];
+#pragma unroll
+  for (int k = 0; k < 2 * MT; ++k)
+    if (k < nka) xf[k] = ffn_load8(a.x + rc * c + 16 * k + 8 * h);
+  if constexpr (BWD) {
+#pragma unroll
+    for (int k = 0; k < 2 * MT; ++k)
+      if (k < nkb) gf[k] = ffn_load8(a.g + rc * cout + 16 * k + 8 * h);
+  }
+  ff_f32x16 o[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) ffn_zero(o[t]);
+
+  auto stage_chunk = [&](int j) {
+    T *sa = s_buf + (j & 1) * buf_elems, *sb = sa + 32 * lda, *sc = sb + (BWD ? 32 * ldb : 0);
+    stage<T>(a.wa + (int64_t)32 * j * c, c, 32, c, sa, lda);
+    if constexpr (BWD) stage<T>(a.wb + (int64_t)32 * j * cout, cout, 32, cout, sb, ldb);
+    stage<T>(a.wc + 32 * j, hd, co, 32, sc, ldc);
+    if (threadIdx.x < 32) s_bias[(j & 1) * 32 + threadIdx.x] = a.b1 != nullptr ? (float)a.b1[32 * j + threadIdx.x] : 0.f;
+  };
+  stage_chunk(0);
+  for (int j = 0; j < nchunks; ++j) {
+    __syncthreads();   // chunk j is staged, and every wave is done with chunk j - 1, whose buffer chunk j + 1 takes
+    if (j + 1 < nchunks) stage_chunk(j + 1);
+    const T *sa = s_buf + (j & 1) * buf_elems, *sb = sa + 32 * lda, *sc = sb + (BWD ? 32 * ldb : 0);
+    ff_f32x16 z;
+    ffn_zero(z);
+#pragma unroll
+    for (int k = 0; k < 2 * MT; ++k)
+      if (k < nka) ffn_mma(z, ffn_load8(sa + r * lda + 16 * k + 8 * h), xf[k]);   // Z^T[hidden][row]
+    float bias[16], hv[16], unused[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) bias[i] = s_bias[(j & 1) * 32 + ffn_row(i, h)];
+    if constexpr (BWD) {
+      ff_f32x16 dh;
+      ffn_zero(dh);
+#pragma unroll
+      for (int k = 0; k < 2 * MT; ++k)
+        if (k < nkb) ffn_mma(dh, ffn_load8(sb + r * ldb + 16 * k + 8 * h), gf[k]);   // dH^T[hidden][row]
+      hidden<true>(a.act, z, dh, bias, hv, unused);
+    } else {
+      hidden<false>(a.act, z, z, bias, hv, unused);
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const Frag<T> hf = ffn_acc_frag<T>(hv, s);
+#pragma unroll
+      for (int t = 0; t < MT; ++t)   // out^T[channel][row] += wc[channel][hidden] hidden^T[hidden][row]
+        if (t < nto) ffn_mma(o[t], ffn_load44(sc + (t * 32 + r) * ldc + 16 * s + 4 * h), hf);
+    }
+  }
+  if (row >= a.n) return;
+  T *base = a.out + row * co;
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    if (t >= nto) continue;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int ch = t * 32 + 8 * g + 4 * h;
+      float b[4] = {0.f, 0.f, 0.f, 0.f};
+      if (!BWD && a.b2 != nullptr) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) b[e] = (float)a.b2[ch + e];
+      }
+      ffn_store4(base + ch, o[t][4 * g] + b[0], o[t][4 * g + 1] + b[1], o[t][4 * g + 2] + b[2], o[t][4 * g + 3] + b[3]);
+    }
+  }
+}
+
+template <typename T, int MT> __global__ __launch_bounds__(kThreads) void k_ffn_fwd(const RowsArgs<T> a) {
+  ffn_rows<T, MT, false>(a);
+}
+template <typename T, int MT> __global__ __launch_bounds__(kThreads) void k_ffn_bwd_x(const RowsArgs<T> a) {
+  ffn_rows<T, MT, true>(a);
+}
+
+// ---- dst [cols, rows] = src [rows, cols]^T; both dimensions multiples of 32 ------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_ffn_transpose(const T *__restrict__ src, T *__restrict__ dst, int rows,
+                                                            int cols) {
+  __shared__ T tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) tile[ty + 8 * i][tx] = src[(int64_t)(r0 + ty + 8 * i) * cols + c0 + tx];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) dst[(int64_t)(c0 + ty + 8 * i) * rows + r0 + tx] = tile[tx][ty + 8 * i];
+}
+
+// ---- weight gradient: hidden-stationary -------------------------------------------------------------------------------
+// floats of one partial image: [dW1 hd x c | dW2 cout x hd | db1 hd | db2 cout]
+static __host__ __device__ __forceinline__ int64_t image_floats(int c, int hd, int cout) {
+  return (int64_t)hd * c + (int64_t)cout * hd + hd + cout;
+}
+
+template <typename T> struct WArgs {
+  const T *x, *dy, *w1, *w2t, *b1;   // w2t: W2^T [hd, cout]
+  float *partial;                     // [splits * 4][image_floats]
+  int64_t n;
+  int c, hd, cout, act, splits;
+};
+
+// LDS: [32][c + PAD] (W1 chunk), [32][cout + PAD] (W2^T chunk), four wave-private [max(c, cout)][32 + PAD] transposed images
+static inline int64_t w_lds_bytes(int elem, int c, int cout) {
+  const int pad = 16 / elem;
+  return ((int64_t)32 * (c + pad) + 32 * (cout + pad) + 4 * (int64_t)std::max(c, cout) * (32 + pad)) * elem;
+}
+
+// a wave's fragment of 8 channels of 32 rows into its transposed image [channel][row]
+template <typename T> __device__ __forceinline__ void scatter_t(T *s_t, int ldt, int ch0, int r, const Frag<T> &f) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s_t[(ch0 + j) * ldt + r] = f.v[j];
+}
+
+template <typename T, int MT> __global__ __launch_bounds__(kThreads) void k_ffn_bwd_w(const WArgs<T> a) {
+  constexpr int PAD = FfnT<T>::PAD;
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_ffn[];
+  const int c = a.c, hd = a.hd, cout = a.cout;
+  const int lda = c + PAD, ldb = cout + PAD, ldt = 32 + PAD;
+  const int nka = c / 16, nkb = cout / 16, ntc = c / 32, nto = cout / 32;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int j = blockIdx.x, split = blockIdx.y;
+  T *s_w1 = reinterpret_cast<T *>(s_ffn), *s_w2t = s_w1 + 32 * lda;
+  T *s_t = s_w2t + 32 * ldb + wave * (c > cout ? c : cout) * ldt;
+  stage<T>(a.w1 + (int64_t)32 * j * c, c, 32, c, s_w1, lda);
+  stage<T>(a.w2t + (int64_t)32 * j * cout, cout, 32, cout, s_w2t, ldb);
+  float bias[16];
+  {
+    const float b = a.b1 != nullptr ? (float)a.b1[32 * j + r] : 0.f;   // the hidden unit is the lane
+#pragma unroll
+    for (int i = 0; i < 16; ++i) bias[i] = b;
+  }
+  ff_f32x16 dw1[MT], dw2[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) { ffn_zero(dw1[t]); ffn_zero(dw2[t]); }
+  float db1 = 0.f, db2[MT / 2];
+#pragma unroll
+  for (int q = 0; q < MT / 2; ++q) db2[q] = 0.f;
+
+  const int64_t blocks = (a.n + kRows - 1) / kRows, per = (blocks + a.splits - 1) / a.splits;
+  const int64_t blk_end = (split + 1) * per < blocks ? (split + 1) * per : blocks;
+  __syncthreads();
+  for (int64_t blk = split * per; blk < blk_end; ++blk) {   // workgroup-uniform
+    const int64_t row = blk * kRows + wave * 32 + r, rc = row < a.n ? row : a.n - 1;
+    const bool valid = row < a.n;
+    ff_f32x16 z, dh;
+    ffn_zero(z);
+    ffn_zero(dh);
+#pragma unroll
+    for (int k = 0; k < 2 * MT; ++k) {
+      if (k >= nka) continue;
+      const Frag<T> xa = valid ? ffn_load8(a.x + rc * c + 16 * k + 8 * h) : ffn_zero_frag<T>();
+      ffn_mma(z, xa, ffn_load8(s_w1 + r * lda + 16 * k + 8 * h));   // Z[row][hidden]
+      scatter_t<T>(s_t, ldt, 16 * k + 8 * h, r, xa);
+    }
+#pragma unroll
+    for (int k = 0; k < 2 * MT; ++k) {
+      if (k >= nkb) continue;
+      const Frag<T> ga = valid ? ffn_load8(a.dy + rc * cout + 16 * k + 8 * h) : ffn_zero_frag<T>();
+      ffn_mma(dh, ga, ffn_load8(s_w2t + r * ldb + 16 * k + 8 * h));   // dH[row][hidden]
+    }
+    float dz[16], hact[16];
+    hidden<true>(a.act, z, dh, bias, dz, hact);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) db1 += dz[i];   // a clamped row has dh = 0
+    __syncthreads();   // X^T is in the wave's image
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const Frag<T> f = ffn_acc_frag<T>(dz, s);
+#pragma unroll
+      for (int t = 0; t < MT; ++t)   // dW1^T[channel][hidden] += X^T[channel][row] dZ[row][hidden]
+        if (t < ntc) ffn_mma(dw1[t], ffn_load44(s_t + (t * 32 + r) * ldt + 16 * s + 4 * h), f);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2 * MT; ++k) {
+      if (k >= nkb) continue;
+      const Frag<T> ga = valid ? ffn_load8(a.dy + rc * cout + 16 * k + 8 * h) : ffn_zero_frag<T>();
+      scatter_t<T>(s_t, ldt, 16 * k + 8 * h, r, ga);
+    }
+    __syncthreads();   // dY^T is in the wave's image
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const Frag<T> f = ffn_acc_frag<T>(hact, s);
+#pragma unroll
+      for (int t = 0; t < MT; ++t)   // dW2[channel][hidden] += dY^T[channel][row] H[row][hidden]
+        if (t < nto) ffn_mma(dw2[t], ffn_load44(s_t + (t * 32 + r) * ldt + 16 * s + 4 * h), f);
+    }
+    if (j == 0) {   // db2: a lane sums the 32 rows of its channels in ascending order
+#pragma unroll
+      for (int q = 0; q < MT / 2; ++q) {
+        const int ch = lane + 64 * q;
+        if (ch < cout)
+          for (int k = 0; k < 32; ++k) db2[q] += (float)s_t[ch * ldt + k];
+      }
+    }
+    __syncthreads();   // the image is free for the next step
+  }
+
+  float *img = a.partial + ((int64_t)split * 4 + wave) * image_floats(c, hd, cout);
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    if (t >= ntc) continue;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      ffn_store4(img + (int64_t)(32 * j + r) * c + 32 * t + 8 * g + 4 * h, dw1[t][4 * g], dw1[t][4 * g + 1],
+                 dw1[t][4 * g + 2], dw1[t][4 * g + 3]);
+  }
+  img += (int64_t)hd * c;
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    if (t >= nto) continue;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) img[(int64_t)(32 * t + ffn_row(i, h)) * hd + 32 * j + r] = dw2[t][i];
+  }
+  img += (int64_t)cout * hd;
+  const float other = __shfl_xor(db1, 32, 64);
+  if (h == 0) img[32 * j + r] = db1 + other;
+  if (j == 0) {
+    img += hd;
+#pragma unroll
+    for (int q = 0; q < MT / 2; ++q)
+      if (lane + 64 * q < cout) img[lane + 64 * q] = db2[q];
+  }
+}
+
+// element e of the image: the sum of the `slots` partial images in ascending order, rounded once to T.  A null destination
+// is not written.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_ffn_reduce(const float *__restrict__ partial, int slots, int c, int hd,
+                                                         int cout, T *__restrict__ dw1, T *__restrict__ db1,
+                                                         T *__restrict__ dw2, T *__restrict__ db2) {
+  const int64_t total = image_floats(c, hd, cout), e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (e >= total) return;
+  const int64_t n1 = (int64_t)hd * c, n2 = n1 + (int64_t)cout * hd, n3 = n2 + hd;
+  T *dst = e < n1 ? (dw1 ? dw1 + e : nullptr)
+                  : e < n2 ? (dw2 ? dw2 + (e - n1) : nullptr)
+                           : e < n3 ? (db1 ? db1 + (e - n2) : nullptr) : (db2 ? db2 + (e - n3) : nullptr);
+  if (dst == nullptr) return;
+  float s = 0.f;
+  for (int q = 0; q < slots; ++q) s += partial[q * total + e];
+  *dst = (T)s;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------
+template <typename K> inline int allow_lds(K fn, int64_t lds) {
+  if (lds > 48 * 1024)
+    ME_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
+  return 0;
+}
+
+template <typename T, int MT, bool BWD> int launch_rows(const RowsArgs<T> &a, hipStream_t stream) {
+  const int64_t lds = rows_lds_bytes((int)sizeof(T), a.c, a.cout, BWD);
+  ME_CHECK(lds <= kLdsBudget, "the weight chunks do not fit into LDS");
+  auto fn = BWD ? &k_ffn_bwd_x<T, MT> : &k_ffn_fwd<T, MT>;
+  if (allow_lds(fn, lds) != 0) return 1;
+  hipLaunchKernelGGL(fn, dim3((unsigned)ceil_div(a.n, kRows)), dim3(kThreads), (size_t)lds, stream, a);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T, int MT> int launch_w(const WArgs<T> &a, hipStream_t stream) {
+  const int64_t lds = w_lds_bytes((int)sizeof(T), a.c, a.cout);
+  ME_CHECK(lds <= kLdsBudget, "the weight chunks and row images do not fit into LDS");
+  auto fn = &k_ffn_bwd_w<T, MT>;
+  if (allow_lds(fn, lds) != 0) return 1;
+  hipLaunchKernelGGL(fn, dim3((unsigned)(a.hd / 32), (unsigned)a.splits), dim3(kThreads), (size_t)lds, stream, a);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+// MT = 2 | 4 | 8 register tiles for max(c, cout) / 32 (fp32 rows: at most 4)
+#define ME_FFN_DISPATCH(T, width, ...)                                      \
+  do {                                                                      \
+    if ((width) <= 64) { constexpr int MT = 2; return __VA_ARGS__; }        \
+    if ((width) <= 128) { constexpr int MT = 4; return __VA_ARGS__; }       \
+    if constexpr (sizeof(T) == 2) { constexpr int MT = 8; return __VA_ARGS__; } \
+    ME_FAIL("width not served");                                            \
+  } while (0)
+
+template <typename T> int rows_any(const RowsArgs<T> &a, bool bwd, hipStream_t stream) {
+  const int width = std::max(a.c, a.cout);
+  if (bwd) ME_FFN_DISPATCH(T, width, launch_rows<T, MT, true>(a, stream));
+  ME_FFN_DISPATCH(T, width, launch_rows<T, MT, false>(a, stream));
+}
+template <typename T> int w_any(const WArgs<T> &a, hipStream_t stream) {
+  ME_FFN_DISPATCH(T, std::max(a.c, a.cout), launch_w<T, MT>(a, stream));
+}
+
+template <typename T> int transpose(const T *src, T *dst, int rows, int cols, hipStream_t stream) {
+  hipLaunchKernelGGL(k_ffn_transpose<T>, dim3((unsigned)(cols / 32), (unsigned)(rows / 32)), dim3(kThreads), 0, stream,
+                     src, dst, rows, cols);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+inline int64_t transposed_bytes(int c, int hd, int cout, int elem) {
+  return align_up(((int64_t)c * hd + (int64_t)hd * cout) * elem, 256);
+}
+
+struct BackwardCall {
+  const void *x, *dy, *w1, *b1, *w2;
+  void *dx, *dw1, *db1, *dw2, *db2, *ws;
+  int64_t n;
+  int c, hd, cout, act;
+  bool need_dx, need_w;
+};
+
+template <typename T> int backward(const BackwardCall &b, hipStream_t stream) {
+  T *w1t = (T *)b.ws, *w2t = w1t + (int64_t)b.c * b.hd;   // W1^T [c, hd], W2^T [hd, cout]
+  float *partial = (float *)((char *)b.ws + transposed_bytes(b.c, b.hd, b.cout, (int)sizeof(T)));
+  if (transpose<T>((const T *)b.w2, w2t, b.cout, b.hd, stream) != 0) return 1;
+  if (b.need_dx) {
+    if (transpose<T>((const T *)b.w1, w1t, b.hd, b.c, stream) != 0) return 1;
+    const RowsArgs<T> a{(const T *)b.x, (const T *)b.dy, (const T *)b.w1, w2t, w1t, (const T *)b.b1, nullptr,
+                        (T *)b.dx, b.n, b.c, b.hd, b.cout, b.act};
+    if (rows_any<T>(a, true, stream) != 0) return 1;
+  }
+  if (!b.need_w) return 0;
+  const int splits = me_ffn_row_splits(b.n, b.c, b.hd, b.cout, (int)sizeof(T));
+  const WArgs<T> a{(const T *)b.x, (const T *)b.dy, (const T *)b.w1, w2t, (const T *)b.b1, partial, b.n, b.c, b.hd,
+                   b.cout, b.act, splits};
+  if (w_any<T>(a, stream) != 0) return 1;
+  hipLaunchKernelGGL(k_ffn_reduce<T>, dim3((unsigned)ceil_div(image_floats(b.c, b.hd, b.cout), kThreads)), dim3(kThreads),
+                     0, stream, partial, 4 * splits, b.c, b.hd, b.cout, (T *)b.dw1, (T *)b.db1, (T *)b.dw2, (T *)b.db2);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+inline bool aligned16(std::initializer_list<const void *> ps) {
+  for (const void *p : ps)
+    if (((uintptr_t)p & 15) != 0) return false;
+  return true;
+}
+
+}  // namespace ffn
+}  // namespace me
+
+using namespace me;
+using namespace me::ffn;
+
+#define ME_FFN_CHECK_SHAPE(n, c, hd, cout, elem, act)                                                                \
+  ME_CHECK(n >= 0 && n < (1ll << 31), "the row count must fit in int32");                                            \
+  ME_CHECK(me_ffn_supported(c, hd, cout, elem) != 0,                                                                 \
+           "widths not served: c and cout multiples of 32 up to ME_FFN_MAX_WIDTH_*, hd a multiple of 32");           \
+  ME_CHECK(act >= ME_FFN_GELU && act <= ME_FFN_SILU, "unknown activation")
+
+extern "C" {
+
+int32_t me_ffn_supported(int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes) {
+  if (elem_bytes != 2 && elem_bytes != 4) return 0;
+  const int max_w = elem_bytes == 2 ? ME_FFN_MAX_WIDTH_BF16 : ME_FFN_MAX_WIDTH_F32;
+  return (c >= 32 && c % 32 == 0 && c <= max_w && cout >= 32 && cout % 32 == 0 && cout <= max_w && hd >= 32 &&
+          hd % 32 == 0) ? 1 : 0;
+}
+
+int32_t me_ffn_row_splits(int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes) {
+  if (n < 1 || me_ffn_supported(c, hd, cout, elem_bytes) == 0) return 1;
+  const int64_t blocks = ceil_div(n, kRows);
+  const int64_t fill = ceil_div(kTargetGroups, hd / 32);
+  // four partial images per split; together no larger than x and dy
+  const int64_t cap = n * (c + cout) * elem_bytes / (16 * image_floats(c, hd, cout));
+  const int64_t want = std::min(blocks, std::max<int64_t>(4, std::min(fill, cap)));
+  return (int32_t)ceil_div(blocks, ceil_div(blocks, want));   // no empty split
+}
+
+int64_t me_ffn_workspace_bytes(int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes) {
+  if (me_ffn_supported(c, hd, cout, elem_bytes) == 0) return 0;
+  return transposed_bytes(c, hd, cout, elem_bytes) +
+         4 * (int64_t)me_ffn_row_splits(n, c, hd, cout, elem_bytes) * image_floats(c, hd, cout) * (int64_t)sizeof(float);
+}
+
+int me_ffn_forward(const void *x_dev, const void *w1_dev, const void *b1_dev, const void *w2_dev, const void *b2_dev,
+                   int32_t is_bf16, int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t activation, void *y_dev,
+                   void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ME_FFN_CHECK_SHAPE(n, c, hd, cout, is_bf16 ? 2 : 4, activation);
+  if (n == 0) return 0;
+  ME_CHECK(x_dev != nullptr && w1_dev != nullptr && w2_dev != nullptr && y_dev != nullptr, "x, w1, w2 and y must be given");
+  ME_CHECK(aligned16({x_dev, w1_dev, w2_dev, y_dev}), "x, w1, w2 and y must be aligned to 16 bytes");
+  if (is_bf16) {
+    const RowsArgs<__bf16> a{(const __bf16 *)x_dev, nullptr, (const __bf16 *)w1_dev, nullptr, (const __bf16 *)w2_dev,
+                             (const __bf16 *)b1_dev, (const __bf16 *)b2_dev, (__bf16 *)y_dev, n, c, hd, cout, activation};
+    return rows_any<__bf16>(a, false, stream);
+  }
+  const RowsArgs<float> a{(const float *)x_dev, nullptr, (const float *)w1_dev, nullptr, (const float *)w2_dev,
+                          (const float *)b1_dev, (const float *)b2_dev, (float *)y_dev, n, c, hd, cout, activation};
+  return rows_any<float>(a, false, stream);
+}
+
+int me_ffn_backward(const void *x_dev, const void *dy_dev, const void *w1_dev, const void *b1_dev, const void *w2_dev,
+                    int32_t is_bf16, int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t activation,
+                    int32_t need_dx, int32_t need_fc1, int32_t need_fc2, void *dx_dev, void *dw1_dev, void *db1_dev,
+                    void *dw2_dev, void *db2_dev, void *workspace_dev, int64_t workspace_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const int elem = is_bf16 ? 2 : 4;
+  ME_FFN_CHECK_SHAPE(n, c, hd, cout, elem, activation);
+  ME_CHECK(!need_dx || dx_dev != nullptr, "need_dx without dx");
+  ME_CHECK(!need_fc1 || dw1_dev != nullptr, "need_fc1 without dw1");
+  ME_CHECK(!need_fc2 || dw2_dev != nullptr, "need_fc2 without dw2");
+  const bool need_w = need_fc1 != 0 || need_fc2 != 0;
+  if (!need_dx && !need_w) return 0;
+  // n = 0: the reduce over the images of one empty split writes the zeros
+  ME_CHECK(workspace_dev != nullptr && workspace_bytes >= me_ffn_workspace_bytes(n, c, hd, cout, elem),
+           "the workspace must hold me_ffn_workspace_bytes");
+  ME_CHECK(w1_dev != nullptr && w2_dev != nullptr && (n == 0 || (x_dev != nullptr && dy_dev != nullptr)),
+           "x, dy, w1 and w2 must be given");
+  ME_CHECK(aligned16({x_dev, dy_dev, w1_dev, w2_dev, dx_dev, workspace_dev}), "the operands must be aligned to 16 bytes");
+  const BackwardCall b{x_dev, dy_dev, w1_dev, b1_dev, w2_dev, dx_dev,
+                       need_fc1 ? dw1_dev : nullptr, need_fc1 ? db1_dev : nullptr, need_fc2 ? dw2_dev : nullptr,
+                       need_fc2 ? db2_dev : nullptr, workspace_dev, n, c, hd, cout, activation, need_dx != 0 && n > 0,
+                       need_w};
+  return is_bf16 ? backward<__bf16>(b, stream) : backward<float>(b, stream);
+}
+
+}  // extern "C"

@@ -1760,6 +1760,79 @@ std::vector<Tensor> layer_norm_backward(const Tensor &in_feat, const Tensor &gra
   return g;
 }
 
+// ---- fused two-layer MLP (csrc/feed_forward.hip, ABI 1.24; twin of backend.FeedForward{Forward,Backward}GPU): row-local,
+// no coordinate map -----------------------------------------------------------------------------------------------------
+static int ffn_activation(const std::string &activation) {
+  static const char *names[] = {"gelu", "gelu_tanh", "relu", "silu"};   // enum me_ffn_activation
+  for (int i = 0; i < 4; i++)
+    if (activation == names[i]) return i;
+  check(false, "activation must be one of gelu, gelu_tanh, relu, silu, not '" + activation + "'");
+  return -1;
+}
+
+static void ffn_check(const Tensor &x, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2) {
+  check(x.is_cuda(), "in_feat must be CUDA (ROCm) — the MI355X path has no CPU implementation");
+  check(x.dim() == 2 && w1.dim() == 2 && w2.dim() == 2, "in_feat, w1 and w2 must be 2-D");
+  check(w1.size(1) == x.size(1) && w2.size(1) == w1.size(0), "channel mismatch between in_feat, w1 and w2");
+  check(!b1.defined() || (b1.dim() == 1 && b1.size(0) == w1.size(0)), "b1 must have one value per hidden unit");
+  check(!b2.defined() || (b2.dim() == 1 && b2.size(0) == w2.size(0)), "b2 must have one value per output channel");
+  for (const Tensor *t : {&w1, &b1, &w2, &b2})
+    check(!t->defined() || (t->scalar_type() == x.scalar_type() && t->device() == x.device()),
+          "w1, b1, w2 and b2 must have the dtype and device of in_feat");
+  const bool served = x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16;
+  check(served && me_ffn_supported((int32_t)x.size(1), (int32_t)w1.size(0), (int32_t)w2.size(0),
+                                   (int32_t)x.element_size()) != 0,
+        "widths are not served by the feed-forward kernels");
+}
+
+static Tensor ffn_plain(const Tensor &t) { return t.defined() ? t.detach().contiguous() : t; }
+
+Tensor feed_forward_forward(const Tensor &in_feat, const Tensor &w1_, const Tensor &b1_, const Tensor &w2_,
+                            const Tensor &b2_, const std::string &activation) {
+  const int act = ffn_activation(activation);
+  ffn_check(in_feat, w1_, b1_, w2_, b2_);
+  const Tensor x = ffn_plain(in_feat), w1 = ffn_plain(w1_), b1 = ffn_plain(b1_), w2 = ffn_plain(w2_), b2 = ffn_plain(b2_);
+  const int64_t n = x.size(0);
+  const int c = (int)x.size(1), hd = (int)w1.size(0), cout = (int)w2.size(0);
+  Tensor out = at::empty({n, cout}, x.options());
+  if (n == 0) return out;
+  c10::DeviceGuard guard(x.device());
+  me_ok(me_ffn_forward(vptr(x), vptr(w1), vptr(b1), vptr(w2), vptr(b2), x.scalar_type() == at::kBFloat16 ? 1 : 0, n, c,
+                       hd, cout, act, vptr(out), stream_of(x.device())));
+  return out;
+}
+
+std::vector<Tensor> feed_forward_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &w1_,
+                                          const Tensor &b1_, const Tensor &w2_, const std::string &activation,
+                                          bool need_grad_in, bool need_grad_fc1, bool need_grad_fc2) {
+  const int act = ffn_activation(activation);
+  ffn_check(in_feat, w1_, b1_, w2_, Tensor());
+  const Tensor x = ffn_plain(in_feat), w1 = ffn_plain(w1_), b1 = ffn_plain(b1_), w2 = ffn_plain(w2_);
+  const int64_t n = x.size(0);
+  const int c = (int)x.size(1), hd = (int)w1.size(0), cout = (int)w2.size(0);
+  const Tensor dy = grad_out.detach().to(x.scalar_type()).contiguous();
+  check(dy.dim() == 2 && dy.size(0) == n && dy.size(1) == cout && dy.device() == x.device(),
+        "grad_out_feat must be [n, cout] on the device of in_feat");
+  std::vector<Tensor> g(5);   // grad_in, grad_w1, grad_b1, grad_w2, grad_b2
+  if (need_grad_in) g[0] = at::empty({n, c}, x.options());
+  if (need_grad_fc1) g[1] = at::empty({hd, c}, x.options());
+  if (need_grad_fc1 && b1.defined()) g[2] = at::empty({hd}, x.options());
+  if (need_grad_fc2) g[3] = at::empty({cout, hd}, x.options());
+  if (need_grad_fc2) g[4] = at::empty({cout}, x.options());
+  if (n == 0) {
+    for (size_t i = 1; i < 5; i++)
+      if (g[i].defined()) g[i].zero_();
+    return g;
+  }
+  if (!need_grad_in && !need_grad_fc1 && !need_grad_fc2) return g;
+  c10::DeviceGuard guard(x.device());
+  Tensor ws = workspace(me_ffn_workspace_bytes(n, c, hd, cout, (int32_t)x.element_size()), x.device());
+  me_ok(me_ffn_backward(vptr(x), vptr(dy), vptr(w1), vptr(b1), vptr(w2), x.scalar_type() == at::kBFloat16 ? 1 : 0, n, c, hd,
+                        cout, act, need_grad_in ? 1 : 0, need_grad_fc1 ? 1 : 0, need_grad_fc2 ? 1 : 0, vptr(g[0]),
+                        vptr(g[1]), vptr(g[2]), vptr(g[3]), vptr(g[4]), vptr(ws), ws.numel(), stream_of(x.device())));
+  return g;
+}
+
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------
 Tensor pruning_forward(const Tensor &in_feat, const Tensor &keep, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr) {

@@ -125,7 +125,10 @@ typedef struct me_region {
  *   1.24 (340)  round 24: the two-layer MLP of a transformer block as fused MFMA kernels that never write the hidden
  *              matrix: row-stationary forward and input gradient, hidden-stationary weight gradient with fixed-order
  *              partial sums (me_ffn_supported, me_ffn_row_splits, me_ffn_workspace_bytes, me_ffn_forward,
- *              me_ffn_backward) */
+ *              me_ffn_backward)
+ *   1.25 (350)  round 25: the gated MLP (SwiGLU / GeGLU / ReGLU) on the same design: two first products off one set of
+ *              row fragments, the gate applied in registers, two second products into one accumulator set in the input
+ *              gradient (me_glu_supported, me_glu_row_splits, me_glu_workspace_bytes, me_glu_forward, me_glu_backward) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1505,6 +1508,40 @@ int me_ffn_backward(const void *x_dev, const void *dy_dev, const void *w1_dev, c
                     int32_t is_bf16, int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t activation,
                     int32_t need_dx, int32_t need_fc1, int32_t need_fc2, void *dx_dev, void *dw1_dev, void *db1_dev,
                     void *dw2_dev, void *db2_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
+/* ---- fused gated MLP: SwiGLU / GeGLU / ReGLU (MinkowskiGatedFeedForward, MinkowskiFunctional.gated_feed_forward;
+ *      csrc/gated_feed_forward.hip, ABI 1.25) ----
+ *   y = (act(x wg^T + bg) * (x wu^T + bu)) w2^T + b2
+ * x [n, c], wg and wu [hd, c], bg and bu [hd] | NULL, w2 [cout, hd], b2 [cout] | NULL, y [n, cout]: contiguous, all float or
+ * all __bf16 (is_bf16 != 0), torch.nn.Linear's layouts; activation: enum me_ffn_activation (silu: SwiGLU, gelu: GeGLU,
+ * relu: ReGLU).  The kernels of me_ffn_* with a second first product off the same registers of x: none of the three
+ * [n, hd] matrices of the unfused form (gate, up, product) is written, forward or backward.  bf16 rows round the hidden
+ * product and the two pre-activation gradients once where they become an MFMA operand; fp32 accumulation; outputs are
+ * rounded once.  No atomics, fixed summation orders: bitwise reproducible.
+ * Widths (me_glu_supported): c and cout multiples of 32 up to ME_GLU_MAX_WIDTH_BF16 / ME_GLU_MAX_WIDTH_F32, hd any multiple
+ * of 32.  A workgroup of the row kernels owns ME_FFN_ROWS rows.
+ * Backward recomputes both pre-activations from x: dx [n, c] (need_dx), dwg and dwu [hd, c] with dbg and dbu [hd] | NULL
+ * (need_fc1: both first-layer matrices and their biases), dw2 [cout, hd] and db2 [cout] | NULL (need_fc2).  The parameter
+ * gradients are fp32 partial images [dwg | dwu | dw2 | dbg | dbu | db2] per (row split, wave), added in ascending order by a
+ * reduce kernel; me_glu_row_splits is the number of row splits (whole blocks of ME_FFN_ROWS rows; a function of its
+ * arguments only).  The workspace also holds the three transposed weights.  Launches: 1 forward; backward 1 transpose +
+ * (need_dx: 2 transposes + 1) + (weights: 2).
+ * Host-side errors, nothing launched: unsupported widths, an unknown activation, n < 0 or n >= 2^31, a needed output that is
+ * NULL, a workspace below me_glu_workspace_bytes, operands not aligned to 16 bytes.  n = 0: forward does nothing, backward
+ * writes the wanted parameter gradients as zeros. */
+#define ME_GLU_MAX_WIDTH_BF16 128
+#define ME_GLU_MAX_WIDTH_F32 64
+int32_t me_glu_supported(int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes);
+int32_t me_glu_row_splits(int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes);
+int64_t me_glu_workspace_bytes(int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes);
+int me_glu_forward(const void *x_dev, const void *wg_dev, const void *bg_dev, const void *wu_dev, const void *bu_dev,
+                   const void *w2_dev, const void *b2_dev, int32_t is_bf16, int64_t n, int32_t c, int32_t hd,
+                   int32_t cout, int32_t activation, void *y_dev, void *stream);
+int me_glu_backward(const void *x_dev, const void *dy_dev, const void *wg_dev, const void *bg_dev, const void *wu_dev,
+                    const void *bu_dev, const void *w2_dev, int32_t is_bf16, int64_t n, int32_t c, int32_t hd,
+                    int32_t cout, int32_t activation, int32_t need_dx, int32_t need_fc1, int32_t need_fc2, void *dx_dev,
+                    void *dwg_dev, void *dbg_dev, void *dwu_dev, void *dbu_dev, void *dw2_dev, void *db2_dev,
+                    void *workspace_dev, int64_t workspace_bytes, void *stream);
 
 /* ---- cross-attention to a dense context (MinkowskiCrossAttention, MinkowskiFunctional.cross_attention;
  *      csrc/attention.hip, ABI 1.20) ----

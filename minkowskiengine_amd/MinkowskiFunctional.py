@@ -9,7 +9,8 @@ operators of local_attention.py (csrc/local_attention.hip); and `serialized_atte
 of a space-filling curve on the operators of serialized_attention.py (csrc/serial_attention.hip); and `cross_attention`,
 which attends from the rows of a sparse tensor to a dense context (attention.py, csrc/attention.hip); and `layer_norm` /
 `rms_norm`, which run MinkowskiLayerNorm's operators (normalization.py, csrc/layer_norm.hip); and `feed_forward`, the fused
-two-layer MLP of MinkowskiFeedForward (feed_forward.py, csrc/feed_forward.hip)."""
+two-layer MLP of MinkowskiFeedForward (feed_forward.py, csrc/feed_forward.hip), and `gated_feed_forward`, its gated form
+(gated_feed_forward.py, csrc/gated_feed_forward.hip)."""
 import torch.nn.functional as F
 
 from .layers import _rewrap
@@ -218,7 +219,15 @@ def feed_forward(input, w1, b1, w2, b2, activation="gelu"):
     return _feed_forward(input, w1, b1, w2, b2, activation)
 
 
+def gated_feed_forward(input, wg, bg, wu, bu, w2, b2, activation="silu"):
+    """(act(F wg^T + bg) * (F wu^T + bu)) w2^T + b2 over the features F of a SparseTensor or a TensorField
+    (MinkowskiGatedFeedForward as a function).  wg, wu [hidden, C], w2 [C_out, hidden], bg / bu / b2 vectors or None;
+    activation: silu (SwiGLU), gelu or gelu_tanh (GeGLU), relu (ReGLU)."""
+    from .gated_feed_forward import gated_feed_forward as _gated_feed_forward
+    return _gated_feed_forward(input, wg, bg, wu, bu, w2, b2, activation)
+
+
 __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention",
                                                 "local_attention", "serialized_attention", "cross_attention",
                                                 "window_attention", "rotary_embedding", "layer_norm", "rms_norm",
-                                                "feed_forward"]
+                                                "feed_forward", "gated_feed_forward"]

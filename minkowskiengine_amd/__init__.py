@@ -30,6 +30,7 @@ from .serialized_attention import (  # noqa: F401
     MinkowskiSerializedAttentionFunction, MinkowskiSerializedSelfAttention)
 from .window_attention import MinkowskiWindowAttentionFunction, MinkowskiWindowSelfAttention  # noqa: F401
 from .feed_forward import MinkowskiFeedForward, MinkowskiFeedForwardFunction  # noqa: F401
+from .gated_feed_forward import MinkowskiGatedFeedForward, MinkowskiGatedFeedForwardFunction  # noqa: F401
 from .rotary import MinkowskiRotaryEmbedding, MinkowskiRotaryEmbeddingFunction  # noqa: F401
 from .local_attention import MinkowskiLocalAttentionFunction, MinkowskiLocalSelfAttention  # noqa: F401
 from .pruning import MinkowskiPruning, MinkowskiPruningFunction  # noqa: F401

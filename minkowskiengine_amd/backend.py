@@ -4221,6 +4221,102 @@ def FeedForwardBackwardGPU(in_feat, grad_out_feat, w1, b1, w2, activation, need_
 
 
 # ------------------------------------------------------------------------------------------------
+# fused gated MLP, SwiGLU / GeGLU / ReGLU (csrc/gated_feed_forward.hip, ABI 1.25; not in the reference):
+# y = (act(x wg^T + bg) * (x wu^T + bu)) w2^T + b2 without any of the three hidden matrices in memory.
+# ------------------------------------------------------------------------------------------------
+GLU_MAX_WIDTH = {torch.bfloat16: 128, torch.float32: 64}                # ME_GLU_MAX_WIDTH_BF16 / _F32
+# the widest rows MinkowskiGatedFeedForward sends to the kernels: the plain module's rule, not yet measured for the gated
+# kernels
+GLU_FUSED_WIDTH = {torch.bfloat16: 128, torch.float32: 64}
+
+
+def gated_feed_forward_supported(c, hd, cout, dtype):
+    """what the kernels can serve: fp32 / bf16, c and cout multiples of 32 up to GLU_MAX_WIDTH, hd a multiple of 32"""
+    top = GLU_MAX_WIDTH.get(dtype)
+    return (top is not None and c % 32 == 0 and 32 <= c <= top and cout % 32 == 0 and 32 <= cout <= top and
+            hd % 32 == 0 and hd >= 32)
+
+
+def gated_feed_forward_fused(c, hd, cout, dtype):
+    """the width rule of MinkowskiGatedFeedForward"""
+    return gated_feed_forward_supported(c, hd, cout, dtype) and max(c, cout) <= GLU_FUSED_WIDTH[dtype]
+
+
+def gated_feed_forward_row_splits(n, c, hd, cout, dtype):
+    """row splits of the weight-gradient kernel (me_glu_row_splits)"""
+    return int(_lib.load().me_glu_row_splits(n, c, hd, cout, torch.finfo(dtype).bits // 8))
+
+
+def _glu_operands(in_feat, wg, bg, wu, bu, w2, b2, activation):
+    _check(activation in FFN_ACTIVATIONS, "activation must be one of", sorted(FFN_ACTIVATIONS), "not", repr(activation))
+    _check(in_feat.is_cuda, "in_feat must be CUDA (ROCm) — the MI355X path has no CPU implementation")
+    _check(in_feat.dim() == 2 and wg.dim() == 2 and wu.dim() == 2 and w2.dim() == 2, "in_feat, wg, wu and w2 must be 2-D")
+    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
+    hd, cout = int(wg.shape[0]), int(w2.shape[0])
+    _check(wg.shape[1] == c and tuple(wu.shape) == tuple(wg.shape) and w2.shape[1] == hd, "channel mismatch: in_feat",
+           tuple(in_feat.shape), "wg", tuple(wg.shape), "wu", tuple(wu.shape), "w2", tuple(w2.shape))
+    _check(all(b is None or tuple(b.shape) == (hd,) for b in (bg, bu)), "bg and bu must have", hd, "values")
+    _check(b2 is None or tuple(b2.shape) == (cout,), "b2 must have", cout, "values")
+    for name, t in (("wg", wg), ("bg", bg), ("wu", wu), ("bu", bu), ("w2", w2), ("b2", b2)):
+        _check(t is None or (t.dtype == in_feat.dtype and t.device == in_feat.device), name,
+               "must have the dtype and device of in_feat")
+    _check(gated_feed_forward_supported(c, hd, cout, in_feat.dtype), "widths", (c, hd, cout), "of", in_feat.dtype,
+           "are not served by the gated feed-forward kernels")
+    ops = [t if t is None else t.detach().contiguous() for t in (in_feat, wg, bg, wu, bu, w2, b2)]
+    return ops, n, c, hd, cout
+
+
+def GatedFeedForwardForwardGPU(in_feat, wg, bg, wu, bu, w2, b2, activation):
+    """-> out_feat [n, cout] = (act(in_feat wg^T + bg) * (in_feat wu^T + bu)) w2^T + b2 (wg, wu [hd, c], w2 [cout, hd],
+    torch.nn.Linear's layouts; all of one dtype, fp32 or bf16).  One launch (me_glu_forward)."""
+    (x, wg, bg, wu, bu, w2, b2), n, c, hd, cout = _glu_operands(in_feat, wg, bg, wu, bu, w2, b2, activation)
+    out = torch.empty((n, cout), dtype=x.dtype, device=x.device)
+    if n == 0:
+        return out
+    lib = _lib.load()
+    with _on(x.device):
+        _timed("glu_forward", x.device, lambda: _lib.check(lib.me_glu_forward(
+            _ptr(x), _ptr(wg), _ptr(bg), _ptr(wu), _ptr(bu), _ptr(w2), _ptr(b2), 1 if x.dtype == torch.bfloat16 else 0, n,
+            c, hd, cout, FFN_ACTIVATIONS[activation], _ptr(out), _stream(x.device))), 4.0 * n * hd * (2 * c + cout) / 2)
+    return out
+
+
+def GatedFeedForwardBackwardGPU(in_feat, grad_out_feat, wg, bg, wu, bu, w2, activation, need_grad_in=True,
+                                need_grad_fc1=True, need_grad_fc2=True):
+    """-> (grad_in, grad_wg, grad_bg, grad_wu, grad_bu, grad_w2, grad_b2), None where not wanted (grad_bg / grad_bu also
+    without that bias; grad_b2 is returned whenever fc2's gradients are wanted).  need_grad_fc1 covers both first-layer
+    matrices and their biases.  Both pre-activations are recomputed from in_feat; the parameter gradients are fixed-order
+    sums without atomics, in the dtype of the rows (me_glu_backward)."""
+    (x, wg, bg, wu, bu, w2, _), n, c, hd, cout = _glu_operands(in_feat, wg, bg, wu, bu, w2, None, activation)
+    dy = grad_out_feat.detach().to(x.dtype).contiguous()
+    _check(tuple(dy.shape) == (n, cout) and dy.device == x.device, "grad_out_feat must be", (n, cout), "on the device of in_feat")
+    dev = x.device
+
+    def new(*shape, want=True):
+        return torch.empty(shape, dtype=x.dtype, device=dev) if want else None
+    dx = new(n, c, want=need_grad_in)
+    dwg, dbg = new(hd, c, want=need_grad_fc1), new(hd, want=need_grad_fc1 and bg is not None)
+    dwu, dbu = new(hd, c, want=need_grad_fc1), new(hd, want=need_grad_fc1 and bu is not None)
+    dw2, db2 = new(cout, hd, want=need_grad_fc2), new(cout, want=need_grad_fc2)
+    grads = (dx, dwg, dbg, dwu, dbu, dw2, db2)
+    if n == 0:
+        for t in grads[1:]:
+            if t is not None:
+                t.zero_()
+        return grads
+    if not (need_grad_in or need_grad_fc1 or need_grad_fc2):
+        return grads
+    lib = _lib.load()
+    with _on(dev):
+        ws = _workspace(int(lib.me_glu_workspace_bytes(n, c, hd, cout, x.element_size())), dev)
+        _timed("glu_backward", dev, lambda: _lib.check(lib.me_glu_backward(
+            _ptr(x), _ptr(dy), _ptr(wg), _ptr(bg), _ptr(wu), _ptr(bu), _ptr(w2), 1 if x.dtype == torch.bfloat16 else 0, n, c,
+            hd, cout, FFN_ACTIVATIONS[activation], int(need_grad_in), int(need_grad_fc1), int(need_grad_fc2),
+            *(_ptr(t) for t in grads), _ptr(ws), ws.numel(), _stream(dev))))
+    return grads
+
+
+# ------------------------------------------------------------------------------------------------
 # pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu)
 # ------------------------------------------------------------------------------------------------
 def PruningForwardGPU(in_feat, keep, in_key, out_key, manager):

@@ -884,6 +884,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         },
         py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("activation"),
         py::arg("need_grad_in") = true, py::arg("need_grad_fc1") = true, py::arg("need_grad_fc2") = true);
+  // fused gated MLP: csrc/gated_feed_forward.hip
+  m.def("GatedFeedForwardForwardGPU",
+        [](const Tensor &in_feat, const Tensor &wg, const py::object &bg, const Tensor &wu, const py::object &bu,
+           const Tensor &w2, const py::object &b2, const std::string &activation) {
+          const Tensor bgt = opt_tensor(bg), but = opt_tensor(bu), b2t = opt_tensor(b2);
+          py::gil_scoped_release nogil;
+          return gated_feed_forward_forward(in_feat, wg, bgt, wu, but, w2, b2t, activation);
+        },
+        py::arg("in_feat"), py::arg("wg"), py::arg("bg"), py::arg("wu"), py::arg("bu"), py::arg("w2"), py::arg("b2"),
+        py::arg("activation"));
+  m.def("GatedFeedForwardBackwardGPU",
+        [](const Tensor &in_feat, const Tensor &grad_out, const Tensor &wg, const py::object &bg, const Tensor &wu,
+           const py::object &bu, const Tensor &w2, const std::string &activation, bool need_grad_in, bool need_grad_fc1,
+           bool need_grad_fc2) {
+          const Tensor bgt = opt_tensor(bg), but = opt_tensor(bu);
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = gated_feed_forward_backward(in_feat, grad_out, wg, bgt, wu, but, w2, activation, need_grad_in,
+                                            need_grad_fc1, need_grad_fc2);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]), opt_out(r[3]), opt_out(r[4]), opt_out(r[5]),
+                                opt_out(r[6]));
+        },
+        py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("wg"), py::arg("bg"), py::arg("wu"), py::arg("bu"),
+        py::arg("w2"), py::arg("activation"), py::arg("need_grad_in") = true, py::arg("need_grad_fc1") = true,
+        py::arg("need_grad_fc2") = true);
   // tensor fields (field.cpp): the reference's InterpolationForwardGPU / InterpolationBackwardGPU and coo_spmm_int32 /
   // coo_spmm_average_int32 (pybind/extern.hpp:497-506), plus the CSR building blocks the autograd functions cache
   m.def("CsrFromCooGPU",

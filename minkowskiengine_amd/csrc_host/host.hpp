@@ -464,6 +464,14 @@ Tensor feed_forward_forward(const Tensor &in_feat, const Tensor &w1, const Tenso
 std::vector<Tensor> feed_forward_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &w1,
                                           const Tensor &b1, const Tensor &w2, const std::string &activation,
                                           bool need_grad_in, bool need_grad_fc1, bool need_grad_fc2);
+// fused gated MLP (csrc/gated_feed_forward.hip; twin of backend.GatedFeedForward{Forward,Backward}GPU);
+// backward -> (grad_in, grad_wg, grad_bg, grad_wu, grad_bu, grad_w2, grad_b2), undefined where not wanted
+Tensor gated_feed_forward_forward(const Tensor &in_feat, const Tensor &wg, const Tensor &bg, const Tensor &wu,
+                                  const Tensor &bu, const Tensor &w2, const Tensor &b2, const std::string &activation);
+std::vector<Tensor> gated_feed_forward_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &wg,
+                                                const Tensor &bg, const Tensor &wu, const Tensor &bu, const Tensor &w2,
+                                                const std::string &activation, bool need_grad_in, bool need_grad_fc1,
+                                                bool need_grad_fc2);
 // dense <-> sparse conversion (csrc/dense.hip; twin of backend.Dense*GPU / DensePolicy)
 int64_t dense_policy(int64_t n, int64_t n_cells, int64_t c, int64_t elem_bytes, bool to_box);
 std::tuple<Tensor, Tensor, Tensor> dense_cell_index(const Tensor &coordinates, const ivec &min_coordinate,

@@ -1833,6 +1833,77 @@ std::vector<Tensor> feed_forward_backward(const Tensor &in_feat, const Tensor &g
   return g;
 }
 
+// ---- fused gated MLP (csrc/gated_feed_forward.hip, ABI 1.25; twin of backend.GatedFeedForward{Forward,Backward}GPU) ------
+static void glu_check(const Tensor &x, const Tensor &wg, const Tensor &bg, const Tensor &wu, const Tensor &bu,
+                      const Tensor &w2, const Tensor &b2) {
+  check(x.is_cuda(), "in_feat must be CUDA (ROCm) — the MI355X path has no CPU implementation");
+  check(x.dim() == 2 && wg.dim() == 2 && wu.dim() == 2 && w2.dim() == 2, "in_feat, wg, wu and w2 must be 2-D");
+  check(wg.size(1) == x.size(1) && wu.sizes() == wg.sizes() && w2.size(1) == wg.size(0),
+        "channel mismatch between in_feat, wg, wu and w2");
+  for (const Tensor *b : {&bg, &bu})
+    check(!b->defined() || (b->dim() == 1 && b->size(0) == wg.size(0)), "bg and bu must have one value per hidden unit");
+  check(!b2.defined() || (b2.dim() == 1 && b2.size(0) == w2.size(0)), "b2 must have one value per output channel");
+  for (const Tensor *t : {&wg, &bg, &wu, &bu, &w2, &b2})
+    check(!t->defined() || (t->scalar_type() == x.scalar_type() && t->device() == x.device()),
+          "wg, bg, wu, bu, w2 and b2 must have the dtype and device of in_feat");
+  const bool served = x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16;
+  check(served && me_glu_supported((int32_t)x.size(1), (int32_t)wg.size(0), (int32_t)w2.size(0),
+                                   (int32_t)x.element_size()) != 0,
+        "widths are not served by the gated feed-forward kernels");
+}
+
+Tensor gated_feed_forward_forward(const Tensor &in_feat, const Tensor &wg_, const Tensor &bg_, const Tensor &wu_,
+                                  const Tensor &bu_, const Tensor &w2_, const Tensor &b2_, const std::string &activation) {
+  const int act = ffn_activation(activation);
+  glu_check(in_feat, wg_, bg_, wu_, bu_, w2_, b2_);
+  const Tensor x = ffn_plain(in_feat), wg = ffn_plain(wg_), bg = ffn_plain(bg_), wu = ffn_plain(wu_), bu = ffn_plain(bu_),
+               w2 = ffn_plain(w2_), b2 = ffn_plain(b2_);
+  const int64_t n = x.size(0);
+  const int c = (int)x.size(1), hd = (int)wg.size(0), cout = (int)w2.size(0);
+  Tensor out = at::empty({n, cout}, x.options());
+  if (n == 0) return out;
+  c10::DeviceGuard guard(x.device());
+  me_ok(me_glu_forward(vptr(x), vptr(wg), vptr(bg), vptr(wu), vptr(bu), vptr(w2), vptr(b2),
+                       x.scalar_type() == at::kBFloat16 ? 1 : 0, n, c, hd, cout, act, vptr(out), stream_of(x.device())));
+  return out;
+}
+
+std::vector<Tensor> gated_feed_forward_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &wg_,
+                                                const Tensor &bg_, const Tensor &wu_, const Tensor &bu_, const Tensor &w2_,
+                                                const std::string &activation, bool need_grad_in, bool need_grad_fc1,
+                                                bool need_grad_fc2) {
+  const int act = ffn_activation(activation);
+  glu_check(in_feat, wg_, bg_, wu_, bu_, w2_, Tensor());
+  const Tensor x = ffn_plain(in_feat), wg = ffn_plain(wg_), bg = ffn_plain(bg_), wu = ffn_plain(wu_), bu = ffn_plain(bu_),
+               w2 = ffn_plain(w2_);
+  const int64_t n = x.size(0);
+  const int c = (int)x.size(1), hd = (int)wg.size(0), cout = (int)w2.size(0);
+  const Tensor dy = grad_out.detach().to(x.scalar_type()).contiguous();
+  check(dy.dim() == 2 && dy.size(0) == n && dy.size(1) == cout && dy.device() == x.device(),
+        "grad_out_feat must be [n, cout] on the device of in_feat");
+  std::vector<Tensor> g(7);   // grad_in, grad_wg, grad_bg, grad_wu, grad_bu, grad_w2, grad_b2
+  if (need_grad_in) g[0] = at::empty({n, c}, x.options());
+  if (need_grad_fc1) g[1] = at::empty({hd, c}, x.options());
+  if (need_grad_fc1 && bg.defined()) g[2] = at::empty({hd}, x.options());
+  if (need_grad_fc1) g[3] = at::empty({hd, c}, x.options());
+  if (need_grad_fc1 && bu.defined()) g[4] = at::empty({hd}, x.options());
+  if (need_grad_fc2) g[5] = at::empty({cout, hd}, x.options());
+  if (need_grad_fc2) g[6] = at::empty({cout}, x.options());
+  if (n == 0) {
+    for (size_t i = 1; i < 7; i++)
+      if (g[i].defined()) g[i].zero_();
+    return g;
+  }
+  if (!need_grad_in && !need_grad_fc1 && !need_grad_fc2) return g;
+  c10::DeviceGuard guard(x.device());
+  Tensor ws = workspace(me_glu_workspace_bytes(n, c, hd, cout, (int32_t)x.element_size()), x.device());
+  me_ok(me_glu_backward(vptr(x), vptr(dy), vptr(wg), vptr(bg), vptr(wu), vptr(bu), vptr(w2),
+                        x.scalar_type() == at::kBFloat16 ? 1 : 0, n, c, hd, cout, act, need_grad_in ? 1 : 0,
+                        need_grad_fc1 ? 1 : 0, need_grad_fc2 ? 1 : 0, vptr(g[0]), vptr(g[1]), vptr(g[2]), vptr(g[3]),
+                        vptr(g[4]), vptr(g[5]), vptr(g[6]), vptr(ws), ws.numel(), stream_of(x.device())));
+  return g;
+}
+
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------
 Tensor pruning_forward(const Tensor &in_feat, const Tensor &keep, CoordinateMapKey *in_key, CoordinateMapKey *out_key,
                        CoordinateMapManager *mgr) {

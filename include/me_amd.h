@@ -128,7 +128,12 @@ typedef struct me_region {
  *              me_ffn_backward)
  *   1.25 (350)  round 25: the gated MLP (SwiGLU / GeGLU / ReGLU) on the same design: two first products off one set of
  *              row fragments, the gate applied in registers, two second products into one accumulator set in the input
- *              gradient (me_glu_supported, me_glu_row_splits, me_glu_workspace_bytes, me_glu_forward, me_glu_backward) */
+ *              gradient (me_glu_supported, me_glu_row_splits, me_glu_workspace_bytes, me_glu_forward, me_glu_backward)
+ *   1.26 (360)  round 26: layer norm / RMS norm modulated per instance with a gated residual add (adaLN): the tables of
+ *              scale / shift / gate read through batch_row in the forward pass, a backward pass whose chunks are cut over
+ *              the per-instance row lists so that a workgroup owns rows of one instance, fixed-order merges for the
+ *              conditioning and parameter gradients (me_adaln_chunks, me_adaln_workspace_bytes, me_adaln_forward,
+ *              me_adaln_backward and the _f64 twins me_adaln_forward_f64, me_adaln_backward_f64) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1475,6 +1480,66 @@ int me_lnorm_backward_f64(const double *x_dev, const double *dy_dev, const doubl
                           int64_t dy_stride, int64_t dstream_stride, int64_t n, int32_t c, int32_t rms,
                           const double *gamma_dev, const double *mean_dev, const double *rstd_dev, double *dx_dev,
                           int64_t dx_stride, double *grad_gamma_dev, double *grad_beta_dev, void *stream);
+
+/* ---- layer norm / RMS norm modulated per instance, with a gated residual add (MinkowskiAdaLayerNorm,
+ *      MinkowskiFunctional.ada_layer_norm; csrc/ada_layer_norm.hip, ABI 1.26) ----
+ * One half of a DiT block.  Rows, strides, gamma / beta, mean / rstd as me_lnorm_*; b = batch_row[r] (int32 [n], rows of the
+ * origin map, in any order) selects row b of scale, shift, gate: [n_batch, c] floats, contiguous, each NULL for 0 / 0 / 1
+ * (then not read; batch_row is read only when one of them is given).  Forward, in fp32:
+ *   stream[r] = T(fma(gate[b], x[r], residual[r]))        (without a residual: stream = x, nothing is written)
+ *   xhat      = me_lnorm_forward's, bit for bit, from the rounded stream;   yhat = xhat gamma + beta
+ *   y[r]      = T(fma(yhat, 1 + scale[b], shift[b]))
+ * so with scale = shift = 0 and gate = 1 the call equals me_lnorm_forward.  Backward takes the rows that were normalised
+ * (stream_rows: stream_out, or x without a residual), dy (gradient of y) and / or dstream (gradient arriving at
+ * stream_out), and input (= the forward's x) when a gate was given:
+ *   g  = dy (1 + scale[b]) gamma,  dx = me_lnorm_backward's formula on g,  dS = T(dx) (+ dstream, rounded again)
+ *   dstream_out = dS (the gradient of residual; of x too without a gate),  dinput = T(gate[b] dS)
+ *   grad_shift[b] = sum_{r in b} dy,  grad_scale[b] = sum_{r in b} dy yhat,  grad_gate[b] = sum_{r in b} input[r] dS[r]
+ *   grad_gamma = sum_r dy (1 + scale[b]) xhat,  grad_beta = sum_r dy (1 + scale[b])
+ * without dy the norm terms drop out (dS = dstream).  Every output pointer may be NULL: not computed, not written.
+ * The rows come through the per-instance row lists seg_ptr int32 [n_batch + 1], seg_rows int32 [n] (rows ascending inside
+ * an instance): instance b of m rows is cut into ceil(m / rc) chunks of rc consecutive list entries,
+ * rc = max(ceil(16384 / (c elem_bytes)), ceil(n / 1024)); a workgroup owns one chunk (it finds it by walking seg_ptr; the
+ * grid is me_adaln_chunks = me_lnorm_chunks + n_batch, an upper bound, and the surplus workgroups leave) and writes one record
+ * [3][c] (sum dy xhat, sum dy, sum input dS) into the workspace.  One kernel adds the records of an instance in ascending
+ * chunk order and forms grad_scale / grad_shift / grad_gate and the instance's share of grad_gamma / grad_beta; one more
+ * adds the shares in ascending instance order.  No atomics: every output is bitwise reproducible, and the sums of an
+ * instance do not depend on the other instances while n <= 1024 rc.  An instance without rows gets zeros.
+ * Host-side errors, nothing launched: c < 1, c > ME_LNORM_MAX_C (fp32 / bf16 entry points), n < 0 or n >= 2^31, rows without
+ * an instance, a row stride below c, a residual without stream_out, a gate without a residual (forward) or without input
+ * (backward), a gradient of gamma / beta / scale / shift without dy, a workspace below me_adaln_workspace_bytes when a
+ * parameter or conditioning gradient is wanted; then, with n > 0, a missing data pointer.
+ * The _f64 twins are the plain formulas in double for any c (one wave a row; one thread per (instance, channel) or per
+ * channel for the sums, rows in ascending order; they read mean_dev and batch_row): the gradcheck yardstick. */
+int32_t me_adaln_chunks(int64_t n, int32_t n_batch, int32_t c, int32_t elem_bytes);
+int64_t me_adaln_workspace_bytes(int64_t n, int32_t n_batch, int32_t c, int32_t elem_bytes);
+int me_adaln_forward(const void *x_dev, const void *residual_dev, void *stream_out_dev, int32_t is_bf16, int64_t x_stride,
+                     int64_t residual_stride, int64_t stream_out_stride, int64_t n, int32_t c, int32_t rms,
+                     const int32_t *batch_row_dev, int32_t n_batch, const float *gamma_dev, const float *beta_dev,
+                     const float *scale_dev, const float *shift_dev, const float *gate_dev, float eps, void *y_dev,
+                     int64_t y_stride, float *mean_dev, float *rstd_dev, void *stream);
+int me_adaln_backward(const void *stream_rows_dev, const void *dy_dev, const void *dstream_dev, const void *input_dev,
+                      int32_t is_bf16, int64_t x_stride, int64_t dy_stride, int64_t dstream_stride, int64_t input_stride,
+                      int64_t n, int32_t c, int32_t rms, const int32_t *seg_ptr_dev, const int32_t *seg_rows_dev,
+                      int32_t n_batch, const float *gamma_dev, const float *beta_dev, const float *scale_dev,
+                      const float *gate_dev, const float *rstd_dev, void *dstream_out_dev, int64_t dstream_out_stride,
+                      void *dinput_dev, int64_t dinput_stride, float *grad_gamma_dev, float *grad_beta_dev,
+                      float *grad_scale_dev, float *grad_shift_dev, float *grad_gate_dev, void *workspace_dev,
+                      int64_t workspace_bytes, void *stream);
+int me_adaln_forward_f64(const double *x_dev, const double *residual_dev, double *stream_out_dev, int64_t x_stride,
+                         int64_t residual_stride, int64_t stream_out_stride, int64_t n, int32_t c, int32_t rms,
+                         const int32_t *batch_row_dev, int32_t n_batch, const double *gamma_dev, const double *beta_dev,
+                         const double *scale_dev, const double *shift_dev, const double *gate_dev, double eps,
+                         double *y_dev, int64_t y_stride, double *mean_dev, double *rstd_dev, void *stream);
+int me_adaln_backward_f64(const double *stream_rows_dev, const double *dy_dev, const double *dstream_dev,
+                          const double *input_dev, int64_t x_stride, int64_t dy_stride, int64_t dstream_stride,
+                          int64_t input_stride, int64_t n, int32_t c, int32_t rms, const int32_t *batch_row_dev,
+                          const int32_t *seg_ptr_dev, const int32_t *seg_rows_dev, int32_t n_batch,
+                          const double *gamma_dev, const double *beta_dev, const double *scale_dev,
+                          const double *gate_dev, const double *mean_dev, const double *rstd_dev,
+                          double *dstream_out_dev, int64_t dstream_out_stride, double *dinput_dev, int64_t dinput_stride,
+                          double *grad_gamma_dev, double *grad_beta_dev, double *grad_scale_dev, double *grad_shift_dev,
+                          double *grad_gate_dev, void *stream);
 
 /* ---- fused two-layer MLP (MinkowskiFeedForward, MinkowskiFunctional.feed_forward; csrc/feed_forward.hip, ABI 1.24) ----
  *   y = act(x w1^T + b1) w2^T + b2

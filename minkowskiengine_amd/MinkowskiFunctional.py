@@ -212,6 +212,14 @@ def rms_norm(input, weight=None, eps=None):
     return _row_norm(input, None, weight, None, eps, True)
 
 
+def ada_layer_norm(input, scale=None, shift=None, residual=None, gate=None, weight=None, bias=None, eps=1e-6, rms=False):
+    """MinkowskiAdaLayerNorm as a function: norm(stream) * (1 + scale[b]) + shift[b] over the channel axis of a
+    SparseTensor, stream = residual + gate[b] * input.  scale / shift / gate: (instances, C) tensors or None; weight /
+    bias: (C,) tensors or None.  -> normed, or (normed, stream) with a residual."""
+    from .normalization import _ada_row_norm
+    return _ada_row_norm(input, residual, weight, bias, scale, shift, gate, eps, rms)
+
+
 def feed_forward(input, w1, b1, w2, b2, activation="gelu"):
     """act(F w1^T + b1) w2^T + b2 over the features F of a SparseTensor or a TensorField (MinkowskiFeedForward as a
     function).  w1 [hidden, C], w2 [C_out, hidden], b1 / b2 vectors or None; activation: gelu, gelu_tanh, relu or silu."""
@@ -230,4 +238,4 @@ def gated_feed_forward(input, wg, bg, wu, bu, w2, b2, activation="silu"):
 __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention",
                                                 "local_attention", "serialized_attention", "cross_attention",
                                                 "window_attention", "rotary_embedding", "layer_norm", "rms_norm",
-                                                "feed_forward", "gated_feed_forward"]
+                                                "ada_layer_norm", "feed_forward", "gated_feed_forward"]

@@ -21,8 +21,9 @@ from .convolution import (  # noqa: F401
     MinkowskiConvolutionTransposeFunction, MinkowskiGenerativeConvolutionTranspose)
 from .channelwise import MinkowskiChannelwiseConvolution, MinkowskiChannelwiseConvolutionFunction  # noqa: F401
 from .normalization import (  # noqa: F401
-    MinkowskiConditionalGroupNorm, MinkowskiConditionalGroupNormFunction, MinkowskiGroupNorm, MinkowskiGroupNormFunction,
-    MinkowskiInstanceNorm, MinkowskiInstanceNormFunction, MinkowskiLayerNorm, MinkowskiLayerNormFunction, MinkowskiRMSNorm,
+    MinkowskiAdaLayerNorm, MinkowskiAdaLayerNormFunction, MinkowskiConditionalGroupNorm,
+    MinkowskiConditionalGroupNormFunction, MinkowskiGroupNorm, MinkowskiGroupNormFunction, MinkowskiInstanceNorm,
+    MinkowskiInstanceNormFunction, MinkowskiLayerNorm, MinkowskiLayerNormFunction, MinkowskiRMSNorm,
     MinkowskiStableInstanceNorm)
 from .attention import (  # noqa: F401
     MinkowskiAttentionFunction, MinkowskiCrossAttention, MinkowskiCrossAttentionFunction, MinkowskiSelfAttention)

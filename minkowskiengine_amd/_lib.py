@@ -223,6 +223,19 @@ SIGNATURES = {
                                             ctypes.c_double, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "me_lnorm_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp,
                                              c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "me_adaln_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32]),
+    "me_adaln_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "me_adaln_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_float, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "me_adaln_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32,
+                                         c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_adaln_forward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_i32,
+                                            c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_double, c_vp, c_i64, c_vp, c_vp,
+                                            c_vp]),
+    "me_adaln_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32,
+                                             c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                             c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "me_ffn_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "me_ffn_row_splits": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),
     "me_ffn_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32, c_i32]),

@@ -4126,6 +4126,113 @@ def LayerNormBackwardGPU(in_feat, grad_out_feat, grad_stream, weight, mean, rstd
 
 
 # ------------------------------------------------------------------------------------------------
+# layer norm / RMS norm modulated per instance with a gated residual add, adaLN (csrc/ada_layer_norm.hip, ABI 1.26; not in
+# the reference).  The rows are LayerNorm*GPU's; the map key and the manager give batch_row (forward) and the per-instance
+# row lists (backward), both cached per map.
+# ------------------------------------------------------------------------------------------------
+def _adaln_prepare(in_feat, residual, weight, bias, mods, in_key, manager):
+    """-> (x, res, n_batch) after the checks both directions share; mods: ((name, tensor | None), ...) of [n_batch, C]"""
+    x = _lnorm_rows("in_feat", in_feat)
+    res = None if residual is None else _lnorm_rows("residual", residual, x)
+    _check(manager.exists(in_key), "coordinate map not found")
+    _check(x.shape[0] == manager.size(in_key), "Invalid in_feat size", x.shape[0], "!=", manager.size(in_key))
+    n_batch, c = manager.size(manager.origin()), int(x.shape[1])
+    _inorm_check_vec("weight", weight, x, c)
+    _inorm_check_vec("bias", bias, x, c)
+    for name, t in mods:
+        _gnorm_cond_check_mod(name, t, x, n_batch, c)
+    _check(x.dtype == torch.float64 or c <= LNORM_MAX_C, "rows of more than", LNORM_MAX_C,
+           "channels are not served by the fp32 / bf16 kernels")
+    return x, res, n_batch
+
+
+def AdaLayerNormForwardGPU(in_feat, residual, weight, bias, scale, shift, gate, eps, rms, in_key, manager):
+    """-> (out_feat, stream | None, mean | None, rstd): stream = residual + gate[b] * in_feat (one fma, rounded once; None
+    without a residual), out = norm(stream) * (1 + scale[b]) + shift[b] with LayerNormForwardGPU's norm and b the row of the
+    origin map (the j-th smallest batch index) of every row.  scale / shift / gate: [instances, C] in the parameter dtype or
+    None (0 / 0 / 1); a gate needs a residual.  One launch (me_adaln_forward)."""
+    _check(gate is None or residual is not None, "a gate needs a residual")
+    x, res, n_batch = _adaln_prepare(in_feat, residual, weight, bias, (("scale", scale), ("shift", shift), ("gate", gate)),
+                                     in_key, manager)
+    n, c = int(x.shape[0]), int(x.shape[1])
+    dev, pd = x.device, _inorm_param_dtype(x)
+    out = torch.empty((n, c), dtype=x.dtype, device=dev)
+    stream = None if res is None else torch.empty((n, c), dtype=x.dtype, device=dev)
+    mean = None if rms else torch.empty((n,), dtype=pd, device=dev)
+    rstd = torch.empty((n,), dtype=pd, device=dev)
+    if n == 0:
+        return out, stream, mean, rstd
+    lib = _lib.load()
+    rows = manager._origin_rows(in_key)
+    strides = (_attn_stride(x), 0 if res is None else _attn_stride(res), c)
+    tail = (n, c, 1 if rms else 0, _ptr(rows), n_batch, _ptr(weight), _ptr(bias), _ptr(scale), _ptr(shift), _ptr(gate),
+            float(eps), _ptr(out), c, _ptr(mean), _ptr(rstd))
+    with _on(dev):
+        if x.dtype == torch.float64:
+            _lib.check(lib.me_adaln_forward_f64(_ptr(x), _ptr(res), _ptr(stream), *strides, *tail, _stream(dev)))
+        else:
+            _timed("adaln_forward", dev, lambda: _lib.check(lib.me_adaln_forward(
+                _ptr(x), _ptr(res), _ptr(stream), 1 if x.dtype == torch.bfloat16 else 0, *strides, *tail, _stream(dev))))
+    return out, stream, mean, rstd
+
+
+def AdaLayerNormBackwardGPU(stream_feat, grad_out_feat, grad_stream, in_feat, weight, bias, scale, gate, mean, rstd, rms,
+                            in_key, manager, need_grad_in=True, need_grad_residual=True, need_grad_weight=True,
+                            need_grad_bias=True, need_grad_scale=True, need_grad_shift=True, need_grad_gate=True):
+    """-> (grad_in, grad_residual, grad_weight [C], grad_bias [C], grad_scale, grad_shift, grad_gate [instances, C]), None
+    where not needed.  stream_feat: the rows that were normalised (the stream of the residual form); grad_out_feat /
+    grad_stream: the gradients arriving at out and at stream, either may be None; in_feat: the forward's in_feat, read only
+    with a gate (None otherwise).  Without a gate grad_in IS grad_residual (one tensor).  Parameter and conditioning
+    gradients have the parameter dtype and are fixed-order sums without atomics (me_adaln_backward)."""
+    _check(grad_out_feat is not None or grad_stream is not None, "grad_out_feat or grad_stream must be given")
+    _check((gate is None) == (in_feat is None), "gate and in_feat are given together")
+    x, _, n_batch = _adaln_prepare(stream_feat, None, weight, bias, (("scale", scale), ("gate", gate)), in_key, manager)
+    dy = None if grad_out_feat is None else _lnorm_rows("grad_out_feat", grad_out_feat.to(x.dtype), x)
+    ds = None if grad_stream is None else _lnorm_rows("grad_stream", grad_stream.to(x.dtype), x)
+    xin = None if in_feat is None else _lnorm_rows("in_feat", in_feat, x)
+    n, c = int(x.shape[0]), int(x.shape[1])
+    if dy is not None:
+        _check(rstd is not None and (rms or mean is not None), "ada layer norm backward needs mean and rstd")
+        _inorm_check_vec("mean", mean, x, n)
+        _inorm_check_vec("rstd", rstd, x, n)
+    else:
+        need_grad_weight = need_grad_bias = need_grad_scale = need_grad_shift = False
+    need_grad_gate = need_grad_gate and gate is not None
+    need_s = need_grad_residual or (need_grad_in and gate is None)
+    dev, pd = x.device, _inorm_param_dtype(x)
+    grad_s = torch.empty((n, c), dtype=x.dtype, device=dev) if need_s else None
+    grad_in = grad_s if gate is None else (torch.empty((n, c), dtype=x.dtype, device=dev) if need_grad_in else None)
+    grad_w = torch.empty((c,), dtype=pd, device=dev) if need_grad_weight else None
+    grad_b = torch.empty((c,), dtype=pd, device=dev) if need_grad_bias else None
+    grad_sc, grad_sh, grad_g = (torch.empty((n_batch, c), dtype=pd, device=dev) if need else None
+                                for need in (need_grad_scale, need_grad_shift, need_grad_gate))
+    sums = (grad_w, grad_b, grad_sc, grad_sh, grad_g)
+    if n == 0:
+        return (grad_in if need_grad_in else None, grad_s if need_grad_residual else None,
+                *(None if g is None else g.zero_() for g in sums))
+    lib = _lib.load()
+    seg_ptr, seg_rows = manager._instance_rows(in_key)
+    strides = (_attn_stride(x), 0 if dy is None else _attn_stride(dy), 0 if ds is None else _attn_stride(ds),
+               0 if xin is None else _attn_stride(xin))
+    outs = (_ptr(grad_s), c, _ptr(None if gate is None else grad_in), c, *map(_ptr, sums))
+    with _on(dev):
+        if x.dtype == torch.float64:
+            _lib.check(lib.me_adaln_backward_f64(
+                _ptr(x), _ptr(dy), _ptr(ds), _ptr(xin), *strides, n, c, 1 if rms else 0, _ptr(manager._origin_rows(in_key)),
+                _ptr(seg_ptr), _ptr(seg_rows), n_batch, _ptr(weight), _ptr(bias), _ptr(scale), _ptr(gate), _ptr(mean),
+                _ptr(rstd), *outs, _stream(dev)))
+        else:
+            elem = x.element_size()
+            ws = _workspace(int(lib.me_adaln_workspace_bytes(n, n_batch, c, elem)), dev) if any(
+                g is not None for g in sums) else None
+            _timed("adaln_backward", dev, lambda: _lib.check(lib.me_adaln_backward(
+                _ptr(x), _ptr(dy), _ptr(ds), _ptr(xin), 1 if x.dtype == torch.bfloat16 else 0, *strides, n, c,
+                1 if rms else 0, _ptr(seg_ptr), _ptr(seg_rows), n_batch, _ptr(weight), _ptr(bias), _ptr(scale), _ptr(gate),
+                _ptr(rstd), *outs, _ptr(ws), 0 if ws is None else ws.numel(), _stream(dev))))
+    return (grad_in if need_grad_in else None, grad_s if need_grad_residual else None, *sums)
+
+
+# ------------------------------------------------------------------------------------------------
 # fused two-layer MLP (csrc/feed_forward.hip, ABI 1.24; not in the reference): y = act(x w1^T + b1) w2^T + b2 without the
 # hidden matrix in memory.  Row-local, so the operators take no coordinate map.
 # ------------------------------------------------------------------------------------------------

@@ -861,6 +861,46 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("in_feat"), py::arg("grad_out_feat"), py::arg("grad_stream"), py::arg("weight"), py::arg("mean"),
         py::arg("rstd"), py::arg("rms") = false, py::arg("need_grad_in") = true, py::arg("need_grad_weight") = true,
         py::arg("need_grad_bias") = true);
+  // layer norm / RMS norm modulated per instance with a gated residual add (adaLN): csrc/ada_layer_norm.hip
+  m.def("AdaLayerNormForwardGPU",
+        [](const Tensor &in_feat, const py::object &residual, const py::object &weight, const py::object &bias,
+           const py::object &scale, const py::object &shift, const py::object &gate, double eps, bool rms,
+           CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+          const Tensor res = opt_tensor(residual), w = opt_tensor(weight), b = opt_tensor(bias), sc = opt_tensor(scale),
+                       sh = opt_tensor(shift), gt = opt_tensor(gate);
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = ada_layer_norm_forward(in_feat, res, w, b, sc, sh, gt, eps, rms, in_key, mgr);
+          }
+          return py::make_tuple(r[0], opt_out(r[1]), opt_out(r[2]), r[3]);
+        },
+        py::arg("in_feat"), py::arg("residual"), py::arg("weight"), py::arg("bias"), py::arg("scale"), py::arg("shift"),
+        py::arg("gate"), py::arg("eps"), py::arg("rms"), py::arg("in_key"), py::arg("manager"));
+  m.def("AdaLayerNormBackwardGPU",
+        [](const Tensor &stream_feat, const py::object &grad_out, const py::object &grad_stream, const py::object &in_feat,
+           const py::object &weight, const py::object &bias, const py::object &scale, const py::object &gate,
+           const py::object &mean, const py::object &rstd, bool rms, CoordinateMapKey *in_key, CoordinateMapManager *mgr,
+           bool need_grad_in, bool need_grad_residual, bool need_grad_weight, bool need_grad_bias, bool need_grad_scale,
+           bool need_grad_shift, bool need_grad_gate) {
+          const Tensor dy = opt_tensor(grad_out), ds = opt_tensor(grad_stream), xin = opt_tensor(in_feat),
+                       w = opt_tensor(weight), b = opt_tensor(bias), sc = opt_tensor(scale), gt = opt_tensor(gate),
+                       mu = opt_tensor(mean), rs = opt_tensor(rstd);
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = ada_layer_norm_backward(stream_feat, dy, ds, xin, w, b, sc, gt, mu, rs, rms, in_key, mgr,
+                                        {need_grad_in, need_grad_residual, need_grad_weight, need_grad_bias,
+                                         need_grad_scale, need_grad_shift, need_grad_gate});
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]), opt_out(r[3]), opt_out(r[4]), opt_out(r[5]),
+                                opt_out(r[6]));
+        },
+        py::arg("stream_feat"), py::arg("grad_out_feat"), py::arg("grad_stream"), py::arg("in_feat"), py::arg("weight"),
+        py::arg("bias"), py::arg("scale"), py::arg("gate"), py::arg("mean"), py::arg("rstd"), py::arg("rms"),
+        py::arg("in_key"), py::arg("manager"), py::arg("need_grad_in") = true, py::arg("need_grad_residual") = true,
+        py::arg("need_grad_weight") = true, py::arg("need_grad_bias") = true, py::arg("need_grad_scale") = true,
+        py::arg("need_grad_shift") = true, py::arg("need_grad_gate") = true);
   // fused two-layer MLP: csrc/feed_forward.hip
   m.def("FeedForwardForwardGPU",
         [](const Tensor &in_feat, const Tensor &w1, const py::object &b1, const Tensor &w2, const py::object &b2,

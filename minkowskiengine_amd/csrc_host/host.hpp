@@ -14,6 +14,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
+#include <array>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -457,6 +458,17 @@ std::vector<Tensor> layer_norm_forward(const Tensor &in_feat, const Tensor &resi
 std::vector<Tensor> layer_norm_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &grad_stream,
                                         const Tensor &weight, const Tensor &mean, const Tensor &rstd, bool rms,
                                         bool need_grad_in, bool need_grad_weight, bool need_grad_bias);
+// layer norm / RMS norm modulated per instance with a gated residual add (csrc/ada_layer_norm.hip; twin of
+// backend.AdaLayerNorm{Forward,Backward}GPU); -> (out, stream, mean, rstd) and (grad_in, grad_residual, grad_weight,
+// grad_bias, grad_scale, grad_shift, grad_gate), undefined where not wanted
+std::vector<Tensor> ada_layer_norm_forward(const Tensor &in_feat, const Tensor &residual, const Tensor &weight,
+                                           const Tensor &bias, const Tensor &scale, const Tensor &shift, const Tensor &gate,
+                                           double eps, bool rms, CoordinateMapKey *in_key, CoordinateMapManager *mgr);
+std::vector<Tensor> ada_layer_norm_backward(const Tensor &stream_feat, const Tensor &grad_out, const Tensor &grad_stream,
+                                            const Tensor &in_feat, const Tensor &weight, const Tensor &bias,
+                                            const Tensor &scale, const Tensor &gate, const Tensor &mean, const Tensor &rstd,
+                                            bool rms, CoordinateMapKey *in_key, CoordinateMapManager *mgr,
+                                            const std::array<bool, 7> &need);
 // fused two-layer MLP (csrc/feed_forward.hip; twin of backend.FeedForward{Forward,Backward}GPU);
 // backward -> (grad_in, grad_w1, grad_b1, grad_w2, grad_b2), undefined where not wanted
 Tensor feed_forward_forward(const Tensor &in_feat, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2,

@@ -1760,6 +1760,122 @@ std::vector<Tensor> layer_norm_backward(const Tensor &in_feat, const Tensor &gra
   return g;
 }
 
+// ---- layer norm / RMS norm modulated per instance with a gated residual add (csrc/ada_layer_norm.hip, ABI 1.26; twin of
+// backend.AdaLayerNorm{Forward,Backward}GPU): LayerNorm*GPU's rows; the map gives batch_row and the per-instance row lists ---
+// -> n_batch after the checks both directions share
+static int adaln_prepare(const Tensor &x, const Tensor &weight, const Tensor &bias,
+                         std::initializer_list<std::pair<const char *, const Tensor *>> mods, CoordinateMapKey *in_key,
+                         CoordinateMapManager *mgr) {
+  const KeyT &ik = in_key->get();
+  check(mgr->exists(ik), "coordinate map not found");
+  check(x.size(0) == mgr->get(ik)->n, "Invalid in_feat size");
+  const int64_t n_batch = mgr->get(mgr->origin())->n;
+  inorm_check_vec("weight", weight, x, x.size(1));
+  inorm_check_vec("bias", bias, x, x.size(1));
+  for (const auto &m : mods) gnorm_cond_check_mod(m.first, *m.second, x, n_batch, x.size(1));
+  lnorm_check_width(x);
+  return (int)n_batch;
+}
+
+std::vector<Tensor> ada_layer_norm_forward(const Tensor &in_feat, const Tensor &residual, const Tensor &weight,
+                                           const Tensor &bias, const Tensor &scale, const Tensor &shift, const Tensor &gate,
+                                           double eps, bool rms, CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+  check(!gate.defined() || residual.defined(), "a gate needs a residual");
+  const Tensor x = lnorm_rows("in_feat", in_feat);
+  const Tensor res = residual.defined() ? lnorm_rows("residual", residual, &x) : Tensor();
+  const int n_batch = adaln_prepare(x, weight, bias, {{"scale", &scale}, {"shift", &shift}, {"gate", &gate}}, in_key, mgr);
+  const int64_t n = x.size(0);
+  const int c = (int)x.size(1);
+  const c10::Device dev = x.device();
+  const bool f64 = x.scalar_type() == at::kDouble;
+  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  Tensor out = at::empty({n, c}, x.options());
+  Tensor stream = res.defined() ? at::empty({n, c}, x.options()) : Tensor();
+  Tensor mean = rms ? Tensor() : at::empty({n}, popt), rstd = at::empty({n}, popt);
+  if (n == 0) return {out, stream, mean, rstd};
+  c10::DeviceGuard guard(dev);
+  const Tensor rows = mgr->origin_rows(in_key->get());
+  const int64_t xs = attn_stride(x), rs = res.defined() ? attn_stride(res) : 0;
+  if (f64)
+    me_ok(me_adaln_forward_f64(ptr<double>(x), ptr<double>(res), ptr<double>(stream), xs, rs, c, n, c, rms ? 1 : 0,
+                               ptr<int32_t>(rows), n_batch, ptr<double>(weight), ptr<double>(bias), ptr<double>(scale),
+                               ptr<double>(shift), ptr<double>(gate), eps, ptr<double>(out), c, ptr<double>(mean),
+                               ptr<double>(rstd), stream_of(dev)));
+  else
+    me_ok(me_adaln_forward(vptr(x), vptr(res), vptr(stream), x.scalar_type() == at::kBFloat16 ? 1 : 0, xs, rs, c, n, c,
+                           rms ? 1 : 0, ptr<int32_t>(rows), n_batch, ptr<float>(weight), ptr<float>(bias),
+                           ptr<float>(scale), ptr<float>(shift), ptr<float>(gate), (float)eps, vptr(out), c,
+                           ptr<float>(mean), ptr<float>(rstd), stream_of(dev)));
+  return {out, stream, mean, rstd};
+}
+
+// need: grad_in, grad_residual, grad_weight, grad_bias, grad_scale, grad_shift, grad_gate
+std::vector<Tensor> ada_layer_norm_backward(const Tensor &stream_feat, const Tensor &grad_out, const Tensor &grad_stream,
+                                            const Tensor &in_feat, const Tensor &weight, const Tensor &bias,
+                                            const Tensor &scale, const Tensor &gate, const Tensor &mean, const Tensor &rstd,
+                                            bool rms, CoordinateMapKey *in_key, CoordinateMapManager *mgr,
+                                            const std::array<bool, 7> &need_in) {
+  check(grad_out.defined() || grad_stream.defined(), "grad_out_feat or grad_stream must be given");
+  check(gate.defined() == in_feat.defined(), "gate and in_feat are given together");
+  const Tensor x = lnorm_rows("in_feat", stream_feat);
+  const int n_batch = adaln_prepare(x, weight, bias, {{"scale", &scale}, {"gate", &gate}}, in_key, mgr);
+  const Tensor dy = grad_out.defined() ? lnorm_rows("grad_out_feat", grad_out.to(x.scalar_type()), &x) : Tensor();
+  const Tensor ds = grad_stream.defined() ? lnorm_rows("grad_stream", grad_stream.to(x.scalar_type()), &x) : Tensor();
+  const Tensor xin = in_feat.defined() ? lnorm_rows("in_feat", in_feat, &x) : Tensor();
+  const int64_t n = x.size(0);
+  const int c = (int)x.size(1);
+  std::array<bool, 7> need = need_in;
+  if (dy.defined()) {
+    check(rstd.defined() && (rms || mean.defined()), "ada layer norm backward needs mean and rstd");
+    inorm_check_vec("mean", mean, x, n);
+    inorm_check_vec("rstd", rstd, x, n);
+  } else {
+    need[2] = need[3] = need[4] = need[5] = false;
+  }
+  need[6] = need[6] && gate.defined();
+  const bool need_s = need[1] || (need[0] && !gate.defined());
+  const c10::Device dev = x.device();
+  const bool f64 = x.scalar_type() == at::kDouble;
+  const auto popt = at::TensorOptions().dtype(f64 ? at::kDouble : at::kFloat).device(dev);
+  Tensor grad_s = need_s ? at::empty({n, c}, x.options()) : Tensor();
+  Tensor grad_g = gate.defined() && need[0] ? at::empty({n, c}, x.options()) : Tensor();   // gate dS; else grad_in IS grad_s
+  std::vector<Tensor> g(7);
+  if (need[2]) g[2] = at::empty({c}, popt);
+  if (need[3]) g[3] = at::empty({c}, popt);
+  for (size_t i = 4; i < 7; i++)
+    if (need[i]) g[i] = at::empty({n_batch, c}, popt);
+  if (need[0]) g[0] = gate.defined() ? grad_g : grad_s;
+  if (need[1]) g[1] = grad_s;
+  if (n == 0) {
+    for (size_t i = 2; i < 7; i++)
+      if (g[i].defined()) g[i].zero_();
+    return g;
+  }
+  c10::DeviceGuard guard(dev);
+  const auto &lists = mgr->instance_rows(in_key->get());
+  const int64_t xs = attn_stride(x), dys = dy.defined() ? attn_stride(dy) : 0, dss = ds.defined() ? attn_stride(ds) : 0,
+                ins = xin.defined() ? attn_stride(xin) : 0;
+  if (f64) {
+    const Tensor rows = mgr->origin_rows(in_key->get());
+    me_ok(me_adaln_backward_f64(ptr<double>(x), ptr<double>(dy), ptr<double>(ds), ptr<double>(xin), xs, dys, dss, ins, n,
+                                c, rms ? 1 : 0, ptr<int32_t>(rows), ptr<int32_t>(lists.first), ptr<int32_t>(lists.second),
+                                n_batch, ptr<double>(weight), ptr<double>(bias), ptr<double>(scale), ptr<double>(gate),
+                                ptr<double>(mean), ptr<double>(rstd), ptr<double>(grad_s), c, ptr<double>(grad_g), c,
+                                ptr<double>(g[2]), ptr<double>(g[3]), ptr<double>(g[4]), ptr<double>(g[5]),
+                                ptr<double>(g[6]), stream_of(dev)));
+    return g;
+  }
+  Tensor ws;
+  if (need[2] || need[3] || need[4] || need[5] || need[6])
+    ws = workspace(me_adaln_workspace_bytes(n, n_batch, c, (int32_t)x.element_size()), dev);
+  me_ok(me_adaln_backward(vptr(x), vptr(dy), vptr(ds), vptr(xin), x.scalar_type() == at::kBFloat16 ? 1 : 0, xs, dys, dss,
+                          ins, n, c, rms ? 1 : 0, ptr<int32_t>(lists.first), ptr<int32_t>(lists.second), n_batch,
+                          ptr<float>(weight), ptr<float>(bias), ptr<float>(scale), ptr<float>(gate), ptr<float>(rstd),
+                          vptr(grad_s), c, vptr(grad_g), c, ptr<float>(g[2]), ptr<float>(g[3]), ptr<float>(g[4]),
+                          ptr<float>(g[5]), ptr<float>(g[6]), vptr(ws), ws.defined() ? ws.numel() : 0, stream_of(dev)));
+  return g;
+}
+
 // ---- fused two-layer MLP (csrc/feed_forward.hip, ABI 1.24; twin of backend.FeedForward{Forward,Backward}GPU): row-local,
 // no coordinate map -----------------------------------------------------------------------------------------------------
 static int ffn_activation(const std::string &activation) {

@@ -33,7 +33,11 @@ says which operator pair it is and where its gradients go among its inputs.
 MinkowskiLayerNorm, MinkowskiRMSNorm and MinkowskiLayerNormFunction normalise every ROW over its channels
 (torch.nn.LayerNorm / torch.nn.RMSNorm on the feature matrix): no instance, no coordinate map.  One operator pair,
 `LayerNorm{Forward,Backward}GPU` on csrc/layer_norm.hip, runs one pass forward and one pass plus a small merge backward,
-and takes the residual add of a pre-norm block into the same launches (`forward_residual`)."""
+and takes the residual add of a pre-norm block into the same launches (`forward_residual`).
+
+MinkowskiAdaLayerNorm and MinkowskiAdaLayerNormFunction (adaLN, one half of a DiT block) add one row of scale / shift /
+gate per instance to that: `stream = residual + gate[b] * input; normed = norm(stream) * (1 + scale[b]) + shift[b]` on
+`AdaLayerNorm{Forward,Backward}GPU` (csrc/ada_layer_norm.hip), sparse tensors only."""
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
@@ -471,3 +475,143 @@ class MinkowskiRMSNorm(_RowNormBase):
     def __repr__(self):
         return (self.__class__.__name__ +
                 f"({self.normalized_shape[0]}, eps={self.eps}, elementwise_affine={self.elementwise_affine})")
+
+
+class MinkowskiAdaLayerNormFunction(Function):
+    """Layer norm (rms=False) or RMS norm (rms=True) of the rows of a coordinate map, modulated per instance, with a gated
+    residual add, on `AdaLayerNorm{Forward,Backward}GPU`:
+
+        stream = residual + gate[b] * in_feat            (without a residual: stream = in_feat, gate must be None)
+        normed = norm(stream) * (1 + scale[b]) + shift[b]
+
+    b: the row of the origin map of every row (the j-th smallest batch index).  weight / bias: (C,) tensors of the
+    parameter dtype (fp32 for fp32 and bf16 features, float64 for float64) or None; scale / shift / gate: (instances, C)
+    tensors of the parameter dtype or None (0 / 0 / 1).  Returns normed, or (normed, stream) with a residual.  One launch
+    forward; one launch plus two small merges backward; every gradient is a fixed-order sum, bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, in_feat, residual, weight, bias, scale, shift, gate, eps, rms, in_coords_key, coords_manager):
+        fw_fn = get_minkowski_function("AdaLayerNormForward", in_feat, in_coords_key)
+        w, b, sc, sh, gt = (None if t is None else t.detach().contiguous() for t in (weight, bias, scale, shift, gate))
+        out, stream, mean, rstd = fw_fn(in_feat, residual, w, b, sc, sh, gt, float(eps), bool(rms), in_coords_key,
+                                        coords_manager._manager)
+        ctx.save_for_backward(in_feat if residual is None else stream, None if gt is None else in_feat, w, b, sc, gt, mean,
+                              rstd)
+        ctx.misc = (bool(rms), in_coords_key, coords_manager, residual is not None, sh is not None)
+        ctx.set_materialize_grads(False)
+        return out if residual is None else (out, stream)
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_stream=None):
+        rms, in_key, coords_manager, has_res, has_sh = ctx.misc
+        x, xin, w, b, sc, gt, mean, rstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        tail = (None, None, None, None)
+        if grad_out is None and (grad_stream is None or gt is None):          # nothing, or the add alone
+            return (grad_stream if need[0] else None, grad_stream if has_res and need[1] else None, None, None, None, None,
+                    None) + tail
+        bw_fn = get_minkowski_function("AdaLayerNormBackward", x, in_key)
+        grads = bw_fn(x, grad_out, grad_stream, xin, w, b, sc, gt, mean, rstd, rms, in_key, coords_manager._manager,
+                      need_grad_in=need[0], need_grad_residual=has_res and need[1], need_grad_weight=w is not None and need[2],
+                      need_grad_bias=b is not None and need[3], need_grad_scale=sc is not None and need[4],
+                      need_grad_shift=has_sh and need[5], need_grad_gate=gt is not None and need[6])
+        return tuple(grads) + tail
+
+
+def _ada_modulation(name, t, instances, c, pd):
+    """scale / shift / gate as the operators take them: (instances, C) in the parameter dtype"""
+    if t is None:
+        return None
+    if t.dim() != 2 or t.shape[0] != instances:
+        raise ValueError(f"{name} must have one row per instance: ({instances}, {c}), got {tuple(t.shape)}")
+    if t.shape[1] != c:
+        raise ValueError(f"{name} must have {c} channels, got {tuple(t.shape)}")
+    return t.to(pd)
+
+
+def _ada_row_norm(input, residual, weight, bias, scale, shift, gate, eps, rms):
+    """what MinkowskiAdaLayerNorm and the functional run: the Function, or torch for the shapes the kernels do not serve"""
+    if not isinstance(input, SparseTensor):
+        raise TypeError(f"a SparseTensor is expected, not a {type(input).__name__}")
+    key, f = input.coordinate_map_key, input.F
+    get_minkowski_function("AdaLayerNormForward", f, key)              # (CPU features raise here, as everywhere)
+    pd = torch.float64 if f.dtype == torch.float64 else torch.float32
+    weight = weight if weight is None or weight.dtype == pd else weight.to(pd)
+    bias = bias if bias is None or bias.dtype == pd else bias.to(pd)
+    instances, c = input._manager.origin_map_size(), f.shape[-1]
+    scale, shift, gate = (_ada_modulation(name, t, instances, c, pd)
+                          for name, t in (("scale", scale), ("shift", shift), ("gate", gate)))
+    r = None
+    if residual is not None:
+        if not isinstance(residual, SparseTensor):
+            raise TypeError(f"a SparseTensor is expected, not a {type(residual).__name__}")
+        assert key == residual.coordinate_map_key, "residual add needs a shared coordinate map"
+        r = residual.F
+        assert r.dtype == f.dtype and r.shape == f.shape, "input and residual must share dtype and shape"
+    elif gate is not None:
+        raise ValueError("a gate needs a residual")
+    if f.dim() != 2 or (f.dtype != torch.float64 and c > _LNORM_MAX_C):
+        rows = input._manager._manager._origin_rows(key).long()
+        stream = f if r is None else (r + f if gate is None else r + gate.to(f.dtype)[rows] * f)
+        w, b = None if weight is None else weight.to(f.dtype), None if bias is None else bias.to(f.dtype)
+        y = F.rms_norm(stream, (c,), w, eps) if rms else F.layer_norm(stream, (c,), w, b, eps)
+        if rms and b is not None:
+            y = y + b
+        if scale is not None:
+            y = y * (1 + scale.to(f.dtype)[rows])
+        if shift is not None:
+            y = y + shift.to(f.dtype)[rows]
+        return _rewrap(input, y) if r is None else (_rewrap(input, y), _rewrap(input, stream))
+    out = MinkowskiAdaLayerNormFunction.apply(f, r, weight, bias, scale, shift, gate, eps, rms, key, input._manager)
+    return _rewrap(input, out) if r is None else (_rewrap(input, out[0]), _rewrap(input, out[1]))
+
+
+class MinkowskiAdaLayerNorm(_RowNormBase):
+    r"""Adaptive layer norm (adaLN, one half of a DiT block) over the channel axis of a SparseTensor:
+
+        stream = residual + gate[b] * input,    normed = norm(stream) * (1 + scale[b]) + shift[b]
+
+    with one row of scale / shift / gate per instance — row j belongs to row j of the origin map, that is to the j-th
+    smallest batch index of the tensor — in one launch forward and one pass plus two small merges backward.
+    `forward(input, scale=None, shift=None)` returns normed; `forward_residual(input, residual, scale=None, shift=None,
+    gate=None)` returns (normed, stream).  Absent operands mean 0 / 0 / 1 and are not read; with all three absent the
+    layer equals MinkowskiLayerNorm (MinkowskiRMSNorm with `rms=True`) bit for bit.  scale / shift / gate are converted
+    to the parameter dtype with `.to()`, so their gradients flow back in the caller's dtype; a row count other than the
+    number of instances or a channel count other than C raises ValueError.  `elementwise_affine` defaults to False and
+    eps to 1e-6, as DiT's norms; `weight` / `bias` are named as torch.nn.LayerNorm's (RMSNorm's with `rms=True`: no bias),
+    so a checkpoint of MinkowskiLayerNorm loads strictly.  All gradients are fixed-order sums, bitwise reproducible.
+    Sparse tensors only (a TensorField raises TypeError).  Fallback to torch: fp32 / bf16 rows wider than 2048 channels
+    and features that are not 2-D."""
+
+    def __init__(self, normalized_shape, eps=1e-6, elementwise_affine=False, bias=True, rms=False):
+        super().__init__()
+        self._set_shape(normalized_shape)
+        self.eps = eps
+        self.elementwise_affine = elementwise_affine
+        self.rms = self._RMS = bool(rms)
+        if elementwise_affine:
+            self.weight = Parameter(torch.ones(self.normalized_shape, dtype=torch.float32))
+        else:
+            self.register_parameter("weight", None)
+        if not rms:
+            if elementwise_affine and bias:
+                self.bias = Parameter(torch.zeros(self.normalized_shape, dtype=torch.float32))
+            else:
+                self.register_parameter("bias", None)
+
+    def __repr__(self):
+        return (self.__class__.__name__ + f"({self.normalized_shape[0]}, eps={self.eps}, "
+                f"elementwise_affine={self.elementwise_affine}, bias={getattr(self, 'bias', None) is not None}, "
+                f"rms={self.rms})")
+
+    def forward(self, input, scale=None, shift=None):
+        return self.forward_residual(input, None, scale, shift)
+
+    def forward_residual(self, input, residual, scale=None, shift=None, gate=None):
+        """-> (normed, stream) (normed alone with residual=None): stream = residual + gate[b] * input, normed = the
+        modulated norm of stream — the gated tail of one half of a DiT block and the head of the next."""
+        if not isinstance(input, SparseTensor):
+            raise TypeError(f"a SparseTensor is expected, not a {type(input).__name__}")
+        self._check(input)
+        return _ada_row_norm(input, residual, self.weight, getattr(self, "bias", None), scale, shift, gate, self.eps,
+                             self.rms)

@@ -4261,38 +4261,90 @@ def feed_forward_row_splits(n, c, hd, cout, dtype):
     return int(_lib.load().me_ffn_row_splits(n, c, hd, cout, torch.finfo(dtype).bits // 8))
 
 
-def _ffn_operands(in_feat, w1, b1, w2, b2, activation):
+class _Mlp(typing.NamedTuple):
+    """what tells one fused MLP from the other"""
+    first: tuple        # names of the first layer's (weight, bias) pairs, in the order of the operators' arguments
+    abi: str            # me_<abi>_forward, me_<abi>_backward and me_<abi>_workspace_bytes; KernelTimer's <abi>_forward /
+                        # <abi>_backward
+    supported: typing.Callable   # the width rule of the kernels
+    kernels: str        # "... are not served by the <kernels> kernels"
+
+
+def _mlp_operands(op, in_feat, first, w2, b2, activation):
+    """first: the first layer's (weight, bias) pairs.  -> ([x, w, b, ..., w2, b2] detached and contiguous, n, c, hd, cout)"""
+    ws, bs = first[0::2], first[1::2]
+    wn, bn = [w for w, _ in op.first], [b for _, b in op.first]
     _check(activation in FFN_ACTIVATIONS, "activation must be one of", sorted(FFN_ACTIVATIONS), "not", repr(activation))
     _check(in_feat.is_cuda, "in_feat must be CUDA (ROCm) — the MI355X path has no CPU implementation")
-    _check(in_feat.dim() == 2 and w1.dim() == 2 and w2.dim() == 2, "in_feat, w1 and w2 must be 2-D")
+    _check(in_feat.dim() == 2 and w2.dim() == 2 and all(w.dim() == 2 for w in ws), "in_feat,", ", ".join(wn),
+           "and w2 must be 2-D")
     n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
-    hd, cout = int(w1.shape[0]), int(w2.shape[0])
-    _check(w1.shape[1] == c and w2.shape[1] == hd, "channel mismatch: in_feat", tuple(in_feat.shape), "w1", tuple(w1.shape),
-           "w2", tuple(w2.shape))
-    _check(b1 is None or tuple(b1.shape) == (hd,), "b1 must have", hd, "values")
+    hd, cout = int(ws[0].shape[0]), int(w2.shape[0])
+    _check(all(tuple(w.shape) == (hd, c) for w in ws) and w2.shape[1] == hd, "channel mismatch: in_feat", tuple(in_feat.shape),
+           *(x for name, w in zip(wn, ws) for x in (name, tuple(w.shape))), "w2", tuple(w2.shape))
+    _check(all(b is None or tuple(b.shape) == (hd,) for b in bs), " and ".join(bn), "must have", hd, "values")
     _check(b2 is None or tuple(b2.shape) == (cout,), "b2 must have", cout, "values")
-    for name, t in (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)):
+    names = [name for pair in op.first for name in pair] + ["w2", "b2"]
+    for name, t in zip(names, (*first, w2, b2)):
         _check(t is None or (t.dtype == in_feat.dtype and t.device == in_feat.device), name,
                "must have the dtype and device of in_feat")
-    _check(feed_forward_supported(c, hd, cout, in_feat.dtype), "widths", (c, hd, cout), "of", in_feat.dtype,
-           "are not served by the feed-forward kernels")
-    ops = [t if t is None else t.detach().contiguous() for t in (in_feat, w1, b1, w2, b2)]
+    _check(op.supported(c, hd, cout, in_feat.dtype), "widths", (c, hd, cout), "of", in_feat.dtype, "are not served by the",
+           op.kernels, "kernels")
+    ops = [t if t is None else t.detach().contiguous() for t in (in_feat, *first, w2, b2)]
     return ops, n, c, hd, cout
 
 
-def FeedForwardForwardGPU(in_feat, w1, b1, w2, b2, activation):
-    """-> out_feat [n, cout] = act(in_feat w1^T + b1) w2^T + b2 (w1 [hd, c], w2 [cout, hd], torch.nn.Linear's layouts; all
-    of one dtype, fp32 or bf16).  One launch (me_ffn_forward)."""
-    (x, w1, b1, w2, b2), n, c, hd, cout = _ffn_operands(in_feat, w1, b1, w2, b2, activation)
+def _mlp_forward(op, in_feat, first, w2, b2, activation):
+    (x, *params), n, c, hd, cout = _mlp_operands(op, in_feat, first, w2, b2, activation)
     out = torch.empty((n, cout), dtype=x.dtype, device=x.device)
     if n == 0:
         return out
     lib = _lib.load()
     with _on(x.device):
-        _timed("ffn_forward", x.device, lambda: _lib.check(lib.me_ffn_forward(
-            _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), 1 if x.dtype == torch.bfloat16 else 0, n, c, hd, cout,
-            FFN_ACTIVATIONS[activation], _ptr(out), _stream(x.device))), 4.0 * n * hd * (c + cout) / 2)
+        _timed(op.abi + "_forward", x.device, lambda: _lib.check(getattr(lib, f"me_{op.abi}_forward")(
+            _ptr(x), *(_ptr(t) for t in params), 1 if x.dtype == torch.bfloat16 else 0, n, c, hd, cout,
+            FFN_ACTIVATIONS[activation], _ptr(out), _stream(x.device))), 4.0 * n * hd * (len(op.first) * c + cout) / 2)
     return out
+
+
+def _mlp_backward(op, in_feat, grad_out_feat, first, w2, activation, need_grad_in, need_grad_fc1, need_grad_fc2):
+    """-> (grad_in, a (grad_w, grad_b) per first-layer pair, grad_w2, grad_b2), None where not wanted"""
+    (x, *params), n, c, hd, cout = _mlp_operands(op, in_feat, first, w2, None, activation)
+    params = params[:-1]                                                   # the backward entry points take no b2
+    dy = grad_out_feat.detach().to(x.dtype).contiguous()
+    _check(tuple(dy.shape) == (n, cout) and dy.device == x.device, "grad_out_feat must be", (n, cout), "on the device of in_feat")
+    dev = x.device
+
+    def new(*shape, want=True):
+        return torch.empty(shape, dtype=x.dtype, device=dev) if want else None
+    grads = [new(n, c, want=need_grad_in)]
+    for bias in params[1:-1:2]:
+        grads += [new(hd, c, want=need_grad_fc1), new(hd, want=need_grad_fc1 and bias is not None)]
+    grads = (*grads, new(cout, hd, want=need_grad_fc2), new(cout, want=need_grad_fc2))
+    if n == 0:
+        for t in grads[1:]:
+            if t is not None:
+                t.zero_()
+        return grads
+    if not (need_grad_in or need_grad_fc1 or need_grad_fc2):
+        return grads
+    lib = _lib.load()
+    with _on(dev):
+        ws = _workspace(int(getattr(lib, f"me_{op.abi}_workspace_bytes")(n, c, hd, cout, x.element_size())), dev)
+        _timed(op.abi + "_backward", dev, lambda: _lib.check(getattr(lib, f"me_{op.abi}_backward")(
+            _ptr(x), _ptr(dy), *(_ptr(t) for t in params), 1 if x.dtype == torch.bfloat16 else 0, n, c, hd, cout,
+            FFN_ACTIVATIONS[activation], int(need_grad_in), int(need_grad_fc1), int(need_grad_fc2),
+            *(_ptr(t) for t in grads), _ptr(ws), ws.numel(), _stream(dev))))
+    return grads
+
+
+_FFN = _Mlp((("w1", "b1"),), "ffn", feed_forward_supported, "feed-forward")
+
+
+def FeedForwardForwardGPU(in_feat, w1, b1, w2, b2, activation):
+    """-> out_feat [n, cout] = act(in_feat w1^T + b1) w2^T + b2 (w1 [hd, c], w2 [cout, hd], torch.nn.Linear's layouts; all
+    of one dtype, fp32 or bf16).  One launch (me_ffn_forward)."""
+    return _mlp_forward(_FFN, in_feat, (w1, b1), w2, b2, activation)
 
 
 def FeedForwardBackwardGPU(in_feat, grad_out_feat, w1, b1, w2, activation, need_grad_in=True, need_grad_fc1=True,
@@ -4300,31 +4352,7 @@ def FeedForwardBackwardGPU(in_feat, grad_out_feat, w1, b1, w2, activation, need_
     """-> (grad_in, grad_w1, grad_b1, grad_w2, grad_b2), None where not wanted (grad_b1 also without b1; grad_b2 is
     returned whenever fc2's gradients are wanted).  The pre-activation is recomputed from in_feat; the parameter gradients
     are fixed-order sums without atomics, in the dtype of the rows (me_ffn_backward)."""
-    (x, w1, b1, w2, _), n, c, hd, cout = _ffn_operands(in_feat, w1, b1, w2, None, activation)
-    dy = grad_out_feat.detach().to(x.dtype).contiguous()
-    _check(tuple(dy.shape) == (n, cout) and dy.device == x.device, "grad_out_feat must be", (n, cout), "on the device of in_feat")
-    dev = x.device
-
-    def new(*shape, want=True):
-        return torch.empty(shape, dtype=x.dtype, device=dev) if want else None
-    dx = new(n, c, want=need_grad_in)
-    dw1, db1 = new(hd, c, want=need_grad_fc1), new(hd, want=need_grad_fc1 and b1 is not None)
-    dw2, db2 = new(cout, hd, want=need_grad_fc2), new(cout, want=need_grad_fc2)
-    if n == 0:
-        for t in (dw1, db1, dw2, db2):
-            if t is not None:
-                t.zero_()
-        return dx, dw1, db1, dw2, db2
-    if not (need_grad_in or need_grad_fc1 or need_grad_fc2):
-        return dx, dw1, db1, dw2, db2
-    lib = _lib.load()
-    with _on(dev):
-        ws = _workspace(int(lib.me_ffn_workspace_bytes(n, c, hd, cout, x.element_size())), dev)
-        _timed("ffn_backward", dev, lambda: _lib.check(lib.me_ffn_backward(
-            _ptr(x), _ptr(dy), _ptr(w1), _ptr(b1), _ptr(w2), 1 if x.dtype == torch.bfloat16 else 0, n, c, hd, cout,
-            FFN_ACTIVATIONS[activation], int(need_grad_in), int(need_grad_fc1), int(need_grad_fc2), _ptr(dx), _ptr(dw1),
-            _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ws), ws.numel(), _stream(dev))))
-    return dx, dw1, db1, dw2, db2
+    return _mlp_backward(_FFN, in_feat, grad_out_feat, (w1, b1), w2, activation, need_grad_in, need_grad_fc1, need_grad_fc2)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -4354,38 +4382,13 @@ def gated_feed_forward_row_splits(n, c, hd, cout, dtype):
     return int(_lib.load().me_glu_row_splits(n, c, hd, cout, torch.finfo(dtype).bits // 8))
 
 
-def _glu_operands(in_feat, wg, bg, wu, bu, w2, b2, activation):
-    _check(activation in FFN_ACTIVATIONS, "activation must be one of", sorted(FFN_ACTIVATIONS), "not", repr(activation))
-    _check(in_feat.is_cuda, "in_feat must be CUDA (ROCm) — the MI355X path has no CPU implementation")
-    _check(in_feat.dim() == 2 and wg.dim() == 2 and wu.dim() == 2 and w2.dim() == 2, "in_feat, wg, wu and w2 must be 2-D")
-    n, c = int(in_feat.shape[0]), int(in_feat.shape[1])
-    hd, cout = int(wg.shape[0]), int(w2.shape[0])
-    _check(wg.shape[1] == c and tuple(wu.shape) == tuple(wg.shape) and w2.shape[1] == hd, "channel mismatch: in_feat",
-           tuple(in_feat.shape), "wg", tuple(wg.shape), "wu", tuple(wu.shape), "w2", tuple(w2.shape))
-    _check(all(b is None or tuple(b.shape) == (hd,) for b in (bg, bu)), "bg and bu must have", hd, "values")
-    _check(b2 is None or tuple(b2.shape) == (cout,), "b2 must have", cout, "values")
-    for name, t in (("wg", wg), ("bg", bg), ("wu", wu), ("bu", bu), ("w2", w2), ("b2", b2)):
-        _check(t is None or (t.dtype == in_feat.dtype and t.device == in_feat.device), name,
-               "must have the dtype and device of in_feat")
-    _check(gated_feed_forward_supported(c, hd, cout, in_feat.dtype), "widths", (c, hd, cout), "of", in_feat.dtype,
-           "are not served by the gated feed-forward kernels")
-    ops = [t if t is None else t.detach().contiguous() for t in (in_feat, wg, bg, wu, bu, w2, b2)]
-    return ops, n, c, hd, cout
+_GLU = _Mlp((("wg", "bg"), ("wu", "bu")), "glu", gated_feed_forward_supported, "gated feed-forward")
 
 
 def GatedFeedForwardForwardGPU(in_feat, wg, bg, wu, bu, w2, b2, activation):
     """-> out_feat [n, cout] = (act(in_feat wg^T + bg) * (in_feat wu^T + bu)) w2^T + b2 (wg, wu [hd, c], w2 [cout, hd],
     torch.nn.Linear's layouts; all of one dtype, fp32 or bf16).  One launch (me_glu_forward)."""
-    (x, wg, bg, wu, bu, w2, b2), n, c, hd, cout = _glu_operands(in_feat, wg, bg, wu, bu, w2, b2, activation)
-    out = torch.empty((n, cout), dtype=x.dtype, device=x.device)
-    if n == 0:
-        return out
-    lib = _lib.load()
-    with _on(x.device):
-        _timed("glu_forward", x.device, lambda: _lib.check(lib.me_glu_forward(
-            _ptr(x), _ptr(wg), _ptr(bg), _ptr(wu), _ptr(bu), _ptr(w2), _ptr(b2), 1 if x.dtype == torch.bfloat16 else 0, n,
-            c, hd, cout, FFN_ACTIVATIONS[activation], _ptr(out), _stream(x.device))), 4.0 * n * hd * (2 * c + cout) / 2)
-    return out
+    return _mlp_forward(_GLU, in_feat, (wg, bg, wu, bu), w2, b2, activation)
 
 
 def GatedFeedForwardBackwardGPU(in_feat, grad_out_feat, wg, bg, wu, bu, w2, activation, need_grad_in=True,
@@ -4394,33 +4397,8 @@ def GatedFeedForwardBackwardGPU(in_feat, grad_out_feat, wg, bg, wu, bu, w2, acti
     without that bias; grad_b2 is returned whenever fc2's gradients are wanted).  need_grad_fc1 covers both first-layer
     matrices and their biases.  Both pre-activations are recomputed from in_feat; the parameter gradients are fixed-order
     sums without atomics, in the dtype of the rows (me_glu_backward)."""
-    (x, wg, bg, wu, bu, w2, _), n, c, hd, cout = _glu_operands(in_feat, wg, bg, wu, bu, w2, None, activation)
-    dy = grad_out_feat.detach().to(x.dtype).contiguous()
-    _check(tuple(dy.shape) == (n, cout) and dy.device == x.device, "grad_out_feat must be", (n, cout), "on the device of in_feat")
-    dev = x.device
-
-    def new(*shape, want=True):
-        return torch.empty(shape, dtype=x.dtype, device=dev) if want else None
-    dx = new(n, c, want=need_grad_in)
-    dwg, dbg = new(hd, c, want=need_grad_fc1), new(hd, want=need_grad_fc1 and bg is not None)
-    dwu, dbu = new(hd, c, want=need_grad_fc1), new(hd, want=need_grad_fc1 and bu is not None)
-    dw2, db2 = new(cout, hd, want=need_grad_fc2), new(cout, want=need_grad_fc2)
-    grads = (dx, dwg, dbg, dwu, dbu, dw2, db2)
-    if n == 0:
-        for t in grads[1:]:
-            if t is not None:
-                t.zero_()
-        return grads
-    if not (need_grad_in or need_grad_fc1 or need_grad_fc2):
-        return grads
-    lib = _lib.load()
-    with _on(dev):
-        ws = _workspace(int(lib.me_glu_workspace_bytes(n, c, hd, cout, x.element_size())), dev)
-        _timed("glu_backward", dev, lambda: _lib.check(lib.me_glu_backward(
-            _ptr(x), _ptr(dy), _ptr(wg), _ptr(bg), _ptr(wu), _ptr(bu), _ptr(w2), 1 if x.dtype == torch.bfloat16 else 0, n, c,
-            hd, cout, FFN_ACTIVATIONS[activation], int(need_grad_in), int(need_grad_fc1), int(need_grad_fc2),
-            *(_ptr(t) for t in grads), _ptr(ws), ws.numel(), _stream(dev))))
-    return grads
+    return _mlp_backward(_GLU, in_feat, grad_out_feat, (wg, bg, wu, bu), w2, activation, need_grad_in, need_grad_fc1,
+                         need_grad_fc2)
 
 
 # ------------------------------------------------------------------------------------------------

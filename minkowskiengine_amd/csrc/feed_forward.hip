@@ -32,8 +32,6 @@
 // widths are skipped by wave-uniform branches.
 #include "feed_forward.hpp"
 
-#include <algorithm>
-
 namespace me {
 namespace ffn {
 
@@ -319,77 +317,34 @@ __global__ __launch_bounds__(kThreads) void k_ffn_reduce(const float *__restrict
   *dst = (T)s;
 }
 
-// ---- host side ----------------------------------------------------------------------------------------------------------
-template <typename T, int MT, bool BWD> int launch_rows(const RowsArgs<T> &a, hipStream_t stream) {
-  const int64_t lds = rows_lds_bytes((int)sizeof(T), a.c, a.cout, BWD);
-  ME_CHECK(lds <= kLdsBudget, "the weight chunks do not fit into LDS");
-  auto fn = BWD ? &k_ffn_bwd_x<T, MT> : &k_ffn_fwd<T, MT>;
-  if (allow_lds(fn, lds) != 0) return 1;
-  hipLaunchKernelGGL(fn, dim3((unsigned)ceil_div(a.n, kRows)), dim3(kThreads), (size_t)lds, stream, a);
-  ME_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename T, int MT> int launch_w(const WArgs<T> &a, hipStream_t stream) {
-  const int64_t lds = w_lds_bytes((int)sizeof(T), a.c, a.cout);
-  ME_CHECK(lds <= kLdsBudget, "the weight chunks and row images do not fit into LDS");
-  auto fn = &k_ffn_bwd_w<T, MT>;
-  if (allow_lds(fn, lds) != 0) return 1;
-  hipLaunchKernelGGL(fn, dim3((unsigned)(a.hd / 32), (unsigned)a.splits), dim3(kThreads), (size_t)lds, stream, a);
-  ME_LAUNCH_CHECK();
-  return 0;
-}
-
-// MT = 2 | 4 | 8 register tiles for max(c, cout) / 32 (fp32 rows: at most 4)
-#define ME_FFN_DISPATCH(T, width, ...)                                      \
-  do {                                                                      \
-    if ((width) <= 64) { constexpr int MT = 2; return __VA_ARGS__; }        \
-    if ((width) <= 128) { constexpr int MT = 4; return __VA_ARGS__; }       \
-    if constexpr (sizeof(T) == 2) { constexpr int MT = 8; return __VA_ARGS__; } \
-    ME_FAIL("width not served");                                            \
-  } while (0)
-
-template <typename T> int rows_any(const RowsArgs<T> &a, bool bwd, hipStream_t stream) {
-  const int width = std::max(a.c, a.cout);
-  if (bwd) ME_FFN_DISPATCH(T, width, launch_rows<T, MT, true>(a, stream));
-  ME_FFN_DISPATCH(T, width, launch_rows<T, MT, false>(a, stream));
-}
-template <typename T> int w_any(const WArgs<T> &a, hipStream_t stream) {
-  ME_FFN_DISPATCH(T, std::max(a.c, a.cout), launch_w<T, MT>(a, stream));
-}
-
-inline int64_t transposed_bytes(int c, int hd, int cout, int elem) {
-  return align_up(((int64_t)c * hd + (int64_t)hd * cout) * elem, 256);
-}
-
-struct BackwardCall {
-  const void *x, *dy, *w1, *b1, *w2;
-  void *dx, *dw1, *db1, *dw2, *db2, *ws;
-  int64_t n;
-  int c, hd, cout, act;
-  bool need_dx, need_w;
-};
-
-template <typename T> int backward(const BackwardCall &b, hipStream_t stream) {
-  T *w1t = (T *)b.ws, *w2t = w1t + (int64_t)b.c * b.hd;   // W1^T [c, hd], W2^T [hd, cout]
-  float *partial = (float *)((char *)b.ws + transposed_bytes(b.c, b.hd, b.cout, (int)sizeof(T)));
-  if (transpose<T>((const T *)b.w2, w2t, b.cout, b.hd, stream) != 0) return 1;
-  if (b.need_dx) {
-    if (transpose<T>((const T *)b.w1, w1t, b.hd, b.c, stream) != 0) return 1;
-    const RowsArgs<T> a{(const T *)b.x, (const T *)b.dy, (const T *)b.w1, w2t, w1t, (const T *)b.b1, nullptr,
-                        (T *)b.dx, b.n, b.c, b.hd, b.cout, b.act};
-    if (rows_any<T>(a, true, stream) != 0) return 1;
+// ---- host side: the family description of feed_forward.hpp's launch and policy code ---------------------------------------
+struct Plain {
+  static constexpr int NZ = 1, kMaxBf16 = ME_FFN_MAX_WIDTH_BF16, kMaxF32 = ME_FFN_MAX_WIDTH_F32;
+  template <typename T> using Rows = RowsArgs<T>;
+  template <typename T> using Weights = WArgs<T>;
+  template <typename T, int MT> static auto fwd() { return &k_ffn_fwd<T, MT>; }
+  template <typename T, int MT> static auto bwd_x() { return &k_ffn_bwd_x<T, MT>; }
+  template <typename T, int MT> static auto bwd_w() { return &k_ffn_bwd_w<T, MT>; }
+  static int64_t rows_lds(int elem, int c, int cout, bool bwd) { return rows_lds_bytes(elem, c, cout, bwd); }
+  static int64_t w_lds(int elem, int c, int cout) { return w_lds_bytes(elem, c, cout); }
+  static int64_t image(int c, int hd, int cout) { return image_floats(c, hd, cout); }
+  // wt = {W1^T}, w2t: backward (out = dx); null: forward (out = y)
+  template <typename T> static Rows<T> rows(const Call<1> &m, T *const *wt, T *w2t) {
+    if (wt == nullptr)
+      return {(const T *)m.x, nullptr, (const T *)m.w[0], nullptr, (const T *)m.w2, (const T *)m.b[0], (const T *)m.b2,
+              (T *)m.out, m.n, m.c, m.hd, m.cout, m.act};
+    return {(const T *)m.x, (const T *)m.dy, (const T *)m.w[0], w2t, wt[0], (const T *)m.b[0], nullptr, (T *)m.out, m.n,
+            m.c, m.hd, m.cout, m.act};
   }
-  if (!b.need_w) return 0;
-  const int splits = me_ffn_row_splits(b.n, b.c, b.hd, b.cout, (int)sizeof(T));
-  const WArgs<T> a{(const T *)b.x, (const T *)b.dy, (const T *)b.w1, w2t, (const T *)b.b1, partial, b.n, b.c, b.hd,
-                   b.cout, b.act, splits};
-  if (w_any<T>(a, stream) != 0) return 1;
-  hipLaunchKernelGGL(k_ffn_reduce<T>, dim3((unsigned)ceil_div(image_floats(b.c, b.hd, b.cout), kThreads)), dim3(kThreads),
-                     0, stream, partial, 4 * splits, b.c, b.hd, b.cout, (T *)b.dw1, (T *)b.db1, (T *)b.dw2, (T *)b.db2);
-  ME_LAUNCH_CHECK();
-  return 0;
-}
+  template <typename T> static Weights<T> weights(const Call<1> &m, T *w2t, float *partial, int splits) {
+    return {(const T *)m.x, (const T *)m.dy, (const T *)m.w[0], w2t, (const T *)m.b[0], partial, m.n, m.c, m.hd, m.cout,
+            m.act, splits};
+  }
+  template <typename T> static void reduce(const Call<1> &m, const float *partial, int slots, hipStream_t stream) {
+    hipLaunchKernelGGL(k_ffn_reduce<T>, dim3((unsigned)ceil_div(image_floats(m.c, m.hd, m.cout), kThreads)), dim3(kThreads),
+                       0, stream, partial, slots, m.c, m.hd, m.cout, (T *)m.dw[0], (T *)m.db[0], (T *)m.dw2, (T *)m.db2);
+  }
+};
 
 }  // namespace ffn
 }  // namespace me
@@ -397,53 +352,32 @@ template <typename T> int backward(const BackwardCall &b, hipStream_t stream) {
 using namespace me;
 using namespace me::ffn;
 
-#define ME_FFN_CHECK_SHAPE(n, c, hd, cout, elem, act)                                                                \
-  ME_CHECK(n >= 0 && n < (1ll << 31), "the row count must fit in int32");                                            \
-  ME_CHECK(me_ffn_supported(c, hd, cout, elem) != 0,                                                                 \
-           "widths not served: c and cout multiples of 32 up to ME_FFN_MAX_WIDTH_*, hd a multiple of 32");           \
-  ME_CHECK(act >= ME_FFN_GELU && act <= ME_FFN_SILU, "unknown activation")
-
 extern "C" {
 
 int32_t me_ffn_supported(int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes) {
-  if (elem_bytes != 2 && elem_bytes != 4) return 0;
-  const int max_w = elem_bytes == 2 ? ME_FFN_MAX_WIDTH_BF16 : ME_FFN_MAX_WIDTH_F32;
-  return (c >= 32 && c % 32 == 0 && c <= max_w && cout >= 32 && cout % 32 == 0 && cout <= max_w && hd >= 32 &&
-          hd % 32 == 0) ? 1 : 0;
+  return supported<Plain>(c, hd, cout, elem_bytes);
 }
 
 int32_t me_ffn_row_splits(int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes) {
-  if (n < 1 || me_ffn_supported(c, hd, cout, elem_bytes) == 0) return 1;
-  const int64_t blocks = ceil_div(n, kRows);
-  const int64_t fill = ceil_div(kTargetGroups, hd / 32);
-  // four partial images per split; together no larger than x and dy
-  const int64_t cap = n * (c + cout) * elem_bytes / (16 * image_floats(c, hd, cout));
-  const int64_t want = std::min(blocks, std::max<int64_t>(4, std::min(fill, cap)));
-  return (int32_t)ceil_div(blocks, ceil_div(blocks, want));   // no empty split
+  return row_splits<Plain>(n, c, hd, cout, elem_bytes);
 }
 
 int64_t me_ffn_workspace_bytes(int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes) {
-  if (me_ffn_supported(c, hd, cout, elem_bytes) == 0) return 0;
-  return transposed_bytes(c, hd, cout, elem_bytes) +
-         4 * (int64_t)me_ffn_row_splits(n, c, hd, cout, elem_bytes) * image_floats(c, hd, cout) * (int64_t)sizeof(float);
+  return workspace_bytes<Plain>(n, c, hd, cout, elem_bytes);
 }
 
 int me_ffn_forward(const void *x_dev, const void *w1_dev, const void *b1_dev, const void *w2_dev, const void *b2_dev,
                    int32_t is_bf16, int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t activation, void *y_dev,
                    void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  ME_FFN_CHECK_SHAPE(n, c, hd, cout, is_bf16 ? 2 : 4, activation);
+  ME_FFN_CHECK_SHAPE(Plain, "ME_FFN_MAX_WIDTH", n, c, hd, cout, is_bf16 ? 2 : 4, activation);
   if (n == 0) return 0;
   ME_CHECK(x_dev != nullptr && w1_dev != nullptr && w2_dev != nullptr && y_dev != nullptr, "x, w1, w2 and y must be given");
   ME_CHECK(aligned16({x_dev, w1_dev, w2_dev, y_dev}), "x, w1, w2 and y must be aligned to 16 bytes");
-  if (is_bf16) {
-    const RowsArgs<__bf16> a{(const __bf16 *)x_dev, nullptr, (const __bf16 *)w1_dev, nullptr, (const __bf16 *)w2_dev,
-                             (const __bf16 *)b1_dev, (const __bf16 *)b2_dev, (__bf16 *)y_dev, n, c, hd, cout, activation};
-    return rows_any<__bf16>(a, false, stream);
-  }
-  const RowsArgs<float> a{(const float *)x_dev, nullptr, (const float *)w1_dev, nullptr, (const float *)w2_dev,
-                          (const float *)b1_dev, (const float *)b2_dev, (float *)y_dev, n, c, hd, cout, activation};
-  return rows_any<float>(a, false, stream);
+  Call<1> m{};
+  m.x = x_dev, m.w[0] = w1_dev, m.b[0] = b1_dev, m.w2 = w2_dev, m.b2 = b2_dev, m.out = y_dev;
+  m.n = n, m.c = c, m.hd = hd, m.cout = cout, m.act = activation;
+  return is_bf16 ? forward<Plain, __bf16>(m, stream) : forward<Plain, float>(m, stream);
 }
 
 int me_ffn_backward(const void *x_dev, const void *dy_dev, const void *w1_dev, const void *b1_dev, const void *w2_dev,
@@ -452,7 +386,7 @@ int me_ffn_backward(const void *x_dev, const void *dy_dev, const void *w1_dev, c
                     void *dw2_dev, void *db2_dev, void *workspace_dev, int64_t workspace_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int elem = is_bf16 ? 2 : 4;
-  ME_FFN_CHECK_SHAPE(n, c, hd, cout, elem, activation);
+  ME_FFN_CHECK_SHAPE(Plain, "ME_FFN_MAX_WIDTH", n, c, hd, cout, elem, activation);
   ME_CHECK(!need_dx || dx_dev != nullptr, "need_dx without dx");
   ME_CHECK(!need_fc1 || dw1_dev != nullptr, "need_fc1 without dw1");
   ME_CHECK(!need_fc2 || dw2_dev != nullptr, "need_fc2 without dw2");
@@ -464,11 +398,12 @@ int me_ffn_backward(const void *x_dev, const void *dy_dev, const void *w1_dev, c
   ME_CHECK(w1_dev != nullptr && w2_dev != nullptr && (n == 0 || (x_dev != nullptr && dy_dev != nullptr)),
            "x, dy, w1 and w2 must be given");
   ME_CHECK(aligned16({x_dev, dy_dev, w1_dev, w2_dev, dx_dev, workspace_dev}), "the operands must be aligned to 16 bytes");
-  const BackwardCall b{x_dev, dy_dev, w1_dev, b1_dev, w2_dev, dx_dev,
-                       need_fc1 ? dw1_dev : nullptr, need_fc1 ? db1_dev : nullptr, need_fc2 ? dw2_dev : nullptr,
-                       need_fc2 ? db2_dev : nullptr, workspace_dev, n, c, hd, cout, activation, need_dx != 0 && n > 0,
-                       need_w};
-  return is_bf16 ? backward<__bf16>(b, stream) : backward<float>(b, stream);
+  Call<1> m{};
+  m.x = x_dev, m.dy = dy_dev, m.w[0] = w1_dev, m.b[0] = b1_dev, m.w2 = w2_dev, m.out = dx_dev, m.ws = workspace_dev;
+  if (need_fc1) m.dw[0] = dw1_dev, m.db[0] = db1_dev;
+  if (need_fc2) m.dw2 = dw2_dev, m.db2 = db2_dev;
+  m.n = n, m.c = c, m.hd = hd, m.cout = cout, m.act = activation, m.need_dx = need_dx != 0 && n > 0, m.need_w = need_w;
+  return is_bf16 ? backward<Plain, __bf16>(m, stream) : backward<Plain, float>(m, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Fragment helpers of the fused MLP kernels for gfx950 (feed_forward.hip, gated_feed_forward.hip): the 32x32 MFMA shape of
 // both dtypes, operand fragments and their loads from LDS, the accumulator-as-operand identity, the activations, the
-// 16-byte staging of weight blocks and the weight transposition.
+// 16-byte staging of weight blocks and the weight transposition; then, host only, the one copy of the launch and policy code
+// of both units, which each unit instantiates with a description of its family.
 //
 // One 32x32 MFMA shape serves both dtypes: v_mfma_f32_32x32x16_bf16 on bf16 rows, the exact v_mfma_f32_32x32x2_f32 on fp32
 // rows; C/D lane map: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  The 16 accumulator registers of a
@@ -10,6 +11,7 @@
 #pragma once
 #include "common.hpp"
 
+#include <algorithm>
 #include <initializer_list>
 
 namespace me {
@@ -184,6 +186,125 @@ inline bool aligned16(std::initializer_list<const void *> ps) {
   for (const void *p : ps)
     if (((uintptr_t)p & 15) != 0) return false;
   return true;
+}
+
+// ---- launch and policy code of both MLPs (host only: nothing below reaches a kernel) --------------------------------------
+// A unit describes its family by a struct F:
+//   NZ                      first-layer (weight, bias) pairs: 1 plain, 2 gated (gate, up)
+//   kMaxBf16, kMaxF32       the widest rows it instantiates kernels for
+//   Rows<T>, Weights<T>     the argument structs of its row-stationary and weight-gradient kernels
+//   fwd<T, MT>(), bwd_x<T, MT>(), bwd_w<T, MT>()     its __global__ symbols
+//   rows_lds, w_lds, image  its LDS sizes and the floats of one partial image
+//   rows<T>(call, wt, w2t), weights<T>(call, w2t, partial, splits), reduce<T>(call, partial, slots, stream)
+//                           fill the argument structs from a Call and launch its reduce kernel
+
+// the operands of an entry point, checked; w / b / dw / db: the first layer's pairs in the family's order.  forward reads
+// x, w, b, w2, b2 and out = y; backward x, dy, w, b, w2, out = dx and what follows
+template <int NZ> struct Call {
+  const void *x, *dy, *w[NZ], *b[NZ], *w2, *b2;
+  void *out, *dw[NZ], *db[NZ], *dw2, *db2, *ws;
+  int64_t n;
+  int c, hd, cout, act;
+  bool need_dx, need_w;
+};
+
+template <typename F, typename T, int MT, bool BWD> int launch_rows(const typename F::template Rows<T> &a, hipStream_t stream) {
+  const int64_t lds = F::rows_lds((int)sizeof(T), a.c, a.cout, BWD);
+  ME_CHECK(lds <= kLdsBudget, "the weight chunks do not fit into LDS");
+  auto fn = BWD ? F::template bwd_x<T, MT>() : F::template fwd<T, MT>();
+  if (allow_lds(fn, lds) != 0) return 1;
+  hipLaunchKernelGGL(fn, dim3((unsigned)ceil_div(a.n, kRows)), dim3(kThreads), (size_t)lds, stream, a);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename F, typename T, int MT> int launch_w(const typename F::template Weights<T> &a, hipStream_t stream) {
+  const int64_t lds = F::w_lds((int)sizeof(T), a.c, a.cout);
+  ME_CHECK(lds <= kLdsBudget, "the weight chunks and row images do not fit into LDS");
+  auto fn = F::template bwd_w<T, MT>();
+  if (allow_lds(fn, lds) != 0) return 1;
+  hipLaunchKernelGGL(fn, dim3((unsigned)(a.hd / 32), (unsigned)a.splits), dim3(kThreads), (size_t)lds, stream, a);
+  ME_LAUNCH_CHECK();
+  return 0;
+}
+
+// MT = 2 | 4 | 8 register tiles for max(c, cout) / 32, up to top = the family's widest rows of the dtype / 32
+#define ME_FFN_DISPATCH(top, width, ...)                                                             \
+  do {                                                                                               \
+    if ((width) <= 64) { constexpr int MT = 2; return __VA_ARGS__; }                                 \
+    if constexpr ((top) >= 4) { if ((width) <= 128) { constexpr int MT = 4; return __VA_ARGS__; } }  \
+    if constexpr ((top) >= 8) { constexpr int MT = 8; return __VA_ARGS__; }                          \
+    ME_FAIL("width not served");                                                                     \
+  } while (0)
+
+template <typename F, typename T> int rows_any(const typename F::template Rows<T> &a, bool bwd, hipStream_t stream) {
+  constexpr int top = (sizeof(T) == 2 ? F::kMaxBf16 : F::kMaxF32) / 32;
+  const int width = std::max(a.c, a.cout);
+  if (bwd) ME_FFN_DISPATCH(top, width, launch_rows<F, T, MT, true>(a, stream));
+  ME_FFN_DISPATCH(top, width, launch_rows<F, T, MT, false>(a, stream));
+}
+template <typename F, typename T> int w_any(const typename F::template Weights<T> &a, hipStream_t stream) {
+  constexpr int top = (sizeof(T) == 2 ? F::kMaxBf16 : F::kMaxF32) / 32;
+  ME_FFN_DISPATCH(top, std::max(a.c, a.cout), launch_w<F, T, MT>(a, stream));
+}
+
+template <typename F> int32_t supported(int c, int hd, int cout, int elem) {
+  if (elem != 2 && elem != 4) return 0;
+  const int max_w = elem == 2 ? F::kMaxBf16 : F::kMaxF32;
+  return (c >= 32 && c % 32 == 0 && c <= max_w && cout >= 32 && cout % 32 == 0 && cout <= max_w && hd >= 32 &&
+          hd % 32 == 0) ? 1 : 0;
+}
+
+template <typename F> int32_t row_splits(int64_t n, int c, int hd, int cout, int elem) {
+  if (n < 1 || supported<F>(c, hd, cout, elem) == 0) return 1;
+  const int64_t blocks = ceil_div(n, kRows);
+  const int64_t fill = ceil_div(kTargetGroups, hd / 32);
+  // four partial images per split; together no larger than x and dy
+  const int64_t cap = n * (c + cout) * elem / (16 * F::image(c, hd, cout));
+  const int64_t want = std::min(blocks, std::max<int64_t>(4, std::min(fill, cap)));
+  return (int32_t)ceil_div(blocks, ceil_div(blocks, want));   // no empty split
+}
+
+// the workspace of a backward call: w[i]^T [c, hd] for every i, W2^T [hd, cout], then the partial images
+template <typename F> int64_t transposed_bytes(int c, int hd, int cout, int elem) {
+  return align_up((F::NZ * (int64_t)c * hd + (int64_t)hd * cout) * elem, 256);
+}
+template <typename F> int64_t workspace_bytes(int64_t n, int c, int hd, int cout, int elem) {
+  if (supported<F>(c, hd, cout, elem) == 0) return 0;
+  return transposed_bytes<F>(c, hd, cout, elem) +
+         4 * (int64_t)row_splits<F>(n, c, hd, cout, elem) * F::image(c, hd, cout) * (int64_t)sizeof(float);
+}
+
+// max_name: "ME_FFN_MAX_WIDTH" | "ME_GLU_MAX_WIDTH"
+#define ME_FFN_CHECK_SHAPE(F, max_name, n, c, hd, cout, elem, act)                                                    \
+  ME_CHECK(n >= 0 && n < (1ll << 31), "the row count must fit in int32");                                            \
+  ME_CHECK(supported<F>(c, hd, cout, elem) != 0,                                                                     \
+           "widths not served: c and cout multiples of 32 up to " max_name "_*, hd a multiple of 32");               \
+  ME_CHECK(act >= ME_FFN_GELU && act <= ME_FFN_SILU, "unknown activation")
+
+template <typename F, typename T> int forward(const Call<F::NZ> &m, hipStream_t stream) {
+  return rows_any<F, T>(F::template rows<T>(m, nullptr, nullptr), false, stream);
+}
+
+// the transposes, the input gradient, the weight-gradient kernel and its reduce
+template <typename F, typename T> int backward(const Call<F::NZ> &m, hipStream_t stream) {
+  const int64_t ch = (int64_t)m.c * m.hd;
+  T *wt[F::NZ], *w2t = (T *)m.ws + F::NZ * ch;   // w[i]^T [c, hd], W2^T [hd, cout]
+  float *partial = (float *)((char *)m.ws + transposed_bytes<F>(m.c, m.hd, m.cout, (int)sizeof(T)));
+  if (transpose<T>((const T *)m.w2, w2t, m.cout, m.hd, stream) != 0) return 1;
+  if (m.need_dx) {
+    for (int i = 0; i < F::NZ; ++i) {
+      wt[i] = (T *)m.ws + i * ch;
+      if (transpose<T>((const T *)m.w[i], wt[i], m.hd, m.c, stream) != 0) return 1;
+    }
+    if (rows_any<F, T>(F::template rows<T>(m, wt, w2t), true, stream) != 0) return 1;
+  }
+  if (!m.need_w) return 0;
+  const int splits = row_splits<F>(m.n, m.c, m.hd, m.cout, (int)sizeof(T));
+  if (w_any<F, T>(F::template weights<T>(m, w2t, partial, splits), stream) != 0) return 1;
+  F::template reduce<T>(m, partial, 4 * splits, stream);
+  ME_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace ffn

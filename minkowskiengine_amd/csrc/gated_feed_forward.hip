@@ -27,8 +27,6 @@
 // instantiation per (dtype, MT) with MT = 2 | 4 (bf16) or 2 (fp32) register tiles for max(C, Cout) / 32.
 #include "feed_forward.hpp"
 
-#include <algorithm>
-
 namespace me {
 namespace glu {
 
@@ -364,92 +362,34 @@ __global__ __launch_bounds__(kThreads) void k_glu_reduce(const float *__restrict
   base[e - first] = (T)s;
 }
 
-// ---- host side ----------------------------------------------------------------------------------------------------------
-template <typename T, int MT, bool BWD> int launch_rows(const RowsArgs<T> &a, hipStream_t stream) {
-  const int64_t lds = rows_lds_bytes((int)sizeof(T), a.c, a.cout, BWD);
-  ME_CHECK(lds <= kLdsBudget, "the weight chunks do not fit into LDS");
-  auto fn = BWD ? &k_glu_bwd_x<T, MT> : &k_glu_fwd<T, MT>;
-  if (allow_lds(fn, lds) != 0) return 1;
-  hipLaunchKernelGGL(fn, dim3((unsigned)ceil_div(a.n, kRows)), dim3(kThreads), (size_t)lds, stream, a);
-  ME_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename T, int MT> int launch_w(const WArgs<T> &a, hipStream_t stream) {
-  const int64_t lds = w_lds_bytes((int)sizeof(T), a.c, a.cout);
-  ME_CHECK(lds <= kLdsBudget, "the weight chunks and row images do not fit into LDS");
-  auto fn = &k_glu_bwd_w<T, MT>;
-  if (allow_lds(fn, lds) != 0) return 1;
-  hipLaunchKernelGGL(fn, dim3((unsigned)(a.hd / 32), (unsigned)a.splits), dim3(kThreads), (size_t)lds, stream, a);
-  ME_LAUNCH_CHECK();
-  return 0;
-}
-
-// MT = 2 | 4 register tiles for max(c, cout) / 32 (fp32 rows: 2)
-#define ME_GLU_DISPATCH(T, width, ...)                                      \
-  do {                                                                      \
-    if ((width) <= 64) { constexpr int MT = 2; return __VA_ARGS__; }        \
-    if constexpr (sizeof(T) == 2) { constexpr int MT = 4; return __VA_ARGS__; } \
-    ME_FAIL("width not served");                                            \
-  } while (0)
-
-template <typename T> int rows_any(const RowsArgs<T> &a, bool bwd, hipStream_t stream) {
-  const int width = std::max(a.c, a.cout);
-  if (bwd) ME_GLU_DISPATCH(T, width, launch_rows<T, MT, true>(a, stream));
-  ME_GLU_DISPATCH(T, width, launch_rows<T, MT, false>(a, stream));
-}
-template <typename T> int w_any(const WArgs<T> &a, hipStream_t stream) {
-  ME_GLU_DISPATCH(T, std::max(a.c, a.cout), launch_w<T, MT>(a, stream));
-}
-
-inline int64_t transposed_bytes(int c, int hd, int cout, int elem) {
-  return align_up((2 * (int64_t)c * hd + (int64_t)hd * cout) * elem, 256);
-}
-
-struct ForwardCall {
-  const void *x, *wg, *bg, *wu, *bu, *w2, *b2;
-  void *y;
-  int64_t n;
-  int c, hd, cout, act;
-};
-
-template <typename T> int forward(const ForwardCall &f, hipStream_t stream) {
-  const RowsArgs<T> a{(const T *)f.x, nullptr, (const T *)f.wg, (const T *)f.wu, (const T *)f.w2, nullptr, nullptr, nullptr,
-                      (const T *)f.bg, (const T *)f.bu, (const T *)f.b2, (T *)f.y, f.n, f.c, f.hd, f.cout, f.act};
-  return rows_any<T>(a, false, stream);
-}
-
-struct BackwardCall {
-  const void *x, *dy, *wg, *bg, *wu, *bu, *w2;
-  void *dx, *dwg, *dbg, *dwu, *dbu, *dw2, *db2, *ws;
-  int64_t n;
-  int c, hd, cout, act;
-  bool need_dx, need_w;
-};
-
-template <typename T> int backward(const BackwardCall &b, hipStream_t stream) {
-  const int64_t ch = (int64_t)b.c * b.hd;
-  T *wgt = (T *)b.ws, *wut = wgt + ch, *w2t = wut + ch;   // Wg^T, Wu^T [c, hd], W2^T [hd, cout]
-  float *partial = (float *)((char *)b.ws + transposed_bytes(b.c, b.hd, b.cout, (int)sizeof(T)));
-  if (transpose<T>((const T *)b.w2, w2t, b.cout, b.hd, stream) != 0) return 1;
-  if (b.need_dx) {
-    if (transpose<T>((const T *)b.wg, wgt, b.hd, b.c, stream) != 0) return 1;
-    if (transpose<T>((const T *)b.wu, wut, b.hd, b.c, stream) != 0) return 1;
-    const RowsArgs<T> a{(const T *)b.x, (const T *)b.dy, (const T *)b.wg, (const T *)b.wu, nullptr, w2t, wgt, wut,
-                        (const T *)b.bg, (const T *)b.bu, nullptr, (T *)b.dx, b.n, b.c, b.hd, b.cout, b.act};
-    if (rows_any<T>(a, true, stream) != 0) return 1;
+// ---- host side: the family description of feed_forward.hpp's launch and policy code ---------------------------------------
+struct Gated {
+  static constexpr int NZ = 2, kMaxBf16 = ME_GLU_MAX_WIDTH_BF16, kMaxF32 = ME_GLU_MAX_WIDTH_F32;
+  template <typename T> using Rows = RowsArgs<T>;
+  template <typename T> using Weights = WArgs<T>;
+  template <typename T, int MT> static auto fwd() { return &k_glu_fwd<T, MT>; }
+  template <typename T, int MT> static auto bwd_x() { return &k_glu_bwd_x<T, MT>; }
+  template <typename T, int MT> static auto bwd_w() { return &k_glu_bwd_w<T, MT>; }
+  static int64_t rows_lds(int elem, int c, int cout, bool bwd) { return rows_lds_bytes(elem, c, cout, bwd); }
+  static int64_t w_lds(int elem, int c, int cout) { return w_lds_bytes(elem, c, cout); }
+  static int64_t image(int c, int hd, int cout) { return image_floats(c, hd, cout); }
+  // wt = {Wg^T, Wu^T}, w2t: backward (out = dx); null: forward (out = y)
+  template <typename T> static Rows<T> rows(const Call<2> &m, T *const *wt, T *w2t) {
+    const bool bwd = wt != nullptr;
+    return {(const T *)m.x, bwd ? (const T *)m.dy : nullptr, (const T *)m.w[0], (const T *)m.w[1],
+            bwd ? nullptr : (const T *)m.w2, w2t, bwd ? wt[0] : nullptr, bwd ? wt[1] : nullptr, (const T *)m.b[0],
+            (const T *)m.b[1], bwd ? nullptr : (const T *)m.b2, (T *)m.out, m.n, m.c, m.hd, m.cout, m.act};
   }
-  if (!b.need_w) return 0;
-  const int splits = me_glu_row_splits(b.n, b.c, b.hd, b.cout, (int)sizeof(T));
-  const WArgs<T> a{(const T *)b.x, (const T *)b.dy, (const T *)b.wg, (const T *)b.wu, w2t, (const T *)b.bg,
-                   (const T *)b.bu, partial, b.n, b.c, b.hd, b.cout, b.act, splits};
-  if (w_any<T>(a, stream) != 0) return 1;
-  const Grads<T> g{(T *)b.dwg, (T *)b.dwu, (T *)b.dw2, (T *)b.dbg, (T *)b.dbu, (T *)b.db2};
-  hipLaunchKernelGGL(k_glu_reduce<T>, dim3((unsigned)ceil_div(image_floats(b.c, b.hd, b.cout), kThreads)), dim3(kThreads),
-                     0, stream, partial, 4 * splits, b.c, b.hd, b.cout, g);
-  ME_LAUNCH_CHECK();
-  return 0;
-}
+  template <typename T> static Weights<T> weights(const Call<2> &m, T *w2t, float *partial, int splits) {
+    return {(const T *)m.x, (const T *)m.dy, (const T *)m.w[0], (const T *)m.w[1], w2t, (const T *)m.b[0],
+            (const T *)m.b[1], partial, m.n, m.c, m.hd, m.cout, m.act, splits};
+  }
+  template <typename T> static void reduce(const Call<2> &m, const float *partial, int slots, hipStream_t stream) {
+    const Grads<T> g{(T *)m.dw[0], (T *)m.dw[1], (T *)m.dw2, (T *)m.db[0], (T *)m.db[1], (T *)m.db2};
+    hipLaunchKernelGGL(k_glu_reduce<T>, dim3((unsigned)ceil_div(image_floats(m.c, m.hd, m.cout), kThreads)), dim3(kThreads),
+                       0, stream, partial, slots, m.c, m.hd, m.cout, g);
+  }
+};
 
 }  // namespace glu
 }  // namespace me
@@ -457,48 +397,33 @@ template <typename T> int backward(const BackwardCall &b, hipStream_t stream) {
 using namespace me;
 using namespace me::glu;
 
-#define ME_GLU_CHECK_SHAPE(n, c, hd, cout, elem, act)                                                                \
-  ME_CHECK(n >= 0 && n < (1ll << 31), "the row count must fit in int32");                                            \
-  ME_CHECK(me_glu_supported(c, hd, cout, elem) != 0,                                                                 \
-           "widths not served: c and cout multiples of 32 up to ME_GLU_MAX_WIDTH_*, hd a multiple of 32");           \
-  ME_CHECK(act >= ME_FFN_GELU && act <= ME_FFN_SILU, "unknown activation")
-
 extern "C" {
 
 int32_t me_glu_supported(int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes) {
-  if (elem_bytes != 2 && elem_bytes != 4) return 0;
-  const int max_w = elem_bytes == 2 ? ME_GLU_MAX_WIDTH_BF16 : ME_GLU_MAX_WIDTH_F32;
-  return (c >= 32 && c % 32 == 0 && c <= max_w && cout >= 32 && cout % 32 == 0 && cout <= max_w && hd >= 32 &&
-          hd % 32 == 0) ? 1 : 0;
+  return supported<Gated>(c, hd, cout, elem_bytes);
 }
 
 int32_t me_glu_row_splits(int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes) {
-  if (n < 1 || me_glu_supported(c, hd, cout, elem_bytes) == 0) return 1;
-  const int64_t blocks = ceil_div(n, kRows);
-  const int64_t fill = ceil_div(kTargetGroups, hd / 32);
-  // four partial images per split; together no larger than x and dy
-  const int64_t cap = n * (c + cout) * elem_bytes / (16 * image_floats(c, hd, cout));
-  const int64_t want = std::min(blocks, std::max<int64_t>(4, std::min(fill, cap)));
-  return (int32_t)ceil_div(blocks, ceil_div(blocks, want));   // no empty split
+  return row_splits<Gated>(n, c, hd, cout, elem_bytes);
 }
 
 int64_t me_glu_workspace_bytes(int64_t n, int32_t c, int32_t hd, int32_t cout, int32_t elem_bytes) {
-  if (me_glu_supported(c, hd, cout, elem_bytes) == 0) return 0;
-  return transposed_bytes(c, hd, cout, elem_bytes) +
-         4 * (int64_t)me_glu_row_splits(n, c, hd, cout, elem_bytes) * image_floats(c, hd, cout) * (int64_t)sizeof(float);
+  return workspace_bytes<Gated>(n, c, hd, cout, elem_bytes);
 }
 
 int me_glu_forward(const void *x_dev, const void *wg_dev, const void *bg_dev, const void *wu_dev, const void *bu_dev,
                    const void *w2_dev, const void *b2_dev, int32_t is_bf16, int64_t n, int32_t c, int32_t hd,
                    int32_t cout, int32_t activation, void *y_dev, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  ME_GLU_CHECK_SHAPE(n, c, hd, cout, is_bf16 ? 2 : 4, activation);
+  ME_FFN_CHECK_SHAPE(Gated, "ME_GLU_MAX_WIDTH", n, c, hd, cout, is_bf16 ? 2 : 4, activation);
   if (n == 0) return 0;
   ME_CHECK(x_dev != nullptr && wg_dev != nullptr && wu_dev != nullptr && w2_dev != nullptr && y_dev != nullptr,
            "x, wg, wu, w2 and y must be given");
   ME_CHECK(aligned16({x_dev, wg_dev, wu_dev, w2_dev, y_dev}), "x, wg, wu, w2 and y must be aligned to 16 bytes");
-  const ForwardCall f{x_dev, wg_dev, bg_dev, wu_dev, bu_dev, w2_dev, b2_dev, y_dev, n, c, hd, cout, activation};
-  return is_bf16 ? forward<__bf16>(f, stream) : forward<float>(f, stream);
+  Call<2> m{};
+  m.x = x_dev, m.w[0] = wg_dev, m.b[0] = bg_dev, m.w[1] = wu_dev, m.b[1] = bu_dev, m.w2 = w2_dev, m.b2 = b2_dev;
+  m.out = y_dev, m.n = n, m.c = c, m.hd = hd, m.cout = cout, m.act = activation;
+  return is_bf16 ? forward<Gated, __bf16>(m, stream) : forward<Gated, float>(m, stream);
 }
 
 int me_glu_backward(const void *x_dev, const void *dy_dev, const void *wg_dev, const void *bg_dev, const void *wu_dev,
@@ -508,7 +433,7 @@ int me_glu_backward(const void *x_dev, const void *dy_dev, const void *wg_dev, c
                     void *workspace_dev, int64_t workspace_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int elem = is_bf16 ? 2 : 4;
-  ME_GLU_CHECK_SHAPE(n, c, hd, cout, elem, activation);
+  ME_FFN_CHECK_SHAPE(Gated, "ME_GLU_MAX_WIDTH", n, c, hd, cout, elem, activation);
   ME_CHECK(!need_dx || dx_dev != nullptr, "need_dx without dx");
   ME_CHECK(!need_fc1 || (dwg_dev != nullptr && dwu_dev != nullptr), "need_fc1 without dwg and dwu");
   ME_CHECK(!need_fc2 || dw2_dev != nullptr, "need_fc2 without dw2");
@@ -521,11 +446,13 @@ int me_glu_backward(const void *x_dev, const void *dy_dev, const void *wg_dev, c
            "x, dy, wg, wu and w2 must be given");
   ME_CHECK(aligned16({x_dev, dy_dev, wg_dev, wu_dev, w2_dev, dx_dev, workspace_dev}),
            "the operands must be aligned to 16 bytes");
-  const BackwardCall b{x_dev, dy_dev, wg_dev, bg_dev, wu_dev, bu_dev, w2_dev, dx_dev,
-                       need_fc1 ? dwg_dev : nullptr, need_fc1 ? dbg_dev : nullptr, need_fc1 ? dwu_dev : nullptr,
-                       need_fc1 ? dbu_dev : nullptr, need_fc2 ? dw2_dev : nullptr, need_fc2 ? db2_dev : nullptr,
-                       workspace_dev, n, c, hd, cout, activation, need_dx != 0 && n > 0, need_w};
-  return is_bf16 ? backward<__bf16>(b, stream) : backward<float>(b, stream);
+  Call<2> m{};
+  m.x = x_dev, m.dy = dy_dev, m.w[0] = wg_dev, m.b[0] = bg_dev, m.w[1] = wu_dev, m.b[1] = bu_dev, m.w2 = w2_dev;
+  m.out = dx_dev, m.ws = workspace_dev;
+  if (need_fc1) m.dw[0] = dwg_dev, m.db[0] = dbg_dev, m.dw[1] = dwu_dev, m.db[1] = dbu_dev;
+  if (need_fc2) m.dw2 = dw2_dev, m.db2 = db2_dev;
+  m.n = n, m.c = c, m.hd = hd, m.cout = cout, m.act = activation, m.need_dx = need_dx != 0 && n > 0, m.need_w = need_w;
+  return is_bf16 ? backward<Gated, __bf16>(m, stream) : backward<Gated, float>(m, stream);
 }
 
 }  // extern "C"

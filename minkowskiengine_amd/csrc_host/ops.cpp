@@ -1886,138 +1886,130 @@ static int ffn_activation(const std::string &activation) {
   return -1;
 }
 
-static void ffn_check(const Tensor &x, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2) {
+// what tells one fused MLP from the other
+struct Mlp {
+  int pairs;                                 // first-layer (weight, bias) pairs: 1 plain, 2 gated (gate, up)
+  const char *weights, *biases, *params;     // the names in the messages: first-layer weights, biases, every parameter
+  const char *kernels;                       // "... are not served by the <kernels> kernels"
+  int32_t (*supported)(int32_t, int32_t, int32_t, int32_t);
+  int64_t (*workspace_bytes)(int64_t, int32_t, int32_t, int32_t, int32_t);
+};
+static const Mlp kFfn = {1, "w1", "b1", "w1, b1, w2 and b2", "feed-forward", me_ffn_supported, me_ffn_workspace_bytes};
+static const Mlp kGlu = {2, "wg, wu", "bg and bu", "wg, bg, wu, bu, w2 and b2", "gated feed-forward", me_glu_supported,
+                         me_glu_workspace_bytes};
+
+// the operands of a call, checked, detached and contiguous (an undefined one stays undefined); first: w, b per pair
+struct MlpOperands {
+  Tensor x, w2, b2;
+  std::vector<Tensor> first;
+  int64_t n, c, hd, cout, bf16;
+};
+
+static MlpOperands mlp_operands(const Mlp &op, const Tensor &x, const std::vector<Tensor> &first, const Tensor &w2,
+                                const Tensor &b2) {
+  const std::string weights = op.weights;
+  const Tensor &w = first[0];
+  bool two_d = x.dim() == 2 && w2.dim() == 2, alike = true, bias_ok = true;
+  for (int i = 0; i < op.pairs; i++) {
+    const Tensor &wi = first[2 * i], &bi = first[2 * i + 1];
+    two_d = two_d && wi.dim() == 2;
+    alike = alike && two_d && wi.sizes() == w.sizes();
+    bias_ok = bias_ok && two_d && (!bi.defined() || (bi.dim() == 1 && bi.size(0) == w.size(0)));
+  }
   check(x.is_cuda(), "in_feat must be CUDA (ROCm) — the MI355X path has no CPU implementation");
-  check(x.dim() == 2 && w1.dim() == 2 && w2.dim() == 2, "in_feat, w1 and w2 must be 2-D");
-  check(w1.size(1) == x.size(1) && w2.size(1) == w1.size(0), "channel mismatch between in_feat, w1 and w2");
-  check(!b1.defined() || (b1.dim() == 1 && b1.size(0) == w1.size(0)), "b1 must have one value per hidden unit");
+  check(two_d, "in_feat, " + weights + " and w2 must be 2-D");
+  check(alike && w.size(1) == x.size(1) && w2.size(1) == w.size(0), "channel mismatch between in_feat, " + weights + " and w2");
+  check(bias_ok, std::string(op.biases) + " must have one value per hidden unit");
   check(!b2.defined() || (b2.dim() == 1 && b2.size(0) == w2.size(0)), "b2 must have one value per output channel");
-  for (const Tensor *t : {&w1, &b1, &w2, &b2})
+  MlpOperands o{x, w2, b2, first, x.size(0), x.size(1), w.size(0), w2.size(0), x.scalar_type() == at::kBFloat16 ? 1 : 0};
+  std::vector<Tensor *> all = {&o.x, &o.w2, &o.b2};
+  for (Tensor &t : o.first) all.push_back(&t);
+  for (Tensor *t : all) {
     check(!t->defined() || (t->scalar_type() == x.scalar_type() && t->device() == x.device()),
-          "w1, b1, w2 and b2 must have the dtype and device of in_feat");
+          std::string(op.params) + " must have the dtype and device of in_feat");
+    if (t->defined()) *t = t->detach().contiguous();
+  }
   const bool served = x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16;
-  check(served && me_ffn_supported((int32_t)x.size(1), (int32_t)w1.size(0), (int32_t)w2.size(0),
-                                   (int32_t)x.element_size()) != 0,
-        "widths are not served by the feed-forward kernels");
+  check(served && op.supported(o.c, o.hd, o.cout, (int32_t)x.element_size()) != 0,
+        std::string("widths are not served by the ") + op.kernels + " kernels");
+  return o;
 }
 
-static Tensor ffn_plain(const Tensor &t) { return t.defined() ? t.detach().contiguous() : t; }
-
-Tensor feed_forward_forward(const Tensor &in_feat, const Tensor &w1_, const Tensor &b1_, const Tensor &w2_,
-                            const Tensor &b2_, const std::string &activation) {
+static Tensor mlp_forward(const Mlp &op, const Tensor &in_feat, const std::vector<Tensor> &first, const Tensor &w2,
+                          const Tensor &b2, const std::string &activation) {
   const int act = ffn_activation(activation);
-  ffn_check(in_feat, w1_, b1_, w2_, b2_);
-  const Tensor x = ffn_plain(in_feat), w1 = ffn_plain(w1_), b1 = ffn_plain(b1_), w2 = ffn_plain(w2_), b2 = ffn_plain(b2_);
-  const int64_t n = x.size(0);
-  const int c = (int)x.size(1), hd = (int)w1.size(0), cout = (int)w2.size(0);
-  Tensor out = at::empty({n, cout}, x.options());
-  if (n == 0) return out;
-  c10::DeviceGuard guard(x.device());
-  me_ok(me_ffn_forward(vptr(x), vptr(w1), vptr(b1), vptr(w2), vptr(b2), x.scalar_type() == at::kBFloat16 ? 1 : 0, n, c,
-                       hd, cout, act, vptr(out), stream_of(x.device())));
+  const MlpOperands o = mlp_operands(op, in_feat, first, w2, b2);
+  Tensor out = at::empty({o.n, o.cout}, o.x.options());
+  if (o.n == 0) return out;
+  c10::DeviceGuard guard(o.x.device());
+  void *x = vptr(o.x), *w2p = vptr(o.w2), *b2p = vptr(o.b2), *y = vptr(out), *stream = stream_of(o.x.device());
+  const std::vector<Tensor> &f = o.first;
+  me_ok(op.pairs == 1 ? me_ffn_forward(x, vptr(f[0]), vptr(f[1]), w2p, b2p, o.bf16, o.n, o.c, o.hd, o.cout, act, y, stream)
+                      : me_glu_forward(x, vptr(f[0]), vptr(f[1]), vptr(f[2]), vptr(f[3]), w2p, b2p, o.bf16, o.n, o.c, o.hd,
+                                       o.cout, act, y, stream));
   return out;
 }
 
-std::vector<Tensor> feed_forward_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &w1_,
-                                          const Tensor &b1_, const Tensor &w2_, const std::string &activation,
-                                          bool need_grad_in, bool need_grad_fc1, bool need_grad_fc2) {
+// -> grad_in, a (grad_w, grad_b) per first-layer pair, grad_w2, grad_b2; undefined where not wanted
+static std::vector<Tensor> mlp_backward(const Mlp &op, const Tensor &in_feat, const Tensor &grad_out,
+                                        const std::vector<Tensor> &first, const Tensor &w2, const std::string &activation,
+                                        bool need_grad_in, bool need_grad_fc1, bool need_grad_fc2) {
   const int act = ffn_activation(activation);
-  ffn_check(in_feat, w1_, b1_, w2_, Tensor());
-  const Tensor x = ffn_plain(in_feat), w1 = ffn_plain(w1_), b1 = ffn_plain(b1_), w2 = ffn_plain(w2_);
-  const int64_t n = x.size(0);
-  const int c = (int)x.size(1), hd = (int)w1.size(0), cout = (int)w2.size(0);
-  const Tensor dy = grad_out.detach().to(x.scalar_type()).contiguous();
-  check(dy.dim() == 2 && dy.size(0) == n && dy.size(1) == cout && dy.device() == x.device(),
+  const MlpOperands o = mlp_operands(op, in_feat, first, w2, Tensor());
+  const Tensor dy = grad_out.detach().to(o.x.scalar_type()).contiguous();
+  check(dy.dim() == 2 && dy.size(0) == o.n && dy.size(1) == o.cout && dy.device() == o.x.device(),
         "grad_out_feat must be [n, cout] on the device of in_feat");
-  std::vector<Tensor> g(5);   // grad_in, grad_w1, grad_b1, grad_w2, grad_b2
-  if (need_grad_in) g[0] = at::empty({n, c}, x.options());
-  if (need_grad_fc1) g[1] = at::empty({hd, c}, x.options());
-  if (need_grad_fc1 && b1.defined()) g[2] = at::empty({hd}, x.options());
-  if (need_grad_fc2) g[3] = at::empty({cout, hd}, x.options());
-  if (need_grad_fc2) g[4] = at::empty({cout}, x.options());
-  if (n == 0) {
-    for (size_t i = 1; i < 5; i++)
+  std::vector<Tensor> g;
+  g.push_back(need_grad_in ? at::empty({o.n, o.c}, o.x.options()) : Tensor());
+  for (int i = 0; i < op.pairs; i++) {
+    g.push_back(need_grad_fc1 ? at::empty({o.hd, o.c}, o.x.options()) : Tensor());
+    g.push_back(need_grad_fc1 && o.first[2 * i + 1].defined() ? at::empty({o.hd}, o.x.options()) : Tensor());
+  }
+  g.push_back(need_grad_fc2 ? at::empty({o.cout, o.hd}, o.x.options()) : Tensor());
+  g.push_back(need_grad_fc2 ? at::empty({o.cout}, o.x.options()) : Tensor());
+  if (o.n == 0) {
+    for (size_t i = 1; i < g.size(); i++)
       if (g[i].defined()) g[i].zero_();
     return g;
   }
   if (!need_grad_in && !need_grad_fc1 && !need_grad_fc2) return g;
-  c10::DeviceGuard guard(x.device());
-  Tensor ws = workspace(me_ffn_workspace_bytes(n, c, hd, cout, (int32_t)x.element_size()), x.device());
-  me_ok(me_ffn_backward(vptr(x), vptr(dy), vptr(w1), vptr(b1), vptr(w2), x.scalar_type() == at::kBFloat16 ? 1 : 0, n, c, hd,
-                        cout, act, need_grad_in ? 1 : 0, need_grad_fc1 ? 1 : 0, need_grad_fc2 ? 1 : 0, vptr(g[0]),
-                        vptr(g[1]), vptr(g[2]), vptr(g[3]), vptr(g[4]), vptr(ws), ws.numel(), stream_of(x.device())));
+  c10::DeviceGuard guard(o.x.device());
+  Tensor ws = workspace(op.workspace_bytes(o.n, o.c, o.hd, o.cout, (int32_t)o.x.element_size()), o.x.device());
+  void *x = vptr(o.x), *dyp = vptr(dy), *w2p = vptr(o.w2), *wsp = vptr(ws), *stream = stream_of(o.x.device());
+  const std::vector<Tensor> &f = o.first;
+  me_ok(op.pairs == 1
+            ? me_ffn_backward(x, dyp, vptr(f[0]), vptr(f[1]), w2p, o.bf16, o.n, o.c, o.hd, o.cout, act, need_grad_in,
+                              need_grad_fc1, need_grad_fc2, vptr(g[0]), vptr(g[1]), vptr(g[2]), vptr(g[3]), vptr(g[4]), wsp,
+                              ws.numel(), stream)
+            : me_glu_backward(x, dyp, vptr(f[0]), vptr(f[1]), vptr(f[2]), vptr(f[3]), w2p, o.bf16, o.n, o.c, o.hd, o.cout,
+                              act, need_grad_in, need_grad_fc1, need_grad_fc2, vptr(g[0]), vptr(g[1]), vptr(g[2]),
+                              vptr(g[3]), vptr(g[4]), vptr(g[5]), vptr(g[6]), wsp, ws.numel(), stream));
   return g;
+}
+
+Tensor feed_forward_forward(const Tensor &in_feat, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2,
+                            const std::string &activation) {
+  return mlp_forward(kFfn, in_feat, {w1, b1}, w2, b2, activation);
+}
+
+std::vector<Tensor> feed_forward_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &w1, const Tensor &b1,
+                                          const Tensor &w2, const std::string &activation, bool need_grad_in,
+                                          bool need_grad_fc1, bool need_grad_fc2) {
+  return mlp_backward(kFfn, in_feat, grad_out, {w1, b1}, w2, activation, need_grad_in, need_grad_fc1, need_grad_fc2);
 }
 
 // ---- fused gated MLP (csrc/gated_feed_forward.hip, ABI 1.25; twin of backend.GatedFeedForward{Forward,Backward}GPU) ------
-static void glu_check(const Tensor &x, const Tensor &wg, const Tensor &bg, const Tensor &wu, const Tensor &bu,
-                      const Tensor &w2, const Tensor &b2) {
-  check(x.is_cuda(), "in_feat must be CUDA (ROCm) — the MI355X path has no CPU implementation");
-  check(x.dim() == 2 && wg.dim() == 2 && wu.dim() == 2 && w2.dim() == 2, "in_feat, wg, wu and w2 must be 2-D");
-  check(wg.size(1) == x.size(1) && wu.sizes() == wg.sizes() && w2.size(1) == wg.size(0),
-        "channel mismatch between in_feat, wg, wu and w2");
-  for (const Tensor *b : {&bg, &bu})
-    check(!b->defined() || (b->dim() == 1 && b->size(0) == wg.size(0)), "bg and bu must have one value per hidden unit");
-  check(!b2.defined() || (b2.dim() == 1 && b2.size(0) == w2.size(0)), "b2 must have one value per output channel");
-  for (const Tensor *t : {&wg, &bg, &wu, &bu, &w2, &b2})
-    check(!t->defined() || (t->scalar_type() == x.scalar_type() && t->device() == x.device()),
-          "wg, bg, wu, bu, w2 and b2 must have the dtype and device of in_feat");
-  const bool served = x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16;
-  check(served && me_glu_supported((int32_t)x.size(1), (int32_t)wg.size(0), (int32_t)w2.size(0),
-                                   (int32_t)x.element_size()) != 0,
-        "widths are not served by the gated feed-forward kernels");
+Tensor gated_feed_forward_forward(const Tensor &in_feat, const Tensor &wg, const Tensor &bg, const Tensor &wu,
+                                  const Tensor &bu, const Tensor &w2, const Tensor &b2, const std::string &activation) {
+  return mlp_forward(kGlu, in_feat, {wg, bg, wu, bu}, w2, b2, activation);
 }
 
-Tensor gated_feed_forward_forward(const Tensor &in_feat, const Tensor &wg_, const Tensor &bg_, const Tensor &wu_,
-                                  const Tensor &bu_, const Tensor &w2_, const Tensor &b2_, const std::string &activation) {
-  const int act = ffn_activation(activation);
-  glu_check(in_feat, wg_, bg_, wu_, bu_, w2_, b2_);
-  const Tensor x = ffn_plain(in_feat), wg = ffn_plain(wg_), bg = ffn_plain(bg_), wu = ffn_plain(wu_), bu = ffn_plain(bu_),
-               w2 = ffn_plain(w2_), b2 = ffn_plain(b2_);
-  const int64_t n = x.size(0);
-  const int c = (int)x.size(1), hd = (int)wg.size(0), cout = (int)w2.size(0);
-  Tensor out = at::empty({n, cout}, x.options());
-  if (n == 0) return out;
-  c10::DeviceGuard guard(x.device());
-  me_ok(me_glu_forward(vptr(x), vptr(wg), vptr(bg), vptr(wu), vptr(bu), vptr(w2), vptr(b2),
-                       x.scalar_type() == at::kBFloat16 ? 1 : 0, n, c, hd, cout, act, vptr(out), stream_of(x.device())));
-  return out;
-}
-
-std::vector<Tensor> gated_feed_forward_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &wg_,
-                                                const Tensor &bg_, const Tensor &wu_, const Tensor &bu_, const Tensor &w2_,
+std::vector<Tensor> gated_feed_forward_backward(const Tensor &in_feat, const Tensor &grad_out, const Tensor &wg,
+                                                const Tensor &bg, const Tensor &wu, const Tensor &bu, const Tensor &w2,
                                                 const std::string &activation, bool need_grad_in, bool need_grad_fc1,
                                                 bool need_grad_fc2) {
-  const int act = ffn_activation(activation);
-  glu_check(in_feat, wg_, bg_, wu_, bu_, w2_, Tensor());
-  const Tensor x = ffn_plain(in_feat), wg = ffn_plain(wg_), bg = ffn_plain(bg_), wu = ffn_plain(wu_), bu = ffn_plain(bu_),
-               w2 = ffn_plain(w2_);
-  const int64_t n = x.size(0);
-  const int c = (int)x.size(1), hd = (int)wg.size(0), cout = (int)w2.size(0);
-  const Tensor dy = grad_out.detach().to(x.scalar_type()).contiguous();
-  check(dy.dim() == 2 && dy.size(0) == n && dy.size(1) == cout && dy.device() == x.device(),
-        "grad_out_feat must be [n, cout] on the device of in_feat");
-  std::vector<Tensor> g(7);   // grad_in, grad_wg, grad_bg, grad_wu, grad_bu, grad_w2, grad_b2
-  if (need_grad_in) g[0] = at::empty({n, c}, x.options());
-  if (need_grad_fc1) g[1] = at::empty({hd, c}, x.options());
-  if (need_grad_fc1 && bg.defined()) g[2] = at::empty({hd}, x.options());
-  if (need_grad_fc1) g[3] = at::empty({hd, c}, x.options());
-  if (need_grad_fc1 && bu.defined()) g[4] = at::empty({hd}, x.options());
-  if (need_grad_fc2) g[5] = at::empty({cout, hd}, x.options());
-  if (need_grad_fc2) g[6] = at::empty({cout}, x.options());
-  if (n == 0) {
-    for (size_t i = 1; i < 7; i++)
-      if (g[i].defined()) g[i].zero_();
-    return g;
-  }
-  if (!need_grad_in && !need_grad_fc1 && !need_grad_fc2) return g;
-  c10::DeviceGuard guard(x.device());
-  Tensor ws = workspace(me_glu_workspace_bytes(n, c, hd, cout, (int32_t)x.element_size()), x.device());
-  me_ok(me_glu_backward(vptr(x), vptr(dy), vptr(wg), vptr(bg), vptr(wu), vptr(bu), vptr(w2),
-                        x.scalar_type() == at::kBFloat16 ? 1 : 0, n, c, hd, cout, act, need_grad_in ? 1 : 0,
-                        need_grad_fc1 ? 1 : 0, need_grad_fc2 ? 1 : 0, vptr(g[0]), vptr(g[1]), vptr(g[2]), vptr(g[3]),
-                        vptr(g[4]), vptr(g[5]), vptr(g[6]), vptr(ws), ws.numel(), stream_of(x.device())));
-  return g;
+  return mlp_backward(kGlu, in_feat, grad_out, {wg, bg, wu, bu}, w2, activation, need_grad_in, need_grad_fc1,
+                      need_grad_fc2);
 }
 
 // ---- pruning (src/pruning_cpu.cpp:40-150, src/pruning_gpu.cu) ------------------------------------------------------------------

@@ -51,42 +51,51 @@ def timed(fns, reps):
     return [t / (reps // block * block) for t in total]
 
 
-def gated_table(args, dev):
+def table(args, dev, gated):
+    """the timing table of the plain (gated: the gated) module against its torch formulation"""
+    served = backend.gated_feed_forward_supported if gated else backend.feed_forward_supported
+    cases = [(n, c, hd) for n, c in GATED_SHAPES for hd in gated_hiddens(c)] if gated else [(n, c, RATIO * c) for n, c in SHAPES]
     lines = ["n c hidden dtype | fwd us ours / torch | fwd+bwd us ours / torch | TFLOP/s fwd (ours)"]
-    for (n, c) in GATED_SHAPES:
-        for hd in gated_hiddens(c):
-            for dtype in (torch.bfloat16, torch.float32):
-                if not backend.gated_feed_forward_supported(c, hd, c, dtype):
-                    lines.append(f"{n} {c} {hd} {str(dtype)[6:]} | not served (torch formulation)")
-                    print(lines[-1], flush=True)
-                    continue
-                g = torch.Generator().manual_seed(0)
-                rnd = lambda *s: torch.randn(*s, generator=g).to(dtype).to(dev)
-                x, dy = rnd(n, c), rnd(n, c)
-                wg, bg, wu, bu = rnd(hd, c) * c ** -0.5, rnd(hd), rnd(hd, c) * c ** -0.5, rnd(hd)
-                w2, b2 = rnd(c, hd) * hd ** -0.5, rnd(c)
-                leaves = (x, wg, bg, wu, bu, w2, b2)
-
-                def ours():
-                    return ME.MinkowskiGatedFeedForwardFunction.apply(*leaves, "silu")
-
-                def torch_():
-                    return F.linear(F.silu(F.linear(x, wg, bg)) * F.linear(x, wu, bu), w2, b2)
-
-                def train(fn):
-                    def step():
-                        for t in leaves:
-                            t.grad = None
-                        fn().backward(dy)
-                    return step
-                with torch.no_grad():
-                    fwd = timed([ours, torch_], args.reps)
-                for t in leaves:
-                    t.requires_grad_(True)
-                both = timed([train(ours), train(torch_)], args.reps)
-                lines.append(f"{n} {c} {hd} {str(dtype)[6:]} | {fwd[0]:.1f} / {fwd[1]:.1f} | {both[0]:.1f} / {both[1]:.1f} | "
-                             f"{6.0 * n * c * hd / fwd[0] / 1e6:.1f}")
+    for n, c, hd in cases:
+        for dtype in (torch.bfloat16, torch.float32):
+            if not served(c, hd, c, dtype):
+                lines.append(f"{n} {c} {hd} {str(dtype)[6:]} | not served (torch formulation)")
                 print(lines[-1], flush=True)
+                continue
+            g = torch.Generator().manual_seed(0)
+            rnd = lambda *s: torch.randn(*s, generator=g).to(dtype).to(dev)
+            x, dy = rnd(n, c), rnd(n, c)
+            first = [rnd(hd, c) * c ** -0.5, rnd(hd)]
+            if gated:
+                first += [rnd(hd, c) * c ** -0.5, rnd(hd)]
+            leaves = (x, *first, rnd(c, hd) * hd ** -0.5, rnd(c))
+
+            def ours():
+                if gated:
+                    return ME.MinkowskiGatedFeedForwardFunction.apply(*leaves, "silu")
+                return ME.MinkowskiFeedForwardFunction.apply(*leaves, "gelu")
+
+            def torch_():
+                if gated:
+                    x, wg, bg, wu, bu, w2, b2 = leaves
+                    return F.linear(F.silu(F.linear(x, wg, bg)) * F.linear(x, wu, bu), w2, b2)
+                x, w1, b1, w2, b2 = leaves
+                return F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)
+
+            def train(fn):
+                def step():
+                    for t in leaves:
+                        t.grad = None
+                    fn().backward(dy)
+                return step
+            with torch.no_grad():
+                fwd = timed([ours, torch_], args.reps)
+            for t in leaves:
+                t.requires_grad_(True)
+            both = timed([train(ours), train(torch_)], args.reps)
+            lines.append(f"{n} {c} {hd} {str(dtype)[6:]} | {fwd[0]:.1f} / {fwd[1]:.1f} | {both[0]:.1f} / {both[1]:.1f} | "
+                         f"{(6.0 if gated else 4.0) * n * c * hd / fwd[0] / 1e6:.1f}")
+            print(lines[-1], flush=True)
     return lines
 
 
@@ -102,45 +111,9 @@ def main():
     if args.gated:
         lines = []
         for run in range(args.repeat):
-            lines += [f"# run {run + 1} of {args.repeat}"] + gated_table(args, dev)
-        if args.out:
-            with open(args.out, "w") as f:
-                f.write("\n".join(lines) + "\n")
-        return
-    lines = ["n c hidden dtype | fwd us ours / torch | fwd+bwd us ours / torch | TFLOP/s fwd (ours)"]
-    for n, c in SHAPES:
-        hd = RATIO * c
-        for dtype in (torch.bfloat16, torch.float32):
-            if not backend.feed_forward_supported(c, hd, c, dtype):
-                lines.append(f"{n} {c} {hd} {str(dtype)[6:]} | not served (torch formulation)")
-                print(lines[-1], flush=True)
-                continue
-            g = torch.Generator().manual_seed(0)
-            rnd = lambda *s: torch.randn(*s, generator=g).to(dtype).to(dev)
-            x, dy = rnd(n, c), rnd(n, c)
-            w1, b1, w2, b2 = rnd(hd, c) * c ** -0.5, rnd(hd), rnd(c, hd) * hd ** -0.5, rnd(c)
-            leaves = (x, w1, b1, w2, b2)
-
-            def ours():
-                return ME.MinkowskiFeedForwardFunction.apply(x, w1, b1, w2, b2, "gelu")
-
-            def torch_():
-                return F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)
-
-            def train(fn):
-                def step():
-                    for t in leaves:
-                        t.grad = None
-                    fn().backward(dy)
-                return step
-            with torch.no_grad():
-                fwd = timed([ours, torch_], args.reps)
-            for t in leaves:
-                t.requires_grad_(True)
-            both = timed([train(ours), train(torch_)], args.reps)
-            lines.append(f"{n} {c} {hd} {str(dtype)[6:]} | {fwd[0]:.1f} / {fwd[1]:.1f} | {both[0]:.1f} / {both[1]:.1f} | "
-                         f"{4.0 * n * c * hd / fwd[0] / 1e6:.1f}")
-            print(lines[-1], flush=True)
+            lines += [f"# run {run + 1} of {args.repeat}"] + table(args, dev, True)
+    else:
+        lines = table(args, dev, False)
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")

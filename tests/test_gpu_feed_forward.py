@@ -72,6 +72,37 @@ def test_integer_inputs_are_exact(device, dtype, widths, rows):
         assert torch.equal(ours[name].cpu(), ref[name].to(dtype)), name
 
 
+@pytest.mark.parametrize("mode", ["no-bias", "in", "fc1", "fc2"])
+@pytest.mark.parametrize("rows", ["33", "block+1"])
+@pytest.mark.parametrize("widths", ["32", "64-160-96"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
+def test_integer_inputs_are_exact_without_biases_and_per_gradient(device, dtype, widths, rows, mode):
+    """The operators called directly on the inputs of test_integer_inputs_are_exact: with every bias None, and with
+    each need_grad_* flag alone (an output that is not wanted is None)."""
+    c, hd, cout = _widths(widths, dtype)
+    n = {"33": 33, "block+1": ROWS + 1}[rows]
+    t = _inputs(n, c, hd, cout, dtype, device, integer=True)
+    bias = mode != "no-bias"
+    cpu = {k: v.double().cpu() * (1.0 if bias or k not in ("b1", "b2") else 0.0) for k, v in t.items()}
+    z = cpu["x"] @ cpu["w1"].T + cpu["b1"]
+    dh = cpu["dy"] @ cpu["w2"]
+    ref = _torch(cpu, "relu")
+    assert z.abs().max() <= 256 and dh.abs().max() <= 256                   # exact in bf16
+    assert all(v.abs().max() < 2 ** 24 for v in ref.values())               # every sum exact in fp32
+    b1, b2 = (t["b1"], t["b2"]) if bias else (None, None)
+    need = {"no-bias": (True, True, True), "in": (True, False, False), "fc1": (False, True, False),
+            "fc2": (False, False, True)}[mode]
+    y = backend.FeedForwardForwardGPU(t["x"], t["w1"], b1, t["w2"], b2, "relu")
+    grads = backend.FeedForwardBackwardGPU(t["x"], t["dy"], t["w1"], b1, t["w2"], "relu", *need)
+    wanted = dict(zip(NAMES[1:], (need[0], need[1], need[1] and bias, need[2], need[2])))
+    assert torch.equal(y.cpu(), ref["y"].to(dtype))
+    for name, g in zip(NAMES[1:], grads):
+        if wanted[name]:
+            assert torch.equal(g.cpu(), ref[name].to(dtype)), name
+        else:
+            assert g is None, name
+
+
 @pytest.mark.parametrize("shape", [(133, 64, 128, 64), (128, 32, 96, 64)], ids=str)
 @pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
 @pytest.mark.parametrize("act", sorted(ACTIVATIONS))

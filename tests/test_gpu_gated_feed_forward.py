@@ -79,6 +79,41 @@ def test_integer_inputs_are_exact(device, dtype, widths, rows):
         assert torch.equal(ours[name].cpu(), ref[name].to(dtype)), name
 
 
+@pytest.mark.parametrize("mode", ["no-bias", "in", "fc1", "fc2"])
+@pytest.mark.parametrize("rows", ["33", "block+1"])
+@pytest.mark.parametrize("widths", ["32", "64-160-96"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
+def test_integer_inputs_are_exact_without_biases_and_per_gradient(device, dtype, widths, rows, mode):
+    """The operators called directly on the inputs of test_integer_inputs_are_exact: with every bias None, and with
+    each need_grad_* flag alone (an output that is not wanted is None).  The bounds that keep the float64 reference exact
+    in bf16 are asserted again, on the inputs as this test uses them."""
+    c, hd, cout = _widths(widths, dtype)
+    n = {"33": 33, "block+1": ROWS + 1}[rows]
+    t = _inputs(n, c, hd, cout, dtype, device, integer=True)
+    bias = mode != "no-bias"
+    cpu = {k: v.double().cpu() * (1.0 if bias or k not in ("bg", "bu", "b2") else 0.0) for k, v in t.items()}
+    zg, zu = cpu["x"] @ cpu["wg"].T + cpu["bg"], cpu["x"] @ cpu["wu"].T + cpu["bu"]
+    dh = cpu["dy"] @ cpu["w2"]
+    ref = _torch(cpu, "relu")
+    top = lambda v: float(v.abs().max())
+    assert top(zg) <= 5 and top(zu) <= 5 and top(F.relu(zg) * zu) <= 25 and top(dh) <= 4          # exact in bf16
+    assert top(dh * zu * (zg > 0)) <= 20 and top(dh * F.relu(zg)) <= 20
+    assert all(top(v) < 2 ** 24 for v in ref.values())                                            # every sum exact in fp32
+    bg, bu, b2 = (t["bg"], t["bu"], t["b2"]) if bias else (None, None, None)
+    need = {"no-bias": (True, True, True), "in": (True, False, False), "fc1": (False, True, False),
+            "fc2": (False, False, True)}[mode]
+    y = backend.GatedFeedForwardForwardGPU(t["x"], t["wg"], bg, t["wu"], bu, t["w2"], b2, "relu")
+    grads = backend.GatedFeedForwardBackwardGPU(t["x"], t["dy"], t["wg"], bg, t["wu"], bu, t["w2"], "relu", *need)
+    fc1b = need[1] and bias
+    wanted = dict(zip(NAMES[1:], (need[0], need[1], fc1b, need[1], fc1b, need[2], need[2])))
+    assert torch.equal(y.cpu(), ref["y"].to(dtype))
+    for name, g in zip(NAMES[1:], grads):
+        if wanted[name]:
+            assert torch.equal(g.cpu(), ref[name].to(dtype)), name
+        else:
+            assert g is None, name
+
+
 @pytest.mark.parametrize("shape", [(133, 64, 128, 64), (128, 32, 96, 64)], ids=str)
 @pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
 @pytest.mark.parametrize("act", sorted(ACTIVATIONS))

@@ -133,7 +133,12 @@ typedef struct me_region {
  *              scale / shift / gate read through batch_row in the forward pass, a backward pass whose chunks are cut over
  *              the per-instance row lists so that a workgroup owns rows of one instance, fixed-order merges for the
  *              conditioning and parameter gradients (me_adaln_chunks, me_adaln_workspace_bytes, me_adaln_forward,
- *              me_adaln_backward and the _f64 twins me_adaln_forward_f64, me_adaln_backward_f64) */
+ *              me_adaln_backward and the _f64 twins me_adaln_forward_f64, me_adaln_backward_f64)
+ *   1.27 (370)  round 27: the selective state-space scan (Mamba S6) over the serialized voxel order: global chunks of 64
+ *              positions with reset flags at the instance starts, a chunk-local pass, a carry over the chunks and the pass
+ *              that writes the rows; backward on two checkpoint levels (chunk entry states in memory, sub-chunk entry
+ *              states in LDS, one sub-chunk's states in registers), fixed-order merges (me_sscan_supported, me_sscan_chunk,
+ *              me_sscan_workspace_bytes, me_sscan_forward, me_sscan_backward) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1540,6 +1545,44 @@ int me_adaln_backward_f64(const double *stream_rows_dev, const double *dy_dev, c
                           double *dstream_out_dev, int64_t dstream_out_stride, double *dinput_dev, int64_t dinput_stride,
                           double *grad_gamma_dev, double *grad_beta_dev, double *grad_scale_dev, double *grad_shift_dev,
                           double *grad_gate_dev, void *stream);
+
+/* ---- selective state-space scan over the serialized voxel order (MinkowskiMamba, MinkowskiFunctional.selective_scan;
+ *      csrc/selective_scan.hip, ABI 1.27) ----
+ * Position p of the sequence is row seg_rows[p] (seg_rows[n - 1 - p] with reverse != 0); seg_rows int32 [n] holds the rows
+ * of every instance along its curve, instance after instance (the patch lists of me_attn_patch_lists with patches of one
+ * row).  A position whose row has another batch_row (int32 [n], the instance of every row) than the position before it,
+ * and position 0, starts from h = 0.  Per channel d < c and state s < S, in fp32:
+ *   dt   = delta[row, d] + delta_bias[d]             (delta_softplus: dt > 20 ? dt : log1p(exp(dt)))
+ *   h[s] = exp(dt A[d, s]) h[s] + dt u[row, d] B[row, s]
+ *   out[row, d] = (sum_s C[row, s] h[s] + Dskip[d] u[row, d]) * silu(z[row, d])
+ * u, delta, z, out, dout: [n, d] rows of float or (is_bf16) __bf16 with a row stride in elements; B, C: [n, s] rows of the
+ * same type with a row stride; A [d, s], Dskip [d], delta_bias [d]: contiguous floats.  z, Dskip and delta_bias may be NULL
+ * (no factor, no skip, no bias).  The kernels serve d >= 1 and s = 8 or 16 (me_sscan_supported).
+ * The sequence is cut into chunks of me_sscan_chunk consecutive positions (64): ceil(n / 64) chunks.  Forward writes out and entry
+ * (float [chunks, d, s]: the state before every chunk), which backward takes next to the forward's operands.  Backward
+ * writes du, ddelta, dz [n, d] and dB, dC [n, s] (contiguous, the rows' type) and dA [d, s], dDskip [d], ddelta_bias [d]
+ * (floats); every output pointer may be NULL: not written (dB and dC: not computed).  All sums are formed in a fixed order
+ * without atomics.  workspace: at least me_sscan_workspace_bytes(n, d, s, backward) bytes, 4-byte aligned.
+ * Host-side errors, nothing launched: unsupported d / s, n < 0 or n >= 2^31, a row stride below the row width, dz without z,
+ * a gradient of Dskip / delta_bias without the operand; then, with n > 0, a missing data pointer or a workspace that is too
+ * small.  n = 0 launches nothing in forward and writes zero parameter gradients in backward. */
+int32_t me_sscan_supported(int32_t d, int32_t s, int32_t is_bf16);
+int32_t me_sscan_chunk(void);
+int64_t me_sscan_workspace_bytes(int64_t n, int32_t d, int32_t s, int32_t backward);
+int me_sscan_forward(const void *u_dev, const void *delta_dev, const void *z_dev, const void *b_dev, const void *c_dev,
+                     int32_t is_bf16, int64_t u_stride, int64_t delta_stride, int64_t z_stride, int64_t b_stride,
+                     int64_t c_stride, const float *a_dev, const float *dskip_dev, const float *delta_bias_dev,
+                     int32_t delta_softplus, const int32_t *seg_rows_dev, const int32_t *batch_row_dev, int32_t reverse,
+                     int64_t n, int32_t d, int32_t s, void *out_dev, int64_t out_stride, float *entry_dev,
+                     void *workspace_dev, int64_t workspace_bytes, void *stream);
+int me_sscan_backward(const void *u_dev, const void *delta_dev, const void *z_dev, const void *b_dev, const void *c_dev,
+                      const void *dout_dev, int32_t is_bf16, int64_t u_stride, int64_t delta_stride, int64_t z_stride,
+                      int64_t b_stride, int64_t c_stride, int64_t dout_stride, const float *a_dev, const float *dskip_dev,
+                      const float *delta_bias_dev, int32_t delta_softplus, const int32_t *seg_rows_dev,
+                      const int32_t *batch_row_dev, int32_t reverse, int64_t n, int32_t d, int32_t s,
+                      const float *entry_dev, void *du_dev, void *ddelta_dev, void *dz_dev, void *db_dev, void *dc_dev,
+                      float *da_dev, float *ddskip_dev, float *ddelta_bias_dev, void *workspace_dev,
+                      int64_t workspace_bytes, void *stream);
 
 /* ---- fused two-layer MLP (MinkowskiFeedForward, MinkowskiFunctional.feed_forward; csrc/feed_forward.hip, ABI 1.24) ----
  *   y = act(x w1^T + b1) w2^T + b2

@@ -220,6 +220,23 @@ def ada_layer_norm(input, scale=None, shift=None, residual=None, gate=None, weig
     return _ada_row_norm(input, residual, weight, bias, scale, shift, gate, eps, rms)
 
 
+def selective_scan(u, delta, A, B, C, Dskip=None, z=None, delta_bias=None, delta_softplus=False, order="z", reverse=False):
+    """The selective state-space scan (Mamba's S6; MinkowskiMamba without its projections) along the curve `order` of
+    every instance.  u, delta, z: SparseTensors of D channels on ONE coordinate map (z may be None); B, C: (N, S) matrices
+    or SparseTensors on that map; A (D, S), Dskip (D,), delta_bias (D,): float32 tensors.  The result sits on u's map."""
+    from .selective_scan import selective_scan as _scan
+    from .sparse_tensor import SparseTensor
+    if not isinstance(u, SparseTensor):
+        raise TypeError(f"selective_scan takes a SparseTensor u, not a {type(u).__name__}")
+    for name, t in (("delta", delta), ("z", z), ("B", B), ("C", C)):
+        if isinstance(t, SparseTensor) and (t.coordinate_map_key != u.coordinate_map_key or t._manager is not u._manager):
+            raise ValueError(f"u, delta, z, B and C must share one coordinate map; {name} sits on another")
+    feats = [t.F if isinstance(t, SparseTensor) else t for t in (delta, B, C, z)]
+    out = _scan(u.F, feats[0], A, feats[1], feats[2], Dskip, feats[3], delta_bias, delta_softplus, order, reverse,
+                u.coordinate_map_key, u._manager)
+    return SparseTensor(out, coordinate_map_key=u.coordinate_map_key, coordinate_manager=u._manager)
+
+
 def feed_forward(input, w1, b1, w2, b2, activation="gelu"):
     """act(F w1^T + b1) w2^T + b2 over the features F of a SparseTensor or a TensorField (MinkowskiFeedForward as a
     function).  w1 [hidden, C], w2 [C_out, hidden], b1 / b2 vectors or None; activation: gelu, gelu_tanh, relu or silu."""
@@ -238,4 +255,5 @@ def gated_feed_forward(input, wg, bg, wu, bu, w2, b2, activation="silu"):
 __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group_norm", "scaled_dot_product_attention",
                                                 "local_attention", "serialized_attention", "cross_attention",
                                                 "window_attention", "rotary_embedding", "layer_norm", "rms_norm",
-                                                "ada_layer_norm", "feed_forward", "gated_feed_forward"]
+                                                "ada_layer_norm", "feed_forward", "gated_feed_forward",
+                                                "selective_scan"]

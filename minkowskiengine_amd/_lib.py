@@ -236,6 +236,15 @@ SIGNATURES = {
     "me_adaln_backward_f64": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32,
                                              c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
                                              c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "me_sscan_supported": (c_i32, [c_i32, c_i32, c_i32]),
+    "me_sscan_chunk": (c_i32, []),
+    "me_sscan_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "me_sscan_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                        c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64,
+                                        c_vp]),
+    "me_sscan_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                         c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "me_ffn_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "me_ffn_row_splits": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),
     "me_ffn_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32, c_i32]),

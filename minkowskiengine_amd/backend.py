@@ -4233,6 +4233,87 @@ def AdaLayerNormBackwardGPU(stream_feat, grad_out_feat, grad_stream, in_feat, we
 
 
 # ------------------------------------------------------------------------------------------------
+# selective state-space scan over the serialized voxel order (csrc/selective_scan.hip, ABI 1.27; not in the reference).
+# The sequence is manager._patch_rows(in_key, 1, order): with patches of one row seg_rows is the row of every sequence
+# position (instance after instance, each along its curve); manager._origin_rows gives the instance of every row, from
+# which the kernels take the reset flags.  Both are cached per map.
+# ------------------------------------------------------------------------------------------------
+def _sscan_prepare(u, delta, A, B, C, Dskip, z, delta_bias, order, in_key, manager):
+    """-> (u, delta, z, B, C, seg_rows, batch_row) after the checks both directions share"""
+    u = _attn_rows("u", u)
+    _check(u.dtype in (torch.float32, torch.bfloat16), "the selective scan kernels take float32 or bfloat16 rows, got", u.dtype)
+    delta = _attn_rows("delta", delta, u)
+    z = None if z is None else _attn_rows("z", z, u)
+    _check(manager.exists(in_key), "coordinate map not found")
+    n, d = manager.size(in_key), int(u.shape[1])
+    _check(u.shape[0] == n and delta.shape[0] == n and (z is None or z.shape[0] == n), "Invalid u / delta / z size",
+           u.shape[0], delta.shape[0], "!=", n)
+    _check(A.is_cuda and A.dim() == 2 and A.dtype == torch.float32 and A.is_contiguous() and A.shape[0] == d and
+           A.device == u.device, "A must be a contiguous float32 GPU tensor [D, S]")
+    s = int(A.shape[1])
+    _check(bool(_lib.load().me_sscan_supported(d, s, 1 if u.dtype == torch.bfloat16 else 0)),
+           "the selective scan kernels serve 8 or 16 states, got", s)
+    B, C = _attn_rows("B", B), _attn_rows("C", C)
+    for name, t in (("B", B), ("C", C)):
+        _check(t.dtype == u.dtype and t.device == u.device and tuple(t.shape) == (n, s), name,
+               "must have the dtype and device of u and the shape [N, S]")
+    _inorm_check_vec("Dskip", Dskip, u, d)
+    _inorm_check_vec("delta_bias", delta_bias, u, d)
+    seg_rows = manager._patch_rows(in_key, 1, order)[1]
+    return u, delta, z, B, C, seg_rows, manager._origin_rows(in_key)
+
+
+def SelectiveScanForwardGPU(u, delta, A, B, C, Dskip, z, delta_bias, delta_softplus, order, reverse, in_key, manager):
+    """-> (out [N, D], entry [chunks, D, S] fp32): the selective scan of csrc/selective_scan.hip over the rows of `in_key`
+    in the order `order` of every instance (backwards with `reverse`); entry, the state before every chunk of
+    me_sscan_chunk() positions, is what SelectiveScanBackwardGPU takes next to the operands.  Three launches."""
+    u, delta, z, B, C, seg_rows, rows = _sscan_prepare(u, delta, A, B, C, Dskip, z, delta_bias, order, in_key, manager)
+    lib = _lib.load()
+    n, d, s = int(u.shape[0]), int(u.shape[1]), int(A.shape[1])
+    dev = u.device
+    out = torch.empty((n, d), dtype=u.dtype, device=dev)
+    entry = torch.empty((-(-n // int(lib.me_sscan_chunk())), d, s), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out, entry
+    ws = _workspace(int(lib.me_sscan_workspace_bytes(n, d, s, 0)), dev)
+    with _on(dev):
+        _timed("sscan_forward", dev, lambda: _lib.check(lib.me_sscan_forward(
+            _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C), 1 if u.dtype == torch.bfloat16 else 0, _attn_stride(u),
+            _attn_stride(delta), d if z is None else _attn_stride(z), _attn_stride(B), _attn_stride(C), _ptr(A), _ptr(Dskip),
+            _ptr(delta_bias), 1 if delta_softplus else 0, _ptr(seg_rows), _ptr(rows), 1 if reverse else 0, n, d, s,
+            _ptr(out), d, _ptr(entry), _ptr(ws), ws.numel(), _stream(dev))))
+    return out, entry
+
+
+def SelectiveScanBackwardGPU(u, delta, A, B, C, Dskip, z, delta_bias, entry, grad_out, delta_softplus, order, reverse, in_key,
+                             manager, need_grad=(True,) * 8):
+    """-> (grad_u, grad_delta, grad_A, grad_B, grad_C, grad_Dskip, grad_z, grad_delta_bias), None where need_grad (same
+    order) is False or the operand is None; rows in the dtype of u, parameters in fp32.  Fixed-order sums, no atomics."""
+    u, delta, z, B, C, seg_rows, rows = _sscan_prepare(u, delta, A, B, C, Dskip, z, delta_bias, order, in_key, manager)
+    lib = _lib.load()
+    n, d, s = int(u.shape[0]), int(u.shape[1]), int(A.shape[1])
+    dev = u.device
+    grad_out = _attn_rows("grad_out", grad_out.to(u.dtype), u)
+    _check(grad_out.shape[0] == n, "grad_out must have the shape of u")
+    _check(entry.is_cuda and entry.is_contiguous() and entry.dtype == torch.float32 and
+           tuple(entry.shape) == (-(-n // int(lib.me_sscan_chunk())), d, s), "entry must be the forward pass's [chunks, D, S]")
+    need = list(need_grad)
+    need[5], need[6], need[7] = need[5] and Dskip is not None, need[6] and z is not None, need[7] and delta_bias is not None
+    shapes = ((n, d), (n, d), (d, s), (n, s), (n, s), (d,), (n, d), (d,))
+    dtypes = (u.dtype, u.dtype, torch.float32, u.dtype, u.dtype, torch.float32, u.dtype, torch.float32)
+    g = [torch.empty(sh, dtype=dt, device=dev) if nd else None for sh, dt, nd in zip(shapes, dtypes, need)]
+    ws = _workspace(int(lib.me_sscan_workspace_bytes(n, d, s, 1)), dev)
+    with _on(dev):
+        _timed("sscan_backward", dev, lambda: _lib.check(lib.me_sscan_backward(
+            _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C), _ptr(grad_out), 1 if u.dtype == torch.bfloat16 else 0,
+            _attn_stride(u), _attn_stride(delta), d if z is None else _attn_stride(z), _attn_stride(B), _attn_stride(C),
+            _attn_stride(grad_out), _ptr(A), _ptr(Dskip), _ptr(delta_bias), 1 if delta_softplus else 0, _ptr(seg_rows),
+            _ptr(rows), 1 if reverse else 0, n, d, s, _ptr(entry), _ptr(g[0]), _ptr(g[1]), _ptr(g[6]), _ptr(g[3]),
+            _ptr(g[4]), _ptr(g[2]), _ptr(g[5]), _ptr(g[7]), _ptr(ws), ws.numel(), _stream(dev))))
+    return tuple(g)
+
+
+# ------------------------------------------------------------------------------------------------
 # fused two-layer MLP (csrc/feed_forward.hip, ABI 1.24; not in the reference): y = act(x w1^T + b1) w2^T + b2 without the
 # hidden matrix in memory.  Row-local, so the operators take no coordinate map.
 # ------------------------------------------------------------------------------------------------

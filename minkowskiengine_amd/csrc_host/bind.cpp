@@ -901,6 +901,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("in_key"), py::arg("manager"), py::arg("need_grad_in") = true, py::arg("need_grad_residual") = true,
         py::arg("need_grad_weight") = true, py::arg("need_grad_bias") = true, py::arg("need_grad_scale") = true,
         py::arg("need_grad_shift") = true, py::arg("need_grad_gate") = true);
+  // selective state-space scan over the serialized voxel order: csrc/selective_scan.hip
+  m.def("SelectiveScanForwardGPU",
+        [](const Tensor &u, const Tensor &delta, const Tensor &A, const Tensor &B, const Tensor &C, const py::object &Dskip,
+           const py::object &z, const py::object &delta_bias, bool delta_softplus, const std::string &order, bool reverse,
+           CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+          const Tensor dk = opt_tensor(Dskip), zz = opt_tensor(z), db = opt_tensor(delta_bias);
+          std::pair<Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = selective_scan_forward(u, delta, A, B, C, dk, zz, db, delta_softplus, order, reverse, in_key, mgr);
+          }
+          return py::make_tuple(r.first, r.second);
+        },
+        py::arg("u"), py::arg("delta"), py::arg("A"), py::arg("B"), py::arg("C"), py::arg("Dskip"), py::arg("z"),
+        py::arg("delta_bias"), py::arg("delta_softplus"), py::arg("order"), py::arg("reverse"), py::arg("in_key"),
+        py::arg("manager"));
+  m.def("SelectiveScanBackwardGPU",
+        [](const Tensor &u, const Tensor &delta, const Tensor &A, const Tensor &B, const Tensor &C, const py::object &Dskip,
+           const py::object &z, const py::object &delta_bias, const Tensor &entry, const Tensor &grad_out,
+           bool delta_softplus, const std::string &order, bool reverse, CoordinateMapKey *in_key,
+           CoordinateMapManager *mgr, const std::array<bool, 8> &need_grad) {
+          const Tensor dk = opt_tensor(Dskip), zz = opt_tensor(z), db = opt_tensor(delta_bias);
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = selective_scan_backward(u, delta, A, B, C, dk, zz, db, entry, grad_out, delta_softplus, order, reverse,
+                                        in_key, mgr, need_grad);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]), opt_out(r[3]), opt_out(r[4]), opt_out(r[5]),
+                                opt_out(r[6]), opt_out(r[7]));
+        },
+        py::arg("u"), py::arg("delta"), py::arg("A"), py::arg("B"), py::arg("C"), py::arg("Dskip"), py::arg("z"),
+        py::arg("delta_bias"), py::arg("entry"), py::arg("grad_out"), py::arg("delta_softplus"), py::arg("order"),
+        py::arg("reverse"), py::arg("in_key"), py::arg("manager"),
+        py::arg("need_grad") = std::array<bool, 8>{true, true, true, true, true, true, true, true});
   // fused two-layer MLP: csrc/feed_forward.hip
   m.def("FeedForwardForwardGPU",
         [](const Tensor &in_feat, const Tensor &w1, const py::object &b1, const Tensor &w2, const py::object &b2,

@@ -469,6 +469,18 @@ std::vector<Tensor> ada_layer_norm_backward(const Tensor &stream_feat, const Ten
                                             const Tensor &scale, const Tensor &gate, const Tensor &mean, const Tensor &rstd,
                                             bool rms, CoordinateMapKey *in_key, CoordinateMapManager *mgr,
                                             const std::array<bool, 7> &need);
+// selective state-space scan over the serialized voxel order (csrc/selective_scan.hip; twin of
+// backend.SelectiveScan{Forward,Backward}GPU); -> (out, entry) and (grad_u, grad_delta, grad_A, grad_B, grad_C, grad_Dskip,
+// grad_z, grad_delta_bias), undefined where not wanted
+std::pair<Tensor, Tensor> selective_scan_forward(Tensor u, Tensor delta, const Tensor &A, Tensor B, Tensor C,
+                                                 const Tensor &Dskip, Tensor z, const Tensor &delta_bias,
+                                                 bool delta_softplus, const std::string &order, bool reverse,
+                                                 CoordinateMapKey *in_key, CoordinateMapManager *mgr);
+std::vector<Tensor> selective_scan_backward(Tensor u, Tensor delta, const Tensor &A, Tensor B, Tensor C, const Tensor &Dskip,
+                                            Tensor z, const Tensor &delta_bias, const Tensor &entry, Tensor grad_out,
+                                            bool delta_softplus, const std::string &order, bool reverse,
+                                            CoordinateMapKey *in_key, CoordinateMapManager *mgr,
+                                            const std::array<bool, 8> &need);
 // fused two-layer MLP (csrc/feed_forward.hip; twin of backend.FeedForward{Forward,Backward}GPU);
 // backward -> (grad_in, grad_w1, grad_b1, grad_w2, grad_b2), undefined where not wanted
 Tensor feed_forward_forward(const Tensor &in_feat, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2,

@@ -1876,6 +1876,103 @@ std::vector<Tensor> ada_layer_norm_backward(const Tensor &stream_feat, const Ten
   return g;
 }
 
+// ---- selective state-space scan over the serialized voxel order (csrc/selective_scan.hip, ABI 1.27; twin of
+// backend.SelectiveScan{Forward,Backward}GPU): the sequence is mgr->patch_rows with patches of one row, the instance of
+// every row mgr->origin_rows ---------------------------------------------------------------------------------------------
+struct SscanPrep {
+  Tensor seg_rows, rows;
+  int64_t n;
+  int d, s;
+};
+static SscanPrep sscan_prepare(Tensor &u, Tensor &delta, const Tensor &A, Tensor &B, Tensor &C, const Tensor &Dskip, Tensor &z,
+                               const Tensor &delta_bias, const std::string &order, CoordinateMapKey *in_key,
+                               CoordinateMapManager *mgr) {
+  u = attn_rows("u", u);
+  check(u.scalar_type() == at::kFloat || u.scalar_type() == at::kBFloat16,
+        "the selective scan kernels take float32 or bfloat16 rows");
+  delta = attn_rows("delta", delta, &u);
+  if (z.defined()) z = attn_rows("z", z, &u);
+  const KeyT &ik = in_key->get();
+  check(mgr->exists(ik), "coordinate map not found");
+  const int64_t n = mgr->get(ik)->n, d = u.size(1);
+  check(u.size(0) == n && delta.size(0) == n && (!z.defined() || z.size(0) == n), "Invalid u / delta / z size");
+  check(A.is_cuda() && A.dim() == 2 && A.scalar_type() == at::kFloat && A.is_contiguous() && A.size(0) == d &&
+            A.device() == u.device(),
+        "A must be a contiguous float32 GPU tensor [D, S]");
+  const int64_t s = A.size(1);
+  check(me_sscan_supported((int32_t)d, (int32_t)s, u.scalar_type() == at::kBFloat16 ? 1 : 0) != 0,
+        "the selective scan kernels serve 8 or 16 states, got " + std::to_string(s));
+  B = attn_rows("B", B);
+  C = attn_rows("C", C);
+  for (const Tensor *t : {&B, &C})
+    check(t->scalar_type() == u.scalar_type() && t->device() == u.device() && t->size(0) == n && t->size(1) == s,
+          "B and C must have the dtype and device of u and the shape [N, S]");
+  inorm_check_vec("Dskip", Dskip, u, d);
+  inorm_check_vec("delta_bias", delta_bias, u, d);
+  const std::vector<Tensor> &l = mgr->patch_rows(ik, 1, serial_order_code(order));
+  return {l[1], mgr->origin_rows(ik), n, (int)d, (int)s};
+}
+
+std::pair<Tensor, Tensor> selective_scan_forward(Tensor u, Tensor delta, const Tensor &A, Tensor B, Tensor C,
+                                                 const Tensor &Dskip, Tensor z, const Tensor &delta_bias,
+                                                 bool delta_softplus, const std::string &order, bool reverse,
+                                                 CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+  const SscanPrep p = sscan_prepare(u, delta, A, B, C, Dskip, z, delta_bias, order, in_key, mgr);
+  const c10::Device dev = u.device();
+  Tensor out = at::empty({p.n, p.d}, u.options());
+  Tensor entry = at::empty({(p.n + me_sscan_chunk() - 1) / me_sscan_chunk(), p.d, p.s},
+                           at::TensorOptions().dtype(at::kFloat).device(dev));
+  if (p.n == 0) return {out, entry};
+  c10::DeviceGuard guard(dev);
+  Tensor ws = workspace(me_sscan_workspace_bytes(p.n, p.d, p.s, 0), dev);
+  me_ok(me_sscan_forward(vptr(u), vptr(delta), vptr(z), vptr(B), vptr(C), u.scalar_type() == at::kBFloat16 ? 1 : 0,
+                         attn_stride(u), attn_stride(delta), z.defined() ? attn_stride(z) : p.d, attn_stride(B),
+                         attn_stride(C), ptr<float>(A), ptr<float>(Dskip), ptr<float>(delta_bias), delta_softplus ? 1 : 0,
+                         ptr<int32_t>(p.seg_rows), ptr<int32_t>(p.rows), reverse ? 1 : 0, p.n, p.d, p.s, vptr(out), p.d,
+                         ptr<float>(entry), vptr(ws), ws.numel(), stream_of(dev)));
+  return {out, entry};
+}
+
+// need and the result: grad_u, grad_delta, grad_A, grad_B, grad_C, grad_Dskip, grad_z, grad_delta_bias
+std::vector<Tensor> selective_scan_backward(Tensor u, Tensor delta, const Tensor &A, Tensor B, Tensor C, const Tensor &Dskip,
+                                            Tensor z, const Tensor &delta_bias, const Tensor &entry, Tensor grad_out,
+                                            bool delta_softplus, const std::string &order, bool reverse,
+                                            CoordinateMapKey *in_key, CoordinateMapManager *mgr,
+                                            const std::array<bool, 8> &need_in) {
+  const SscanPrep p = sscan_prepare(u, delta, A, B, C, Dskip, z, delta_bias, order, in_key, mgr);
+  const c10::Device dev = u.device();
+  grad_out = attn_rows("grad_out", grad_out.to(u.scalar_type()), &u);
+  check(grad_out.size(0) == p.n, "grad_out must have the shape of u");
+  check(entry.is_cuda() && entry.is_contiguous() && entry.scalar_type() == at::kFloat && entry.dim() == 3 &&
+            entry.size(0) == (p.n + me_sscan_chunk() - 1) / me_sscan_chunk() && entry.size(1) == p.d &&
+            entry.size(2) == p.s,
+        "entry must be the forward pass's [chunks, D, S]");
+  std::array<bool, 8> need = need_in;
+  need[5] = need[5] && Dskip.defined();
+  need[6] = need[6] && z.defined();
+  need[7] = need[7] && delta_bias.defined();
+  const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
+  std::vector<Tensor> g(8);
+  if (need[0]) g[0] = at::empty({p.n, p.d}, u.options());
+  if (need[1]) g[1] = at::empty({p.n, p.d}, u.options());
+  if (need[2]) g[2] = at::empty({p.d, p.s}, fopt);
+  if (need[3]) g[3] = at::empty({p.n, p.s}, u.options());
+  if (need[4]) g[4] = at::empty({p.n, p.s}, u.options());
+  if (need[5]) g[5] = at::empty({p.d}, fopt);
+  if (need[6]) g[6] = at::empty({p.n, p.d}, u.options());
+  if (need[7]) g[7] = at::empty({p.d}, fopt);
+  c10::DeviceGuard guard(dev);
+  Tensor ws = workspace(me_sscan_workspace_bytes(p.n, p.d, p.s, 1), dev);
+  me_ok(me_sscan_backward(vptr(u), vptr(delta), vptr(z), vptr(B), vptr(C), vptr(grad_out),
+                          u.scalar_type() == at::kBFloat16 ? 1 : 0, attn_stride(u), attn_stride(delta),
+                          z.defined() ? attn_stride(z) : p.d, attn_stride(B), attn_stride(C), attn_stride(grad_out),
+                          ptr<float>(A), ptr<float>(Dskip), ptr<float>(delta_bias), delta_softplus ? 1 : 0,
+                          ptr<int32_t>(p.seg_rows), ptr<int32_t>(p.rows), reverse ? 1 : 0, p.n, p.d, p.s, ptr<float>(entry),
+                          vptr(g[0]), vptr(g[1]), vptr(g[6]), vptr(g[3]), vptr(g[4]), ptr<float>(g[2]), ptr<float>(g[5]),
+                          ptr<float>(g[7]), vptr(ws), ws.numel(), stream_of(dev)));
+  return g;
+}
+
 // ---- fused two-layer MLP (csrc/feed_forward.hip, ABI 1.24; twin of backend.FeedForward{Forward,Backward}GPU): row-local,
 // no coordinate map -----------------------------------------------------------------------------------------------------
 static int ffn_activation(const std::string &activation) {

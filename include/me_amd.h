@@ -138,7 +138,11 @@ typedef struct me_region {
  *              positions with reset flags at the instance starts, a chunk-local pass, a carry over the chunks and the pass
  *              that writes the rows; backward on two checkpoint levels (chunk entry states in memory, sub-chunk entry
  *              states in LDS, one sub-chunk's states in registers), fixed-order merges (me_sscan_supported, me_sscan_chunk,
- *              me_sscan_workspace_bytes, me_sscan_forward, me_sscan_backward) */
+ *              me_sscan_workspace_bytes, me_sscan_forward, me_sscan_backward)
+ *   1.28 (380)  round 28: the causal depthwise conv1d (+ SiLU) along the same sequence, the local mixing of a Mamba block:
+ *              a workgroup of channel lanes x position teams slides a register window of K rows over its piece of a chunk,
+ *              the backward pass recomputes the pre-activation and sums the parameter gradients in a fixed order
+ *              (me_cconv_supported, me_cconv_chunk, me_cconv_workspace_bytes, me_cconv_forward, me_cconv_backward) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1583,6 +1587,35 @@ int me_sscan_backward(const void *u_dev, const void *delta_dev, const void *z_de
                       const float *entry_dev, void *du_dev, void *ddelta_dev, void *dz_dev, void *db_dev, void *dc_dev,
                       float *da_dev, float *ddskip_dev, float *ddelta_bias_dev, void *workspace_dev,
                       int64_t workspace_bytes, void *stream);
+
+/* ---- causal depthwise conv1d along the serialized voxel order (MinkowskiFunctional.causal_conv1d, MinkowskiMamba;
+ *      csrc/causal_conv1d.hip, ABI 1.28) ----
+ * The sequence is the selective scan's (seg_rows, batch_row, reverse: see above).  Per channel c < d, with k taps:
+ *   pre[row_p, c] = bias[c] + sum_{j < k} weight[c, k - 1 - j] x[row_{p - j}, c]
+ * where tap j is dropped when fewer than j positions of the instance of position p precede it, and y = pre, or
+ * pre * sigmoid(pre) with silu != 0.  x, y, dy, dx: [n, d] rows of float or (is_bf16) __bf16 with a row stride in elements;
+ * weight [d, k] and bias [d] (may be NULL): contiguous floats.  All arithmetic is fp32; rows are rounded once at the store.
+ * The kernels serve d >= 1 and k = 2, 3 or 4 (me_cconv_supported); they move 16 bytes a lane when d, the row pointers and
+ * the row strides are multiples of 16 bytes, one element otherwise.  The sequence is cut into chunks of me_cconv_chunk
+ * positions (256); a workgroup walks a run of ceil(chunks / ME_CCONV_MAX_RUNS) consecutive chunks.
+ * Backward recomputes pre from x and writes dx [n, d] (row stride dx_stride), dweight [d, k] and dbias [d] (floats); each
+ * may be NULL: not written.  The parameter gradients are sums in a fixed order, without atomics.  workspace: at least
+ * me_cconv_workspace_bytes(n, d, k, 1) bytes, 4-byte aligned (forward needs none: 0 bytes).
+ * Host-side errors, nothing launched: unsupported d / k, n < 0 or n >= 2^31, a row stride below d, dbias without bias; then,
+ * with n > 0, a missing data pointer or a workspace that is too small.  n = 0 launches nothing in forward and writes zero
+ * parameter gradients in backward. */
+#define ME_CCONV_MAX_RUNS 512
+int32_t me_cconv_supported(int32_t d, int32_t k, int32_t is_bf16);
+int32_t me_cconv_chunk(void);
+int64_t me_cconv_workspace_bytes(int64_t n, int32_t d, int32_t k, int32_t backward);
+int me_cconv_forward(const void *x_dev, int32_t is_bf16, int64_t x_stride, const float *weight_dev, const float *bias_dev,
+                     int32_t silu, const int32_t *seg_rows_dev, const int32_t *batch_row_dev, int32_t reverse, int64_t n,
+                     int32_t d, int32_t k, void *y_dev, int64_t y_stride, void *stream);
+int me_cconv_backward(const void *x_dev, const void *dy_dev, int32_t is_bf16, int64_t x_stride, int64_t dy_stride,
+                      const float *weight_dev, const float *bias_dev, int32_t silu, const int32_t *seg_rows_dev,
+                      const int32_t *batch_row_dev, int32_t reverse, int64_t n, int32_t d, int32_t k, void *dx_dev,
+                      int64_t dx_stride, float *dweight_dev, float *dbias_dev, void *workspace_dev, int64_t workspace_bytes,
+                      void *stream);
 
 /* ---- fused two-layer MLP (MinkowskiFeedForward, MinkowskiFunctional.feed_forward; csrc/feed_forward.hip, ABI 1.24) ----
  *   y = act(x w1^T + b1) w2^T + b2

@@ -237,6 +237,18 @@ def selective_scan(u, delta, A, B, C, Dskip=None, z=None, delta_bias=None, delta
     return SparseTensor(out, coordinate_map_key=u.coordinate_map_key, coordinate_manager=u._manager)
 
 
+def causal_conv1d(input, weight, bias=None, activation=None, order="z", reverse=False):
+    """The causal depthwise conv1d along the curve `order` of every instance of a SparseTensor (MinkowskiMamba's local
+    mixing as a function): weight (D, K) or (D, 1, K), bias (D,) or None, activation None or "silu".  Tap j reads the voxel
+    j positions back in the instance's sequence and nothing before its start.  The result sits on the input's map."""
+    from .causal_conv1d import causal_conv1d as _conv
+    from .sparse_tensor import SparseTensor
+    if not isinstance(input, SparseTensor):
+        raise TypeError(f"causal_conv1d takes a SparseTensor, not a {type(input).__name__}")
+    out = _conv(input.F, weight, bias, activation, order, reverse, input.coordinate_map_key, input._manager)
+    return SparseTensor(out, coordinate_map_key=input.coordinate_map_key, coordinate_manager=input._manager)
+
+
 def feed_forward(input, w1, b1, w2, b2, activation="gelu"):
     """act(F w1^T + b1) w2^T + b2 over the features F of a SparseTensor or a TensorField (MinkowskiFeedForward as a
     function).  w1 [hidden, C], w2 [C_out, hidden], b1 / b2 vectors or None; activation: gelu, gelu_tanh, relu or silu."""
@@ -256,4 +268,4 @@ __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group
                                                 "local_attention", "serialized_attention", "cross_attention",
                                                 "window_attention", "rotary_embedding", "layer_norm", "rms_norm",
                                                 "ada_layer_norm", "feed_forward", "gated_feed_forward",
-                                                "selective_scan"]
+                                                "selective_scan", "causal_conv1d"]

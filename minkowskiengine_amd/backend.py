@@ -4314,6 +4314,70 @@ def SelectiveScanBackwardGPU(u, delta, A, B, C, Dskip, z, delta_bias, entry, gra
 
 
 # ------------------------------------------------------------------------------------------------
+# causal depthwise conv1d (+ SiLU) along the same sequence (csrc/causal_conv1d.hip, ABI 1.28; not in the reference)
+# ------------------------------------------------------------------------------------------------
+CCONV_ACTIVATIONS = {None: 0, "silu": 1}
+CCONV_MAX_RUNS = 512                # ME_CCONV_MAX_RUNS: a workgroup walks ceil(chunks / CCONV_MAX_RUNS) chunks
+
+
+def _cconv_prepare(x, weight, bias, activation, order, in_key, manager):
+    """-> (x, k, silu, seg_rows, batch_row) after the checks both directions share"""
+    x = _attn_rows("x", x)
+    _check(x.dtype in (torch.float32, torch.bfloat16), "the causal conv1d kernels take float32 or bfloat16 rows, got", x.dtype)
+    _check(activation in CCONV_ACTIVATIONS, "activation must be None or 'silu', not", repr(activation))
+    _check(manager.exists(in_key), "coordinate map not found")
+    n, d = manager.size(in_key), int(x.shape[1])
+    _check(x.shape[0] == n, "Invalid x size", x.shape[0], "!=", n)
+    _check(weight.is_cuda and weight.dim() == 2 and weight.dtype == torch.float32 and weight.is_contiguous() and
+           weight.shape[0] == d and weight.device == x.device, "weight must be a contiguous float32 GPU tensor [D, K]")
+    k = int(weight.shape[1])
+    _check(bool(_lib.load().me_cconv_supported(d, k, 1 if x.dtype == torch.bfloat16 else 0)),
+           "the causal conv1d kernels serve 2, 3 or 4 taps, got", k)
+    _inorm_check_vec("bias", bias, x, d)
+    seg_rows = manager._patch_rows(in_key, 1, order)[1]
+    return x, k, CCONV_ACTIVATIONS[activation], seg_rows, manager._origin_rows(in_key)
+
+
+def CausalConv1dForwardGPU(x, weight, bias, activation, order, reverse, in_key, manager):
+    """-> y [N, D]: the causal depthwise conv1d of csrc/causal_conv1d.hip over the rows of `in_key` in the order `order`
+    of every instance (backwards with `reverse`); weight [D, K] and bias [D] | None float32, activation None | "silu"."""
+    x, k, silu, seg_rows, rows = _cconv_prepare(x, weight, bias, activation, order, in_key, manager)
+    n, d = int(x.shape[0]), int(x.shape[1])
+    dev = x.device
+    y = torch.empty((n, d), dtype=x.dtype, device=dev)
+    if n == 0:
+        return y
+    with _on(dev):
+        _timed("cconv_forward", dev, lambda: _lib.check(_lib.load().me_cconv_forward(
+            _ptr(x), 1 if x.dtype == torch.bfloat16 else 0, _attn_stride(x), _ptr(weight), _ptr(bias), silu, _ptr(seg_rows),
+            _ptr(rows), 1 if reverse else 0, n, d, k, _ptr(y), d, _stream(dev))))
+    return y
+
+
+def CausalConv1dBackwardGPU(x, weight, bias, grad_out, activation, order, reverse, in_key, manager,
+                            need_grad=(True, True, True)):
+    """-> (grad_x, grad_weight, grad_bias), None where need_grad (same order) is False or bias is None; grad_x in the dtype
+    of x, the parameters in fp32.  The pre-activation is recomputed from x; fixed-order sums, no atomics."""
+    x, k, silu, seg_rows, rows = _cconv_prepare(x, weight, bias, activation, order, in_key, manager)
+    lib = _lib.load()
+    n, d = int(x.shape[0]), int(x.shape[1])
+    dev = x.device
+    grad_out = _attn_rows("grad_out", grad_out.to(x.dtype), x)
+    _check(grad_out.shape[0] == n, "grad_out must have the shape of x")
+    need = (need_grad[0], need_grad[1], need_grad[2] and bias is not None)
+    gx = torch.empty((n, d), dtype=x.dtype, device=dev) if need[0] else None
+    gw = torch.empty((d, k), dtype=torch.float32, device=dev) if need[1] else None
+    gb = torch.empty((d,), dtype=torch.float32, device=dev) if need[2] else None
+    ws = _workspace(int(lib.me_cconv_workspace_bytes(n, d, k, 1)), dev)
+    with _on(dev):
+        _timed("cconv_backward", dev, lambda: _lib.check(lib.me_cconv_backward(
+            _ptr(x), _ptr(grad_out), 1 if x.dtype == torch.bfloat16 else 0, _attn_stride(x), _attn_stride(grad_out),
+            _ptr(weight), _ptr(bias), silu, _ptr(seg_rows), _ptr(rows), 1 if reverse else 0, n, d, k, _ptr(gx), d, _ptr(gw),
+            _ptr(gb), _ptr(ws), ws.numel(), _stream(dev))))
+    return gx, gw, gb
+
+
+# ------------------------------------------------------------------------------------------------
 # fused two-layer MLP (csrc/feed_forward.hip, ABI 1.24; not in the reference): y = act(x w1^T + b1) w2^T + b2 without the
 # hidden matrix in memory.  Row-local, so the operators take no coordinate map.
 # ------------------------------------------------------------------------------------------------

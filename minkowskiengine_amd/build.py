@@ -22,7 +22,8 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=h
 # alike, element by element, and new kernels of this library keep to the scalar fp32 forms
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"layer_norm.hip": _NO_PACKED_FP32, "ada_layer_norm.hip": _NO_PACKED_FP32, "feed_forward.hip": _NO_PACKED_FP32,
-              "gated_feed_forward.hip": _NO_PACKED_FP32, "selective_scan.hip": _NO_PACKED_FP32}
+              "gated_feed_forward.hip": _NO_PACKED_FP32, "selective_scan.hip": _NO_PACKED_FP32,
+              "causal_conv1d.hip": _NO_PACKED_FP32}
 
 
 def sources():

@@ -936,6 +936,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("delta_bias"), py::arg("entry"), py::arg("grad_out"), py::arg("delta_softplus"), py::arg("order"),
         py::arg("reverse"), py::arg("in_key"), py::arg("manager"),
         py::arg("need_grad") = std::array<bool, 8>{true, true, true, true, true, true, true, true});
+  // causal depthwise conv1d along the serialized voxel order: csrc/causal_conv1d.hip
+  m.def("CausalConv1dForwardGPU",
+        [](const Tensor &x, const Tensor &weight, const py::object &bias, const py::object &activation,
+           const std::string &order, bool reverse, CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+          const Tensor b = opt_tensor(bias);
+          const std::string act = activation.is_none() ? std::string() : activation.cast<std::string>();
+          py::gil_scoped_release nogil;
+          return causal_conv1d_forward(x, weight, b, act, order, reverse, in_key, mgr);
+        },
+        py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("activation"), py::arg("order"), py::arg("reverse"),
+        py::arg("in_key"), py::arg("manager"));
+  m.def("CausalConv1dBackwardGPU",
+        [](const Tensor &x, const Tensor &weight, const py::object &bias, const Tensor &grad_out,
+           const py::object &activation, const std::string &order, bool reverse, CoordinateMapKey *in_key,
+           CoordinateMapManager *mgr, const std::array<bool, 3> &need_grad) {
+          const Tensor b = opt_tensor(bias);
+          const std::string act = activation.is_none() ? std::string() : activation.cast<std::string>();
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = causal_conv1d_backward(x, weight, b, grad_out, act, order, reverse, in_key, mgr, need_grad);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]));
+        },
+        py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("grad_out"), py::arg("activation"), py::arg("order"),
+        py::arg("reverse"), py::arg("in_key"), py::arg("manager"),
+        py::arg("need_grad") = std::array<bool, 3>{true, true, true});
   // fused two-layer MLP: csrc/feed_forward.hip
   m.def("FeedForwardForwardGPU",
         [](const Tensor &in_feat, const Tensor &w1, const py::object &b1, const Tensor &w2, const py::object &b2,

@@ -481,6 +481,15 @@ std::vector<Tensor> selective_scan_backward(Tensor u, Tensor delta, const Tensor
                                             bool delta_softplus, const std::string &order, bool reverse,
                                             CoordinateMapKey *in_key, CoordinateMapManager *mgr,
                                             const std::array<bool, 8> &need);
+// causal depthwise conv1d (+ SiLU) along the same sequence (csrc/causal_conv1d.hip; twin of
+// backend.CausalConv1d{Forward,Backward}GPU); activation "" or "silu"; backward -> (grad_x, grad_weight, grad_bias),
+// undefined where not wanted
+Tensor causal_conv1d_forward(Tensor x, const Tensor &weight, const Tensor &bias, const std::string &activation,
+                             const std::string &order, bool reverse, CoordinateMapKey *in_key, CoordinateMapManager *mgr);
+std::vector<Tensor> causal_conv1d_backward(Tensor x, const Tensor &weight, const Tensor &bias, Tensor grad_out,
+                                           const std::string &activation, const std::string &order, bool reverse,
+                                           CoordinateMapKey *in_key, CoordinateMapManager *mgr,
+                                           const std::array<bool, 3> &need);
 // fused two-layer MLP (csrc/feed_forward.hip; twin of backend.FeedForward{Forward,Backward}GPU);
 // backward -> (grad_in, grad_w1, grad_b1, grad_w2, grad_b2), undefined where not wanted
 Tensor feed_forward_forward(const Tensor &in_feat, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2,

@@ -1973,6 +1973,70 @@ std::vector<Tensor> selective_scan_backward(Tensor u, Tensor delta, const Tensor
   return g;
 }
 
+// ---- causal depthwise conv1d (+ SiLU) along the same sequence (csrc/causal_conv1d.hip, ABI 1.28; twin of
+// backend.CausalConv1d{Forward,Backward}GPU) ---------------------------------------------------------------------------
+struct CconvPrep {
+  Tensor seg_rows, rows;
+  int64_t n;
+  int d, k, silu;
+};
+static CconvPrep cconv_prepare(Tensor &x, const Tensor &weight, const Tensor &bias, const std::string &activation,
+                               const std::string &order, CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+  x = attn_rows("x", x);
+  check(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16,
+        "the causal conv1d kernels take float32 or bfloat16 rows");
+  check(activation.empty() || activation == "silu", "activation must be None or 'silu', not '" + activation + "'");
+  const KeyT &ik = in_key->get();
+  check(mgr->exists(ik), "coordinate map not found");
+  const int64_t n = mgr->get(ik)->n, d = x.size(1);
+  check(x.size(0) == n, "Invalid x size");
+  check(weight.is_cuda() && weight.dim() == 2 && weight.scalar_type() == at::kFloat && weight.is_contiguous() &&
+            weight.size(0) == d && weight.device() == x.device(),
+        "weight must be a contiguous float32 GPU tensor [D, K]");
+  const int64_t k = weight.size(1);
+  check(me_cconv_supported((int32_t)d, (int32_t)k, x.scalar_type() == at::kBFloat16 ? 1 : 0) != 0,
+        "the causal conv1d kernels serve 2, 3 or 4 taps, got " + std::to_string(k));
+  inorm_check_vec("bias", bias, x, d);
+  const std::vector<Tensor> &l = mgr->patch_rows(ik, 1, serial_order_code(order));
+  return {l[1], mgr->origin_rows(ik), n, (int)d, (int)k, activation.empty() ? 0 : 1};
+}
+
+Tensor causal_conv1d_forward(Tensor x, const Tensor &weight, const Tensor &bias, const std::string &activation,
+                             const std::string &order, bool reverse, CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+  const CconvPrep p = cconv_prepare(x, weight, bias, activation, order, in_key, mgr);
+  const c10::Device dev = x.device();
+  Tensor y = at::empty({p.n, p.d}, x.options());
+  if (p.n == 0) return y;
+  c10::DeviceGuard guard(dev);
+  me_ok(me_cconv_forward(vptr(x), x.scalar_type() == at::kBFloat16 ? 1 : 0, attn_stride(x), ptr<float>(weight),
+                         ptr<float>(bias), p.silu, ptr<int32_t>(p.seg_rows), ptr<int32_t>(p.rows), reverse ? 1 : 0, p.n,
+                         p.d, p.k, vptr(y), p.d, stream_of(dev)));
+  return y;
+}
+
+// need and the result: grad_x, grad_weight, grad_bias
+std::vector<Tensor> causal_conv1d_backward(Tensor x, const Tensor &weight, const Tensor &bias, Tensor grad_out,
+                                           const std::string &activation, const std::string &order, bool reverse,
+                                           CoordinateMapKey *in_key, CoordinateMapManager *mgr,
+                                           const std::array<bool, 3> &need) {
+  const CconvPrep p = cconv_prepare(x, weight, bias, activation, order, in_key, mgr);
+  const c10::Device dev = x.device();
+  grad_out = attn_rows("grad_out", grad_out.to(x.scalar_type()), &x);
+  check(grad_out.size(0) == p.n, "grad_out must have the shape of x");
+  const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
+  std::vector<Tensor> g(3);
+  if (need[0]) g[0] = at::empty({p.n, p.d}, x.options());
+  if (need[1]) g[1] = at::empty({p.d, p.k}, fopt);
+  if (need[2] && bias.defined()) g[2] = at::empty({p.d}, fopt);
+  c10::DeviceGuard guard(dev);
+  Tensor ws = workspace(me_cconv_workspace_bytes(p.n, p.d, p.k, 1), dev);
+  me_ok(me_cconv_backward(vptr(x), vptr(grad_out), x.scalar_type() == at::kBFloat16 ? 1 : 0, attn_stride(x),
+                          attn_stride(grad_out), ptr<float>(weight), ptr<float>(bias), p.silu, ptr<int32_t>(p.seg_rows),
+                          ptr<int32_t>(p.rows), reverse ? 1 : 0, p.n, p.d, p.k, vptr(g[0]), p.d, ptr<float>(g[1]),
+                          ptr<float>(g[2]), vptr(ws), ws.numel(), stream_of(dev)));
+  return g;
+}
+
 // ---- fused two-layer MLP (csrc/feed_forward.hip, ABI 1.24; twin of backend.FeedForward{Forward,Backward}GPU): row-local,
 // no coordinate map -----------------------------------------------------------------------------------------------------
 static int ffn_activation(const std::string &activation) {

@@ -131,9 +131,9 @@ class MinkowskiMamba(torch.nn.Module):
     state dict in that layout loads strictly.  `bidirectional=True` adds a second scan that walks the same order backwards
     over the same projections; the two results are summed before out_proj.
 
-    The scan runs on the HIP kernels (d_state 8 or 16, float32 / bfloat16).  The causal depthwise conv1d along the
-    sequence is written with torch index operations here — d_conv masked gathers that stop at the instance starts; fusing
-    it into a kernel is not part of this layer yet."""
+    The scan runs on the HIP kernels (d_state 8 or 16, float32 / bfloat16), and so does the causal depthwise conv1d with
+    its SiLU along the same sequence (`causal_conv1d`, d_conv 2 to 4); one forward-direction conv feeds both scans of a
+    bidirectional block.  `fused = False` and float64 run the torch formulations of both."""
 
     def __init__(self, d_model, d_state=16, d_conv=4, expand=2, dt_rank="auto", order="z", bidirectional=False, bias=False,
                  conv_bias=True, dt_min=0.001, dt_max=0.1, dt_init_floor=1e-4):
@@ -167,22 +167,8 @@ class MinkowskiMamba(torch.nn.Module):
         return (f"{self.__class__.__name__}({self.d_model}, d_state={self.d_state}, d_conv={self.d_conv}, "
                 f"expand={self.expand}, dt_rank={self.dt_rank}, order={self.order!r}, bidirectional={self.bidirectional})")
 
-    def _causal_conv(self, x, key, manager):
-        """conv1d along the sequence of every instance: tap j reads the row j positions back, nothing before the start"""
-        seq_rows, starts = scan_sequence(key, manager, self.order)
-        pos = torch.arange(seq_rows.numel(), device=x.device)
-        rank = pos - torch.cummax(torch.where(starts, pos, torch.zeros_like(pos)), 0).values
-        xs = x[seq_rows]
-        w = self.conv1d.weight[:, 0, :].to(x.dtype)                        # tap j back is w[:, d_conv - 1 - j]
-        acc = xs * w[:, self.d_conv - 1]
-        for j in range(1, self.d_conv):
-            back = xs[(pos - j).clamp(min=0)]
-            acc = acc + torch.where((rank >= j)[:, None], back, torch.zeros_like(back)) * w[:, self.d_conv - 1 - j]
-        if self.conv1d.bias is not None:
-            acc = acc + self.conv1d.bias.to(x.dtype)
-        return torch.zeros_like(acc).index_copy(0, seq_rows, acc)
-
     def forward(self, input):
+        from .causal_conv1d import causal_conv1d
         if not isinstance(input, SparseTensor):
             raise TypeError(f"{self.__class__.__name__} takes a SparseTensor, not a {type(input).__name__} "
                             "(quantise a TensorField with .sparse() first)")
@@ -190,7 +176,7 @@ class MinkowskiMamba(torch.nn.Module):
         key, manager = input.coordinate_map_key, input._manager
         xz = self.in_proj(input.F)
         x, z = xz[:, :self.d_inner], xz[:, self.d_inner:]
-        x = torch.nn.functional.silu(self._causal_conv(x, key, manager))
+        x = causal_conv1d(x, self.conv1d.weight, self.conv1d.bias, "silu", self.order, False, key, manager, fused=self.fused)
         x_dbl = self.x_proj(x)
         dt = torch.nn.functional.linear(x_dbl[:, :self.dt_rank], self.dt_proj.weight)
         B = x_dbl[:, self.dt_rank:self.dt_rank + self.d_state]

@@ -142,7 +142,11 @@ typedef struct me_region {
  *   1.28 (380)  round 28: the causal depthwise conv1d (+ SiLU) along the same sequence, the local mixing of a Mamba block:
  *              a workgroup of channel lanes x position teams slides a register window of K rows over its piece of a chunk,
  *              the backward pass recomputes the pre-activation and sums the parameter gradients in a fixed order
- *              (me_cconv_supported, me_cconv_chunk, me_cconv_workspace_bytes, me_cconv_forward, me_cconv_backward) */
+ *              (me_cconv_supported, me_cconv_chunk, me_cconv_workspace_bytes, me_cconv_forward, me_cconv_backward)
+ *   1.29 (390)  round 29: the Mamba-2 state-space-dual scan over the same sequence: one decay a head, so a chunk of 64
+ *              positions is three MFMA products and the chunks are joined by a scalar-times-state carry; 64 or 128 states a
+ *              head, grouped B / C, backward recomputed from the chunk entry states, fixed-order merges (me_ssd_supported,
+ *              me_ssd_chunk, me_ssd_workspace_bytes, me_ssd_forward, me_ssd_backward) */
 int me_version(void);
 const char *me_last_error(void);
 /* Load the device code of every translation unit of the library now (needs a GPU; ABI 1.5): HIP loads a unit's code object
@@ -1587,6 +1591,43 @@ int me_sscan_backward(const void *u_dev, const void *delta_dev, const void *z_de
                       const float *entry_dev, void *du_dev, void *ddelta_dev, void *dz_dev, void *db_dev, void *dc_dev,
                       float *da_dev, float *ddskip_dev, float *ddelta_bias_dev, void *workspace_dev,
                       int64_t workspace_bytes, void *stream);
+
+/* ---- Mamba-2 state-space-dual scan over the serialized voxel order (MinkowskiMamba2, MinkowskiFunctional.ssd_scan;
+ *      csrc/ssd_scan.hip, ABI 1.29) ----
+ * The sequence is the selective scan's (seg_rows, batch_row, reverse: see above).  h heads of width p, s states, g groups
+ * (g divides h; head i reads group i / (h / g)).  Per head, in fp32:
+ *   dt      = dt_in[row, i] + dt_bias[i]                          (dt_softplus: dt > 20 ? dt : log1p(exp(dt)))
+ *   state   = exp(dt A[i]) state + dt B[row, grp, :] (outer) x[row, i, :]          an s x p matrix, zero at an instance start
+ *   out[row, i, :] = C[row, grp, :] . state + D[i] x[row, i, :]
+ * x, out, dout: [n, h p] rows of float or (is_bf16) __bf16 with a row stride in elements; dt: [n, h] rows; B, C: [n, g s]
+ * rows; A [h], D [h], dt_bias [h]: contiguous floats; D and dt_bias may be NULL.  The kernels serve p = 32 or 64 and
+ * s = 64 or 128 (me_ssd_supported).  The sequence is cut into chunks of me_ssd_chunk consecutive positions (64).  Forward
+ * writes out and entry (float [chunks, h, s, p]: the state before every chunk), which backward takes next to the forward's
+ * operands.  Products run on v_mfma_f32_32x32x2_f32 (float rows, exact products) or v_mfma_f32_32x32x16_bf16 (bf16 rows: the
+ * operands, the decay-weighted ones included, are rounded to bf16); accumulators, running sums, exponentials and states are
+ * fp32 (the running sum of dt A inside a chunk fp64).  Backward writes dx [n, h p], ddt [n, h], dB, dC [n, g s] (contiguous,
+ * the rows' type) and dA, dD, ddt_bias [h] (floats); every output pointer may be NULL: not written (dB and dC: not
+ * computed).  All sums are formed in a fixed order without atomics.  workspace: at least
+ * me_ssd_workspace_bytes(n, h, p, s, g, backward) bytes, 4-byte aligned.
+ * Host-side errors, nothing launched: unsupported h / p / s / g, n < 0 or n >= 2^31, a row stride below the row width, a
+ * gradient of D / dt_bias without the operand; then, with n > 0, a missing data pointer or a workspace that is too small.
+ * n = 0 launches nothing in forward and writes zero parameter gradients in backward. */
+int32_t me_ssd_supported(int32_t h, int32_t p, int32_t s, int32_t g, int32_t is_bf16);
+int32_t me_ssd_chunk(void);
+int64_t me_ssd_workspace_bytes(int64_t n, int32_t h, int32_t p, int32_t s, int32_t g, int32_t backward);
+int me_ssd_forward(const void *x_dev, const void *dt_dev, const void *b_dev, const void *c_dev, int32_t is_bf16,
+                   int64_t x_stride, int64_t dt_stride, int64_t b_stride, int64_t c_stride, const float *a_dev,
+                   const float *d_dev, const float *dt_bias_dev, int32_t dt_softplus, const int32_t *seg_rows_dev,
+                   const int32_t *batch_row_dev, int32_t reverse, int64_t n, int32_t h, int32_t p, int32_t s, int32_t g,
+                   void *out_dev, int64_t out_stride, float *entry_dev, void *workspace_dev, int64_t workspace_bytes,
+                   void *stream);
+int me_ssd_backward(const void *x_dev, const void *dt_dev, const void *b_dev, const void *c_dev, const void *dout_dev,
+                    int32_t is_bf16, int64_t x_stride, int64_t dt_stride, int64_t b_stride, int64_t c_stride,
+                    int64_t dout_stride, const float *a_dev, const float *d_dev, const float *dt_bias_dev,
+                    int32_t dt_softplus, const int32_t *seg_rows_dev, const int32_t *batch_row_dev, int32_t reverse,
+                    int64_t n, int32_t h, int32_t p, int32_t s, int32_t g, const float *entry_dev, void *dx_dev,
+                    void *ddt_dev, void *db_dev, void *dc_dev, float *da_dev, float *dd_dev, float *ddt_bias_dev,
+                    void *workspace_dev, int64_t workspace_bytes, void *stream);
 
 /* ---- causal depthwise conv1d along the serialized voxel order (MinkowskiFunctional.causal_conv1d, MinkowskiMamba;
  *      csrc/causal_conv1d.hip, ABI 1.28) ----

@@ -237,6 +237,23 @@ def selective_scan(u, delta, A, B, C, Dskip=None, z=None, delta_bias=None, delta
     return SparseTensor(out, coordinate_map_key=u.coordinate_map_key, coordinate_manager=u._manager)
 
 
+def ssd_scan(x, dt, A, B, C, D=None, dt_bias=None, dt_softplus=False, headdim=64, ngroups=1, order="z", reverse=False):
+    """Mamba-2's state-space-dual scan (MinkowskiMamba2 without its projections) along the curve `order` of every instance.
+    x: a SparseTensor of H * headdim channels; dt (N, H), B, C (N, ngroups * S): matrices or SparseTensors on x's map;
+    A, D, dt_bias: (H,) float32 tensors.  The result sits on x's map."""
+    from .ssd_scan import ssd_scan as _scan
+    from .sparse_tensor import SparseTensor
+    if not isinstance(x, SparseTensor):
+        raise TypeError(f"ssd_scan takes a SparseTensor x, not a {type(x).__name__}")
+    for name, t in (("dt", dt), ("B", B), ("C", C)):
+        if isinstance(t, SparseTensor) and (t.coordinate_map_key != x.coordinate_map_key or t._manager is not x._manager):
+            raise ValueError(f"x, dt, B and C must share one coordinate map; {name} sits on another")
+    feats = [t.F if isinstance(t, SparseTensor) else t for t in (dt, B, C)]
+    out = _scan(x.F, feats[0], A, feats[1], feats[2], D, dt_bias, dt_softplus, headdim, ngroups, order, reverse,
+                x.coordinate_map_key, x._manager)
+    return SparseTensor(out, coordinate_map_key=x.coordinate_map_key, coordinate_manager=x._manager)
+
+
 def causal_conv1d(input, weight, bias=None, activation=None, order="z", reverse=False):
     """The causal depthwise conv1d along the curve `order` of every instance of a SparseTensor (MinkowskiMamba's local
     mixing as a function): weight (D, K) or (D, 1, K), bias (D,) or None, activation None or "silu".  Tap j reads the voxel
@@ -268,4 +285,4 @@ __all__ = list(_FEATURE_FUNCTIONS + _LOSSES) + ["group_norm", "conditional_group
                                                 "local_attention", "serialized_attention", "cross_attention",
                                                 "window_attention", "rotary_embedding", "layer_norm", "rms_norm",
                                                 "ada_layer_norm", "feed_forward", "gated_feed_forward",
-                                                "selective_scan", "causal_conv1d"]
+                                                "selective_scan", "causal_conv1d", "ssd_scan"]

@@ -30,6 +30,7 @@ from .attention import (  # noqa: F401
 from .serialized_attention import (  # noqa: F401
     MinkowskiSerializedAttentionFunction, MinkowskiSerializedSelfAttention)
 from .selective_scan import MinkowskiMamba, MinkowskiSelectiveScanFunction, selective_scan  # noqa: F401
+from .ssd_scan import MinkowskiMamba2, MinkowskiSSDScanFunction, ssd_scan, ssd_scan_reference  # noqa: F401
 from .causal_conv1d import MinkowskiCausalConv1dFunction, causal_conv1d, causal_conv1d_reference  # noqa: F401
 from .window_attention import MinkowskiWindowAttentionFunction, MinkowskiWindowSelfAttention  # noqa: F401
 from .feed_forward import MinkowskiFeedForward, MinkowskiFeedForwardFunction  # noqa: F401

@@ -245,6 +245,15 @@ SIGNATURES = {
     "me_sscan_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64,
                                          c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp,
                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "me_ssd_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "me_ssd_chunk": (c_i32, []),
+    "me_ssd_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "me_ssd_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32,
+                                      c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64,
+                                      c_vp]),
+    "me_ssd_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                       c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "me_cconv_supported": (c_i32, [c_i32, c_i32, c_i32]),
     "me_cconv_chunk": (c_i32, []),
     "me_cconv_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),

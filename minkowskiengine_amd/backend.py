@@ -4314,6 +4314,86 @@ def SelectiveScanBackwardGPU(u, delta, A, B, C, Dskip, z, delta_bias, entry, gra
 
 
 # ------------------------------------------------------------------------------------------------
+# Mamba-2 state-space-dual scan over the same sequence (csrc/ssd_scan.hip, ABI 1.29; not in the reference)
+# ------------------------------------------------------------------------------------------------
+def _ssd_prepare(x, dt, A, B, C, D, dt_bias, headdim, ngroups, order, in_key, manager):
+    """-> (x, dt, B, C, seg_rows, batch_row, h, p, s, g) after the checks both directions share"""
+    x = _attn_rows("x", x)
+    _check(x.dtype in (torch.float32, torch.bfloat16), "the SSD scan kernels take float32 or bfloat16 rows, got", x.dtype)
+    dt, B, C = _attn_rows("dt", dt), _attn_rows("B", B), _attn_rows("C", C)
+    _check(manager.exists(in_key), "coordinate map not found")
+    n, p, g = manager.size(in_key), int(headdim), int(ngroups)
+    _check(p >= 1 and g >= 1 and x.shape[1] % p == 0, "x must hold whole heads of width", p)
+    h = int(x.shape[1]) // p
+    _check(B.shape[1] % g == 0, "B must hold", g, "groups")
+    s = int(B.shape[1]) // g
+    for name, t, width in (("dt", dt, h), ("B", B, g * s), ("C", C, g * s)):
+        _check(t.dtype == x.dtype and t.device == x.device and tuple(t.shape) == (n, width), name,
+               "must have the dtype and device of x and the shape", (n, width))
+    _check(x.shape[0] == n, "Invalid x size", x.shape[0], "!=", n)
+    _check(bool(_lib.load().me_ssd_supported(h, p, s, g, 1 if x.dtype == torch.bfloat16 else 0)),
+           "the SSD scan kernels serve heads of width 32 or 64, 64 or 128 states and groups dividing the heads, got",
+           (h, p, s, g))
+    _inorm_check_vec("A", A, x, h)
+    _check(A is not None, "A must be given")
+    _inorm_check_vec("D", D, x, h)
+    _inorm_check_vec("dt_bias", dt_bias, x, h)
+    seg_rows = manager._patch_rows(in_key, 1, order)[1]
+    return x, dt, B, C, seg_rows, manager._origin_rows(in_key), h, p, s, g
+
+
+def SSDScanForwardGPU(x, dt, A, B, C, D, dt_bias, dt_softplus, headdim, ngroups, order, reverse, in_key, manager):
+    """-> (out [N, H P], entry [chunks, H, S, P] fp32): the state-space-dual scan of csrc/ssd_scan.hip over the rows of
+    `in_key` in the order `order` of every instance (backwards with `reverse`); entry, the state before every chunk of
+    me_ssd_chunk() positions, is what SSDScanBackwardGPU takes next to the operands.  Three launches."""
+    x, dt, B, C, seg_rows, rows, h, p, s, g = _ssd_prepare(x, dt, A, B, C, D, dt_bias, headdim, ngroups, order, in_key,
+                                                           manager)
+    lib = _lib.load()
+    n, dev = int(x.shape[0]), x.device
+    out = torch.empty((n, h * p), dtype=x.dtype, device=dev)
+    entry = torch.empty((-(-n // int(lib.me_ssd_chunk())), h, s, p), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out, entry
+    ws = _workspace(int(lib.me_ssd_workspace_bytes(n, h, p, s, g, 0)), dev)
+    with _on(dev):
+        _timed("ssd_forward", dev, lambda: _lib.check(lib.me_ssd_forward(
+            _ptr(x), _ptr(dt), _ptr(B), _ptr(C), 1 if x.dtype == torch.bfloat16 else 0, _attn_stride(x), _attn_stride(dt),
+            _attn_stride(B), _attn_stride(C), _ptr(A), _ptr(D), _ptr(dt_bias), 1 if dt_softplus else 0, _ptr(seg_rows),
+            _ptr(rows), 1 if reverse else 0, n, h, p, s, g, _ptr(out), h * p, _ptr(entry), _ptr(ws), ws.numel(),
+            _stream(dev))))
+    return out, entry
+
+
+def SSDScanBackwardGPU(x, dt, A, B, C, D, dt_bias, entry, grad_out, dt_softplus, headdim, ngroups, order, reverse, in_key,
+                       manager, need_grad=(True,) * 7):
+    """-> (grad_x, grad_dt, grad_A, grad_B, grad_C, grad_D, grad_dt_bias), None where need_grad (same order) is False or
+    the operand is None; rows in the dtype of x, parameters in fp32.  Fixed-order sums, no atomics."""
+    x, dt, B, C, seg_rows, rows, h, p, s, g = _ssd_prepare(x, dt, A, B, C, D, dt_bias, headdim, ngroups, order, in_key,
+                                                           manager)
+    lib = _lib.load()
+    n, dev = int(x.shape[0]), x.device
+    grad_out = _attn_rows("grad_out", grad_out.to(x.dtype), x)
+    _check(grad_out.shape[0] == n, "grad_out must have the shape of x")
+    _check(entry.is_cuda and entry.is_contiguous() and entry.dtype == torch.float32 and
+           tuple(entry.shape) == (-(-n // int(lib.me_ssd_chunk())), h, s, p),
+           "entry must be the forward pass's [chunks, H, S, P]")
+    need = list(need_grad)
+    need[5], need[6] = need[5] and D is not None, need[6] and dt_bias is not None
+    shapes = ((n, h * p), (n, h), (h,), (n, g * s), (n, g * s), (h,), (h,))
+    dtypes = (x.dtype, x.dtype, torch.float32, x.dtype, x.dtype, torch.float32, torch.float32)
+    gr = [torch.empty(sh, dtype=ty, device=dev) if nd else None for sh, ty, nd in zip(shapes, dtypes, need)]
+    ws = _workspace(int(lib.me_ssd_workspace_bytes(n, h, p, s, g, 1)), dev)
+    with _on(dev):
+        _timed("ssd_backward", dev, lambda: _lib.check(lib.me_ssd_backward(
+            _ptr(x), _ptr(dt), _ptr(B), _ptr(C), _ptr(grad_out), 1 if x.dtype == torch.bfloat16 else 0, _attn_stride(x),
+            _attn_stride(dt), _attn_stride(B), _attn_stride(C), _attn_stride(grad_out), _ptr(A), _ptr(D), _ptr(dt_bias),
+            1 if dt_softplus else 0, _ptr(seg_rows), _ptr(rows), 1 if reverse else 0, n, h, p, s, g, _ptr(entry),
+            _ptr(gr[0]), _ptr(gr[1]), _ptr(gr[3]), _ptr(gr[4]), _ptr(gr[2]), _ptr(gr[5]), _ptr(gr[6]), _ptr(ws),
+            0 if ws is None else ws.numel(), _stream(dev))))
+    return tuple(gr)
+
+
+# ------------------------------------------------------------------------------------------------
 # causal depthwise conv1d (+ SiLU) along the same sequence (csrc/causal_conv1d.hip, ABI 1.28; not in the reference)
 # ------------------------------------------------------------------------------------------------
 CCONV_ACTIVATIONS = {None: 0, "silu": 1}

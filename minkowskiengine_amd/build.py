@@ -23,7 +23,7 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=h
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"layer_norm.hip": _NO_PACKED_FP32, "ada_layer_norm.hip": _NO_PACKED_FP32, "feed_forward.hip": _NO_PACKED_FP32,
               "gated_feed_forward.hip": _NO_PACKED_FP32, "selective_scan.hip": _NO_PACKED_FP32,
-              "causal_conv1d.hip": _NO_PACKED_FP32}
+              "causal_conv1d.hip": _NO_PACKED_FP32, "ssd_scan.hip": _NO_PACKED_FP32}
 
 
 def sources():

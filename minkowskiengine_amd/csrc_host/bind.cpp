@@ -936,6 +936,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("delta_bias"), py::arg("entry"), py::arg("grad_out"), py::arg("delta_softplus"), py::arg("order"),
         py::arg("reverse"), py::arg("in_key"), py::arg("manager"),
         py::arg("need_grad") = std::array<bool, 8>{true, true, true, true, true, true, true, true});
+  // Mamba-2 state-space-dual scan over the serialized voxel order: csrc/ssd_scan.hip
+  m.def("SSDScanForwardGPU",
+        [](const Tensor &x, const Tensor &dt, const Tensor &A, const Tensor &B, const Tensor &C, const py::object &D,
+           const py::object &dt_bias, bool dt_softplus, int64_t headdim, int64_t ngroups, const std::string &order,
+           bool reverse, CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+          const Tensor dk = opt_tensor(D), db = opt_tensor(dt_bias);
+          std::pair<Tensor, Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = ssd_scan_forward(x, dt, A, B, C, dk, db, dt_softplus, headdim, ngroups, order, reverse, in_key, mgr);
+          }
+          return py::make_tuple(r.first, r.second);
+        },
+        py::arg("x"), py::arg("dt"), py::arg("A"), py::arg("B"), py::arg("C"), py::arg("D"), py::arg("dt_bias"),
+        py::arg("dt_softplus"), py::arg("headdim"), py::arg("ngroups"), py::arg("order"), py::arg("reverse"),
+        py::arg("in_key"), py::arg("manager"));
+  m.def("SSDScanBackwardGPU",
+        [](const Tensor &x, const Tensor &dt, const Tensor &A, const Tensor &B, const Tensor &C, const py::object &D,
+           const py::object &dt_bias, const Tensor &entry, const Tensor &grad_out, bool dt_softplus, int64_t headdim,
+           int64_t ngroups, const std::string &order, bool reverse, CoordinateMapKey *in_key, CoordinateMapManager *mgr,
+           const std::array<bool, 7> &need_grad) {
+          const Tensor dk = opt_tensor(D), db = opt_tensor(dt_bias);
+          std::vector<Tensor> r;
+          {
+            py::gil_scoped_release nogil;
+            r = ssd_scan_backward(x, dt, A, B, C, dk, db, entry, grad_out, dt_softplus, headdim, ngroups, order, reverse,
+                                  in_key, mgr, need_grad);
+          }
+          return py::make_tuple(opt_out(r[0]), opt_out(r[1]), opt_out(r[2]), opt_out(r[3]), opt_out(r[4]), opt_out(r[5]),
+                                opt_out(r[6]));
+        },
+        py::arg("x"), py::arg("dt"), py::arg("A"), py::arg("B"), py::arg("C"), py::arg("D"), py::arg("dt_bias"),
+        py::arg("entry"), py::arg("grad_out"), py::arg("dt_softplus"), py::arg("headdim"), py::arg("ngroups"),
+        py::arg("order"), py::arg("reverse"), py::arg("in_key"), py::arg("manager"),
+        py::arg("need_grad") = std::array<bool, 7>{true, true, true, true, true, true, true});
   // causal depthwise conv1d along the serialized voxel order: csrc/causal_conv1d.hip
   m.def("CausalConv1dForwardGPU",
         [](const Tensor &x, const Tensor &weight, const py::object &bias, const py::object &activation,

@@ -481,6 +481,17 @@ std::vector<Tensor> selective_scan_backward(Tensor u, Tensor delta, const Tensor
                                             bool delta_softplus, const std::string &order, bool reverse,
                                             CoordinateMapKey *in_key, CoordinateMapManager *mgr,
                                             const std::array<bool, 8> &need);
+// Mamba-2 state-space-dual scan over the same sequence (csrc/ssd_scan.hip; twin of backend.SSDScan{Forward,Backward}GPU);
+// -> (out, entry) and (grad_x, grad_dt, grad_A, grad_B, grad_C, grad_D, grad_dt_bias), undefined where not wanted
+std::pair<Tensor, Tensor> ssd_scan_forward(Tensor x, Tensor dt, const Tensor &A, Tensor B, Tensor C, const Tensor &D,
+                                           const Tensor &dt_bias, bool dt_softplus, int64_t headdim, int64_t ngroups,
+                                           const std::string &order, bool reverse, CoordinateMapKey *in_key,
+                                           CoordinateMapManager *mgr);
+std::vector<Tensor> ssd_scan_backward(Tensor x, Tensor dt, const Tensor &A, Tensor B, Tensor C, const Tensor &D,
+                                      const Tensor &dt_bias, const Tensor &entry, Tensor grad_out, bool dt_softplus,
+                                      int64_t headdim, int64_t ngroups, const std::string &order, bool reverse,
+                                      CoordinateMapKey *in_key, CoordinateMapManager *mgr,
+                                      const std::array<bool, 7> &need);
 // causal depthwise conv1d (+ SiLU) along the same sequence (csrc/causal_conv1d.hip; twin of
 // backend.CausalConv1d{Forward,Backward}GPU); activation "" or "silu"; backward -> (grad_x, grad_weight, grad_bias),
 // undefined where not wanted

@@ -1973,6 +1973,101 @@ std::vector<Tensor> selective_scan_backward(Tensor u, Tensor delta, const Tensor
   return g;
 }
 
+// ---- Mamba-2 state-space-dual scan over the same sequence (csrc/ssd_scan.hip, ABI 1.29; twin of
+// backend.SSDScan{Forward,Backward}GPU) ---------------------------------------------------------------------------------
+struct SsdPrep {
+  Tensor seg_rows, rows;
+  int64_t n;
+  int h, p, s, g;
+};
+static SsdPrep ssd_prepare(Tensor &x, Tensor &dt, const Tensor &A, Tensor &B, Tensor &C, const Tensor &D,
+                           const Tensor &dt_bias, int64_t headdim, int64_t ngroups, const std::string &order,
+                           CoordinateMapKey *in_key, CoordinateMapManager *mgr) {
+  x = attn_rows("x", x);
+  check(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16,
+        "the SSD scan kernels take float32 or bfloat16 rows");
+  dt = attn_rows("dt", dt);
+  B = attn_rows("B", B);
+  C = attn_rows("C", C);
+  const KeyT &ik = in_key->get();
+  check(mgr->exists(ik), "coordinate map not found");
+  const int64_t n = mgr->get(ik)->n, p = headdim, g = ngroups;
+  check(p >= 1 && g >= 1 && x.size(1) % p == 0, "x must hold whole heads of width " + std::to_string(p));
+  const int64_t h = x.size(1) / p;
+  check(B.size(1) % g == 0, "B must hold " + std::to_string(g) + " groups");
+  const int64_t s = B.size(1) / g;
+  const std::pair<const Tensor *, int64_t> ops[] = {{&dt, h}, {&B, g * s}, {&C, g * s}};
+  for (const auto &o : ops)
+    check(o.first->scalar_type() == x.scalar_type() && o.first->device() == x.device() && o.first->size(0) == n &&
+              o.first->size(1) == o.second,
+          "dt, B and C must have the dtype and device of x and the shapes [N, H], [N, G S], [N, G S]");
+  check(x.size(0) == n, "Invalid x size");
+  check(me_ssd_supported((int32_t)h, (int32_t)p, (int32_t)s, (int32_t)g, x.scalar_type() == at::kBFloat16 ? 1 : 0) != 0,
+        "the SSD scan kernels serve heads of width 32 or 64, 64 or 128 states and groups dividing the heads");
+  check(A.defined(), "A must be given");
+  inorm_check_vec("A", A, x, h);
+  inorm_check_vec("D", D, x, h);
+  inorm_check_vec("dt_bias", dt_bias, x, h);
+  const std::vector<Tensor> &l = mgr->patch_rows(ik, 1, serial_order_code(order));
+  return {l[1], mgr->origin_rows(ik), n, (int)h, (int)p, (int)s, (int)g};
+}
+
+std::pair<Tensor, Tensor> ssd_scan_forward(Tensor x, Tensor dt, const Tensor &A, Tensor B, Tensor C, const Tensor &D,
+                                           const Tensor &dt_bias, bool dt_softplus, int64_t headdim, int64_t ngroups,
+                                           const std::string &order, bool reverse, CoordinateMapKey *in_key,
+                                           CoordinateMapManager *mgr) {
+  const SsdPrep q = ssd_prepare(x, dt, A, B, C, D, dt_bias, headdim, ngroups, order, in_key, mgr);
+  const c10::Device dev = x.device();
+  Tensor out = at::empty({q.n, (int64_t)q.h * q.p}, x.options());
+  Tensor entry = at::empty({(q.n + me_ssd_chunk() - 1) / me_ssd_chunk(), q.h, q.s, q.p},
+                           at::TensorOptions().dtype(at::kFloat).device(dev));
+  if (q.n == 0) return {out, entry};
+  c10::DeviceGuard guard(dev);
+  Tensor ws = workspace(me_ssd_workspace_bytes(q.n, q.h, q.p, q.s, q.g, 0), dev);
+  me_ok(me_ssd_forward(vptr(x), vptr(dt), vptr(B), vptr(C), x.scalar_type() == at::kBFloat16 ? 1 : 0, attn_stride(x),
+                       attn_stride(dt), attn_stride(B), attn_stride(C), ptr<float>(A), ptr<float>(D), ptr<float>(dt_bias),
+                       dt_softplus ? 1 : 0, ptr<int32_t>(q.seg_rows), ptr<int32_t>(q.rows), reverse ? 1 : 0, q.n, q.h, q.p,
+                       q.s, q.g, vptr(out), (int64_t)q.h * q.p, ptr<float>(entry), vptr(ws), ws.numel(), stream_of(dev)));
+  return {out, entry};
+}
+
+// need and the result: grad_x, grad_dt, grad_A, grad_B, grad_C, grad_D, grad_dt_bias
+std::vector<Tensor> ssd_scan_backward(Tensor x, Tensor dt, const Tensor &A, Tensor B, Tensor C, const Tensor &D,
+                                      const Tensor &dt_bias, const Tensor &entry, Tensor grad_out, bool dt_softplus,
+                                      int64_t headdim, int64_t ngroups, const std::string &order, bool reverse,
+                                      CoordinateMapKey *in_key, CoordinateMapManager *mgr,
+                                      const std::array<bool, 7> &need_in) {
+  const SsdPrep q = ssd_prepare(x, dt, A, B, C, D, dt_bias, headdim, ngroups, order, in_key, mgr);
+  const c10::Device dev = x.device();
+  grad_out = attn_rows("grad_out", grad_out.to(x.scalar_type()), &x);
+  check(grad_out.size(0) == q.n, "grad_out must have the shape of x");
+  check(entry.is_cuda() && entry.is_contiguous() && entry.scalar_type() == at::kFloat && entry.dim() == 4 &&
+            entry.size(0) == (q.n + me_ssd_chunk() - 1) / me_ssd_chunk() && entry.size(1) == q.h &&
+            entry.size(2) == q.s && entry.size(3) == q.p,
+        "entry must be the forward pass's [chunks, H, S, P]");
+  std::array<bool, 7> need = need_in;
+  need[5] = need[5] && D.defined();
+  need[6] = need[6] && dt_bias.defined();
+  const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
+  std::vector<Tensor> g(7);
+  if (need[0]) g[0] = at::empty({q.n, (int64_t)q.h * q.p}, x.options());
+  if (need[1]) g[1] = at::empty({q.n, q.h}, x.options());
+  if (need[2]) g[2] = at::empty({q.h}, fopt);
+  if (need[3]) g[3] = at::empty({q.n, (int64_t)q.g * q.s}, x.options());
+  if (need[4]) g[4] = at::empty({q.n, (int64_t)q.g * q.s}, x.options());
+  if (need[5]) g[5] = at::empty({q.h}, fopt);
+  if (need[6]) g[6] = at::empty({q.h}, fopt);
+  c10::DeviceGuard guard(dev);
+  Tensor ws = workspace(me_ssd_workspace_bytes(q.n, q.h, q.p, q.s, q.g, 1), dev);
+  me_ok(me_ssd_backward(vptr(x), vptr(dt), vptr(B), vptr(C), vptr(grad_out), x.scalar_type() == at::kBFloat16 ? 1 : 0,
+                        attn_stride(x), attn_stride(dt), attn_stride(B), attn_stride(C), attn_stride(grad_out),
+                        ptr<float>(A), ptr<float>(D), ptr<float>(dt_bias), dt_softplus ? 1 : 0, ptr<int32_t>(q.seg_rows),
+                        ptr<int32_t>(q.rows), reverse ? 1 : 0, q.n, q.h, q.p, q.s, q.g, ptr<float>(entry), vptr(g[0]),
+                        vptr(g[1]), vptr(g[3]), vptr(g[4]), ptr<float>(g[2]), ptr<float>(g[5]), ptr<float>(g[6]), vptr(ws),
+                        ws.defined() ? ws.numel() : 0, stream_of(dev)));
+  return g;
+}
+
 // ---- causal depthwise conv1d (+ SiLU) along the same sequence (csrc/causal_conv1d.hip, ABI 1.28; twin of
 // backend.CausalConv1d{Forward,Backward}GPU) ---------------------------------------------------------------------------
 struct CconvPrep {
